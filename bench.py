@@ -17,11 +17,22 @@ are resident in HBM before the timed region.  For N > 1 every rank keeps 4096 ra
 sharded, parameters replicated, the gradients go reduce-scatter -> Adam on the owned slice -> all-gather
 (--dp zero1, default) or all-reduce (--dp allreduce).
 
-Prints ONE JSON line (rank 0).  `value` = rays consumed by the whole job per second.  At N = 1 the same line
-also carries: the kernel roofline (HIP-event timings of every launch + committed rocprofv3 PMC summaries), the
-final-stage figure (grid [331,368,220], 270 samples/ray, where 78 % of the reference's iterations run), the
-render legs (whole frame and the reference's 512-ray eval chunks), and the CPU baseline (the oracle's
-re-enactment of the same step on the host cores)."""
+Prints ONE JSON line (rank 0).  `value` = rays consumed by the whole job per second.  A plain run sets up, warms up,
+times the K steps and prints the line.  With --full the same line also carries (at N = 1): the kernel roofline
+(HIP-event timings of every launch + committed rocprofv3 PMC summaries), the final-stage figure (grid [331,368,220],
+270 samples/ray, where 78 % of the reference's iterations run), the render legs (whole frame and the reference's
+512-ray eval chunks), and the CPU baseline (the oracle's re-enactment of the same step on the host cores).
+
+--dump-outputs DIR writes what the timed path computes (loss terms, both fields' flat parameter and gradient buffers,
+the pose table / field of view where they are optimised) as DIR/<name>.npy, from inputs fixed by the arguments alone, so
+that two builds run with the same arguments can be compared output for output.  The timed iterations themselves cannot
+serve: they continue one training run, and the product library's fp32 atomics vary the low bits of every gradient from
+run to run, which the training amplifies: two runs' dynamic-field parameters differ by up to ~1e-6 of their largest
+value after one iteration, ~4e-2 after five, ~0.3 after twenty.  So after the timed region (and after the --full legs) the
+timed step (Trainer.step + finish_step) runs once more, untimed, on a fresh trainer with the same seeds, at the index of
+the last timed iteration (its batch, loss weights and gates) from the seeded initial weights and optimiser state.
+Two runs of that step agree to rounding (RDRF_DETERMINISTIC=1, the fixed-point debugging build: bit for bit).
+"""
 import argparse
 import ctypes as C
 import importlib
@@ -197,6 +208,16 @@ def cpu_baseline(trainer, n_rays, repeats, dead_work=True):
                        f"1 warm-up, {med:.1f} s per step (the CPU throughput grows with the batch)")
 
 
+def replay_window(shard, make_trainer, warmup, steps):
+    """roofline()'s replay without its HIP events and probes: iterations 0 .. warmup + steps of a fresh trainer"""
+    import torch
+    trainer = make_trainer()
+    for _ in range(warmup + steps):
+        trainer.step(shard)
+        trainer.finish_step()
+    torch.cuda.synchronize()
+
+
 def quoted_baseline_config(world):
     """the BASELINE.json configs index quoted for this GPU count (configs[3]: 4 GPUs, configs[4]: 8 GPUs, else configs[1])"""
     return {4: "3", 8: "4"}.get(world, "1")
@@ -293,6 +314,47 @@ def timed_steps(trainer, shard, steps, warmup, world, dev, fractions=None):
     if fractions is not None:
         fractions["end"] = mask_fractions(fractions.pop("S_"), trainer)
     return dt / steps, loss
+
+
+DUMP_MAX_ELEMS = 1 << 21   # per array (8 MB of fp32): a larger buffer is written as a fixed, seeded sample of its entries
+
+
+def dump_step(make_trainer, shard, iteration):
+    """The timed step once more, untimed, from inputs the arguments alone fix (see the module docstring): a fresh trainer
+    (same seeds) set to `iteration` runs Trainer.step + finish_step.  Collective: every rank calls it.  Returns the trainer
+    and the loss step() returned."""
+    import torch
+    trainer = make_trainer()
+    trainer.it = iteration
+    loss = trainer.step(shard)
+    trainer.finish_step()
+    torch.cuda.synchronize()
+    return trainer, loss
+
+
+def dump_outputs(trainer, loss, out_dir):
+    """What the step of dump_step() handed its caller, as out_dir/<name>.npy (float32): the loss Trainer.step() returned
+    and its two groups, then the state finish_step() left -- each field's flat parameter buffer (after Adam) and flat
+    gradient buffer, the pose table and field of view where they are optimised.  A buffer of more than DUMP_MAX_ELEMS
+    entries is written as the entries at DUMP_MAX_ELEMS sorted indices drawn without replacement by a generator seeded
+    with 0 (the same indices for the same length), which keeps the whole dump under 64 MB."""
+    import numpy as np
+    import torch
+    arrays = {"loss": loss, "loss_dynamic": trainer.last.get("loss_dynamic"), "loss_static": trainer.last.get("loss_static")}
+    for name, st in zip(("static", "dynamic"), trainer.opt.state):
+        arrays[f"{name}_params"] = st["p"]
+        arrays[f"{name}_grads"] = st["g"]
+    if trainer.optimize_poses:
+        arrays["poses"], arrays["fov"] = trainer.poses, trainer.fov
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        a = t.detach().reshape(-1).float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 KERNELS = ["pack", "generate_rays", "generate_rays_bwd", "sample_ndc", "sample_contract", "sample_bwd", "static_density",
@@ -745,9 +807,17 @@ def main():
     ap.add_argument("--no-sparse", action="store_true", help="skip the W-sparse (app mask ~0.10) training / render leg")
     ap.add_argument("--no-cpu-4096", action="store_true", help="skip the single 4096-ray CPU step (about one minute)")
     ap.add_argument("--render-chunk", type=int, default=0, help="rays per render call (default: a whole frame)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the profiled replay with its per-kernel roofline, "
+                         "the liveness, render, final-stage, schedule, launch-bound-stage and W-sparse legs, the CPU baselines "
+                         "and the committed HBM rooflines (the --no-* options trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps run the timed step once more, untimed, from the seeded initial state at the last "
+                         "timed iteration's index, and write what it computed as DIR/<name>.npy (see dump_step / dump_outputs)")
     ap.add_argument("--full-line", action="store_true",
                     help="print the full record (bench_detail.json's content) as the last line instead of the compact one: for "
-                         "the tools/ab_*.sh scripts, which read per-kernel tables from the line -- never for the driver")
+                         "the tools/ab_*.sh scripts, which read per-kernel tables from the line -- never for the driver.  "
+                         "Implies --full")
     ap.add_argument("--no-liveness-leg", action="store_true",
                     help="skip the secondary liveness_exploited leg (profiling runs: every iteration of the process is then the "
                          "same workload)")
@@ -762,6 +832,8 @@ def main():
                          "passes E / P3 / P4 and the colours of both fields in passes B-D / P1-P4; by default it is executed like "
                          "the reference does")
     args = ap.parse_args()
+    if args.full_line:
+        args.full = True
     if args.graph:
         if args.gpus > 1:
             raise SystemExit("bench.py --graph is the single-process path")
@@ -803,11 +875,17 @@ def main():
     # exactly the iterations that are timed afterwards, and it is the process's clock warm-up: the first ~second of GPU
     # work of a fresh process runs the MFMA-bound kernels up to ~10 % slower than steady state (measured: a 20-step
     # window timed right at start-up showed ms_per_step - kernel sum = 2.2 ms, of which 1.3 ms was clock ramp -- the same
-    # kernels profiled 4 s later were that much faster), which a training run of 100 000 iterations never sees.
+    # kernels profiled 4 s later were that much faster), which a training run of 100 000 iterations never sees.  Without
+    # --full the replay runs the same iterations without the HIP events: the same clock warm-up, and the same device draws
+    # consumed before the timed region, so the timed iterations compute what they compute with --full.
     rf = None
-    if not args.no_roofline:   # collective: every rank runs the profiled steps (rank 0 reports)
-        rf = roofline(L, S_, trainer, cfg, shard, rpg, 1.0, window=(make_trainer, args.warmup, min(args.steps, 400)))
-    frs = {"S_": S_}
+    if not args.no_roofline:   # collective: every rank runs the replayed steps (rank 0 reports)
+        window = (make_trainer, args.warmup, min(args.steps, 400))
+        if args.full:
+            rf = roofline(L, S_, trainer, cfg, shard, rpg, 1.0, window=window)
+        else:
+            replay_window(shard, *window)
+    frs = {"S_": S_} if args.full else None
     dt, loss = timed_steps(trainer, shard, args.steps, args.warmup, world, dev, fractions=frs)
     ms = dt * 1e3
     value = cfg["batch_size"] / dt
@@ -839,6 +917,10 @@ def main():
                    "timed_region": ("preceded by a profiled REPLAY of the same window on a second trainer (iterations 0 .. warmup + steps, "
                                     "same seeds): it yields the per-kernel table of exactly the timed iterations and warms the clocks; "
                                     "then the driver's warmup + steps iterations run on the main trainer and `steps` of them are timed"
+                                    if rf is not None else
+                                    "preceded by an unprofiled REPLAY of the same window on a second trainer (iterations 0 .. warmup + "
+                                    "steps, same seeds): it warms the clocks; then the driver's warmup + steps iterations run on the "
+                                    "main trainer and `steps` of them are timed"
                                     if not args.no_roofline else "warmup + steps iterations on a fresh trainer"),
                    "config": args.config, "stage": args.stage, "grid": cfg["grid"], "samples_per_ray": cfg["n_samples"],
                    "global_batch": cfg["batch_size"], "rays_per_gpu": rpg, "weights": args.weights, "step_graph": bool(args.graph),
@@ -858,16 +940,17 @@ def main():
                    "loss_statistics": ("whole batch (all-reduced mask sums, gathered per-frame depth statistics)"
                                        if trainer._dp() is not None else "single process"),
                    "final_loss": loss_val,
-                   "app_mask_fractions_over_the_timed_steps": {
-                       "first": {"static": frs["start"][1], "dynamic": frs["start"][2]},
-                       "last": {"static": frs["end"][1], "dynamic": frs["end"][2]},
-                       "note": "the appearance kernels' work follows these; they fall as the reference-initialised weights "
-                               "train, so a 20-step window right after start-up times a heavier step than a 200-step one"},
                    "dead_work": "skipped (SURVEY 3.1: pass E's dynamic forward, the colours of passes B-D)" if args.exploit_liveness
                    else "executed (work the reference also computes although nothing consumes it)"},
     }
+    if frs is not None:
+        out["config"]["app_mask_fractions_over_the_timed_steps"] = {
+            "first": {"static": frs["start"][1], "dynamic": frs["start"][2]},
+            "last": {"static": frs["end"][1], "dynamic": frs["end"][2]},
+            "note": "the appearance kernels' work follows these; they fall as the reference-initialised weights "
+                    "train, so a 20-step window right after start-up times a heavier step than a 200-step one"}
 
-    if not args.exploit_liveness and not args.no_liveness_leg:
+    if args.full and not args.exploit_liveness and not args.no_liveness_leg:
         # secondary figure: the same step without the dead dynamic forwards (identical results)
         trainer.dead_work = False
         dt2, _ = timed_steps(trainer, shard, max(10, args.steps // 4), 2, world, dev)
@@ -879,7 +962,7 @@ def main():
         trainer.dead_work = True
     if rf is not None and rank == 0:
         out["roofline"] = price_step(rf, ms, rpg)
-    if rank == 0 and world == 1 and not args.no_render:
+    if args.full and rank == 0 and world == 1 and not args.no_render:
         # BASELINE.json's second metric: render Mpix/s through the no-grad chunk loop of renderer.py:740-812 --
         # whole frames per call, and the reference's own eval chunk of 512 rays (renderer.py:732)
         H, W = cfg["H"], cfg["W"]
@@ -889,7 +972,7 @@ def main():
         # chip, the small kernels of the other chunks run beside them)
         out["render_chunk512"] = render_leg(L, R, S_, trainer, cfg, dev, 512, frames=4, streams=8)
         out["render_chunk512_one_stream"] = render_leg(L, R, S_, trainer, cfg, dev, 512, frames=2, streams=1)
-    if rank == 0 and world == 1 and not args.no_final_stage and args.config == "nvidia" and args.stage == "stage0":
+    if args.full and rank == 0 and world == 1 and not args.no_final_stage and args.config == "nvidia" and args.stage == "stage0":
         # 78 % of the reference's iterations run after the last upsampling (configs/Nvidia.txt: upsamp_list[-1] =
         # 22000 of 100000): the same step at the final resolution
         cfg_f = S_.scene_config("nvidia", "final")
@@ -939,7 +1022,7 @@ def main():
             "note": "rays of a whole 100000-iteration Nvidia.txt run / its time: every stage of the resolution schedule measured "
                     "at its own grid and sample count from reference-initialised weights (stage 0 = the headline window; up1-up3 "
                     "8 timed steps after 3; final = the final_stage leg), weighted by its share of the iterations"}
-    if (rank == 0 and world == 1 and not args.no_graph_leg and not args.graph and not trainer.opt.ex.active
+    if (args.full and rank == 0 and world == 1 and not args.no_graph_leg and not args.graph and not trainer.opt.ex.active
             and args.config == "nvidia" and args.stage == "stage0"):
         # the launch-bound coarse stage of configs[2] (configs/Nvidia_no_poses.txt: grid [17,19,11], S = 13, the first 2000
         # iterations; 7 dynamic + 9 static passes with pose / focal optimisation): one iteration enqueued launch by launch from
@@ -957,7 +1040,7 @@ def main():
             del tr_c
             torch.cuda.empty_cache()
         out["launch_bound_stage"] = leg
-    if rank == 0 and world == 1 and not args.no_sparse and args.weights == "dense":
+    if args.full and rank == 0 and world == 1 and not args.no_sparse and args.weights == "dense":
         # SURVEY 8d W-sparse: the same step / render with trained-scene-like occupancy (app mask ~0.10 in both fields)
         tr_s = S_.Trainer(dict(cfg), dev, weights="sparse", dead_work=not args.exploit_liveness)
         dts, _ = timed_steps(tr_s, shard, max(10, args.steps // 5), 3, 1, dev)
@@ -970,11 +1053,16 @@ def main():
             sp["render"] = render_leg(L, R, S_, tr_s, cfg, dev, cfg["H"] * cfg["W"], frames=3)
         out["sparse_weights"] = sp
         del tr_s
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(trainer, args.cpu_rays, args.cpu_repeats, dead_work=not args.exploit_liveness)
         if args.cpu_rays < 4096 and not args.no_cpu_4096:   # BASELINE.json configs[0]: "4k rays/iter, PyTorch-CPU": one timed step
             out["cpu_baseline_4096"] = cpu_baseline(trainer, 4096, 1, dead_work=not args.exploit_liveness)
             out["cpu_baseline_4096"]["note"] = "the configs[0] batch size; one timed step after a 512-ray warm-up"
+    if args.dump_outputs:   # last, on a trainer of its own: the --full legs above run on the state the timed region left
+        tr_d, loss_d = dump_step(make_trainer, shard, args.warmup + args.steps - 1)
+        if rank == 0:
+            dump_outputs(tr_d, loss_d, args.dump_outputs)
+        del tr_d, loss_d
     if rank == 0:
         # what a reader of the driver's `parsed` summary should see without opening nested keys
         if "final_stage" in out:
@@ -997,7 +1085,7 @@ def main():
                 out["final_stage_frac_of_fp32_mfma_peak"] = out["final_stage"]["roofline"]["frac"]
             if "render" in out["final_stage"]:
                 out["render_final_stage_mpix_per_s"] = out["final_stage"]["render"]["value"]
-        if world == 1:
+        if args.full and world == 1:
             r640 = committed_hbm_roofline("640_", "BASELINE.json configs[4] shape: nvidia_no_poses final, grid [706,786,471], S=578, 4096 rays, 1 GPU "
                                                   "(421 MB of factors > the 256 MB Infinity Cache: the HBM roof is physical here)")
             rdav = committed_hbm_roofline("davis_final_", "BASELINE.json configs[3] shape: davis final, grid 256^3, S=221, 8192 rays, 1 GPU")

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || true
 mkdir -p gpurun_out
 {
 for stage in stage0 final; do for lib in librodynrf_tools abl_dwnl abl_dwnm; do for x in 0 1; do
-  RDRF_LIB=$PWD/robust-dynrf_amd/$lib.so RDRF_DW3=$x timeout 300 python bench.py --stage $stage --steps 12 --warmup 4 --no-cpu-baseline --no-final-stage --no-render --no-sparse >/dev/null 2>&1
+  RDRF_LIB=$PWD/robust-dynrf_amd/$lib.so RDRF_DW3=$x timeout 300 python bench.py --full --stage $stage --steps 12 --warmup 4 --no-cpu-baseline --no-final-stage --no-render --no-sparse >/dev/null 2>&1
   python - "$stage $lib RDRF_DW3=$x" <<'PY'
 import json, sys
 d = json.load(open("bench_detail.json")); r = d["roofline"]["kernel_ms_per_step"]

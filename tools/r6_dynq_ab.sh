@@ -5,7 +5,7 @@ mkdir -p gpurun_out
 export RDRF_LIB=$PWD/robust-dynrf_amd/librodynrf_tools.so
 {
 for stage in stage0 final; do for i in 1 2 3; do for x in 0 1; do
-  RDRF_DYNQ=$x timeout 300 python bench.py --stage $stage --steps 20 --warmup 5 --no-cpu-baseline --no-final-stage --no-render --no-sparse --no-liveness-leg >/dev/null 2>&1
+  RDRF_DYNQ=$x timeout 300 python bench.py --full --stage $stage --steps 20 --warmup 5 --no-cpu-baseline --no-final-stage --no-render --no-sparse --no-liveness-leg >/dev/null 2>&1
   python - "$stage RDRF_DYNQ=$x" <<'PY'
 import json, sys
 d = json.load(open("bench_detail.json")); r = d["roofline"]["kernel_ms_per_step"]

@@ -7,7 +7,7 @@ cat gpurun_out/sortc_tests.txt
 export RDRF_LIB=$PWD/robust-dynrf_amd/librodynrf_tools.so
 {
 for stage in stage0 final; do for i in 1 2; do for x in 0 1; do
-  RDRF_SORT_COMPACT=$x timeout 300 python bench.py --stage $stage --steps 20 --warmup 5 --no-cpu-baseline --no-final-stage --no-render --no-sparse --no-liveness-leg >/dev/null 2>&1
+  RDRF_SORT_COMPACT=$x timeout 300 python bench.py --full --stage $stage --steps 20 --warmup 5 --no-cpu-baseline --no-final-stage --no-render --no-sparse --no-liveness-leg >/dev/null 2>&1
   python - "$stage RDRF_SORT_COMPACT=$x" <<'PY'
 import json, sys
 d = json.load(open("bench_detail.json")); r = d["roofline"]["kernel_ms_per_step"]
