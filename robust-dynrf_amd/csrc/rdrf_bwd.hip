@@ -134,6 +134,8 @@ struct BwdArgs {
   float* dxw_app;  // [N*S*3] coordinate grads arriving from the appearance phase
   float* dxn_app;  // [N*S*3]
   float* dtout;    // [N*32]
+  float* gsig;     // flat-tile path: total d(sigma) per sample, [N*S] (k_ray_scan_bwd)
+  float* dtp;      // flat-tile path: d(tout) partial sums of the rays that cross a tile edge, [tiles][2][32] (k_time_branch_bwd sums them)
   float* dfs;      // sorted scatter: d(features) of the density / blending heads SAMPLE-major, [N*S][2][72] in the
                    // order [XY quads of level 0, 1, 2 | XZ quads | YZ quads] (nullptr: row layout for the ray-tile scatter)
   float* dfa;      // sorted appearance scatter: d(app features) per COMPACTED sample, [count][216] (dfa_off); nullptr: rows
@@ -1220,6 +1222,7 @@ struct ScatterArgs {
   RdrfVM vm[2], gvm[2];
   int nsets;
   const float* rows;   // d(feature) rows: tile t, row r at rows + (t*stride + row0[set] + r)*32
+  int flat;            // ray-tile mode: the tiles are 32-sample tiles of the flat [N * S] array, not (ray, tile) pairs
   int stride, row0[2];
   const float* xw;     // [idx][3] normalised coordinates, or nullptr -> normalise xyz
   const float* xyz;
@@ -1249,7 +1252,7 @@ __global__ __launch_bounds__(512, 3) void k_scatter(ScatterArgs a) {
   const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
   const int tpr = (a.S + 31) >> 5;
   const int count = a.list ? *a.count : 0;
-  const int ntiles = a.list ? ((count + 31) >> 5) : a.N * tpr;
+  const int ntiles = a.list ? ((count + 31) >> 5) : (a.flat ? (a.N * a.S + 31) >> 5 : a.N * tpr);
   for (int t = blockIdx.x * nwaves + wave; t < ntiles; t += gridDim.x * nwaves) {
     int idx;
     bool live;
@@ -1257,6 +1260,11 @@ __global__ __launch_bounds__(512, 3) void k_scatter(ScatterArgs a) {
       const int li = t * 32 + s;
       live = li < count;
       idx = live ? a.list[li] : 0;
+    } else if (a.flat) {
+      const int i = t * 32 + s;
+      const bool act = i < a.N * a.S;
+      idx = act ? i : 0;
+      live = act && a.valid[idx] != 0;
     } else {
       const int n = t / tpr, j = (t - n * tpr) * 32 + s;
       const bool act = j < a.S;
@@ -1379,6 +1387,7 @@ struct SortKeyArgs {
   int kb;                // bits of the cell part of the key
   unsigned* keys;        // [3][N*S]; compact: [3][*count]
   int* counts;           // [3] live entries per plane
+  int flat;              // the density-phase rows are addressed by flat 32-sample tile (rdrf_flat_density)
   int compact;           // list mode: the key arrays hold the *count compacted entries of each plane back to back (stride *count
                          // instead of N*S), so that the sort and the key generation touch live entries only (round 6)
 };
@@ -1404,7 +1413,8 @@ __global__ __launch_bounds__(256) void k_sort_keys(SortKeyArgs a) {
     } else {
       const int idx = e;
       const int n = idx / a.S, j = idx - n * a.S;
-      const float* sm = a.grows1 + ((size_t)(n * tpr + (j >> 5)) * sv::K1G_ROWS + sv::K1G_SM) * 32 + (j & 31);
+      const float* sm = a.grows1 + ((size_t)(a.flat ? idx >> 5 : n * tpr + (j >> 5)) * sv::K1G_ROWS + sv::K1G_SM) * 32 +
+                        (a.flat ? idx & 31 : j & 31);
       live = a.valid[idx] != 0 && (sm[3 * 32] != 0.f || sm[4 * 32] != 0.f);
       x0 = a.xw[(size_t)idx * 3 + 0]; x1 = a.xw[(size_t)idx * 3 + 1]; x2 = a.xw[(size_t)idx * 3 + 2];
     }
@@ -1683,8 +1693,95 @@ RDRF_D float reduce_scatter32(const float (&p)[32], int s) {
   return (b0 ? u[1] : u[0]) + __shfl_xor(b0 ? u[0] : u[1], 1, 64);
 }
 
-template <int PHASE, bool FEAT>
+// The scan half of the heads' backward on the flat-tile path (rdrf_flat_density): per ray, the transmittance carries at
+// the tile starts (pre-pass) and the reverse suffix sweep of d(weight) -> d(alpha); per sample the total
+// g_sigma = the caller's g_sigma + g_alpha ds (1 - alpha) (BwdArgs::gsig), the g_z updates, and the ray norm's share of
+// g_rays.  A half-wave per ray (two rays per wave, as ray_scan_body).  The expressions and the order of every sum are
+// those of the wave-per-ray k_dyn_density_bwd<0>, so g_sigma comes out bit-identical.
+__global__ __launch_bounds__(512) void k_ray_scan_bwd(BwdArgs a) {
+  __shared__ float carr[16][128];   // per half-wave: transmittance at the tile starts (S <= 4096)
+  const int lane = threadIdx.x & 63, h = lane >> 5, s = lane & 31;
+  const int hw = (threadIdx.x >> 6) * 2 + h;
+  const int n_ = blockIdx.x * 16 + hw;
+  const bool ray = n_ < a.N;
+  const int n = ray ? n_ : 0;
+  const int tpr = (a.S + 31) >> 5;
+  float vx, vy, vz;
+  const float nrm = ray_norm(a.rays, n, a.ray_type, vx, vy, vz);
+  if (a.g_weight) {  // pre-pass: transmittance at each tile start
+    float carry = 1.0f;
+    for (int j0 = 0; j0 < a.S; j0 += 32) {
+      if (s == 0) carr[hw][j0 >> 5] = carry;
+      const int j = j0 + s;
+      const bool act = ray && j < a.S;
+      const int idx = n * a.S + (act ? j : 0);
+      const bool vld = act && a.valid[idx] != 0;
+      const float sigma = vld ? density_act(a.sp.raw[(size_t)idx * 2], a.act, a.density_shift) : 0.f;
+      const float zj = act ? a.z[idx] : 0.f;
+      const float zn = (j + 1 < a.S) ? a.z[idx + 1] : zj;
+      const float ds = ((j + 1 < a.S) ? (zn - zj) : 0.0f) * nrm * a.distance_scale;
+      const float alpha = 1.0f - expf(-sigma * ds);
+      const float p = act ? one_minus_alpha_eps(alpha) : 1.0f;
+      carry *= __shfl(scan_mul32(p, s), 31, 32);
+    }
+  }
+  float sufcarry = 0.f, g_nrm = 0.f;
+  for (int tli = tpr - 1; tli >= 0; --tli) {  // LAST tile first: direct suffix sums
+    const int j = (tli << 5) + s;
+    const bool act = ray && j < a.S;
+    const int idx = n * a.S + (act ? j : 0);
+    const bool vld = act && a.valid[idx] != 0;
+    const float sigma = vld ? density_act(a.sp.raw[(size_t)idx * 2], a.act, a.density_shift) : 0.f;
+    const float zj = act ? a.z[idx] : 0.f;
+    const float zn = (j + 1 < a.S) ? a.z[idx + 1] : zj;
+    const float ds = ((j + 1 < a.S) ? (zn - zj) : 0.0f) * nrm * a.distance_scale;
+    const float alpha = 1.0f - expf(-sigma * ds);
+    const float p = act ? one_minus_alpha_eps(alpha) : 1.0f;
+    float g_alpha = 0.f;
+    if (a.g_weight) {
+      const float incl = scan_mul32(p, s);
+      float excl = __shfl_up(incl, 1, 32);
+      if (s == 0) excl = 1.0f;
+      const float T = carr[hw][tli] * excl;
+      const float gwv = act ? a.g_weight[idx] : 0.f;
+      float rinc = gwv * alpha * T;
+#pragma unroll
+      for (int d = 1; d < 32; d <<= 1) {
+        const float o = __shfl_down(rinc, d, 32);
+        if (s + d < 32) rinc += o;
+      }
+      float rex = __shfl_down(rinc, 1, 32);
+      if (s == 31) rex = 0.f;
+      g_alpha = gwv * T - (sufcarry + rex) / p;
+      sufcarry += __shfl(rinc, 0, 32);
+    }
+    float g_sigma = (act && a.g_sigma) ? a.g_sigma[idx] : 0.f;
+    g_sigma += g_alpha * ds * (1.0f - alpha);
+    if (act) a.gsig[idx] = g_sigma;
+    if ((a.g_rays || a.g_z) && act) {
+      const float g_ds = (a.g_dists ? a.g_dists[idx] : 0.f) + g_alpha * sigma * (1.0f - alpha);
+      if (a.g_rays) g_nrm += g_ds * ((j + 1 < a.S) ? (zn - zj) : 0.0f) * a.distance_scale;
+      if (a.g_z && j + 1 < a.S) {
+        const float gz = g_ds * nrm * a.distance_scale;
+        atomicAdd(a.g_z + idx, -gz);
+        atomicAdd(a.g_z + idx + 1, gz);
+      }
+    }
+  }
+  if (a.g_rays && a.ray_type != RDRF_RAY_OTHER) {   // the half-wave owns its ray: one update per component
+#pragma unroll
+    for (int d = 16; d >= 1; d >>= 1) g_nrm += __shfl_xor(g_nrm, d, 64);
+    if (ray && s < 3) atomicAdd(a.g_rays + (size_t)n * 6 + 3 + s, g_nrm * (s == 0 ? vx : (s == 1 ? vy : vz)));
+  }
+}
+
+// FLAT (training, rdrf_flat_density): the unit of work is a 32-sample tile of the flat [N * S] array, the saved rows and the
+// gradient rows are those of tile `n`; phase 0 reads the total d(sigma) per sample from k_ray_scan_bwd, phase 1 reduces
+// d(tout) per ray over the tile's lanes (segmented by the lane's ray) and writes it directly for a ray that lies inside
+// the tile, or as one of the tile's two partial records (first / last ray) that k_time_branch_bwd sums in a fixed order.
+template <int PHASE, bool FEAT, bool FLAT = false>
 __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_density_bwd(BwdArgs a, DynW w, DynG gw) {
+  static_assert(!(FLAT && FEAT), "feature mode keeps its pseudo-ray geometry (S = 32: a ray is a tile)");
   __shared__ __attribute__((aligned(16))) float lds[PHASE == 0 ? pkb::K1H_SIZE : pkb::K1W_SIZE];
   __shared__ float carr[8][128];  // per-wave transmittance carries at tile starts (S <= 4096)
   lds_fill(lds, a.pk + (PHASE == 0 ? pkb::REG_K1H : pkb::REG_K1W), PHASE == 0 ? pkb::K1H_SIZE : pkb::K1W_SIZE);
@@ -1694,11 +1791,12 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_density_bwd(BwdArgs a, D
   // small-layer weight gradients of this wave (ray path): lane (s, h) holds input element elem_of(s, h) of up to three
   // output rows (PHASE 0: density / blending layer2; PHASE 1: the three rows of layer5) + the rows' bias sums per lane
   float sw[3] = {0.f, 0.f, 0.f}, sb[3] = {0.f, 0.f, 0.f};
-  for (int n = blockIdx.x * nwaves + wave; n < a.N; n += gridDim.x * nwaves) {
+  const int nunits = FLAT ? (a.N * a.S + 31) >> 5 : a.N;
+  for (int n = blockIdx.x * nwaves + wave; n < nunits; n += gridDim.x * nwaves) {
     float vx = 0.f, vy = 0.f, vz = 0.f;
     float nrm = 1.0f;
-    if constexpr (!FEAT) nrm = ray_norm(a.rays, n, a.ray_type, vx, vy, vz);
-    if (!FEAT && PHASE == 0 && a.g_weight) {  // pre-pass: transmittance at each tile start
+    if constexpr (!FEAT && !FLAT) nrm = ray_norm(a.rays, n, a.ray_type, vx, vy, vz);
+    if (!FEAT && !FLAT && PHASE == 0 && a.g_weight) {  // pre-pass: transmittance at each tile start
       float carry = 1.0f;
       for (int j0 = 0; j0 < a.S; j0 += 32) {
         if (lane == 0) carr[wave][j0 >> 5] = carry;
@@ -1719,13 +1817,13 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_density_bwd(BwdArgs a, D
     float dTacc[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) dTacc[i] = 0.f;
-    for (int tli = tpr - 1; tli >= 0; --tli) {  // LAST tile first: direct suffix sums
+    for (int tli = FLAT ? 0 : tpr - 1; tli >= 0; --tli) {  // LAST tile first: direct suffix sums
       const int j0 = tli << 5;
       const int j = j0 + s;
-      const bool act = j < a.S && (!FEAT || n * a.S + j < a.M);
-      const int idx = n * a.S + (act ? j : 0);
+      const bool act = FLAT ? n * 32 + s < a.N * a.S : j < a.S && (!FEAT || n * a.S + j < a.M);
+      const int idx = FLAT ? (act ? n * 32 + s : 0) : n * a.S + (act ? j : 0);
       const bool vld = act && (FEAT || a.valid[idx] != 0);
-      const size_t tl = (size_t)n * tpr + tli;
+      const size_t tl = FLAT ? (size_t)n : (size_t)n * tpr + tli;
       const float* svb = a.sp.act1 + tl * sv::K1_ROWS * 32;
       float* gb = a.grows1 + tl * sv::K1G_ROWS * 32;
       if (PHASE == 0) {
@@ -1733,6 +1831,12 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_density_bwd(BwdArgs a, D
         if constexpr (FEAT) {  // the gradients of the raw head outputs arrive directly
           g_fd = (act && a.g_sigma) ? a.g_sigma[idx] : 0.f;
           g_fb = (act && a.g_blending) ? a.g_blending[idx] : 0.f;
+        } else if constexpr (FLAT) {   // the scan half ran in k_ray_scan_bwd
+          const float fd = a.sp.raw[(size_t)idx * 2], fb = a.sp.raw[(size_t)idx * 2 + 1];
+          const float g_sigma = act ? a.gsig[idx] : 0.f;
+          g_fd = vld ? g_sigma * act_grad(fd, a.act, a.density_shift) : 0.f;
+          const float bl = sigmoidf_(fb);
+          g_fb = (vld && a.g_blending) ? a.g_blending[idx] * bl * (1.0f - bl) : 0.f;
         } else {
         const float fd = a.sp.raw[(size_t)idx * 2], fb = a.sp.raw[(size_t)idx * 2 + 1];
         const float sigma = vld ? density_act(fd, a.act, a.density_shift) : 0.f;
@@ -1954,7 +2058,27 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_density_bwd(BwdArgs a, D
         }
       }
     }
-    if (PHASE == 1 && !FEAT) {  // per-ray d(tout): sum over the samples (lanes of each half)
+    if (PHASE == 1 && !FEAT && FLAT) {
+      // d(tout) of the tile's rays: segmented suffix sums over the lanes of each half (keys: the lane's ray, contiguous);
+      // the first lane of a segment ends up with the segment's sum
+      const int i0 = n * 32 + s, nl = i0 / a.S;
+      const int rb = nl * a.S - n * 32, re = rb + a.S - 1;   // the lane's ray: first / last sample relative to the tile
+      const int end = re < 31 ? re : 31;
+      const bool head = i0 < a.N * a.S && (s == 0 || rb == s);
+      float* dst = (rb >= 0 && re <= 31) ? a.dtout + (size_t)nl * 32           // the ray lies inside the tile
+                                         : a.dtp + ((size_t)n * 2 + (s == 0 ? 0 : 1)) * 32;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        float v = dTacc[i];
+#pragma unroll
+        for (int d = 1; d < 32; d <<= 1) {
+          const float o = __shfl_down(v, d, 32);
+          if (s + d <= end) v += o;
+        }
+        if (head) dst[elem_of(i, h)] = v;
+      }
+    }
+    if (PHASE == 1 && !FEAT && !FLAT) {  // per-ray d(tout): sum over the samples (lanes of each half)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         float v = dTacc[i];
@@ -1963,7 +2087,7 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_density_bwd(BwdArgs a, D
         if (s == 0) a.dtout[(size_t)n * 32 + elem_of(i, h)] = v;
       }
     }
-    if (!FEAT && PHASE == 0 && a.g_rays && a.ray_type != RDRF_RAY_OTHER) {
+    if (!FEAT && !FLAT && PHASE == 0 && a.g_rays && a.ray_type != RDRF_RAY_OTHER) {
       g_nrm = wave_sum(g_nrm);
       if (lane < 3) atomicAdd(a.g_rays + (size_t)n * 6 + 3 + lane, g_nrm * (lane == 0 ? vx : (lane == 1 ? vy : vz)));
     }
@@ -2003,8 +2127,20 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_density_bwd(BwdArgs a, D
 // one atomic per entry.  (128 rays per block / thread per ray used 32 CUs: 56 us per launch.)
 // ------------------------------------------------------------------------------------------------
 #define TB_RPB 32
+// d(tout) of ray n, element o.  dtp == nullptr: dtout holds it.  Flat-tile path (k_dyn_density_bwd<1, false, true>): a ray
+// inside one tile was written to dtout; a ray that crosses tile edges is the sum of its tiles' partial records, in tile
+// order: [t0][last ray] (or [t0][first ray] if the ray starts the tile), then [t][first ray] for the following tiles.
+RDRF_D float dtout_of_ray(const float* __restrict__ dtout, const float* __restrict__ dtp, int S, int n, int o) {
+  const int b = n * S, t0 = b >> 5, t1 = (b + S - 1) >> 5;
+  if (dtp == nullptr || t0 == t1) return dtout[(size_t)n * 32 + o];
+  float v = dtp[((size_t)t0 * 2 + ((b & 31) == 0 ? 0 : 1)) * 32 + o];
+  for (int t = t0 + 1; t <= t1; ++t) v += dtp[(size_t)t * 64 + o];
+  return v;
+}
+
 __global__ __launch_bounds__(128) void k_time_branch_bwd(const float* __restrict__ ts, DynW w, int N,
                                                          const float* __restrict__ dtout,
+                                                         const float* __restrict__ dtp, int S,
                                                          float* __restrict__ g_l1w,
                                                          float* __restrict__ g_l1b,
                                                          float* __restrict__ g_l2w,
@@ -2024,7 +2160,7 @@ __global__ __launch_bounds__(128) void k_time_branch_bwd(const float* __restrict
   for (int f = 0; f < 8; ++f) sincosf(ldexpf(t, f), &tin[1 + f], &tin[9 + f]);
   if (q == 0)
     for (int i = 0; i < 17; ++i) s_tin[r][i] = tin[i];
-  for (int o = q; o < 30; o += 4) s_dz2[r][o] = act ? dtout[(size_t)n * 32 + o] : 0.f;
+  for (int o = q; o < 30; o += 4) s_dz2[r][o] = act ? dtout_of_ray(dtout, dtp, S, n, o) : 0.f;
   __syncthreads();
   for (int k = 16 * q; k < 16 * q + 16; ++k) {
     float hk = w.l1b[k];
@@ -2747,6 +2883,8 @@ extern "C" size_t rdrf_workspace_bytes(int N, int S) {
                ns * 3 * 4 * 2 + (size_t)N * 32 * 4 + (1 << 14);
   // sorted scatter: sample-major d(feature) records, keys in / out, sorted positions, counters, radix-sort scratch
   bwd += ns * DFS_FLOATS * 4 + ns * DFA_FLOATS * 4 + 3 * ns * 4 * 3 + 1024 + rdrf_sort_temp_bytes((unsigned)(3 * ns), 32) + (1 << 12);
+  // flat-tile density phase: total d(sigma) per sample + the d(tout) partial records of the tiles
+  bwd += ns * 4 + t3 * 64 * 4 + 512;
   size_t sf = (size_t)PACK_AREA_FLOATS * 4 + t3 * sv::SFG_ROWS * 32 * 4 + (1 << 12);
   size_t m = fwd > bwd ? fwd : bwd;
   return m > sf ? m : sf;
@@ -2766,6 +2904,8 @@ struct BwdWs {
   float* dxw;
   float* dxn;
   float* dtout;
+  float* gsig;     // flat-tile density phase (BwdArgs::gsig, ::dtp)
+  float* dtp;
 };
 static int carve_bwd(BwdWs& b, void* ws, size_t ws_bytes, int N, int S, int dynamic) {
   WsCarver c(ws, ws_bytes);
@@ -2779,6 +2919,7 @@ static int carve_bwd(BwdWs& b, void* ws, size_t ws_bytes, int N, int S, int dyna
   b.gf = dynamic ? nullptr : c.take<float>(t1 * 32);
   b.dfs = nullptr;
   b.dfa = nullptr;
+  b.gsig = b.dtp = nullptr;
   if (dynamic) {
     b.dfs = c.take<float>(ns * DFS_FLOATS);
     b.dfa = c.take<float>(ns * DFA_FLOATS);
@@ -2788,6 +2929,8 @@ static int carve_bwd(BwdWs& b, void* ws, size_t ws_bytes, int N, int S, int dyna
     b.counts = c.take<int>(64);
     b.sort_tmp_bytes = rdrf_sort_temp_bytes((unsigned)(3 * ns), 32);
     b.sort_tmp = c.take<char>(b.sort_tmp_bytes);
+    b.gsig = c.take<float>(ns);
+    b.dtp = c.take<float>(t3 * 64);
   }
   RDRF_CHECK(c.ok(), -3, "backward workspace too small: need %zu have %zu", c.off, ws_bytes);
   return 0;
@@ -3071,6 +3214,7 @@ static int scatter_dyn_density_sorted(const BwdArgs& a, const BwdWs& b, const Rd
   SortKeyArgs ka;
   memset(&ka, 0, sizeof(ka));
   ka.grows1 = b.grows1;
+  ka.flat = rdrf_flat_density() ? 1 : 0;
   int rc = sorted_scatter_prepare(ka, P->density, a, b, stream);
   if (rc) return rc;
   SortedScatterArgs sa;
@@ -3246,6 +3390,9 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
   if (rc) return rc;
   a.pk = b.pk; a.grows1 = b.grows1; a.grows3 = b.grows3; a.dxw_app = b.dxw; a.dxn_app = b.dxn;
   a.dtout = b.dtout;
+  // the density phase on flat 32-sample tiles (the forward wrote its saved rows that way: rdrf_dynamic_fwd)
+  const bool flat = rdrf_flat_density();
+  a.gsig = b.gsig; a.dtp = b.dtp;
   DynW w;
   fill_dyn_w(w, P);
   DynG gw;
@@ -3259,7 +3406,7 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
     rc = pack_launch(J, b.pk, stream);
     if (rc) return rc;
   }
-  const size_t ns = (size_t)N * S, t3 = (ns + 31) / 32, t1 = (size_t)N * ((S + 31) / 32);
+  const size_t ns = (size_t)N * S, t3 = (ns + 31) / 32, t1 = flat ? t3 : (size_t)N * ((S + 31) / 32);   // density-phase tiles
   RDRF_FILL(b.dxw, 0, ns * 3 * 4, stream);
   RDRF_FILL(b.dxn, 0, ns * 3 * 4, stream);
   const int* cnt = &a.sp.hdr->count;
@@ -3303,10 +3450,13 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
     dw_blk(D, sv::K3_X1, SEG_RGB1_X1, 0);
   }
   {
-    const Geo g = geo_for_units(N);
+    const Geo g = geo_for_units(flat ? (long)t1 : (long)N);
     const int smode = scatter_mode(ns, stream);
     a.dfs = smode != 0 ? b.dfs : nullptr;
-    RDRF_LAUNCH("dyn_heads_bwd", (k_dyn_density_bwd<0, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+    if (flat) {
+      RDRF_LAUNCH("ray_scan_bwd", k_ray_scan_bwd, dim3((N + 15) / 16), dim3(512), stream, a);   // 16 rays per workgroup
+      RDRF_LAUNCH("dyn_heads_bwd", (k_dyn_density_bwd<0, false, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+    } else RDRF_LAUNCH("dyn_heads_bwd", (k_dyn_density_bwd<0, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
     if (smode != 0) {
       const int set_mask = ((g_sigma != nullptr || g_weight != nullptr) ? 1 : 0) | (g_blending != nullptr ? 2 : 0);
       if (set_mask != 0) {
@@ -3325,15 +3475,16 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
         sa.nsets = 0;
         if (has_d) { sa.vm[sa.nsets] = P->density; sa.gvm[sa.nsets] = G->density; sa.row0[sa.nsets] = sv::K1G_DFD; ++sa.nsets; }
         if (has_b) { sa.vm[sa.nsets] = P->blending; sa.gvm[sa.nsets] = G->blending; sa.row0[sa.nsets] = sv::K1G_DFB; ++sa.nsets; }
-        sa.rows = b.grows1; sa.stride = sv::K1G_ROWS;
+        sa.rows = b.grows1; sa.stride = sv::K1G_ROWS; sa.flat = flat ? 1 : 0;
         sa.xw = a.sp.xw;
         sa.dxw = b.dxw; sa.dxw_accumulate = 1;
         { int rc_ = launch_scatter("scatter_dyn_density", k_scatter<4, 1, 9>, sa, (long)t1, stream); if (rc_) return rc_; }
       }
     }
-    RDRF_LAUNCH("dyn_warp_bwd", (k_dyn_density_bwd<1, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+    if (flat) RDRF_LAUNCH("dyn_warp_bwd", (k_dyn_density_bwd<1, false, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+    else RDRF_LAUNCH("dyn_warp_bwd", (k_dyn_density_bwd<1, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
     RDRF_LAUNCH("time_branch_bwd", k_time_branch_bwd, dim3((N + TB_RPB - 1) / TB_RPB), dim3(128), stream, ts, w,
-                N, b.dtout, G->l1w, G->l1b, G->l2w, G->l2b);
+                N, b.dtout, flat ? (const float*)b.dtp : nullptr, S, G->l1w, G->l1b, G->l2w, G->l2b);
     const bool small_in_kernel = a.small_dw != 0;
     add_density_phase_dw(D, b.grows1, a.sp.act1, G, (int)t1, g_sigma != nullptr || g_weight != nullptr, g_blending != nullptr,
                          small_in_kernel);
@@ -3504,7 +3655,7 @@ extern "C" int rdrf_dynamic_features_bwd(const RdrfDynamicParams* P, const RdrfF
   }
   RDRF_LAUNCH("feat_dyn_warp_bwd", (k_dyn_density_bwd<1, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
   RDRF_LAUNCH("time_branch_bwd", k_time_branch_bwd, dim3((M + TB_RPB - 1) / TB_RPB), dim3(128), stream, t, w, M,
-              b.dtout, G->l1w, G->l1b, G->l2w, G->l2b);
+              b.dtout, (const float*)nullptr, 32, G->l1w, G->l1b, G->l2w, G->l2b);
   add_density_phase_dw(D, b.grows1, a.sp.act1, G, Np, g_density != nullptr, g_blending != nullptr);
   return dw_launch(D, stream, "feat_dw_dyn");
 }

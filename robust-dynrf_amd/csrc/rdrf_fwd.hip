@@ -46,9 +46,10 @@ __global__ __launch_bounds__(256) void k_time_branch(const float* __restrict__ t
   time_branch_body(ts, w, N, tout, s_h, grid_ctx());
 }
 
-// inference: the density phase of the dynamic field at tile granularity + the per-ray scan (rdrf_fwd_dev.hpp)
+// the density phase of the dynamic field at tile granularity + the per-ray scan (rdrf_fwd_dev.hpp); SAVE: training
+template <bool SAVE>
 __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_density_flat(FieldArgs a, DynW w) {
-  dyn_density_body<false, false, false, true>(a, w, nullptr, grid_ctx());
+  dyn_density_body<false, SAVE, false, true>(a, w, nullptr, grid_ctx());
 }
 __global__ __launch_bounds__(512) void k_ray_scan(FieldArgs a) { ray_scan_body(a); }   // 16 rays per workgroup
 
@@ -428,22 +429,22 @@ extern "C" int rdrf_dynamic_fwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
     rc = pack_launch(J, (float*)a.pk, stream);
     if (rc) return rc;
   }
-  // inference calls run the density phase at tile granularity (k_dyn_density_flat + k_ray_scan): a 512-ray eval chunk
-  // fills the chip and no tile is padded to the end of its ray; training keeps the wave-per-ray kernel, whose saved rows
-  // the backward kernels address by (ray, tile)
-  static const int flat_env = RDRF_ENV("RDRF_FLAT") ? atoi(RDRF_ENV("RDRF_FLAT")) : 1;   // 0: wave per ray (tools build)
-  const bool flat = saved == nullptr && flat_env != 0;
+  // the density phase runs at tile granularity (k_dyn_density_flat + k_ray_scan): no tile is padded to the end of its ray,
+  // and a 512-ray eval chunk fills the chip.  In training the saved rows are addressed by flat tile, and the backward
+  // (rdrf_dynamic_bwd) reads them the same way: both sides take the switch from rdrf_flat_density()
+  const bool flat = rdrf_flat_density();
   if (!flat && rgb != nullptr) RDRF_FILL(rgb, 0, (size_t)N * S * 3 * sizeof(float), stream);   // flat: k_ray_scan
   RDRF_LAUNCH("time_branch", k_time_branch, dim3((N + 7) / 8), dim3(256), stream, ts, w, N, a.tout, a.counter);
   const Geo g1 = geo_for_units(N), g3 = geo_for_tiles(N, S);
 #ifdef RDRF_DETERMINISTIC
   RDRF_FILL(a.list, 0x7f, (size_t)N * S * sizeof(int), stream);
 #endif
-  if (saved != nullptr) RDRF_LAUNCH("dyn_density", (k_dyn_density<false, true>), dim3(g1.grid), dim3(g1.block), stream, a, w);
-  else if (flat) {
-    RDRF_LAUNCH("dyn_density", k_dyn_density_flat, dim3(g3.grid), dim3(g3.block), stream, a, w);
+  if (flat) {
+    if (saved != nullptr) RDRF_LAUNCH("dyn_density", k_dyn_density_flat<true>, dim3(g3.grid), dim3(g3.block), stream, a, w);
+    else RDRF_LAUNCH("dyn_density", k_dyn_density_flat<false>, dim3(g3.grid), dim3(g3.block), stream, a, w);
     RDRF_LAUNCH("ray_scan", k_ray_scan, dim3((N + 15) / 16), dim3(512), stream, a);
-  } else RDRF_LAUNCH("dyn_density", (k_dyn_density<false, false>), dim3(g1.grid), dim3(g1.block), stream, a, w);
+  } else if (saved != nullptr) RDRF_LAUNCH("dyn_density", (k_dyn_density<false, true>), dim3(g1.grid), dim3(g1.block), stream, a, w);
+  else RDRF_LAUNCH("dyn_density", (k_dyn_density<false, false>), dim3(g1.grid), dim3(g1.block), stream, a, w);
 #ifdef RDRF_DETERMINISTIC
   { int rc_ = rdrf_sort_ints_inplace(a.list, (unsigned)((size_t)N * S), stream); if (rc_) return rc_; }
 #endif

@@ -444,26 +444,33 @@ RDRF_D void head_layer1(f32x16 (&acc)[2], const float (&Fv)[36], const float (&X
 }
 #endif
 
-// FLAT (inference only): the unit of work is a 32-sample tile of the flattened [N * S] sample array instead of a ray, so a
-// 512-ray eval chunk is 1840 tiles for the 2048 resident waves instead of 512 rays, and no tile is padded to the ray's
-// end (S = 115: 3.6 tiles per ray instead of 4).  The per-ray constants (time, tout, PE8(t)) are fetched per lane through
-// the sample's ray index; sigma and blending are written per sample and the transmittance scan / app-mask compaction run
-// afterwards in ray_scan_body (same arithmetic in the same order: results are bit-identical to the wave-per-ray form).
+// FLAT: the unit of work is a 32-sample tile of the flattened [N * S] sample array instead of a ray, so no tile is padded
+// to the ray's end (S = 115: 3.6 tiles per ray instead of 4; S = 13: 0.41 instead of 1) and a 512-ray eval chunk is 1840
+// tiles for the 2048 resident waves instead of 512 rays.  The tiles come from the workgroup's queue (tile_queue_next).  The
+// per-ray constants (time, tout, PE8(t)) are fetched per lane through the sample's ray index; sigma and blending (and in
+// training the raw head outputs and the saved rows of tile `n`) are written per sample, and the transmittance scan /
+// app-mask compaction run afterwards in ray_scan_body (same arithmetic in the same order: results are bit-identical to the
+// wave-per-ray form).  The backward kernels address the saved rows by flat tile as well (k_dyn_density_bwd<., ., true>).
 template <bool FEAT, bool SAVE = true, bool FUSED = false, bool FLAT = false>
 RDRF_D void dyn_density_body(const FieldArgs a, const DynW w, float* lds_fused, const GridCtx gc) {
-  static_assert(!FLAT || (!FEAT && !SAVE && !FUSED), "the flat-tile form is the inference kernel");
+  static_assert(!FLAT || (!FEAT && !FUSED), "the flat-tile form is a ray-path kernel of its own");
   float* lds;
   if constexpr (FUSED) lds = lds_fused;
   else {   // the standalone kernel owns its image as a named LDS array (constant addresses in every ds_read)
     __shared__ __attribute__((aligned(16))) float lds_own[pk::K1_SIZE];
     lds = lds_own;
   }
-  lds_fill(lds, a.pk + pk::REG_K1, pk::K1_SIZE);
   const int lane = GC_TID & 63, h = lane >> 5, s = lane & 31;
   const int wave = GC_TID >> 6, nwaves = GC_NTHR >> 6;
+  __shared__ int s_next;   // FLAT: the workgroup's tile queue
+  if (FLAT && GC_TID == 0) s_next = nwaves;
+  lds_fill(lds, a.pk + pk::REG_K1, pk::K1_SIZE);
   const float* pkw = lds;
   const int nunits = FLAT ? (int)(((long)a.N * a.S + 31) >> 5) : a.N;
-  for (int n = GC_BID * nwaves + wave; n < nunits; n += GC_NBLK * nwaves) {
+  const bool dynq = FLAT && (a.dynq & 1) != 0;
+  int k = wave;   // FLAT: queue position of the wave's current tile (tile = block + k * blocks)
+  for (int n = FLAT ? GC_BID + k * GC_NBLK : GC_BID * nwaves + wave; n < nunits;
+       n = FLAT ? GC_BID + (k = tile_queue_next(&s_next, k, nwaves, dynq)) * GC_NBLK : n + GC_NBLK * nwaves) {
   float t = 0.f, nrm = 1.0f;
   float T[16];
   float X1[8];
@@ -523,7 +530,7 @@ RDRF_D void dyn_density_body(const FieldArgs a, const DynW w, float* lds_fused, 
     const float xn2 = raw_in ? pz : norm_c(pz, a.box.lo[2], a.box.inv[2]);
     float X0[32];
     fill_x0(X0, xn0, xn1, xn2, t, h);
-    float* svb = (SAVE && a.act1) ? a.act1 + ((size_t)n * ((a.S + 31) >> 5) + (j0 >> 5)) * sv::K1_ROWS * 32 : nullptr;
+    float* svb = (SAVE && a.act1) ? a.act1 + (FLAT ? (size_t)n : (size_t)n * ((a.S + 31) >> 5) + (j0 >> 5)) * sv::K1_ROWS * 32 : nullptr;
     save_rows<32>(svb, sv::K1_X0, X0, s, h);
     save_rows<8>(svb, sv::K1_X1, X1, s, h);
     save_rows<16>(svb, sv::K1_T, T, s, h);
@@ -619,6 +626,7 @@ RDRF_D void dyn_density_body(const FieldArgs a, const DynW w, float* lds_fused, 
       if (act && h == 0) {
         a.sigma[idx] = vld ? density_act(fd, a.act, a.density_shift) : 0.0f;
         a.blending[idx] = vld ? sigmoidf_(fb) : 0.0f;
+        if (SAVE && a.raw != nullptr) { a.raw[(size_t)idx * 2] = fd; a.raw[(size_t)idx * 2 + 1] = fb; }
       }
     } else {
     const float sigma = vld ? density_act(fd, a.act, a.density_shift) : 0.0f;

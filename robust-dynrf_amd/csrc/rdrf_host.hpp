@@ -20,6 +20,14 @@ void rdrf_set_error(const char* fmt, ...);
 #define RDRF_ENV(name) ((const char*)nullptr)
 #endif
 
+// The dynamic field's density phase on flat 32-sample tiles of the [N * S] sample array (k_dyn_density_flat + k_ray_scan
+// forward; k_ray_scan_bwd + k_dyn_density_bwd<., ., true> backward) instead of a wave per ray.  Read once per process, so the
+// forward and the backward of a step agree on the saved-row addressing.  RDRF_FLAT=0 (tools build): wave per ray.
+inline bool rdrf_flat_density() {
+  static const bool flat = !(RDRF_ENV("RDRF_FLAT") != nullptr && atoi(RDRF_ENV("RDRF_FLAT")) == 0);
+  return flat;
+}
+
 #define RDRF_CHECK(cond, code, ...)  \
   do {                               \
     if (!(cond)) {                   \
