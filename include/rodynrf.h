@@ -452,6 +452,52 @@ int rdrf_render_chunks_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s
                            float near, float far, float* rgb_map, float* depth_map, void* ws, size_t ws_bytes,
                            rdrf_stream_t main_stream, const rdrf_stream_t* streams, int nstreams);
 
+/* ---- decomposed maps of the no-grad render (the eval loop keeps seven maps per frame, renderer.py:745-826) ------------
+ * One nullable DEVICE pointer per per-ray output of raw2outputs (renderer.py:173-315; the three per-sample weight planes
+ * are not offered).  NULL = not wanted: that output goes to the workspace, as with the entry points above.  The same
+ * workspace sizes apply (rdrf_render_workspace_bytes, rdrf_render_chunks_workspace_bytes), and every requested map has
+ * the bits the corresponding output of rdrf_composite_fwd has after the fields' forward. */
+typedef struct RdrfRenderMaps {
+  float* rgb;        /* rgb_map_full[N][3] */
+  float* depth;      /* depth_map_full[N] */
+  float* acc;        /* acc_map_full[N] */
+  float* rgb_s;      /* rgb_map_s[N][3] */
+  float* depth_s;    /* depth_map_s[N] */
+  float* acc_s;      /* acc_map_s[N] */
+  float* rgb_d;      /* rgb_map_d[N][3] */
+  float* depth_d;    /* depth_map_d[N] */
+  float* acc_d;      /* acc_map_d[N] */
+  float* blending;   /* dynamicness_map[N] */
+} RdrfRenderMaps;
+/* mode: the launch form of rdrf_render_fwd (AUTO), rdrf_render_sequence_fwd (SEQUENCE) or rdrf_render_fused_fwd (FUSED);
+ * a barrier time-out of the fused form sets every requested map of the affected rays to NaN. */
+enum { RDRF_RENDER_AUTO = 0, RDRF_RENDER_SEQUENCE = 1, RDRF_RENDER_FUSED = 2 };
+int rdrf_render_maps_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                         const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near, float far,
+                         int mode, const RdrfRenderMaps* maps, void* ws, size_t ws_bytes, rdrf_stream_t stream);
+/* the chunk loop of rdrf_render_chunks_fwd (same streams, same coalescing) with every non-NULL map offset per chunk */
+int rdrf_render_chunks_maps_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                                const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, int chunk,
+                                float near, float far, const RdrfRenderMaps* maps, void* ws, size_t ws_bytes,
+                                rdrf_stream_t main_stream, const rdrf_stream_t* streams, int nstreams);
+
+/* ---- rays of arbitrary cameras (evaluation_path, renderer.py:1013-1030; evaluation, :702-716) -----------------------
+ * c2w[B][3][4] camera-to-world matrices, focal[B] per camera.  Ray k is flat pixel first + k over (B, H, W):
+ * get_ray_directions_blender (pixel centre + 0.5, centre (W/2, H/2), focal on both axes, dataLoader/ray_utils.py:93-110),
+ * get_rays (:143-160, world rays, unnormalised directions) and, if ndc != 0, ndc_rays_blender with `near` (:197-218).
+ * rays[N][6]; first + N <= B H W. */
+int rdrf_camera_rays(const float* c2w, const float* focal, int B, int H, int W, int ndc, float near, int64_t first, int N,
+                     float* rays, rdrf_stream_t stream);
+
+/* ---- SSIM of two images (rgb_ssim, utils.py:98-151, with its defaults: 11-tap Gaussian, sigma 1.5, k1 = 0.01,
+ * k2 = 0.03) ----------------------------------------------------------------------------------------------------------
+ * img0, img1 [H][W][C] fp32, H, W >= 11.  The five moments and the map are accumulated in fp64 (the reference's
+ * float64 filter upcasts); *mean_out (one DEVICE double) = the mean of the map; map_out (nullable) [H-10][W-10][C] fp32.
+ * The mean is reduced in a fixed order: the same bits run after run.  ws: rdrf_ssim_workspace_bytes(H, W, C). */
+size_t rdrf_ssim_workspace_bytes(int H, int W, int C);
+int rdrf_ssim(const float* img0, const float* img1, int H, int W, int C, float max_val, double* mean_out, float* map_out,
+              void* ws, size_t ws_bytes, rdrf_stream_t stream);
+
 /* ---- process-wide choice of the density / blending scatter of the dynamic field's backward (models/tensoRF.py:646-811,
  * grid_sampler_2d_backward semantics either way): RDRF_SCATTER_RAY = ray tiles, RDRF_SCATTER_SORTED = samples grouped by
  * plane cell first (about 10x fewer memory-side atomic requests, a fixed grouping cost per launch), RDRF_SCATTER_AUTO

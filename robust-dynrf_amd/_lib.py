@@ -52,6 +52,17 @@ class RdrfDynamicParams(C.Structure):
                 ("sfw", C.c_void_p * 4), ("sfb", C.c_void_p * 4), ("packed_fwd", C.c_void_p), ("packed_bwd", C.c_void_p)]
 
 
+# RdrfRenderMaps (include/rodynrf.h): one nullable device pointer per per-ray output of the render, in this order
+RENDER_MAPS = ("rgb", "depth", "acc", "rgb_s", "depth_s", "acc_s", "rgb_d", "depth_d", "acc_d", "blending")
+
+
+class RenderMapsC(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in RENDER_MAPS]
+
+
+RENDER_MODES = {"auto": 0, "sequence": 1, "fused": 2}
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -94,6 +105,18 @@ def _load():
     lib.rdrf_render_workspace_bytes.argtypes = [C.c_int, C.c_int]
     lib.rdrf_render_chunks_workspace_bytes.restype = C.c_size_t
     lib.rdrf_render_chunks_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.rdrf_render_maps_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                         C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(RenderMapsC), C.c_void_p,
+                                         C.c_size_t, C.c_void_p]
+    lib.rdrf_render_chunks_maps_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(RenderMapsC),
+                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
+    lib.rdrf_camera_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int64,
+                                     C.c_int, C.c_void_p, C.c_void_p]
+    lib.rdrf_ssim_workspace_bytes.restype = C.c_size_t
+    lib.rdrf_ssim_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.rdrf_ssim.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_size_t, C.c_void_p]
     lib.rdrf_prof_get.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     lib.rdrf_det_bind.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.rdrf_det_finish.argtypes = [C.c_int, C.c_void_p]
@@ -121,6 +144,7 @@ SYMBOLS = [
     "rdrf_render_fused_fwd", "rdrf_render_sequence_fwd",
     "rdrf_frame_depth_loss_workspace_bytes", "rdrf_frame_depth_loss_fwd", "rdrf_frame_depth_loss_bwd",
     "rdrf_render_workspace_bytes", "rdrf_render_fwd", "rdrf_render_chunks_workspace_bytes", "rdrf_render_chunks_fwd",
+    "rdrf_render_maps_fwd", "rdrf_render_chunks_maps_fwd", "rdrf_camera_rays", "rdrf_ssim_workspace_bytes", "rdrf_ssim",
     "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_prof_reset",
     "rdrf_prof_enable", "rdrf_prof_get",
 ]

@@ -94,11 +94,16 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_render_fused(RenderFusedArgs
   // ---- phase 3: raw2outputs per ray
   if (ok) {
     composite_body(r.comp, gc);
-  } else {   // a barrier timed out: the phases ran on partial data -- poison this workgroup's share of the image
+  } else {   // a barrier timed out: the phases ran on partial data -- poison this workgroup's share of every per-ray
+    // output (the caller's maps and the workspace's alike; the per-sample weight planes 3, 7, 11 are no maps)
     const float nan = __int_as_float(0x7fc00000);
     for (int i = gc.bid * gc.nthr + gc.tid; i < N; i += gc.nblk * gc.nthr) {
-      r.comp.out[0][i * 3 + 0] = nan; r.comp.out[0][i * 3 + 1] = nan; r.comp.out[0][i * 3 + 2] = nan;
-      r.comp.out[1][i] = nan;
+#pragma unroll
+      for (int m = 0; m < 13; ++m) {
+        if (m == 3 || m == 7 || m == 11) continue;
+        const int w = (m % 4 == 0 && m < 12) ? 3 : 1;
+        for (int c = 0; c < w; ++c) r.comp.out[m][i * w + c] = nan;
+      }
     }
   }
 }
@@ -116,7 +121,20 @@ struct RenderBufs {
   void *fws_s, *fws_d;
   unsigned* barrier;
 };
-static int carve_render(RenderBufs& b, void* ws, size_t ws_bytes, int N, int S, float* rgb_map, float* depth_map) {
+// the per-ray outputs among the compositor's 13 (out13 order of rdrf_composite_fwd) and their widths; the three per-sample
+// weight planes (3, 7, 11) always stay in the workspace
+static const int kMapSlot[10] = {0, 1, 2, 4, 5, 6, 8, 9, 10, 12};
+static inline int map_width(int slot) { return (slot % 4 == 0 && slot < 12) ? 3 : 1; }
+static void maps_to_slots(float* out[13], const RdrfRenderMaps* m) {
+  for (int i = 0; i < 13; ++i) out[i] = nullptr;
+  if (!m) return;
+  float* const p[10] = {m->rgb, m->depth, m->acc, m->rgb_s, m->depth_s, m->acc_s, m->rgb_d, m->depth_d, m->acc_d, m->blending};
+  for (int i = 0; i < 10; ++i) out[kMapSlot[i]] = p[i];
+}
+
+// want[13]: the caller's output buffers (NULL: the output goes to the workspace).  The legacy entry points pass rgb and
+// depth only, which carves the workspace exactly as before the maps existed.
+static int carve_render(RenderBufs& b, void* ws, size_t ws_bytes, int N, int S, float* const want[13]) {
   WsCarver c(ws, ws_bytes);
   const size_t ns = (size_t)N * S;
   b.xyz = c.take<float>(ns * 3);
@@ -132,11 +150,9 @@ static int carve_render(RenderBufs& b, void* ws, size_t ws_bytes, int N, int S, 
   b.dists_d = c.take<float>(ns);
   b.blending = c.take<float>(ns);
   b.xyz_prime = c.take<float>(ns * 3);
-  const size_t osz[13] = {0, 0, (size_t)N, ns, (size_t)N * 3, (size_t)N, (size_t)N, ns, (size_t)N * 3,
+  const size_t osz[13] = {(size_t)N * 3, (size_t)N, (size_t)N, ns, (size_t)N * 3, (size_t)N, (size_t)N, ns, (size_t)N * 3,
                           (size_t)N, (size_t)N, ns, (size_t)N};
-  for (int i = 0; i < 13; ++i) b.out[i] = (i < 2) ? nullptr : c.take<float>(osz[i]);
-  b.out[0] = rgb_map;
-  b.out[1] = depth_map;
+  for (int i = 0; i < 13; ++i) b.out[i] = want[i] ? want[i] : c.take<float>(osz[i]);
   b.barrier = c.take<unsigned>(64);
   b.fws_s = c.take<char>(rdrf_forward_workspace_bytes(N, S));
   b.fws_d = c.take<char>(rdrf_forward_workspace_bytes(N, S));
@@ -145,9 +161,8 @@ static int carve_render(RenderBufs& b, void* ws, size_t ws_bytes, int N, int S, 
 }
 
 static int render_check(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
-                        const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float* rgb_map,
-                        float* depth_map, size_t ws_bytes) {
-  RDRF_CHECK(PS && PD && cfg_s && cfg_d && rays && ts && rgb_map && depth_map && N > 0 && S > 0, -1, "render: bad arguments");
+                        const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, size_t ws_bytes) {
+  RDRF_CHECK(PS && PD && cfg_s && cfg_d && rays && ts && N > 0 && S > 0, -1, "render: bad arguments");
   RDRF_CHECK((size_t)N * S * 3 < (size_t)INT32_MAX, -1, "render: N * S * 3 must stay below 2^31: render in chunks");
   RDRF_CHECK(ws_bytes >= rdrf_render_workspace_bytes(N, S), -3, "render: workspace too small");
   RDRF_CHECK(vm_ok(PS->density, 16, 4) && vm_ok(PS->app, 48, 12) && vm_ok(PD->density, 16, 4) && vm_ok(PD->blending, 16, 4) &&
@@ -157,16 +172,15 @@ static int render_check(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, c
 }
 
 /* one cooperative launch (see k_render_fused) */
-extern "C" int rdrf_render_fused_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
-                                     const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near,
-                                     float far, float* rgb_map, float* depth_map, void* ws, size_t ws_bytes,
-                                     rdrf_stream_t stream_) {
+static int render_fused(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                        const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near, float far,
+                        float* const want[13], void* ws, size_t ws_bytes, rdrf_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (N == 0) return 0;
-  int rc = render_check(PS, cfg_s, PD, cfg_d, rays, ts, N, S, rgb_map, depth_map, ws_bytes);
+  int rc = render_check(PS, cfg_s, PD, cfg_d, rays, ts, N, S, ws_bytes);
   if (rc) return rc;
   RenderBufs b;
-  rc = carve_render(b, ws, ws_bytes, N, S, rgb_map, depth_map);
+  rc = carve_render(b, ws, ws_bytes, N, S, want);
   if (rc) return rc;
   RenderFusedArgs r;
   memset(&r, 0, sizeof(r));
@@ -222,16 +236,25 @@ extern "C" int rdrf_render_fused_fwd(const RdrfStaticParams* PS, const RdrfField
   RDRF_CHECK(e == hipSuccess, -5, "render_fused: cooperative launch failed: %s", hipGetErrorString(e));
   return 0;
 }
+extern "C" int rdrf_render_fused_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                                     const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near,
+                                     float far, float* rgb_map, float* depth_map, void* ws, size_t ws_bytes,
+                                     rdrf_stream_t stream) {
+  if (N == 0) return 0;
+  RDRF_CHECK(rgb_map && depth_map, -1, "render: bad arguments");
+  float* want[13] = {rgb_map, depth_map};
+  return render_fused(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, want, ws, ws_bytes, stream);
+}
 
 /* launch sequence of the per-phase kernels (whole frames: every kernel fills the chip, nothing to gain from fusion) */
-extern "C" int rdrf_render_sequence_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+static int render_sequence(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
                            const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near,
-                           float far, float* rgb_map, float* depth_map, void* ws, size_t ws_bytes, rdrf_stream_t stream) {
+                           float far, float* const want[13], void* ws, size_t ws_bytes, rdrf_stream_t stream) {
   if (N == 0) return 0;
-  int rc = render_check(PS, cfg_s, PD, cfg_d, rays, ts, N, S, rgb_map, depth_map, ws_bytes);
+  int rc = render_check(PS, cfg_s, PD, cfg_d, rays, ts, N, S, ws_bytes);
   if (rc) return rc;
   RenderBufs b;
-  rc = carve_render(b, ws, ws_bytes, N, S, rgb_map, depth_map);
+  rc = carve_render(b, ws, ws_bytes, N, S, want);
   if (rc) return rc;
   if (cfg_d->ray_type == RDRF_RAY_NDC)
     rc = rdrf_sample_ndc(rays, N, S, near, far, nullptr, cfg_d->aabb, b.xyz, b.z, b.valid, stream);
@@ -250,6 +273,14 @@ extern "C" int rdrf_render_sequence_fwd(const RdrfStaticParams* PS, const RdrfFi
   return rdrf_composite_fwd(b.rgb_s, b.sigma_s, b.rgb_d, b.sigma_d, b.dists_d, b.blending, b.z, rays, N, S,
                             cfg_d->ray_type, 0, nullptr, b.out, stream);
 }
+extern "C" int rdrf_render_sequence_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                           const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near,
+                           float far, float* rgb_map, float* depth_map, void* ws, size_t ws_bytes, rdrf_stream_t stream) {
+  if (N == 0) return 0;
+  RDRF_CHECK(rgb_map && depth_map, -1, "render: bad arguments");
+  float* want[13] = {rgb_map, depth_map};
+  return render_sequence(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, want, ws, ws_bytes, stream);
+}
 
 // Measured on MI355X (tools/render_bench.py, Balloon1 stage-0 shape, 240 x 135 frame): whole frame 7.7 ms either way (the
 // kernels ARE the frame time: their HIP-event sum is 7.9 ms); 512-ray chunks 274 us per chunk as a launch sequence -- the
@@ -262,9 +293,22 @@ extern "C" int rdrf_render_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* c
                                const float* ts, int N, int S, float near, float far, float* rgb_map,
                                float* depth_map, void* ws, size_t ws_bytes, rdrf_stream_t stream) {
   if (N == 0) return 0;   // empty batch: a no-op, like torch ops on empty tensors (their data pointers are null)
-  int rc = render_check(PS, cfg_s, PD, cfg_d, rays, ts, N, S, rgb_map, depth_map, ws_bytes);
-  if (rc) return rc;
   return rdrf_render_sequence_fwd(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, rgb_map, depth_map, ws, ws_bytes, stream);
+}
+
+// The decomposed maps (renderer.py:745-826 keeps rgb / depth of the full, static and dynamic renders and the blending map
+// of every frame): the same launches, the caller's buffers replace the workspace slices of the requested outputs.
+extern "C" int rdrf_render_maps_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                                    const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near,
+                                    float far, int mode, const RdrfRenderMaps* maps, void* ws, size_t ws_bytes,
+                                    rdrf_stream_t stream) {
+  if (N == 0) return 0;
+  RDRF_CHECK(mode == RDRF_RENDER_AUTO || mode == RDRF_RENDER_SEQUENCE || mode == RDRF_RENDER_FUSED, -1,
+             "render_maps: unknown mode %d", mode);
+  float* want[13];
+  maps_to_slots(want, maps);
+  return mode == RDRF_RENDER_FUSED ? render_fused(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, want, ws, ws_bytes, stream)
+                                   : render_sequence(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, want, ws, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -280,12 +324,16 @@ extern "C" int rdrf_render_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* c
 extern "C" size_t rdrf_render_chunks_workspace_bytes(int chunk, int S, int nstreams) {
   return (size_t)(nstreams < 1 ? 1 : nstreams) * ((rdrf_render_workspace_bytes(chunk, S) + 255) & ~(size_t)255);
 }
-extern "C" int rdrf_render_chunks_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
-                                      const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, int chunk,
-                                      float near, float far, float* rgb_map, float* depth_map, void* ws, size_t ws_bytes,
-                                      rdrf_stream_t main_stream_, const rdrf_stream_t* streams, int nstreams) {
+// the requested outputs of the rays from r0 on
+static void offset_slots(float* dst[13], float* const src[13], int r0) {
+  for (int i = 0; i < 13; ++i) dst[i] = src[i] ? src[i] + (size_t)r0 * map_width(i) : nullptr;
+}
+static int render_chunks(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                         const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, int chunk,
+                         float near, float far, float* const want[13], void* ws, size_t ws_bytes,
+                         rdrf_stream_t main_stream_, const rdrf_stream_t* streams, int nstreams) {
   if (N == 0) return 0;
-  RDRF_CHECK(PS && PD && cfg_s && cfg_d && rays && ts && rgb_map && depth_map && ws && chunk > 0 && S > 0, -1,
+  RDRF_CHECK(PS && PD && cfg_s && cfg_d && rays && ts && ws && chunk > 0 && S > 0, -1,
              "render_chunks: bad arguments");
   RDRF_CHECK(PS->packed_fwd != nullptr && PD->packed_fwd != nullptr, -1,
              "render_chunks: both packed weight images are required (rdrf_static_pack / rdrf_dynamic_pack)");
@@ -316,8 +364,10 @@ extern "C" int rdrf_render_chunks_fwd(const RdrfStaticParams* PS, const RdrfFiel
       const int super = g * chunk;
       for (int c0 = 0; c0 < N; c0 += super) {
         const int n = N - c0 < super ? N - c0 : super;
-        const int rc = rdrf_render_sequence_fwd(PS, cfg_s, PD, cfg_d, rays + (size_t)c0 * 6, ts + c0, n, S, near, far,
-                                                rgb_map + (size_t)c0 * 3, depth_map + c0, ws, ws_bytes, main_stream_);
+        float* part[13];
+        offset_slots(part, want, c0);
+        const int rc = render_sequence(PS, cfg_s, PD, cfg_d, rays + (size_t)c0 * 6, ts + c0, n, S, near, far, part, ws,
+                                       ws_bytes, main_stream_);
         if (rc) return rc;
       }
       return 0;
@@ -338,8 +388,10 @@ extern "C" int rdrf_render_chunks_fwd(const RdrfStaticParams* PS, const RdrfFiel
     const int n = N - c0 < chunk ? N - c0 : chunk;
     const int si = k % ns;
     rdrf_stream_t st = nstreams >= 1 ? streams[si] : main_stream_;
-    rc = rdrf_render_sequence_fwd(PS, cfg_s, PD, cfg_d, rays + (size_t)c0 * 6, ts + c0, n, S, near, far, rgb_map + (size_t)c0 * 3,
-                                  depth_map + c0, (char*)ws + slice * si, slice, st);
+    float* part[13];
+    offset_slots(part, want, c0);
+    rc = render_sequence(PS, cfg_s, PD, cfg_d, rays + (size_t)c0 * 6, ts + c0, n, S, near, far, part, (char*)ws + slice * si,
+                         slice, st);
   }
   if (nstreams >= 1) {   // join (also on error: the streams must not run past the caller's buffers unobserved)
     for (int q = 0; q < nstreams; ++q) {
@@ -351,6 +403,26 @@ extern "C" int rdrf_render_chunks_fwd(const RdrfStaticParams* PS, const RdrfFiel
     (void)hipEventDestroy(ev_start);
   }
   return rc;
+}
+extern "C" int rdrf_render_chunks_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                                      const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, int chunk,
+                                      float near, float far, float* rgb_map, float* depth_map, void* ws, size_t ws_bytes,
+                                      rdrf_stream_t main_stream, const rdrf_stream_t* streams, int nstreams) {
+  if (N == 0) return 0;
+  RDRF_CHECK(rgb_map && depth_map, -1, "render_chunks: bad arguments");
+  float* want[13] = {rgb_map, depth_map};
+  return render_chunks(PS, cfg_s, PD, cfg_d, rays, ts, N, S, chunk, near, far, want, ws, ws_bytes, main_stream, streams,
+                       nstreams);
+}
+extern "C" int rdrf_render_chunks_maps_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                                           const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S,
+                                           int chunk, float near, float far, const RdrfRenderMaps* maps, void* ws,
+                                           size_t ws_bytes, rdrf_stream_t main_stream, const rdrf_stream_t* streams,
+                                           int nstreams) {
+  float* want[13];
+  maps_to_slots(want, maps);
+  return render_chunks(PS, cfg_s, PD, cfg_d, rays, ts, N, S, chunk, near, far, want, ws, ws_bytes, main_stream, streams,
+                       nstreams);
 }
 
 // ------------------------------------------------------------------------------------------------

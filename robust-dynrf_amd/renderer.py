@@ -2,10 +2,15 @@
 ``raw2outputs`` and a working ``OctreeRender_trilinear_fast`` chunk loop.  All arithmetic runs in
 the HIP kernels (rdrf_sample_*, rdrf_composite_*); torch only supplies memory, RNG and autograd."""
 import ctypes as C
+from collections import namedtuple
 
 import torch
 
 from . import _lib as L
+
+# the per-ray outputs of raw2outputs (renderer.py:173-315) that the eval loop keeps per frame (renderer.py:745-826):
+# rgb / depth / acc of the full, static (_s) and dynamic (_d) renders and the blending ("dynamicness") map
+RenderMaps = namedtuple("RenderMaps", L.RENDER_MAPS)
 
 
 class _SampleFn(torch.autograd.Function):
@@ -169,20 +174,40 @@ def OctreeRender_trilinear_fast(rays, ts, timeembeddings, tensorf, xyz_sampled, 
     return (r[0], r[1], r[2], r[3], r[4], r[5], None, r[6], r[7], r[8], r[9])
 
 
+def _map_names(maps):
+    """maps=True: all ten; else an iterable of RenderMaps field names (the others are not written)"""
+    names = L.RENDER_MAPS if maps is True else tuple(maps)
+    bad = [n for n in names if n not in L.RENDER_MAPS]
+    if bad or not names:
+        raise ValueError(f"maps: True or a non-empty subset of {L.RENDER_MAPS}, got {maps!r}")
+    return names
+
+
+def _alloc_maps(names, N, dev):
+    return {n: torch.empty((N, 3) if n.startswith("rgb") else (N,), device=dev) for n in names}
+
+
+def _maps_struct(bufs):
+    return L.RenderMapsC(*[bufs[n].data_ptr() if n in bufs else None for n in L.RENDER_MAPS])
+
+
 @torch.no_grad()
-def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc", mode="auto"):
+def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc", mode="auto", maps=False):
     """No-grad render of a ray chunk through ONE C-ABI call: the loop body of renderer.py:740-812.
     mode "auto" (rdrf_render_fwd: the per-phase launch sequence), "fused" (rdrf_render_fused_fwd:
     one cooperative launch) or "sequence" (rdrf_render_sequence_fwd); all three give the same bits.
-    Returns (rgb_map_full[N,3], depth_map_full[N])."""
+    Returns (rgb_map_full[N,3], depth_map_full[N]); with `maps` (True, or a subset of the RenderMaps field names)
+    a RenderMaps of the per-ray outputs ([N,3] rgb maps, [N] others; None where not requested), through
+    rdrf_render_maps_fwd: the same bits as raw2outputs after the fields' forward."""
     from .fields import _attach_packed, _cfg_struct, _dynamic_struct, _static_struct
     L.require_device(rays, ts)
     rays, ts = L.f32c(rays), L.f32c(ts)
     N = rays.shape[0]
     S = int(N_samples) if N_samples and N_samples > 0 else tensorf.nSamples
     dev = rays.device
-    rgb = torch.empty(N, 3, device=dev)
-    depth = torch.empty(N, device=dev)
+    if not maps:
+        rgb = torch.empty(N, 3, device=dev)
+        depth = torch.empty(N, device=dev)
     nbytes = int(L.lib.rdrf_render_workspace_bytes(N, S))
     ws = L.workspace(dev, nbytes)
     ps_list, pd_list = tensorf_static._param_list(), tensorf._param_list()
@@ -191,6 +216,14 @@ def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc",
     _attach_packed(tensorf, PD, pd_list, False, True)
     cs, cd = _cfg_struct(tensorf_static, ray_type), _cfg_struct(tensorf, ray_type)
     near, far = tensorf.near_far
+    if maps:
+        names = _map_names(maps)
+        bufs = _alloc_maps(names, N, dev)
+        M = _maps_struct(bufs)
+        L.check(L.lib.rdrf_render_maps_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S,
+                                           near, far, L.RENDER_MODES[mode], C.byref(M), L.ptr(ws), ws.numel(),
+                                           L.stream_of(rays)), "rdrf_render_maps_fwd")
+        return RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS})
     fn = {"auto": L.lib.rdrf_render_fwd, "fused": L.lib.rdrf_render_fused_fwd, "sequence": L.lib.rdrf_render_sequence_fwd}[mode]
     L.check(fn(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S, C.c_float(near),
                C.c_float(far), L.ptr(rgb), L.ptr(depth), L.ptr(ws), C.c_size_t(ws.numel()), L.stream_of(rays)),
@@ -202,23 +235,28 @@ _stream_pool = {}
 
 
 @torch.no_grad()
-def render_chunks(tensorf_static, tensorf, rays, ts, chunk, N_samples=-1, ray_type="ndc", streams=8):
+def render_chunks(tensorf_static, tensorf, rays, ts, chunk, N_samples=-1, ray_type="ndc", streams=8, maps=False):
     """The chunk loop of renderer.py:740-812 (`for chunk_idx in range(N_rays_all // chunk + ...)`, chunk = 512 at
     renderer.py:732) as ONE native call (rdrf_render_chunks_fwd): the chunks' launch sequences are issued from C,
     round-robin on `streams` HIP streams (0 / 1: all on the current stream).  Issued chunk by chunk from Python the loop
     is host-bound (~250 us of marshalling per chunk against ~190 us of GPU work); and one 512-ray chunk fills only
     64-110 of the 256 CUs, so independent chunks run side by side.  Same bits as render_rays on the whole batch.
-    Returns (rgb_map [N,3], depth_map [N])."""
+    Returns (rgb_map [N,3], depth_map [N]); with `maps`, a RenderMaps as render_rays (rdrf_render_chunks_maps_fwd)."""
     from .fields import _attach_packed, _cfg_struct, _dynamic_struct, _static_struct
     L.require_device(rays, ts)
     rays, ts = L.f32c(rays), L.f32c(ts)
     N, dev = rays.shape[0], rays.device
     S = int(N_samples) if N_samples and N_samples > 0 else tensorf.nSamples
     chunk = int(chunk)
-    rgb = torch.empty(N, 3, device=dev)
-    depth = torch.empty(N, device=dev)
+    if maps:
+        bufs = _alloc_maps(_map_names(maps), N, dev)
+        outs = list(bufs.values())
+    else:
+        rgb = torch.empty(N, 3, device=dev)
+        depth = torch.empty(N, device=dev)
+        outs = [rgb, depth]
     if N == 0:
-        return rgb, depth
+        return RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS}) if maps else (rgb, depth)
     ns = int(streams) if streams and streams > 1 and N > chunk else 0
     ws = L.workspace(dev, int(L.lib.rdrf_render_chunks_workspace_bytes(min(chunk, N), S, max(ns, 1))))
     ps_list, pd_list = tensorf_static._param_list(), tensorf._param_list()
@@ -231,22 +269,62 @@ def render_chunks(tensorf_static, tensorf, rays, ts, chunk, N_samples=-1, ray_ty
     if pool is None:
         pool = _stream_pool[(dev, ns)] = [torch.cuda.Stream(device=dev) for _ in range(ns)]
     arr = (C.c_void_p * max(ns, 1))(*[st.cuda_stream for st in pool]) if ns else None
-    L.check(L.lib.rdrf_render_chunks_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S, chunk,
-                                         C.c_float(near), C.c_float(far), L.ptr(rgb), L.ptr(depth), L.ptr(ws),
-                                         C.c_size_t(ws.numel()), L.stream_of(rays), arr, ns), "rdrf_render_chunks_fwd")
+    if maps:
+        M = _maps_struct(bufs)
+        L.check(L.lib.rdrf_render_chunks_maps_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N,
+                                                  S, chunk, near, far, C.byref(M), L.ptr(ws), ws.numel(), L.stream_of(rays),
+                                                  arr, ns), "rdrf_render_chunks_maps_fwd")
+    else:
+        L.check(L.lib.rdrf_render_chunks_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S,
+                                             chunk, C.c_float(near), C.c_float(far), L.ptr(rgb), L.ptr(depth), L.ptr(ws),
+                                             C.c_size_t(ws.numel()), L.stream_of(rays), arr, ns), "rdrf_render_chunks_fwd")
     for st in pool:   # the caching allocator must not hand these buffers to another stream's request while the side
-        for t in (rays, ts, rgb, depth, ws):   # streams may still read / write them
+        for t in [rays, ts, ws] + outs:   # streams may still read / write them
             t.record_stream(st)
-    return rgb, depth
+    return RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS}) if maps else (rgb, depth)
+
+
+def _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps):
+    """the rays of one H x W image through render_rays in chunks (default: the whole image in one launch sequence)"""
+    dev = rays.device
+    S_ = int(N_samples) if N_samples and N_samples > 0 else tensorf.nSamples
+    if not chunk:   # whole frame in one launch sequence, bounded by the kernels' 32-bit sample indices
+        chunk = max(1, min(H * W, (2 ** 31 - 1) // (3 * S_) - 1))
+    chunk = int(chunk)
+    if not maps:
+        rgb = torch.empty(H * W, 3, device=dev)
+        depth = torch.empty(H * W, device=dev)
+        for c0 in range(0, H * W, chunk):
+            r, d = render_rays(tensorf_static, tensorf, rays[c0:c0 + chunk], ts[c0:c0 + chunk], N_samples, ray_type)
+            rgb[c0:c0 + chunk], depth[c0:c0 + chunk] = r, d
+        return rgb.clamp_(0.0, 1.0).view(H, W, 3), depth.view(H, W)
+    names = _map_names(maps)
+    if chunk >= H * W:
+        out = render_rays(tensorf_static, tensorf, rays, ts, N_samples, ray_type, maps=names)._asdict()
+    else:
+        out = _alloc_maps(names, H * W, dev)
+        for c0 in range(0, H * W, chunk):
+            part = render_rays(tensorf_static, tensorf, rays[c0:c0 + chunk], ts[c0:c0 + chunk], N_samples, ray_type,
+                               maps=names)
+            for n in names:
+                out[n][c0:c0 + chunk] = getattr(part, n)
+    for n in ("rgb", "rgb_s", "rgb_d", "blending"):   # renderer.py:829-832; the depths stay raw
+        if out.get(n) is not None:
+            out[n].clamp_(0.0, 1.0)
+    return RenderMaps(**{n: None if out.get(n) is None else out[n].view(H, W, 3) if n.startswith("rgb") else out[n].view(H, W)
+                         for n in L.RENDER_MAPS})
 
 
 @torch.no_grad()
 def render_frame(tensorf_static, tensorf, poses9, focal, frame, H, W, N_samples=-1, ray_type="ndc",
-                 chunk=None, t=None):
+                 chunk=None, t=None, maps=False):
     """Whole-frame no-grad render (the per-image body of renderer.py:661-966 `evaluation`): rays of
     every pixel of `frame` are generated on the device and pushed through rdrf_render_fwd in chunks
     (default: the whole frame in one launch sequence).  `t` overrides the frame's own time in [-1,1].
-    Returns (rgb [H,W,3] clamped to [0,1], depth [H,W])."""
+    Returns (rgb [H,W,3] clamped to [0,1], depth [H,W]).  With `maps` (True, or a subset of the RenderMaps field names):
+    a RenderMaps of [H,W,3] / [H,W] images, rgb, rgb_s, rgb_d and blending clamped to [0,1] as renderer.py:829-832, the
+    depths raw.  (For contract scenes the reference writes the depths as -1 / (d + 1e-6), renderer.py:862-865: that display
+    transform is the caller's.)"""
     from .ray_utils import generate_rays
     dev = poses9.device
     T = poses9.shape[0]
@@ -254,21 +332,100 @@ def render_frame(tensorf_static, tensorf, poses9, focal, frame, H, W, N_samples=
     rays = generate_rays(ids, poses9, focal, H, W, ndc=ray_type == "ndc", near=1.0)
     tv = (2.0 * frame / max(T - 1, 1) - 1.0) if t is None else float(t)
     ts = torch.full((H * W,), tv, device=dev)
-    S_ = int(N_samples) if N_samples and N_samples > 0 else tensorf.nSamples
-    if not chunk:   # whole frame in one launch sequence, bounded by the kernels' 32-bit sample indices
-        chunk = max(1, min(H * W, (2 ** 31 - 1) // (3 * S_) - 1))
-    chunk = int(chunk)
-    rgb = torch.empty(H * W, 3, device=dev)
-    depth = torch.empty(H * W, device=dev)
-    for c0 in range(0, H * W, chunk):
-        r, d = render_rays(tensorf_static, tensorf, rays[c0:c0 + chunk], ts[c0:c0 + chunk], N_samples, ray_type)
-        rgb[c0:c0 + chunk], depth[c0:c0 + chunk] = r, d
-    return rgb.clamp_(0.0, 1.0).view(H, W, 3), depth.view(H, W)
+    return _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps)
+
+
+def _focal_per_camera(focal, B, dev):
+    f = torch.as_tensor(focal, dtype=torch.float32, device=dev).reshape(-1)
+    if f.numel() == 1:
+        return f.expand(B).contiguous()
+    if f.numel() != B:
+        raise L.RdrfError(f"camera_rays: focal must be a scalar or one value per camera ({B}), got {f.numel()}")
+    return f.contiguous()
+
+
+def camera_rays(c2w, focal, H, W, ndc=True, near=1.0, first=0, n=None):
+    """Rays [n,6] of the flat pixels first .. first + n - 1 over (B, H, W) of the cameras c2w [B,3,4] (or [3,4]), focal a
+    scalar or one per camera: get_ray_directions_blender -> get_rays -> ndc_rays_blender (with `near`) when `ndc`
+    (dataLoader/ray_utils.py:93-110, 143-160, 197-218; the eval rays of renderer.py:702-716, 1013-1030) in one kernel
+    (rdrf_camera_rays).  World rays keep unnormalised directions, as get_rays does.  No gradient (eval is no-grad)."""
+    L.require_device(c2w)
+    dev = c2w.device
+    c2w = L.f32c(c2w.detach().reshape(-1, 3, 4))
+    B = c2w.shape[0]
+    f = _focal_per_camera(focal.detach() if torch.is_tensor(focal) else focal, B, dev)
+    n = B * int(H) * int(W) - int(first) if n is None else int(n)
+    rays = torch.empty(n, 6, device=dev)
+    L.check(L.lib.rdrf_camera_rays(L.ptr(c2w), L.ptr(f), B, int(H), int(W), int(bool(ndc)), float(near), int(first), n,
+                                   L.ptr(rays), L.stream_of(c2w)), "rdrf_camera_rays")
+    return rays
+
+
+@torch.no_grad()
+def render_view(tensorf_static, tensorf, c2w, focal, H, W, t, N_samples=-1, ray_type="ndc", maps=True, chunk=None):
+    """One arbitrary camera c2w [3,4] (host or device; moved to the fields' device) at time t in [-1,1]: the per-view body
+    of renderer.py:970-1263 `evaluation_path` (eval rays: camera_rays, NDC with near = 1 for ndc scenes).  Returns a
+    RenderMaps of [H,W,3] / [H,W] images (clamped as render_frame) with `maps`, else (rgb [H,W,3], depth [H,W])."""
+    if ray_type not in ("ndc", "contract"):
+        raise NotImplementedError("ray_type must be 'ndc' or 'contract' (the shipped configs)")
+    dev = tensorf.aabb.device
+    c2w = torch.as_tensor(c2w, dtype=torch.float32).to(dev)
+    if torch.is_tensor(focal) and focal.device != dev:
+        focal = focal.to(dev)
+    rays = camera_rays(c2w.reshape(1, 3, 4), focal, H, W, ndc=ray_type == "ndc", near=1.0)
+    ts = torch.full((H * W,), float(t), device=dev)
+    return _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps)
+
+
+def path_time(change_time, idx, n):
+    """evaluation_path's time of view idx of n (renderer.py:1034-1043): "change" walks the path's own time axis,
+    round(idx / (n - 1) * (n - 1)) / (n - 1) * 2 - 1 (a one-view path: -1, the first time instance); a number is
+    that time for every view."""
+    if isinstance(change_time, str):
+        if change_time != "change":
+            raise ValueError(f"change_time: 'change' or a time in [-1, 1], got {change_time!r}")
+        return round(idx / (n - 1) * (n - 1)) / (n - 1) * 2.0 - 1.0 if n > 1 else -1.0
+    return float(change_time)
+
+
+def render_path(tensorf_static, tensorf, c2ws, focal, H, W, change_time="change", N_samples=-1, ray_type="ndc",
+                maps=True, chunk=None):
+    """renderer.py:970-1263 `evaluation_path`: yields render_view(c2ws[idx], focal[idx] or focal, path_time(...)) per
+    view, in order.  c2ws [n,3,4] (a tensor, an array or a list of [3,4]); focal a scalar or one per view (render_focal);
+    change_time "change" or a fixed time (path_time).  The image / video writing is the caller's."""
+    n = len(c2ws)
+    per_view = (torch.is_tensor(focal) and focal.numel() > 1) or (not torch.is_tensor(focal) and hasattr(focal, "__len__"))
+    if per_view and len(focal) != n:
+        raise ValueError(f"render_path: {len(focal)} focal values for {n} views")
+    for idx in range(n):
+        yield render_view(tensorf_static, tensorf, c2ws[idx], focal[idx] if per_view else focal, H, W,
+                          path_time(change_time, idx, n), N_samples, ray_type, maps, chunk)
 
 
 def psnr(img, ref):
     """-10 log10(mse) on the device (renderer.py:905-906 computes it per image on the host)."""
     return -10.0 * torch.log10(((img - ref) ** 2).mean())
+
+
+def ssim(img, ref, max_val=1.0, return_map=False):
+    """utils.py:98-151 rgb_ssim with its defaults (11-tap Gaussian, sigma 1.5, k1 0.01, k2 0.03) on the device
+    (rdrf_ssim; the reference runs scipy on the host per image): img, ref [H,W,C] device tensors, H, W >= 11.  Moments,
+    map and mean in fp64 (the products of the pixels included).  Returns the mean as a 0-d fp64 tensor, or with
+    `return_map` the map [H-10,W-10,C] (fp32), as rgb_ssim does."""
+    L.require_device(img, ref)
+    if img.dim() != 3 or img.shape != ref.shape:
+        raise L.RdrfError(f"ssim: img and ref must be [H,W,C] of one shape, got {tuple(img.shape)} and {tuple(ref.shape)}")
+    H, W, Cc = img.shape
+    if H < 11 or W < 11 or Cc < 1:
+        raise L.RdrfError(f"ssim: the images ({H} x {W}) must be at least 11 x 11 (valid 11-tap filter)")
+    img, ref = L.f32c(img), L.f32c(ref)
+    dev = img.device
+    mean = torch.empty((), dtype=torch.float64, device=dev)
+    smap = torch.empty(H - 10, W - 10, Cc, device=dev) if return_map else None
+    ws = L.workspace(dev, int(L.lib.rdrf_ssim_workspace_bytes(H, W, Cc)))
+    L.check(L.lib.rdrf_ssim(L.ptr(img), L.ptr(ref), H, W, Cc, float(max_val), L.ptr(mean), L.ptr(smap), L.ptr(ws), ws.numel(),
+                            L.stream_of(img)), "rdrf_ssim")
+    return smap if return_map else mean
 
 
 # --------------------------------------------------------------------------------------------
