@@ -481,6 +481,42 @@ int rdrf_render_chunks_maps_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* 
                                 float near, float far, const RdrfRenderMaps* maps, void* ws, size_t ws_bytes,
                                 rdrf_stream_t main_stream, const rdrf_stream_t* streams, int nstreams);
 
+/* ---- motion maps of the no-grad render (the per-frame `render` of renderer.py:319-657 keeps, beside the maps above, four
+ * induced optical-flow maps and the warp displacement of every frame) --------------------------------------------------
+ * One nullable DEVICE pointer per map; NULL = not wanted, not computed (the scene-flow MLP runs only if flow_f or flow_b
+ * is wanted).  Every map is reduced in a fixed order that depends on S alone: the same bits run after run, for any
+ * chunking of the image, for any subset of requested maps, in every render mode and in the deterministic build. */
+typedef struct RdrfMotionMaps {
+  float* flow_f;     /* [N][2] induced flow to the next frame through scene_flow_f   (renderer.py:493-503) */
+  float* flow_b;     /* [N][2] ... to the previous frame through scene_flow_b        (:504-514) */
+  float* flow_s_f;   /* [N][2] static field, camera motion only, next frame          (:516-526) */
+  float* flow_s_b;   /* [N][2] ... previous frame                                    (:527-537) */
+  float* delta_xyz;  /* [N][3] sum_s weights_d (xyz_prime - xyz), raw               (:460, :610) */
+} RdrfMotionMaps;
+typedef struct RdrfMotionCams {
+  int H, W;
+  const float* focal;     /* DEVICE, one float (as rdrf_induce_flow_fwd) */
+  const float* c2w_f;     /* DEVICE [3][4]: pose of the next frame, one for all rays */
+  const float* c2w_b;     /* DEVICE [3][4]: pose of the previous frame */
+  int64_t first_pixel;    /* ray k is flat pixel first_pixel + k of the H x W image: pts_2d = (p % W, p / W % H), the
+                             reference's integer meshgrid (renderer.py:372-375) */
+} RdrfMotionCams;
+/* rdrf_render_maps_fwd (same `mode`, same bits in every requested RdrfRenderMaps entry; `maps` may be NULL), then the
+ * motion kernel on the same workspace and stream.  A barrier time-out of the fused form sets the motion maps to NaN as
+ * well.  ws: rdrf_render_motion_workspace_bytes(N, S) (>= rdrf_render_workspace_bytes(N, S)). */
+size_t rdrf_render_motion_workspace_bytes(int N, int S);
+int rdrf_render_motion_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                           const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near, float far,
+                           int mode, const RdrfRenderMaps* maps, const RdrfMotionCams* cams, const RdrfMotionMaps* motion,
+                           void* ws, size_t ws_bytes, rdrf_stream_t stream);
+
+/* ---- flow_viz.flow_to_image with its defaults (flow_viz.py:107-136: no clip, RGB; the Middlebury colour wheel) --------
+ * flow [H][W][2] fp32 -> rgb [H][W][3] uint8, both on the DEVICE; the flow is not modified.  +-inf entries count as 0,
+ * a NaN entry makes the radius maximum NaN and with it every pixel white, as in numpy.  numpy's precision sequence: fp32
+ * up to the wheel position, fp64 for the colour mix.  ws: rdrf_flow_to_image_workspace_bytes(H, W). */
+size_t rdrf_flow_to_image_workspace_bytes(int H, int W);
+int rdrf_flow_to_image(const float* flow, int H, int W, uint8_t* rgb, void* ws, size_t ws_bytes, rdrf_stream_t stream);
+
 /* ---- rays of arbitrary cameras (evaluation_path, renderer.py:1013-1030; evaluation, :702-716) -----------------------
  * c2w[B][3][4] camera-to-world matrices, focal[B] per camera.  Ray k is flat pixel first + k over (B, H, W):
  * get_ray_directions_blender (pixel centre + 0.5, centre (W/2, H/2), focal on both axes, dataLoader/ray_utils.py:93-110),

@@ -16,13 +16,13 @@ from .fields import TensorVMSplit, TensorVMSplit_TimeEmbedding, TensorBase
 from .renderer import (sampleXYZ, raw2outputs, OctreeRender_trilinear_fast, sample_rays, render_rays, render_chunks,
                        induce_flow, induce_flow_single, render_3d_point, render_single_3d_point,
                        eff_distloss, flatten_eff_distloss, render_frame, psnr, RenderMaps, camera_rays, render_view,
-                       render_path, path_time, ssim)
+                       render_path, path_time, ssim, MotionMaps, flow_to_image, delta_xyz_image)
 from .ray_utils import generate_rays, ids2pixel, pose_to_mtx
 from .regularizers import TVLoss
 from .losses import LossTerms
 from ._lib import RdrfError
 
-__all__ = ["render_frame", "psnr", "RenderMaps", "camera_rays", "render_view", "render_path", "path_time", "ssim", "TVLoss", "pose_to_mtx", "eff_distloss", "flatten_eff_distloss", "induce_flow", "induce_flow_single", "render_3d_point", "render_single_3d_point",
+__all__ = ["MotionMaps", "flow_to_image", "delta_xyz_image", "render_frame", "psnr", "RenderMaps", "camera_rays", "render_view", "render_path", "path_time", "ssim", "TVLoss", "pose_to_mtx", "eff_distloss", "flatten_eff_distloss", "induce_flow", "induce_flow_single", "render_3d_point", "render_single_3d_point",
            "TensorVMSplit", "TensorVMSplit_TimeEmbedding", "TensorBase", "sampleXYZ", "raw2outputs",
            "OctreeRender_trilinear_fast", "sample_rays", "render_rays", "render_chunks", "generate_rays", "ids2pixel", "LossTerms",
            "RdrfError"]

@@ -62,6 +62,18 @@ class RenderMapsC(C.Structure):
 
 RENDER_MODES = {"auto": 0, "sequence": 1, "fused": 2}
 
+# RdrfMotionMaps / RdrfMotionCams (include/rodynrf.h): the motion maps of the no-grad render and the cameras they project into
+MOTION_MAPS = ("flow_f", "flow_b", "flow_s_f", "flow_s_b", "delta_xyz")
+
+
+class MotionMapsC(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in MOTION_MAPS]
+
+
+class MotionCamsC(C.Structure):
+    _fields_ = [("H", C.c_int), ("W", C.c_int), ("focal", C.c_void_p), ("c2w_f", C.c_void_p), ("c2w_b", C.c_void_p),
+                ("first_pixel", C.c_int64)]
+
 
 def _load():
     if not os.path.exists(LIB_PATH):
@@ -111,6 +123,14 @@ def _load():
     lib.rdrf_render_chunks_maps_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(RenderMapsC),
                                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
+    lib.rdrf_render_motion_workspace_bytes.restype = C.c_size_t
+    lib.rdrf_render_motion_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.rdrf_render_motion_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                           C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(RenderMapsC),
+                                           C.POINTER(MotionCamsC), C.POINTER(MotionMapsC), C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.rdrf_flow_to_image_workspace_bytes.restype = C.c_size_t
+    lib.rdrf_flow_to_image_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.rdrf_flow_to_image.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.rdrf_camera_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int64,
                                      C.c_int, C.c_void_p, C.c_void_p]
     lib.rdrf_ssim_workspace_bytes.restype = C.c_size_t
@@ -145,6 +165,7 @@ SYMBOLS = [
     "rdrf_frame_depth_loss_workspace_bytes", "rdrf_frame_depth_loss_fwd", "rdrf_frame_depth_loss_bwd",
     "rdrf_render_workspace_bytes", "rdrf_render_fwd", "rdrf_render_chunks_workspace_bytes", "rdrf_render_chunks_fwd",
     "rdrf_render_maps_fwd", "rdrf_render_chunks_maps_fwd", "rdrf_camera_rays", "rdrf_ssim_workspace_bytes", "rdrf_ssim",
+    "rdrf_render_motion_workspace_bytes", "rdrf_render_motion_fwd", "rdrf_flow_to_image_workspace_bytes", "rdrf_flow_to_image",
     "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_prof_reset",
     "rdrf_prof_enable", "rdrf_prof_get",
 ]

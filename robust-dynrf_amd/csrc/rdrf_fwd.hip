@@ -56,34 +56,6 @@ __global__ __launch_bounds__(512) void k_ray_scan(FieldArgs a) { ray_scan_body(a
 // ------------------------------------------------------------------------------------------------
 // scene flow MLP over all N*S samples (models/tensoRF.py:446-462)
 // ------------------------------------------------------------------------------------------------
-RDRF_D void fill_sf_x(float (&X)[20], float xn0, float xn1, float xn2, float t, int h) {
-#pragma unroll
-  for (int o = 0; o < 5; ++o) {
-    if (o == 0 && h == 0) {
-      X[0] = xn0; X[1] = xn1; X[2] = xn2; X[3] = t;
-    } else {
-      const int k = 2 * o + h - 1;
-      // (exact sin / cos for every octave here: the scene-flow losses are L1 terms, and with the doubled-angle form of
-      // rdrf_common.hpp sincos_double one sign flip of a ~0 flow component moved the nvidia_late reference-trainer
-      // comparison by 8e-4 of a gradient's max -- the kernel is 0.15 ms of the step, the 60 VALU instructions stay)
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const int pr = 2 * k + p;
-        float sv = 0.f, cv = 0.f;
-        if (pr < 16) {
-          const int d = pr >> 2, f = pr & 3;
-          const float x = pr < 12 ? (d == 0 ? xn0 : (d == 1 ? xn1 : xn2)) : t;
-          const float a_ = ldexpf(x, f);
-          if (__builtin_expect(!(fabsf(a_) <= RDRF_PE_FAST_MAX), 0)) sincosf(a_, &sv, &cv);
-          else sincos_sel<true>(a_, sv, cv);
-        }
-        X[o * 4 + 2 * p] = sv;
-        X[o * 4 + 2 * p + 1] = cv;
-      }
-    }
-  }
-}
-
 __global__ __launch_bounds__(64 * RDRF_MAXW) void k_scene_flow(const float* __restrict__ pts,
                                                    const float* __restrict__ ts, int N, int S,
                                                    Box box, const float* __restrict__ pkg, DynW w,

@@ -199,4 +199,67 @@ RDRF_D void composite_body(const CompArgs a, const GridCtx gc) {
   }  // ray loop
 }
 
-
+// ------------------------------------------------------------------------------------------------
+// per-ray tail of render_3d_point + induce_flow (renderer.py:1328-1392): far-point fill, NDC2world / contract2world,
+// projection into the neighbour camera.  Shared by k_induce_flow / k_induce_flow_bwd (rdrf_misc.hip) and k_motion_maps
+// (rdrf_motion.hip).
+// ------------------------------------------------------------------------------------------------
+struct FlowRay {
+  float far[3], P[3], world[3], q[3], cam[3];
+  float acc, c, pz;            // NDC: clamped P.z and 2/(c-1)
+  float fn, fs; int fk;        // contract far point: norm, scale g(n), arg-max component (fk<0: inside)
+  float wn, wsc; int wk;       // contract2world: norm, scale s(m), arg-max (wk<0: identity)
+};
+RDRF_D int argmax_abs3(const float (&v)[3], float& n) {
+  int k = 0;
+  n = fabsf(v[0]);
+  if (fabsf(v[1]) > n) { n = fabsf(v[1]); k = 1; }
+  if (fabsf(v[2]) > n) { n = fabsf(v[2]); k = 2; }
+  return k;
+}
+RDRF_D void flow_ray_fwd(FlowRay& r, const float* ray, const float* c2w, float acc, const float (&ps)[3],
+                         int H, int W, float f, int ray_type, float& u, float& v, float& disp) {
+#pragma clang fp contract(off)
+  r.acc = acc;
+  if (ray_type == RDRF_RAY_NDC) {
+    for (int i = 0; i < 3; ++i) r.far[i] = ray[i] + ray[3 + i];
+    r.fk = -1;
+  } else {
+    float f0[3];
+    for (int i = 0; i < 3; ++i) f0[i] = ray[i] + ray[3 + i] * 256.0f;
+    const int k = argmax_abs3(f0, r.fn);
+    if (r.fn > 1.0f) {
+      r.fk = k;
+      r.fs = (2.0f - 1.0f / r.fn);
+      for (int i = 0; i < 3; ++i) r.far[i] = r.fs * (f0[i] / r.fn);
+    } else {
+      r.fk = -1;
+      for (int i = 0; i < 3; ++i) r.far[i] = f0[i];
+    }
+  }
+  for (int i = 0; i < 3; ++i) r.P[i] = ps[i] + (1.0f - acc) * r.far[i];
+  if (ray_type == RDRF_RAY_NDC) {
+    r.c = fminf(fmaxf(r.P[2], -1.0f), 1.0f - 1e-6f);
+    r.pz = 2.0f / (r.c - 1.0f);
+    r.world[0] = -r.P[0] * r.pz * (float)W / 2.0f / f;
+    r.world[1] = -r.P[1] * r.pz * (float)H / 2.0f / f;
+    r.world[2] = r.pz;
+    r.wk = -1;
+  } else {
+    const int k = argmax_abs3(r.P, r.wn);
+    if (r.wn > 1.0f) {
+      r.wk = k;
+      r.wsc = -1.0f / (r.wn - 2.0f);
+      for (int i = 0; i < 3; ++i) r.world[i] = r.P[i] / r.wn * r.wsc;
+    } else {
+      r.wk = -1;
+      for (int i = 0; i < 3; ++i) r.world[i] = r.P[i];
+    }
+  }
+  for (int j = 0; j < 3; ++j) r.q[j] = r.world[j] - c2w[j * 4 + 3];
+  for (int i = 0; i < 3; ++i)   // cam_i = sum_j q_j R[j][i]  (w2c = R^T)
+    r.cam[i] = r.q[0] * c2w[0 * 4 + i] + r.q[1] * c2w[1 * 4 + i] + r.q[2] * c2w[2 * 4 + i];
+  u = r.cam[0] / (-r.cam[2]) * f + (float)W * 0.5f;
+  v = -r.cam[1] / (-r.cam[2]) * f + (float)H * 0.5f;
+  disp = 1.0f + 2.0f / r.cam[2];
+}

@@ -311,6 +311,19 @@ extern "C" int rdrf_render_maps_fwd(const RdrfStaticParams* PS, const RdrfFieldC
                                    : render_sequence(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, want, ws, ws_bytes, stream);
 }
 
+// where a render with these `maps` left what the motion maps read (rdrf_motion.hip): the carve of the render itself
+int render_motion_views(const RdrfRenderMaps* maps, void* ws, size_t ws_bytes, int N, int S, const float** xyz,
+                        const float** xyz_prime, const float** weights_s, const float** weights_d, const unsigned** barrier,
+                        void** fws_d) {
+  float* want[13];
+  maps_to_slots(want, maps);
+  RenderBufs b;
+  const int rc = carve_render(b, ws, ws_bytes, N, S, want);
+  if (rc) return rc;
+  *xyz = b.xyz; *xyz_prime = b.xyz_prime; *weights_s = b.out[7]; *weights_d = b.out[11]; *barrier = b.barrier; *fws_d = b.fws_d;
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------
 // The reference's eval loop (renderer.py:740-812: `for chunk_idx in range(N_rays_all // chunk + ...)`, chunk = 512,
 // renderer.py:732) as ONE native call: the chunks' launch sequences are issued round-robin on `nstreams` caller streams.

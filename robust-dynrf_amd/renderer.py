@@ -11,6 +11,10 @@ from . import _lib as L
 # the per-ray outputs of raw2outputs (renderer.py:173-315) that the eval loop keeps per frame (renderer.py:745-826):
 # rgb / depth / acc of the full, static (_s) and dynamic (_d) renders and the blending ("dynamicness") map
 RenderMaps = namedtuple("RenderMaps", L.RENDER_MAPS)
+# the motion maps of the per-frame render (renderer.py:487-537, :610): induced optical flow to the next / previous frame
+# through the scene-flow MLP (flow_f, flow_b) and through camera motion alone (flow_s_f, flow_s_b), [N,2] pixels, and the
+# warp displacement sum_s weights_d (xyz_prime - xyz) [N,3]
+MotionMaps = namedtuple("MotionMaps", L.MOTION_MAPS)
 
 
 class _SampleFn(torch.autograd.Function):
@@ -191,14 +195,43 @@ def _maps_struct(bufs):
     return L.RenderMapsC(*[bufs[n].data_ptr() if n in bufs else None for n in L.RENDER_MAPS])
 
 
+def _motion_names(want):
+    """True: all five; else an iterable of MotionMaps field names (the others are not computed)"""
+    names = L.MOTION_MAPS if want is True else tuple(want)
+    bad = [n for n in names if n not in L.MOTION_MAPS]
+    if bad or not names:
+        raise ValueError(f"motion maps: True or a non-empty subset of {L.MOTION_MAPS}, got {want!r}")
+    return names
+
+
+def _motion_request(motion, N, dev):
+    """motion: dict of H, W, focal, c2w_f, c2w_b [3,4], first_pixel (default 0) and maps (default True: all five).
+    Returns (output buffers by name, RdrfMotionMaps, RdrfMotionCams, tensors the structs point into)."""
+    names = _motion_names(motion.get("maps", True))
+    bufs = {n: torch.empty((N, 3) if n == "delta_xyz" else (N, 2), device=dev) for n in names}
+    focal = motion["focal"]
+    focal = _focal_tensor(focal.to(dev) if torch.is_tensor(focal) else focal, dev).contiguous()
+    pose = [L.f32c(torch.as_tensor(motion[k], dtype=torch.float32).detach().to(dev)) for k in ("c2w_f", "c2w_b")]
+    if any(p_.shape != (3, 4) for p_ in pose):
+        raise L.RdrfError("motion: c2w_f and c2w_b are [3,4] camera-to-world matrices")
+    cams = L.MotionCamsC(int(motion["H"]), int(motion["W"]), focal.data_ptr(), pose[0].data_ptr(), pose[1].data_ptr(),
+                         int(motion.get("first_pixel", 0)))
+    mm = L.MotionMapsC(*[bufs[n].data_ptr() if n in bufs else None for n in L.MOTION_MAPS])
+    return bufs, mm, cams, (focal, pose)
+
+
 @torch.no_grad()
-def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc", mode="auto", maps=False):
+def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc", mode="auto", maps=False, motion=None):
     """No-grad render of a ray chunk through ONE C-ABI call: the loop body of renderer.py:740-812.
     mode "auto" (rdrf_render_fwd: the per-phase launch sequence), "fused" (rdrf_render_fused_fwd:
     one cooperative launch) or "sequence" (rdrf_render_sequence_fwd); all three give the same bits.
     Returns (rgb_map_full[N,3], depth_map_full[N]); with `maps` (True, or a subset of the RenderMaps field names)
     a RenderMaps of the per-ray outputs ([N,3] rgb maps, [N] others; None where not requested), through
-    rdrf_render_maps_fwd: the same bits as raw2outputs after the fields' forward."""
+    rdrf_render_maps_fwd: the same bits as raw2outputs after the fields' forward.
+    With `motion` (a dict: H, W, focal, c2w_f, c2w_b -- the [3,4] poses of the next / previous frame --, first_pixel = flat
+    pixel of ray 0 in the H x W image (default 0), maps = True or a subset of the MotionMaps field names) the call goes
+    through rdrf_render_motion_fwd and returns (the above, MotionMaps): the induced-flow and warp-displacement maps of
+    renderer.py:487-537, :610 from the render's own workspace, the colour maps bit for bit as without `motion`."""
     from .fields import _attach_packed, _cfg_struct, _dynamic_struct, _static_struct
     L.require_device(rays, ts)
     rays, ts = L.f32c(rays), L.f32c(ts)
@@ -208,7 +241,7 @@ def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc",
     if not maps:
         rgb = torch.empty(N, 3, device=dev)
         depth = torch.empty(N, device=dev)
-    nbytes = int(L.lib.rdrf_render_workspace_bytes(N, S))
+    nbytes = int(L.lib.rdrf_render_motion_workspace_bytes(N, S) if motion is not None else L.lib.rdrf_render_workspace_bytes(N, S))
     ws = L.workspace(dev, nbytes)
     ps_list, pd_list = tensorf_static._param_list(), tensorf._param_list()
     PS, PD = _static_struct(ps_list), _dynamic_struct(pd_list)
@@ -216,6 +249,18 @@ def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc",
     _attach_packed(tensorf, PD, pd_list, False, True)
     cs, cd = _cfg_struct(tensorf_static, ray_type), _cfg_struct(tensorf, ray_type)
     near, far = tensorf.near_far
+    if motion is not None:
+        if ray_type not in L.RAY_TYPES:
+            raise NotImplementedError("ray_type must be 'ndc' or 'contract' (the shipped configs)")
+        bufs = _alloc_maps(_map_names(maps), N, dev) if maps else {"rgb": rgb, "depth": depth}
+        M = _maps_struct(bufs)
+        mbufs, MM, cams, keep = _motion_request(motion, N, dev)
+        L.check(L.lib.rdrf_render_motion_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S,
+                                             near, far, L.RENDER_MODES[mode], C.byref(M), C.byref(cams), C.byref(MM),
+                                             L.ptr(ws), ws.numel(), L.stream_of(rays)), "rdrf_render_motion_fwd")
+        del keep
+        out = RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS}) if maps else (rgb, depth)
+        return out, MotionMaps(**{n: mbufs.get(n) for n in L.MOTION_MAPS})
     if maps:
         names = _map_names(maps)
         bufs = _alloc_maps(names, N, dev)
@@ -284,55 +329,81 @@ def render_chunks(tensorf_static, tensorf, rays, ts, chunk, N_samples=-1, ray_ty
     return RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS}) if maps else (rgb, depth)
 
 
-def _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps):
-    """the rays of one H x W image through render_rays in chunks (default: the whole image in one launch sequence)"""
+def _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps, motion=None):
+    """the rays of one H x W image through render_rays in chunks (default: the whole image in one launch sequence);
+    `motion`: the dict of render_rays without first_pixel (every chunk passes its own) -> (images, MotionMaps of images)"""
     dev = rays.device
     S_ = int(N_samples) if N_samples and N_samples > 0 else tensorf.nSamples
     if not chunk:   # whole frame in one launch sequence, bounded by the kernels' 32-bit sample indices
         chunk = max(1, min(H * W, (2 ** 31 - 1) // (3 * S_) - 1))
     chunk = int(chunk)
+    mout = None
+    if motion is not None:
+        mnames = _motion_names(motion.get("maps", True))
+        mout = {n: torch.empty((H * W, 3) if n == "delta_xyz" else (H * W, 2), device=dev) for n in mnames}
+
+    def run(c0, want):
+        if motion is None:
+            return render_rays(tensorf_static, tensorf, rays[c0:c0 + chunk], ts[c0:c0 + chunk], N_samples, ray_type, maps=want)
+        part, mpart = render_rays(tensorf_static, tensorf, rays[c0:c0 + chunk], ts[c0:c0 + chunk], N_samples, ray_type,
+                                  maps=want, motion=dict(motion, first_pixel=c0))
+        for n in mout:
+            mout[n][c0:c0 + chunk] = getattr(mpart, n)
+        return part
+
+    def finish(images):
+        if motion is None:
+            return images
+        return images, MotionMaps(**{n: None if n not in mout else mout[n].view(H, W, -1) for n in L.MOTION_MAPS})
+
     if not maps:
         rgb = torch.empty(H * W, 3, device=dev)
         depth = torch.empty(H * W, device=dev)
         for c0 in range(0, H * W, chunk):
-            r, d = render_rays(tensorf_static, tensorf, rays[c0:c0 + chunk], ts[c0:c0 + chunk], N_samples, ray_type)
+            r, d = run(c0, False)
             rgb[c0:c0 + chunk], depth[c0:c0 + chunk] = r, d
-        return rgb.clamp_(0.0, 1.0).view(H, W, 3), depth.view(H, W)
+        return finish((rgb.clamp_(0.0, 1.0).view(H, W, 3), depth.view(H, W)))
     names = _map_names(maps)
     if chunk >= H * W:
-        out = render_rays(tensorf_static, tensorf, rays, ts, N_samples, ray_type, maps=names)._asdict()
+        out = run(0, names)._asdict()
     else:
         out = _alloc_maps(names, H * W, dev)
         for c0 in range(0, H * W, chunk):
-            part = render_rays(tensorf_static, tensorf, rays[c0:c0 + chunk], ts[c0:c0 + chunk], N_samples, ray_type,
-                               maps=names)
+            part = run(c0, names)
             for n in names:
                 out[n][c0:c0 + chunk] = getattr(part, n)
     for n in ("rgb", "rgb_s", "rgb_d", "blending"):   # renderer.py:829-832; the depths stay raw
         if out.get(n) is not None:
             out[n].clamp_(0.0, 1.0)
-    return RenderMaps(**{n: None if out.get(n) is None else out[n].view(H, W, 3) if n.startswith("rgb") else out[n].view(H, W)
-                         for n in L.RENDER_MAPS})
+    return finish(RenderMaps(**{n: None if out.get(n) is None else out[n].view(H, W, 3) if n.startswith("rgb") else out[n].view(H, W)
+                                for n in L.RENDER_MAPS}))
 
 
 @torch.no_grad()
 def render_frame(tensorf_static, tensorf, poses9, focal, frame, H, W, N_samples=-1, ray_type="ndc",
-                 chunk=None, t=None, maps=False):
+                 chunk=None, t=None, maps=False, motion=False):
     """Whole-frame no-grad render (the per-image body of renderer.py:661-966 `evaluation`): rays of
     every pixel of `frame` are generated on the device and pushed through rdrf_render_fwd in chunks
     (default: the whole frame in one launch sequence).  `t` overrides the frame's own time in [-1,1].
     Returns (rgb [H,W,3] clamped to [0,1], depth [H,W]).  With `maps` (True, or a subset of the RenderMaps field names):
     a RenderMaps of [H,W,3] / [H,W] images, rgb, rgb_s, rgb_d and blending clamped to [0,1] as renderer.py:829-832, the
     depths raw.  (For contract scenes the reference writes the depths as -1 / (d + 1e-6), renderer.py:862-865: that display
-    transform is the caller's.)"""
-    from .ray_utils import generate_rays
+    transform is the caller's.)
+    With `motion` (True, or a subset of the MotionMaps field names): returns (the above, MotionMaps) with the flows as
+    [H,W,2] and delta_xyz as [H,W,3]; the neighbour cameras are the reference's, frames min(frame + 1, T - 1) and
+    max(frame - 1, 0) of `poses9` (renderer.py:386-387)."""
+    from .ray_utils import generate_rays, pose_to_mtx
     dev = poses9.device
     T = poses9.shape[0]
     ids = torch.arange(H * W, device=dev) + int(frame) * H * W
     rays = generate_rays(ids, poses9, focal, H, W, ndc=ray_type == "ndc", near=1.0)
     tv = (2.0 * frame / max(T - 1, 1) - 1.0) if t is None else float(t)
     ts = torch.full((H * W,), tv, device=dev)
-    return _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps)
+    req = None
+    if motion:
+        mtx = pose_to_mtx(poses9.detach().float())
+        req = dict(H=H, W=W, focal=focal, c2w_f=mtx[min(int(frame) + 1, T - 1)], c2w_b=mtx[max(int(frame) - 1, 0)], maps=motion)
+    return _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps, req)
 
 
 def _focal_per_camera(focal, B, dev):
@@ -362,10 +433,13 @@ def camera_rays(c2w, focal, H, W, ndc=True, near=1.0, first=0, n=None):
 
 
 @torch.no_grad()
-def render_view(tensorf_static, tensorf, c2w, focal, H, W, t, N_samples=-1, ray_type="ndc", maps=True, chunk=None):
+def render_view(tensorf_static, tensorf, c2w, focal, H, W, t, N_samples=-1, ray_type="ndc", maps=True, chunk=None,
+                c2w_f=None, c2w_b=None, motion=False):
     """One arbitrary camera c2w [3,4] (host or device; moved to the fields' device) at time t in [-1,1]: the per-view body
     of renderer.py:970-1263 `evaluation_path` (eval rays: camera_rays, NDC with near = 1 for ndc scenes).  Returns a
-    RenderMaps of [H,W,3] / [H,W] images (clamped as render_frame) with `maps`, else (rgb [H,W,3], depth [H,W])."""
+    RenderMaps of [H,W,3] / [H,W] images (clamped as render_frame) with `maps`, else (rgb [H,W,3], depth [H,W]).
+    With `motion` (True, or a subset of the MotionMaps field names) and the neighbour cameras c2w_f / c2w_b [3,4] (default:
+    the view's own camera): returns (the above, MotionMaps of [H,W,2] / [H,W,3] images) as render_frame."""
     if ray_type not in ("ndc", "contract"):
         raise NotImplementedError("ray_type must be 'ndc' or 'contract' (the shipped configs)")
     dev = tensorf.aabb.device
@@ -374,7 +448,34 @@ def render_view(tensorf_static, tensorf, c2w, focal, H, W, t, N_samples=-1, ray_
         focal = focal.to(dev)
     rays = camera_rays(c2w.reshape(1, 3, 4), focal, H, W, ndc=ray_type == "ndc", near=1.0)
     ts = torch.full((H * W,), float(t), device=dev)
-    return _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps)
+    req = None
+    if motion:
+        own = c2w.reshape(3, 4)
+        req = dict(H=H, W=W, focal=focal, c2w_f=own if c2w_f is None else c2w_f, c2w_b=own if c2w_b is None else c2w_b,
+                   maps=motion)
+    return _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps, req)
+
+
+def flow_to_image(flow):
+    """flow_viz.flow_to_image with its defaults (flow_viz.py:107-136) on the device (rdrf_flow_to_image): flow [H,W,2] ->
+    uint8 [H,W,3] RGB of the Middlebury colour wheel, in numpy's precision sequence.  The input is not modified."""
+    L.require_device(flow)
+    if flow.dim() != 3 or flow.shape[2] != 2:
+        raise L.RdrfError(f"flow_to_image: flow must be [H,W,2], got {tuple(flow.shape)}")
+    flow = L.f32c(flow.detach())
+    H, W, _ = flow.shape
+    rgb = torch.empty(H, W, 3, dtype=torch.uint8, device=flow.device)
+    if H * W == 0:
+        return rgb
+    ws = L.workspace(flow.device, int(L.lib.rdrf_flow_to_image_workspace_bytes(H, W)))
+    L.check(L.lib.rdrf_flow_to_image(L.ptr(flow), H, W, L.ptr(rgb), L.ptr(ws), ws.numel(), L.stream_of(flow)),
+            "rdrf_flow_to_image")
+    return rgb
+
+
+def delta_xyz_image(delta_xyz):
+    """renderer.py:611-613: the warp-displacement map as a picture, (d / max|d| + 1) / 2"""
+    return (delta_xyz / torch.max(torch.abs(delta_xyz)) + 1.0) / 2.0
 
 
 def path_time(change_time, idx, n):
