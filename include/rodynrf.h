@@ -559,6 +559,27 @@ int rdrf_det_finish(int slot, rdrf_stream_t stream);
 int rdrf_selftest_mlp(const float* x, const float* w, const float* b, int M, int K, int OUT,
                       float* y, void* ws, size_t ws_bytes, rdrf_stream_t stream);
 
+/* Every MLP layer primitive on its own, with the template arguments of the product kernels and the product's pack code; the
+ * raw accumulators are returned (no bias, no relu).  w[OUT][K] is a torch.nn.Linear weight.  Forward forms: x[M][K] ->
+ * y[M][OUT] = x w^T.  Transposed forms (_T, the backward-data product): x[M][OUT] -> y[M][K] = x w.  Instantiated (K, OUT):
+ *   F32        fp32 MFMA, pack mode 0            (64, 64) (128, 128) (72, 32)
+ *   F32_T      fp32 MFMA, mode 2                 (64, 64) (32, 128)
+ *   B3         bf16 x 3, mode 7                  (144, 64): the heads' first layer, three segments in one image; (64, 64)
+ *   B3_T       bf16 x 3, mode 8                  (64, 64)
+ *   B3_PAIR_T  two images, one input, mode 8     (160, 64): y = 96 columns of image A, 64 of B; (96, 64): 64 + 32
+ *   B3S        split storage, mode 9, as chains  (112, 128): 16 | 32 | 8 slots (dynamic appearance); (160, 128): 16 | 64 (static)
+ *   B3S_T      split storage, mode 10            (224, 32) (96, 32) (128, 128) (96, 128) (160, 128)
+ * Any other (form, K, OUT) returns -1.  M = 0 is a no-op.  ws: 16-byte aligned scratch, 128 KiB suffice for every form. */
+#define RDRF_ST_F32 0
+#define RDRF_ST_F32_T 1
+#define RDRF_ST_B3 2
+#define RDRF_ST_B3_T 3
+#define RDRF_ST_B3_PAIR_T 4
+#define RDRF_ST_B3S 5
+#define RDRF_ST_B3S_T 6
+int rdrf_selftest_layer(int form, const float* x, const float* w, int M, int K, int OUT, float* y, void* ws, size_t ws_bytes,
+                        rdrf_stream_t stream);
+
 /* timing hook: average device time (ms) of the dominant kernel launches recorded with HIP events
  * since the last reset; used by bench.py for the roofline figure. */
 void rdrf_prof_reset(void);

@@ -137,6 +137,8 @@ def _load():
     lib.rdrf_ssim_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.rdrf_ssim.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.rdrf_selftest_layer.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_size_t, C.c_void_p]
     lib.rdrf_prof_get.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     lib.rdrf_det_bind.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.rdrf_det_finish.argtypes = [C.c_int, C.c_void_p]
@@ -166,10 +168,13 @@ SYMBOLS = [
     "rdrf_render_workspace_bytes", "rdrf_render_fwd", "rdrf_render_chunks_workspace_bytes", "rdrf_render_chunks_fwd",
     "rdrf_render_maps_fwd", "rdrf_render_chunks_maps_fwd", "rdrf_camera_rays", "rdrf_ssim_workspace_bytes", "rdrf_ssim",
     "rdrf_render_motion_workspace_bytes", "rdrf_render_motion_fwd", "rdrf_flow_to_image_workspace_bytes", "rdrf_flow_to_image",
-    "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_prof_reset",
+    "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_selftest_layer", "rdrf_prof_reset",
     "rdrf_prof_enable", "rdrf_prof_get",
 ]
 
+
+# rdrf_selftest_layer forms (include/rodynrf.h RDRF_ST_*)
+SELFTEST_FORMS = {"F32": 0, "F32_T": 1, "B3": 2, "B3_T": 3, "B3_PAIR_T": 4, "B3S": 5, "B3S_T": 6}
 
 SCATTER_MODES = {"ray": 0, "sorted": 1, "auto": 2, "sorted_plain": 3}
 

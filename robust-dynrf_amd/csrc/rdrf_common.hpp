@@ -264,24 +264,49 @@ RDRF_D void split3(float x, unsigned& hi, unsigned& mid, unsigned& lo) {
   lo = __float_as_uint(r - __uint_as_float(mid));
 }
 RDRF_D unsigned pack_hi16(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }   // (a >> 16) | (b & 0xffff0000)
+// The weight fragments of the bf16 x 3 layers are read through ONE lane base per image and immediate offsets.  Addressed as
+// `image + constant`, every fragment beyond the 64 KB an LDS offset field reaches had its address formed by a VALU instruction
+// of its own (v_or_b32 / v_add_u32 lane_base, constant), which the register allocator placed in the first register of the
+// fragment the preceding MFMA had just read: a write of an MFMA's A operand ZERO instructions behind it (120 sites in
+// k_static_app / k_dyn_app, 4 in k_dyn_density_bwd; tests/test_mfma_hazards_cpu.py).  The base is made opaque once per call,
+// BEFORE the loads and the split of the first step (the no-asm rule below is about the instructions between a piece's VALU
+// write and the MFMA that reads it), so that the constant cannot be folded back in; an image is at most 64 512 bytes long.
+// The images live in LDS: the low half of a generic LDS pointer is the LDS byte address.
+typedef const __attribute__((address_space(3))) u32x4* LdsFragPtr;
+RDRF_D unsigned lds_frag_base(const float* __restrict__ image, int lane) {
+  unsigned a = (unsigned)(size_t)image + (unsigned)lane * 16u;
+  asm volatile("" : "+v"(a));
+  return a;
+}
+RDRF_D u32x4 lds_frag(unsigned base, int frag) { return *(LdsFragPtr)(size_t)(base + (unsigned)frag * 1024u); }
+RDRF_D u32x4 lds_frag2(unsigned base, unsigned base64, int frag) { return frag < 64 ? lds_frag(base, frag) : lds_frag(base64, frag - 64); }
+// After the LAST step of a layer nothing of the layer separates its final MFMAs from the caller's code, whose address
+// arithmetic reused B-operand registers one and two instructions behind them in k_dyn_density_bwd (the distance at which the
+// fused render kernel returned stale pieces, see mfma_seg_b3): three wait states keep every such write more than two away.
+RDRF_D void mfma_tail_pad() {
+  asm volatile("s_nop 2");   // (no builtin for it; it follows the MFMAs, no piece is written before it)
+  __builtin_amdgcn_sched_barrier(0);
+}
 template <int NBO, int KK>
 RDRF_D void mfma_seg_b3(f32x16 (&acc)[NBO], const float (&in)[KK], const float* __restrict__ wpf, int lane) {
   static_assert(KK % 8 == 0, "one K = 16 step takes eight slots per lane half");
   constexpr int K8 = KK / 8;
-  const unsigned* __restrict__ wp = reinterpret_cast<const unsigned*>(wpf);
+  static_assert(NBO * K8 * 3 <= 64, "fragment offsets fit the 16-bit LDS offset field");
+  const unsigned wp = lds_frag_base(wpf, lane);
 #pragma unroll
   for (int k8 = 0; k8 < K8; ++k8) {
     // the step's weight pieces are requested first: the ~44 VALU instructions of the split below cover the LDS latency, so no
     // step-ahead copy of the fragments is kept (24 registers at NBO = 2).  The scheduling barriers stop hipcc from hoisting
     // every split of the fully unrolled layer to the top (148 spilled registers in the microbenchmark).
-    // NO inline asm in this function: hipcc counts an `asm` statement as an instruction when it pads the VALU-write ->
+    // NO inline asm between a piece's VALU write and the MFMA that reads it (the two statements of this file's bf16 x 3 code sit
+    // before the first load of a call, lds_frag_base, and behind the last MFMA of a step, mfma_tail_pad): hipcc counts an `asm` statement as an instruction when it pads the VALU-write ->
     // MFMA-read wait states, an empty one (used to defeat common-subexpression elimination) left the last piece register
     // short of them -- one sample in ~15 000 came out with a stale lo piece (tools/graph/det_fwd.py).
     u32x4 wc[NBO][3];
 #pragma unroll
     for (int nb = 0; nb < NBO; ++nb)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) wc[nb][p] = *(const u32x4*)(wp + ((size_t)((nb * K8 + k8) * 3 + p) * 64 + lane) * 4);
+      for (int p = 0; p < 3; ++p) wc[nb][p] = lds_frag(wp, (nb * K8 + k8) * 3 + p);
     // The loads stay FIRST after the previous step's MFMAs: the split below reuses the registers of the previous step's pieces,
     // and a v_sub_f32 that overwrote the B operand two instructions after the last MFMA of the step (the fused render kernel's
     // schedule) gave one ray in ~700 a stale piece, run to run -- a write-after-read window on the 4-register operands of
@@ -299,6 +324,7 @@ RDRF_D void mfma_seg_b3(f32x16 (&acc)[NBO], const float (&in)[KK], const float* 
     for (int e = 0; e < 8; ++e) hi[e] = __float_as_uint(in[k8 * 8 + e]) & 0xffff0000u;
 #pragma unroll
     for (int q = 0; q < 4; ++q) bh[q] = pack_hi16(hi[2 * q], hi[2 * q + 1]);
+    __builtin_amdgcn_sched_barrier(0);   // the sweeps stay apart: a piece is complete a whole sweep before the MFMAs start
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       r1[e] = __float_as_uint(in[k8 * 8 + e] - __uint_as_float(hi[e]));   // exact
@@ -306,6 +332,7 @@ RDRF_D void mfma_seg_b3(f32x16 (&acc)[NBO], const float (&in)[KK], const float* 
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) bm[q] = pack_hi16(mid[2 * q], mid[2 * q + 1]);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int q = 0; q < 4; ++q)   // the instruction reads the top 16 bits of r1 - mid
       bl[q] = pack_hi16(__float_as_uint(__uint_as_float(r1[2 * q]) - __uint_as_float(mid[2 * q])),
@@ -319,6 +346,7 @@ RDRF_D void mfma_seg_b3(f32x16 (&acc)[NBO], const float (&in)[KK], const float* 
     RDRF_B3_STEP(0, xh) RDRF_B3_STEP(1, xh) RDRF_B3_STEP(2, xh) RDRF_B3_STEP(0, xm) RDRF_B3_STEP(1, xm) RDRF_B3_STEP(0, xl)
 #undef RDRF_B3_STEP
     __builtin_amdgcn_sched_barrier(0);
+    mfma_tail_pad();
   }
 }
 
@@ -330,15 +358,15 @@ RDRF_D void mfma_seg_b3_pair(f32x16 (&accA)[NA], f32x16 (&accB)[NB], const float
                              const float* __restrict__ wpfB, int lane) {
   static_assert(KK % 8 == 0, "one K = 16 step takes eight slots per lane half");
   constexpr int K8 = KK / 8;
-  const unsigned* __restrict__ wpA = reinterpret_cast<const unsigned*>(wpfA);
-  const unsigned* __restrict__ wpB = reinterpret_cast<const unsigned*>(wpfB);
+  static_assert(NA * K8 * 3 <= 64 && NB * K8 * 3 <= 64, "fragment offsets fit the 16-bit LDS offset field");
+  const unsigned wpA = lds_frag_base(wpfA, lane), wpB = lds_frag_base(wpfB, lane);
 #pragma unroll
   for (int k8 = 0; k8 < K8; ++k8) {
     u32x4 wa[NA][3], wb[NB][3];
 #pragma unroll
     for (int nb = 0; nb < NA; ++nb)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) wa[nb][p] = *(const u32x4*)(wpA + ((size_t)((nb * K8 + k8) * 3 + p) * 64 + lane) * 4);
+      for (int p = 0; p < 3; ++p) wa[nb][p] = lds_frag(wpA, (nb * K8 + k8) * 3 + p);
     __builtin_amdgcn_sched_barrier(0);
     unsigned hi[8], r1[8], mid[8];
     u32x4 bh, bm, bl;
@@ -346,6 +374,7 @@ RDRF_D void mfma_seg_b3_pair(f32x16 (&accA)[NA], f32x16 (&accB)[NB], const float
     for (int e = 0; e < 8; ++e) hi[e] = __float_as_uint(in[k8 * 8 + e]) & 0xffff0000u;
 #pragma unroll
     for (int q = 0; q < 4; ++q) bh[q] = pack_hi16(hi[2 * q], hi[2 * q + 1]);
+    __builtin_amdgcn_sched_barrier(0);   // the sweeps stay apart: a piece is complete a whole sweep before the MFMAs start
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       r1[e] = __float_as_uint(in[k8 * 8 + e] - __uint_as_float(hi[e]));
@@ -353,6 +382,7 @@ RDRF_D void mfma_seg_b3_pair(f32x16 (&accA)[NA], f32x16 (&accB)[NB], const float
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) bm[q] = pack_hi16(mid[2 * q], mid[2 * q + 1]);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
       bl[q] = pack_hi16(__float_as_uint(__uint_as_float(r1[2 * q]) - __uint_as_float(mid[2 * q])),
@@ -362,7 +392,7 @@ RDRF_D void mfma_seg_b3_pair(f32x16 (&accA)[NA], f32x16 (&accB)[NB], const float
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) wb[nb][p] = *(const u32x4*)(wpB + ((size_t)((nb * K8 + k8) * 3 + p) * 64 + lane) * 4);
+      for (int p = 0; p < 3; ++p) wb[nb][p] = lds_frag(wpB, (nb * K8 + k8) * 3 + p);
 #define RDRF_B3_STEP(ACC, W, N, WP, XP)                                                                                   \
     _Pragma("unroll") for (int nb = 0; nb < N; ++nb)                                                                      \
       ACC[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, W[nb][WP]), XP, ACC[nb], 0, 0, 0);
@@ -373,6 +403,7 @@ RDRF_D void mfma_seg_b3_pair(f32x16 (&accA)[NA], f32x16 (&accB)[NB], const float
     RDRF_B3_STEP(accB, wb, NB, 0, xm) RDRF_B3_STEP(accB, wb, NB, 1, xm) RDRF_B3_STEP(accB, wb, NB, 0, xl)
 #undef RDRF_B3_STEP
     __builtin_amdgcn_sched_barrier(0);
+    mfma_tail_pad();
   }
 }
 
@@ -418,19 +449,22 @@ RDRF_D void mfma_seg_b3s(f32x16 (&acc)[NBO], const float (&in)[KK], const float*
   // fragments there too) --, the split is done once, group B's fragments arrive while group A's MFMAs run.  The product
   // that reads the streamed lo pieces comes LAST in its group: a whole step lies between their request and their use.
   constexpr bool EARLY_B = NA * 2 + NBO < 6;
-  const unsigned* __restrict__ wp = reinterpret_cast<const unsigned*>(wpf);
+  // (the five-block backward images are 80 fragments long: a second base for the fragments from 64 on)
+  static_assert(NBO * K8 * 2 <= 128, "fragment offsets fit the 16-bit LDS offset field of one of two bases");
+  const unsigned wp = lds_frag_base(wpf, lane);
+  const unsigned wp2 = NBO * K8 * 2 > 64 ? lds_frag_base(wpf + 64 * 256, lane) : wp;
 #pragma unroll
   for (int k8 = 0; k8 < K8; ++k8) {
     u32x4 wa[NA][2], wb[NB][2];
 #pragma unroll
     for (int nb = 0; nb < NA; ++nb)
 #pragma unroll
-      for (int p = 0; p < 2; ++p) wa[nb][p] = *(const u32x4*)(wp + ((size_t)((nb * K8 + k8) * 2 + p) * 64 + lane) * 4);
+      for (int p = 0; p < 2; ++p) wa[nb][p] = lds_frag2(wp, wp2, (nb * K8 + k8) * 2 + p);
     if (EARLY_B) {
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) wb[nb][p] = *(const u32x4*)(wp + ((size_t)(((NA + nb) * K8 + k8) * 2 + p) * 64 + lane) * 4);
+        for (int p = 0; p < 2; ++p) wb[nb][p] = lds_frag2(wp, wp2, ((NA + nb) * K8 + k8) * 2 + p);
     }
     __builtin_amdgcn_sched_barrier(0);
     unsigned hi[8], r1[8], mid[8];
@@ -439,6 +473,7 @@ RDRF_D void mfma_seg_b3s(f32x16 (&acc)[NBO], const float (&in)[KK], const float*
     for (int e = 0; e < 8; ++e) hi[e] = __float_as_uint(in[k8 * 8 + e]) & 0xffff0000u;
 #pragma unroll
     for (int q = 0; q < 4; ++q) bh[q] = pack_hi16(hi[2 * q], hi[2 * q + 1]);
+    __builtin_amdgcn_sched_barrier(0);   // the sweeps stay apart: a piece is complete a whole sweep before the MFMAs start
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       r1[e] = __float_as_uint(in[k8 * 8 + e] - __uint_as_float(hi[e]));   // exact
@@ -446,6 +481,7 @@ RDRF_D void mfma_seg_b3s(f32x16 (&acc)[NBO], const float (&in)[KK], const float*
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) bm[q] = pack_hi16(mid[2 * q], mid[2 * q + 1]);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int q = 0; q < 4; ++q)
       bl[q] = pack_hi16(__float_as_uint(__uint_as_float(r1[2 * q]) - __uint_as_float(mid[2 * q])),
@@ -456,7 +492,7 @@ RDRF_D void mfma_seg_b3s(f32x16 (&acc)[NBO], const float (&in)[KK], const float*
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-        for (int p = 0; p < 2; ++p) wb[nb][p] = *(const u32x4*)(wp + ((size_t)(((NA + nb) * K8 + k8) * 2 + p) * 64 + lane) * 4);
+        for (int p = 0; p < 2; ++p) wb[nb][p] = lds_frag2(wp, wp2, ((NA + nb) * K8 + k8) * 2 + p);
     }
 #define RDRF_B3S_STEP(N, NB0, WV, XP)                                                                                     \
     _Pragma("unroll") for (int nb = 0; nb < N; ++nb)                                                                      \
@@ -471,6 +507,7 @@ RDRF_D void mfma_seg_b3s(f32x16 (&acc)[NBO], const float (&in)[KK], const float*
     // the lo pieces are consumed: request the next step's (this segment's, or step 0 of the segment that follows in the tile)
     if (k8 + 1 < K8) b3s_lo_load<NBO>(lo, st, off, K8, k8 + 1);
     else if (KK_NEXT > 0) b3s_lo_load<NBO>(lo, st, off_next, KK_NEXT / 8, 0);
+    else mfma_tail_pad();
     __builtin_amdgcn_sched_barrier(0);
   }
 }
