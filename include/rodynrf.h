@@ -125,6 +125,14 @@ size_t rdrf_forward_workspace_bytes(int N, int S);
  * 1 = dynamic field, 2 = scene flow) stores the activations its backward needs; the matching
  * *_bwd call must receive the same buffer untouched.  saved == NULL => inference, nothing kept. */
 size_t rdrf_saved_bytes(int kind, int N, int S);
+/* Rows are saved only where a backward can read them.  `flags` of the *_ex entry points (0 = as the plain ones):
+ *   RDRF_SAVE_NO_APP  the colours of this call are values only -- no gradient will arrive for rgb.  The density phase saves
+ *                     as usual, the appearance phase runs the inference kernels and writes no rows; the appearance block is
+ *                     the last one of the buffer, so a buffer of this kind is a prefix of the full layout.  The matching
+ *                     *_bwd call tells the two kinds apart by `saved_bytes` (the size the forward was given) and refuses
+ *                     (-1, nothing launched) a non-NULL g_rgb for a buffer without appearance rows.  Kind 2 ignores it. */
+#define RDRF_SAVE_NO_APP 1
+size_t rdrf_saved_bytes_ex(int kind, int N, int S, int flags);
 /* Bytes per sample of the activation rows inside that buffer (a measurement aid, bench.py `saved_bytes_per_sample`):
  * phase 0 = dynamic field, density phase (every sample); 1 = dynamic field, appearance phase (per sample that passes the
  * weight > 1e-4 mask, models/tensorBase.py:773-790); 2 = static field, appearance phase (per masked sample); 3 = scene flow. */
@@ -174,6 +182,11 @@ int rdrf_static_fwd(const RdrfStaticParams* P, const RdrfFieldCfg* cfg, const fl
                     const float* ts, const float* xyz, const float* z, const uint8_t* valid, int N,
                     int S, float* rgb, float* sigma, float* weight, float* dists, void* saved,
                     size_t saved_bytes, void* ws, size_t ws_bytes, rdrf_stream_t stream);
+/* the same with a flags word (RDRF_SAVE_*: see rdrf_saved_bytes_ex); `saved_bytes` is rdrf_saved_bytes_ex of the same flags */
+int rdrf_static_fwd_ex(const RdrfStaticParams* P, const RdrfFieldCfg* cfg, const float* rays,
+                       const float* ts, const float* xyz, const float* z, const uint8_t* valid, int N,
+                       int S, float* rgb, float* sigma, float* weight, float* dists, void* saved,
+                       size_t saved_bytes, void* ws, size_t ws_bytes, rdrf_stream_t stream, int flags);
 /* g_* are gradients wrt the four outputs (any may be NULL = zero). G receives parameter
  * gradients (+=); g_xyz[N][S][3], g_z[N][S], g_rays[N][6] (+=, each may be NULL). */
 int rdrf_static_bwd(const RdrfStaticParams* P, const RdrfFieldCfg* cfg, const float* rays,
@@ -190,6 +203,11 @@ int rdrf_dynamic_fwd(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, const 
                      int N, int S, float* blending, float* weight, float* xyz_prime, float* rgb,
                      float* sigma, float* dists, void* saved, size_t saved_bytes, void* ws,
                      size_t ws_bytes, rdrf_stream_t stream);
+int rdrf_dynamic_fwd_ex(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, const float* rays,
+                        const float* ts, const float* xyz, const float* z, const uint8_t* valid,
+                        int N, int S, float* blending, float* weight, float* xyz_prime, float* rgb,
+                        float* sigma, float* dists, void* saved, size_t saved_bytes, void* ws,
+                        size_t ws_bytes, rdrf_stream_t stream, int flags);
 int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, const float* rays,
                      const float* ts, const float* xyz, const float* z, const uint8_t* valid,
                      int N, int S, const float* g_blending, const float* g_weight,

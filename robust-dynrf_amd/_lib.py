@@ -18,6 +18,7 @@ ABI_VERSION = 6   # include/rodynrf.h RDRF_ABI_VERSION: the parameter structs be
 RAY_TYPES = {"ndc": 0, "contract": 1}
 ACTS = {"relu": 0, "softplus": 1}
 HEADS = {"MLP_Fea": 0, "MLP_Fea_TimeEmbedding": 1}
+SAVE_NO_APP = 1   # include/rodynrf.h RDRF_SAVE_NO_APP (flags of rdrf_saved_bytes_ex / rdrf_*_fwd_ex)
 
 fp = C.POINTER(C.c_float)
 
@@ -94,6 +95,8 @@ def _load():
     lib.rdrf_forward_workspace_bytes.argtypes = [C.c_int, C.c_int]
     lib.rdrf_saved_bytes.restype = C.c_size_t
     lib.rdrf_saved_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.rdrf_saved_bytes_ex.restype = C.c_size_t
+    lib.rdrf_saved_bytes_ex.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.rdrf_saved_row_bytes.restype = C.c_size_t
     lib.rdrf_saved_row_bytes.argtypes = [C.c_int]
     for name, args in (("rdrf_features_saved_bytes", [C.c_int, C.c_int]),
@@ -151,10 +154,10 @@ lib = _load()
 
 # every symbol include/rodynrf.h declares (tests check that the library exports all of them)
 SYMBOLS = [
-    "rdrf_abi_version", "rdrf_last_error", "rdrf_workspace_bytes", "rdrf_forward_workspace_bytes", "rdrf_saved_bytes", "rdrf_saved_row_bytes",
+    "rdrf_abi_version", "rdrf_last_error", "rdrf_workspace_bytes", "rdrf_forward_workspace_bytes", "rdrf_saved_bytes", "rdrf_saved_bytes_ex", "rdrf_saved_row_bytes",
     "rdrf_generate_rays",
     "rdrf_generate_rays_bwd", "rdrf_generate_rays_uv", "rdrf_generate_rays_uv_bwd", "rdrf_sample_ndc", "rdrf_sample_contract", "rdrf_sample_bwd",
-    "rdrf_static_fwd", "rdrf_static_bwd", "rdrf_dynamic_fwd", "rdrf_dynamic_bwd",
+    "rdrf_static_fwd", "rdrf_static_fwd_ex", "rdrf_static_bwd", "rdrf_dynamic_fwd", "rdrf_dynamic_fwd_ex", "rdrf_dynamic_bwd",
     "rdrf_features_saved_bytes", "rdrf_features_workspace_bytes", "rdrf_features_bwd_workspace_bytes",
     "rdrf_static_features_fwd", "rdrf_static_features_bwd", "rdrf_dynamic_features_fwd",
     "rdrf_dynamic_features_bwd",

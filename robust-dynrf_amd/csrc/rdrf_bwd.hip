@@ -3295,7 +3295,12 @@ extern "C" int rdrf_static_bwd(const RdrfStaticParams* P, const RdrfFieldCfg* cf
   fill_bwd_common(a, cfg, rays, ts, xyz, z, valid, N, S);
   a.g_rgb = g_rgb; a.g_sigma = g_sigma; a.g_weight = g_weight; a.g_xyz = g_xyz;
   a.g_rays = g_rays; a.g_dists = g_dists; a.g_z = g_z;
-  RDRF_CHECK(carve_saved(a.sp, saved, saved_bytes, 0, N, S), -3, "static_bwd: saved buffer too small");
+  // a buffer the forward filled under RDRF_SAVE_NO_APP has no appearance rows (a prefix of the full layout): told apart by its
+  // size, on the host, before anything is launched
+  const int saved_kind = carve_saved_bwd(a.sp, saved, saved_bytes, 0, N, S);
+  RDRF_CHECK(saved_kind >= 0, -3, "static_bwd: saved buffer too small");
+  RDRF_CHECK(saved_kind == 1 || g_rgb == nullptr, -1,
+             "static_bwd: the forward saved no appearance rows (RDRF_SAVE_NO_APP): no gradient can flow through rgb");
   BwdWs b;
   int rc = carve_bwd(b, ws, ws_bytes, N, S, 0);
   if (rc) return rc;
@@ -3384,7 +3389,12 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
   a.g_xyz_prime = g_xyz_prime; a.g_xyz = g_xyz; a.g_rays = g_rays; a.g_dists = g_dists; a.g_z = g_z;
   static const bool small_dw = !(RDRF_ENV("RDRF_DW_SMALL") && atoi(RDRF_ENV("RDRF_DW_SMALL")) == 0);   // 0: as k_dw2 products (tools build)
   a.small_dw = small_dw ? 1 : 0;
-  RDRF_CHECK(carve_saved(a.sp, saved, saved_bytes, 1, N, S), -3, "dynamic_bwd: saved buffer too small");
+  // a buffer the forward filled under RDRF_SAVE_NO_APP has no appearance rows (a prefix of the full layout): told apart by its
+  // size, on the host, before anything is launched
+  const int saved_kind = carve_saved_bwd(a.sp, saved, saved_bytes, 1, N, S);
+  RDRF_CHECK(saved_kind >= 0, -3, "dynamic_bwd: saved buffer too small");
+  RDRF_CHECK(saved_kind == 1 || g_rgb == nullptr, -1,
+             "dynamic_bwd: the forward saved no appearance rows (RDRF_SAVE_NO_APP): no gradient can flow through rgb");
   BwdWs b;
   int rc = carve_bwd(b, ws, ws_bytes, N, S, 1);
   if (rc) return rc;

@@ -226,8 +226,8 @@ void fill_dyn_w(DynW& w, const RdrfDynamicParams* P) {
 #define PACK_AREA_FLOATS (1 << 20) /* 4 MiB: forward + transposed packs of either field */
 
 
-int ws_carve_fwd(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S, void* saved,
-                 size_t saved_bytes, int dynamic) {
+static int ws_carve_fwd_ex(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S, void* saved,
+                           size_t saved_bytes, int dynamic, int flags) {
   WsCarver c(ws, ws_bytes);
   size_t ns = (size_t)N * S;
   a.pk = c.take<float>(PACK_AREA_FLOATS);
@@ -238,8 +238,8 @@ int ws_carve_fwd(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S, void* sa
   RDRF_CHECK(c.ok(), -3, "workspace too small: need %zu have %zu", c.off, ws_bytes);
   if (saved != nullptr) {  // training mode: the backward re-uses these instead of recomputing
     SavedPtrs sp;
-    RDRF_CHECK(carve_saved(sp, saved, saved_bytes, dynamic, N, S), -3,
-               "saved buffer too small: need %zu have %zu", saved_bytes_field(dynamic, N, S),
+    RDRF_CHECK(carve_saved(sp, saved, saved_bytes, dynamic, N, S, flags), -3,
+               "saved buffer too small: need %zu have %zu", saved_bytes_field(dynamic, N, S, flags),
                saved_bytes);
     a.counter = &sp.hdr->count;
     a.list = sp.list;
@@ -247,15 +247,21 @@ int ws_carve_fwd(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S, void* sa
     a.tout = sp.tout;
     a.raw = sp.raw;
     a.act1 = sp.act1;
-    a.act3 = sp.act3;
+    a.act3 = sp.act3;   // nullptr with RDRF_SAVE_NO_APP
   }
   return 0;
 }
 
-extern "C" size_t rdrf_saved_bytes(int kind, int N, int S) {
-  if (kind == 2) return ((size_t)N * S + 31) / 32 * sv::SF_ROWS * 32 * 4 + 256;
-  return saved_bytes_field(kind == 1, N, S);
+int ws_carve_fwd(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S, void* saved,
+                 size_t saved_bytes, int dynamic) {   // (also rdrf_render.hip, rdrf_motion.hip)
+  return ws_carve_fwd_ex(a, ws, ws_bytes, N, S, saved, saved_bytes, dynamic, 0);
 }
+
+extern "C" size_t rdrf_saved_bytes_ex(int kind, int N, int S, int flags) {
+  if (kind == 2) return ((size_t)N * S + 31) / 32 * sv::SF_ROWS * 32 * 4 + 256;
+  return saved_bytes_field(kind == 1, N, S, flags);
+}
+extern "C" size_t rdrf_saved_bytes(int kind, int N, int S) { return rdrf_saved_bytes_ex(kind, N, S, 0); }
 
 extern "C" size_t rdrf_saved_row_bytes(int phase) {
   return (size_t)4 * (phase == 0 ? sv::K1_ROWS : phase == 1 ? sv::K3_ROWS : phase == 2 ? sv::S3_ROWS : sv::SF_ROWS);
@@ -305,22 +311,26 @@ int fwd_dynq() {
   return (dynq ? 1 : 0) | (wprio ? 2 : 0) | (stagger << 8);
 }
 
-extern "C" int rdrf_static_fwd(const RdrfStaticParams* P, const RdrfFieldCfg* cfg, const float* rays,
-                               const float* ts, const float* xyz, const float* z,
-                               const uint8_t* valid, int N, int S, float* rgb, float* sigma,
-                               float* weight, float* dists, void* saved, size_t saved_bytes,
-                               void* ws, size_t ws_bytes, rdrf_stream_t stream_) {
+extern "C" int rdrf_static_fwd_ex(const RdrfStaticParams* P, const RdrfFieldCfg* cfg, const float* rays,
+                                  const float* ts, const float* xyz, const float* z,
+                                  const uint8_t* valid, int N, int S, float* rgb, float* sigma,
+                                  float* weight, float* dists, void* saved, size_t saved_bytes,
+                                  void* ws, size_t ws_bytes, rdrf_stream_t stream_, int flags) {
   hipStream_t stream = (hipStream_t)stream_;
   if (N == 0) return 0;   // empty batch: a no-op, like torch ops on empty tensors (their data pointers are null)
   RDRF_CHECK(P && cfg && N > 0 && S > 0, -1, "static_fwd: bad arguments");
+  RDRF_CHECK((flags & ~RDRF_SAVE_NO_APP) == 0, -1, "static_fwd: unknown flags 0x%x", flags);
   RDRF_CHECK((size_t)N * S * 3 < (size_t)INT32_MAX, -1, "static_fwd: N * S * 3 must stay below 2^31 (32-bit sample indices): render / train in smaller chunks");
   RDRF_CHECK(vm_ok(P->density, 16, 4) && vm_ok(P->app, 48, 12), -1,
              "static_fwd: only density comps {16,4,4} / app comps {48,12,12}, the planes and lines of a set spanning one grid, are built");
   FieldArgs a;
   fill_common(a, cfg, rays, ts, xyz, z, valid, N, S);
   a.rgb = rgb; a.sigma = sigma; a.weight = weight; a.dists = dists;
-  int rc = ws_carve_fwd(a, ws, ws_bytes, N, S, saved, saved_bytes, 0);
+  int rc = ws_carve_fwd_ex(a, ws, ws_bytes, N, S, saved, saved_bytes, 0, flags);
   if (rc) return rc;
+  // rows are saved only where a backward can read them: no buffer, or one without appearance rows (RDRF_SAVE_NO_APP: the
+  // colours are values only) -> the inference instantiation of the appearance kernel
+  const bool save_app = saved != nullptr && !(flags & RDRF_SAVE_NO_APP);
   StaticW w;
   fill_static_w(w, P);
   if (P->packed_fwd != nullptr) a.pk = P->packed_fwd;   // caller-packed image (rdrf_static_pack)
@@ -353,7 +363,7 @@ extern "C" int rdrf_static_fwd(const RdrfStaticParams* P, const RdrfFieldCfg* cf
     waves = waves < 1 ? 1 : (waves > 16 ? 16 : waves);
     const long blocks = (t16 + waves - 1) / waves;
     const dim3 gr((unsigned)(blocks > 256 ? 256 : blocks)), bl(waves * 64);
-    if (saved != nullptr) {
+    if (save_app) {
       if (fea) RDRF_LAUNCH("static_app", (k_static_app16<RDRF_HEAD_MLP_FEA, true>), gr, bl, stream, a, w);
       else RDRF_LAUNCH("static_app", (k_static_app16<RDRF_HEAD_MLP_FEA_TIMEEMBEDDING, true>), gr, bl, stream, a, w);
     } else {
@@ -363,7 +373,7 @@ extern "C" int rdrf_static_fwd(const RdrfStaticParams* P, const RdrfFieldCfg* cf
     return 0;
   }
 #endif
-  if (saved != nullptr) {
+  if (save_app) {
     if (fea) RDRF_LAUNCH("static_app", (k_static_app<RDRF_HEAD_MLP_FEA, false, true>), dim3(g.grid), dim3(g.block), stream, a, w);
     else RDRF_LAUNCH("static_app", (k_static_app<RDRF_HEAD_MLP_FEA_TIMEEMBEDDING, false, true>), dim3(g.grid), dim3(g.block), stream, a, w);
   } else {
@@ -373,15 +383,25 @@ extern "C" int rdrf_static_fwd(const RdrfStaticParams* P, const RdrfFieldCfg* cf
   return 0;
 }
 
-extern "C" int rdrf_dynamic_fwd(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg,
-                                const float* rays, const float* ts, const float* xyz,
-                                const float* z, const uint8_t* valid, int N, int S,
-                                float* blending, float* weight, float* xyz_prime, float* rgb,
-                                float* sigma, float* dists, void* saved, size_t saved_bytes,
-                                void* ws, size_t ws_bytes, rdrf_stream_t stream_) {
+extern "C" int rdrf_static_fwd(const RdrfStaticParams* P, const RdrfFieldCfg* cfg, const float* rays,
+                               const float* ts, const float* xyz, const float* z,
+                               const uint8_t* valid, int N, int S, float* rgb, float* sigma,
+                               float* weight, float* dists, void* saved, size_t saved_bytes,
+                               void* ws, size_t ws_bytes, rdrf_stream_t stream_) {
+  return rdrf_static_fwd_ex(P, cfg, rays, ts, xyz, z, valid, N, S, rgb, sigma, weight, dists, saved, saved_bytes, ws, ws_bytes,
+                            stream_, 0);
+}
+
+extern "C" int rdrf_dynamic_fwd_ex(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg,
+                                   const float* rays, const float* ts, const float* xyz,
+                                   const float* z, const uint8_t* valid, int N, int S,
+                                   float* blending, float* weight, float* xyz_prime, float* rgb,
+                                   float* sigma, float* dists, void* saved, size_t saved_bytes,
+                                   void* ws, size_t ws_bytes, rdrf_stream_t stream_, int flags) {
   hipStream_t stream = (hipStream_t)stream_;
   if (N == 0) return 0;   // empty batch: a no-op, like torch ops on empty tensors (their data pointers are null)
   RDRF_CHECK(P && cfg && N > 0 && S > 0, -1, "dynamic_fwd: bad arguments");
+  RDRF_CHECK((flags & ~RDRF_SAVE_NO_APP) == 0, -1, "dynamic_fwd: unknown flags 0x%x", flags);
   RDRF_CHECK((size_t)N * S * 3 < (size_t)INT32_MAX, -1, "dynamic_fwd: N * S * 3 must stay below 2^31 (32-bit sample indices): render / train in smaller chunks");
   RDRF_CHECK(vm_ok(P->density, 16, 4) && vm_ok(P->blending, 16, 4) && vm_ok(P->app, 48, 12) && vm_same_grid(P->density, P->blending), -1,
              "dynamic_fwd: only density comps {16,4,4} / app comps {48,12,12}, the planes and lines of a set spanning one grid, are built");
@@ -390,7 +410,7 @@ extern "C" int rdrf_dynamic_fwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
   a.rgb = rgb; a.sigma = sigma; a.weight = weight; a.dists = dists;
   a.blending = blending; a.xyz_prime = xyz_prime;
   a.dynq = fwd_dynq();
-  int rc = ws_carve_fwd(a, ws, ws_bytes, N, S, saved, saved_bytes, 1);
+  int rc = ws_carve_fwd_ex(a, ws, ws_bytes, N, S, saved, saved_bytes, 1, flags);
   if (rc) return rc;
   DynW w;
   fill_dyn_w(w, P);
@@ -421,9 +441,21 @@ extern "C" int rdrf_dynamic_fwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
   { int rc_ = rdrf_sort_ints_inplace(a.list, (unsigned)((size_t)N * S), stream); if (rc_) return rc_; }
 #endif
   if (rgb == nullptr) return 0;   // the caller does not consume the colours: the appearance phase is not run
-  if (saved != nullptr) RDRF_LAUNCH("dyn_app", (k_dyn_app<false, true>), dim3(g3.grid), dim3(g3.block), stream, a, w);
+  // RDRF_SAVE_NO_APP: the density phase above saved as usual (list, xw, tout, raw, K1 rows, count); the colours are values
+  // only, so the appearance phase is the inference instantiation and writes no K3 rows (see rdrf_static_fwd_ex)
+  if (saved != nullptr && !(flags & RDRF_SAVE_NO_APP)) RDRF_LAUNCH("dyn_app", (k_dyn_app<false, true>), dim3(g3.grid), dim3(g3.block), stream, a, w);
   else RDRF_LAUNCH("dyn_app", (k_dyn_app<false, false>), dim3(g3.grid), dim3(g3.block), stream, a, w);
   return 0;
+}
+
+extern "C" int rdrf_dynamic_fwd(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg,
+                                const float* rays, const float* ts, const float* xyz,
+                                const float* z, const uint8_t* valid, int N, int S,
+                                float* blending, float* weight, float* xyz_prime, float* rgb,
+                                float* sigma, float* dists, void* saved, size_t saved_bytes,
+                                void* ws, size_t ws_bytes, rdrf_stream_t stream_) {
+  return rdrf_dynamic_fwd_ex(P, cfg, rays, ts, xyz, z, valid, N, S, blending, weight, xyz_prime, rgb, sigma, dists, saved,
+                             saved_bytes, ws, ws_bytes, stream_, 0);
 }
 
 // ------------------------------------------------------------------------------------------------

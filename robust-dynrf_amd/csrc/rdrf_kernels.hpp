@@ -172,17 +172,19 @@ static inline bool carve_saved_feat(SavedPtrs& p, void* saved, size_t bytes, int
   p.act3 = c.take<float>(t * (dynamic ? sv::K3_ROWS : sv::S3_ROWS) * 32);
   return c.ok();
 }
-static inline size_t saved_bytes_field(int dynamic, int N, int S) {
+// flags: RDRF_SAVE_* (include/rodynrf.h).  RDRF_SAVE_NO_APP: no appearance rows -- act3 is the LAST block, so such a buffer
+// is a prefix of the full layout
+static inline size_t saved_bytes_field(int dynamic, int N, int S, int flags = 0) {
   size_t ns = (size_t)N * S, t1 = (size_t)N * ((S + 31) / 32), t3 = (ns + 31) / 32;
   size_t b = sizeof(SavedHdr) + 256;
   b += ns * 4 + 256;                                  // list
   b += ns * 3 * 4 + 256 + (size_t)N * 32 * 4 + 256;   // xw, tout
   b += ns * 2 * 4 + 256;                              // raw
   if (dynamic) b += t1 * sv::K1_ROWS * 32 * 4 + 256;
-  b += t3 * (dynamic ? sv::K3_ROWS : sv::S3_ROWS) * 32 * 4 + 256;
+  if (!(flags & RDRF_SAVE_NO_APP)) b += t3 * (dynamic ? sv::K3_ROWS : sv::S3_ROWS) * 32 * 4 + 256;
   return b;
 }
-static inline bool carve_saved(SavedPtrs& p, void* saved, size_t bytes, int dynamic, int N, int S) {
+static inline bool carve_saved(SavedPtrs& p, void* saved, size_t bytes, int dynamic, int N, int S, int flags = 0) {
   WsCarver c(saved, bytes);
   size_t ns = (size_t)N * S, t1 = (size_t)N * ((S + 31) / 32), t3 = (ns + 31) / 32;
   p.hdr = c.take<SavedHdr>(1);
@@ -191,6 +193,12 @@ static inline bool carve_saved(SavedPtrs& p, void* saved, size_t bytes, int dyna
   p.tout = c.take<float>((size_t)N * 32);
   p.raw = c.take<float>(ns * 2);
   p.act1 = dynamic ? c.take<float>(t1 * sv::K1_ROWS * 32) : nullptr;
-  p.act3 = c.take<float>(t3 * (dynamic ? sv::K3_ROWS : sv::S3_ROWS) * 32);
+  p.act3 = (flags & RDRF_SAVE_NO_APP) ? nullptr : c.take<float>(t3 * (dynamic ? sv::K3_ROWS : sv::S3_ROWS) * 32);
   return c.ok();
+}
+// backward side: which kind of buffer `bytes` is (the size the forward was given).  1: full, 0: without appearance rows
+// (act3 == nullptr), -1: too small for either.  Host arithmetic only.
+static inline int carve_saved_bwd(SavedPtrs& p, void* saved, size_t bytes, int dynamic, int N, int S) {
+  if (carve_saved(p, saved, bytes, dynamic, N, S, 0)) return 1;
+  return carve_saved(p, saved, bytes, dynamic, N, S, RDRF_SAVE_NO_APP) ? 0 : -1;
 }

@@ -11,6 +11,7 @@ VM factors are stored channel-last: a plane parameter has the reference's logica
 (1,C,H,W) with strides of an [H][W][C] array, so state_dicts interchange with the reference while
 one bilinear tap of 4 components is a single 16-byte load on the GPU.
 """
+import collections
 import ctypes as C
 
 import os
@@ -197,13 +198,50 @@ def _attach_packed(field, P, params, backward, dynamic):
         P.packed_fwd = slot[1].data_ptr()
 
 
-def _alloc_saved(ctx, kind, N, S, dev):
+# Saved-byte accounting: per kind of call (0 static field, 1 dynamic field, 2 scene flow, "feat0" / "feat1" the
+# per-point entry points) the number of forwards that saved "full" rows, "no_app" rows (RDRF_SAVE_NO_APP) or "none", and the
+# bytes allocated for them -- what the trainer's tests read to see which forward saved what.
+SAVE_STATS = collections.Counter()
+
+
+def _grad_mode(grad_mode):
+    """Rows are saved only where a backward can read them.  Under torch.no_grad() none can exist, yet
+    ctx.needs_input_grad still reports True for parameters there -- and inside Function.forward grad mode is always
+    off -- so the modules capture the CALLER's mode and hand it in; None = the mode right here."""
+    return torch.is_grad_enabled() if grad_mode is None else bool(grad_mode)
+
+
+def _alloc_saved(ctx, kind, N, S, dev, grad_mode=None, flags=0):
     """training mode: a per-call buffer the forward fills with the activations its backward needs
-    (inference -- no input requires grad -- keeps nothing)."""
-    if not any(ctx.needs_input_grad):
+    (inference -- the caller runs under no_grad, or no input requires grad -- keeps nothing).
+    flags: RDRF_SAVE_* of rdrf_saved_bytes_ex (L.SAVE_NO_APP: the colours are values only, no appearance rows)."""
+    if not _grad_mode(grad_mode) or not any(ctx.needs_input_grad):
+        SAVE_STATS[(kind, "none")] += 1
         return None, 0
-    nbytes = int(L.lib.rdrf_saved_bytes(kind, N, S))
+    nbytes = int(L.lib.rdrf_saved_bytes_ex(kind, N, S, flags))
+    SAVE_STATS[(kind, "no_app" if flags & L.SAVE_NO_APP else "full")] += 1
+    SAVE_STATS[(kind, "bytes")] += nbytes
     return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+
+
+_RGB_SUFFIX = {True: "", False: "-norgb", "value": "-valrgb"}
+
+
+def _call_mode(ray_type, rgb):
+    """what the field modules hand to their autograd Function next to the ray type, as suffixes of that string: the rgb
+    mode of forward() ("-norgb": rgb=False, "-valrgb": rgb="value") and "-nograd" when the caller runs under no_grad"""
+    rgb = rgb if isinstance(rgb, str) else bool(rgb)
+    if rgb not in _RGB_SUFFIX:
+        raise ValueError(f"forward(..., rgb=...) takes True, False or 'value', not {rgb!r}")
+    return ray_type + _RGB_SUFFIX[rgb] + ("" if torch.is_grad_enabled() else "-nograd")
+
+
+def _parse_mode(mode):
+    """-> (ray_type, rgb: True | False | "value", grad mode of the caller); see _call_mode"""
+    grad_mode = not mode.endswith("-nograd")
+    mode = mode.replace("-nograd", "")
+    rgb = "value" if mode.endswith("-valrgb") else not mode.endswith("-norgb")
+    return mode.replace("-valrgb", "").replace("-norgb", ""), rgb, grad_mode
 
 
 def _prep_inputs(rays, ts, xyz, z, valid):
@@ -222,24 +260,27 @@ class _StaticFn(torch.autograd.Function):
         rays, ts, xyz, z, valid = _prep_inputs(rays, ts, xyz, z, valid)
         N, S = z.shape
         dev = z.device
-        # ray_type "ndc" / "contract"; a trailing "-norgb" (forward(..., rgb=False)): the colours are not wanted
-        want_rgb = not ray_type.endswith("-norgb")
-        ray_type = ray_type.replace("-norgb", "")
+        # ray_type "ndc" / "contract" + the suffixes of _call_mode: rgb=False -- the colours are not wanted; rgb="value" --
+        # computed, but no gradient will be asked for them: no appearance rows are saved
+        ray_type, rgb_mode, grad_mode = _parse_mode(ray_type)
+        want_rgb, flags = rgb_mode is not False, L.SAVE_NO_APP if rgb_mode == "value" else 0
         rgb = torch.empty(N, S, 3, device=dev) if want_rgb else None
         sigma = torch.empty(N, S, device=dev)
         weight = torch.empty(N, S, device=dev)
         dists = torch.empty(N, S, device=dev)
-        saved, sbytes = _alloc_saved(ctx, 0, N, S, dev)
+        saved, sbytes = _alloc_saved(ctx, 0, N, S, dev, grad_mode, flags)
         ws = L.workspace(dev, (L.lib.rdrf_workspace_bytes if saved is not None else L.lib.rdrf_forward_workspace_bytes)(N, S))
         P = _static_struct(params)
         _attach_packed(field, P, params, False, False)
         cfg = _cfg_struct(field, ray_type)
-        L.check(L.lib.rdrf_static_fwd(C.byref(P), C.byref(cfg), L.ptr(rays), L.ptr(ts), L.ptr(xyz),
-                                      L.ptr(z), L.ptr(valid), N, S, L.ptr(rgb), L.ptr(sigma),
-                                      L.ptr(weight), L.ptr(dists), L.ptr(saved), C.c_size_t(sbytes),
-                                      L.ptr(ws), C.c_size_t(ws.numel()), L.stream_of(z)),
+        L.check(L.lib.rdrf_static_fwd_ex(C.byref(P), C.byref(cfg), L.ptr(rays), L.ptr(ts), L.ptr(xyz),
+                                         L.ptr(z), L.ptr(valid), N, S, L.ptr(rgb), L.ptr(sigma),
+                                         L.ptr(weight), L.ptr(dists), L.ptr(saved), C.c_size_t(sbytes),
+                                         L.ptr(ws), C.c_size_t(ws.numel()), L.stream_of(z), flags),
                 "rdrf_static_fwd")
-        ctx.field, ctx.ray_type, ctx.saved, ctx.want_rgb = field, ray_type, saved, want_rgb
+        if rgb_mode == "value":
+            ctx.mark_non_differentiable(rgb)
+        ctx.field, ctx.ray_type, ctx.saved, ctx.want_rgb = field, ray_type, saved, rgb_mode is True
         ctx.save_for_backward(rays, ts, xyz, z, valid, *params)
         return rgb, sigma, weight, dists
 
@@ -247,7 +288,7 @@ class _StaticFn(torch.autograd.Function):
     def backward(ctx, g_rgb, g_sigma, g_weight, g_dists):
         rays, ts, xyz, z, valid, *params = ctx.saved_tensors
         if g_rgb is not None and not ctx.want_rgb:
-            raise L.RdrfError("forward(..., rgb=False) did not run the appearance phase: no gradient can flow through rgb")
+            raise L.RdrfError("forward(..., rgb=False | 'value') saved no appearance rows: no gradient can flow through rgb")
         need = ctx.needs_input_grad
         if g_rgb is None and g_sigma is None and g_weight is None and not (need[2] or need[5]):
             # only `dists` is consumed downstream: it depends on z_vals and |d| alone, no parameter
@@ -291,22 +332,24 @@ class _DynamicFn(torch.autograd.Function):
         rays, ts, xyz, z, valid = _prep_inputs(rays, ts, xyz, z, valid)
         N, S = z.shape
         dev = z.device
-        want_rgb = not ray_type.endswith("-norgb")   # see _StaticFn
-        ray_type = ray_type.replace("-norgb", "")
+        ray_type, rgb_mode, grad_mode = _parse_mode(ray_type)   # see _StaticFn
+        want_rgb, flags = rgb_mode is not False, L.SAVE_NO_APP if rgb_mode == "value" else 0
         rgb = torch.empty(N, S, 3, device=dev) if want_rgb else None
         xyz_prime = torch.empty(N, S, 3, device=dev)
         sigma, weight, dists, blending = (torch.empty(N, S, device=dev) for _ in range(4))
-        saved, sbytes = _alloc_saved(ctx, 1, N, S, dev)
+        saved, sbytes = _alloc_saved(ctx, 1, N, S, dev, grad_mode, flags)
         ws = L.workspace(dev, (L.lib.rdrf_workspace_bytes if saved is not None else L.lib.rdrf_forward_workspace_bytes)(N, S))
         P = _dynamic_struct(params)
         _attach_packed(field, P, params, False, True)
         cfg = _cfg_struct(field, ray_type)
-        L.check(L.lib.rdrf_dynamic_fwd(C.byref(P), C.byref(cfg), L.ptr(rays), L.ptr(ts), L.ptr(xyz),
-                                       L.ptr(z), L.ptr(valid), N, S, L.ptr(blending), L.ptr(weight),
-                                       L.ptr(xyz_prime), L.ptr(rgb), L.ptr(sigma), L.ptr(dists),
-                                       L.ptr(saved), C.c_size_t(sbytes), L.ptr(ws),
-                                       C.c_size_t(ws.numel()), L.stream_of(z)), "rdrf_dynamic_fwd")
-        ctx.field, ctx.ray_type, ctx.saved, ctx.want_rgb = field, ray_type, saved, want_rgb
+        L.check(L.lib.rdrf_dynamic_fwd_ex(C.byref(P), C.byref(cfg), L.ptr(rays), L.ptr(ts), L.ptr(xyz),
+                                          L.ptr(z), L.ptr(valid), N, S, L.ptr(blending), L.ptr(weight),
+                                          L.ptr(xyz_prime), L.ptr(rgb), L.ptr(sigma), L.ptr(dists),
+                                          L.ptr(saved), C.c_size_t(sbytes), L.ptr(ws),
+                                          C.c_size_t(ws.numel()), L.stream_of(z), flags), "rdrf_dynamic_fwd")
+        if rgb_mode == "value":
+            ctx.mark_non_differentiable(rgb)
+        ctx.field, ctx.ray_type, ctx.saved, ctx.want_rgb = field, ray_type, saved, rgb_mode is True
         ctx.save_for_backward(rays, ts, xyz, z, valid, *params)
         return blending, weight, xyz_prime, rgb, sigma, dists
 
@@ -314,7 +357,7 @@ class _DynamicFn(torch.autograd.Function):
     def backward(ctx, g_blending, g_weight, g_xyz_prime, g_rgb, g_sigma, g_dists):
         rays, ts, xyz, z, valid, *params = ctx.saved_tensors
         if g_rgb is not None and not ctx.want_rgb:
-            raise L.RdrfError("forward(..., rgb=False) did not run the appearance phase: no gradient can flow through rgb")
+            raise L.RdrfError("forward(..., rgb=False | 'value') saved no appearance rows: no gradient can flow through rgb")
         need = ctx.needs_input_grad
         if all(g is None for g in (g_blending, g_weight, g_xyz_prime, g_rgb, g_sigma)) and not (need[2] or need[5]):
             # only `dists` is consumed (pass E of the trainer feeds the dynamic field's dists to the
@@ -353,7 +396,7 @@ class _DynamicFn(torch.autograd.Function):
 
 class _SceneFlowFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, field, pts, ts, *params):
+    def forward(ctx, field, grad_mode, pts, ts, *params):
         ctx.set_materialize_grads(False)
         L.require_device(pts, ts)
         pts, ts = L.f32c(pts), L.f32c(ts)
@@ -361,7 +404,7 @@ class _SceneFlowFn(torch.autograd.Function):
         sf_f = torch.empty(N, S, 3, device=pts.device)
         sf_b = torch.empty(N, S, 3, device=pts.device)
         ws = L.workspace(pts.device, L.lib.rdrf_workspace_bytes(N, S))
-        saved, sbytes = _alloc_saved(ctx, 2, N, S, pts.device)
+        saved, sbytes = _alloc_saved(ctx, 2, N, S, pts.device, grad_mode)
         P = _dynamic_struct(params)
         _attach_packed(field, P, params, False, True)
         cfg = _cfg_struct(field, "ndc")
@@ -386,7 +429,7 @@ class _SceneFlowFn(torch.autograd.Function):
         P = _dynamic_struct(params)
         _attach_packed(ctx.field, P, params, True, True)
         cfg = _cfg_struct(ctx.field, "ndc")
-        g_pts = torch.zeros_like(pts) if ctx.needs_input_grad[1] else None
+        g_pts = torch.zeros_like(pts) if ctx.needs_input_grad[2] else None
         g_f = None if g_f is None else L.f32c(g_f)
         g_b = None if g_b is None else L.f32c(g_b)
         ws = L.workspace(pts.device, L.lib.rdrf_workspace_bytes(N, S))
@@ -398,16 +441,20 @@ class _SceneFlowFn(torch.autograd.Function):
         ctx.saved = None
         if fused:
             grads = [None] * len(params)
-        return (None, g_pts, None, *grads)
+        return (None, None, g_pts, None, *grads)
 
 
 # --------------------------------------------------------------------------------------------
 # compute_* / warp_coordinate: the per-point building blocks (rdrf_*_features_fwd/bwd)
 # --------------------------------------------------------------------------------------------
-def _feat_saved(ctx, dynamic, M, dev):
-    if not any(ctx.needs_input_grad):
+def _feat_saved(ctx, dynamic, M, dev, grad_mode=None):
+    """see _alloc_saved"""
+    if not _grad_mode(grad_mode) or not any(ctx.needs_input_grad):
+        SAVE_STATS[("feat%d" % int(dynamic), "none")] += 1
         return None, 0
     nbytes = int(L.lib.rdrf_features_saved_bytes(int(dynamic), M))
+    SAVE_STATS[("feat%d" % int(dynamic), "full")] += 1
+    SAVE_STATS[("feat%d" % int(dynamic), "bytes")] += nbytes
     return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
 
 
@@ -415,7 +462,7 @@ class _StaticFeatFn(torch.autograd.Function):
     """(density feature [M], appearance feature [M,27]) of the static field at normalised points"""
 
     @staticmethod
-    def forward(ctx, field, want_density, want_app, xn, *params):
+    def forward(ctx, field, grad_mode, want_density, want_app, xn, *params):
         ctx.set_materialize_grads(False)
         L.require_device(xn)
         xn = L.f32c(xn)
@@ -423,7 +470,7 @@ class _StaticFeatFn(torch.autograd.Function):
         dens = torch.empty(M, device=dev) if want_density else None
         app = torch.empty(M, 27, device=dev) if want_app else None
         ws = L.workspace(dev, L.lib.rdrf_features_workspace_bytes(M))
-        saved, sbytes = _feat_saved(ctx, 0, M, dev)
+        saved, sbytes = _feat_saved(ctx, 0, M, dev, grad_mode)
         P = _static_struct(params)
         _attach_packed(field, P, params, False, False)
         cfg = _cfg_struct(field, "ndc")
@@ -445,11 +492,11 @@ class _StaticFeatFn(torch.autograd.Function):
         ctx.field._det_bind()
         grads = ctx.field.fused_grads() if fused else [torch.zeros_like(p) for p in params]
         if g_dens is None and g_app is None:
-            return (None,) * (4 + len(params))
+            return (None,) * (5 + len(params))
         G, P = _static_struct(grads), _static_struct(params)
         _attach_packed(ctx.field, P, params, True, False)
         cfg = _cfg_struct(ctx.field, "ndc")
-        g_xn = torch.zeros_like(xn) if ctx.needs_input_grad[3] else None
+        g_xn = torch.zeros_like(xn) if ctx.needs_input_grad[4] else None
         g_dens = None if g_dens is None else L.f32c(g_dens)
         g_app = None if g_app is None else L.f32c(g_app)
         ws = L.workspace(dev, L.lib.rdrf_features_bwd_workspace_bytes(M))
@@ -460,7 +507,7 @@ class _StaticFeatFn(torch.autograd.Function):
         ctx.saved = None
         if fused:
             grads = [None] * len(params)
-        return (None, None, None, g_xn, *grads)
+        return (None, None, None, None, g_xn, *grads)
 
 
 class _DynFeatFn(torch.autograd.Function):
@@ -468,7 +515,7 @@ class _DynFeatFn(torch.autograd.Function):
     per-point times; `x` normalised (compute_*) or un-normalised (warp_coordinate)"""
 
     @staticmethod
-    def forward(ctx, field, want, x_is_normalized, x, t, *params):
+    def forward(ctx, field, grad_mode, want, x_is_normalized, x, t, *params):
         ctx.set_materialize_grads(False)
         L.require_device(x, t)
         x, t = L.f32c(x), L.f32c(t)
@@ -478,7 +525,7 @@ class _DynFeatFn(torch.autograd.Function):
         app = torch.empty(M, 27, device=dev) if "app" in want else None
         xp = torch.empty(M, 3, device=dev) if "warp" in want else None
         ws = L.workspace(dev, L.lib.rdrf_features_workspace_bytes(M))
-        saved, sbytes = _feat_saved(ctx, 1, M, dev)
+        saved, sbytes = _feat_saved(ctx, 1, M, dev, grad_mode)
         P = _dynamic_struct(params)
         _attach_packed(field, P, params, False, True)
         cfg = _cfg_struct(field, "ndc")
@@ -495,7 +542,7 @@ class _DynFeatFn(torch.autograd.Function):
     def backward(ctx, g_dens, g_blend, g_app, g_xp):
         x, t, *params = ctx.saved_tensors
         if all(g is None for g in (g_dens, g_blend, g_app, g_xp)):
-            return (None,) * (5 + len(params))
+            return (None,) * (6 + len(params))
         if ctx.saved is None:
             raise L.RdrfError("compute_*: backward called twice (the saved activations were released)")
         M, dev = x.shape[0], x.device
@@ -505,7 +552,7 @@ class _DynFeatFn(torch.autograd.Function):
         G, P = _dynamic_struct(grads), _dynamic_struct(params)
         _attach_packed(ctx.field, P, params, True, True)
         cfg = _cfg_struct(ctx.field, "ndc")
-        g_x = torch.zeros_like(x) if ctx.needs_input_grad[3] else None
+        g_x = torch.zeros_like(x) if ctx.needs_input_grad[4] else None
         c = lambda g: None if g is None else L.f32c(g)
         g_dens, g_blend, g_app, g_xp = c(g_dens), c(g_blend), c(g_app), c(g_xp)
         ws = L.workspace(dev, L.lib.rdrf_features_bwd_workspace_bytes(M))
@@ -517,7 +564,7 @@ class _DynFeatFn(torch.autograd.Function):
         ctx.saved = None
         if fused:
             grads = [None] * len(params)
-        return (None, None, None, g_x, None, *grads)
+        return (None, None, None, None, g_x, None, *grads)
 
 
 # --------------------------------------------------------------------------------------------
@@ -828,11 +875,11 @@ class TensorVMSplit(TensorBase):
         """xyz_sampled [M,3] NORMALISED coordinates -> sigma feature [M] (sum of the 24 VM products,
         before feature2density).  t_sampled / time_embedding_sampled are accepted and unused, as in
         the reference.  Differentiable wrt the density factors and the coordinates."""
-        return _StaticFeatFn.apply(self, True, False, xyz_sampled.reshape(-1, 3), *self._param_list())[0]
+        return _StaticFeatFn.apply(self, torch.is_grad_enabled(), True, False, xyz_sampled.reshape(-1, 3), *self._param_list())[0]
 
     def compute_appfeature(self, xyz_sampled, t_sampled=None, time_embedding_sampled=None):
         """xyz_sampled [M,3] normalised -> basis_mat(72 VM products) [M,27]"""
-        return _StaticFeatFn.apply(self, False, True, xyz_sampled.reshape(-1, 3), *self._param_list())[1]
+        return _StaticFeatFn.apply(self, torch.is_grad_enabled(), False, True, xyz_sampled.reshape(-1, 3), *self._param_list())[1]
 
     # models/tensoRF.py:63-98
     def vectorDiffs(self, vector_comps):
@@ -854,10 +901,13 @@ class TensorVMSplit(TensorBase):
     def forward(self, rays_chunk, ts_chunk, timeembeddings_chunk, xyz_sampled, z_vals, ray_valid,
                 white_bg=True, is_train=False, ray_type="ndc", N_samples=-1, rgb=True):
         """rgb=False (extension): the caller does not consume the colours (entry 6 of the tuple is None) and the
-        appearance phase -- gather, basis, RGB head: ~70 % of this field's forward work -- is not run."""
+        appearance phase -- gather, basis, RGB head: ~70 % of this field's forward work -- is not run.
+        rgb="value": the colours are computed and returned bit-identically, but as values only (not differentiable): the
+        appearance phase runs the inference kernel and saves no rows -- rows are saved only where a backward can read them.
+        Under torch.no_grad() no backward can exist and nothing at all is saved."""
         if timeembeddings_chunk is not None:
             raise NotImplementedError("timeembeddings_chunk is None at every reference call site")
-        rgb, sigma, weight, dists = _StaticFn.apply(self, ray_type if rgb else ray_type + "-norgb", rays_chunk, ts_chunk,
+        rgb, sigma, weight, dists = _StaticFn.apply(self, _call_mode(ray_type, rgb), rays_chunk, ts_chunk,
                                                     xyz_sampled, z_vals, ray_valid, *self._param_list())
         return (None, None, None, xyz_sampled, weight, None, rgb, sigma, z_vals, dists)
 
@@ -930,11 +980,11 @@ class TensorVMSplit_TimeEmbedding(TensorBase):
 
     def forward(self, rays_chunk, ts_chunk, timeembeddings_chunk, xyz_sampled, z_vals, ray_valid,
                 white_bg=True, is_train=False, ray_type="ndc", N_samples=-1, rgb=True):
-        """rgb=False (extension): see TensorVMSplit.forward"""
+        """rgb=False | "value" (extension): see TensorVMSplit.forward"""
         if timeembeddings_chunk is not None:
             raise NotImplementedError("timeembeddings_chunk is None at every reference call site")
         blending, weight, xyz_prime, rgb, sigma, dists = _DynamicFn.apply(
-            self, ray_type if rgb else ray_type + "-norgb", rays_chunk, ts_chunk, xyz_sampled, z_vals, ray_valid,
+            self, _call_mode(ray_type, rgb), rays_chunk, ts_chunk, xyz_sampled, z_vals, ray_valid,
             *self._param_list())
         return (None, None, blending, xyz_sampled, weight, xyz_prime, rgb, sigma, z_vals, dists)
 
@@ -956,14 +1006,14 @@ class TensorVMSplit_TimeEmbedding(TensorBase):
         return tv_family(self, reg, self.app_plane, self.app_line)
 
     def get_forward_backward_scene_flow(self, unnormalized_pts, t_sampled):
-        return _SceneFlowFn.apply(self, unnormalized_pts, t_sampled, *self._param_list())
+        return _SceneFlowFn.apply(self, torch.is_grad_enabled(), unnormalized_pts, t_sampled, *self._param_list())
 
     def _features(self, want, x, t, normalized):
         x2 = x.reshape(-1, 3)
         t2 = t.reshape(-1)
         if t2.numel() != x2.shape[0]:
             raise L.RdrfError(f"compute_*: {x2.shape[0]} points but {t2.numel()} times")
-        return _DynFeatFn.apply(self, want, normalized, x2, t2, *self._param_list())
+        return _DynFeatFn.apply(self, torch.is_grad_enabled(), want, normalized, x2, t2, *self._param_list())
 
     def warp_coordinate(self, unnormalized_xyz_sampled, t_sampled):
         """models/tensoRF.py:521-541: (...,3) un-normalised points, (...) times -> warped un-normalised

@@ -305,7 +305,11 @@ def ray_pass(st, dy, rays, ts, n_samples, ray_type, rng, is_train=True, static_g
     """sampleXYZ -> static -> dynamic -> raw2outputs (one ray-pass).  The static field runs value-only unless
     `static_grad`; with dynamic=False (dead work of passes E / P3 / P4 skipped) zeros stand in for the dynamic
     outputs, which the static maps do not depend on; rgb_s / rgb_d = False: that field's colours are not consumed by
-    any loss of this pass (passes B-D, P1-P4) and its appearance phase is not run."""
+    any loss of this pass (passes B-D, P1-P4) and its appearance phase is not run; "value": computed, as values only
+    (fields.TensorVMSplit.forward).  With static_grad the dynamic evaluation is the dead work of passes E / P3 / P4: its
+    outputs feed maps no loss reads, and the only gradient that can reach it is that of `dists` for the rays / z_vals.  It
+    then saves no appearance rows, and when neither rays nor z_vals require grad (fixed poses) it runs under no_grad and
+    saves nothing -- rows are saved only where a backward can read them."""
     jit, jit_o = rng.jitter(n_samples, ray_type, rays.device) if is_train else (None, None)
     xyz, z, valid = sampleXYZ(dy, rays, n_samples, ray_type=ray_type, is_train=is_train, jitter=jit,
                               jitter_outer=jit_o)
@@ -318,7 +322,11 @@ def ray_pass(st, dy, rays, ts, n_samples, ray_type, rng, is_train=True, static_g
     sigma_s = o_s[7]
     rgb_s = _rgb_or_zeros(o_s[6], sigma_s)
     if dynamic:   # in passes E / P3 / P4 this evaluation is dead work the reference performs (autograd graph and all)
-        o_d = dy(rays, ts, None, xyz, z, valid, is_train=is_train, ray_type=ray_type, rgb=rgb_d)
+        dead = static_grad
+        if dead and rgb_d is True:
+            rgb_d = "value"
+        with torch.set_grad_enabled(torch.is_grad_enabled() and (not dead or rays.requires_grad or z.requires_grad)):
+            o_d = dy(rays, ts, None, xyz, z, valid, is_train=is_train, ray_type=ray_type, rgb=rgb_d)
         rgb_d, sigma_d, dists, blending, zv = _rgb_or_zeros(o_d[6], o_d[7]), o_d[7], o_d[9], o_d[2], o_d[8]
     else:
         o_d = None
@@ -369,8 +377,9 @@ def ray_passes(st, dy, rays_list, ts_list, n_samples, ray_type, rng, groups, rgb
     liveness, so that a batched call prunes what each of its passes would).  Same arithmetic and the same draw order
     (jitter, coin per pass, in pass order) as one ray_pass per entry; the persistent MLP kernels see 3-4x the tiles per
     launch (tail quantisation: 2.4 -> 3 tile rounds per wave becomes 7.3 -> 8) and fill their LDS images once.
-    Calls are capped at BATCH_MAX_SAMPLES samples.  rgb (list of bool per pass, default all True): passes whose colours no
-    loss consumes run both fields without their appearance phase (the static call is then cut at the flag changes).
+    Calls are capped at BATCH_MAX_SAMPLES samples.  rgb (list of True | False | "value" per pass, default all True): passes
+    whose colours no loss consumes run both fields without their appearance phase (False) or with colours that are values
+    only and save no appearance rows ("value"); the static call is cut at the flag changes.
     Returns one (o_s, o_d, outs, xyz) per pass; the per-pass tensors are views (unbind) of the batched outputs."""
     P, N, dev = len(rays_list), rays_list[0].shape[0], rays_list[0].device
     PASSES.update(static=P, dynamic=P)
@@ -383,13 +392,14 @@ def ray_passes(st, dy, rays_list, ts_list, n_samples, ray_type, rng, groups, rgb
     rgb = [True] * P if rgb is None else list(rgb)
     o_ss, o_ds = [None] * P, [None] * P
     runs, lo = [], 0   # maximal runs of passes with the same colour flag: one static call each
+    want_s = [bool(f) for f in rgb]   # (the static call is value-only: "value" and True are the same call there)
     for p in range(1, P + 1):
-        if p == P or rgb[p] != rgb[lo]:
+        if p == P or want_s[p] != want_s[lo]:
             runs.append(list(range(lo, p)))
             lo = p
     for run in runs:
         for g in batch_groups(run, ns):
-            for k, o in zip(g, batched_field(st, rays_list, ts_list, samples, g, ray_type, grad=False, rgb=rgb[run[0]])):
+            for k, o in zip(g, batched_field(st, rays_list, ts_list, samples, g, ray_type, grad=False, rgb=want_s[run[0]])):
                 o_ss[k] = o
     for group in groups:
         assert list(group) == list(range(group[0], group[0] + len(group)))
@@ -416,7 +426,8 @@ class Trainer:
                  dp_mode="allreduce", lr_pose=3e-3, dp_exact_stats=False, batch_passes=None, graph=False):
         """dead_work: also run what the reference computes although nothing consumes it (SURVEY.md 3.1 liveness table):
         the dynamic-field forward of passes E / P3 / P4, and the appearance phase (colours) of both fields in passes B-D
-        and P1-P4, whose rgb maps no loss term reads; off = skipped, losses and gradients identical.
+        and P1-P4, whose rgb maps no loss term reads; off = skipped, losses and gradients identical.  Dead work is computed
+        but never saved for a backward that cannot read it (forward(rgb="value"), no_grad: see ray_pass).
         dp_exact_stats (data-parallel runs): the batch statistics of the losses -- the mask sums of the masked means
         (train.py:1391-1394, 1522-1524, 1828-1832, 1277-1291) and the per-frame medians / deviations / ray counts of
         the monocular depth losses (train.py:797-807) -- are those of the WHOLE batch (one all-reduce of ~30 pairs of
@@ -482,6 +493,11 @@ class Trainer:
             dist.all_reduce(g, op=dist.ReduceOp.SUM, group=dp[0])
             return g, dp[2]
         return LossTerms(reducer)
+
+    def _dead_rgb(self):
+        """the rgb mode of the fields in passes whose colours no loss reads (B-D, P1-P4): with dead_work they are computed as
+        the reference does, but as values only -- no gradient can arrive for them, so no appearance rows are saved"""
+        return "value" if self.dead_work else False
 
     # ---- geometry ----------------------------------------------------------------------------------
     def focal(self):
@@ -572,7 +588,7 @@ class Trainer:
             # dead work the reference computes (self.dead_work keeps it)
             pA, pB, pC, pD = ray_passes(self.st, self.dy, [rays_d, rays_d, rays_n_of[1], rays_n_of[-1]],
                                         [ts, b["ts_rand"], ts + dt, ts - dt], S, rt, rng, groups,
-                                        rgb=[True] + [self.dead_work] * 3)
+                                        rgb=[True] + [self._dead_rgb()] * 3)
             osA, oA, outA, xyzA = pA
             batched = {"B": pB, 1: pC, -1: pD}
         else:
@@ -604,7 +620,7 @@ class Trainer:
             Ld.add(k_dist, "identity", distloss_rays(outA[11], oA[8].detach(), 1.0 / S))
         # ---- pass B (second random time)
         _, oB, outB, _ = batched["B"] if batched else ray_pass(self.st, self.dy, rays_d, b["ts_rand"], S, rt, rng,
-                                                               rgb_s=self.dead_work, rgb_d=self.dead_work)
+                                                               rgb_s=self._dead_rgb(), rgb_d=self._dead_rgb())
         if late:
             Ld.add(0.01, "identity", skewed(outB[12]))                                  # :1248-1266
             Ld.add(0.01, "abs", outB[12])                                               # novel_view_time_mask_loss, :1267
@@ -633,8 +649,8 @@ class Trainer:
                 _, oN, outN, _ = batched[sgn]
             else:
                 rays_n = self.rays_for(ids, poses_d, focal_d, uv=grid + flow_t, view_shift=sgn)
-                _, oN, outN, _ = ray_pass(self.st, self.dy, rays_n, ts + sgn * dt, S, rt, rng, rgb_s=self.dead_work,
-                                          rgb_d=self.dead_work)
+                _, oN, outN, _ = ray_pass(self.st, self.dy, rays_n, ts + sgn * dt, S, rt, rng, rgb_s=self._dead_rgb(),
+                                          rgb_d=self._dead_rgb())
             _, ind_disp_n = induce_flow(H, W, focal_d, pose_n, outN[11], oN[3], px, rays_n, ray_type=rt)
             Ld.add(0.04 * temp, "abs", ind_disp, ind_disp_n, w=mask_t, norm="weight")   # :1522-1524, 1619-1621
             if w_dist > 0:
@@ -689,13 +705,14 @@ class Trainer:
             ns = rays.shape[0] * smp[0][1].shape[1]
             o_P = [None] * 4
             for g in batch_groups(range(4), ns):
-                for k, o in zip(g, batched_field(self.st, rays_P, ts_P, smp, g, rt, rgb=self.dead_work)):
+                for k, o in zip(g, batched_field(self.st, rays_P, ts_P, smp, g, rt, rgb=self._dead_rgb())):
                     o_P[k] = o   # (P1-P4 read weights / depths only: train.py:1951-2311)
             d_P = [None, None]
             if self.dead_work:   # the dynamic forwards of P3 / P4: dead work the reference performs
                 PASSES.update(dynamic=2, dynamic_dead=2)
                 for g in batch_groups((2, 3), ns):
-                    for k, o in zip(g, batched_field(self.dy, rays_P, ts_P, smp, g, rt)):
+                    live = any(rays_P[k].requires_grad or smp[k][1].requires_grad for k in g)   # `dists` -> rays / z_vals
+                    for k, o in zip(g, batched_field(self.dy, rays_P, ts_P, smp, g, rt, grad=live, rgb="value")):
                         d_P[k - 2] = o
             batched = (rays_P, smp, coins, o_P, d_P)
         for k, (sgn, flow_t, mask_t) in enumerate(((1, b["flow_f"], b["mask_f"]), (-1, b["flow_b"], b["mask_b"]))):
@@ -711,7 +728,7 @@ class Trainer:
                 jit, jit_o = rng.jitter(S, rt, rays.device)
                 xyz, z, valid = sampleXYZ(self.st, rays_n, S, ray_type=rt, is_train=True, jitter=jit, jitter_outer=jit_o)
                 PASSES.update(static=1, static_grad=1)
-                o = self.st(rays_n, ts, None, xyz, z, valid, is_train=True, ray_type=rt, rgb=self.dead_work)
+                o = self.st(rays_n, ts, None, xyz, z, valid, is_train=True, ray_type=rt, rgb=self._dead_rgb())
             _, ind_disp_n = induce_flow(H, W, focal, pose_n, o[4], xyz, px, rays_n, ray_type=rt)
             Ls.add(self._coef(0.04, "temp_static", temp_static), "abs", ind_disp, ind_disp_n, w=mm, norm="weight")  # :2012-2017, 2079-2084
         # per-frame median-normalised monocular depth of the static field on the background rays
@@ -736,7 +753,7 @@ class Trainer:
             else:
                 rays_n = self.rays_for(ids, poses, focal, uv=uv_n)
                 _, _, outN, _ = ray_pass(self.st, self.dy, rays_n, ts, S, rt, rng, static_grad=True, dynamic=self.dead_work,
-                                         rgb_s=self.dead_work)
+                                         rgb_s=self._dead_rgb())
             Ls.add(50.0 * temp_disp_tv, "square", inv_d, 1.0 / torch.clamp(outN[5], min=1e-6))  # :2293-2305
 
     def step(self, shard=None):

@@ -1,6 +1,7 @@
 """Per-kernel HIP-event times of the FORWARD field kernels on a fixed workload (reference-initialised weights, fixed rays:
 app-mask fractions ~0.49 static / ~0.74 dynamic, the state the driver's 20-step window starts from), in inference mode
-(no saved rows) and in training mode (rows saved), for A/B runs of kernel builds:
+(under torch.no_grad(): no saved buffer, the SAVE=false instantiations -- fields._alloc_saved follows the grad mode) and in
+training mode (rows saved), for A/B runs of kernel builds:
 
     RDRF_LIB=$PWD/robust-dynrf_amd/abl_x.so python tools/fwd_ab.py [N=16384] [S=115] [grid=141,157,94]
 """
