@@ -552,6 +552,42 @@ size_t rdrf_ssim_workspace_bytes(int H, int W, int C);
 int rdrf_ssim(const float* img0, const float* img1, int H, int W, int C, float max_val, double* mean_out, float* map_out,
               void* ws, size_t ws_bytes, rdrf_stream_t stream);
 
+/* ---- batch assembly of a device-resident training set (train.py:1043-1060: `allrgbs[ray_idx]`, `alldisps[ray_idx]`,
+ * `allflows_f[ray_idx]`, ... one index launch per tensor there) -----------------------------------------------------------
+ * The per-pixel tables of T frames of H x W pixels, flat over (T, H, W); total = T H W, T >= 2.  Pixel centre, integer
+ * pixel, frame and time are not stored: they are arithmetic on the index (ids2pixel, train.py:96-103). */
+typedef struct RdrfSceneTables {
+  int T, H, W;
+  int rgb_u8;            /* 1: rgb is uint8 [total][3], converted as (float)x / 255.0f; 0: fp32 [total][3] */
+  const void* rgb;
+  const float* disp;     /* [total]; NULL: the batch's disp is zeros */
+  const float* flow_f;   /* [total][2], pixels, 8-byte aligned */
+  const float* flow_b;
+  const uint8_t* masks;  /* [total]: bit 0 foreground mask, bit 1 forward flow mask, bit 2 backward flow mask; a scene
+                            without a foreground mask leaves bit 0 clear (the batch's fg is zeros) */
+} RdrfSceneTables;
+/* Everything one iteration reads of its N rays; every pointer is required. */
+typedef struct RdrfBatch {
+  float* rgb;      /* [N][3] */
+  float* disp;     /* [N] */
+  float* fg;       /* [N] 0 / 1 */
+  float* mask_f;   /* [N] 0 / 1 */
+  float* mask_b;   /* [N] 0 / 1 */
+  float* flow_f;   /* [N][2], 8-byte aligned (as flow_b, grid, px) */
+  float* flow_b;   /* [N][2] */
+  float* ts;       /* [N] (float)view * (float)(2.0 / (T - 1)) - 1.0f */
+  float* ts_rand;  /* [N] the same of ids2: the second, independent sampler's times (train.py:1011-1012) */
+  float* grid;     /* [N][2] pixel centre (col + 0.5, row + 0.5) */
+  float* px;       /* [N][2] integer pixel (col, row): `allgrids` (train.py:983-988) */
+  int64_t* view;   /* [N] frame index id / (H W) */
+} RdrfBatch;
+/* ONE launch writes every tensor of `out` for the flat pixel indices ids[N] (and ts_rand for ids2[N]).  Each fp32
+ * operation is rounded on its own, in the order above: the values are bit-identical to gathers from fp32 tables built
+ * with those expressions.  An index outside [0, total) is UNDEFINED (not checked: the indices live on the device and no
+ * entry point synchronises).  N = 0 is a no-op that touches nothing. */
+int rdrf_gather_batch(const RdrfSceneTables* tables, const int64_t* ids, const int64_t* ids2, int N, RdrfBatch* out,
+                      rdrf_stream_t stream);
+
 /* ---- process-wide choice of the density / blending scatter of the dynamic field's backward (models/tensoRF.py:646-811,
  * grid_sampler_2d_backward semantics either way): RDRF_SCATTER_RAY = ray tiles, RDRF_SCATTER_SORTED = samples grouped by
  * plane cell first (about 10x fewer memory-side atomic requests, a fixed grouping cost per launch), RDRF_SCATTER_AUTO

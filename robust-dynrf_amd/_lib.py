@@ -76,6 +76,19 @@ class MotionCamsC(C.Structure):
                 ("first_pixel", C.c_int64)]
 
 
+# RdrfSceneTables / RdrfBatch (include/rodynrf.h): the tables of a device-resident training set and the tensors of one batch
+class SceneTablesC(C.Structure):
+    _fields_ = [("T", C.c_int), ("H", C.c_int), ("W", C.c_int), ("rgb_u8", C.c_int), ("rgb", C.c_void_p), ("disp", C.c_void_p),
+                ("flow_f", C.c_void_p), ("flow_b", C.c_void_p), ("masks", C.c_void_p)]
+
+
+BATCH_OUTPUTS = ("rgb", "disp", "fg", "mask_f", "mask_b", "flow_f", "flow_b", "ts", "ts_rand", "grid", "px", "view")
+
+
+class BatchC(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in BATCH_OUTPUTS]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -140,6 +153,7 @@ def _load():
     lib.rdrf_ssim_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.rdrf_ssim.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.rdrf_gather_batch.argtypes = [C.POINTER(SceneTablesC), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(BatchC), C.c_void_p]
     lib.rdrf_selftest_layer.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_size_t, C.c_void_p]
     lib.rdrf_prof_get.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
@@ -171,6 +185,7 @@ SYMBOLS = [
     "rdrf_render_workspace_bytes", "rdrf_render_fwd", "rdrf_render_chunks_workspace_bytes", "rdrf_render_chunks_fwd",
     "rdrf_render_maps_fwd", "rdrf_render_chunks_maps_fwd", "rdrf_camera_rays", "rdrf_ssim_workspace_bytes", "rdrf_ssim",
     "rdrf_render_motion_workspace_bytes", "rdrf_render_motion_fwd", "rdrf_flow_to_image_workspace_bytes", "rdrf_flow_to_image",
+    "rdrf_gather_batch",
     "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_selftest_layer", "rdrf_prof_reset",
     "rdrf_prof_enable", "rdrf_prof_get",
 ]

@@ -24,9 +24,10 @@ outputs (train.py:1380-1625), every static-field loss is independent of the dyna
 runs in two phases -- static first -- and the data-parallel exchange of the static gradients overlaps the
 dynamic backward (optim.FlatAdam.begin_exchange).
 
-The dataset (RGB, RAFT flow, DPT disparity, masks) is synthetic: random tensors of the right shape resident
-in HBM.  Losses keep every term that decides which hot-path outputs carry gradient; there is no
-per-iteration host sync (``.item()``): losses and the per-frame medians stay on the device.
+The dataset (RGB, RAFT flow, DPT disparity, masks) is synthetic by default: random tensors of the right shape resident
+in HBM (SyntheticScene: what the benchmark times); Trainer(data=scene.Scene(...)) trains on a video given as arrays, and
+Trainer.fit / save / load are the run around the iteration (resolution schedule, checkpoints, resume).  Losses keep
+every term that decides which hot-path outputs carry gradient; there is no per-iteration host sync (``.item()``): losses and the per-frame medians stay on the device.
 """
 import collections
 import math
@@ -55,7 +56,7 @@ def scene_config(name="nvidia", stage="stage0"):
     if name == "nvidia":
         cfg = dict(aabb=NDC_AABB, near_far=[0.0, 1.0], T=12, H=135, W=240, ray_type="ndc", batch_size=4096,
                    static_head="MLP_Fea", optimize_poses=False, tv_density=1.0, tv_app=1.0, dist_static=0.0,
-                   dist_dynamic=0.01, l1_weight=0.0)
+                   dist_dynamic=0.01, l1_weight=0.0, N_voxel_init=128 ** 3, N_voxel_final=300 ** 3)
         # up1..up3: the intermediate grids of the resolution schedule (train.py:937-947: N_voxel_list linear in log
         # space between N_voxel_init = 128^3 and N_voxel_final = 300^3, utils.py:58-65 N_to_reso / cal_n_samples)
         stages = {"stage0": ([141, 157, 94], 115), "up1": ([174, 194, 116], 142), "up2": ([216, 240, 144], 176),
@@ -63,13 +64,14 @@ def scene_config(name="nvidia", stage="stage0"):
     elif name == "nvidia_no_poses":
         cfg = dict(aabb=NDC_AABB, near_far=[0.0, 1.0], T=12, H=135, W=240, ray_type="ndc", batch_size=4096,
                    static_head="MLP_Fea", optimize_poses=True, tv_density=0.0, tv_app=0.0, dist_static=0.01,
-                   dist_dynamic=0.01, l1_weight=0.0)
+                   dist_dynamic=0.01, l1_weight=0.0, N_voxel_init=16 ** 3, N_voxel_final=640 ** 3)
         stages = {"stage0": ([17, 19, 11], 13), "final": ([706, 786, 471], 578), "huge": ([706, 786, 471], 578)}
     elif name == "davis":
         # DAVIS 480p frames (854 x 480) at downsample_train = 2; 50 frames; contracted rays to far = 256
         cfg = dict(aabb=[[-2.0, -2.0, -2.0], [2.0, 2.0, 2.0]], near_far=[0.0, 256.0], T=50, H=240, W=427,
                    ray_type="contract", batch_size=8192, static_head="MLP_Fea_TimeEmbedding", optimize_poses=True,
-                   tv_density=0.1, tv_app=0.01, dist_static=0.02, dist_dynamic=0.005, l1_weight=8e-5)
+                   tv_density=0.1, tv_app=0.01, dist_static=0.02, dist_dynamic=0.005, l1_weight=8e-5,
+                   N_voxel_init=16 ** 3, N_voxel_final=256 ** 3)
         stages = {"stage0": ([16, 16, 16], 13), "final": ([256, 256, 256], 221)}
     else:
         raise ValueError(name)
@@ -95,6 +97,39 @@ def resolution_schedule(name="nvidia"):
     cfg = scene_config(name, "stage0")
     edges = [0] + cfg["upsamp_list"] + [cfg["n_iters"]]
     return [(st, edges[i], edges[i + 1]) for i, st in enumerate(["stage0", "up1", "up2", "up3", "final"])]
+
+
+def N_to_reso(n_voxels, aabb):
+    """grid of about n_voxels cubic voxels filling the box (utils.py:58-61), in fp32 torch as the reference computes it:
+    the truncation of .long() depends on the fp32 rounding of the cube root and the quotient"""
+    lo, hi = torch.as_tensor(aabb, dtype=torch.float32)
+    extent = hi - lo
+    voxel = (extent.prod() / n_voxels).pow(1 / 3)
+    return (extent / voxel).long().tolist()
+
+
+def cal_n_samples(reso, step_ratio=0.5):
+    """samples per ray: the grid's diagonal in voxels over the step ratio (utils.py:64-65; fp64, truncated)"""
+    return int(math.sqrt(sum(float(r) ** 2 for r in reso)) / step_ratio)
+
+
+def resolution_stages(cfg):
+    """[(first iteration, grid, n_samples)] of a run of `cfg`: the voxel counts are linear in log space between
+    cfg["N_voxel_init"] and cfg["N_voxel_final"] (train.py:937-947, fp32 linspace / exp / round), one per entry of
+    cfg["upsamp_list"]; the grid changes AFTER the optimiser step of iteration upsamp_list[k] (train.py:2582-2587), so
+    stage k + 1 first runs at upsamp_list[k] + 1.  n_samples = min(cfg["nSamples"] (1e6), cal_n_samples(grid,
+    cfg["step_ratio"] (2.0))) (train.py:870-871, 2585)."""
+    ups = list(cfg["upsamp_list"])
+    aabb = torch.tensor(cfg["aabb"], dtype=torch.float32)
+    cap, ratio = int(cfg.get("nSamples", 1e6)), cfg.get("step_ratio", 2.0)
+    counts = torch.round(torch.exp(torch.linspace(math.log(cfg["N_voxel_init"]), math.log(cfg["N_voxel_final"]),
+                                                  len(ups) + 1))).long().tolist()
+    counts[0] = cfg["N_voxel_init"]   # train.py:870: the first grid comes from the count itself, not from exp(log(.))
+    out = []
+    for first, n in zip([0] + [u + 1 for u in ups], counts):
+        reso = N_to_reso(n, aabb)
+        out.append((first, reso, min(cap, cal_n_samples(reso, ratio))))
+    return out
 
 
 def balloon1_config(stage="stage0"):
@@ -423,8 +458,11 @@ def masked_mean(x, m):
 
 class Trainer:
     def __init__(self, cfg, device, weights="dense", lr_init=0.02, lr_basis=1e-3, dead_work=False,
-                 dp_mode="allreduce", lr_pose=3e-3, dp_exact_stats=False, batch_passes=None, graph=False):
-        """dead_work: also run what the reference computes although nothing consumes it (SURVEY.md 3.1 liveness table):
+                 dp_mode="allreduce", lr_pose=3e-3, dp_exact_stats=False, batch_passes=None, graph=False, data=None):
+        """data: the training set, an object with SyntheticScene's interface (scene.Scene: a video from arrays; T, H, W and,
+        unless it is optimised, the focal length are then the scene's, and a config without a "grid" starts at the grid of its
+        resolution_stages); default: SyntheticScene(cfg).
+        dead_work: also run what the reference computes although nothing consumes it (SURVEY.md 3.1 liveness table):
         the dynamic-field forward of passes E / P3 / P4, and the appearance phase (colours) of both fields in passes B-D
         and P1-P4, whose rgb maps no loss term reads; off = skipped, losses and gradients identical.  Dead work is computed
         but never saved for a backward that cannot read it (forward(rgb="value"), no_grad: see ray_pass).
@@ -445,12 +483,17 @@ class Trainer:
         self.batch_passes = (os.environ.get("RDRF_BATCH_PASSES", "1") != "0") if batch_passes is None else bool(batch_passes)
         self.dead_work = dead_work
         self.dp_exact_stats = bool(dp_exact_stats)
+        if data is not None:
+            data.bind(cfg)
+            if "grid" not in cfg:
+                it0 = int(cfg.get("start_iteration", 0))
+                _, cfg["grid"], cfg["n_samples"] = [s for s in resolution_stages(cfg) if s[0] <= it0][-1]
         self.cfg = cfg
         self.device = device
         self.st, self.dy = build_fields(cfg, device)
         if weights == "sparse":
             sparsify_(self.st, self.dy, cfg, device)
-        self.data = SyntheticScene(cfg, device)
+        self.data = SyntheticScene(cfg, device) if data is None else data
         lr_factor = cfg.get("lr_decay_target_ratio", 0.1) ** (1.0 / cfg.get("n_iters", 100000))   # train.py:926-930
         self.opt = FlatAdam([self.st, self.dy], lr_init, lr_basis, betas=(0.9, 0.99), lr_factor=lr_factor,
                             mode=dp_mode)
@@ -901,22 +944,118 @@ class Trainer:
         self.opt.step()
         self.it += 1
 
-    def upsample(self, grid, n_samples=None):
+    def upsample(self, grid, n_samples=None, iteration=None):
         """train.py:2582-2606: both fields to the new grid, a NEW Adam (moments dropped) whose learning rates restart
         at lr_init / lr_basis (lr_upsample_reset = 1, opt.py:73-77); the pose rate restarts at lr_pose, the focal rate
-        is switched on from upsamp_list[3]."""
+        is switched on from upsamp_list[3].  iteration: the iteration the reference's `iteration` would hold (default:
+        self.it; fit() passes the iteration whose optimiser step has just run)."""
+        iteration = self.it if iteration is None else int(iteration)
         self.st.upsample_volume_grid(grid)
         self.dy.upsample_volume_grid(grid)
         self.cfg["grid"] = list(grid)
         if n_samples is not None:
             self.cfg["n_samples"] = int(n_samples)
-        self.opt.rebuild(iteration=self.it)
+        self.opt.rebuild(iteration=iteration)
         self._graphs, self._graph_seen = {}, None   # captured iterations hold the old factor tensors
         if self.optimize_poses and self.opt.lr_upsample_reset:
             self.opt_pose.param_groups[0]["lr"] = self.lr_pose
-            if self.it >= self.cfg.get("upsamp_list", [0, 0, 0, 0])[3]:
+            if iteration >= self.cfg.get("upsamp_list", [0, 0, 0, 0])[3]:
                 self.opt_focal.param_groups[0]["lr"] = self.lr_pose
         self.grad_flats = self.opt.grad_flats()
+
+    # ---- a run: the loop of train.py:1032-2621 ----------------------------------------------------------------------
+    def fit(self, n_iters=None, callback=None):
+        """step() + finish_step() until cfg["n_iters"], or for n_iters more iterations; after the optimiser step of an
+        iteration listed in cfg["upsamp_list"] both fields go to the next grid of resolution_stages(cfg) (train.py:2582-2606).
+        callback(trainer, it, loss) ends every iteration (after the upsample, if any) with the iteration's loss as a device
+        tensor: nothing here waits for the device.  Returns the last loss tensor.  (Past n_iters // 2 finish_step zeroes
+        the pose rates before the upsample restarts them, the reference after, train.py:2608-2610: an upsample that late is in no
+        shipped config.)"""
+        c = self.cfg
+        end = int(c["n_iters"]) if n_iters is None else min(int(c["n_iters"]), self.it + int(n_iters))
+        ups = list(c.get("upsamp_list", []))
+        stages = resolution_stages(c) if ups else []
+        loss = None
+        while self.it < end:
+            it = self.it
+            loss = self.step()
+            self.finish_step()
+            if it in ups:
+                _, grid, n_samples = stages[ups.index(it) + 1]
+                self.upsample(grid, n_samples, iteration=it)
+            if callback is not None:
+                callback(self, it, loss)
+        return loss
+
+    # ---- state of a run ---------------------------------------------------------------------------------------------
+    def save(self, prefix):
+        """prefix.th / prefix_static.th: the dynamic and the static field in the reference's checkpoint format with the
+        pose matrices [T,3,4] and the focal length (train.py:2612-2621), and prefix_state.th: what a run needs beside them
+        to continue -- iteration, grid, n_samples, Adam moments / step count / rates, pose table and field of view with
+        their Adam state, the sampler's seed, the state of the iteration's random draws (with the device generator's, which
+        refills the jitter pool)."""
+        poses_mtx = pose_to_mtx(self.pose_table().detach()).cpu()
+        focal = self.focal()
+        focal = focal.detach().cpu() if torch.is_tensor(focal) else torch.tensor(float(focal))
+        self.dy.save(poses_mtx, focal, prefix + ".th")
+        self.st.save(poses_mtx, focal, prefix + "_static.th")
+        rng = self.rng
+        if isinstance(rng, GraphRng):
+            rs = dict(kind="graph", pool=rng.pool.cpu(), coins=rng.coins.cpu(), frozen=rng.frozen)
+        else:
+            rs = dict(kind="step", gen=rng.gen.get_state(), pool=None if rng._pool is None else rng._pool.cpu(), cur=rng._cur)
+        state = dict(it=self.it, grid=list(self.cfg["grid"]), n_samples=int(self.cfg["n_samples"]),
+                     adam=dict(t=self.opt.t, lr0=self.opt.lr0, lr1=self.opt.lr1,
+                               m=[s["m"].cpu() for s in self.opt.state], v=[s["v"].cpu() for s in self.opt.state]),
+                     sampler_seed=getattr(self.data, "seed", None), rng=rs,
+                     device_rng=torch.cuda.get_rng_state(self.device) if torch.device(self.device).type == "cuda" else None)
+        if self.optimize_poses:
+            state["pose"] = dict(poses=self.poses.detach().cpu(), fov=self.fov.detach().cpu(),
+                                 opt_pose=self.opt_pose.state_dict(), opt_focal=self.opt_focal.state_dict())
+        torch.save(state, prefix + "_state.th")
+
+    def load(self, prefix):
+        """restore what save(prefix) wrote into a trainer built on the same scene and config (single process; the fields
+        are brought to the saved grid first)"""
+        state = torch.load(prefix + "_state.th", map_location="cpu", weights_only=False)
+        if "pose" in state and not self.optimize_poses:
+            raise ValueError("the saved run optimised its poses, this trainer does not")
+        self.it = int(state["it"])
+        if list(state["grid"]) != list(self.cfg["grid"]):
+            self.upsample(state["grid"], state["n_samples"])
+        self.cfg["n_samples"] = int(state["n_samples"])
+        for f, path in ((self.dy, prefix + ".th"), (self.st, prefix + "_static.th")):
+            f.load(torch.load(path, map_location="cpu", weights_only=False))   # in place: the flat parameter buffers stay
+            f._pack_epoch += 1
+        self._graphs, self._graph_seen, self._c2w_fixed = {}, None, None
+        a = state["adam"]
+        self.opt.t, self.opt.lr0, self.opt.lr1 = int(a["t"]), float(a["lr0"]), float(a["lr1"])
+        for s, m, v in zip(self.opt.state, a["m"], a["v"]):
+            s["m"].copy_(m)
+            s["v"].copy_(v)
+        if self.optimize_poses:
+            p = state["pose"]
+            with torch.no_grad():
+                self.poses.copy_(p["poses"])
+                self.fov.copy_(p["fov"])
+            self.opt_pose.load_state_dict(p["opt_pose"])
+            self.opt_focal.load_state_dict(p["opt_focal"])
+        if state["sampler_seed"] is not None and hasattr(self.data, "seed"):
+            self.data.seed = int(state["sampler_seed"])
+            self.data._perms.clear()
+        rs = state["rng"]
+        if rs["kind"] == "graph":
+            self.rng = GraphRng(self.device)
+            self.rng.pool.copy_(rs["pool"])
+            self.rng.coins.copy_(rs["coins"])
+            self.rng.frozen = rs["frozen"]
+        else:
+            self.rng = StepRng()
+            self.rng.gen.set_state(rs["gen"])
+            self.rng._pool = None if rs["pool"] is None else rs["pool"].to(self.device)
+            self.rng._cur = rs["cur"]
+        if state["device_rng"] is not None:
+            torch.cuda.set_rng_state(state["device_rng"], self.device)
 
 
 @torch.no_grad()

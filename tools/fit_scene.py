@@ -1,0 +1,64 @@
+"""Reconstruct a video from arrays:   python tools/fit_scene.py scene.npz out_dir [--config davis] [--iters N] [--graph]
+
+scene.npz holds the arguments of rodynrf.Scene under their own names (rgb [T,H,W,3] uint8 | float32, flow_f / flow_b
+[T,H,W,2], flow_mask_f / flow_mask_b [T,H,W], optionally disp, fg_mask, poses [T,3,4], focal, and held-out views as
+heldout_c2w [K,3,4], heldout_t [K], heldout_rgb [K,H,W,3]).  The run follows the config's resolution schedule
+(rodynrf.resolution_stages) and writes out_dir/run.th, run_static.th (the reference's checkpoint format), run_state.th (what
+Trainer.load needs to continue the run) and metrics.json (PSNR / SSIM of the training frames and of the held-out views).
+--resume continues from out_dir/run_state.th."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import rodynrf  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("npz")
+    ap.add_argument("out")
+    ap.add_argument("--config", default=None, help="nvidia | nvidia_no_poses | davis (default: nvidia with poses, else nvidia_no_poses)")
+    ap.add_argument("--iters", type=int, default=None, help="iterations of this call (default: to the config's n_iters)")
+    ap.add_argument("--batch-size", type=int, default=None)
+    ap.add_argument("--graph", action="store_true", help="replay captured iterations (single GPU)")
+    ap.add_argument("--resume", action="store_true")
+    ap.add_argument("--seed", type=int, default=20211202)
+    ap.add_argument("--log-every", type=int, default=1000)
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    scene = rodynrf.Scene.from_npz(a.npz, device=dev, seed=a.seed)
+    cfg = rodynrf.scene_config(a.config or ("nvidia" if scene.has_poses else "nvidia_no_poses"))
+    for k in ("T", "H", "W", "grid", "n_samples"):    # the scene's shape, the schedule's first grid
+        cfg.pop(k, None)
+    if a.batch_size:
+        cfg["batch_size"] = a.batch_size
+    tr = rodynrf.Trainer(cfg, dev, graph=a.graph, data=scene)
+    os.makedirs(a.out, exist_ok=True)
+    prefix = os.path.join(a.out, "run")
+    if a.resume:
+        tr.load(prefix)
+    log = []
+
+    def callback(trainer, it, loss):
+        if it % a.log_every == 0:
+            log.append((it, loss))     # device tensors: read once, at the end
+
+    tr.fit(n_iters=a.iters, callback=callback)
+    tr.save(prefix)
+    metrics = dict(iterations=tr.it, grid=tr.cfg["grid"], n_samples=tr.cfg["n_samples"],
+                   loss=[(it, float(l)) for it, l in log], train=rodynrf.evaluate(tr, scene, frames="train"))
+    if scene.heldout:
+        metrics["heldout"] = rodynrf.evaluate(tr, scene, frames="heldout")
+    with open(os.path.join(a.out, "metrics.json"), "w") as f:
+        json.dump(metrics, f, indent=1)
+    print(json.dumps({k: (v if not isinstance(v, dict) else {"psnr_mean": v["psnr_mean"], "ssim_mean": v["ssim_mean"]})
+                      for k, v in metrics.items() if k != "loss"}))
+
+
+if __name__ == "__main__":
+    main()
