@@ -1,0 +1,91 @@
+// rdrf_bwd_host.hpp -- host interface between the backward entry points (rdrf_bwd.hip) and the units that launch the
+// kernels they define: the gradient scatter (rdrf_scatter.hip) and the dW products (rdrf_dw.hip).  Without relocatable
+// device code a kernel is launched from the unit that defines it, so these are plain functions, not kernel pointers.
+#pragma once
+#include "rdrf_host.hpp"
+
+struct BwdArgs;   // rdrf_bwd_dev.hpp
+
+// backward workspace (carve_bwd, rdrf_bwd.hip)
+struct BwdWs {
+  float* dfs;            // sorted scatter (dynamic field)
+  float* dfa;            // sorted appearance scatter: [N*S] records of DFA_FLOATS (capacity; count <= N*S entries are used)
+  unsigned *keys_in, *keys_out, *order;
+  int* counts;
+  void* sort_tmp;
+  size_t sort_tmp_bytes;
+  float* pk;
+  float* gf;       // static field: d(density feature) per sample, [N][ceil(S/32)*32]
+  float* grows1;
+  float* grows3;
+  float* dxw;
+  float* dxn;
+  float* dtout;
+  float* gsig;     // flat-tile density phase (BwdArgs::gsig, ::dtp)
+  float* dtp;
+};
+
+// ------------------------------------------------------------------------------------------------
+// gradient scatter (rdrf_scatter.hip)
+// ------------------------------------------------------------------------------------------------
+struct ScatterArgs {
+  RdrfVM vm[2], gvm[2];
+  int nsets;
+  const float* rows;   // d(feature) rows: tile t, row r at rows + (t*stride + row0[set] + r)*32
+  int flat;            // ray-tile mode: the tiles are 32-sample tiles of the flat [N * S] array, not (ray, tile) pairs
+  int stride, row0[2];
+  const float* xw;     // [idx][3] normalised coordinates, or nullptr -> normalise xyz
+  const float* xyz;
+  Box box;
+  const int* list;     // compacted mode: sample ids (+ device count); nullptr -> ray tiles
+  const int* count;
+  const uint8_t* valid;
+  int N, S;
+  float* dxw;          // [idx][3] coordinate gradients (nullable)
+  int dxw_accumulate;
+  float* g_xyz;        // static field: g_xyz += dw * inv (nullable)
+  int lds_bytes;       // dynamic LDS for the line accumulators (0: lines go to global memory)
+  int lds_f64;         // the accumulators are doubles (ds_add_f64: 11 x the update rate of ds_add_f32) / floats
+  int bcast;           // 1: every component's gradient is row 0 of the tile (static density: the
+                       //    feature is the plain sum of the 24 products)
+};
+enum ScatterKernel {   // the instantiations of k_scatter<C0Q, C1Q, NQ> in use
+  SCATTER_4_1_3,       // static density
+  SCATTER_4_1_9,       // dynamic density + blending
+  SCATTER_12_3_9,      // static appearance
+  SCATTER_12_3_27      // dynamic appearance
+};
+void fill_scatter_common(ScatterArgs& sa, const BwdArgs& a);
+int launch_scatter(const char* name, ScatterKernel kern, ScatterArgs& sa, long ntiles, hipStream_t stream);
+int scatter_mode(size_t ns, hipStream_t stream);   // 0 ray, 1 sorted
+int scatter_dyn_app_sorted(const BwdArgs& a, const BwdWs& b, const RdrfDynamicParams* P, const RdrfDynamicParams* G,
+                           hipStream_t stream);
+int scatter_dyn_density_sorted(const BwdArgs& a, const BwdWs& b, const RdrfDynamicParams* P, const RdrfDynamicParams* G,
+                               int set_mask, hipStream_t stream);
+
+// ------------------------------------------------------------------------------------------------
+// generic dW kernel: dW[out][col(e)] += sum_tiles sum_samples dz[out][s] * in[e][s]
+// (rdrf_dw.hip)
+// ------------------------------------------------------------------------------------------------
+struct DwJob {
+  const float* A;   // dz rows: tile t, row r at A + (t*A_stride + A_row0 + r)*32
+  int A_stride, A_row0, nbo, out_dim, out_row0;
+  const float* B;   // input rows
+  int B_stride;
+  int nblk;         // number of 32-row input blocks
+  int blk_row0[8], blk_seg[8], blk_e0[8];
+  int in_dim, ld;
+  float* dW;
+  float* db;        // bias gradient (nullable), indexed like the out rows
+  const int* count; // device sample count (compacted phases) or nullptr
+  int ntiles;
+};
+#define RDRF_MAX_DW_JOBS 12
+struct DwJobs {
+  DwJob j[RDRF_MAX_DW_JOBS];
+  int n;
+};
+void dw_add(DwJobs& D, const float* A, int A_stride, int A_row0, int nbo, int out_dim, int out_row0, const float* B,
+            int B_stride, int in_dim, int ld, float* dW, float* db, const int* count, int ntiles);
+void dw_blk(DwJobs& D, int row0, int seg, int e0);
+int dw_launch(DwJobs& D, hipStream_t stream, const char* name);

@@ -65,8 +65,17 @@ struct DetMap {
   unsigned long long* shadow;
 };
 // one copy per translation unit, written only from the host (rdrf_det_bind): `volatile` keeps the optimiser from
-// treating the never-stored-to internal global as a zero constant and folding every lookup away
+// treating the never-stored-to internal global as a zero constant and folding every lookup away.
+// Every unit with a kernel that calls grad_add invokes RDRF_DET_UNIT(name) once, and rdrf_det.hip lists det_bind_<name>
+// among its binders.  A unit that uses grad_add without the macro is a BUG: its copy stays zero, its additions fall
+// through to the fp32 atomics below and the gradients are almost right but no longer bit-reproducible
+// (tests/test_gpu_det_binding.py finds such additions in the fp32 buffer before the fold).
 static __device__ volatile DetMap g_det[2];
+#define RDRF_DET_UNIT(name)                                                                                         \
+  int det_bind_##name(int slot, const DetMap* m, hipStream_t stream) {                                              \
+    RDRF_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_det), m, sizeof(DetMap), slot * sizeof(DetMap), hipMemcpyHostToDevice, stream)); \
+    return 0;                                                                                                       \
+  }
 #define RDRF_DET_SCALE 1099511627776.0f   // 2^40: quantum 9.1e-13, range +-8.4e6
 RDRF_D void grad_add(float* p, float v) {
 #pragma unroll
@@ -82,6 +91,7 @@ RDRF_D void grad_add(float* p, float v) {
   atomicAdd(p, v);
 }
 #else
+#define RDRF_DET_UNIT(name)
 RDRF_D void grad_add(float* p, float v) { atomicAdd(p, v); }
 #endif
 

@@ -1,4 +1,4 @@
-// rdrf_misc.hip -- ray generation, ray samplers and the three-way alpha compositor.
+// rdrf_misc.hip -- ray generation and its backward, ray samplers and the three-way alpha compositor.
 //   ray generation : /root/reference/train.py:96-103,1062-1077; dataLoader/ray_utils.py:53-140;
 //                    camera.py:8-15
 //   samplers       : models/tensorBase.py:487-499 (ndc), 524-559 (contract); renderer.py:147-170
@@ -70,6 +70,128 @@ extern "C" int rdrf_generate_rays(const int64_t* ids, const float* poses9, const
                                   int N, int T, int H, int W, int ndc, float near, float* rays,
                                   rdrf_stream_t stream_) {
   return rdrf_generate_rays_uv(ids, nullptr, 0, poses9, focal, N, T, H, W, ndc, near, rays, stream_);
+}
+
+// ------------------------------------------------------------------------------------------------
+// ray generation backward: hand-written adjoint of k_generate_rays above
+// The gradients of a batch land on T x 9 pose entries and ONE focal length: one global atomic per ray and entry was
+// 36 864 atomics on 108 addresses for a 4096-ray launch at T = 12 (109 us; five launches per iteration of the
+// pose-optimising configs).  Each workgroup now accumulates its rays in LDS (ds_add_f32) and issues one global atomic
+// per touched entry: GRB_LDS_POSES pose rows fit (any longer table falls back to global atomics).
+#define GRB_LDS_POSES 448
+__global__ __launch_bounds__(256) void k_generate_rays_bwd(const int64_t* __restrict__ ids, const float* __restrict__ uv, int view_shift,
+                                    const float* __restrict__ poses9,
+                                    const float* __restrict__ focal_p, int N, int T, int H, int W,
+                                    int ndc, float near, const float* __restrict__ g_rays,
+                                    float* __restrict__ g_poses, float* __restrict__ g_focal) {
+  __shared__ float s_gp[GRB_LDS_POSES * 9];
+  __shared__ float s_gf[4];
+  const bool in_lds = T <= GRB_LDS_POSES;   // (uniform)
+  if (in_lds) {
+    for (int i = threadIdx.x; i < T * 9; i += blockDim.x) s_gp[i] = 0.f;
+    __syncthreads();
+  }
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  float gf = 0.f;
+  if (n < N) {
+    const long id = ids[n];
+    const int col = (int)(id % W), row = (int)((id / W) % H);
+    int view = (int)(id / ((long)W * H)) + view_shift;
+    view = view < 0 ? 0 : (view >= T ? T - 1 : view);
+    const float f = focal_p[0];
+    const float pu = uv ? uv[2 * n] : (float)col + 0.5f, pv = uv ? uv[2 * n + 1] : (float)row + 0.5f;
+    const float dir[3] = {(pu - 0.5f * W) / f, -(pv - 0.5f * H) / f, -1.0f};
+    const float* p = poses9 + view * 9;
+    float b1[3] = {p[0], p[1], p[2]};
+    const float n1 = sqrtf(b1[0] * b1[0] + b1[1] * b1[1] + b1[2] * b1[2]);
+    for (int k = 0; k < 3; ++k) b1[k] /= n1;
+    const float dt = b1[0] * p[3] + b1[1] * p[4] + b1[2] * p[5];
+    float u[3] = {p[3] - dt * b1[0], p[4] - dt * b1[1], p[5] - dt * b1[2]};
+    const float n2 = sqrtf(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    float b2[3] = {u[0] / n2, u[1] / n2, u[2] / n2};
+    const float b3[3] = {b1[1] * b2[2] - b1[2] * b2[1], b1[2] * b2[0] - b1[0] * b2[2],
+                         b1[0] * b2[1] - b1[1] * b2[0]};
+    float d[3], o[3] = {p[6], p[7], p[8]};
+    for (int r = 0; r < 3; ++r) d[r] = dir[0] * b1[r] + dir[1] * b2[r] + dir[2] * b3[r];
+    const float* g = g_rays + (size_t)n * 6;
+    float go[3] = {g[0], g[1], g[2]}, gd[3] = {g[3], g[4], g[5]};
+    if (ndc) {
+      const float t = -(near + o[2]) / d[2];
+      const float op[3] = {o[0] + t * d[0], o[1] + t * d[1], o[2] + t * d[2]};
+      const float kw = -2.0f * f / (float)W, kh = -2.0f * f / (float)H;
+      const float aa = op[0] / op[2], bb = op[1] / op[2], ra = d[0] / d[2], rb = d[1] / d[2];
+      const float g_kw = go[0] * aa + gd[0] * (ra - aa), g_kh = go[1] * bb + gd[1] * (rb - bb);
+      gf += g_kw * (-2.0f / (float)W) + g_kh * (-2.0f / (float)H);
+      const float g_a = kw * (go[0] - gd[0]), g_b = kh * (go[1] - gd[1]);
+      const float g_ra = kw * gd[0], g_rb = kh * gd[1];
+      float gop[3];
+      gop[0] = g_a / op[2];
+      gop[1] = g_b / op[2];
+      gop[2] = -(g_a * aa + g_b * bb) / op[2] - 2.0f * near * go[2] / (op[2] * op[2]) +
+               2.0f * near * gd[2] / (op[2] * op[2]);
+      float gdd[3] = {g_ra / d[2], g_rb / d[2], -(g_ra * ra + g_rb * rb) / d[2]};
+      const float g_t = gop[0] * d[0] + gop[1] * d[1] + gop[2] * d[2];
+      for (int k = 0; k < 3; ++k) { go[k] = gop[k]; gdd[k] += t * gop[k]; }
+      go[2] += -g_t / d[2];
+      gdd[2] += -g_t * t / d[2];
+      for (int k = 0; k < 3; ++k) gd[k] = gdd[k];
+    }
+    // d = sum_c dir_c b_c
+    float gb1[3], gb2[3], gb3[3], gdir[3];
+    for (int k = 0; k < 3; ++k) { gb1[k] = dir[0] * gd[k]; gb2[k] = dir[1] * gd[k]; gb3[k] = dir[2] * gd[k]; }
+    gdir[0] = gd[0] * b1[0] + gd[1] * b1[1] + gd[2] * b1[2];
+    gdir[1] = gd[0] * b2[0] + gd[1] * b2[1] + gd[2] * b2[2];
+    gf += -gdir[0] * dir[0] / f - gdir[1] * dir[1] / f;
+    // b3 = b1 x b2:  g_b1 += b2 x g_b3,  g_b2 += g_b3 x b1
+    gb1[0] += b2[1] * gb3[2] - b2[2] * gb3[1]; gb1[1] += b2[2] * gb3[0] - b2[0] * gb3[2];
+    gb1[2] += b2[0] * gb3[1] - b2[1] * gb3[0];
+    gb2[0] += gb3[1] * b1[2] - gb3[2] * b1[1]; gb2[1] += gb3[2] * b1[0] - gb3[0] * b1[2];
+    gb2[2] += gb3[0] * b1[1] - gb3[1] * b1[0];
+    // b2 = u/|u|
+    const float dot2 = gb2[0] * b2[0] + gb2[1] * b2[1] + gb2[2] * b2[2];
+    float gu[3];
+    for (int k = 0; k < 3; ++k) gu[k] = (gb2[k] - dot2 * b2[k]) / n2;
+    float gp1[3];
+    float g_dt = 0.f;
+    for (int k = 0; k < 3; ++k) { gp1[k] = gu[k]; g_dt -= gu[k] * b1[k]; gb1[k] -= dt * gu[k]; }
+    for (int k = 0; k < 3; ++k) { gb1[k] += g_dt * p[3 + k]; gp1[k] += g_dt * b1[k]; }
+    const float dot1 = gb1[0] * b1[0] + gb1[1] * b1[1] + gb1[2] * b1[2];
+    float* gp = in_lds ? s_gp + view * 9 : g_poses + view * 9;
+    for (int k = 0; k < 3; ++k) {
+      atomicAdd(gp + k, (gb1[k] - dot1 * b1[k]) / n1);
+      atomicAdd(gp + 3 + k, gp1[k]);
+      atomicAdd(gp + 6 + k, go[k]);
+    }
+  }
+  gf = wave_sum(gf);
+  if ((threadIdx.x & 63) == 0) s_gf[threadIdx.x >> 6] = gf;
+  __syncthreads();
+  if (in_lds)
+    for (int i = threadIdx.x; i < T * 9; i += blockDim.x)
+      if (s_gp[i] != 0.f) atomicAdd(g_poses + i, s_gp[i]);
+  if (threadIdx.x == 0) {
+    const float t = (s_gf[0] + s_gf[1]) + (s_gf[2] + s_gf[3]);
+    if (t != 0.f) atomicAdd(g_focal, t);
+  }
+}
+
+extern "C" int rdrf_generate_rays_uv_bwd(const int64_t* ids, const float* uv, int view_shift, const float* poses9,
+                                         const float* focal, int N, int T, int H, int W, int ndc, float near,
+                                         const float* grad_rays, float* grad_poses9, float* grad_focal,
+                                         rdrf_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (N == 0) return 0;   // empty batch: a no-op, like torch ops on empty tensors (their data pointers are null)
+  RDRF_CHECK(N > 0 && T > 0 && grad_rays && grad_poses9 && grad_focal, -1, "generate_rays_bwd: bad arguments");
+  RDRF_LAUNCH("generate_rays_bwd", k_generate_rays_bwd, dim3((N + 255) / 256), dim3(256), stream, ids, uv,
+              view_shift, poses9, focal, N, T, H, W, ndc, near, grad_rays, grad_poses9, grad_focal);
+  return 0;
+}
+extern "C" int rdrf_generate_rays_bwd(const int64_t* ids, const float* poses9, const float* focal,
+                                      int N, int T, int H, int W, int ndc, float near,
+                                      const float* grad_rays, float* grad_poses9, float* grad_focal,
+                                      rdrf_stream_t stream_) {
+  return rdrf_generate_rays_uv_bwd(ids, nullptr, 0, poses9, focal, N, T, H, W, ndc, near, grad_rays, grad_poses9,
+                                   grad_focal, stream_);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -4,6 +4,8 @@
 // All three are HBM-streaming kernels (a few bytes of arithmetic per byte moved).
 #include "rdrf_host.hpp"
 
+RDRF_DET_UNIT(optim)   // k_dense_l1 adds the regulariser's gradients with grad_add
+
 // ------------------------------------------------------------------------------------------------
 // Adam (torch.optim.Adam as train.py:924-934 builds it: betas (0.9, 0.99), eps 1e-8, no weight decay,
 // no amsgrad) over ONE flat fp32 range.  p, g, m, v are views of flat buffers (fields.TensorBase keeps
@@ -322,12 +324,3 @@ extern "C" int rdrf_dense_l1_bwd(const RdrfVM* vm, const RdrfVM* gvm, int act, f
   return 0;
 }
 
-
-#ifdef RDRF_DETERMINISTIC
-int det_bind_optim(int slot, const float* base, size_t n, unsigned long long* shadow, hipStream_t stream) {
-  static DetMap host[2];
-  host[slot].base = base; host[slot].n = n; host[slot].shadow = shadow;
-  RDRF_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_det), &host[slot], sizeof(DetMap), slot * sizeof(DetMap), hipMemcpyHostToDevice, stream));
-  return 0;
-}
-#endif

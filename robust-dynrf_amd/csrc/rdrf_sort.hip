@@ -1,4 +1,4 @@
-// rdrf_sort.hip -- device-wide stable key sort for the sorted scatter (rdrf_bwd.hip), hand-written for gfx950.
+// rdrf_sort.hip -- device-wide stable key sort for the sorted scatter (rdrf_scatter.hip), hand-written for gfx950.
 //
 // The keys are (plane | level-0 cell) codes of every live sample: 17-19 significant bits, a few million entries, the value
 // of an entry is its position in the key array.  An LSD radix sort over digits of <= 9 bits (two passes for up to 18

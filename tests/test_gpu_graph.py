@@ -74,7 +74,7 @@ def test_captured_iteration_replays_the_eager_iteration(name):
             # captured-vs-eager next to eager-vs-eager (two runs of ONE path) per buffer -- field buffers and pose table
             # <= 8.1e-6 / <= 8.1e-6; the field of view is ONE float that every ray's gradient is added to, with heavy
             # cancellation: 1.8e-4 captured-vs-eager, 6.1e-5 between two eager runs (davis, 8192 rays).  A captured launch
-            # sequence takes the sorted scatter at every size (rdrf_bwd.hip scatter_mode), the eager twin the ray-tile
+            # sequence takes the sorted scatter at every size (rdrf_scatter.hip scatter_mode), the eager twin the ray-tile
             # scatter below 300 k samples: the same distance as batched-vs-per-pass (tests/test_gpu_trainer.py: <= 8.9e-6,
             # bound 5e-5).  Bounds: 5e-5, and 2e-3 for that scalar.  A replay on stale inputs (a coin, a jitter vector, the
             # iteration scalars) moves every buffer by >= 1e-2.
