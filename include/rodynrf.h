@@ -634,6 +634,32 @@ int rdrf_selftest_mlp(const float* x, const float* w, const float* b, int M, int
 int rdrf_selftest_layer(int form, const float* x, const float* w, int M, int K, int OUT, float* y, void* ws, size_t ws_bytes,
                         rdrf_stream_t stream);
 
+/* The dW products (k_dw3 behind its host planner) on rows the caller supplies, with the job lists of the backward entry points:
+ * one plan per list.  A: dz rows [ntiles][A_stride][32], B: activation rows [ntiles][B_stride][32] (device, 16-byte aligned,
+ * A_floats / B_floats long); a plan with two row regions (DYN, FEAT_DYN: the appearance rows, then the density-phase rows)
+ * takes region 1 right behind the ntiles tiles of region 0, in both arrays.  count: nullable device sample count; the plans whose
+ * entry point passes one (STATIC_*, DYN_APP, the appearance region of DYN) then walk ceil(count / 32) <= ntiles tiles.  flags:
+ * the density phase's live heads and whether the small layers' gradients are formed by the backward-data kernel instead.
+ * grads: RdrfStaticParams (STATIC_*, FEAT_STATIC) or RdrfDynamicParams of gradient pointers, added into.  Unknown plan: -1;
+ * ntiles == 0 without a count the plan reads (STATIC_*, DYN_APP, DYN read it; the others ignore one): a no-op.
+ * FEAT_DYN ignores RDRF_DW_SMALL_IN_KERNEL, as rdrf_dynamic_features_bwd always forms the small layers' gradients in k_dw3.
+ * rdrf_selftest_dw_describe writes the plan's job list in resolved form to host memory (layout: csrc/rdrf_selftest.hip) and
+ * returns the number of ints written; -3 when cap is too small. */
+#define RDRF_DW_DENSITY 0
+#define RDRF_DW_STATIC_FEA 1
+#define RDRF_DW_STATIC_TE 2
+#define RDRF_DW_DYN_APP 3
+#define RDRF_DW_DYN 4
+#define RDRF_DW_SCENE_FLOW 5
+#define RDRF_DW_FEAT_STATIC 6
+#define RDRF_DW_FEAT_DYN 7
+#define RDRF_DW_LIVE_D 1
+#define RDRF_DW_LIVE_B 2
+#define RDRF_DW_SMALL_IN_KERNEL 4
+int rdrf_selftest_dw(int plan, int flags, const float* A, size_t A_floats, const float* B, size_t B_floats, int ntiles,
+                     const int* count, const void* grads, rdrf_stream_t stream);
+int rdrf_selftest_dw_describe(int plan, int flags, int* out, int cap);
+
 /* timing hook: average device time (ms) of the dominant kernel launches recorded with HIP events
  * since the last reset; used by bench.py for the roofline figure. */
 void rdrf_prof_reset(void);

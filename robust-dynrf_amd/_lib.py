@@ -156,6 +156,9 @@ def _load():
     lib.rdrf_gather_batch.argtypes = [C.POINTER(SceneTablesC), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(BatchC), C.c_void_p]
     lib.rdrf_selftest_layer.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_size_t, C.c_void_p]
+    lib.rdrf_selftest_dw.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]
+    lib.rdrf_selftest_dw_describe.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]
     lib.rdrf_prof_get.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     lib.rdrf_det_bind.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.rdrf_det_finish.argtypes = [C.c_int, C.c_void_p]
@@ -186,13 +189,18 @@ SYMBOLS = [
     "rdrf_render_maps_fwd", "rdrf_render_chunks_maps_fwd", "rdrf_camera_rays", "rdrf_ssim_workspace_bytes", "rdrf_ssim",
     "rdrf_render_motion_workspace_bytes", "rdrf_render_motion_fwd", "rdrf_flow_to_image_workspace_bytes", "rdrf_flow_to_image",
     "rdrf_gather_batch",
-    "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_selftest_layer", "rdrf_prof_reset",
+    "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_selftest_layer", "rdrf_selftest_dw", "rdrf_selftest_dw_describe",
+    "rdrf_prof_reset",
     "rdrf_prof_enable", "rdrf_prof_get",
 ]
 
 
 # rdrf_selftest_layer forms (include/rodynrf.h RDRF_ST_*)
 SELFTEST_FORMS = {"F32": 0, "F32_T": 1, "B3": 2, "B3_T": 3, "B3_PAIR_T": 4, "B3S": 5, "B3S_T": 6}
+
+# rdrf_selftest_dw plans and flags (include/rodynrf.h RDRF_DW_*)
+DW_PLANS = {"DENSITY": 0, "STATIC_FEA": 1, "STATIC_TE": 2, "DYN_APP": 3, "DYN": 4, "SCENE_FLOW": 5, "FEAT_STATIC": 6, "FEAT_DYN": 7}
+DW_LIVE_D, DW_LIVE_B, DW_SMALL_IN_KERNEL = 1, 2, 4
 
 SCATTER_MODES = {"ray": 0, "sorted": 1, "auto": 2, "sorted_plain": 3}
 

@@ -1212,8 +1212,8 @@ static int carve_bwd(BwdWs& b, void* ws, size_t ws_bytes, int N, int S, int dyna
 }
 
 // dW jobs of the dynamic field's density phase (warp MLP, density / blending heads)
-static void add_density_phase_dw(DwJobs& D, const float* grows1, const float* act1, const RdrfDynamicParams* G,
-                                 int T1, bool live_d = true, bool live_b = true, bool small_in_kernel = false) {
+void add_density_phase_dw(DwJobs& D, const float* grows1, const float* act1, const RdrfDynamicParams* G, int T1, bool live_d,
+                          bool live_b, bool small_in_kernel) {
   // layer3: [X0 | tout]
   dw_add(D, grows1, sv::K1G_ROWS, sv::K1G_DZ3, 2, 64, 0, act1, sv::K1_ROWS, 93, 93, G->l3w, G->l3b, nullptr, T1);
   dw_blk(D, sv::K1_X0, SEG_WARP3_X0, 0);
@@ -1252,6 +1252,74 @@ static void add_density_phase_dw(DwJobs& D, const float* grows1, const float* ac
     dw_blk(D, sv::K1_X0 + 32, SEG_DEN1_X0, 32);
     dw_blk(D, sv::K1_X1, SEG_DEN1_X1, 0);
   }
+}
+// static appearance phase (compacted: device count), MLP_Fea (fea) or MLP_Fea_TimeEmbedding head
+void add_static_app_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfStaticParams* G, bool fea, const int* cnt,
+                       int ntiles) {
+  const int in1 = fea ? 138 : 135;
+  dw_add(D, grows3, sv::K3G_ROWS, sv::K3G_DZV, 1, 3, 0, act3, sv::S3_ROWS, 128,
+         fea ? 128 : 131, G->w3, G->b3, cnt, ntiles);
+  for (int i = 0; i < 4; ++i) dw_blk(D, sv::S3_H2 + 32 * i, SEG_IDENT, 32 * i);
+  if (!fea) dw_blk(D, sv::S3_VD, SEG_VIEW3, 0);
+  dw_add(D, grows3, sv::K3G_ROWS, sv::K3G_DF, 1, 27, 0, act3, sv::S3_ROWS, 72, 72, G->basis,
+         nullptr, cnt, ntiles);
+  for (int i = 0; i < 3; ++i) dw_blk(D, sv::S3_G + 32 * i, SEG_IDENT, 32 * i);
+  dw_add(D, grows3, sv::K3G_ROWS, sv::K3G_DZ2, 4, 128, 0, act3, sv::S3_ROWS, 128, 128, G->w2,
+         G->b2, cnt, ntiles);
+  for (int i = 0; i < 4; ++i) dw_blk(D, sv::S3_H1 + 32 * i, SEG_IDENT, 32 * i);
+  dw_add(D, grows3, sv::K3G_ROWS, sv::K3G_DZ1, 4, 128, 0, act3, sv::S3_ROWS, in1, in1, G->w1,
+         G->b1, cnt, ntiles);
+  dw_blk(D, sv::S3_F, fea ? SEG_STAT1_F_FEA : SEG_STAT1_F_TE, 0);
+  for (int i = 0; i < 4; ++i) dw_blk(D, sv::S3_P + 32 * i, fea ? SEG_STAT1_P_FEA : SEG_STAT1_P_TE, 32 * i);
+}
+// dynamic appearance phase (compacted: device count)
+void add_dyn_app_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfDynamicParams* G, const int* cnt, int ntiles) {
+  dw_add(D, grows3, sv::K3G_ROWS, sv::K3G_DZV, 1, 3, 0, act3, sv::K3_ROWS, 128, 131, G->rwv,
+         G->rbv, cnt, ntiles);
+  for (int i = 0; i < 4; ++i) dw_blk(D, sv::K3_H2 + 32 * i, SEG_IDENT, 32 * i);
+  dw_blk(D, sv::K3_VD, SEG_VIEW3, 0);
+  dw_add(D, grows3, sv::K3G_ROWS, sv::K3G_DF, 1, 27, 0, act3, sv::K3_ROWS, 216, 216, G->basis,
+         nullptr, cnt, ntiles);
+  for (int i = 0; i < 7; ++i) dw_blk(D, sv::K3_A + 32 * i, SEG_IDENT, 32 * i);
+  dw_add(D, grows3, sv::K3G_ROWS, sv::K3G_DZ2, 4, 128, 0, act3, sv::K3_ROWS, 128, 128, G->rw2,
+         G->rb2, cnt, ntiles);
+  for (int i = 0; i < 4; ++i) dw_blk(D, sv::K3_H1 + 32 * i, SEG_IDENT, 32 * i);
+  dw_add(D, grows3, sv::K3G_ROWS, sv::K3G_DZ1, 4, 128, 0, act3, sv::K3_ROWS, 107, 107, G->rw1,
+         G->rb1, cnt, ntiles);
+  dw_blk(D, sv::K3_F, SEG_RGB1_F, 0);
+  dw_blk(D, sv::K3_X0, SEG_RGB1_X0, 0);
+  dw_blk(D, sv::K3_X0 + 32, SEG_RGB1_X0, 32);
+  dw_blk(D, sv::K3_X1, SEG_RGB1_X1, 0);
+}
+// scene flow MLP
+void add_scene_flow_dw(DwJobs& D, const float* grows, const float* act, const RdrfDynamicParams* G, int T) {
+  dw_add(D, grows, sv::SFG_ROWS, sv::SFG_DZ6, 1, 6, 0, act, sv::SF_ROWS, 64, 64, G->sfw[3], G->sfb[3],
+         nullptr, T);
+  dw_blk(D, sv::SF_H4, SEG_IDENT, 0);
+  dw_blk(D, sv::SF_H4 + 32, SEG_IDENT, 32);
+  dw_add(D, grows, sv::SFG_ROWS, sv::SFG_DZ4, 2, 64, 0, act, sv::SF_ROWS, 64, 64, G->sfw[2], G->sfb[2],
+         nullptr, T);
+  dw_blk(D, sv::SF_H2, SEG_IDENT, 0);
+  dw_blk(D, sv::SF_H2 + 32, SEG_IDENT, 32);
+  dw_add(D, grows, sv::SFG_ROWS, sv::SFG_DZ2, 2, 64, 0, act, sv::SF_ROWS, 64, 64, G->sfw[1], G->sfb[1],
+         nullptr, T);
+  dw_blk(D, sv::SF_H0, SEG_IDENT, 0);
+  dw_blk(D, sv::SF_H0 + 32, SEG_IDENT, 32);
+  dw_add(D, grows, sv::SFG_ROWS, sv::SFG_DZ0, 2, 64, 0, act, sv::SF_ROWS, 36, 36, G->sfw[0], G->sfb[0],
+         nullptr, T);
+  dw_blk(D, sv::SF_X, SEG_SF_X, 0);
+  dw_blk(D, sv::SF_X + 32, SEG_SF_X, 32);
+}
+// feature mode: the basis matrix of the static / the dynamic appearance features (Np tiles of 32 points)
+void add_feat_static_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfStaticParams* G, int Np) {
+  dw_add(D, grows3, sv::K3G_ROWS, sv::K3G_DF, 1, 27, 0, act3, sv::S3_ROWS, 72, 72, G->basis, nullptr,
+         nullptr, Np);
+  for (int i = 0; i < 3; ++i) dw_blk(D, sv::S3_G + 32 * i, SEG_IDENT, 32 * i);
+}
+void add_feat_dyn_app_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfDynamicParams* G, int Np) {
+  dw_add(D, grows3, sv::K3G_ROWS, sv::K3G_DF, 1, 27, 0, act3, sv::K3_ROWS, 216, 216, G->basis, nullptr,
+         nullptr, Np);
+  for (int i = 0; i < 7; ++i) dw_blk(D, sv::K3_A + 32 * i, SEG_IDENT, 32 * i);
 }
 
 extern "C" int rdrf_static_bwd(const RdrfStaticParams* P, const RdrfFieldCfg* cfg, const float* rays,
@@ -1310,24 +1378,10 @@ extern "C" int rdrf_static_bwd(const RdrfStaticParams* P, const RdrfFieldCfg* cf
       { int rc_ = launch_scatter("scatter_static_app", SCATTER_12_3_9, sa, (long)t3, stream); if (rc_) return rc_; }
     }
     const bool fea = cfg->static_head == RDRF_HEAD_MLP_FEA;
-    const int in1 = fea ? 138 : 135;
     const int* cnt = &a.sp.hdr->count;
     DwJobs D;
     D.n = 0;
-    dw_add(D, b.grows3, sv::K3G_ROWS, sv::K3G_DZV, 1, 3, 0, a.sp.act3, sv::S3_ROWS, 128,
-           fea ? 128 : 131, G->w3, G->b3, cnt, 0);
-    for (int i = 0; i < 4; ++i) dw_blk(D, sv::S3_H2 + 32 * i, SEG_IDENT, 32 * i);
-    if (!fea) dw_blk(D, sv::S3_VD, SEG_VIEW3, 0);
-    dw_add(D, b.grows3, sv::K3G_ROWS, sv::K3G_DF, 1, 27, 0, a.sp.act3, sv::S3_ROWS, 72, 72, G->basis,
-           nullptr, cnt, 0);
-    for (int i = 0; i < 3; ++i) dw_blk(D, sv::S3_G + 32 * i, SEG_IDENT, 32 * i);
-    dw_add(D, b.grows3, sv::K3G_ROWS, sv::K3G_DZ2, 4, 128, 0, a.sp.act3, sv::S3_ROWS, 128, 128, G->w2,
-           G->b2, cnt, 0);
-    for (int i = 0; i < 4; ++i) dw_blk(D, sv::S3_H1 + 32 * i, SEG_IDENT, 32 * i);
-    dw_add(D, b.grows3, sv::K3G_ROWS, sv::K3G_DZ1, 4, 128, 0, a.sp.act3, sv::S3_ROWS, in1, in1, G->w1,
-           G->b1, cnt, 0);
-    dw_blk(D, sv::S3_F, fea ? SEG_STAT1_F_FEA : SEG_STAT1_F_TE, 0);
-    for (int i = 0; i < 4; ++i) dw_blk(D, sv::S3_P + 32 * i, fea ? SEG_STAT1_P_FEA : SEG_STAT1_P_TE, 32 * i);
+    add_static_app_dw(D, b.grows3, a.sp.act3, G, fea, cnt, 0);
     rc = dw_launch(D, stream, "dw_static");
     if (rc) return rc;
   }
@@ -1417,22 +1471,7 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
       sa.dxw = b.dxw; sa.dxw_accumulate = 0;
       { int rc_ = launch_scatter("scatter_dyn_app", SCATTER_12_3_27, sa, (long)t3, stream); if (rc_) return rc_; }
     }
-    dw_add(D, b.grows3, sv::K3G_ROWS, sv::K3G_DZV, 1, 3, 0, a.sp.act3, sv::K3_ROWS, 128, 131, G->rwv,
-           G->rbv, cnt, 0);
-    for (int i = 0; i < 4; ++i) dw_blk(D, sv::K3_H2 + 32 * i, SEG_IDENT, 32 * i);
-    dw_blk(D, sv::K3_VD, SEG_VIEW3, 0);
-    dw_add(D, b.grows3, sv::K3G_ROWS, sv::K3G_DF, 1, 27, 0, a.sp.act3, sv::K3_ROWS, 216, 216, G->basis,
-           nullptr, cnt, 0);
-    for (int i = 0; i < 7; ++i) dw_blk(D, sv::K3_A + 32 * i, SEG_IDENT, 32 * i);
-    dw_add(D, b.grows3, sv::K3G_ROWS, sv::K3G_DZ2, 4, 128, 0, a.sp.act3, sv::K3_ROWS, 128, 128, G->rw2,
-           G->rb2, cnt, 0);
-    for (int i = 0; i < 4; ++i) dw_blk(D, sv::K3_H1 + 32 * i, SEG_IDENT, 32 * i);
-    dw_add(D, b.grows3, sv::K3G_ROWS, sv::K3G_DZ1, 4, 128, 0, a.sp.act3, sv::K3_ROWS, 107, 107, G->rw1,
-           G->rb1, cnt, 0);
-    dw_blk(D, sv::K3_F, SEG_RGB1_F, 0);
-    dw_blk(D, sv::K3_X0, SEG_RGB1_X0, 0);
-    dw_blk(D, sv::K3_X0 + 32, SEG_RGB1_X0, 32);
-    dw_blk(D, sv::K3_X1, SEG_RGB1_X1, 0);
+    add_dyn_app_dw(D, b.grows3, a.sp.act3, G, cnt, 0);
   }
   {
     const Geo g = geo_for_units(flat ? (long)t1 : (long)N);
@@ -1564,9 +1603,7 @@ extern "C" int rdrf_static_features_bwd(const RdrfStaticParams* P, const RdrfFie
     { int rc_ = launch_scatter("feat_scatter_static_app", SCATTER_12_3_9, sa, (long)Np, stream); if (rc_) return rc_; }
     DwJobs D;
     D.n = 0;
-    dw_add(D, b.grows3, sv::K3G_ROWS, sv::K3G_DF, 1, 27, 0, a.sp.act3, sv::S3_ROWS, 72, 72, G->basis, nullptr,
-           nullptr, Np);
-    for (int i = 0; i < 3; ++i) dw_blk(D, sv::S3_G + 32 * i, SEG_IDENT, 32 * i);
+    add_feat_static_dw(D, b.grows3, a.sp.act3, G, Np);
     rc = dw_launch(D, stream, "feat_dw_static");
     if (rc) return rc;
   }
@@ -1622,9 +1659,7 @@ extern "C" int rdrf_dynamic_features_bwd(const RdrfDynamicParams* P, const RdrfF
     sa.xw = a.sp.xw;
     sa.dxw = b.dxw; sa.dxw_accumulate = 0;
     { int rc_ = launch_scatter("feat_scatter_dyn_app", SCATTER_12_3_27, sa, (long)Np, stream); if (rc_) return rc_; }
-    dw_add(D, b.grows3, sv::K3G_ROWS, sv::K3G_DF, 1, 27, 0, a.sp.act3, sv::K3_ROWS, 216, 216, G->basis, nullptr,
-           nullptr, Np);
-    for (int i = 0; i < 7; ++i) dw_blk(D, sv::K3_A + 32 * i, SEG_IDENT, 32 * i);
+    add_feat_dyn_app_dw(D, b.grows3, a.sp.act3, G, Np);
   }
   RDRF_LAUNCH("feat_dyn_heads_bwd", (k_dyn_density_bwd<0, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
   if (g_density != nullptr || g_blending != nullptr) {
@@ -1677,22 +1712,7 @@ extern "C" int rdrf_scene_flow_bwd(const RdrfDynamicParams* P, const RdrfFieldCf
   const int T = (int)tiles;
   DwJobs D;
   D.n = 0;
-  dw_add(D, grows, sv::SFG_ROWS, sv::SFG_DZ6, 1, 6, 0, act, sv::SF_ROWS, 64, 64, G->sfw[3], G->sfb[3],
-         nullptr, T);
-  dw_blk(D, sv::SF_H4, SEG_IDENT, 0);
-  dw_blk(D, sv::SF_H4 + 32, SEG_IDENT, 32);
-  dw_add(D, grows, sv::SFG_ROWS, sv::SFG_DZ4, 2, 64, 0, act, sv::SF_ROWS, 64, 64, G->sfw[2], G->sfb[2],
-         nullptr, T);
-  dw_blk(D, sv::SF_H2, SEG_IDENT, 0);
-  dw_blk(D, sv::SF_H2 + 32, SEG_IDENT, 32);
-  dw_add(D, grows, sv::SFG_ROWS, sv::SFG_DZ2, 2, 64, 0, act, sv::SF_ROWS, 64, 64, G->sfw[1], G->sfb[1],
-         nullptr, T);
-  dw_blk(D, sv::SF_H0, SEG_IDENT, 0);
-  dw_blk(D, sv::SF_H0 + 32, SEG_IDENT, 32);
-  dw_add(D, grows, sv::SFG_ROWS, sv::SFG_DZ0, 2, 64, 0, act, sv::SF_ROWS, 36, 36, G->sfw[0], G->sfb[0],
-         nullptr, T);
-  dw_blk(D, sv::SF_X, SEG_SF_X, 0);
-  dw_blk(D, sv::SF_X + 32, SEG_SF_X, 32);
+  add_scene_flow_dw(D, grows, act, G, T);
   return dw_launch(D, stream, "dw_sf");
 }
 

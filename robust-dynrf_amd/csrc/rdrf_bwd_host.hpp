@@ -89,3 +89,14 @@ void dw_add(DwJobs& D, const float* A, int A_stride, int A_row0, int nbo, int ou
             int B_stride, int in_dim, int ld, float* dW, float* db, const int* count, int ntiles);
 void dw_blk(DwJobs& D, int row0, int seg, int e0);
 int dw_launch(DwJobs& D, hipStream_t stream, const char* name);
+
+// the job lists of the backward entry points, one builder per list (rdrf_bwd.hip); rdrf_selftest_dw (rdrf_selftest.hip) runs
+// the same lists on caller-supplied rows.  cnt / ntiles: the device sample count of a compacted phase, or the host tile count.
+void add_density_phase_dw(DwJobs& D, const float* grows1, const float* act1, const RdrfDynamicParams* G, int T1,
+                          bool live_d = true, bool live_b = true, bool small_in_kernel = false);
+void add_static_app_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfStaticParams* G, bool fea, const int* cnt,
+                       int ntiles);
+void add_dyn_app_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfDynamicParams* G, const int* cnt, int ntiles);
+void add_scene_flow_dw(DwJobs& D, const float* grows, const float* act, const RdrfDynamicParams* G, int T);
+void add_feat_static_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfStaticParams* G, int Np);
+void add_feat_dyn_app_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfDynamicParams* G, int Np);

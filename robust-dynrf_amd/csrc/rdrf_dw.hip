@@ -4,6 +4,21 @@
 // (16 samples) straight into its operand registers, so nothing is transposed.  The entry points describe their products
 // as jobs (dw_add / dw_blk); dw_launch plans them into launches of k_dw3 (k_dw2: its A/B partner in the tools build).
 // Host interface: rdrf_bwd_host.hpp.
+//
+// ROW CONTRACT.  k_dw3 multiplies whole 32-sample tiles: it knows no sample mask.  In every sample slot of every tile it walks,
+// of every 32-row block that is an operand of a product -- the slots past `count` in the last compacted tile, the slots past S
+// of a ragged ray tile, the slots of invalid samples -- the dz entry is ZERO and the activation entry is FINITE (0 x NaN and
+// 0 x inf are NaN in the matrix unit, and one NaN poisons a whole gradient row).  This is a REQUIREMENT ON THE PRODUCERS of the
+// rows, not on the allocators: the saved-row buffers and the workspace arrive uninitialised (torch.empty, reused across calls
+// of other shapes) and nobody clears them.  So the backward-data kernels (rdrf_bwd.hip) have to store every dz row a job names
+// with all 32 lanes of the tile's wave, a lane without a live sample storing 0, and the forward kernels (rdrf_fwd_dev.hpp)
+// every activation row likewise, a lane without a sample storing a finite value.  tests/test_gpu_poisoned_scratch.py holds them
+// to it: it runs every entry point on buffers pre-filled with NaN bytes.  The kernel's side is checked on its own by
+// tests/test_gpu_dw_primitives.py through rdrf_selftest_dw (rdrf_selftest.hip: the product's job lists on rows a test
+// supplies): 3e38 behind a zero dz changes no bit.  Tiles past ceil(count / 32) are not read.  Rows of a dz block past a job's
+// out_dim are multiplied and their products dropped at the write-out (rows of the product are independent), and the blocks
+// dw_launch stages only to bridge a hole in the row ranges (a pruned head) are operands of no product: neither needs to hold
+// anything.
 #include <algorithm>
 
 #include "rdrf_kernels.hpp"

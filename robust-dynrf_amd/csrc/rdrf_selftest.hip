@@ -6,7 +6,10 @@
 // are stored: no bias, no relu, so the result is linear in x and w.  Rows past M read as zero and are not stored.
 //   forward forms     x[M][K]   , w[OUT][K]  ->  y[M][OUT] = x w^T
 //   transposed forms  x[M][OUT] , w[OUT][K]  ->  y[M][K]   = x w      (the backward-data product of the same layer)
-#include "rdrf_host.hpp"
+//
+// rdrf_selftest_dw (end of the file, host code only): the dW job lists of the backward entry points (the builders of
+// rdrf_bwd.hip) planned and launched by dw_launch on rows the caller supplies; reference: tests/_dw_prim.py.
+#include "rdrf_bwd_host.hpp"
 
 namespace {
 
@@ -216,4 +219,130 @@ extern "C" int rdrf_selftest_layer(int form, const float* x, const float* w, int
   }
   rdrf_set_error("selftest_layer: form %d is not instantiated for K = %d, OUT = %d", form, K, OUT);
   return -1;
+}
+
+// ------------------------------------------------------------------------------------------------
+// rdrf_selftest_dw: the product's dW job lists on caller-supplied rows.  A plan is one DwJobs list as an entry point of
+// rdrf_bwd.hip hands it to dw_launch.  Its jobs fall into one or two row regions (a region = one dz array and one activation
+// array with their strides: what dw_launch plans together); region g + 1 starts where region g ends, ntiles tiles on.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct DwPlanInfo {
+  int dynamic;                          // the gradient struct is RdrfDynamicParams / RdrfStaticParams
+  int region[RDRF_MAX_DW_JOBS];         // region of each job
+  int nregions;
+};
+
+int dw_plan_jobs(int plan, int flags, const float* A, const float* B, size_t ntiles, const int* count, const void* G, DwJobs& D,
+                 DwPlanInfo& I) {
+  const RdrfStaticParams* Gs = (const RdrfStaticParams*)G;
+  const RdrfDynamicParams* Gd = (const RdrfDynamicParams*)G;
+  const bool live_d = (flags & RDRF_DW_LIVE_D) != 0, live_b = (flags & RDRF_DW_LIVE_B) != 0, small = (flags & RDRF_DW_SMALL_IN_KERNEL) != 0;
+  const int T = (int)ntiles, Tc = count ? 0 : T;   // a compacted phase passes (count, 0) in the product
+  D.n = 0;
+  I.dynamic = 1;
+  int n0 = -1;   // first job of the second region
+  const float *A1 = nullptr, *B1 = nullptr;
+  auto second = [&]() {
+    n0 = D.n;
+    A1 = A + ntiles * (size_t)D.j[0].A_stride * 32;
+    B1 = B + ntiles * (size_t)D.j[0].B_stride * 32;
+  };
+  switch (plan) {
+    case RDRF_DW_DENSITY: add_density_phase_dw(D, A, B, Gd, T, live_d, live_b, small); break;
+    case RDRF_DW_STATIC_FEA: I.dynamic = 0; add_static_app_dw(D, A, B, Gs, true, count, Tc); break;
+    case RDRF_DW_STATIC_TE: I.dynamic = 0; add_static_app_dw(D, A, B, Gs, false, count, Tc); break;
+    case RDRF_DW_DYN_APP: add_dyn_app_dw(D, A, B, Gd, count, Tc); break;
+    case RDRF_DW_DYN:   // rdrf_dynamic_bwd: appearance + density phase in one list
+      add_dyn_app_dw(D, A, B, Gd, count, Tc);
+      second();
+      add_density_phase_dw(D, A1, B1, Gd, T, live_d, live_b, small);
+      break;
+    case RDRF_DW_SCENE_FLOW: add_scene_flow_dw(D, A, B, Gd, T); break;
+    case RDRF_DW_FEAT_STATIC: I.dynamic = 0; add_feat_static_dw(D, A, B, Gs, T); break;
+    case RDRF_DW_FEAT_DYN:   // rdrf_dynamic_features_bwd
+      add_feat_dyn_app_dw(D, A, B, Gd, T);
+      second();
+      add_density_phase_dw(D, A1, B1, Gd, T, live_d, live_b);
+      break;
+    default: rdrf_set_error("selftest_dw: unknown plan %d", plan); return -1;
+  }
+  I.nregions = n0 < 0 ? 1 : 2;
+  for (int j = 0; j < D.n; ++j) I.region[j] = (n0 >= 0 && j >= n0) ? 1 : 0;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int rdrf_selftest_dw(int plan, int flags, const float* A, size_t A_floats, const float* B, size_t B_floats, int ntiles,
+                                const int* count, const void* grads, rdrf_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  DwJobs D;
+  DwPlanInfo I;
+  RDRF_CHECK(plan >= RDRF_DW_DENSITY && plan <= RDRF_DW_FEAT_DYN, -1, "selftest_dw: unknown plan %d", plan);
+  RDRF_CHECK(ntiles >= 0, -1, "selftest_dw: bad arguments (ntiles < 0)");
+  const bool takes_count = plan >= RDRF_DW_STATIC_FEA && plan <= RDRF_DW_DYN;   // the plans with a compacted phase
+  if (!takes_count) count = nullptr;                                           // the others never read it
+  if (ntiles == 0 && count == nullptr) return 0;   // no tile: a no-op
+  RDRF_CHECK(A && B && grads, -1, "selftest_dw: bad arguments (null rows or gradient struct)");
+  RDRF_CHECK((((uintptr_t)A | (uintptr_t)B) & 15) == 0, -1, "selftest_dw: the rows must be 16-byte aligned");
+  int rc = dw_plan_jobs(plan, flags, A, B, (size_t)ntiles, count, grads, D, I);
+  if (rc) return rc;
+  size_t needA = 0, needB = 0;
+  for (int g = 0, j = 0; g < I.nregions; ++g) {
+    while (j < D.n && I.region[j] != g) ++j;
+    needA += (size_t)ntiles * D.j[j].A_stride * 32;
+    needB += (size_t)ntiles * D.j[j].B_stride * 32;
+  }
+  RDRF_CHECK(A_floats >= needA && B_floats >= needB, -3, "selftest_dw: rows too small (A %zu < %zu or B %zu < %zu floats)", A_floats,
+             needA, B_floats, needB);
+  bool uses_count = false;
+  for (int j = 0; j < D.n; ++j) uses_count |= D.j[j].count != nullptr;
+  if (uses_count) {   // the kernel walks ceil(count / 32) tiles: they must lie inside the rows
+    int c = -1;
+    RDRF_HIP(hipMemcpyAsync(&c, count, sizeof(int), hipMemcpyDeviceToHost, stream));
+    RDRF_HIP(hipStreamSynchronize(stream));
+    RDRF_CHECK(c >= 0 && ((size_t)c + 31) / 32 <= (size_t)ntiles, -1, "selftest_dw: count %d does not fit %d tiles", c, ntiles);
+  }
+  return dw_launch(D, stream, "selftest_dw");
+}
+
+// The job list of a plan in resolved form (host memory, ints), so that a reference needs no knowledge of the row layouts or the
+// segment maps:  [0] ints used, [1] regions, [2] jobs, [3] 1 = RdrfDynamicParams / 0 = RdrfStaticParams;
+// per region: A_stride, B_stride, 1 if its jobs take the device count;
+// per job: region, A_row0, nbo, out_dim, out_row0, in_dim, ld, byte offset of the dW pointer in the gradient struct, of the db
+// pointer (-1: none), number of input blocks; per block: row0 and the 32 columns seg_imap(seg, e0 + li, in_dim) (-1: none).
+extern "C" int rdrf_selftest_dw_describe(int plan, int flags, int* out, int cap) {
+  constexpr size_t NSLOT = (sizeof(RdrfDynamicParams) > sizeof(RdrfStaticParams) ? sizeof(RdrfDynamicParams) : sizeof(RdrfStaticParams)) / 8;
+  uintptr_t slots[NSLOT];   // a gradient struct whose pointer fields hold their own byte offset + 8
+  for (size_t i = 0; i < NSLOT; ++i) slots[i] = (i + 1) * 8;
+  alignas(16) static const float rowsA[4] = {0.f}, rowsB[4] = {0.f};   // addresses only: never read
+  static const int cnt = 0;
+  DwJobs D;
+  DwPlanInfo I;
+  int rc = dw_plan_jobs(plan, flags, rowsA, rowsB, 1, &cnt, slots, D, I);
+  if (rc) return rc;
+  int need = 4 + 3 * I.nregions;
+  for (int j = 0; j < D.n; ++j) need += 10 + 33 * D.j[j].nblk;
+  RDRF_CHECK(out != nullptr && cap >= need, -3, "selftest_dw_describe: description buffer too small (%d < %d ints)", out ? cap : 0, need);
+  int n = 0;
+  out[n++] = need; out[n++] = I.nregions; out[n++] = D.n; out[n++] = I.dynamic;
+  for (int g = 0, j = 0; g < I.nregions; ++g) {
+    while (j < D.n && I.region[j] != g) ++j;
+    out[n++] = D.j[j].A_stride; out[n++] = D.j[j].B_stride; out[n++] = D.j[j].count != nullptr ? 1 : 0;
+  }
+  for (int j = 0; j < D.n; ++j) {
+    const DwJob& J = D.j[j];
+    out[n++] = I.region[j]; out[n++] = J.A_row0; out[n++] = J.nbo; out[n++] = J.out_dim; out[n++] = J.out_row0;
+    out[n++] = J.in_dim; out[n++] = J.ld;
+    out[n++] = (int)((uintptr_t)J.dW - 8);
+    out[n++] = J.db != nullptr ? (int)((uintptr_t)J.db - 8) : -1;
+    out[n++] = J.nblk;
+    for (int k = 0; k < J.nblk; ++k) {
+      out[n++] = J.blk_row0[k];
+      for (int li = 0; li < 32; ++li) out[n++] = seg_imap(J.blk_seg[k], J.blk_e0[k] + li, J.in_dim);
+    }
+  }
+  return n;
 }
