@@ -659,6 +659,9 @@ int rdrf_selftest_layer(int form, const float* x, const float* w, int M, int K, 
 int rdrf_selftest_dw(int plan, int flags, const float* A, size_t A_floats, const float* B, size_t B_floats, int ntiles,
                      const int* count, const void* grads, rdrf_stream_t stream);
 int rdrf_selftest_dw_describe(int plan, int flags, int* out, int cap);
+/* launch geometry of the scene-flow backward kernel that forms its weight gradients itself, for ntiles 32-sample tiles:
+ * workgroups and waves per workgroup (a wave walks the tiles wg * waves + wave, + grid * waves, ...).  Host code only. */
+int rdrf_selftest_sf_geometry(int ntiles, int* grid, int* waves);
 
 /* timing hook: average device time (ms) of the dominant kernel launches recorded with HIP events
  * since the last reset; used by bench.py for the roofline figure. */

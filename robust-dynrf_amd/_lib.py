@@ -190,6 +190,7 @@ SYMBOLS = [
     "rdrf_render_motion_workspace_bytes", "rdrf_render_motion_fwd", "rdrf_flow_to_image_workspace_bytes", "rdrf_flow_to_image",
     "rdrf_gather_batch",
     "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_selftest_layer", "rdrf_selftest_dw", "rdrf_selftest_dw_describe",
+    "rdrf_selftest_sf_geometry",
     "rdrf_prof_reset",
     "rdrf_prof_enable", "rdrf_prof_get",
 ]

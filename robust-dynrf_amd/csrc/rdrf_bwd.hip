@@ -1065,6 +1065,298 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_scene_flow_bwd(int N, int S,
 }
 
 // ------------------------------------------------------------------------------------------------
+// scene flow backward with the weight gradients formed in the kernel (k_scene_flow_bwd_dw).  k_scene_flow_bwd above writes
+// its 224 dz rows per tile for the dw_sf launch of k_dw3, which reads them back together with the 256 activation rows the
+// backward-data kernel had just loaded.  Here the wave that owns a tile keeps going: the data gradient runs exactly as
+// above (same calls on the same values: g_pts keeps its bits), and after each layer the wave writes that layer's dz into
+// its OWN LDS stage in the saved-row layout [row][32 samples] (8 KB, chunk-swizzled), reads it back as the A operand of
+// the fp32 MFMA -- lane (li, h): row li, samples 16 h .. 16 h + 15, as k_dw3 reads its stage -- and multiplies it with the
+// layer's input rows, read in the same form from the saved rows (64 contiguous bytes of a row: L2 hits, the wave has just
+// loaded those rows as relu masks, or is about to).  The 12 products (32 x 32 blocks) of the three 64-row layers
+// accumulate in registers of the wave for the whole launch: 192 accumulator registers, hence FOUR waves per workgroup
+// (512 registers per lane), no workgroup barrier in the tile loop, no round of tiles that could be partly empty.  The
+// 6-output layer stays off the matrix pipe: as two 32 x 32 products 26 of its 32 rows would be empty (2048 MFMA cycles per
+// tile); the lane that holds row li of the H4 blocks for the 16 samples of its half reads the six dz6 rows of those samples
+// as LDS broadcasts and keeps 12 sums (192 FMAs per tile).  At the end the waves of a workgroup add their accumulators
+// through LDS in wave order (a fixed order: the deterministic build stays bit-reproducible) and the workgroup flushes once
+// through grad_add, columns mapped as dw_launch maps them.
+// From the first stage write on, a tile's pass is ONE basic block (PTS is a template argument, both lane halves store the
+// dz6 rows, the masked update of g_pts is a buffer access whose offset is out of range in the lanes that do not take part):
+// with a branch in it, hipcc sinks every product -- pure arithmetic that only the next pass reads -- behind the branch to
+// the end of the pass and keeps the operands of all of them alive until there (100 to 140 spilled registers).
+// Row contract (head of rdrf_dw.hip): a lane past N * S has dz6 = 0, so every dz it stages is 0 (0 x finite = 0); tiles
+// past ceil(N * S / 32) are never read; every stage row that is read was written by the same wave for the same tile.
+// ------------------------------------------------------------------------------------------------
+#define SFD_WAVES 4
+namespace sfd {
+constexpr int ST_DZ = 0, ST_DZ6 = 64 * 32, ST_SIZE = 72 * 32;   // a wave's stage: one layer's dz (64 rows) + the dz6 rows
+constexpr int NPROD = 12, NDZ = 6;                               // MFMA products / their dz blocks (dz4 x 2 | dz2 x 2 | dz0 x 2)
+constexpr int NSM = 18;                                          // 6-output layer: 6 x 2 weight sums, 6 bias sums per lane
+constexpr int LDS = pkb::SF_SIZE + SFD_WAVES * ST_SIZE;
+constexpr int RED = NPROD * 1024 + (NDZ + NSM) * 64;             // the cross-wave sum, over the image and the stages
+static_assert(RED <= LDS && LDS * 4 <= 160 * 1024, "the cross-wave sum reuses the kernel's LDS");
+}  // namespace sfd
+struct SfGrads {
+  float* w[4];   // sfw[0..3]
+  float* b[4];   // sfb[0..3]
+};
+// float offset of 16-byte chunk `chunk` (4 samples) of stage row `row`: the chunk index is XORed with bits of the row so
+// that the 16 lanes of a ds_read_b128 group (consecutive rows, one chunk) cover all 64 banks
+RDRF_D int sfd_pos(int row, int chunk) { return row * 32 + ((chunk ^ ((row >> 1) & 7)) << 2); }
+RDRF_D void sfd_wave_sync() {   // LDS traffic of ONE wave: in order in hardware; this orders it for the compiler
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  __builtin_amdgcn_sched_barrier(0);
+}
+// Lane (s, h) writes slot kk to row elem_of(kk, h) = 8 (kk >> 2) + 4 h + (kk & 3), whose swizzle term ((row >> 1) & 7) is
+// (h << 1) ^ C with C = 4 ((kk >> 2) & 1) + ((kk & 3) >> 1): FOUR lane offsets (SfdPos::w) + a constant per slot, and the reads of
+// row 32 a + li are four more (SfdPos::r) + 1024 a.  Spelled out because hipcc, given sfd_pos per slot, keeps one address
+// register per slot (32) alive across the tile loop.
+struct SfdPos {
+  int w[4], r[4];
+};
+RDRF_D SfdPos sfd_lane_pos(int s, int h) {
+  SfdPos p;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    p.w[c] = h * 128 + ((((s >> 2) ^ (h << 1)) ^ ((c >> 1) * 4 + (c & 1))) << 2) + (s & 3);
+    p.r[c] = sfd_pos(s, 4 * h + c);
+  }
+  return p;
+}
+RDRF_D void sfd_stage(float* __restrict__ st, const float (&v)[32], const SfdPos& p) {
+#pragma unroll
+  for (int kk = 0; kk < 32; ++kk) st[p.w[(((kk >> 2) & 1) << 1) | ((kk & 3) >> 1)] + (8 * (kk >> 2) + (kk & 3)) * 32] = v[kk];
+}
+RDRF_D void sfd_read(f32x4 (&o)[4], const float* __restrict__ st, int blk, const SfdPos& p) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) o[q] = *(const f32x4*)(st + p.r[q] + 1024 * blk);
+}
+RDRF_D void sfd_load(f32x4 (&o)[4], const float* __restrict__ tile_base, int row, int h) {
+  const float* p = tile_base + (size_t)row * 32 + 16 * h;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) o[q] = *(const f32x4*)(p + 4 * q);
+}
+RDRF_D float sfd_sum(const f32x4 (&a)[4]) {
+  float t = 0.f;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) t += a[q].x + a[q].y + a[q].z + a[q].w;
+  return t;
+}
+RDRF_D void sfd_prod(f32x16& acc, const f32x4 (&a)[4], const f32x4 (&b)[4]) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].x, b[q].x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].y, b[q].y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].z, b[q].z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].w, b[q].w, acc, 0, 0, 0);
+  }
+}
+// the products of one layer: NA dz blocks (stage rows 32 a + li of lane (li, h)) x the two input blocks b0 | b1 -> accW[P0 ..], bsum[A0 ..]
+template <int NA, int P0, int A0>
+RDRF_D void sfd_layer(f32x16 (&accW)[sfd::NPROD], float (&bsum)[sfd::NDZ], const float* __restrict__ st, const f32x4 (&b0)[4],
+                      const f32x4 (&b1)[4], const SfdPos& p) {
+#pragma unroll
+  for (int a = 0; a < NA; ++a) {
+    f32x4 av[4];
+    sfd_read(av, st, a, p);
+    bsum[A0 + a] += sfd_sum(av);
+    sfd_prod(accW[P0 + 2 * a], av, b0);
+    sfd_prod(accW[P0 + 2 * a + 1], av, b1);
+    // (scheduling fences here and in the 6-output layer below: left free, hipcc gathers the LDS reads of every block in front
+    // of the first product -- 96 live registers for the dz6 rows alone -- and spills)
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// sf_x_bwd without a branch (see the head comment): every lane runs the pair path of every octet -- where sf_x_bwd skips it
+// (h == 0 in octet 0: pair -2 / -1; pairs 12 ..) nothing is selected and 0.f is added -- and the lanes h == 0 add dX[0..2] first,
+// as there.  The same values in the same order, plus additions of 0.f.
+RDRF_D void sf_x_bwd_flat(const float (&X)[20], const float (&dX)[20], int h, float& d0, float& d1, float& d2) {
+  d0 += h == 0 ? dX[0] : 0.f; d1 += h == 0 ? dX[1] : 0.f; d2 += h == 0 ? dX[2] : 0.f;
+#pragma unroll
+  for (int o = 0; o < 5; ++o) {
+    const int k = 2 * o + h - 1;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int pr = 2 * k + p;
+      const int d = (pr >= 0 && pr < 12) ? pr >> 2 : -1, f = pr & 3;
+      const float dq = ldexpf(dX[o * 4 + 2 * p] * X[o * 4 + 2 * p + 1] - dX[o * 4 + 2 * p + 1] * X[o * 4 + 2 * p], f);
+      d0 += d == 0 ? dq : 0.f; d1 += d == 1 ? dq : 0.f; d2 += d == 2 ? dq : 0.f;
+    }
+  }
+}
+
+template <bool PTS>   // PTS: the caller takes the point gradient (g_pts); without it the first layer's data product is skipped
+__global__ __launch_bounds__(64 * SFD_WAVES) void k_scene_flow_bwd_dw(int N, int S, Box box,
+                                                        const float* __restrict__ pkg,
+                                                        const float* __restrict__ act_rows,
+                                                        const float* __restrict__ g_f,
+                                                        const float* __restrict__ g_b,
+                                                        SfGrads G,
+                                                        float* __restrict__ g_pts) {
+  __shared__ __attribute__((aligned(16))) float lds[sfd::LDS];
+  const int lane = threadIdx.x & 63, h = lane >> 5, s = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = blockDim.x >> 6;
+  float* st = lds + pkb::SF_SIZE + wave * sfd::ST_SIZE;
+  lds_fill(lds, pkg + pkb::REG_SF, pkb::SF_SIZE);
+  const int total = N * S;
+  const int ntiles = (total + 31) >> 5;
+  const SfdPos pos = sfd_lane_pos(s, h);
+  f32x16 accW[sfd::NPROD];
+  float bsum[sfd::NDZ], sm[sfd::NSM];   // sm: dW of sfw[3], [o][input block] for input li of the block; then db of sfb[3]
+  acc_zero<sfd::NPROD>(accW);
+#pragma unroll
+  for (int a = 0; a < sfd::NDZ; ++a) bsum[a] = 0.f;
+#pragma unroll
+  for (int a = 0; a < sfd::NSM; ++a) sm[a] = 0.f;
+  for (int tile = blockIdx.x * nwaves + wave; tile < ntiles; tile += gridDim.x * nwaves) {
+    const int li = tile * 32 + s;
+    const bool act = li < total;
+    const int idx = act ? li : 0;
+    const float* svb = act_rows + (size_t)tile * sv::SF_ROWS * 32;
+    float dz6[6];
+#pragma unroll
+    for (int o = 0; o < 6; ++o) {
+      const float* gsrc = o < 3 ? g_f : g_b;
+      dz6[o] = (act && gsrc) ? gsrc[(size_t)idx * 3 + (o % 3)] : 0.f;
+    }
+    float dz[32], Hh[32];
+    f32x4 b0[4], b1[4];
+    load_rows<32>(svb, sv::SF_H4, Hh, s, h);
+    sfd_load(b0, svb, sv::SF_H4 + s, h);
+    sfd_load(b1, svb, sv::SF_H4 + 32 + s, h);
+    small_layer_bwd<32, 6>(dz, Hh, lds + pkb::SF_W6, h, dz6);
+    sfd_wave_sync();   // the previous tile's reads of the stage are done
+#pragma unroll
+    for (int o = 0; o < 6; ++o) st[sfd::ST_DZ6 + o * 32 + s] = dz6[o];   // (both halves, the same value; read as broadcasts)
+    sfd_stage(st + sfd::ST_DZ, dz, pos);
+    sfd_wave_sync();
+#pragma unroll
+    for (int o = 0; o < 6; ++o) {   // sfw[3]: dz6 x H4
+      f32x4 d[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) d[q] = *(const f32x4*)(st + sfd::ST_DZ6 + o * 32 + 16 * h + 4 * q);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        sm[2 * o] = fmaf(d[q].x, b0[q].x, sm[2 * o]); sm[2 * o + 1] = fmaf(d[q].x, b1[q].x, sm[2 * o + 1]);
+        sm[2 * o] = fmaf(d[q].y, b0[q].y, sm[2 * o]); sm[2 * o + 1] = fmaf(d[q].y, b1[q].y, sm[2 * o + 1]);
+        sm[2 * o] = fmaf(d[q].z, b0[q].z, sm[2 * o]); sm[2 * o + 1] = fmaf(d[q].z, b1[q].z, sm[2 * o + 1]);
+        sm[2 * o] = fmaf(d[q].w, b0[q].w, sm[2 * o]); sm[2 * o + 1] = fmaf(d[q].w, b1[q].w, sm[2 * o + 1]);
+      }
+      sm[12 + o] += sfd_sum(d);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    sfd_load(b0, svb, sv::SF_H2 + s, h);
+    sfd_load(b1, svb, sv::SF_H2 + 32 + s, h);
+    f32x16 acc[2];
+    acc_zero<2>(acc);
+    mfma_seg<2, 32>(acc, dz, lds + pkb::SF_W4T, lane);
+    load_rows<32>(svb, sv::SF_H2, Hh, s, h);
+    sfd_layer<2, 0, 0>(accW, bsum, st + sfd::ST_DZ, b0, b1, pos);    // sfw[2]: dz4 x H2
+#pragma unroll
+    for (int kk = 0; kk < 32; ++kk) dz[kk] = Hh[kk] > 0.f ? acc[kk >> 4][kk & 15] : 0.f;
+    sfd_wave_sync();
+    sfd_stage(st + sfd::ST_DZ, dz, pos);
+    sfd_wave_sync();
+    sfd_load(b0, svb, sv::SF_H0 + s, h);
+    sfd_load(b1, svb, sv::SF_H0 + 32 + s, h);
+    acc_zero<2>(acc);
+    mfma_seg<2, 32>(acc, dz, lds + pkb::SF_W2T, lane);
+    load_rows<32>(svb, sv::SF_H0, Hh, s, h);
+    sfd_layer<2, 4, 2>(accW, bsum, st + sfd::ST_DZ, b0, b1, pos);    // sfw[1]: dz2 x H0
+#pragma unroll
+    for (int kk = 0; kk < 32; ++kk) dz[kk] = Hh[kk] > 0.f ? acc[kk >> 4][kk & 15] : 0.f;
+    sfd_wave_sync();
+    sfd_stage(st + sfd::ST_DZ, dz, pos);
+    sfd_wave_sync();
+    sfd_load(b0, svb, sv::SF_X + s, h);
+    sfd_load(b1, svb, sv::SF_X + 32 + s, h);
+    if constexpr (PTS) {
+      acc_zero<2>(acc);
+      mfma_seg<2, 32>(acc, dz, lds + pkb::SF_W0T, lane);
+    }
+    sfd_layer<2, 8, 4>(accW, bsum, st + sfd::ST_DZ, b0, b1, pos);   // sfw[0]: dz0 x X
+    if constexpr (PTS) {
+      float X[20], dX[20];
+      load_rows<20>(svb, sv::SF_X, X, s, h);
+#pragma unroll
+      for (int kk = 0; kk < 20; ++kk) dX[kk] = acc[kk >> 4][kk & 15];
+      float d0 = 0.f, d1 = 0.f, d2 = 0.f;
+      sf_x_bwd_flat(X, dX, h, d0, d1, d2);
+      d0 += __shfl_xor(d0, 32, 64); d1 += __shfl_xor(d1, 32, 64); d2 += __shfl_xor(d2, 32, 64);
+      // g_pts[idx][0..2] += d * box.inv in the lanes (act, h == 0): the tile's 384 bytes as a buffer, every other lane out of range
+      const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(g_pts + (size_t)tile * 96), 0, 384, 0x00020000);
+      const int off = (act && h == 0) ? s * 12 : 1 << 20;
+      const float p0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, off, 0, 0));
+      const float p1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, off, 4, 0));
+      const float p2 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, off, 8, 0));
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p0 + d0 * box.inv[0]), rp, off, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p1 + d1 * box.inv[1]), rp, off, 4, 0);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p2 + d2 * box.inv[2]), rp, off, 8, 0);
+    }
+  }
+  // cross-wave sum in wave order, then one flush per workgroup.  C row i = (rr & 3) + 8 (rr >> 2) + 4 h (out neuron of the dz
+  // block), column = li (element of the input block)
+  float* red = lds;
+  for (int w = 0; w < nwaves; ++w) {
+    __syncthreads();   // (the first: every wave is done with the image and its stage)
+    if (wave == w) {
+#pragma unroll
+      for (int p = 0; p < sfd::NPROD; ++p)
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+          float* r = red + p * 1024 + rr * 64 + lane;
+          *r = w == 0 ? accW[p][rr] : *r + accW[p][rr];
+        }
+#pragma unroll
+      for (int a = 0; a < sfd::NDZ; ++a) {
+        float* r = red + sfd::NPROD * 1024 + a * 64 + lane;
+        *r = w == 0 ? bsum[a] : *r + bsum[a];
+      }
+#pragma unroll
+      for (int a = 0; a < sfd::NSM; ++a) {
+        float* r = red + sfd::NPROD * 1024 + (sfd::NDZ + a) * 64 + lane;
+        *r = w == 0 ? sm[a] : *r + sm[a];
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int p = 0; p < sfd::NPROD; ++p) {
+    // product p: layer, dz block of the layer, input block of the layer (the order of sfd_layer above)
+    const int layer = 2 - (p >> 2), bo = (p & 3) >> 1, k = p & 1;
+    const int in_dim = layer == 0 ? 36 : 64;
+    for (int e = threadIdx.x; e < 1024; e += blockDim.x) {
+      const int rr = e >> 6, hh = (e >> 5) & 1, c = e & 31;
+      const int col = seg_imap(layer == 0 ? SEG_SF_X : SEG_IDENT, 32 * k + c, in_dim);
+      const int orow = bo * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * hh;
+      if (col >= 0) grad_add(G.w[layer] + (size_t)orow * in_dim + col, red[p * 1024 + e]);
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < sfd::NDZ; ++a) {
+    const int layer = 2 - (a >> 1), orow = (a & 1) * 32 + (int)threadIdx.x;
+    if (threadIdx.x < 32)
+      grad_add(G.b[layer] + orow, red[sfd::NPROD * 1024 + a * 64 + threadIdx.x] + red[sfd::NPROD * 1024 + a * 64 + 32 + threadIdx.x]);
+  }
+  // the 6-output layer: the two lane halves hold the two halves of a tile's samples; every lane li holds the same bias sums
+  for (int e = threadIdx.x; e < 12 * 32 + 6; e += blockDim.x) {
+    const int a = e < 12 * 32 ? e >> 5 : 12 + (e - 12 * 32), c = e < 12 * 32 ? e & 31 : 0;
+    const float* r = red + sfd::NPROD * 1024 + (sfd::NDZ + a) * 64 + c;
+    if (a < 12) grad_add(G.w[3] + (a >> 1) * 64 + (a & 1) * 32 + c, r[0] + r[32]);
+    else grad_add(G.b[3] + (a - 12), r[0] + r[32]);
+  }
+}
+// launch geometry of k_scene_flow_bwd_dw: whole workgroups of SFD_WAVES waves, a wave per tile, at most a workgroup per CU
+void scene_flow_fused_geometry(long tiles, int* grid, int* waves) {
+  const long blocks = (tiles + SFD_WAVES - 1) / SFD_WAVES;
+  *grid = (int)(blocks < 1 ? 1 : (blocks > 256 ? 256 : blocks));
+  *waves = SFD_WAVES;
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
 void fill_static_w(StaticW& w, const RdrfStaticParams* P);
@@ -1692,9 +1984,12 @@ extern "C" int rdrf_scene_flow_bwd(const RdrfDynamicParams* P, const RdrfFieldCf
   RDRF_CHECK((size_t)N * S * 3 < (size_t)INT32_MAX, -1, "scene_flow_bwd: N * S * 3 must stay below 2^31 (32-bit sample indices)");
   const size_t tiles = ((size_t)N * S + 31) / 32;
   RDRF_CHECK(saved_bytes >= tiles * sv::SF_ROWS * 32 * 4, -3, "scene_flow_bwd: saved buffer too small");
+  // k_scene_flow_bwd_dw forms the weight gradients itself: no dz rows, no dw_sf launch.  RDRF_SF_FUSED=0 (tools build):
+  // k_scene_flow_bwd + k_dw3, its A/B partner
+  static const int fused = RDRF_ENV("RDRF_SF_FUSED") ? atoi(RDRF_ENV("RDRF_SF_FUSED")) : 1;
   WsCarver c(ws, ws_bytes);
   float* pkbuf = c.take<float>(PACK_AREA_FLOATS);
-  float* grows = c.take<float>(tiles * sv::SFG_ROWS * 32);
+  float* grows = fused ? nullptr : c.take<float>(tiles * sv::SFG_ROWS * 32);
   RDRF_CHECK(c.ok(), -3, "scene_flow_bwd: workspace too small: need %zu have %zu", c.off, ws_bytes);
   const float* pkimg = pkbuf;
   int rc = 0;
@@ -1704,6 +1999,19 @@ extern "C" int rdrf_scene_flow_bwd(const RdrfDynamicParams* P, const RdrfFieldCf
     dyn_pack_jobs_bwd(J, P);
     rc = pack_launch(J, pkbuf, stream);
     if (rc) return rc;
+  }
+  if (fused) {
+    int grid, waves;
+    scene_flow_fused_geometry((long)tiles, &grid, &waves);
+    SfGrads sg;
+    for (int i = 0; i < 4; ++i) { sg.w[i] = G->sfw[i]; sg.b[i] = G->sfb[i]; }
+    if (g_pts != nullptr)
+      RDRF_LAUNCH("scene_flow_bwd", k_scene_flow_bwd_dw<true>, dim3(grid), dim3(64 * waves), stream, N, S, make_box(cfg), pkimg,
+                  (const float*)saved, g_sf_f, g_sf_b, sg, g_pts);
+    else
+      RDRF_LAUNCH("scene_flow_bwd", k_scene_flow_bwd_dw<false>, dim3(grid), dim3(64 * waves), stream, N, S, make_box(cfg), pkimg,
+                  (const float*)saved, g_sf_f, g_sf_b, sg, g_pts);
+    return 0;
   }
   const Geo g = geo_for_units((long)tiles);
   RDRF_LAUNCH("scene_flow_bwd", k_scene_flow_bwd, dim3(g.grid), dim3(g.block), stream, N, S,

@@ -100,3 +100,5 @@ void add_dyn_app_dw(DwJobs& D, const float* grows3, const float* act3, const Rdr
 void add_scene_flow_dw(DwJobs& D, const float* grows, const float* act, const RdrfDynamicParams* G, int T);
 void add_feat_static_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfStaticParams* G, int Np);
 void add_feat_dyn_app_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfDynamicParams* G, int Np);
+// launch geometry of k_scene_flow_bwd_dw (rdrf_bwd.hip) for `tiles` 32-sample tiles: workgroups, waves per workgroup
+void scene_flow_fused_geometry(long tiles, int* grid, int* waves);

@@ -346,3 +346,9 @@ extern "C" int rdrf_selftest_dw_describe(int plan, int flags, int* out, int cap)
   }
   return n;
 }
+
+extern "C" int rdrf_selftest_sf_geometry(int ntiles, int* grid, int* waves) {
+  RDRF_CHECK(ntiles >= 0 && grid && waves, -1, "selftest_sf_geometry: bad arguments");
+  scene_flow_fused_geometry(ntiles, grid, waves);
+  return 0;
+}
