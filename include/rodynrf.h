@@ -656,12 +656,27 @@ int rdrf_selftest_layer(int form, const float* x, const float* w, int M, int K, 
 #define RDRF_DW_LIVE_D 1
 #define RDRF_DW_LIVE_B 2
 #define RDRF_DW_SMALL_IN_KERNEL 4
+#define RDRF_DW_WARP_IN_KERNEL 8 /* density phase: the warp MLP's layer3 / layer4 gradients are formed by the backward-data kernel */
 int rdrf_selftest_dw(int plan, int flags, const float* A, size_t A_floats, const float* B, size_t B_floats, int ntiles,
                      const int* count, const void* grads, rdrf_stream_t stream);
 int rdrf_selftest_dw_describe(int plan, int flags, int* out, int cap);
 /* launch geometry of the scene-flow backward kernel that forms its weight gradients itself, for ntiles 32-sample tiles:
  * workgroups and waves per workgroup (a wave walks the tiles wg * waves + wave, + grid * waves, ...).  Host code only. */
 int rdrf_selftest_sf_geometry(int ntiles, int* grid, int* waves);
+/* the same for the warp MLP backward kernel of the flat training path */
+int rdrf_selftest_warp_geometry(int ntiles, int* grid, int* waves);
+/* The warp MLP backward of the flat training path alone (what rdrf_dynamic_bwd runs between the density scatter and the time
+ * branch), on rows the caller supplies: act1 [T][576][32] saved density-phase rows (X0, T, H3, H4 are read), grows1 [T][544][32]
+ * gradient rows (the d(X0) rows of the heads are read, the small-layer rows 0..2 written), T = ceil(N S / 32) flat tiles; dxw /
+ * dxn [N S][3] coordinate gradients arriving from the appearance phase and the scatter; g_xyz_prime [N S][3] nullable.
+ * Added into: g_xyz [N S][3] (nullable) and, of grads, warp layers 3, 4, 5 (weights and biases).  Written: dtout [N][32] for
+ * the rays inside one tile, dtp [T][2][32] for the others (both must be pre-filled by a caller that compares them whole).
+ * ws: 16-byte aligned scratch of rdrf_selftest_warp_bwd_workspace_bytes(N, S). */
+size_t rdrf_selftest_warp_bwd_workspace_bytes(int N, int S);
+int rdrf_selftest_warp_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int N, int S, const float* act1,
+                           size_t act1_floats, float* grows1, size_t grows1_floats, float* dxw, float* dxn,
+                           const float* g_xyz_prime, const RdrfDynamicParams* grads, float* g_xyz, float* dtout, float* dtp,
+                           void* ws, size_t ws_bytes, rdrf_stream_t stream);
 
 /* timing hook: average device time (ms) of the dominant kernel launches recorded with HIP events
  * since the last reset; used by bench.py for the roofline figure. */

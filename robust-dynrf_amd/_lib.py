@@ -159,6 +159,12 @@ def _load():
     lib.rdrf_selftest_dw.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p]
     lib.rdrf_selftest_dw_describe.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]
+    lib.rdrf_selftest_warp_geometry.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.rdrf_selftest_warp_bwd_workspace_bytes.restype = C.c_size_t
+    lib.rdrf_selftest_warp_bwd_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.rdrf_selftest_warp_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_size_t, C.c_void_p]
     lib.rdrf_prof_get.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     lib.rdrf_det_bind.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.rdrf_det_finish.argtypes = [C.c_int, C.c_void_p]
@@ -190,7 +196,7 @@ SYMBOLS = [
     "rdrf_render_motion_workspace_bytes", "rdrf_render_motion_fwd", "rdrf_flow_to_image_workspace_bytes", "rdrf_flow_to_image",
     "rdrf_gather_batch",
     "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_selftest_layer", "rdrf_selftest_dw", "rdrf_selftest_dw_describe",
-    "rdrf_selftest_sf_geometry",
+    "rdrf_selftest_sf_geometry", "rdrf_selftest_warp_geometry", "rdrf_selftest_warp_bwd_workspace_bytes", "rdrf_selftest_warp_bwd",
     "rdrf_prof_reset",
     "rdrf_prof_enable", "rdrf_prof_get",
 ]
@@ -201,7 +207,7 @@ SELFTEST_FORMS = {"F32": 0, "F32_T": 1, "B3": 2, "B3_T": 3, "B3_PAIR_T": 4, "B3S
 
 # rdrf_selftest_dw plans and flags (include/rodynrf.h RDRF_DW_*)
 DW_PLANS = {"DENSITY": 0, "STATIC_FEA": 1, "STATIC_TE": 2, "DYN_APP": 3, "DYN": 4, "SCENE_FLOW": 5, "FEAT_STATIC": 6, "FEAT_DYN": 7}
-DW_LIVE_D, DW_LIVE_B, DW_SMALL_IN_KERNEL = 1, 2, 4
+DW_LIVE_D, DW_LIVE_B, DW_SMALL_IN_KERNEL, DW_WARP_IN_KERNEL = 1, 2, 4, 8
 
 SCATTER_MODES = {"ray": 0, "sorted": 1, "auto": 2, "sorted_plain": 3}
 

@@ -26,8 +26,11 @@ RDRF_DET_UNIT(bwd)
 
 // d(X0)/d(xn): X0 = [xn, t | (sin q, cos q) pairs], q_j = xn[j/10] * 2^(j%10); returns this lane
 // half's partial (combine with __shfl_xor 32)
+// (no contraction in here: left to hipcc, which products of `a cv - b sv` fuse depends on the kernel around the call, and
+// k_dyn_warp_bwd_dw has to give the bits of k_dyn_density_bwd<1>)
 RDRF_D void x0_bwd(const float (&X0)[32], const float (&dX0)[32], int h, float& d0, float& d1,
                    float& d2) {
+#pragma clang fp contract(off)
 #pragma unroll
   for (int o = 0; o < 8; ++o) {
     if (o == 0 && h == 0) {
@@ -1357,6 +1360,291 @@ void scene_flow_fused_geometry(long tiles, int* grid, int* waves) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// warp MLP backward on flat tiles with the weight gradients of its two 64-row layers formed in the kernel
+// (k_dyn_warp_bwd_dw), after k_scene_flow_bwd_dw above.  k_dyn_density_bwd<1, false, true> writes dz4 and dz3 (128 rows per
+// tile) only for k_dw3 to read them back with T and H3.  Here the wave that owns the tile stages dz4, then dz3, in its own 8 KB
+// of LDS (the stage layout, swizzle and fences of the scene-flow kernel), reads them back as the A operand and multiplies them
+// with H3 (dz4: 2 x 2 products) and with X0 | T (dz3: 2 x 3 products) read from the saved rows as 64 bytes per lane; of those
+// rows only T is not loaded by the data path of the same pass.  10 products = 160 accumulator registers for the whole launch,
+// four waves per workgroup, no workgroup barrier in the tile loop; the cross-wave sum and the flush are those of the scene-flow
+// kernel, and the sums of the 3-row layer (sw / sb of k_dyn_density_bwd) ride along in it.
+// The data gradient runs the calls of k_dyn_density_bwd<1, false, true> on the same values: g_xyz, d(tout) and K1G_SM keep
+// their bits.  From the first stage write on the pass is one basic block: x0_bwd_flat has no branch on the lane half, g_xyz and
+// d(tout) go out as buffer accesses whose offset is out of range in the lanes that do not take part (see the head comment of
+// the scene-flow kernel for what a branch there costs).
+// Row contract: a lane past N * S has dd = 0, hence dz4 = dz3 = 0 behind finite activations; tiles past ceil(N * S / 32) are
+// never read; every stage row that is read was written by the same wave for the same tile.
+// ------------------------------------------------------------------------------------------------
+namespace wpd {
+constexpr int WAVES = SFD_WAVES;
+constexpr int ST_SIZE = 64 * 32;                       // a wave's stage: one layer's dz (64 rows)
+constexpr int NPROD = 10, NDZ = 4, NSM = 6;            // products (dz4 x H3: 4 | dz3 x [X0 | T]: 6), dz blocks, sw[3] + sb[3]
+constexpr int LDS = pkb::K1W_SIZE + WAVES * ST_SIZE;
+constexpr int RED = NPROD * 1024 + (NDZ + NSM) * 64;   // the cross-wave sum, over the image and the stages
+static_assert(pkb::K1W_SIZE % 4 == 0 && RED <= LDS && LDS * 4 <= 160 * 1024, "the cross-wave sum reuses the kernel's LDS");
+}  // namespace wpd
+struct WarpGrads {
+  float *l3w, *l3b, *l4w, *l4b;
+};
+// x0_bwd without the branch on the lane half (as sf_x_bwd_flat): the same values in the same order, plus additions of 0.f
+RDRF_D void x0_bwd_flat(const float (&X0)[32], const float (&dX0)[32], int h, float& d0, float& d1, float& d2) {
+#pragma clang fp contract(off)
+  d0 += h == 0 ? dX0[0] : 0.f; d1 += h == 0 ? dX0[1] : 0.f; d2 += h == 0 ? dX0[2] : 0.f;
+#pragma unroll
+  for (int o = 0; o < 8; ++o) {
+    const int k = 2 * o + h - 1;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const int j = 2 * k + p;
+      const int d = j >= 0 ? j / 10 : -1, f = j >= 0 ? j - d * 10 : 0;
+      const float sv = X0[o * 4 + 2 * p], cv = X0[o * 4 + 2 * p + 1];
+      const float dq = ldexpf(dX0[o * 4 + 2 * p] * cv - dX0[o * 4 + 2 * p + 1] * sv, f);
+      d0 += d == 0 ? dq : 0.f; d1 += d == 1 ? dq : 0.f; d2 += d == 2 ? dq : 0.f;
+    }
+  }
+}
+
+template <bool GX>   // GX: the caller takes g_xyz
+__global__ __launch_bounds__(64 * wpd::WAVES) void k_dyn_warp_bwd_dw(BwdArgs a, DynG gw, WarpGrads G) {
+  __shared__ __attribute__((aligned(16))) float lds[wpd::LDS];
+  const int lane = threadIdx.x & 63, h = lane >> 5, s = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = blockDim.x >> 6;
+  float* st = lds + pkb::K1W_SIZE + wave * wpd::ST_SIZE;
+  lds_fill(lds, a.pk + pkb::REG_K1W, pkb::K1W_SIZE);
+  const int total = a.N * a.S;
+  const int ntiles = (total + 31) >> 5;
+  const SfdPos pos = sfd_lane_pos(s, h);
+  f32x16 accW[wpd::NPROD];
+  float bsum[wpd::NDZ];
+  float sw[3] = {0.f, 0.f, 0.f}, sb[3] = {0.f, 0.f, 0.f};
+  acc_zero<wpd::NPROD>(accW);
+#pragma unroll
+  for (int i = 0; i < wpd::NDZ; ++i) bsum[i] = 0.f;
+  for (int n = blockIdx.x * nwaves + wave; n < ntiles; n += gridDim.x * nwaves) {
+    const bool act = n * 32 + s < total;
+    const int idx = act ? n * 32 + s : 0;
+    const float* svb = a.sp.act1 + (size_t)n * sv::K1_ROWS * 32;
+    float* gb = a.grows1 + (size_t)n * sv::K1G_ROWS * 32;
+    float dw0 = act ? a.dxw_app[(size_t)idx * 3 + 0] : 0.f, dw1 = act ? a.dxw_app[(size_t)idx * 3 + 1] : 0.f,
+          dw2 = act ? a.dxw_app[(size_t)idx * 3 + 2] : 0.f;
+    float dn0 = act ? a.dxn_app[(size_t)idx * 3 + 0] : 0.f, dn1 = act ? a.dxn_app[(size_t)idx * 3 + 1] : 0.f,
+          dn2 = act ? a.dxn_app[(size_t)idx * 3 + 2] : 0.f;
+    float dd0 = dw0 * a.box.inv[0], dd1 = dw1 * a.box.inv[1], dd2 = dw2 * a.box.inv[2];
+    float gp0 = 0.f, gp1 = 0.f, gp2 = 0.f;
+    if (act && a.g_xyz_prime) {
+      gp0 = a.g_xyz_prime[(size_t)idx * 3 + 0]; gp1 = a.g_xyz_prime[(size_t)idx * 3 + 1];
+      gp2 = a.g_xyz_prime[(size_t)idx * 3 + 2];
+    }
+    dd0 += gp0; dd1 += gp1; dd2 += gp2;
+    if (!act) { dd0 = dd1 = dd2 = 0.f; }
+    if (h == 0) {
+      gb[(size_t)(sv::K1G_SM + 0) * 32 + s] = dd0; gb[(size_t)(sv::K1G_SM + 1) * 32 + s] = dd1;
+      gb[(size_t)(sv::K1G_SM + 2) * 32 + s] = dd2;
+    }
+    float dz4[32];
+    {
+      float H4[32];
+      load_rows<32>(svb, sv::K1_H4, H4, s, h);
+      const float* w5 = lds + pkb::K1W_W5 + h * 32;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const f32x4 wa = *reinterpret_cast<const f32x4*>(w5 + 4 * q);
+        const f32x4 wb = *reinterpret_cast<const f32x4*>(w5 + 64 + 4 * q);
+        const f32x4 wc = *reinterpret_cast<const f32x4*>(w5 + 128 + 4 * q);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const float d = wa[c] * dd0 + wb[c] * dd1 + wc[c] * dd2;
+          dz4[4 * q + c] = H4[4 * q + c] > 0.f ? d : 0.f;
+        }
+      }
+      sb[0] += dd0; sb[1] += dd1; sb[2] += dd2;
+#pragma unroll 1
+      for (int o = 0; o < 3; ++o) {   // one row at a time: the three butterflies unrolled together spill
+        const float dd = o == 0 ? dd0 : (o == 1 ? dd1 : dd2);
+        float pw[32];
+#pragma unroll
+        for (int kk = 0; kk < 32; ++kk) pw[kk] = dd * H4[kk];
+        const float r = reduce_scatter32(pw, s);
+        sw[0] += o == 0 ? r : 0.f; sw[1] += o == 1 ? r : 0.f; sw[2] += o == 2 ? r : 0.f;
+      }
+    }
+    // ---- one basic block from here to the end of the pass
+    f32x4 b0[4], b1[4], b2[4];
+    sfd_wave_sync();   // the previous tile's reads of the stage are done
+    sfd_stage(st, dz4, pos);
+    sfd_wave_sync();
+    sfd_load(b0, svb, sv::K1_H3 + s, h);
+    sfd_load(b1, svb, sv::K1_H3 + 32 + s, h);
+    float dz3[32];
+    {
+      f32x16 acc[2];
+      acc_zero<2>(acc);
+#ifdef RDRF_HEADS_BWD_F32
+      mfma_seg<2, 32>(acc, dz4, lds + pkb::K1W_W4T, lane);
+#else
+      mfma_seg_b3<2, 32>(acc, dz4, lds + pkb::K1W_W4T, lane);
+#endif
+      float H3[32];
+      load_rows<32>(svb, sv::K1_H3, H3, s, h);
+#pragma unroll
+      for (int bo = 0; bo < 2; ++bo) {   // layer4: dz4 x H3
+        f32x4 av[4];
+        sfd_read(av, st, bo, pos);
+        bsum[bo] += sfd_sum(av);
+        sfd_prod(accW[2 * bo], av, b0);
+        sfd_prod(accW[2 * bo + 1], av, b1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+#pragma unroll
+      for (int kk = 0; kk < 32; ++kk) dz3[kk] = H3[kk] > 0.f ? acc[kk >> 4][kk & 15] : 0.f;
+    }
+    sfd_wave_sync();
+    sfd_stage(st, dz3, pos);
+    sfd_wave_sync();
+    sfd_load(b0, svb, sv::K1_X0 + s, h);
+    sfd_load(b1, svb, sv::K1_X0 + 32 + s, h);
+    sfd_load(b2, svb, sv::K1_T + s, h);
+    f32x16 accX[2];  // d(X0): heads (from rows) + warp layer 3
+    {
+      float dXh[32];
+      load_rows<32>(gb, sv::K1G_DX0, dXh, s, h);
+#pragma unroll
+      for (int kk = 0; kk < 32; ++kk) accX[kk >> 4][kk & 15] = dXh[kk];
+    }
+    f32x16 accT[1];
+    acc_zero<1>(accT);
+#ifdef RDRF_HEADS_BWD_F32
+    mfma_seg<2, 32>(accX, dz3, lds + pkb::K1W_W3T_X0, lane);
+    mfma_seg<1, 32>(accT, dz3, lds + pkb::K1W_W3T_T, lane);
+#else
+    mfma_seg_b3_pair<2, 1, 32>(accX, accT, dz3, lds + pkb::K1W_W3T_X0, lds + pkb::K1W_W3T_T, lane);
+#endif
+#pragma unroll
+    for (int bo = 0; bo < 2; ++bo) {   // layer3: dz3 x [X0 | T]
+      f32x4 av[4];
+      sfd_read(av, st, bo, pos);
+      bsum[2 + bo] += sfd_sum(av);
+      sfd_prod(accW[4 + 3 * bo], av, b0);
+      sfd_prod(accW[4 + 3 * bo + 1], av, b1);
+      sfd_prod(accW[4 + 3 * bo + 2], av, b2);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    {
+      float X0[32], dX0[32];
+      load_rows<32>(svb, sv::K1_X0, X0, s, h);
+      acc_copy<2>(dX0, accX);
+      float e0 = 0.f, e1 = 0.f, e2 = 0.f;
+      x0_bwd_flat(X0, dX0, h, e0, e1, e2);
+      e0 += __shfl_xor(e0, 32, 64); e1 += __shfl_xor(e1, 32, 64); e2 += __shfl_xor(e2, 32, 64);
+      dn0 += e0 + dw0; dn1 += e1 + dw1; dn2 += e2 + dw2;
+    }
+    if constexpr (GX) {
+      // g_xyz[idx][0..2] += ... in the lanes (act, h == 0): the tile's 384 bytes as a buffer, every other lane out of range
+      const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(a.g_xyz + (size_t)n * 96), 0, 384, 0x00020000);
+      const int off = (act && h == 0) ? s * 12 : 1 << 20;
+      const float p0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, off, 0, 0));
+      const float p1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, off, 4, 0));
+      const float p2 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, off, 8, 0));
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p0 + (dn0 * a.box.inv[0] + gp0)), rp, off, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p1 + (dn1 * a.box.inv[1] + gp1)), rp, off, 4, 0);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p2 + (dn2 * a.box.inv[2] + gp2)), rp, off, 8, 0);
+    }
+    {
+      // d(tout) of the tile's rays, as k_dyn_density_bwd<1, false, true>: segmented suffix sums over the lanes of each half; the
+      // first lane of a segment stores -- to dtout (ray inside the tile: a buffer over the tile's rays) or to one of the tile's two
+      // partial records in dtp (a buffer over the tile's 256 bytes); the other lanes and the other buffer: out of range
+      const int i0 = n * 32 + s, nl = i0 / a.S, nl0 = (n * 32) / a.S;
+      const int rb = nl * a.S - n * 32, re = rb + a.S - 1;
+      const int end = re < 31 ? re : 31;
+      const bool head = i0 < total && (s == 0 || rb == s);
+      const bool inside = rb >= 0 && re <= 31;
+      const int nrays = a.N - nl0 < 32 ? a.N - nl0 : 32;
+      const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc((void*)(a.dtout + (size_t)nl0 * 32), 0, nrays * 128, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)(a.dtp + (size_t)n * 64), 0, 256, 0x00020000);
+      const int offt = (head && inside) ? (nl - nl0) * 128 + h * 16 : 1 << 20;
+      const int offq = (head && !inside) ? (s == 0 ? 0 : 128) + h * 16 : 1 << 20;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        float v = 0.f + accT[0][i];   // (dTacc of the other kernel: 0.f + the tile's product)
+#pragma unroll
+        for (int d = 1; d < 32; d <<= 1) {
+          const float o = __shfl_down(v, d, 32);
+          v += s + d <= end ? o : 0.f;
+        }
+        const int eo = (8 * (i >> 2) + (i & 3)) * 4;   // elem_of(i, h) = 8 (i >> 2) + 4 h + (i & 3)
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rt, offt, eo, 0);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rq, offq, eo, 0);
+      }
+    }
+  }
+  // cross-wave sum in wave order, then one flush per workgroup.  C row i = (rr & 3) + 8 (rr >> 2) + 4 h (out neuron of the dz
+  // block), column = li (element of the input block)
+  float sm[wpd::NSM];
+#pragma unroll
+  for (int o = 0; o < 3; ++o) {
+    sm[o] = sw[o];
+    sm[3 + o] = wave_sum(h == 0 ? sb[o] : 0.f);   // both halves hold the same samples
+  }
+  float* red = lds;
+  for (int w = 0; w < nwaves; ++w) {
+    __syncthreads();   // (the first: every wave is done with the image and its stage)
+    if (wave == w) {
+#pragma unroll
+      for (int p = 0; p < wpd::NPROD; ++p)
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) {
+          float* r = red + p * 1024 + rr * 64 + lane;
+          *r = w == 0 ? accW[p][rr] : *r + accW[p][rr];
+        }
+#pragma unroll
+      for (int i = 0; i < wpd::NDZ; ++i) {
+        float* r = red + wpd::NPROD * 1024 + i * 64 + lane;
+        *r = w == 0 ? bsum[i] : *r + bsum[i];
+      }
+#pragma unroll
+      for (int i = 0; i < wpd::NSM; ++i) {
+        float* r = red + wpd::NPROD * 1024 + (wpd::NDZ + i) * 64 + lane;
+        *r = w == 0 ? sm[i] : *r + sm[i];
+      }
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int p = 0; p < wpd::NPROD; ++p) {
+    // product p: layer4 (p < 4): dz block p >> 1, input block p & 1; layer3: dz block (p - 4) / 3, input block (p - 4) % 3
+    const bool l4 = p < 4;
+    const int bo = l4 ? p >> 1 : (p - 4) / 3, k = l4 ? p & 1 : (p - 4) % 3;
+    const int ld = l4 ? 64 : 93;
+    float* dW = l4 ? G.l4w : G.l3w;
+    for (int e = threadIdx.x; e < 1024; e += blockDim.x) {
+      const int rr = e >> 6, hh = (e >> 5) & 1, c = e & 31;
+      const int col = l4 ? 32 * k + c : (k < 2 ? seg_imap(SEG_WARP3_X0, 32 * k + c, 93) : seg_imap(SEG_WARP3_T, c, 93));
+      const int orow = bo * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * hh;
+      if (col >= 0) grad_add(dW + (size_t)orow * ld + col, red[p * 1024 + e]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < wpd::NDZ; ++i) {
+    float* db = i < 2 ? G.l4b : G.l3b;
+    const int orow = (i & 1) * 32 + (int)threadIdx.x;
+    if (threadIdx.x < 32)
+      grad_add(db + orow, red[wpd::NPROD * 1024 + i * 64 + threadIdx.x] + red[wpd::NPROD * 1024 + i * 64 + 32 + threadIdx.x]);
+  }
+  // the 3-row layer: lane (s, h) of every wave holds input element elem_of(s, h) of the three rows; every lane the rows' bias sums
+  for (int e = threadIdx.x; e < 3 * 64 + 3; e += blockDim.x) {
+    const float* r = red + wpd::NPROD * 1024 + wpd::NDZ * 64;
+    if (e < 192) grad_add(gw.l5w + (e >> 6) * 64 + elem_of(e & 31, (e >> 5) & 1), r[e]);
+    else grad_add(gw.l5b + (e - 192), r[(3 + e - 192) * 64]);
+  }
+}
+// launch geometry of k_dyn_warp_bwd_dw: whole workgroups of wpd::WAVES waves, a wave per tile, at most a workgroup per CU
+void warp_fused_geometry(long tiles, int* grid, int* waves) {
+  const long blocks = (tiles + wpd::WAVES - 1) / wpd::WAVES;
+  *grid = (int)(blocks < 1 ? 1 : (blocks > 256 ? 256 : blocks));
+  *waves = wpd::WAVES;
+}
+
+// ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
 void fill_static_w(StaticW& w, const RdrfStaticParams* P);
@@ -1505,7 +1793,9 @@ static int carve_bwd(BwdWs& b, void* ws, size_t ws_bytes, int N, int S, int dyna
 
 // dW jobs of the dynamic field's density phase (warp MLP, density / blending heads)
 void add_density_phase_dw(DwJobs& D, const float* grows1, const float* act1, const RdrfDynamicParams* G, int T1, bool live_d,
-                          bool live_b, bool small_in_kernel) {
+                          bool live_b, bool small_in_kernel, bool warp_in_kernel) {
+  // warp_in_kernel: k_dyn_warp_bwd_dw formed the gradients of layer3 and layer4 (and wrote no DZ3 / DZ4 rows)
+  if (!warp_in_kernel) {
   // layer3: [X0 | tout]
   dw_add(D, grows1, sv::K1G_ROWS, sv::K1G_DZ3, 2, 64, 0, act1, sv::K1_ROWS, 93, 93, G->l3w, G->l3b, nullptr, T1);
   dw_blk(D, sv::K1_X0, SEG_WARP3_X0, 0);
@@ -1514,6 +1804,7 @@ void add_density_phase_dw(DwJobs& D, const float* grows1, const float* act1, con
   dw_add(D, grows1, sv::K1G_ROWS, sv::K1G_DZ4, 2, 64, 0, act1, sv::K1_ROWS, 64, 64, G->l4w, G->l4b, nullptr, T1);
   dw_blk(D, sv::K1_H3, SEG_IDENT, 0);
   dw_blk(D, sv::K1_H3 + 32, SEG_IDENT, 32);
+  }
   // small layers share one dz block: rows 0..2 -> layer5, row 3 -> density_layer2, row 4 -> blending_layer2.
   // On the ray path k_dyn_density_bwd forms these gradients itself (reduce_scatter32): as MFMA products they were 6 of
   // the 40 per tile, 27 of 32 rows empty, and the 12 waves of k_dw2 take 34 products in 3 rounds instead of 4
@@ -1544,6 +1835,22 @@ void add_density_phase_dw(DwJobs& D, const float* grows1, const float* act1, con
     dw_blk(D, sv::K1_X0 + 32, SEG_DEN1_X0, 32);
     dw_blk(D, sv::K1_X1, SEG_DEN1_X1, 0);
   }
+}
+// The warp MLP backward of the flat training path: k_dyn_warp_bwd_dw forms the gradients of layer3 / layer4 itself (it needs the
+// 3-row layer's sums in the kernel as well: small_dw).  RDRF_WARP_FUSED=0 (tools build): k_dyn_density_bwd<1, false, true> + their
+// products in k_dw3, its A/B partner.  The wave-per-ray and feature-mode paths keep the two kernels.
+static bool warp_fused_path(bool flat, bool small_dw) {
+  static const int fused = RDRF_ENV("RDRF_WARP_FUSED") ? atoi(RDRF_ENV("RDRF_WARP_FUSED")) : 1;
+  return flat && small_dw && fused != 0;
+}
+static int launch_warp_fused(const BwdArgs& a, const DynG& gw, const RdrfDynamicParams* G, long tiles, hipStream_t stream) {
+  int grid, waves;
+  warp_fused_geometry(tiles, &grid, &waves);
+  WarpGrads wg;
+  wg.l3w = G->l3w; wg.l3b = G->l3b; wg.l4w = G->l4w; wg.l4b = G->l4b;
+  if (a.g_xyz != nullptr) RDRF_LAUNCH("dyn_warp_bwd", k_dyn_warp_bwd_dw<true>, dim3(grid), dim3(64 * waves), stream, a, gw, wg);
+  else RDRF_LAUNCH("dyn_warp_bwd", k_dyn_warp_bwd_dw<false>, dim3(grid), dim3(64 * waves), stream, a, gw, wg);
+  return 0;
 }
 // static appearance phase (compacted: device count), MLP_Fea (fea) or MLP_Fea_TimeEmbedding head
 void add_static_app_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfStaticParams* G, bool fea, const int* cnt,
@@ -1797,13 +2104,15 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
         { int rc_ = launch_scatter("scatter_dyn_density", SCATTER_4_1_9, sa, (long)t1, stream); if (rc_) return rc_; }
       }
     }
-    if (flat) RDRF_LAUNCH("dyn_warp_bwd", (k_dyn_density_bwd<1, false, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+    const bool warp_fused = warp_fused_path(flat, a.small_dw != 0);
+    if (warp_fused) { int rc_ = launch_warp_fused(a, gw, G, (long)t1, stream); if (rc_) return rc_; }
+    else if (flat) RDRF_LAUNCH("dyn_warp_bwd", (k_dyn_density_bwd<1, false, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
     else RDRF_LAUNCH("dyn_warp_bwd", (k_dyn_density_bwd<1, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
     RDRF_LAUNCH("time_branch_bwd", k_time_branch_bwd, dim3((N + TB_RPB - 1) / TB_RPB), dim3(128), stream, ts, w,
                 N, b.dtout, flat ? (const float*)b.dtp : nullptr, S, G->l1w, G->l1b, G->l2w, G->l2b);
     const bool small_in_kernel = a.small_dw != 0;
     add_density_phase_dw(D, b.grows1, a.sp.act1, G, (int)t1, g_sigma != nullptr || g_weight != nullptr, g_blending != nullptr,
-                         small_in_kernel);
+                         small_in_kernel, warp_fused);
   }
   rc = dw_launch(D, stream, "dw_dyn");
   return rc;
@@ -2042,4 +2351,40 @@ extern "C" int rdrf_dynamic_pack(const RdrfDynamicParams* P, int backward, float
   PackJobs J;
   if (backward) dyn_pack_jobs_bwd(J, P); else dyn_pack_jobs_fwd(J, P);
   return pack_launch(J, image, (hipStream_t)stream_);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the warp MLP backward alone on caller-supplied rows (rdrf_bwd_host.hpp; rdrf_selftest_warp_bwd)
+// ------------------------------------------------------------------------------------------------
+size_t warp_bwd_on_rows_pack_floats() { return PACK_AREA_FLOATS; }
+int warp_bwd_on_rows(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int N, int S, const float* act1, float* grows1,
+                     float* dxw, float* dxn, const float* g_xyz_prime, const RdrfDynamicParams* G, float* g_xyz, float* dtout,
+                     float* dtp, float* pk, uint8_t* valid, hipStream_t stream) {
+  BwdArgs a;
+  fill_bwd_common(a, cfg, nullptr, nullptr, nullptr, nullptr, valid, N, S);
+  a.g_xyz_prime = g_xyz_prime; a.g_xyz = g_xyz;
+  a.small_dw = 1;
+  a.sp.act1 = const_cast<float*>(act1);
+  a.pk = pk; a.grows1 = grows1; a.dxw_app = dxw; a.dxn_app = dxn; a.dtout = dtout; a.dtp = dtp;
+  DynW w;
+  fill_dyn_w(w, P);
+  DynG gw;
+  memset(&gw, 0, sizeof(gw));
+  gw.l5b = G->l5b; gw.l5w = G->l5w;
+  if (P->packed_bwd != nullptr) a.pk = P->packed_bwd;
+  else {
+    PackJobs J;
+    dyn_pack_jobs_bwd(J, P);
+    int rc = pack_launch(J, pk, stream);
+    if (rc) return rc;
+  }
+  const size_t ns = (size_t)N * S, t1 = (ns + 31) / 32;
+  RDRF_FILL(valid, 1, ns, stream);
+  if (warp_fused_path(true, true)) return launch_warp_fused(a, gw, G, (long)t1, stream);
+  const Geo g = geo_for_units((long)t1);
+  RDRF_LAUNCH("dyn_warp_bwd", (k_dyn_density_bwd<1, false, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+  DwJobs D;
+  D.n = 0;
+  add_density_phase_dw(D, grows1, act1, G, (int)t1, false, false, true, false);
+  return dw_launch(D, stream, "dw_warp");
 }

@@ -93,7 +93,7 @@ int dw_launch(DwJobs& D, hipStream_t stream, const char* name);
 // the job lists of the backward entry points, one builder per list (rdrf_bwd.hip); rdrf_selftest_dw (rdrf_selftest.hip) runs
 // the same lists on caller-supplied rows.  cnt / ntiles: the device sample count of a compacted phase, or the host tile count.
 void add_density_phase_dw(DwJobs& D, const float* grows1, const float* act1, const RdrfDynamicParams* G, int T1,
-                          bool live_d = true, bool live_b = true, bool small_in_kernel = false);
+                          bool live_d = true, bool live_b = true, bool small_in_kernel = false, bool warp_in_kernel = false);
 void add_static_app_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfStaticParams* G, bool fea, const int* cnt,
                        int ntiles);
 void add_dyn_app_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfDynamicParams* G, const int* cnt, int ntiles);
@@ -102,3 +102,12 @@ void add_feat_static_dw(DwJobs& D, const float* grows3, const float* act3, const
 void add_feat_dyn_app_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfDynamicParams* G, int Np);
 // launch geometry of k_scene_flow_bwd_dw (rdrf_bwd.hip) for `tiles` 32-sample tiles: workgroups, waves per workgroup
 void scene_flow_fused_geometry(long tiles, int* grid, int* waves);
+// the same for k_dyn_warp_bwd_dw
+void warp_fused_geometry(long tiles, int* grid, int* waves);
+// The warp MLP backward of the flat training path alone, on rows the caller supplies (rdrf_selftest_warp_bwd): the kernel(s)
+// rdrf_dynamic_bwd launches under `dyn_warp_bwd`, followed on the two-kernel path by the k_dw3 products of layer3 / layer4.
+// pk: PACK_AREA_FLOATS floats for the weight images; valid: N * S bytes of scratch.
+int warp_bwd_on_rows(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int N, int S, const float* act1, float* grows1,
+                     float* dxw, float* dxn, const float* g_xyz_prime, const RdrfDynamicParams* G, float* g_xyz, float* dtout,
+                     float* dtp, float* pk, uint8_t* valid, hipStream_t stream);
+size_t warp_bwd_on_rows_pack_floats();

@@ -9,6 +9,7 @@
 //
 // rdrf_selftest_dw (end of the file, host code only): the dW job lists of the backward entry points (the builders of
 // rdrf_bwd.hip) planned and launched by dw_launch on rows the caller supplies; reference: tests/_dw_prim.py.
+#include "rdrf_kernels.hpp"
 #include "rdrf_bwd_host.hpp"
 
 namespace {
@@ -238,7 +239,8 @@ int dw_plan_jobs(int plan, int flags, const float* A, const float* B, size_t nti
                  DwPlanInfo& I) {
   const RdrfStaticParams* Gs = (const RdrfStaticParams*)G;
   const RdrfDynamicParams* Gd = (const RdrfDynamicParams*)G;
-  const bool live_d = (flags & RDRF_DW_LIVE_D) != 0, live_b = (flags & RDRF_DW_LIVE_B) != 0, small = (flags & RDRF_DW_SMALL_IN_KERNEL) != 0;
+  const bool live_d = (flags & RDRF_DW_LIVE_D) != 0, live_b = (flags & RDRF_DW_LIVE_B) != 0, small = (flags & RDRF_DW_SMALL_IN_KERNEL) != 0,
+             warp = (flags & RDRF_DW_WARP_IN_KERNEL) != 0;
   const int T = (int)ntiles, Tc = count ? 0 : T;   // a compacted phase passes (count, 0) in the product
   D.n = 0;
   I.dynamic = 1;
@@ -250,14 +252,14 @@ int dw_plan_jobs(int plan, int flags, const float* A, const float* B, size_t nti
     B1 = B + ntiles * (size_t)D.j[0].B_stride * 32;
   };
   switch (plan) {
-    case RDRF_DW_DENSITY: add_density_phase_dw(D, A, B, Gd, T, live_d, live_b, small); break;
+    case RDRF_DW_DENSITY: add_density_phase_dw(D, A, B, Gd, T, live_d, live_b, small, warp); break;
     case RDRF_DW_STATIC_FEA: I.dynamic = 0; add_static_app_dw(D, A, B, Gs, true, count, Tc); break;
     case RDRF_DW_STATIC_TE: I.dynamic = 0; add_static_app_dw(D, A, B, Gs, false, count, Tc); break;
     case RDRF_DW_DYN_APP: add_dyn_app_dw(D, A, B, Gd, count, Tc); break;
     case RDRF_DW_DYN:   // rdrf_dynamic_bwd: appearance + density phase in one list
       add_dyn_app_dw(D, A, B, Gd, count, Tc);
       second();
-      add_density_phase_dw(D, A1, B1, Gd, T, live_d, live_b, small);
+      add_density_phase_dw(D, A1, B1, Gd, T, live_d, live_b, small, warp);
       break;
     case RDRF_DW_SCENE_FLOW: add_scene_flow_dw(D, A, B, Gd, T); break;
     case RDRF_DW_FEAT_STATIC: I.dynamic = 0; add_feat_static_dw(D, A, B, Gs, T); break;
@@ -351,4 +353,33 @@ extern "C" int rdrf_selftest_sf_geometry(int ntiles, int* grid, int* waves) {
   RDRF_CHECK(ntiles >= 0 && grid && waves, -1, "selftest_sf_geometry: bad arguments");
   scene_flow_fused_geometry(ntiles, grid, waves);
   return 0;
+}
+
+extern "C" int rdrf_selftest_warp_geometry(int ntiles, int* grid, int* waves) {
+  RDRF_CHECK(ntiles >= 0 && grid && waves, -1, "selftest_warp_geometry: bad arguments");
+  warp_fused_geometry(ntiles, grid, waves);
+  return 0;
+}
+
+extern "C" size_t rdrf_selftest_warp_bwd_workspace_bytes(int N, int S) {
+  return warp_bwd_on_rows_pack_floats() * 4 + (((size_t)N * S + 255) & ~(size_t)255) + 512;
+}
+extern "C" int rdrf_selftest_warp_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int N, int S, const float* act1,
+                                      size_t act1_floats, float* grows1, size_t grows1_floats, float* dxw, float* dxn,
+                                      const float* g_xyz_prime, const RdrfDynamicParams* grads, float* g_xyz, float* dtout,
+                                      float* dtp, void* ws, size_t ws_bytes, rdrf_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (N == 0) return 0;   // empty batch: a no-op
+  RDRF_CHECK(P && cfg && grads && act1 && grows1 && dxw && dxn && dtout && dtp && ws && N > 0 && S > 0 && S <= 4096, -1,
+             "selftest_warp_bwd: bad arguments");
+  RDRF_CHECK((size_t)N * S * 3 < (size_t)INT32_MAX, -1, "selftest_warp_bwd: N * S * 3 must stay below 2^31");
+  RDRF_CHECK((((uintptr_t)act1 | (uintptr_t)grows1 | (uintptr_t)ws) & 15) == 0, -1, "selftest_warp_bwd: rows and workspace must be 16-byte aligned");
+  const size_t tiles = ((size_t)N * S + 31) / 32;
+  RDRF_CHECK(act1_floats >= tiles * sv::K1_ROWS * 32 && grows1_floats >= tiles * sv::K1G_ROWS * 32, -3,
+             "selftest_warp_bwd: rows too small for %zu tiles", tiles);
+  RDRF_CHECK(ws_bytes >= rdrf_selftest_warp_bwd_workspace_bytes(N, S), -3, "selftest_warp_bwd: workspace too small");
+  WsCarver c(ws, ws_bytes);
+  float* pk = c.take<float>(warp_bwd_on_rows_pack_floats());
+  uint8_t* valid = c.take<uint8_t>((size_t)N * S);
+  return warp_bwd_on_rows(P, cfg, N, S, act1, grows1, dxw, dxn, g_xyz_prime, grads, g_xyz, dtout, dtp, pk, valid, stream);
 }
