@@ -173,6 +173,21 @@ int rdrf_sample_contract(const float* rays, int N, int S, float near, float far,
 int rdrf_sample_bwd(const float* rays, const float* z, int N, int S, int ray_type,
                     const float* grad_xyz, float* grad_rays, rdrf_stream_t stream);
 
+/* world: models/tensorBase.py:501-522, the sampler of every ray_type but ndc / contract (RDRF_RAY_OTHER).  The rays march
+ * through the box aabb_host (lo[3], hi[3]) in world space: t_min = the entry depth max_k min((hi_k - o_k) / vec_k,
+ * (lo_k - o_k) / vec_k), vec = d with 1e-6 for 0, clamped to [near, far]; z[n][j] = t_min[n] + step * (j + u[n]) with the
+ * field's stepSize and jitter_per_ray u[N] (uniform [0,1), one per ray) or NULL; xyz = o + d z; valid = inside the box. */
+int rdrf_sample_world(const float* rays, int N, int S, float near, float far, float step,
+                      const float* jitter_per_ray, const float aabb_host[6], float* xyz, float* z,
+                      uint8_t* valid, rdrf_stream_t stream);
+/* grad_xyz[N][S][3], grad_z[N][S] (either may be NULL) -> grad_rays[N][6] (+=).  Unlike rdrf_sample_bwd's, these z depend
+ * on the ray: beside grad_xyz . d(o + d z) at fixed z, (sum_j grad_xyz . d + sum_j grad_z) flows through t_min -- nowhere
+ * where the clamp is active, else into axis k and face f of the selected quotient: d/do_k = -1 / vec_k, d/dd_k =
+ * -t_min / vec_k (0 where d_k == 0).  The selection is recomputed from rays, aabb_host, near and far. */
+int rdrf_sample_world_bwd(const float* rays, const float* z, int N, int S, float near, float far,
+                          const float aabb_host[6], const float* grad_xyz, const float* grad_z,
+                          float* grad_rays, rdrf_stream_t stream);
+
 /* ---- TensorVMSplit.forward (models/tensorBase.py:704-850, models/tensoRF.py:118-196) ---------
  * outputs: rgb[N][S][3], sigma[N][S], weight[N][S], dists[N][S] (= dists*distance_scale).
  * rgb may be NULL (rdrf_static_fwd and rdrf_dynamic_fwd): the caller does not consume the colours -- passes B-D of the
@@ -498,6 +513,16 @@ int rdrf_render_chunks_maps_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* 
                                 const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, int chunk,
                                 float near, float far, const RdrfRenderMaps* maps, void* ws, size_t ws_bytes,
                                 rdrf_stream_t main_stream, const rdrf_stream_t* streams, int nstreams);
+
+/* ---- the no-grad render of world-space rays (cfg->ray_type == RDRF_RAY_OTHER: sampler rdrf_sample_world, no far-plane
+ * depth term) -- the one entry point of the whole family for this ray type, because its sampler needs the field's `step`
+ * and RdrfFieldCfg carries none; the entry points above refuse RDRF_RAY_OTHER.  chunk <= 0: rdrf_render_maps_fwd with
+ * `mode` on main_stream (streams / nstreams are not read).  chunk > 0: rdrf_render_chunks_maps_fwd (the launch sequence;
+ * `mode` is not read).  Same workspace sizes, same bits in every map as rdrf_composite_fwd after the fields' forward. */
+int rdrf_render_world_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                          const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, int chunk, float near,
+                          float far, float step, int mode, const RdrfRenderMaps* maps, void* ws, size_t ws_bytes,
+                          rdrf_stream_t main_stream, const rdrf_stream_t* streams, int nstreams);
 
 /* ---- motion maps of the no-grad render (the per-frame `render` of renderer.py:319-657 keeps, beside the maps above, four
  * induced optical-flow maps and the warp displacement of every frame) --------------------------------------------------

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("RDRF_LIB", os.path.join(_HERE, "librodynrf_det.so" if
 
 ABI_VERSION = 6   # include/rodynrf.h RDRF_ABI_VERSION: the parameter structs below are read to their full length
 
-RAY_TYPES = {"ndc": 0, "contract": 1}
+RAY_TYPES = {"ndc": 0, "contract": 1}   # any other name ("world") is RDRF_RAY_OTHER = 2: the world-space march
 ACTS = {"relu": 0, "softplus": 1}
 HEADS = {"MLP_Fea": 0, "MLP_Fea_TimeEmbedding": 1}
 SAVE_NO_APP = 1   # include/rodynrf.h RDRF_SAVE_NO_APP (flags of rdrf_saved_bytes_ex / rdrf_*_fwd_ex)
@@ -139,6 +139,9 @@ def _load():
     lib.rdrf_render_chunks_maps_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(RenderMapsC),
                                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
+    lib.rdrf_render_world_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.POINTER(RenderMapsC),
+                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
     lib.rdrf_render_motion_workspace_bytes.restype = C.c_size_t
     lib.rdrf_render_motion_workspace_bytes.argtypes = [C.c_int, C.c_int]
     lib.rdrf_render_motion_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -180,6 +183,7 @@ SYMBOLS = [
     "rdrf_abi_version", "rdrf_last_error", "rdrf_workspace_bytes", "rdrf_forward_workspace_bytes", "rdrf_saved_bytes", "rdrf_saved_bytes_ex", "rdrf_saved_row_bytes",
     "rdrf_generate_rays",
     "rdrf_generate_rays_bwd", "rdrf_generate_rays_uv", "rdrf_generate_rays_uv_bwd", "rdrf_sample_ndc", "rdrf_sample_contract", "rdrf_sample_bwd",
+    "rdrf_sample_world", "rdrf_sample_world_bwd", "rdrf_render_world_fwd",
     "rdrf_static_fwd", "rdrf_static_fwd_ex", "rdrf_static_bwd", "rdrf_dynamic_fwd", "rdrf_dynamic_fwd_ex", "rdrf_dynamic_bwd",
     "rdrf_features_saved_bytes", "rdrf_features_workspace_bytes", "rdrf_features_bwd_workspace_bytes",
     "rdrf_static_features_fwd", "rdrf_static_features_bwd", "rdrf_dynamic_features_fwd",

@@ -239,6 +239,31 @@ extern "C" int rdrf_sample_contract(const float* rays, int N, int S, float near,
   return 0;
 }
 
+__global__ void k_sample_world(const float* __restrict__ rays, int N, int S, float near, float far, float step,
+                               const float* __restrict__ jitter, Box box, float* __restrict__ xyz,
+                               float* __restrict__ z, uint8_t* __restrict__ valid) {
+  sample_world_body(rays, N, S, near, far, step, jitter, box, xyz, z, valid, grid_ctx());
+}
+
+extern "C" int rdrf_sample_world(const float* rays, int N, int S, float near, float far, float step,
+                                 const float* jitter_per_ray, const float aabb_host[6], float* xyz, float* z,
+                                 uint8_t* valid, rdrf_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (N == 0) return 0;   // empty batch: a no-op, like torch ops on empty tensors (their data pointers are null)
+  RDRF_CHECK(N > 0 && S > 0 && rays && aabb_host && xyz && z && valid, -1, "sample_world: bad arguments");
+  RDRF_CHECK(step > 0.0f && near <= far, -1, "sample_world: step must be positive and near <= far");
+  Box b;
+  for (int i = 0; i < 3; ++i) {
+    b.lo[i] = aabb_host[i];
+    b.hi[i] = aabb_host[3 + i];
+    b.inv[i] = 2.0f / (b.hi[i] - b.lo[i]);
+  }
+  const long total = (long)N * S;
+  RDRF_LAUNCH("sample_world", k_sample_world, dim3((unsigned)((total + 255) / 256)), dim3(256), stream,
+              rays, N, S, near, far, step, jitter_per_ray, b, xyz, z, valid);
+  return 0;
+}
+
 __global__ __launch_bounds__(64) void k_composite(CompArgs a) { composite_body(a, grid_ctx()); }
 
 extern "C" int rdrf_composite_fwd(const float* rgb_s, const float* sigma_s, const float* rgb_d,
@@ -502,6 +527,61 @@ extern "C" int rdrf_sample_bwd(const float* rays, const float* z, int N, int S, 
   RDRF_CHECK(N > 0 && S > 0 && rays && z && grad_xyz && grad_rays, -1, "sample_bwd: bad arguments");
   RDRF_LAUNCH("sample_bwd", k_sample_bwd, dim3(N), dim3(64), stream, rays, z, N, S, ray_type, grad_xyz,
               grad_rays);
+  return 0;
+}
+
+// World-space march: xyz = o + d z with z = t_min(o, d) + step (j + u).  Beside the two terms of k_sample_bwd, everything
+// that reaches z (sum_j g_xyz . d, and g_z where the caller has one) flows on through t_min: nowhere while the clamp holds
+// it at near / far, else into the one slab quotient (face - o_k) / vec_k that was selected -- recomputed here, not saved.
+// vec_k = 1e-6 stands in for d_k == 0 through a `where`, which passes no gradient to d_k.
+__global__ __launch_bounds__(64) void k_sample_world_bwd(const float* __restrict__ rays, const float* __restrict__ zrow,
+                                                         int N, int S, float near, float far, Box box,
+                                                         const float* __restrict__ g_xyz, const float* __restrict__ g_z,
+                                                         float* __restrict__ g_rays) {
+  const int lane = threadIdx.x, n = blockIdx.x;
+  if (n >= N) return;
+  const float* r = rays + (size_t)n * 6;
+  float go[3] = {0, 0, 0}, gd[3] = {0, 0, 0}, gt = 0.f;
+  for (int j = lane; j < S; j += 64) {
+    const size_t i = (size_t)n * S + j;
+    const float t = zrow[i];
+    for (int k = 0; k < 3; ++k) {
+      const float g = g_xyz ? g_xyz[i * 3 + k] : 0.f;
+      go[k] += g;
+      gd[k] += g * t;
+      gt += g * r[3 + k];
+    }
+    if (g_z) gt += g_z[i];
+  }
+  for (int k = 0; k < 3; ++k) { go[k] = wave_sum(go[k]); gd[k] = wave_sum(gd[k]); }
+  gt = wave_sum(gt);
+  if (lane == 0) {
+    float raw; int axis; bool upper;
+    world_tmin(r, box, near, far, raw, axis, upper);
+    if (raw >= near && raw <= far) {   // torch's clamp passes the gradient on the closed interval
+      const float vec = r[3 + axis] == 0.0f ? 1e-6f : r[3 + axis];
+      go[axis] += gt * (-1.0f / vec);
+      if (r[3 + axis] != 0.0f) gd[axis] += gt * (-raw / vec);
+    }
+    for (int k = 0; k < 3; ++k) { g_rays[(size_t)n * 6 + k] += go[k]; g_rays[(size_t)n * 6 + 3 + k] += gd[k]; }
+  }
+}
+
+extern "C" int rdrf_sample_world_bwd(const float* rays, const float* z, int N, int S, float near, float far,
+                                     const float aabb_host[6], const float* grad_xyz, const float* grad_z,
+                                     float* grad_rays, rdrf_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (N == 0) return 0;   // empty batch: a no-op, like torch ops on empty tensors (their data pointers are null)
+  RDRF_CHECK(N > 0 && S > 0 && rays && z && aabb_host && (grad_xyz || grad_z) && grad_rays, -1,
+             "sample_world_bwd: bad arguments");
+  Box b;
+  for (int i = 0; i < 3; ++i) {
+    b.lo[i] = aabb_host[i];
+    b.hi[i] = aabb_host[3 + i];
+    b.inv[i] = 2.0f / (b.hi[i] - b.lo[i]);
+  }
+  RDRF_LAUNCH("sample_world_bwd", k_sample_world_bwd, dim3(N), dim3(64), stream, rays, z, N, S, near, far, b, grad_xyz,
+              grad_z, grad_rays);
   return 0;
 }
 

@@ -91,6 +91,50 @@ RDRF_D void sample_contract_body(const float* __restrict__ rays, int N, int S, f
   }
 }
 
+// World-space march (TensorBase.sample_ray, models/tensorBase.py:501-522: every ray_type but ndc / contract): the entry depth
+// of the ray into the box, clamped to [near, far], then S samples a fixed `step` apart.  raw: the depth before the clamp;
+// axis / upper: which slab bound gave it (the backward differentiates that one quotient).  fp32 in the reference's operation
+// order, correctly rounded quotients.
+RDRF_D float world_tmin(const float* __restrict__ r, const Box& box, float near, float far, float& raw, int& axis,
+                        bool& upper) {
+#pragma clang fp contract(off)
+  raw = 0.f; axis = 0; upper = false;
+  for (int k = 0; k < 3; ++k) {
+    const float vec = r[3 + k] == 0.0f ? 1e-6f : r[3 + k];
+    const float ra = __fdiv_rn(box.hi[k] - r[k], vec);
+    const float rb = __fdiv_rn(box.lo[k] - r[k], vec);
+    const bool up = ra < rb;
+    const float m = up ? ra : rb;
+    if (k == 0 || m > raw) { raw = m; axis = k; upper = up; }
+  }
+  return fminf(fmaxf(raw, near), far);
+}
+
+// jitter: one value per ray [N] (the reference's rand_like(rng[:, [0]])) or NULL
+RDRF_D void sample_world_body(const float* __restrict__ rays, int N, int S, float near, float far, float step,
+                              const float* __restrict__ jitter, Box box, float* __restrict__ xyz,
+                              float* __restrict__ z, uint8_t* __restrict__ valid, const GridCtx gc) {
+#pragma clang fp contract(off)
+  for (long i = (long)gc.bid * gc.nthr + gc.tid; i < (long)N * S; i += (long)gc.nblk * gc.nthr) {
+  const int n = (int)(i / S), j = (int)(i - (long)n * S);
+  const float* r = rays + (size_t)n * 6;
+  float raw; int axis; bool upper;
+  const float t_min = world_tmin(r, box, near, far, raw, axis, upper);
+  float rng = (float)j;
+  if (jitter) rng = rng + jitter[n];
+  const float off = step * rng;
+  const float t = t_min + off;
+  bool out = false;
+  for (int k = 0; k < 3; ++k) {
+    const float m = r[3 + k] * t;
+    const float p = r[k] + m;
+    xyz[i * 3 + k] = p;
+    out = out || (box.lo[k] > p) || (p > box.hi[k]);
+  }
+  z[i] = t;
+  valid[i] = out ? 0 : 1;
+  }
+}
 
 // ------------------------------------------------------------------------------------------------
 // compositor (raw2outputs)

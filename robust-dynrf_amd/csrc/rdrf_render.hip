@@ -27,6 +27,7 @@ struct RenderFusedArgs {
   DynW wd;
   CompArgs comp;
   float near, far;
+  float step;            // world-space march (RDRF_RAY_OTHER): the field's stepSize
   unsigned* barrier;     // zero at launch
 };
 
@@ -69,9 +70,12 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_render_fused(RenderFusedArgs
   // compaction counters
   if (r.ad.ray_type == RDRF_RAY_NDC)
     sample_ndc_body(r.as.rays, N, S, r.near, r.far, nullptr, r.ad.box, (float*)r.as.xyz, (float*)r.as.z, (uint8_t*)r.as.valid, gc);
-  else
+  else if (r.ad.ray_type == RDRF_RAY_CONTRACT)
     sample_contract_body(r.as.rays, N, S, r.near, r.far, nullptr, nullptr, (float*)r.as.xyz, (float*)r.as.z,
                          (uint8_t*)r.as.valid, gc);
+  else
+    sample_world_body(r.as.rays, N, S, r.near, r.far, r.step, nullptr, r.ad.box, (float*)r.as.xyz, (float*)r.as.z,
+                      (uint8_t*)r.as.valid, gc);
   time_branch_body<true>(r.ad.ts, r.wd, N, r.ad.tout, lds, gc);
   {
     const size_t n3 = (size_t)N * S * 3;
@@ -161,8 +165,13 @@ static int carve_render(RenderBufs& b, void* ws, size_t ws_bytes, int N, int S, 
 }
 
 static int render_check(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
-                        const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, size_t ws_bytes) {
+                        const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float step,
+                        size_t ws_bytes) {
   RDRF_CHECK(PS && PD && cfg_s && cfg_d && rays && ts && N > 0 && S > 0, -1, "render: bad arguments");
+  // `step` > 0 comes from rdrf_render_world_fwd alone: the world march needs it, the other two samplers have no use for it
+  RDRF_CHECK((cfg_d->ray_type == RDRF_RAY_NDC || cfg_d->ray_type == RDRF_RAY_CONTRACT) == !(step > 0.0f), -1,
+             "render: ray_type ndc / contract through rdrf_render_*_fwd, any other through rdrf_render_world_fwd with "
+             "step > 0 (ray_type %d, step %g)", cfg_d->ray_type, (double)step);
   RDRF_CHECK((size_t)N * S * 3 < (size_t)INT32_MAX, -1, "render: N * S * 3 must stay below 2^31: render in chunks");
   RDRF_CHECK(ws_bytes >= rdrf_render_workspace_bytes(N, S), -3, "render: workspace too small");
   RDRF_CHECK(vm_ok(PS->density, 16, 4) && vm_ok(PS->app, 48, 12) && vm_ok(PD->density, 16, 4) && vm_ok(PD->blending, 16, 4) &&
@@ -174,10 +183,10 @@ static int render_check(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, c
 /* one cooperative launch (see k_render_fused) */
 static int render_fused(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
                         const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near, float far,
-                        float* const want[13], void* ws, size_t ws_bytes, rdrf_stream_t stream_) {
+                        float step, float* const want[13], void* ws, size_t ws_bytes, rdrf_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (N == 0) return 0;
-  int rc = render_check(PS, cfg_s, PD, cfg_d, rays, ts, N, S, ws_bytes);
+  int rc = render_check(PS, cfg_s, PD, cfg_d, rays, ts, N, S, step, ws_bytes);
   if (rc) return rc;
   RenderBufs b;
   rc = carve_render(b, ws, ws_bytes, N, S, want);
@@ -213,7 +222,7 @@ static int render_fused(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, c
   r.comp.dists = b.dists_d; r.comp.blending = b.blending; r.comp.z = b.z; r.comp.rays = rays;
   r.comp.N = N; r.comp.S = S; r.comp.ray_type = cfg_d->ray_type; r.comp.add_white_bg = 0; r.comp.white_dev = nullptr;
   for (int i = 0; i < 13; ++i) r.comp.out[i] = b.out[i];
-  r.near = near; r.far = far; r.barrier = b.barrier;
+  r.near = near; r.far = far; r.step = step; r.barrier = b.barrier;
   RDRF_FILL(b.barrier, 0, 256, stream);
   // one workgroup per CU at most (its LDS holds a whole weight image); fewer when the chunk has fewer units of work
   const long tiles = ((long)N * S + 31) / 32;
@@ -243,23 +252,25 @@ extern "C" int rdrf_render_fused_fwd(const RdrfStaticParams* PS, const RdrfField
   if (N == 0) return 0;
   RDRF_CHECK(rgb_map && depth_map, -1, "render: bad arguments");
   float* want[13] = {rgb_map, depth_map};
-  return render_fused(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, want, ws, ws_bytes, stream);
+  return render_fused(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, 0.f, want, ws, ws_bytes, stream);
 }
 
 /* launch sequence of the per-phase kernels (whole frames: every kernel fills the chip, nothing to gain from fusion) */
 static int render_sequence(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
                            const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near,
-                           float far, float* const want[13], void* ws, size_t ws_bytes, rdrf_stream_t stream) {
+                           float far, float step, float* const want[13], void* ws, size_t ws_bytes, rdrf_stream_t stream) {
   if (N == 0) return 0;
-  int rc = render_check(PS, cfg_s, PD, cfg_d, rays, ts, N, S, ws_bytes);
+  int rc = render_check(PS, cfg_s, PD, cfg_d, rays, ts, N, S, step, ws_bytes);
   if (rc) return rc;
   RenderBufs b;
   rc = carve_render(b, ws, ws_bytes, N, S, want);
   if (rc) return rc;
   if (cfg_d->ray_type == RDRF_RAY_NDC)
     rc = rdrf_sample_ndc(rays, N, S, near, far, nullptr, cfg_d->aabb, b.xyz, b.z, b.valid, stream);
-  else
+  else if (cfg_d->ray_type == RDRF_RAY_CONTRACT)
     rc = rdrf_sample_contract(rays, N, S, near, far, nullptr, nullptr, b.xyz, b.z, b.valid, stream);
+  else
+    rc = rdrf_sample_world(rays, N, S, near, far, step, nullptr, cfg_d->aabb, b.xyz, b.z, b.valid, stream);
   if (rc) return rc;
   // (a side stream for the static density phase under the dynamic field's density kernel does not overlap: the MLP kernels
   // hold all 512 VGPRs of every SIMD, so no other wave becomes resident; measured)
@@ -279,7 +290,7 @@ extern "C" int rdrf_render_sequence_fwd(const RdrfStaticParams* PS, const RdrfFi
   if (N == 0) return 0;
   RDRF_CHECK(rgb_map && depth_map, -1, "render: bad arguments");
   float* want[13] = {rgb_map, depth_map};
-  return render_sequence(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, want, ws, ws_bytes, stream);
+  return render_sequence(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, 0.f, want, ws, ws_bytes, stream);
 }
 
 // Measured on MI355X (tools/render_bench.py, Balloon1 stage-0 shape, 240 x 135 frame): whole frame 7.7 ms either way (the
@@ -307,8 +318,8 @@ extern "C" int rdrf_render_maps_fwd(const RdrfStaticParams* PS, const RdrfFieldC
              "render_maps: unknown mode %d", mode);
   float* want[13];
   maps_to_slots(want, maps);
-  return mode == RDRF_RENDER_FUSED ? render_fused(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, want, ws, ws_bytes, stream)
-                                   : render_sequence(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, want, ws, ws_bytes, stream);
+  return mode == RDRF_RENDER_FUSED ? render_fused(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, 0.f, want, ws, ws_bytes, stream)
+                                   : render_sequence(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, 0.f, want, ws, ws_bytes, stream);
 }
 
 // where a render with these `maps` left what the motion maps read (rdrf_motion.hip): the carve of the render itself
@@ -343,7 +354,7 @@ static void offset_slots(float* dst[13], float* const src[13], int r0) {
 }
 static int render_chunks(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
                          const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, int chunk,
-                         float near, float far, float* const want[13], void* ws, size_t ws_bytes,
+                         float near, float far, float step, float* const want[13], void* ws, size_t ws_bytes,
                          rdrf_stream_t main_stream_, const rdrf_stream_t* streams, int nstreams) {
   if (N == 0) return 0;
   RDRF_CHECK(PS && PD && cfg_s && cfg_d && rays && ts && ws && chunk > 0 && S > 0, -1,
@@ -379,7 +390,7 @@ static int render_chunks(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, 
         const int n = N - c0 < super ? N - c0 : super;
         float* part[13];
         offset_slots(part, want, c0);
-        const int rc = render_sequence(PS, cfg_s, PD, cfg_d, rays + (size_t)c0 * 6, ts + c0, n, S, near, far, part, ws,
+        const int rc = render_sequence(PS, cfg_s, PD, cfg_d, rays + (size_t)c0 * 6, ts + c0, n, S, near, far, step, part, ws,
                                        ws_bytes, main_stream_);
         if (rc) return rc;
       }
@@ -403,8 +414,8 @@ static int render_chunks(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, 
     rdrf_stream_t st = nstreams >= 1 ? streams[si] : main_stream_;
     float* part[13];
     offset_slots(part, want, c0);
-    rc = render_sequence(PS, cfg_s, PD, cfg_d, rays + (size_t)c0 * 6, ts + c0, n, S, near, far, part, (char*)ws + slice * si,
-                         slice, st);
+    rc = render_sequence(PS, cfg_s, PD, cfg_d, rays + (size_t)c0 * 6, ts + c0, n, S, near, far, step, part,
+                         (char*)ws + slice * si, slice, st);
   }
   if (nstreams >= 1) {   // join (also on error: the streams must not run past the caller's buffers unobserved)
     for (int q = 0; q < nstreams; ++q) {
@@ -424,7 +435,7 @@ extern "C" int rdrf_render_chunks_fwd(const RdrfStaticParams* PS, const RdrfFiel
   if (N == 0) return 0;
   RDRF_CHECK(rgb_map && depth_map, -1, "render_chunks: bad arguments");
   float* want[13] = {rgb_map, depth_map};
-  return render_chunks(PS, cfg_s, PD, cfg_d, rays, ts, N, S, chunk, near, far, want, ws, ws_bytes, main_stream, streams,
+  return render_chunks(PS, cfg_s, PD, cfg_d, rays, ts, N, S, chunk, near, far, 0.f, want, ws, ws_bytes, main_stream, streams,
                        nstreams);
 }
 extern "C" int rdrf_render_chunks_maps_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
@@ -434,8 +445,27 @@ extern "C" int rdrf_render_chunks_maps_fwd(const RdrfStaticParams* PS, const Rdr
                                            int nstreams) {
   float* want[13];
   maps_to_slots(want, maps);
-  return render_chunks(PS, cfg_s, PD, cfg_d, rays, ts, N, S, chunk, near, far, want, ws, ws_bytes, main_stream, streams,
+  return render_chunks(PS, cfg_s, PD, cfg_d, rays, ts, N, S, chunk, near, far, 0.f, want, ws, ws_bytes, main_stream, streams,
                        nstreams);
+}
+
+// World-space rays (RDRF_RAY_OTHER): the family above behind one entry point that carries the sampler's `step`.
+extern "C" int rdrf_render_world_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                                     const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, int chunk,
+                                     float near, float far, float step, int mode, const RdrfRenderMaps* maps, void* ws,
+                                     size_t ws_bytes, rdrf_stream_t main_stream, const rdrf_stream_t* streams, int nstreams) {
+  if (N == 0) return 0;
+  RDRF_CHECK(step > 0.0f, -1, "render_world: step must be positive (the field's stepSize)");
+  float* want[13];
+  maps_to_slots(want, maps);
+  if (chunk > 0)
+    return render_chunks(PS, cfg_s, PD, cfg_d, rays, ts, N, S, chunk, near, far, step, want, ws, ws_bytes, main_stream, streams,
+                         nstreams);
+  RDRF_CHECK(mode == RDRF_RENDER_AUTO || mode == RDRF_RENDER_SEQUENCE || mode == RDRF_RENDER_FUSED, -1,
+             "render_world: unknown mode %d", mode);
+  return mode == RDRF_RENDER_FUSED ? render_fused(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, step, want, ws, ws_bytes, main_stream)
+                                   : render_sequence(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, step, want, ws, ws_bytes,
+                                                     main_stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -626,6 +626,10 @@ class TensorBase(nn.Module):
         self.gridSize = torch.LongTensor(list(gridSize)).to(self.device)
         self.units = self.aabbSize / (self.gridSize - 1)
         self.stepSize = torch.mean(self.units) * self.step_ratio
+        # the same fp32 arithmetic on the host, for the world-space sampler's C argument (a device reduction may order the
+        # three-term mean differently, and the sampler's bits are pinned against the host's)
+        size_h = torch.tensor(self._aabb_host[3:]) - torch.tensor(self._aabb_host[:3])
+        self._step_host = float(torch.mean(size_h / (torch.LongTensor(list(gridSize)) - 1)) * self.step_ratio)
         self.aabbDiag = torch.sqrt(torch.sum(torch.square(self.aabbSize)))
         self.nSamples = int((self.aabbDiag / self.stepSize).item()) + 1
         self.tSize = torch.unsqueeze(torch.tensor(tSize), 0).to(self.device)
@@ -705,6 +709,12 @@ class TensorBase(nn.Module):
         xyz, z, valid = sample_rays(self, torch.cat([rays_o, rays_d], -1), N_samples, "contract",
                                     is_train)
         return xyz, z[:1], valid
+
+    def sample_ray(self, rays_o, rays_d, is_train=True, N_samples=-1):
+        """models/tensorBase.py:501-522: the world-space march; z_vals per ray, [N,S]"""
+        from .renderer import sample_rays
+        N_samples = N_samples if N_samples > 0 else self.nSamples
+        return sample_rays(self, torch.cat([rays_o, rays_d], -1), N_samples, "world", is_train)
 
     @torch.no_grad()
     def up_sampling_VM(self, plane_coef, line_coef, res_target):

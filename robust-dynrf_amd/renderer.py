@@ -19,7 +19,7 @@ MotionMaps = namedtuple("MotionMaps", L.MOTION_MAPS)
 
 class _SampleFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, rays, aabb_host, near, far, S, ray_type, jitter, jitter_outer):
+    def forward(ctx, rays, aabb_host, near, far, S, ray_type, jitter, jitter_outer, step):
         ctx.set_materialize_grads(False)
         L.require_device(rays)
         rays = L.f32c(rays)
@@ -38,35 +38,67 @@ class _SampleFn(torch.autograd.Function):
                                                L.ptr(jitter), L.ptr(jitter_outer), L.ptr(xyz),
                                                L.ptr(z), L.ptr(valid), L.stream_of(rays)),
                     "rdrf_sample_contract")
-        else:
-            raise NotImplementedError("ray_type must be 'ndc' or 'contract' (the shipped configs)")
+        else:   # every other ray_type marches in world space (models/tensorBase.py:501-522); jitter: one value per ray
+            ab = (C.c_float * 6)(*aabb_host)
+            L.check(L.lib.rdrf_sample_world(L.ptr(rays), N, S, C.c_float(near), C.c_float(far), C.c_float(step),
+                                            L.ptr(jitter), ab, L.ptr(xyz), L.ptr(z), L.ptr(valid),
+                                            L.stream_of(rays)), "rdrf_sample_world")
+            ctx.world = (ab, near, far)
         ctx.ray_type = ray_type
         ctx.save_for_backward(rays, z)
-        ctx.mark_non_differentiable(valid, z)
+        if ray_type in L.RAY_TYPES:
+            ctx.mark_non_differentiable(valid, z)
+        else:   # these z depend on the ray (through the entry depth t_min)
+            ctx.mark_non_differentiable(valid)
         return xyz, z, valid.view(torch.bool)
 
     @staticmethod
     def backward(ctx, g_xyz, g_z, g_valid):
         rays, z = ctx.saved_tensors
         N, S = z.shape
+        none = (None,) * 9
+        if ctx.ray_type not in L.RAY_TYPES:
+            if g_xyz is None and g_z is None:
+                return none
+            g_rays = torch.zeros_like(rays)
+            g_xyz = None if g_xyz is None else L.f32c(g_xyz)
+            g_z = None if g_z is None else L.f32c(g_z)
+            ab, near, far = ctx.world
+            L.check(L.lib.rdrf_sample_world_bwd(L.ptr(rays), L.ptr(z), N, S, C.c_float(near), C.c_float(far), ab,
+                                                L.ptr(g_xyz), L.ptr(g_z), L.ptr(g_rays), L.stream_of(rays)),
+                    "rdrf_sample_world_bwd")
+            return (g_rays,) + none[1:]
         if g_xyz is None:   # z_vals / valid carry no gradient to the rays
-            return None, None, None, None, None, None, None, None
+            return none
         g_rays = torch.zeros_like(rays)
         g_xyz = L.f32c(g_xyz)
         L.check(L.lib.rdrf_sample_bwd(L.ptr(rays), L.ptr(z), N, S, L.RAY_TYPES[ctx.ray_type],
                                       L.ptr(g_xyz), L.ptr(g_rays), L.stream_of(rays)),
                 "rdrf_sample_bwd")
-        return g_rays, None, None, None, None, None, None, None
+        return (g_rays,) + none[1:]
 
 
 def sample_rays(tensorf, rays, N_samples, ray_type="ndc", is_train=False, jitter=None,
                 jitter_outer=None):
     """sample_ray_ndc / sample_ray_contracted with the z row tiled to [N,S]
     (models/tensorBase.py:487-559 + renderer.py:169). The train-time jitter is drawn with torch's
-    device RNG here unless given."""
+    device RNG here unless given.
+    Any other ray_type -- write "world" -- is sample_ray (models/tensorBase.py:501-522): the rays march through the
+    field's aabb in world space, tensorf.stepSize apart, from their entry depth clamped to near_far; z_vals [N,S] are
+    per ray as sample_ray returns them, and `jitter` is ONE value per ray, [N]."""
     near, far = tensorf.near_far
     S = int(N_samples)
     dev = rays.device
+    if ray_type not in L.RAY_TYPES:
+        N = rays.shape[0]
+        if is_train and jitter is None:
+            jitter = torch.rand(N, device=dev)
+        if jitter is not None:
+            jitter = L.f32c(jitter.reshape(-1))
+            if jitter.numel() != N:
+                raise L.RdrfError(f"sample_rays: the world-space march takes one jitter value per ray ({N}), got {jitter.numel()}")
+        return _SampleFn.apply(rays, tensorf._aabb_host, float(near), float(far), S, ray_type, jitter, None,
+                               tensorf._step_host)
     if is_train and jitter is None:
         if ray_type == "ndc":
             jitter = torch.rand(S, device=dev)
@@ -78,12 +110,13 @@ def sample_rays(tensorf, rays, N_samples, ray_type="ndc", is_train=False, jitter
     if jitter_outer is not None:
         jitter_outer = L.f32c(jitter_outer.reshape(-1))
     return _SampleFn.apply(rays, tensorf._aabb_host, float(near), float(far), S, ray_type, jitter,
-                           jitter_outer)
+                           jitter_outer, None)
 
 
 def sampleXYZ(tensorf, rays_train, N_samples, ray_type="ndc", is_train=False, jitter=None,
               jitter_outer=None):
-    """renderer.py:147-170 (extra keyword: explicit jitter vectors for reproducible tests)."""
+    """renderer.py:147-170 (extra keyword: explicit jitter vectors for reproducible tests).  ray_type "ndc", "contract" or
+    "world" (any other string: the reference's `else` branch, TensorBase.sample_ray)."""
     if N_samples is None or N_samples <= 0:
         N_samples = tensorf.nSamples
     return sample_rays(tensorf, rays_train, N_samples, ray_type, is_train, jitter, jitter_outer)
@@ -225,6 +258,8 @@ def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc",
     """No-grad render of a ray chunk through ONE C-ABI call: the loop body of renderer.py:740-812.
     mode "auto" (rdrf_render_fwd: the per-phase launch sequence), "fused" (rdrf_render_fused_fwd:
     one cooperative launch) or "sequence" (rdrf_render_sequence_fwd); all three give the same bits.
+    ray_type "ndc", "contract" or "world" (any other string: the world-space march of sample_rays, through
+    rdrf_render_world_fwd; no `motion` for it).
     Returns (rgb_map_full[N,3], depth_map_full[N]); with `maps` (True, or a subset of the RenderMaps field names)
     a RenderMaps of the per-ray outputs ([N,3] rgb maps, [N] others; None where not requested), through
     rdrf_render_maps_fwd: the same bits as raw2outputs after the fields' forward.
@@ -251,7 +286,8 @@ def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc",
     near, far = tensorf.near_far
     if motion is not None:
         if ray_type not in L.RAY_TYPES:
-            raise NotImplementedError("ray_type must be 'ndc' or 'contract' (the shipped configs)")
+            raise NotImplementedError("motion maps: ray_type must be 'ndc' or 'contract' (the reference projects no other, "
+                                      "renderer.py:1335-1351)")
         bufs = _alloc_maps(_map_names(maps), N, dev) if maps else {"rgb": rgb, "depth": depth}
         M = _maps_struct(bufs)
         mbufs, MM, cams, keep = _motion_request(motion, N, dev)
@@ -261,6 +297,13 @@ def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc",
         del keep
         out = RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS}) if maps else (rgb, depth)
         return out, MotionMaps(**{n: mbufs.get(n) for n in L.MOTION_MAPS})
+    if ray_type not in L.RAY_TYPES:   # world-space rays: one entry point for the family, it carries the sampler's step
+        bufs = _alloc_maps(_map_names(maps), N, dev) if maps else {"rgb": rgb, "depth": depth}
+        M = _maps_struct(bufs)
+        L.check(L.lib.rdrf_render_world_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S, 0,
+                                            near, far, tensorf._step_host, L.RENDER_MODES[mode], C.byref(M), L.ptr(ws),
+                                            ws.numel(), L.stream_of(rays), None, 0), "rdrf_render_world_fwd")
+        return RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS}) if maps else (rgb, depth)
     if maps:
         names = _map_names(maps)
         bufs = _alloc_maps(names, N, dev)
@@ -314,7 +357,12 @@ def render_chunks(tensorf_static, tensorf, rays, ts, chunk, N_samples=-1, ray_ty
     if pool is None:
         pool = _stream_pool[(dev, ns)] = [torch.cuda.Stream(device=dev) for _ in range(ns)]
     arr = (C.c_void_p * max(ns, 1))(*[st.cuda_stream for st in pool]) if ns else None
-    if maps:
+    if ray_type not in L.RAY_TYPES:   # world-space rays (see render_rays)
+        M = _maps_struct(bufs if maps else {"rgb": rgb, "depth": depth})
+        L.check(L.lib.rdrf_render_world_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S,
+                                            chunk, near, far, tensorf._step_host, 0, C.byref(M), L.ptr(ws), ws.numel(),
+                                            L.stream_of(rays), arr, ns), "rdrf_render_world_fwd")
+    elif maps:
         M = _maps_struct(bufs)
         L.check(L.lib.rdrf_render_chunks_maps_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N,
                                                   S, chunk, near, far, C.byref(M), L.ptr(ws), ws.numel(), L.stream_of(rays),
@@ -436,12 +484,14 @@ def camera_rays(c2w, focal, H, W, ndc=True, near=1.0, first=0, n=None):
 def render_view(tensorf_static, tensorf, c2w, focal, H, W, t, N_samples=-1, ray_type="ndc", maps=True, chunk=None,
                 c2w_f=None, c2w_b=None, motion=False):
     """One arbitrary camera c2w [3,4] (host or device; moved to the fields' device) at time t in [-1,1]: the per-view body
-    of renderer.py:970-1263 `evaluation_path` (eval rays: camera_rays, NDC with near = 1 for ndc scenes).  Returns a
+    of renderer.py:970-1263 `evaluation_path` (eval rays: camera_rays, NDC with near = 1 for ndc scenes; ray_type "world":
+    the camera's un-normalised world rays marched through the aabb, see sample_rays).  Returns a
     RenderMaps of [H,W,3] / [H,W] images (clamped as render_frame) with `maps`, else (rgb [H,W,3], depth [H,W]).
     With `motion` (True, or a subset of the MotionMaps field names) and the neighbour cameras c2w_f / c2w_b [3,4] (default:
     the view's own camera): returns (the above, MotionMaps of [H,W,2] / [H,W,3] images) as render_frame."""
-    if ray_type not in ("ndc", "contract"):
-        raise NotImplementedError("ray_type must be 'ndc' or 'contract' (the shipped configs)")
+    if motion and ray_type not in L.RAY_TYPES:
+        raise NotImplementedError("motion maps: ray_type must be 'ndc' or 'contract' (the reference projects no other, "
+                                  "renderer.py:1335-1351)")
     dev = tensorf.aabb.device
     c2w = torch.as_tensor(c2w, dtype=torch.float32).to(dev)
     if torch.is_tensor(focal) and focal.device != dev:
