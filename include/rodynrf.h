@@ -703,6 +703,52 @@ int rdrf_selftest_warp_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, 
                            const float* g_xyz_prime, const RdrfDynamicParams* grads, float* g_xyz, float* dtout, float* dtp,
                            void* ws, size_t ws_bytes, rdrf_stream_t stream);
 
+/* The radix sort of the sorted scatter as the product calls it: keys [n] (the low `bits` bits are sorted on) -> keys_out ascending
+ * and stable, order[i] = original position of keys_out[i].  count (nullable, device): only the first min(n, n_mul * *count) entries
+ * are sorted and written; the rest of keys_out / order is left alone.  temp: 256-byte aligned, rdrf_selftest_sort_temp_bytes(n, bits).
+ * n = 0 is a no-op. */
+size_t rdrf_selftest_sort_temp_bytes(unsigned n, int bits);
+int rdrf_selftest_sort(const unsigned* keys, unsigned n, int bits, const int* count, unsigned n_mul, unsigned* keys_out,
+                       unsigned* order, void* temp, size_t temp_bytes, rdrf_stream_t stream);
+
+/* The gradient scatter (VM gather backward) on data the caller supplies, through the launch functions of the backward entry
+ * points: kind = one of the four instantiations in use, mode = RDRF_SCATTER_RAY (ray / flat / list tiles), _SORTED (samples
+ * grouped by plane cell: key generation, sort, count search, then the windowed passes where the launch policy takes them) or
+ * _SORTED_PLAIN (the same without windows); the dynamic kinds have the sorted modes.  Layouts: rdrf_selftest_scatter_describe
+ * (csrc/rdrf_selftest.hip).  -1 bad arguments, -2 a mode or tile form the kind does not have, -3 a buffer too small. */
+#define RDRF_SCK_STATIC_DENSITY 0 /* k_scatter<4,1,3>:   row 0 broadcast, xyz + box, g_xyz */
+#define RDRF_SCK_DYN_DENSITY 1    /* k_scatter<4,1,9>:   density and / or blending by set mask, ray or flat tiles, dxw added */
+#define RDRF_SCK_STATIC_APP 2     /* k_scatter<12,3,9>:  list + device count, xyz + box, g_xyz */
+#define RDRF_SCK_DYN_APP 3        /* k_scatter<12,3,27>: list + device count, xw, dxw written (ray) / added (sorted) */
+typedef struct {
+  RdrfVM vm[2], gvm[2];       /* factor values and gradient buffers (same sizes and strides); set 1: blending (DYN_DENSITY only) */
+  int set_mask;               /* DYN_DENSITY: bit 0 density, bit 1 blending */
+  int N, S, flat;             /* flat: the tiles are 32-sample tiles of the [N S] array (DYN_DENSITY) */
+  const float* coords;        /* [N S][3]: xyz (static kinds) or normalised xw (dynamic kinds) */
+  float box_lo[3], box_inv[3];
+  const unsigned char* valid; /* [N S] */
+  const int* list;            /* appearance kinds: sample ids + device count */
+  const int* count;
+  const float* rows;          /* ray modes: d(feature) rows [tiles][stride][32]; DYN_DENSITY sorted: the liveness rows are read */
+  size_t rows_floats;
+  const float* recs;          /* sorted modes: sample-major records [N S][rec_floats] */
+  size_t recs_floats;
+  float* dxw;                 /* [N S][3] */
+  float* g_xyz;               /* [N S][3] */
+  void* ws;                   /* sorted modes: 256-byte aligned, rdrf_selftest_scatter_workspace_bytes(N, S) */
+  size_t ws_bytes;
+  unsigned* keys_out;         /* sorted modes, nullable: [3 N S] keys as generated, [3 N S] sorted keys, [3 N S] order, [3] live entries per plane */
+  unsigned* keys_sorted_out;
+  unsigned* order_out;
+  int* counts_out;
+} RdrfScatterTest;
+size_t rdrf_selftest_scatter_workspace_bytes(int N, int S);
+int rdrf_selftest_scatter(int kind, int mode, const RdrfScatterTest* t, rdrf_stream_t stream);
+/* host only: the kind's layouts / the launch decisions of the most recent scatter as ints; return the number written, -3 when cap
+ * is too small.  grid: nullable {W, H} of the three level-0 planes, for the key layout. */
+int rdrf_selftest_scatter_describe(int kind, const int* grid, int* out, int cap);
+int rdrf_selftest_scatter_last(int* out, int cap);
+
 /* timing hook: average device time (ms) of the dominant kernel launches recorded with HIP events
  * since the last reset; used by bench.py for the roofline figure. */
 void rdrf_prof_reset(void);

@@ -53,6 +53,15 @@ class RdrfDynamicParams(C.Structure):
                 ("sfw", C.c_void_p * 4), ("sfb", C.c_void_p * 4), ("packed_fwd", C.c_void_p), ("packed_bwd", C.c_void_p)]
 
 
+class RdrfScatterTest(C.Structure):   # include/rodynrf.h RdrfScatterTest (rdrf_selftest_scatter)
+    _fields_ = [("vm", RdrfVM * 2), ("gvm", RdrfVM * 2), ("set_mask", C.c_int), ("N", C.c_int), ("S", C.c_int), ("flat", C.c_int),
+                ("coords", C.c_void_p), ("box_lo", C.c_float * 3), ("box_inv", C.c_float * 3), ("valid", C.c_void_p),
+                ("list", C.c_void_p), ("count", C.c_void_p), ("rows", C.c_void_p), ("rows_floats", C.c_size_t),
+                ("recs", C.c_void_p), ("recs_floats", C.c_size_t), ("dxw", C.c_void_p), ("g_xyz", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_size_t), ("keys_out", C.c_void_p), ("keys_sorted_out", C.c_void_p), ("order_out", C.c_void_p),
+                ("counts_out", C.c_void_p)]
+
+
 # RdrfRenderMaps (include/rodynrf.h): one nullable device pointer per per-ray output of the render, in this order
 RENDER_MAPS = ("rgb", "depth", "acc", "rgb_s", "depth_s", "acc_s", "rgb_d", "depth_d", "acc_d", "blending")
 
@@ -168,6 +177,15 @@ def _load():
     lib.rdrf_selftest_warp_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.rdrf_selftest_sort_temp_bytes.restype = C.c_size_t
+    lib.rdrf_selftest_sort_temp_bytes.argtypes = [C.c_uint, C.c_int]
+    lib.rdrf_selftest_sort.argtypes = [C.c_void_p, C.c_uint, C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]
+    lib.rdrf_selftest_scatter_workspace_bytes.restype = C.c_size_t
+    lib.rdrf_selftest_scatter_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.rdrf_selftest_scatter.argtypes = [C.c_int, C.c_int, C.POINTER(RdrfScatterTest), C.c_void_p]
+    lib.rdrf_selftest_scatter_describe.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
+    lib.rdrf_selftest_scatter_last.argtypes = [C.POINTER(C.c_int), C.c_int]
     lib.rdrf_prof_get.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     lib.rdrf_det_bind.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.rdrf_det_finish.argtypes = [C.c_int, C.c_void_p]
@@ -201,6 +219,8 @@ SYMBOLS = [
     "rdrf_gather_batch",
     "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_selftest_layer", "rdrf_selftest_dw", "rdrf_selftest_dw_describe",
     "rdrf_selftest_sf_geometry", "rdrf_selftest_warp_geometry", "rdrf_selftest_warp_bwd_workspace_bytes", "rdrf_selftest_warp_bwd",
+    "rdrf_selftest_sort_temp_bytes", "rdrf_selftest_sort", "rdrf_selftest_scatter_workspace_bytes", "rdrf_selftest_scatter",
+    "rdrf_selftest_scatter_describe", "rdrf_selftest_scatter_last",
     "rdrf_prof_reset",
     "rdrf_prof_enable", "rdrf_prof_get",
 ]
@@ -212,6 +232,9 @@ SELFTEST_FORMS = {"F32": 0, "F32_T": 1, "B3": 2, "B3_T": 3, "B3_PAIR_T": 4, "B3S
 # rdrf_selftest_dw plans and flags (include/rodynrf.h RDRF_DW_*)
 DW_PLANS = {"DENSITY": 0, "STATIC_FEA": 1, "STATIC_TE": 2, "DYN_APP": 3, "DYN": 4, "SCENE_FLOW": 5, "FEAT_STATIC": 6, "FEAT_DYN": 7}
 DW_LIVE_D, DW_LIVE_B, DW_SMALL_IN_KERNEL, DW_WARP_IN_KERNEL = 1, 2, 4, 8
+
+# rdrf_selftest_scatter kinds (include/rodynrf.h RDRF_SCK_*)
+SCATTER_KINDS = {"STATIC_DENSITY": 0, "DYN_DENSITY": 1, "STATIC_APP": 2, "DYN_APP": 3}
 
 SCATTER_MODES = {"ray": 0, "sorted": 1, "auto": 2, "sorted_plain": 3}
 

@@ -62,6 +62,24 @@ int scatter_dyn_app_sorted(const BwdArgs& a, const BwdWs& b, const RdrfDynamicPa
                            hipStream_t stream);
 int scatter_dyn_density_sorted(const BwdArgs& a, const BwdWs& b, const RdrfDynamicParams* P, const RdrfDynamicParams* G,
                                int set_mask, hipStream_t stream);
+int sorted_key_bits(const int W[3], const int H[3]);   // bits of the cell part of a sort key: cells of (W + 3) x (H + 3) + the drop code
+int scatter_mode_swap(int mode);                       // sets the process-wide scatter mode, returns the previous one (self-tests)
+// What the launch policy decided for the most recent scatter (host stores only; rdrf_selftest_scatter_last reads it): one entry
+// per kernel launch of the last launch_scatter / scatter_dyn_*_sorted call.
+struct ScatterLaunch {
+  int elem_bytes;    // LDS line accumulators: 8 doubles, 4 floats, 0 none (global atomics)
+  int threads, workgroups;
+  int tiled;         // sorted passes: 1 k_scatter_tiled taken, 0 refused by the policy (k_scatter_sorted ran), -2 windows switched
+                     // off (_SORTED_PLAIN, deterministic build), -1 not tried (appearance); ray tiles: -1
+  int tw, slice_steps;
+};
+struct ScatterRecord {
+  int form;          // 0 ray tiles (launch_scatter), 1 sorted passes
+  int split;         // ray tiles: one launch per factor set
+  int n;
+  ScatterLaunch l[4];
+};
+const ScatterRecord& scatter_last_record();   // of the calling host thread
 
 // ------------------------------------------------------------------------------------------------
 // generic dW kernel: dW[out][col(e)] += sum_tiles sum_samples dz[out][s] * in[e][s]

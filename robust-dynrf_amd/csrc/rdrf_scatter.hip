@@ -449,6 +449,19 @@ __global__ __launch_bounds__(512, 4) void k_scatter_tiled(SortedScatterArgs a) {
   if (a.set_mask & 2) flush_lds_line(lacc, 1, nl0, a.vm[1].L[PLANE], a.vm[1].C[PLANE], a.gvm[1].line[PLANE]);
 }
 
+// the launch decisions of the most recent scatter of the calling host thread (ScatterRecord, rdrf_bwd_host.hpp): thread_local,
+// so that backward passes running on several host threads do not write one struct
+static thread_local ScatterRecord g_last_scatter;
+const ScatterRecord& scatter_last_record() { return g_last_scatter; }
+static void record_begin(int form) {
+  memset(&g_last_scatter, 0, sizeof(g_last_scatter));
+  g_last_scatter.form = form;
+}
+static void record_launch(int elem_bytes, int threads, long workgroups, int tiled, int tw, int slice_steps) {
+  if (g_last_scatter.n >= 4) return;
+  g_last_scatter.l[g_last_scatter.n++] = ScatterLaunch{elem_bytes, threads, (int)workgroups, tiled, tw, slice_steps};
+}
+
 void fill_scatter_common(ScatterArgs& sa, const BwdArgs& a) {
   memset(&sa, 0, sizeof(sa));
   sa.xyz = a.xyz; sa.box = a.box; sa.valid = a.valid; sa.N = a.N; sa.S = a.S;
@@ -486,6 +499,7 @@ static int launch_scatter_k(const char* name, K kern, ScatterArgs& sa, long ntil
     s1.nsets = 1;
     s1.vm[0] = sa.vm[1]; s1.gvm[0] = sa.gvm[1]; s1.row0[0] = sa.row0[1];
     s1.dxw_accumulate = 1;
+    g_last_scatter.split = 1;
     int rc = launch_scatter_k(name, kern, s0, ntiles, stream);
     return rc ? rc : launch_scatter_k(name, kern, s1, ntiles, stream);
   }
@@ -504,6 +518,7 @@ static int launch_scatter_k(const char* name, K kern, ScatterArgs& sa, long ntil
   static const long cap_env = RDRF_ENV("RDRF_SC_CAP") ? atol(RDRF_ENV("RDRF_SC_CAP")) : 0;   // experiments (tools build)
   const long cap = per_cu == 1 ? 256 : (cap_env > 0 ? cap_env : 256 * per_cu);
   g = g < 1 ? 1 : (g > cap ? cap : g);
+  record_launch(esz, threads, g, -1, 0, 0);
   rdrf_prof_begin(name, stream);
   hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(threads), (size_t)sa.lds_bytes, stream, sa);
   rdrf_prof_end(name, stream);
@@ -511,6 +526,7 @@ static int launch_scatter_k(const char* name, K kern, ScatterArgs& sa, long ntil
   return 0;
 }
 int launch_scatter(const char* name, ScatterKernel kern, ScatterArgs& sa, long ntiles, hipStream_t stream) {
+  record_begin(0);
   switch (kern) {
     case SCATTER_4_1_3: return launch_scatter_k(name, k_scatter<4, 1, 3>, sa, ntiles, stream);
     case SCATTER_4_1_9: return launch_scatter_k(name, k_scatter<4, 1, 9>, sa, ntiles, stream);
@@ -533,6 +549,11 @@ extern "C" int rdrf_set_scatter_mode(int mode) {
   g_scatter_mode = mode;
   return 0;
 }
+int scatter_mode_swap(int mode) {
+  const int old = g_scatter_mode;
+  g_scatter_mode = mode;
+  return old;
+}
 int scatter_mode(size_t ns, hipStream_t stream) {   // 0 ray, 1 sorted
   int m = g_scatter_mode;
   if (const char* e = RDRF_ENV("RDRF_SCATTER")) m = !strcmp(e, "sorted") ? RDRF_SCATTER_SORTED : (!strcmp(e, "ray") ? RDRF_SCATTER_RAY : m);
@@ -552,7 +573,7 @@ int scatter_mode(size_t ns, hipStream_t stream) {   // 0 ray, 1 sorted
 }
 
 template <int PLANE, int C0Q, int C1Q>
-static int launch_scatter_sorted(SortedScatterArgs& sa, long max_samples, hipStream_t stream) {
+static int launch_scatter_sorted(SortedScatterArgs& sa, long max_samples, hipStream_t stream, int tiled_state = -1) {
   // pass PLANE accumulates line PLANE only: L x (C + 4) elements per factor set, doubles when they fit (see LdsLines)
   const long n = ((sa.set_mask & 1) ? (long)sa.vm[0].L[PLANE] * (sa.vm[0].C[PLANE] + 4) : 0) +
                  ((sa.set_mask & 2) ? (long)sa.vm[1].L[PLANE] * (sa.vm[1].C[PLANE] + 4) : 0);
@@ -580,6 +601,7 @@ static int launch_scatter_sorted(SortedScatterArgs& sa, long max_samples, hipStr
   const long cap = 256 * per_cu;
   g = g < 1 ? 1 : (g > cap ? cap : g);
   static const char* names[3] = {"scatter_sorted_xy", "scatter_sorted_xz", "scatter_sorted_yz"};
+  record_launch(sa.lds_bytes > 0 ? esz : 0, threads, g, tiled_state, 0, 0);
   rdrf_prof_begin(names[PLANE], stream);
   hipLaunchKernelGGL((k_scatter_sorted<PLANE, C0Q, C1Q>), dim3((unsigned)g), dim3(threads), (size_t)sa.lds_bytes, stream, sa);
   rdrf_prof_end(names[PLANE], stream);
@@ -645,6 +667,7 @@ static int launch_scatter_tiled(SortedScatterArgs& sa, const unsigned* keys_sort
   long g = nslices < 256L * per_cu ? nslices : 256L * per_cu;
   g = g < 1 ? 1 : g;
   static const char* names[3] = {"scatter_tiled_xy", "scatter_tiled_xz", "scatter_tiled_yz"};
+  record_launch(8, 512, g, 1, tw, sa.slice_steps);
   rdrf_prof_begin(names[PLANE], stream);
   hipLaunchKernelGGL((k_scatter_tiled<PLANE, C0Q, C1Q>), dim3((unsigned)g), dim3(512), (size_t)sa.lds_bytes, stream, sa);
   rdrf_prof_end(names[PLANE], stream);
@@ -652,18 +675,23 @@ static int launch_scatter_tiled(SortedScatterArgs& sa, const unsigned* keys_sort
   return 1;
 }
 
-// keys of the entries (all samples, or the compacted list), stable sort by (plane | cell), live counts per plane
-static int sorted_scatter_prepare(SortKeyArgs& ka, const RdrfVM& vm, const BwdArgs& a, const BwdWs& b, hipStream_t stream) {
-  const size_t ns = (size_t)a.N * a.S;
-  ka.xw = a.sp.xw; ka.valid = a.valid; ka.N = a.N; ka.S = a.S;
+int sorted_key_bits(const int W[3], const int H[3]) {
   long maxcells = 0;
   for (int p = 0; p < 3; ++p) {
-    ka.W[p] = vm.W[p]; ka.H[p] = vm.H[p];
-    const long c = (long)(ka.W[p] + 3) * (ka.H[p] + 3);
+    const long c = (long)(W[p] + 3) * (H[p] + 3);
     maxcells = c > maxcells ? c : maxcells;
   }
   int kb = 1;
   while (((1L << kb) - 1) < maxcells) ++kb;
+  return kb;
+}
+
+// keys of the entries (all samples, or the compacted list), stable sort by (plane | cell), live counts per plane
+static int sorted_scatter_prepare(SortKeyArgs& ka, const RdrfVM& vm, const BwdArgs& a, const BwdWs& b, hipStream_t stream) {
+  const size_t ns = (size_t)a.N * a.S;
+  ka.xw = a.sp.xw; ka.valid = a.valid; ka.N = a.N; ka.S = a.S;
+  for (int p = 0; p < 3; ++p) { ka.W[p] = vm.W[p]; ka.H[p] = vm.H[p]; }
+  const int kb = sorted_key_bits(ka.W, ka.H);
   RDRF_CHECK(kb <= 29, -1, "sorted scatter: plane too large for 32-bit keys");
   ka.kb = kb; ka.keys = b.keys_in; ka.counts = b.counts;
   rdrf_prof_begin("scatter_sort", stream);
@@ -692,6 +720,7 @@ static int sorted_scatter_prepare(SortKeyArgs& ka, const RdrfVM& vm, const BwdAr
 int scatter_dyn_app_sorted(const BwdArgs& a, const BwdWs& b, const RdrfDynamicParams* P, const RdrfDynamicParams* G,
                            hipStream_t stream) {
   const size_t ns = (size_t)a.N * a.S;
+  record_begin(1);
   SortKeyArgs ka;
   memset(&ka, 0, sizeof(ka));
   ka.list = a.sp.list; ka.count = &a.sp.hdr->count;
@@ -734,6 +763,7 @@ int scatter_dyn_density_sorted(const BwdArgs& a, const BwdWs& b, const RdrfDynam
   for (int p = 0; p < 3; ++p)
     RDRF_CHECK(P->blending.W[p] == P->density.W[p] && P->blending.H[p] == P->density.H[p], -1,
                "sorted scatter: density and blending planes differ in size");
+  record_begin(1);
   SortKeyArgs ka;
   memset(&ka, 0, sizeof(ka));
   ka.grows1 = b.grows1;
@@ -744,6 +774,13 @@ int scatter_dyn_density_sorted(const BwdArgs& a, const BwdWs& b, const RdrfDynam
   memset(&sa, 0, sizeof(sa));
   sa.vm[0] = P->density; sa.gvm[0] = G->density; sa.vm[1] = P->blending; sa.gvm[1] = G->blending;
   sa.set_mask = set_mask; sa.dfs = b.dfs; sa.rec_floats = DFS_FLOATS; sa.xw = a.sp.xw; sa.dxw = b.dxw;
+  // what a pass that runs k_scatter_sorted records: 0 = the launch policy refused the windows, -2 = windows switched off
+  // (RDRF_SCATTER_SORTED_PLAIN, the deterministic build)
+#ifdef RDRF_DETERMINISTIC
+  const int why = -2;
+#else
+  const int why = g_scatter_mode == RDRF_SCATTER_SORTED_PLAIN ? -2 : 0;
+#endif
   for (int p = 0; p < 3; ++p) {
     sa.order = b.order + (size_t)p * ns; sa.count = b.counts + p; sa.base = (unsigned)(p * ns);
     const unsigned* ks = b.keys_out + (size_t)p * ns;
@@ -752,8 +789,8 @@ int scatter_dyn_density_sorted(const BwdArgs& a, const BwdWs& b, const RdrfDynam
                           : launch_scatter_tiled<2, 4, 1>(sa, ks, ka.kb, (long)ns, stream));
     if (rc < 0) return rc;
     if (rc == 1) continue;
-    rc = p == 0 ? launch_scatter_sorted<0, 4, 1>(sa, (long)ns, stream)
-                : (p == 1 ? launch_scatter_sorted<1, 4, 1>(sa, (long)ns, stream) : launch_scatter_sorted<2, 4, 1>(sa, (long)ns, stream));
+    rc = p == 0 ? launch_scatter_sorted<0, 4, 1>(sa, (long)ns, stream, why)
+                : (p == 1 ? launch_scatter_sorted<1, 4, 1>(sa, (long)ns, stream, why) : launch_scatter_sorted<2, 4, 1>(sa, (long)ns, stream, why));
     if (rc) return rc;
   }
   return 0;

@@ -9,7 +9,13 @@
 //
 // rdrf_selftest_dw (end of the file, host code only): the dW job lists of the backward entry points (the builders of
 // rdrf_bwd.hip) planned and launched by dw_launch on rows the caller supplies; reference: tests/_dw_prim.py.
-#include "rdrf_kernels.hpp"
+//
+// rdrf_selftest_sort / rdrf_selftest_scatter (host code only): the radix sort as sorted_scatter_prepare calls it, and the
+// gradient scatter through the product's own launch functions (launch_scatter, scatter_dyn_*_sorted of rdrf_scatter.hip) on
+// data the caller supplies; reference: tests/_scatter_prim.py.
+#include <vector>
+
+#include "rdrf_bwd_dev.hpp"
 #include "rdrf_bwd_host.hpp"
 
 namespace {
@@ -382,4 +388,253 @@ extern "C" int rdrf_selftest_warp_bwd(const RdrfDynamicParams* P, const RdrfFiel
   float* pk = c.take<float>(warp_bwd_on_rows_pack_floats());
   uint8_t* valid = c.take<uint8_t>((size_t)N * S);
   return warp_bwd_on_rows(P, cfg, N, S, act1, grows1, dxw, dxn, g_xyz_prime, grads, g_xyz, dtout, dtp, pk, valid, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// rdrf_selftest_sort: rdrf_sort_positions on caller-owned arrays
+// ------------------------------------------------------------------------------------------------
+extern "C" size_t rdrf_selftest_sort_temp_bytes(unsigned n, int bits) { return rdrf_sort_temp_bytes(n, bits); }
+
+extern "C" int rdrf_selftest_sort(const unsigned* keys, unsigned n, int bits, const int* count, unsigned n_mul, unsigned* keys_out,
+                                  unsigned* order, void* temp, size_t temp_bytes, rdrf_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RDRF_CHECK(bits >= 1 && bits <= 32, -1, "selftest_sort: bits must be 1 .. 32 (got %d)", bits);
+  if (n == 0) return 0;   // nothing to sort: a no-op
+  RDRF_CHECK(keys && keys_out && order, -1, "selftest_sort: bad arguments (null keys, keys_out or order)");
+  RDRF_CHECK(count == nullptr || n_mul >= 1, -1, "selftest_sort: a device count needs n_mul >= 1");
+  RDRF_CHECK(temp != nullptr && (((uintptr_t)temp) & 255) == 0, -1, "selftest_sort: the temporary storage must be 256-byte aligned");
+  if (count) {   // n_mul * count is formed in 32 bits on the device
+    int c = -1;
+    RDRF_HIP(hipMemcpyAsync(&c, count, sizeof(int), hipMemcpyDeviceToHost, stream));
+    RDRF_HIP(hipStreamSynchronize(stream));
+    RDRF_CHECK(c >= 0 && (unsigned long long)c * n_mul <= 0xffffffffull, -1, "selftest_sort: device count %d out of range", c);
+  }
+  return rdrf_sort_positions(keys, keys_out, order, n, bits, temp, temp_bytes, stream, count, count ? n_mul : 0u);
+}
+
+// ------------------------------------------------------------------------------------------------
+// rdrf_selftest_scatter: the four instantiations of the scatter in use, with the arguments their backward entry points give
+// them (rdrf_bwd.hip), through launch_scatter (ray tiles) or scatter_dyn_*_sorted (key generation, sort, count search, sorted /
+// tiled passes).
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct ScatterKindInfo {
+  int c0q, c1q, nlv;       // quads of an XY / XZ-YZ texel, stride levels
+  int nsets;               // factor sets a launch can carry
+  int stride, row0[2];     // ray tiles: rows per tile, first d(feature) row of each set
+  int bcast;
+  int rec_floats, set_floats;   // sorted: floats per record / per set inside it (0: the kind has no sorted form)
+  int live_row[2];         // sorted key generation: the two rows whose zero marks a dead sample (-1: none)
+  int list, xw;            // compacted list + device count; normalised coordinates (else xyz + box)
+  int dxw_ray, dxw_sorted; // coordinate gradients: 0 none, 1 written, 2 added
+  int g_xyz, flat;         // g_xyz += dw * inv; the tiles may be flat 32-sample tiles
+  ScatterKernel kern;
+};
+
+bool scatter_kind_info(int kind, ScatterKindInfo& k) {
+  switch (kind) {
+    case RDRF_SCK_STATIC_DENSITY:
+      k = ScatterKindInfo{4, 1, 1, 1, 1, {0, -1}, 1, 0, 0, {-1, -1}, 0, 0, 0, 0, 1, 0, SCATTER_4_1_3};
+      return true;
+    case RDRF_SCK_DYN_DENSITY:
+      k = ScatterKindInfo{4, 1, 3, 2, sv::K1G_ROWS, {sv::K1G_DFD, sv::K1G_DFB}, 0, DFS_FLOATS, DFS_FLOATS / 2,
+                          {sv::K1G_SM + 3, sv::K1G_SM + 4}, 0, 1, 2, 2, 0, 1, SCATTER_4_1_9};
+      return true;
+    case RDRF_SCK_STATIC_APP:
+      k = ScatterKindInfo{12, 3, 1, 1, sv::K3G_ROWS, {sv::K3G_DA, -1}, 0, 0, 0, {-1, -1}, 1, 0, 0, 0, 1, 0, SCATTER_12_3_9};
+      return true;
+    case RDRF_SCK_DYN_APP:
+      k = ScatterKindInfo{12, 3, 3, 1, sv::K3G_ROWS, {sv::K3G_DA, -1}, 0, DFA_FLOATS, DFA_FLOATS, {-1, -1}, 1, 1, 1, 2, 0, 0,
+                          SCATTER_12_3_27};
+      return true;
+  }
+  return false;
+}
+
+bool scatter_vm_ok(const RdrfVM& v, const RdrfVM& g, int c0, int c1) {
+  if (!vm_ok(v, c0, c1)) return false;
+  for (int i = 0; i < 3; ++i) {
+    if (v.W[i] < 2 || v.H[i] < 2 || v.L[i] < 2 || !v.plane[i] || !v.line[i] || !g.plane[i] || !g.line[i]) return false;
+    if (g.C[i] != v.C[i] || g.W[i] != v.W[i] || g.H[i] != v.H[i] || g.L[i] != v.L[i] || g.sH[i] != v.sH[i] || g.sW[i] != v.sW[i])
+      return false;
+    const bool w_fast = v.sW[i] == v.C[i] && v.sH[i] == v.W[i] * v.C[i], h_fast = v.sH[i] == v.C[i] && v.sW[i] == v.H[i] * v.C[i];
+    if (!w_fast && !h_fast) return false;   // the two storage orders of a plane: the arrays hold H W C floats
+    if ((((uintptr_t)v.plane[i] | (uintptr_t)v.line[i] | (uintptr_t)g.plane[i] | (uintptr_t)g.line[i]) & 15) != 0) return false;
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" size_t rdrf_selftest_scatter_workspace_bytes(int N, int S) {
+  const size_t ns = (size_t)(N > 0 ? N : 0) * (size_t)(S > 0 ? S : 0);
+  const size_t arr = (3 * ns * 4 + 255) & ~(size_t)255;
+  return 3 * arr + 256 + ((rdrf_sort_temp_bytes((unsigned)(3 * ns), 32) + 255) & ~(size_t)255) + 512;
+}
+
+extern "C" int rdrf_selftest_scatter(int kind, int mode, const RdrfScatterTest* t, rdrf_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  ScatterKindInfo k;
+  RDRF_CHECK(scatter_kind_info(kind, k), -1, "selftest_scatter: unknown kind %d", kind);
+  RDRF_CHECK(mode == RDRF_SCATTER_RAY || mode == RDRF_SCATTER_SORTED || mode == RDRF_SCATTER_SORTED_PLAIN, -1,
+             "selftest_scatter: mode must be RDRF_SCATTER_RAY, _SORTED or _SORTED_PLAIN (got %d)", mode);
+  const bool sorted = mode != RDRF_SCATTER_RAY;
+  RDRF_CHECK(!sorted || k.rec_floats > 0, -2, "selftest_scatter: kind %d has no sorted form", kind);
+  RDRF_CHECK(t != nullptr, -1, "selftest_scatter: bad arguments (null description)");
+  if (t->N == 0) return 0;   // empty batch: a no-op
+  RDRF_CHECK(t->N > 0 && t->S > 0 && t->S <= 4096 && (size_t)t->N * t->S * 3 < (size_t)INT32_MAX / 4, -1,
+             "selftest_scatter: bad batch shape %d x %d", t->N, t->S);
+  const int N = t->N, S = t->S;
+  const size_t ns = (size_t)N * S;
+  const int flat = t->flat != 0;
+  RDRF_CHECK(!flat || k.flat, -2, "selftest_scatter: kind %d has no flat tiles", kind);
+  // the sorted density / blending passes address the liveness rows the way the process-wide density phase does
+  RDRF_CHECK(!(sorted && kind == RDRF_SCK_DYN_DENSITY) || flat == (rdrf_flat_density() ? 1 : 0), -2,
+             "selftest_scatter: the sorted density scatter of this build runs on %s tiles", rdrf_flat_density() ? "flat" : "ray");
+  const int set_mask = k.nsets == 2 ? t->set_mask : 1;
+  RDRF_CHECK(set_mask >= 1 && set_mask <= 3, -1, "selftest_scatter: set mask must be 1, 2 or 3 (got %d)", t->set_mask);
+  for (int set = 0; set < k.nsets; ++set)
+    RDRF_CHECK(scatter_vm_ok(t->vm[set], t->gvm[set], 16 * k.c0q / 4, 4 * k.c1q), -1,
+               "selftest_scatter: factor set %d: component counts, one grid, W-fastest or H-fastest planes matching the gradient "
+               "buffers, 16-byte aligned", set);
+  RDRF_CHECK(k.nsets == 1 || vm_same_grid(t->vm[0], t->vm[1]), -1, "selftest_scatter: the two factor sets differ in size");
+  RDRF_CHECK(t->coords != nullptr, -1, "selftest_scatter: bad arguments (null coordinates)");
+  RDRF_CHECK(k.list || t->valid != nullptr, -1, "selftest_scatter: bad arguments (null valid)");
+  RDRF_CHECK(!k.list || (t->list != nullptr && t->count != nullptr), -1, "selftest_scatter: kind %d takes a list and a device count", kind);
+  RDRF_CHECK(!(sorted ? k.dxw_sorted : k.dxw_ray) || t->dxw != nullptr, -1, "selftest_scatter: bad arguments (null dxw)");
+  RDRF_CHECK(!k.g_xyz || t->g_xyz != nullptr, -1, "selftest_scatter: bad arguments (null g_xyz)");
+  const size_t tpr = ((size_t)S + 31) / 32, t3 = (ns + 31) / 32, ntiles = k.list || flat ? t3 : (size_t)N * tpr;
+  const bool needs_rows = !sorted || k.live_row[0] >= 0;
+  if (needs_rows) {
+    RDRF_CHECK(t->rows != nullptr && ((uintptr_t)t->rows & 15) == 0, -1, "selftest_scatter: the rows must be 16-byte aligned");
+    RDRF_CHECK(t->rows_floats >= ntiles * (size_t)k.stride * 32, -3, "selftest_scatter: rows too small (%zu < %zu floats)",
+               t->rows_floats, ntiles * (size_t)k.stride * 32);
+  }
+  if (sorted) {
+    RDRF_CHECK(t->recs != nullptr && ((uintptr_t)t->recs & 15) == 0, -1, "selftest_scatter: the records must be 16-byte aligned");
+    RDRF_CHECK(t->recs_floats >= ns * (size_t)k.rec_floats, -3, "selftest_scatter: records too small (%zu < %zu floats)",
+               t->recs_floats, ns * (size_t)k.rec_floats);
+    RDRF_CHECK(t->ws != nullptr && ((uintptr_t)t->ws & 255) == 0, -1, "selftest_scatter: the workspace must be 256-byte aligned");
+    RDRF_CHECK(t->ws_bytes >= rdrf_selftest_scatter_workspace_bytes(N, S), -3, "selftest_scatter: workspace too small (%zu < %zu)",
+               t->ws_bytes, rdrf_selftest_scatter_workspace_bytes(N, S));
+  }
+  if (k.list) {   // the kernels index the batch with the list entries: they must lie inside it
+    int c = -1;
+    RDRF_HIP(hipMemcpyAsync(&c, t->count, sizeof(int), hipMemcpyDeviceToHost, stream));
+    RDRF_HIP(hipStreamSynchronize(stream));
+    RDRF_CHECK(c >= 0 && (size_t)c <= ns, -1, "selftest_scatter: count %d does not fit %zu samples", c, ns);
+    std::vector<int> host((size_t)c);
+    if (c > 0) {
+      RDRF_HIP(hipMemcpyAsync(host.data(), t->list, (size_t)c * sizeof(int), hipMemcpyDeviceToHost, stream));
+      RDRF_HIP(hipStreamSynchronize(stream));
+    }
+    for (int i = 0; i < c; ++i)
+      RDRF_CHECK(host[i] >= 0 && (size_t)host[i] < ns, -1, "selftest_scatter: list[%d] = %d is outside the batch", i, host[i]);
+  }
+  if (!sorted) {
+    ScatterArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.valid = t->valid; sa.N = N; sa.S = S;
+    if (k.xw) sa.xw = t->coords;
+    else {
+      sa.xyz = t->coords;
+      for (int i = 0; i < 3; ++i) { sa.box.lo[i] = t->box_lo[i]; sa.box.inv[i] = t->box_inv[i]; sa.box.hi[i] = t->box_lo[i] + 2.0f / t->box_inv[i]; }
+    }
+    sa.nsets = 0;   // live sets only, as rdrf_dynamic_bwd fills them
+    for (int set = 0; set < k.nsets; ++set)
+      if ((set_mask >> set) & 1) { sa.vm[sa.nsets] = t->vm[set]; sa.gvm[sa.nsets] = t->gvm[set]; sa.row0[sa.nsets] = k.row0[set]; ++sa.nsets; }
+    sa.rows = t->rows; sa.stride = k.stride; sa.bcast = k.bcast; sa.flat = flat;
+    if (k.list) { sa.list = t->list; sa.count = t->count; }
+    if (k.dxw_ray) { sa.dxw = t->dxw; sa.dxw_accumulate = k.dxw_ray == 2; }
+    if (k.g_xyz) sa.g_xyz = t->g_xyz;
+    return launch_scatter("selftest_scatter", k.kern, sa, (long)ntiles, stream);
+  }
+  WsCarver c(t->ws, t->ws_bytes);
+  BwdWs b;
+  memset(&b, 0, sizeof(b));
+  b.keys_in = c.take<unsigned>(3 * ns);
+  b.keys_out = c.take<unsigned>(3 * ns);
+  b.order = c.take<unsigned>(3 * ns);
+  b.counts = c.take<int>(64);
+  b.sort_tmp_bytes = rdrf_sort_temp_bytes((unsigned)(3 * ns), 32);
+  b.sort_tmp = c.take<char>(b.sort_tmp_bytes);
+  RDRF_CHECK(c.ok(), -3, "selftest_scatter: workspace too small");
+  b.dxw = t->dxw;
+  b.grows1 = const_cast<float*>(t->rows);
+  b.dfs = b.dfa = const_cast<float*>(t->recs);
+  BwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.N = N; a.S = S; a.valid = t->valid;
+  a.sp.xw = const_cast<float*>(t->coords);
+  a.sp.list = const_cast<int*>(t->list);
+  a.sp.hdr = reinterpret_cast<SavedHdr*>(const_cast<int*>(t->count));   // only &hdr->count is formed: SavedHdr begins with it
+  static_assert(offsetof(SavedHdr, count) == 0, "the device count is the first member of SavedHdr");
+  RdrfDynamicParams P, G;
+  memset(&P, 0, sizeof(P));
+  memset(&G, 0, sizeof(G));
+  if (kind == RDRF_SCK_DYN_DENSITY) { P.density = t->vm[0]; P.blending = t->vm[1]; G.density = t->gvm[0]; G.blending = t->gvm[1]; }
+  else { P.app = t->vm[0]; G.app = t->gvm[0]; }
+  const int old = scatter_mode_swap(mode);   // launch_scatter_tiled reads the process-wide mode (_SORTED_PLAIN: no windows)
+  const int rc = kind == RDRF_SCK_DYN_DENSITY ? scatter_dyn_density_sorted(a, b, &P, &G, set_mask, stream)
+                                              : scatter_dyn_app_sorted(a, b, &P, &G, stream);
+  scatter_mode_swap(old);
+  if (rc) return rc;
+  if (t->keys_out) RDRF_HIP(hipMemcpyAsync(t->keys_out, b.keys_in, 3 * ns * 4, hipMemcpyDeviceToDevice, stream));   // (the sort leaves them intact)
+  if (t->keys_sorted_out) RDRF_HIP(hipMemcpyAsync(t->keys_sorted_out, b.keys_out, 3 * ns * 4, hipMemcpyDeviceToDevice, stream));
+  if (t->order_out) RDRF_HIP(hipMemcpyAsync(t->order_out, b.order, 3 * ns * 4, hipMemcpyDeviceToDevice, stream));
+  if (t->counts_out) RDRF_HIP(hipMemcpyAsync(t->counts_out, b.counts, 3 * sizeof(int), hipMemcpyDeviceToDevice, stream));
+  return 0;
+}
+
+// A kind's layouts in resolved form (host memory, ints), so that a reference needs none of the sv:: constants:
+// [0] ints used, [1] C0Q, [2] C1Q, [3] stride levels, [4] factor sets, [5] rows per tile, [6] [7] first d(feature) row of set 0 / 1
+// (-1: no such set), [8] 1 = every component's gradient is row 0, [9] floats per record (0: no sorted form), [10] floats per set
+// inside a record, [11] [12] the rows the key kernel reads for liveness (-1: none), [13] takes list + count, [14] coordinates are
+// normalised (xw) / xyz + box, [15] [16] coordinate gradients of the ray / sorted form (0 none, 1 written, 2 added),
+// [17] g_xyz += dw * inv, [18] flat tiles allowed, [19] bits of the cell part of a key and [20..22] key row length W + 3 per plane
+// (0 without `grid`), [23] quads; per quad: row relative to the set's first row, level, plane, first component, float offset inside
+// the set's part of a record (-1: none).  grid: nullable {W, H} x 3 of the level-0 planes.
+extern "C" int rdrf_selftest_scatter_describe(int kind, const int* grid, int* out, int cap) {
+  ScatterKindInfo k;
+  RDRF_CHECK(scatter_kind_info(kind, k), -1, "selftest_scatter_describe: unknown kind %d", kind);
+  const int qpl = k.c0q + 2 * k.c1q, nq = k.nlv * qpl, need = 24 + 5 * nq;
+  RDRF_CHECK(out != nullptr && cap >= need, -3, "selftest_scatter_describe: description buffer too small (%d < %d ints)", out ? cap : 0, need);
+  int n = 0;
+  out[n++] = need; out[n++] = k.c0q; out[n++] = k.c1q; out[n++] = k.nlv; out[n++] = k.nsets; out[n++] = k.stride;
+  out[n++] = k.row0[0]; out[n++] = k.row0[1]; out[n++] = k.bcast; out[n++] = k.rec_floats; out[n++] = k.set_floats;
+  out[n++] = k.live_row[0]; out[n++] = k.live_row[1]; out[n++] = k.list; out[n++] = k.xw; out[n++] = k.dxw_ray; out[n++] = k.dxw_sorted;
+  out[n++] = k.g_xyz; out[n++] = k.flat;
+  if (grid) {
+    const int W[3] = {grid[0], grid[2], grid[4]}, H[3] = {grid[1], grid[3], grid[5]};
+    out[n++] = sorted_key_bits(W, H);
+    for (int p = 0; p < 3; ++p) out[n++] = W[p] + 3;
+  } else {
+    for (int i = 0; i < 4; ++i) out[n++] = 0;
+  }
+  out[n++] = nq;
+  for (int g = 0; g < nq; ++g) {
+    const int lv = g / qpl, w = g - lv * qpl;
+    const int pi = w < k.c0q ? 0 : (w < k.c0q + k.c1q ? 1 : 2), q = w - (pi == 0 ? 0 : (pi == 1 ? k.c0q : k.c0q + k.c1q));
+    out[n++] = k.bcast ? 0 : 4 * g; out[n++] = lv; out[n++] = pi; out[n++] = 4 * q;
+    out[n++] = k.rec_floats == DFS_FLOATS ? dfs_off(g) : (k.rec_floats == DFA_FLOATS ? dfa_off(g) : -1);
+  }
+  return n;
+}
+
+// the launch decisions of the most recent scatter: [0] ints used, [1] form (0 ray tiles, 1 sorted passes), [2] 1 = one launch per
+// factor set, [3] launches; per launch: accumulator element bytes (8 / 4 / 0), threads, workgroups, tiled (1 taken, 0 refused,
+// -2 switched off,
+// -1 not tried), window width, wave steps per slice
+extern "C" int rdrf_selftest_scatter_last(int* out, int cap) {
+  const ScatterRecord& r = scatter_last_record();
+  const int need = 4 + 6 * r.n;
+  RDRF_CHECK(out != nullptr && cap >= need, -3, "selftest_scatter_last: buffer too small (%d < %d ints)", out ? cap : 0, need);
+  int n = 0;
+  out[n++] = need; out[n++] = r.form; out[n++] = r.split; out[n++] = r.n;
+  for (int i = 0; i < r.n; ++i) {
+    out[n++] = r.l[i].elem_bytes; out[n++] = r.l[i].threads; out[n++] = r.l[i].workgroups; out[n++] = r.l[i].tiled;
+    out[n++] = r.l[i].tw; out[n++] = r.l[i].slice_steps;
+  }
+  return n;
 }

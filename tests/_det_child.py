@@ -4,6 +4,8 @@ in a process of their own with RDRF_DETERMINISTIC=1):
     python tests/_det_child.py dw OUT       tests/test_gpu_dw_primitives.py: the exact-integer cases of _DET_SIZES against
                                             librodynrf_det.so, the gradient buffer bound to a fixed-point shadow as the fields
                                             bind theirs; writes the number of cases that ran to OUT
+    python tests/_det_child.py scatter OUT  tests/test_gpu_scatter_primitives.py: det_cases(), every call's flat output buffer bound
+                                            to a shadow; the planes and lines must not move before the fold
     python tests/_det_child.py poison OUT   tests/test_gpu_poisoned_scratch.py: every case, bit for bit per tensor"""
 import ctypes as C
 import importlib
@@ -49,6 +51,37 @@ def dw(L):
     return n
 
 
+class _ScatterBinder:
+    """Dev.call hooks of tests/test_gpu_scatter_primitives.py: bind the flat buffer before the call, fold the shadow after it"""
+
+    def __init__(self, L):
+        self.L = L
+
+    def bind(self, dev):
+        L = self.L
+        self.slot = 1 if dev.d["xw"] else 0          # dynamic / static field
+        self.shadow = torch.zeros(dev.total, dtype=torch.int64, device="cuda")
+        self.before = dev.flat.clone()
+        L.check(L.lib.rdrf_det_bind(self.slot, L.ptr(dev.flat), C.c_size_t(dev.total), L.ptr(self.shadow), L.stream_of(dev.flat)), "rdrf_det_bind")
+        # the other slot may still name the buffers of an earlier case, freed since: bind it to an empty range
+        L.check(L.lib.rdrf_det_bind(1 - self.slot, L.ptr(dev.flat), C.c_size_t(0), L.ptr(self.shadow), L.stream_of(dev.flat)), "rdrf_det_bind")
+
+    def finish(self, dev):
+        L = self.L
+        for k, sl in dev.slices.items():             # (dxw and g_xyz are plain stores of the sample's owner: no additions)
+            if k[0] in ("plane", "line"):
+                assert torch.equal(dev.flat[sl], self.before[sl]), f"{k}: an addition missed the shadow"
+        assert bool((self.shadow != 0).any()) or not bool((dev.flat != self.before).any())
+        L.check(L.lib.rdrf_det_finish(self.slot, L.stream_of(dev.flat)), "rdrf_det_finish")
+        torch.cuda.synchronize()
+
+
+def scatter(L):
+    import test_gpu_scatter_primitives as T
+    T.DET = _ScatterBinder(L)
+    return T.det_cases()
+
+
 def poison(L):
     import test_gpu_poisoned_scratch as T
     for case in T.CASES:
@@ -66,6 +99,6 @@ def poison(L):
 if __name__ == "__main__":
     L = importlib.import_module("robust-dynrf_amd._lib")
     assert L.DETERMINISTIC and L.lib.rdrf_deterministic() == 1
-    n = {"dw": dw, "poison": poison}[sys.argv[1]](L)
+    n = {"dw": dw, "scatter": scatter, "poison": poison}[sys.argv[1]](L)
     with open(sys.argv[2], "w") as f:
         f.write(str(n))
