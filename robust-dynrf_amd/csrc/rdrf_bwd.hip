@@ -1,5 +1,6 @@
 // rdrf_bwd.hip -- backward of the two fields and of the scene-flow MLP for gfx950: the backward-DATA kernels and every
-// backward entry point (ray path, feature mode, scene flow), the backward pack jobs and the workspace carving.
+// backward entry point (ray path, feature mode, scene flow), the backward pack jobs and the workspace carving.  The entry points
+// choose between the two-kernel forms here and the kernels that form the weight gradients themselves (rdrf_bwd_fused.hip).
 //
 // Structure per phase (appearance / density / scene flow):
 //   1. the training-mode forward saved the per-tile activations as [tile][row][32 samples]
@@ -12,7 +13,7 @@
 //   3. the scatter kernels (rdrf_scatter.hip) run the VM gather backward from those rows: atomic scatter
 //      into the channel-last planes / lines + coordinate gradients (per-quad device functions: rdrf_bwd_dev.hpp);
 //   4. k_dw3 (rdrf_dw.hip) forms dW = sum_samples dz (x) in on the MFMA from the dz rows and the saved rows.
-// The entry points call 3 and 4 through the host interface of rdrf_bwd_host.hpp.  The ray-generation backward is in
+// The entry points call 3, 4 and the fused kernels through the host interface of rdrf_bwd_host.hpp.  The ray-generation backward is in
 // rdrf_misc.hip beside its forward, the deterministic build's bind / finish in rdrf_det.hip.
 // References: autograd of /root/reference/models/tensorBase.py:704-850, models/tensoRF.py:118-196,
 // 446-462, 521-811 (grid_sample backward per SURVEY.md Appendix A).
@@ -27,7 +28,7 @@ RDRF_DET_UNIT(bwd)
 // d(X0)/d(xn): X0 = [xn, t | (sin q, cos q) pairs], q_j = xn[j/10] * 2^(j%10); returns this lane
 // half's partial (combine with __shfl_xor 32)
 // (no contraction in here: left to hipcc, which products of `a cv - b sv` fuse depends on the kernel around the call, and
-// k_dyn_warp_bwd_dw has to give the bits of k_dyn_density_bwd<1>)
+// the fused warp kernel of rdrf_bwd_fused.hip, through its x0_bwd_flat, has to give the bits of k_dyn_density_bwd<1>)
 RDRF_D void x0_bwd(const float (&X0)[32], const float (&dX0)[32], int h, float& d0, float& d1,
                    float& d2) {
 #pragma clang fp contract(off)
@@ -52,34 +53,6 @@ RDRF_D void x0_bwd(const float (&X0)[32], const float (&dX0)[32], int h, float& 
 
 RDRF_D float act_grad(float f, int act, float shift) {
   return act == RDRF_ACT_RELU ? (f > 0.0f ? 1.0f : 0.0f) : sigmoidf_(f + shift);
-}
-
-// backward of a small output layer kept on the VALU (NO <= 6 outputs): dz[kk] = relu'(H[kk]) * sum_o W[o][kk] dzo[o]
-// for this lane half's KK inputs.  ws = [NO][2][KK] in LDS, read as 16-byte quads (element-wise `lds[...]` reads
-// compiled to one ds_read_b32 + lgkmcnt(0) wait per weight).
-template <int KK, int NO>
-RDRF_D void small_layer_bwd(float (&dz)[KK], const float (&H)[KK], const float* __restrict__ ws, int h,
-                            const float (&dzo)[NO]) {
-#pragma unroll
-  for (int q = 0; q < KK / 4; ++q) {
-    f32x4 d = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int o = 0; o < NO; ++o) {
-      const f32x4 wv = *reinterpret_cast<const f32x4*>(ws + o * 2 * KK + h * KK + 4 * q);
-      d.x = fmaf(wv.x, dzo[o], d.x); d.y = fmaf(wv.y, dzo[o], d.y);
-      d.z = fmaf(wv.z, dzo[o], d.z); d.w = fmaf(wv.w, dzo[o], d.w);
-    }
-    dz[4 * q + 0] = H[4 * q + 0] > 0.f ? d.x : 0.f; dz[4 * q + 1] = H[4 * q + 1] > 0.f ? d.y : 0.f;
-    dz[4 * q + 2] = H[4 * q + 2] > 0.f ? d.z : 0.f; dz[4 * q + 3] = H[4 * q + 3] > 0.f ? d.w : 0.f;
-  }
-}
-
-template <int NB>
-RDRF_D void acc_zero(f32x16 (&acc)[NB]) {
-#pragma unroll
-  for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -457,24 +430,6 @@ __global__ __launch_bounds__(64) void k_static_density_bwd(BwdArgs a, StaticW w,
 //   PHASE 1 (warp) : coordinate gradients (appearance + density + blending scatter) ->
 //                    warp MLP backward, positional-encoding backward, g_xyz, d(tout)
 // ------------------------------------------------------------------------------------------------
-// Reduce-scatter over the 32 lanes of a half-wave: on return lane s holds the sum over the half's 32 lanes of p[s]
-// (five butterfly stages: 31 lane exchanges + 31 adds).  Used for the weight gradients of the 3- and 1-row layers of the
-// density phase (layer5, density / blending layer2): dW[e] = sum over the tile's samples of dz(sample) * in_e(sample),
-// with dz a per-lane scalar and in_e the 32 slots the lane already holds -- as MFMA products in k_dw2 these were 6 of
-// the 40 per tile, each 27/32 empty.  ALL lanes of the wave must call.
-RDRF_D float reduce_scatter32(const float (&p)[32], int s) {
-  const bool b4 = s & 16, b3 = s & 8, b2 = s & 4, b1 = s & 2, b0 = s & 1;
-  float q[16], r[8], t[4], u[2];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) q[i] = (b4 ? p[i + 16] : p[i]) + __shfl_xor(b4 ? p[i] : p[i + 16], 16, 64);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) r[i] = (b3 ? q[i + 8] : q[i]) + __shfl_xor(b3 ? q[i] : q[i + 8], 8, 64);
-#pragma unroll
-  for (int i = 0; i < 4; ++i) t[i] = (b2 ? r[i + 4] : r[i]) + __shfl_xor(b2 ? r[i] : r[i + 4], 4, 64);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) u[i] = (b1 ? t[i + 2] : t[i]) + __shfl_xor(b1 ? t[i] : t[i + 2], 2, 64);
-  return (b0 ? u[1] : u[0]) + __shfl_xor(b0 ? u[0] : u[1], 1, 64);
-}
 
 // The scan half of the heads' backward on the flat-tile path (rdrf_flat_density): per ray, the transmittance carries at
 // the tile starts (pre-pass) and the reverse suffix sweep of d(weight) -> d(alpha); per sample the total
@@ -1068,583 +1023,6 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_scene_flow_bwd(int N, int S,
 }
 
 // ------------------------------------------------------------------------------------------------
-// scene flow backward with the weight gradients formed in the kernel (k_scene_flow_bwd_dw).  k_scene_flow_bwd above writes
-// its 224 dz rows per tile for the dw_sf launch of k_dw3, which reads them back together with the 256 activation rows the
-// backward-data kernel had just loaded.  Here the wave that owns a tile keeps going: the data gradient runs exactly as
-// above (same calls on the same values: g_pts keeps its bits), and after each layer the wave writes that layer's dz into
-// its OWN LDS stage in the saved-row layout [row][32 samples] (8 KB, chunk-swizzled), reads it back as the A operand of
-// the fp32 MFMA -- lane (li, h): row li, samples 16 h .. 16 h + 15, as k_dw3 reads its stage -- and multiplies it with the
-// layer's input rows, read in the same form from the saved rows (64 contiguous bytes of a row: L2 hits, the wave has just
-// loaded those rows as relu masks, or is about to).  The 12 products (32 x 32 blocks) of the three 64-row layers
-// accumulate in registers of the wave for the whole launch: 192 accumulator registers, hence FOUR waves per workgroup
-// (512 registers per lane), no workgroup barrier in the tile loop, no round of tiles that could be partly empty.  The
-// 6-output layer stays off the matrix pipe: as two 32 x 32 products 26 of its 32 rows would be empty (2048 MFMA cycles per
-// tile); the lane that holds row li of the H4 blocks for the 16 samples of its half reads the six dz6 rows of those samples
-// as LDS broadcasts and keeps 12 sums (192 FMAs per tile).  At the end the waves of a workgroup add their accumulators
-// through LDS in wave order (a fixed order: the deterministic build stays bit-reproducible) and the workgroup flushes once
-// through grad_add, columns mapped as dw_launch maps them.
-// From the first stage write on, a tile's pass is ONE basic block (PTS is a template argument, both lane halves store the
-// dz6 rows, the masked update of g_pts is a buffer access whose offset is out of range in the lanes that do not take part):
-// with a branch in it, hipcc sinks every product -- pure arithmetic that only the next pass reads -- behind the branch to
-// the end of the pass and keeps the operands of all of them alive until there (100 to 140 spilled registers).
-// Row contract (head of rdrf_dw.hip): a lane past N * S has dz6 = 0, so every dz it stages is 0 (0 x finite = 0); tiles
-// past ceil(N * S / 32) are never read; every stage row that is read was written by the same wave for the same tile.
-// ------------------------------------------------------------------------------------------------
-#define SFD_WAVES 4
-namespace sfd {
-constexpr int ST_DZ = 0, ST_DZ6 = 64 * 32, ST_SIZE = 72 * 32;   // a wave's stage: one layer's dz (64 rows) + the dz6 rows
-constexpr int NPROD = 12, NDZ = 6;                               // MFMA products / their dz blocks (dz4 x 2 | dz2 x 2 | dz0 x 2)
-constexpr int NSM = 18;                                          // 6-output layer: 6 x 2 weight sums, 6 bias sums per lane
-constexpr int LDS = pkb::SF_SIZE + SFD_WAVES * ST_SIZE;
-constexpr int RED = NPROD * 1024 + (NDZ + NSM) * 64;             // the cross-wave sum, over the image and the stages
-static_assert(RED <= LDS && LDS * 4 <= 160 * 1024, "the cross-wave sum reuses the kernel's LDS");
-}  // namespace sfd
-struct SfGrads {
-  float* w[4];   // sfw[0..3]
-  float* b[4];   // sfb[0..3]
-};
-// float offset of 16-byte chunk `chunk` (4 samples) of stage row `row`: the chunk index is XORed with bits of the row so
-// that the 16 lanes of a ds_read_b128 group (consecutive rows, one chunk) cover all 64 banks
-RDRF_D int sfd_pos(int row, int chunk) { return row * 32 + ((chunk ^ ((row >> 1) & 7)) << 2); }
-RDRF_D void sfd_wave_sync() {   // LDS traffic of ONE wave: in order in hardware; this orders it for the compiler
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  __builtin_amdgcn_sched_barrier(0);
-}
-// Lane (s, h) writes slot kk to row elem_of(kk, h) = 8 (kk >> 2) + 4 h + (kk & 3), whose swizzle term ((row >> 1) & 7) is
-// (h << 1) ^ C with C = 4 ((kk >> 2) & 1) + ((kk & 3) >> 1): FOUR lane offsets (SfdPos::w) + a constant per slot, and the reads of
-// row 32 a + li are four more (SfdPos::r) + 1024 a.  Spelled out because hipcc, given sfd_pos per slot, keeps one address
-// register per slot (32) alive across the tile loop.
-struct SfdPos {
-  int w[4], r[4];
-};
-RDRF_D SfdPos sfd_lane_pos(int s, int h) {
-  SfdPos p;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    p.w[c] = h * 128 + ((((s >> 2) ^ (h << 1)) ^ ((c >> 1) * 4 + (c & 1))) << 2) + (s & 3);
-    p.r[c] = sfd_pos(s, 4 * h + c);
-  }
-  return p;
-}
-RDRF_D void sfd_stage(float* __restrict__ st, const float (&v)[32], const SfdPos& p) {
-#pragma unroll
-  for (int kk = 0; kk < 32; ++kk) st[p.w[(((kk >> 2) & 1) << 1) | ((kk & 3) >> 1)] + (8 * (kk >> 2) + (kk & 3)) * 32] = v[kk];
-}
-RDRF_D void sfd_read(f32x4 (&o)[4], const float* __restrict__ st, int blk, const SfdPos& p) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) o[q] = *(const f32x4*)(st + p.r[q] + 1024 * blk);
-}
-RDRF_D void sfd_load(f32x4 (&o)[4], const float* __restrict__ tile_base, int row, int h) {
-  const float* p = tile_base + (size_t)row * 32 + 16 * h;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) o[q] = *(const f32x4*)(p + 4 * q);
-}
-RDRF_D float sfd_sum(const f32x4 (&a)[4]) {
-  float t = 0.f;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) t += a[q].x + a[q].y + a[q].z + a[q].w;
-  return t;
-}
-RDRF_D void sfd_prod(f32x16& acc, const f32x4 (&a)[4], const f32x4 (&b)[4]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].x, b[q].x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].y, b[q].y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].z, b[q].z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[q].w, b[q].w, acc, 0, 0, 0);
-  }
-}
-// the products of one layer: NA dz blocks (stage rows 32 a + li of lane (li, h)) x the two input blocks b0 | b1 -> accW[P0 ..], bsum[A0 ..]
-template <int NA, int P0, int A0>
-RDRF_D void sfd_layer(f32x16 (&accW)[sfd::NPROD], float (&bsum)[sfd::NDZ], const float* __restrict__ st, const f32x4 (&b0)[4],
-                      const f32x4 (&b1)[4], const SfdPos& p) {
-#pragma unroll
-  for (int a = 0; a < NA; ++a) {
-    f32x4 av[4];
-    sfd_read(av, st, a, p);
-    bsum[A0 + a] += sfd_sum(av);
-    sfd_prod(accW[P0 + 2 * a], av, b0);
-    sfd_prod(accW[P0 + 2 * a + 1], av, b1);
-    // (scheduling fences here and in the 6-output layer below: left free, hipcc gathers the LDS reads of every block in front
-    // of the first product -- 96 live registers for the dz6 rows alone -- and spills)
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// sf_x_bwd without a branch (see the head comment): every lane runs the pair path of every octet -- where sf_x_bwd skips it
-// (h == 0 in octet 0: pair -2 / -1; pairs 12 ..) nothing is selected and 0.f is added -- and the lanes h == 0 add dX[0..2] first,
-// as there.  The same values in the same order, plus additions of 0.f.
-RDRF_D void sf_x_bwd_flat(const float (&X)[20], const float (&dX)[20], int h, float& d0, float& d1, float& d2) {
-  d0 += h == 0 ? dX[0] : 0.f; d1 += h == 0 ? dX[1] : 0.f; d2 += h == 0 ? dX[2] : 0.f;
-#pragma unroll
-  for (int o = 0; o < 5; ++o) {
-    const int k = 2 * o + h - 1;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int pr = 2 * k + p;
-      const int d = (pr >= 0 && pr < 12) ? pr >> 2 : -1, f = pr & 3;
-      const float dq = ldexpf(dX[o * 4 + 2 * p] * X[o * 4 + 2 * p + 1] - dX[o * 4 + 2 * p + 1] * X[o * 4 + 2 * p], f);
-      d0 += d == 0 ? dq : 0.f; d1 += d == 1 ? dq : 0.f; d2 += d == 2 ? dq : 0.f;
-    }
-  }
-}
-
-template <bool PTS>   // PTS: the caller takes the point gradient (g_pts); without it the first layer's data product is skipped
-__global__ __launch_bounds__(64 * SFD_WAVES) void k_scene_flow_bwd_dw(int N, int S, Box box,
-                                                        const float* __restrict__ pkg,
-                                                        const float* __restrict__ act_rows,
-                                                        const float* __restrict__ g_f,
-                                                        const float* __restrict__ g_b,
-                                                        SfGrads G,
-                                                        float* __restrict__ g_pts) {
-  __shared__ __attribute__((aligned(16))) float lds[sfd::LDS];
-  const int lane = threadIdx.x & 63, h = lane >> 5, s = lane & 31;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = blockDim.x >> 6;
-  float* st = lds + pkb::SF_SIZE + wave * sfd::ST_SIZE;
-  lds_fill(lds, pkg + pkb::REG_SF, pkb::SF_SIZE);
-  const int total = N * S;
-  const int ntiles = (total + 31) >> 5;
-  const SfdPos pos = sfd_lane_pos(s, h);
-  f32x16 accW[sfd::NPROD];
-  float bsum[sfd::NDZ], sm[sfd::NSM];   // sm: dW of sfw[3], [o][input block] for input li of the block; then db of sfb[3]
-  acc_zero<sfd::NPROD>(accW);
-#pragma unroll
-  for (int a = 0; a < sfd::NDZ; ++a) bsum[a] = 0.f;
-#pragma unroll
-  for (int a = 0; a < sfd::NSM; ++a) sm[a] = 0.f;
-  for (int tile = blockIdx.x * nwaves + wave; tile < ntiles; tile += gridDim.x * nwaves) {
-    const int li = tile * 32 + s;
-    const bool act = li < total;
-    const int idx = act ? li : 0;
-    const float* svb = act_rows + (size_t)tile * sv::SF_ROWS * 32;
-    float dz6[6];
-#pragma unroll
-    for (int o = 0; o < 6; ++o) {
-      const float* gsrc = o < 3 ? g_f : g_b;
-      dz6[o] = (act && gsrc) ? gsrc[(size_t)idx * 3 + (o % 3)] : 0.f;
-    }
-    float dz[32], Hh[32];
-    f32x4 b0[4], b1[4];
-    load_rows<32>(svb, sv::SF_H4, Hh, s, h);
-    sfd_load(b0, svb, sv::SF_H4 + s, h);
-    sfd_load(b1, svb, sv::SF_H4 + 32 + s, h);
-    small_layer_bwd<32, 6>(dz, Hh, lds + pkb::SF_W6, h, dz6);
-    sfd_wave_sync();   // the previous tile's reads of the stage are done
-#pragma unroll
-    for (int o = 0; o < 6; ++o) st[sfd::ST_DZ6 + o * 32 + s] = dz6[o];   // (both halves, the same value; read as broadcasts)
-    sfd_stage(st + sfd::ST_DZ, dz, pos);
-    sfd_wave_sync();
-#pragma unroll
-    for (int o = 0; o < 6; ++o) {   // sfw[3]: dz6 x H4
-      f32x4 d[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) d[q] = *(const f32x4*)(st + sfd::ST_DZ6 + o * 32 + 16 * h + 4 * q);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        sm[2 * o] = fmaf(d[q].x, b0[q].x, sm[2 * o]); sm[2 * o + 1] = fmaf(d[q].x, b1[q].x, sm[2 * o + 1]);
-        sm[2 * o] = fmaf(d[q].y, b0[q].y, sm[2 * o]); sm[2 * o + 1] = fmaf(d[q].y, b1[q].y, sm[2 * o + 1]);
-        sm[2 * o] = fmaf(d[q].z, b0[q].z, sm[2 * o]); sm[2 * o + 1] = fmaf(d[q].z, b1[q].z, sm[2 * o + 1]);
-        sm[2 * o] = fmaf(d[q].w, b0[q].w, sm[2 * o]); sm[2 * o + 1] = fmaf(d[q].w, b1[q].w, sm[2 * o + 1]);
-      }
-      sm[12 + o] += sfd_sum(d);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    sfd_load(b0, svb, sv::SF_H2 + s, h);
-    sfd_load(b1, svb, sv::SF_H2 + 32 + s, h);
-    f32x16 acc[2];
-    acc_zero<2>(acc);
-    mfma_seg<2, 32>(acc, dz, lds + pkb::SF_W4T, lane);
-    load_rows<32>(svb, sv::SF_H2, Hh, s, h);
-    sfd_layer<2, 0, 0>(accW, bsum, st + sfd::ST_DZ, b0, b1, pos);    // sfw[2]: dz4 x H2
-#pragma unroll
-    for (int kk = 0; kk < 32; ++kk) dz[kk] = Hh[kk] > 0.f ? acc[kk >> 4][kk & 15] : 0.f;
-    sfd_wave_sync();
-    sfd_stage(st + sfd::ST_DZ, dz, pos);
-    sfd_wave_sync();
-    sfd_load(b0, svb, sv::SF_H0 + s, h);
-    sfd_load(b1, svb, sv::SF_H0 + 32 + s, h);
-    acc_zero<2>(acc);
-    mfma_seg<2, 32>(acc, dz, lds + pkb::SF_W2T, lane);
-    load_rows<32>(svb, sv::SF_H0, Hh, s, h);
-    sfd_layer<2, 4, 2>(accW, bsum, st + sfd::ST_DZ, b0, b1, pos);    // sfw[1]: dz2 x H0
-#pragma unroll
-    for (int kk = 0; kk < 32; ++kk) dz[kk] = Hh[kk] > 0.f ? acc[kk >> 4][kk & 15] : 0.f;
-    sfd_wave_sync();
-    sfd_stage(st + sfd::ST_DZ, dz, pos);
-    sfd_wave_sync();
-    sfd_load(b0, svb, sv::SF_X + s, h);
-    sfd_load(b1, svb, sv::SF_X + 32 + s, h);
-    if constexpr (PTS) {
-      acc_zero<2>(acc);
-      mfma_seg<2, 32>(acc, dz, lds + pkb::SF_W0T, lane);
-    }
-    sfd_layer<2, 8, 4>(accW, bsum, st + sfd::ST_DZ, b0, b1, pos);   // sfw[0]: dz0 x X
-    if constexpr (PTS) {
-      float X[20], dX[20];
-      load_rows<20>(svb, sv::SF_X, X, s, h);
-#pragma unroll
-      for (int kk = 0; kk < 20; ++kk) dX[kk] = acc[kk >> 4][kk & 15];
-      float d0 = 0.f, d1 = 0.f, d2 = 0.f;
-      sf_x_bwd_flat(X, dX, h, d0, d1, d2);
-      d0 += __shfl_xor(d0, 32, 64); d1 += __shfl_xor(d1, 32, 64); d2 += __shfl_xor(d2, 32, 64);
-      // g_pts[idx][0..2] += d * box.inv in the lanes (act, h == 0): the tile's 384 bytes as a buffer, every other lane out of range
-      const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(g_pts + (size_t)tile * 96), 0, 384, 0x00020000);
-      const int off = (act && h == 0) ? s * 12 : 1 << 20;
-      const float p0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, off, 0, 0));
-      const float p1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, off, 4, 0));
-      const float p2 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, off, 8, 0));
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p0 + d0 * box.inv[0]), rp, off, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p1 + d1 * box.inv[1]), rp, off, 4, 0);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p2 + d2 * box.inv[2]), rp, off, 8, 0);
-    }
-  }
-  // cross-wave sum in wave order, then one flush per workgroup.  C row i = (rr & 3) + 8 (rr >> 2) + 4 h (out neuron of the dz
-  // block), column = li (element of the input block)
-  float* red = lds;
-  for (int w = 0; w < nwaves; ++w) {
-    __syncthreads();   // (the first: every wave is done with the image and its stage)
-    if (wave == w) {
-#pragma unroll
-      for (int p = 0; p < sfd::NPROD; ++p)
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-          float* r = red + p * 1024 + rr * 64 + lane;
-          *r = w == 0 ? accW[p][rr] : *r + accW[p][rr];
-        }
-#pragma unroll
-      for (int a = 0; a < sfd::NDZ; ++a) {
-        float* r = red + sfd::NPROD * 1024 + a * 64 + lane;
-        *r = w == 0 ? bsum[a] : *r + bsum[a];
-      }
-#pragma unroll
-      for (int a = 0; a < sfd::NSM; ++a) {
-        float* r = red + sfd::NPROD * 1024 + (sfd::NDZ + a) * 64 + lane;
-        *r = w == 0 ? sm[a] : *r + sm[a];
-      }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int p = 0; p < sfd::NPROD; ++p) {
-    // product p: layer, dz block of the layer, input block of the layer (the order of sfd_layer above)
-    const int layer = 2 - (p >> 2), bo = (p & 3) >> 1, k = p & 1;
-    const int in_dim = layer == 0 ? 36 : 64;
-    for (int e = threadIdx.x; e < 1024; e += blockDim.x) {
-      const int rr = e >> 6, hh = (e >> 5) & 1, c = e & 31;
-      const int col = seg_imap(layer == 0 ? SEG_SF_X : SEG_IDENT, 32 * k + c, in_dim);
-      const int orow = bo * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * hh;
-      if (col >= 0) grad_add(G.w[layer] + (size_t)orow * in_dim + col, red[p * 1024 + e]);
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < sfd::NDZ; ++a) {
-    const int layer = 2 - (a >> 1), orow = (a & 1) * 32 + (int)threadIdx.x;
-    if (threadIdx.x < 32)
-      grad_add(G.b[layer] + orow, red[sfd::NPROD * 1024 + a * 64 + threadIdx.x] + red[sfd::NPROD * 1024 + a * 64 + 32 + threadIdx.x]);
-  }
-  // the 6-output layer: the two lane halves hold the two halves of a tile's samples; every lane li holds the same bias sums
-  for (int e = threadIdx.x; e < 12 * 32 + 6; e += blockDim.x) {
-    const int a = e < 12 * 32 ? e >> 5 : 12 + (e - 12 * 32), c = e < 12 * 32 ? e & 31 : 0;
-    const float* r = red + sfd::NPROD * 1024 + (sfd::NDZ + a) * 64 + c;
-    if (a < 12) grad_add(G.w[3] + (a >> 1) * 64 + (a & 1) * 32 + c, r[0] + r[32]);
-    else grad_add(G.b[3] + (a - 12), r[0] + r[32]);
-  }
-}
-// launch geometry of k_scene_flow_bwd_dw: whole workgroups of SFD_WAVES waves, a wave per tile, at most a workgroup per CU
-void scene_flow_fused_geometry(long tiles, int* grid, int* waves) {
-  const long blocks = (tiles + SFD_WAVES - 1) / SFD_WAVES;
-  *grid = (int)(blocks < 1 ? 1 : (blocks > 256 ? 256 : blocks));
-  *waves = SFD_WAVES;
-}
-
-// ------------------------------------------------------------------------------------------------
-// warp MLP backward on flat tiles with the weight gradients of its two 64-row layers formed in the kernel
-// (k_dyn_warp_bwd_dw), after k_scene_flow_bwd_dw above.  k_dyn_density_bwd<1, false, true> writes dz4 and dz3 (128 rows per
-// tile) only for k_dw3 to read them back with T and H3.  Here the wave that owns the tile stages dz4, then dz3, in its own 8 KB
-// of LDS (the stage layout, swizzle and fences of the scene-flow kernel), reads them back as the A operand and multiplies them
-// with H3 (dz4: 2 x 2 products) and with X0 | T (dz3: 2 x 3 products) read from the saved rows as 64 bytes per lane; of those
-// rows only T is not loaded by the data path of the same pass.  10 products = 160 accumulator registers for the whole launch,
-// four waves per workgroup, no workgroup barrier in the tile loop; the cross-wave sum and the flush are those of the scene-flow
-// kernel, and the sums of the 3-row layer (sw / sb of k_dyn_density_bwd) ride along in it.
-// The data gradient runs the calls of k_dyn_density_bwd<1, false, true> on the same values: g_xyz, d(tout) and K1G_SM keep
-// their bits.  From the first stage write on the pass is one basic block: x0_bwd_flat has no branch on the lane half, g_xyz and
-// d(tout) go out as buffer accesses whose offset is out of range in the lanes that do not take part (see the head comment of
-// the scene-flow kernel for what a branch there costs).
-// Row contract: a lane past N * S has dd = 0, hence dz4 = dz3 = 0 behind finite activations; tiles past ceil(N * S / 32) are
-// never read; every stage row that is read was written by the same wave for the same tile.
-// ------------------------------------------------------------------------------------------------
-namespace wpd {
-constexpr int WAVES = SFD_WAVES;
-constexpr int ST_SIZE = 64 * 32;                       // a wave's stage: one layer's dz (64 rows)
-constexpr int NPROD = 10, NDZ = 4, NSM = 6;            // products (dz4 x H3: 4 | dz3 x [X0 | T]: 6), dz blocks, sw[3] + sb[3]
-constexpr int LDS = pkb::K1W_SIZE + WAVES * ST_SIZE;
-constexpr int RED = NPROD * 1024 + (NDZ + NSM) * 64;   // the cross-wave sum, over the image and the stages
-static_assert(pkb::K1W_SIZE % 4 == 0 && RED <= LDS && LDS * 4 <= 160 * 1024, "the cross-wave sum reuses the kernel's LDS");
-}  // namespace wpd
-struct WarpGrads {
-  float *l3w, *l3b, *l4w, *l4b;
-};
-// x0_bwd without the branch on the lane half (as sf_x_bwd_flat): the same values in the same order, plus additions of 0.f
-RDRF_D void x0_bwd_flat(const float (&X0)[32], const float (&dX0)[32], int h, float& d0, float& d1, float& d2) {
-#pragma clang fp contract(off)
-  d0 += h == 0 ? dX0[0] : 0.f; d1 += h == 0 ? dX0[1] : 0.f; d2 += h == 0 ? dX0[2] : 0.f;
-#pragma unroll
-  for (int o = 0; o < 8; ++o) {
-    const int k = 2 * o + h - 1;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int j = 2 * k + p;
-      const int d = j >= 0 ? j / 10 : -1, f = j >= 0 ? j - d * 10 : 0;
-      const float sv = X0[o * 4 + 2 * p], cv = X0[o * 4 + 2 * p + 1];
-      const float dq = ldexpf(dX0[o * 4 + 2 * p] * cv - dX0[o * 4 + 2 * p + 1] * sv, f);
-      d0 += d == 0 ? dq : 0.f; d1 += d == 1 ? dq : 0.f; d2 += d == 2 ? dq : 0.f;
-    }
-  }
-}
-
-template <bool GX>   // GX: the caller takes g_xyz
-__global__ __launch_bounds__(64 * wpd::WAVES) void k_dyn_warp_bwd_dw(BwdArgs a, DynG gw, WarpGrads G) {
-  __shared__ __attribute__((aligned(16))) float lds[wpd::LDS];
-  const int lane = threadIdx.x & 63, h = lane >> 5, s = lane & 31;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = blockDim.x >> 6;
-  float* st = lds + pkb::K1W_SIZE + wave * wpd::ST_SIZE;
-  lds_fill(lds, a.pk + pkb::REG_K1W, pkb::K1W_SIZE);
-  const int total = a.N * a.S;
-  const int ntiles = (total + 31) >> 5;
-  const SfdPos pos = sfd_lane_pos(s, h);
-  f32x16 accW[wpd::NPROD];
-  float bsum[wpd::NDZ];
-  float sw[3] = {0.f, 0.f, 0.f}, sb[3] = {0.f, 0.f, 0.f};
-  acc_zero<wpd::NPROD>(accW);
-#pragma unroll
-  for (int i = 0; i < wpd::NDZ; ++i) bsum[i] = 0.f;
-  for (int n = blockIdx.x * nwaves + wave; n < ntiles; n += gridDim.x * nwaves) {
-    const bool act = n * 32 + s < total;
-    const int idx = act ? n * 32 + s : 0;
-    const float* svb = a.sp.act1 + (size_t)n * sv::K1_ROWS * 32;
-    float* gb = a.grows1 + (size_t)n * sv::K1G_ROWS * 32;
-    float dw0 = act ? a.dxw_app[(size_t)idx * 3 + 0] : 0.f, dw1 = act ? a.dxw_app[(size_t)idx * 3 + 1] : 0.f,
-          dw2 = act ? a.dxw_app[(size_t)idx * 3 + 2] : 0.f;
-    float dn0 = act ? a.dxn_app[(size_t)idx * 3 + 0] : 0.f, dn1 = act ? a.dxn_app[(size_t)idx * 3 + 1] : 0.f,
-          dn2 = act ? a.dxn_app[(size_t)idx * 3 + 2] : 0.f;
-    float dd0 = dw0 * a.box.inv[0], dd1 = dw1 * a.box.inv[1], dd2 = dw2 * a.box.inv[2];
-    float gp0 = 0.f, gp1 = 0.f, gp2 = 0.f;
-    if (act && a.g_xyz_prime) {
-      gp0 = a.g_xyz_prime[(size_t)idx * 3 + 0]; gp1 = a.g_xyz_prime[(size_t)idx * 3 + 1];
-      gp2 = a.g_xyz_prime[(size_t)idx * 3 + 2];
-    }
-    dd0 += gp0; dd1 += gp1; dd2 += gp2;
-    if (!act) { dd0 = dd1 = dd2 = 0.f; }
-    if (h == 0) {
-      gb[(size_t)(sv::K1G_SM + 0) * 32 + s] = dd0; gb[(size_t)(sv::K1G_SM + 1) * 32 + s] = dd1;
-      gb[(size_t)(sv::K1G_SM + 2) * 32 + s] = dd2;
-    }
-    float dz4[32];
-    {
-      float H4[32];
-      load_rows<32>(svb, sv::K1_H4, H4, s, h);
-      const float* w5 = lds + pkb::K1W_W5 + h * 32;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const f32x4 wa = *reinterpret_cast<const f32x4*>(w5 + 4 * q);
-        const f32x4 wb = *reinterpret_cast<const f32x4*>(w5 + 64 + 4 * q);
-        const f32x4 wc = *reinterpret_cast<const f32x4*>(w5 + 128 + 4 * q);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float d = wa[c] * dd0 + wb[c] * dd1 + wc[c] * dd2;
-          dz4[4 * q + c] = H4[4 * q + c] > 0.f ? d : 0.f;
-        }
-      }
-      sb[0] += dd0; sb[1] += dd1; sb[2] += dd2;
-#pragma unroll 1
-      for (int o = 0; o < 3; ++o) {   // one row at a time: the three butterflies unrolled together spill
-        const float dd = o == 0 ? dd0 : (o == 1 ? dd1 : dd2);
-        float pw[32];
-#pragma unroll
-        for (int kk = 0; kk < 32; ++kk) pw[kk] = dd * H4[kk];
-        const float r = reduce_scatter32(pw, s);
-        sw[0] += o == 0 ? r : 0.f; sw[1] += o == 1 ? r : 0.f; sw[2] += o == 2 ? r : 0.f;
-      }
-    }
-    // ---- one basic block from here to the end of the pass
-    f32x4 b0[4], b1[4], b2[4];
-    sfd_wave_sync();   // the previous tile's reads of the stage are done
-    sfd_stage(st, dz4, pos);
-    sfd_wave_sync();
-    sfd_load(b0, svb, sv::K1_H3 + s, h);
-    sfd_load(b1, svb, sv::K1_H3 + 32 + s, h);
-    float dz3[32];
-    {
-      f32x16 acc[2];
-      acc_zero<2>(acc);
-#ifdef RDRF_HEADS_BWD_F32
-      mfma_seg<2, 32>(acc, dz4, lds + pkb::K1W_W4T, lane);
-#else
-      mfma_seg_b3<2, 32>(acc, dz4, lds + pkb::K1W_W4T, lane);
-#endif
-      float H3[32];
-      load_rows<32>(svb, sv::K1_H3, H3, s, h);
-#pragma unroll
-      for (int bo = 0; bo < 2; ++bo) {   // layer4: dz4 x H3
-        f32x4 av[4];
-        sfd_read(av, st, bo, pos);
-        bsum[bo] += sfd_sum(av);
-        sfd_prod(accW[2 * bo], av, b0);
-        sfd_prod(accW[2 * bo + 1], av, b1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int kk = 0; kk < 32; ++kk) dz3[kk] = H3[kk] > 0.f ? acc[kk >> 4][kk & 15] : 0.f;
-    }
-    sfd_wave_sync();
-    sfd_stage(st, dz3, pos);
-    sfd_wave_sync();
-    sfd_load(b0, svb, sv::K1_X0 + s, h);
-    sfd_load(b1, svb, sv::K1_X0 + 32 + s, h);
-    sfd_load(b2, svb, sv::K1_T + s, h);
-    f32x16 accX[2];  // d(X0): heads (from rows) + warp layer 3
-    {
-      float dXh[32];
-      load_rows<32>(gb, sv::K1G_DX0, dXh, s, h);
-#pragma unroll
-      for (int kk = 0; kk < 32; ++kk) accX[kk >> 4][kk & 15] = dXh[kk];
-    }
-    f32x16 accT[1];
-    acc_zero<1>(accT);
-#ifdef RDRF_HEADS_BWD_F32
-    mfma_seg<2, 32>(accX, dz3, lds + pkb::K1W_W3T_X0, lane);
-    mfma_seg<1, 32>(accT, dz3, lds + pkb::K1W_W3T_T, lane);
-#else
-    mfma_seg_b3_pair<2, 1, 32>(accX, accT, dz3, lds + pkb::K1W_W3T_X0, lds + pkb::K1W_W3T_T, lane);
-#endif
-#pragma unroll
-    for (int bo = 0; bo < 2; ++bo) {   // layer3: dz3 x [X0 | T]
-      f32x4 av[4];
-      sfd_read(av, st, bo, pos);
-      bsum[2 + bo] += sfd_sum(av);
-      sfd_prod(accW[4 + 3 * bo], av, b0);
-      sfd_prod(accW[4 + 3 * bo + 1], av, b1);
-      sfd_prod(accW[4 + 3 * bo + 2], av, b2);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    {
-      float X0[32], dX0[32];
-      load_rows<32>(svb, sv::K1_X0, X0, s, h);
-      acc_copy<2>(dX0, accX);
-      float e0 = 0.f, e1 = 0.f, e2 = 0.f;
-      x0_bwd_flat(X0, dX0, h, e0, e1, e2);
-      e0 += __shfl_xor(e0, 32, 64); e1 += __shfl_xor(e1, 32, 64); e2 += __shfl_xor(e2, 32, 64);
-      dn0 += e0 + dw0; dn1 += e1 + dw1; dn2 += e2 + dw2;
-    }
-    if constexpr (GX) {
-      // g_xyz[idx][0..2] += ... in the lanes (act, h == 0): the tile's 384 bytes as a buffer, every other lane out of range
-      const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc((void*)(a.g_xyz + (size_t)n * 96), 0, 384, 0x00020000);
-      const int off = (act && h == 0) ? s * 12 : 1 << 20;
-      const float p0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, off, 0, 0));
-      const float p1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, off, 4, 0));
-      const float p2 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rp, off, 8, 0));
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p0 + (dn0 * a.box.inv[0] + gp0)), rp, off, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p1 + (dn1 * a.box.inv[1] + gp1)), rp, off, 4, 0);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, p2 + (dn2 * a.box.inv[2] + gp2)), rp, off, 8, 0);
-    }
-    {
-      // d(tout) of the tile's rays, as k_dyn_density_bwd<1, false, true>: segmented suffix sums over the lanes of each half; the
-      // first lane of a segment stores -- to dtout (ray inside the tile: a buffer over the tile's rays) or to one of the tile's two
-      // partial records in dtp (a buffer over the tile's 256 bytes); the other lanes and the other buffer: out of range
-      const int i0 = n * 32 + s, nl = i0 / a.S, nl0 = (n * 32) / a.S;
-      const int rb = nl * a.S - n * 32, re = rb + a.S - 1;
-      const int end = re < 31 ? re : 31;
-      const bool head = i0 < total && (s == 0 || rb == s);
-      const bool inside = rb >= 0 && re <= 31;
-      const int nrays = a.N - nl0 < 32 ? a.N - nl0 : 32;
-      const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc((void*)(a.dtout + (size_t)nl0 * 32), 0, nrays * 128, 0x00020000);
-      const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)(a.dtp + (size_t)n * 64), 0, 256, 0x00020000);
-      const int offt = (head && inside) ? (nl - nl0) * 128 + h * 16 : 1 << 20;
-      const int offq = (head && !inside) ? (s == 0 ? 0 : 128) + h * 16 : 1 << 20;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        float v = 0.f + accT[0][i];   // (dTacc of the other kernel: 0.f + the tile's product)
-#pragma unroll
-        for (int d = 1; d < 32; d <<= 1) {
-          const float o = __shfl_down(v, d, 32);
-          v += s + d <= end ? o : 0.f;
-        }
-        const int eo = (8 * (i >> 2) + (i & 3)) * 4;   // elem_of(i, h) = 8 (i >> 2) + 4 h + (i & 3)
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rt, offt, eo, 0);
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rq, offq, eo, 0);
-      }
-    }
-  }
-  // cross-wave sum in wave order, then one flush per workgroup.  C row i = (rr & 3) + 8 (rr >> 2) + 4 h (out neuron of the dz
-  // block), column = li (element of the input block)
-  float sm[wpd::NSM];
-#pragma unroll
-  for (int o = 0; o < 3; ++o) {
-    sm[o] = sw[o];
-    sm[3 + o] = wave_sum(h == 0 ? sb[o] : 0.f);   // both halves hold the same samples
-  }
-  float* red = lds;
-  for (int w = 0; w < nwaves; ++w) {
-    __syncthreads();   // (the first: every wave is done with the image and its stage)
-    if (wave == w) {
-#pragma unroll
-      for (int p = 0; p < wpd::NPROD; ++p)
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-          float* r = red + p * 1024 + rr * 64 + lane;
-          *r = w == 0 ? accW[p][rr] : *r + accW[p][rr];
-        }
-#pragma unroll
-      for (int i = 0; i < wpd::NDZ; ++i) {
-        float* r = red + wpd::NPROD * 1024 + i * 64 + lane;
-        *r = w == 0 ? bsum[i] : *r + bsum[i];
-      }
-#pragma unroll
-      for (int i = 0; i < wpd::NSM; ++i) {
-        float* r = red + wpd::NPROD * 1024 + (wpd::NDZ + i) * 64 + lane;
-        *r = w == 0 ? sm[i] : *r + sm[i];
-      }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int p = 0; p < wpd::NPROD; ++p) {
-    // product p: layer4 (p < 4): dz block p >> 1, input block p & 1; layer3: dz block (p - 4) / 3, input block (p - 4) % 3
-    const bool l4 = p < 4;
-    const int bo = l4 ? p >> 1 : (p - 4) / 3, k = l4 ? p & 1 : (p - 4) % 3;
-    const int ld = l4 ? 64 : 93;
-    float* dW = l4 ? G.l4w : G.l3w;
-    for (int e = threadIdx.x; e < 1024; e += blockDim.x) {
-      const int rr = e >> 6, hh = (e >> 5) & 1, c = e & 31;
-      const int col = l4 ? 32 * k + c : (k < 2 ? seg_imap(SEG_WARP3_X0, 32 * k + c, 93) : seg_imap(SEG_WARP3_T, c, 93));
-      const int orow = bo * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * hh;
-      if (col >= 0) grad_add(dW + (size_t)orow * ld + col, red[p * 1024 + e]);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < wpd::NDZ; ++i) {
-    float* db = i < 2 ? G.l4b : G.l3b;
-    const int orow = (i & 1) * 32 + (int)threadIdx.x;
-    if (threadIdx.x < 32)
-      grad_add(db + orow, red[wpd::NPROD * 1024 + i * 64 + threadIdx.x] + red[wpd::NPROD * 1024 + i * 64 + 32 + threadIdx.x]);
-  }
-  // the 3-row layer: lane (s, h) of every wave holds input element elem_of(s, h) of the three rows; every lane the rows' bias sums
-  for (int e = threadIdx.x; e < 3 * 64 + 3; e += blockDim.x) {
-    const float* r = red + wpd::NPROD * 1024 + wpd::NDZ * 64;
-    if (e < 192) grad_add(gw.l5w + (e >> 6) * 64 + elem_of(e & 31, (e >> 5) & 1), r[e]);
-    else grad_add(gw.l5b + (e - 192), r[(3 + e - 192) * 64]);
-  }
-}
-// launch geometry of k_dyn_warp_bwd_dw: whole workgroups of wpd::WAVES waves, a wave per tile, at most a workgroup per CU
-void warp_fused_geometry(long tiles, int* grid, int* waves) {
-  const long blocks = (tiles + wpd::WAVES - 1) / wpd::WAVES;
-  *grid = (int)(blocks < 1 ? 1 : (blocks > 256 ? 256 : blocks));
-  *waves = wpd::WAVES;
-}
-
-// ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
 void fill_static_w(StaticW& w, const RdrfStaticParams* P);
@@ -1794,7 +1172,7 @@ static int carve_bwd(BwdWs& b, void* ws, size_t ws_bytes, int N, int S, int dyna
 // dW jobs of the dynamic field's density phase (warp MLP, density / blending heads)
 void add_density_phase_dw(DwJobs& D, const float* grows1, const float* act1, const RdrfDynamicParams* G, int T1, bool live_d,
                           bool live_b, bool small_in_kernel, bool warp_in_kernel) {
-  // warp_in_kernel: k_dyn_warp_bwd_dw formed the gradients of layer3 and layer4 (and wrote no DZ3 / DZ4 rows)
+  // warp_in_kernel: the fused warp kernel (rdrf_bwd_fused.hip) formed the gradients of layer3 and layer4 (and wrote no DZ3 / DZ4 rows)
   if (!warp_in_kernel) {
   // layer3: [X0 | tout]
   dw_add(D, grows1, sv::K1G_ROWS, sv::K1G_DZ3, 2, 64, 0, act1, sv::K1_ROWS, 93, 93, G->l3w, G->l3b, nullptr, T1);
@@ -1836,21 +1214,12 @@ void add_density_phase_dw(DwJobs& D, const float* grows1, const float* act1, con
     dw_blk(D, sv::K1_X1, SEG_DEN1_X1, 0);
   }
 }
-// The warp MLP backward of the flat training path: k_dyn_warp_bwd_dw forms the gradients of layer3 / layer4 itself (it needs the
-// 3-row layer's sums in the kernel as well: small_dw).  RDRF_WARP_FUSED=0 (tools build): k_dyn_density_bwd<1, false, true> + their
+// The warp MLP backward of the flat training path: the fused kernel behind launch_warp_fused (rdrf_bwd_fused.hip) forms the
+// gradients of layer3 / layer4 itself (it needs the 3-row layer's sums in the kernel as well: small_dw).  RDRF_WARP_FUSED=0 (tools build): k_dyn_density_bwd<1, false, true> + their
 // products in k_dw3, its A/B partner.  The wave-per-ray and feature-mode paths keep the two kernels.
 static bool warp_fused_path(bool flat, bool small_dw) {
   static const int fused = RDRF_ENV("RDRF_WARP_FUSED") ? atoi(RDRF_ENV("RDRF_WARP_FUSED")) : 1;
   return flat && small_dw && fused != 0;
-}
-static int launch_warp_fused(const BwdArgs& a, const DynG& gw, const RdrfDynamicParams* G, long tiles, hipStream_t stream) {
-  int grid, waves;
-  warp_fused_geometry(tiles, &grid, &waves);
-  WarpGrads wg;
-  wg.l3w = G->l3w; wg.l3b = G->l3b; wg.l4w = G->l4w; wg.l4b = G->l4b;
-  if (a.g_xyz != nullptr) RDRF_LAUNCH("dyn_warp_bwd", k_dyn_warp_bwd_dw<true>, dim3(grid), dim3(64 * waves), stream, a, gw, wg);
-  else RDRF_LAUNCH("dyn_warp_bwd", k_dyn_warp_bwd_dw<false>, dim3(grid), dim3(64 * waves), stream, a, gw, wg);
-  return 0;
 }
 // static appearance phase (compacted: device count), MLP_Fea (fea) or MLP_Fea_TimeEmbedding head
 void add_static_app_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfStaticParams* G, bool fea, const int* cnt,
@@ -2293,7 +1662,7 @@ extern "C" int rdrf_scene_flow_bwd(const RdrfDynamicParams* P, const RdrfFieldCf
   RDRF_CHECK((size_t)N * S * 3 < (size_t)INT32_MAX, -1, "scene_flow_bwd: N * S * 3 must stay below 2^31 (32-bit sample indices)");
   const size_t tiles = ((size_t)N * S + 31) / 32;
   RDRF_CHECK(saved_bytes >= tiles * sv::SF_ROWS * 32 * 4, -3, "scene_flow_bwd: saved buffer too small");
-  // k_scene_flow_bwd_dw forms the weight gradients itself: no dz rows, no dw_sf launch.  RDRF_SF_FUSED=0 (tools build):
+  // the fused kernel (launch_scene_flow_fused, rdrf_bwd_fused.hip) forms the weight gradients itself: no dz rows, no dw_sf launch.  RDRF_SF_FUSED=0 (tools build):
   // k_scene_flow_bwd + k_dw3, its A/B partner
   static const int fused = RDRF_ENV("RDRF_SF_FUSED") ? atoi(RDRF_ENV("RDRF_SF_FUSED")) : 1;
   WsCarver c(ws, ws_bytes);
@@ -2309,19 +1678,8 @@ extern "C" int rdrf_scene_flow_bwd(const RdrfDynamicParams* P, const RdrfFieldCf
     rc = pack_launch(J, pkbuf, stream);
     if (rc) return rc;
   }
-  if (fused) {
-    int grid, waves;
-    scene_flow_fused_geometry((long)tiles, &grid, &waves);
-    SfGrads sg;
-    for (int i = 0; i < 4; ++i) { sg.w[i] = G->sfw[i]; sg.b[i] = G->sfb[i]; }
-    if (g_pts != nullptr)
-      RDRF_LAUNCH("scene_flow_bwd", k_scene_flow_bwd_dw<true>, dim3(grid), dim3(64 * waves), stream, N, S, make_box(cfg), pkimg,
-                  (const float*)saved, g_sf_f, g_sf_b, sg, g_pts);
-    else
-      RDRF_LAUNCH("scene_flow_bwd", k_scene_flow_bwd_dw<false>, dim3(grid), dim3(64 * waves), stream, N, S, make_box(cfg), pkimg,
-                  (const float*)saved, g_sf_f, g_sf_b, sg, g_pts);
-    return 0;
-  }
+  if (fused)
+    return launch_scene_flow_fused(N, S, make_box(cfg), pkimg, (const float*)saved, g_sf_f, g_sf_b, G, g_pts, (long)tiles, stream);
   const Geo g = geo_for_units((long)tiles);
   RDRF_LAUNCH("scene_flow_bwd", k_scene_flow_bwd, dim3(g.grid), dim3(g.block), stream, N, S,
               make_box(cfg), pkimg, (const float*)saved, grows, g_sf_f, g_sf_b, G->sfb[3], g_pts);

@@ -1,6 +1,7 @@
-// rdrf_bwd_dev.hpp -- device-side pieces shared by the backward-data kernels (rdrf_bwd.hip) and the gradient-scatter
-// kernels (rdrf_scatter.hip): the backward LDS images, the argument block of the backward kernels, the sample-major
-// d(feature) records, and the VM gather backward per quad (run reduction in DPP, LDS line accumulators, plane windows).
+// rdrf_bwd_dev.hpp -- device-side pieces shared by the backward-data kernels (rdrf_bwd.hip, rdrf_bwd_fused.hip) and the
+// gradient-scatter kernels (rdrf_scatter.hip): the backward LDS images, the argument block of the backward kernels, the
+// small-layer / reduce-scatter helpers of the backward-data kernels, the sample-major d(feature) records, and the VM gather
+// backward per quad (run reduction in DPP, LDS line accumulators, plane windows).
 // A unit whose kernels write gradient rows maps RDRF_GROWS_TEMPORAL to RDRF_SAVE_TEMPORAL before it includes this header.
 #pragma once
 #include "rdrf_kernels.hpp"
@@ -148,6 +149,63 @@ struct DynG {
   float *rbv, *rwv, *l5b, *db2, *bb2;
   float *l5w, *dw2, *bw2;   // small layers of the density phase: weight gradients formed in k_dyn_density_bwd (ray path)
 };
+
+// pieces shared by the backward-data kernels (rdrf_bwd.hip) and their fused-dW forms (rdrf_bwd_fused.hip), whose flush targets
+// SfGrads / WarpGrads are
+struct SfGrads {
+  float* w[4];   // sfw[0..3]
+  float* b[4];   // sfb[0..3]
+};
+struct WarpGrads {
+  float *l3w, *l3b, *l4w, *l4b;
+};
+
+// backward of a small output layer kept on the VALU (NO <= 6 outputs): dz[kk] = relu'(H[kk]) * sum_o W[o][kk] dzo[o]
+// for this lane half's KK inputs.  ws = [NO][2][KK] in LDS, read as 16-byte quads (element-wise `lds[...]` reads
+// compiled to one ds_read_b32 + lgkmcnt(0) wait per weight).
+template <int KK, int NO>
+RDRF_D void small_layer_bwd(float (&dz)[KK], const float (&H)[KK], const float* __restrict__ ws, int h,
+                            const float (&dzo)[NO]) {
+#pragma unroll
+  for (int q = 0; q < KK / 4; ++q) {
+    f32x4 d = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+      const f32x4 wv = *reinterpret_cast<const f32x4*>(ws + o * 2 * KK + h * KK + 4 * q);
+      d.x = fmaf(wv.x, dzo[o], d.x); d.y = fmaf(wv.y, dzo[o], d.y);
+      d.z = fmaf(wv.z, dzo[o], d.z); d.w = fmaf(wv.w, dzo[o], d.w);
+    }
+    dz[4 * q + 0] = H[4 * q + 0] > 0.f ? d.x : 0.f; dz[4 * q + 1] = H[4 * q + 1] > 0.f ? d.y : 0.f;
+    dz[4 * q + 2] = H[4 * q + 2] > 0.f ? d.z : 0.f; dz[4 * q + 3] = H[4 * q + 3] > 0.f ? d.w : 0.f;
+  }
+}
+
+template <int NB>
+RDRF_D void acc_zero(f32x16 (&acc)[NB]) {
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
+}
+
+// Reduce-scatter over the 32 lanes of a half-wave: on return lane s holds the sum over the half's 32 lanes of p[s]
+// (five butterfly stages: 31 lane exchanges + 31 adds).  Used for the weight gradients of the 3- and 1-row layers of the
+// density phase (layer5, density / blending layer2): dW[e] = sum over the tile's samples of dz(sample) * in_e(sample),
+// with dz a per-lane scalar and in_e the 32 slots the lane already holds -- as MFMA products in k_dw2 these were 6 of
+// the 40 per tile, each 27/32 empty.  ALL lanes of the wave must call.
+RDRF_D float reduce_scatter32(const float (&p)[32], int s) {
+  const bool b4 = s & 16, b3 = s & 8, b2 = s & 4, b1 = s & 2, b0 = s & 1;
+  float q[16], r[8], t[4], u[2];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) q[i] = (b4 ? p[i + 16] : p[i]) + __shfl_xor(b4 ? p[i] : p[i + 16], 16, 64);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) r[i] = (b3 ? q[i + 8] : q[i]) + __shfl_xor(b3 ? q[i] : q[i + 8], 8, 64);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) t[i] = (b2 ? r[i + 4] : r[i]) + __shfl_xor(b2 ? r[i] : r[i + 4], 4, 64);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) u[i] = (b1 ? t[i + 2] : t[i]) + __shfl_xor(b1 ? t[i] : t[i + 2], 2, 64);
+  return (b0 ? u[1] : u[0]) + __shfl_xor(b0 ? u[0] : u[1], 1, 64);
+}
 
 // ------------------------------------------------------------------------------------------------
 // VM gather backward for one quad: scatter into plane / line (atomics) + coordinate gradients

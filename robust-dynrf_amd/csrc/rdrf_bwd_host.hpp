@@ -1,10 +1,12 @@
 // rdrf_bwd_host.hpp -- host interface between the backward entry points (rdrf_bwd.hip) and the units that launch the
-// kernels they define: the gradient scatter (rdrf_scatter.hip) and the dW products (rdrf_dw.hip).  Without relocatable
-// device code a kernel is launched from the unit that defines it, so these are plain functions, not kernel pointers.
+// kernels they define: the gradient scatter (rdrf_scatter.hip), the dW products (rdrf_dw.hip) and the backward-data kernels
+// that form their weight gradients themselves (rdrf_bwd_fused.hip).  Without relocatable device code a kernel is launched
+// from the unit that defines it, so these are plain functions, not kernel pointers.
 #pragma once
 #include "rdrf_host.hpp"
 
 struct BwdArgs;   // rdrf_bwd_dev.hpp
+struct DynG;
 
 // backward workspace (carve_bwd, rdrf_bwd.hip)
 struct BwdWs {
@@ -118,10 +120,6 @@ void add_dyn_app_dw(DwJobs& D, const float* grows3, const float* act3, const Rdr
 void add_scene_flow_dw(DwJobs& D, const float* grows, const float* act, const RdrfDynamicParams* G, int T);
 void add_feat_static_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfStaticParams* G, int Np);
 void add_feat_dyn_app_dw(DwJobs& D, const float* grows3, const float* act3, const RdrfDynamicParams* G, int Np);
-// launch geometry of k_scene_flow_bwd_dw (rdrf_bwd.hip) for `tiles` 32-sample tiles: workgroups, waves per workgroup
-void scene_flow_fused_geometry(long tiles, int* grid, int* waves);
-// the same for k_dyn_warp_bwd_dw
-void warp_fused_geometry(long tiles, int* grid, int* waves);
 // The warp MLP backward of the flat training path alone, on rows the caller supplies (rdrf_selftest_warp_bwd): the kernel(s)
 // rdrf_dynamic_bwd launches under `dyn_warp_bwd`, followed on the two-kernel path by the k_dw3 products of layer3 / layer4.
 // pk: PACK_AREA_FLOATS floats for the weight images; valid: N * S bytes of scratch.
@@ -129,3 +127,13 @@ int warp_bwd_on_rows(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int N,
                      float* dxw, float* dxn, const float* g_xyz_prime, const RdrfDynamicParams* G, float* g_xyz, float* dtout,
                      float* dtp, float* pk, uint8_t* valid, hipStream_t stream);
 size_t warp_bwd_on_rows_pack_floats();
+
+// ------------------------------------------------------------------------------------------------
+// backward-data kernels with the weight gradients formed in the kernel (rdrf_bwd_fused.hip)
+// ------------------------------------------------------------------------------------------------
+void fused_dw_geometry(long tiles, int* grid, int* waves);   // for `tiles` 32-sample tiles: workgroups, waves per workgroup
+// k_scene_flow_bwd_dw<g_pts != nullptr>: pkimg = the backward weight images, saved = the forward's activation rows, G: sfw / sfb
+int launch_scene_flow_fused(int N, int S, const Box& box, const float* pkimg, const float* saved, const float* g_sf_f,
+                            const float* g_sf_b, const RdrfDynamicParams* G, float* g_pts, long tiles, hipStream_t stream);
+// k_dyn_warp_bwd_dw<a.g_xyz != nullptr>: G = where the gradients of layer3 / layer4 go (layer5: gw)
+int launch_warp_fused(const BwdArgs& a, const DynG& gw, const RdrfDynamicParams* G, long tiles, hipStream_t stream);

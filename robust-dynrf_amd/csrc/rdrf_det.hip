@@ -7,10 +7,11 @@
 // the units that invoke RDRF_DET_UNIT (rdrf_common.hpp): every unit with a grad_add in a kernel has to be in this list
 typedef int (*DetBind)(int slot, const DetMap* m, hipStream_t stream);
 int det_bind_bwd(int, const DetMap*, hipStream_t);
+int det_bind_bwd_fused(int, const DetMap*, hipStream_t);
 int det_bind_scatter(int, const DetMap*, hipStream_t);
 int det_bind_dw(int, const DetMap*, hipStream_t);
 int det_bind_optim(int, const DetMap*, hipStream_t);
-static const DetBind g_det_binders[] = {det_bind_bwd, det_bind_scatter, det_bind_dw, det_bind_optim};
+static const DetBind g_det_binders[] = {det_bind_bwd, det_bind_bwd_fused, det_bind_scatter, det_bind_dw, det_bind_optim};
 static DetMap g_det_host[2];   // what the slots are bound to; the binders copy from here, so it outlives the call
 
 __global__ void k_det_finish(float* __restrict__ g, unsigned long long* __restrict__ shadow, size_t n) {

@@ -1,5 +1,5 @@
 // rdrf_kernels.hpp -- argument structs, saved-activation layout and helpers shared by the forward
-// (rdrf_fwd.hip) and backward (rdrf_bwd.hip, rdrf_scatter.hip, rdrf_dw.hip) kernels.
+// (rdrf_fwd.hip) and backward (rdrf_bwd.hip, rdrf_bwd_fused.hip, rdrf_scatter.hip, rdrf_dw.hip) kernels.
 #pragma once
 #include "rdrf_host.hpp"
 

@@ -357,13 +357,13 @@ extern "C" int rdrf_selftest_dw_describe(int plan, int flags, int* out, int cap)
 
 extern "C" int rdrf_selftest_sf_geometry(int ntiles, int* grid, int* waves) {
   RDRF_CHECK(ntiles >= 0 && grid && waves, -1, "selftest_sf_geometry: bad arguments");
-  scene_flow_fused_geometry(ntiles, grid, waves);
+  fused_dw_geometry(ntiles, grid, waves);
   return 0;
 }
 
 extern "C" int rdrf_selftest_warp_geometry(int ntiles, int* grid, int* waves) {
   RDRF_CHECK(ntiles >= 0 && grid && waves, -1, "selftest_warp_geometry: bad arguments");
-  warp_fused_geometry(ntiles, grid, waves);
+  fused_dw_geometry(ntiles, grid, waves);
   return 0;
 }
 

@@ -1,4 +1,4 @@
-"""rdrf_scene_flow_bwd with the weight gradients formed in the backward-data kernel (csrc/rdrf_bwd.hip k_scene_flow_bwd_dw)
+"""rdrf_scene_flow_bwd with the weight gradients formed in the backward-data kernel (csrc/rdrf_bwd_fused.hip k_scene_flow_bwd_dw)
 on activation rows the test supplies (`saved` is an input of the entry point: [tile][256 rows][32 samples], X | H0 | H2 | H4).
 
 The reference is the layer equations alone, per sample n (dz6 = [g_f, g_b], zero where a gradient is absent):

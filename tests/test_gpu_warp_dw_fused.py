@@ -1,5 +1,5 @@
 """The warp MLP backward of the flat training path with the weight gradients of layer3 / layer4 formed in the backward-data
-kernel (csrc/rdrf_bwd.hip k_dyn_warp_bwd_dw), alone, through rdrf_selftest_warp_bwd on rows the test supplies: act1
+kernel (csrc/rdrf_bwd_fused.hip k_dyn_warp_bwd_dw), alone, through rdrf_selftest_warp_bwd on rows the test supplies: act1
 [tile][576][32] (X0 | X1 | T | H3 | H4 | ...), grows1 [tile][544][32] (the heads' d(X0) rows are an input), the coordinate
 gradients dxw / dxn and g_xyz_prime per sample.  The field's box is [-1, 1]^3, so box.inv = 1 and dd = dxw + g_xyz_prime.
 

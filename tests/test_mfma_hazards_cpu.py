@@ -37,11 +37,12 @@ FAMILIES = {
     "rdrf_bwd": [("k_static_app_bwd", (), 3 * 2 * 6, 3),                    # features only: <3, 16>; full: + <4, 64> + <5, 64>
                  ("k_dyn_app_bwd", (), 7 * 2 * 6, 3),                       # features only: <7, 16>; full: + <4, 64> + <3, 64>
                  ("k_dyn_density_bwd", (), (2 + 3) * 4 * 6, 6)],            # warp: b3<2, 32> + pair<2, 1, 32>; heads: 2 x pair<3, 2, 32>
+    "rdrf_bwd_fused": [("k_dyn_warp_bwd_dw", (), (2 + 1) * 4 * 6, 2)],     # b3<2, 32> + pair<2, 1, 32>, whose two X0 blocks are dead without g_xyz
     "rdrf_render": [("k_render_fused", (), 4 * 18 * 6 + 2 * 2 * 9 * 6 + 4 * 15 * 6, 2)],
     "rdrf_selftest": [("k_st_b3s_chain", (), 4 * 7 * 6, 2), ("k_st_b3s_t", (), 3 * 2 * 6, 5),
                       ("k_st_b3_pair", (), 3 * 4 * 6, 2), ("k_st_b3I", (), 2 * 4 * 6, 2)],
 }
-UNIT_TOTALS = {"rdrf_fwd": 3528, "rdrf_bwd": 2976, "rdrf_render": 2016, "rdrf_motion": 0,   # rdrf_motion: the scene-flow MLP is fp32
+UNIT_TOTALS = {"rdrf_fwd": 3528, "rdrf_bwd": 2976, "rdrf_bwd_fused": 120 + 72, "rdrf_render": 2016, "rdrf_motion": 0,   # rdrf_motion: the scene-flow MLP is fp32
                "rdrf_selftest": 108 + 48 + 120 + 72 + 168 + 240 + 84 + 36 + 192 + 144 + 240}
 
 

@@ -24,7 +24,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "robust-dynrf_amd", "csrc")
-UNITS = ("rdrf_fwd.hip", "rdrf_bwd.hip", "rdrf_render.hip", "rdrf_motion.hip", "rdrf_selftest.hip")
+UNITS = ("rdrf_fwd.hip", "rdrf_bwd.hip", "rdrf_bwd_fused.hip", "rdrf_render.hip", "rdrf_motion.hip", "rdrf_selftest.hip")
 MFMA = "v_mfma_f32_32x32x16_bf16"
 NONE = 10 ** 6   # "no such VALU instruction in the block"
 
