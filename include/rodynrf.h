@@ -749,6 +749,45 @@ int rdrf_selftest_scatter(int kind, int mode, const RdrfScatterTest* t, rdrf_str
 int rdrf_selftest_scatter_describe(int kind, const int* grid, int* out, int cap);
 int rdrf_selftest_scatter_last(int* out, int cap);
 
+/* ---- alpha volumes and alpha-grid masks (models/tensorBase.py:42-79 AlphaGridMask, :565-702) ----------------------------
+ * A mask is the occupancy grid of updateAlphaMask, bit-packed exactly as `save` (:465-469) stores it: the bool volume of
+ * logical shape (G2, G1, G0, T) flattened in C order, eight entries per byte, first entry in the most significant bit
+ * (np.packbits) -- the buffer IS the checkpoint's "alphaMask.mask" payload.  grid = {G0, G1, G2} (x, y, z), aabb = the
+ * mask's own box (min xyz, max xyz). */
+typedef struct RdrfAlphaMask {
+  const uint8_t* bits;
+  int grid[3];
+  int T;
+  float aabb[6];
+} RdrfAlphaMask;
+
+/* compute_alpha (:684-702) for M points x T times: alpha[M][T] = 1 - exp(-sigma length), sigma what the field's forward
+ * gives a sample at that un-normalised position and time (dynamic: warp -> density features at the warped point ->
+ * density head -> feature2density; static: density features -> feature2density), bit for bit.  params: RdrfStaticParams
+ * (dynamic = 0) or RdrfDynamicParams (dynamic = 1).  mask: nullable; a point whose mask sample at a time is <= 0 gets
+ * sigma 0 there.  sigma: nullable [M][T].  The static field needs no workspace. */
+size_t rdrf_compute_alpha_workspace_bytes(int M, int T);
+int rdrf_compute_alpha(const void* params, int dynamic, const RdrfFieldCfg* cfg, const float* xyz, int M,
+                       const float* times, int T, float length, const RdrfAlphaMask* mask, float* alpha, float* sigma,
+                       void* ws, size_t ws_bytes, rdrf_stream_t stream);
+
+/* the native part of updateAlphaMask (:592-629): alpha [G0][G1][G2][T] is clamped to [0, 1], max-pooled 3 x 3 x 3 over
+ * space per time slice (stride 1, padding 1) and thresholded (>= thres is occupied).  bits: ceil(G0 G1 G2 T / 8) bytes in
+ * the layout of RdrfAlphaMask.  stats (7 x int64, device): the occupied count, then the min and the max lattice index
+ * (ix, iy, iz) over all times; with a count of 0 the six indices are meaningless. */
+int rdrf_alpha_mask_build(const float* alpha, int G0, int G1, int G2, int T, float thres, uint8_t* bits, int64_t* stats,
+                          rdrf_stream_t stream);
+
+/* AlphaGridMask.sample_alpha (:56-73): normalise by the mask's aabb, slice round((t + 1) / 2 (T - 1)) (half-way cases to
+ * even; clamped to the slices), trilinear, align_corners, zero padding.  t: one device value for all points
+ * (t_per_point = 0) or one per point. */
+int rdrf_alpha_mask_sample(const RdrfAlphaMask* mask, const float* xyz, const float* t, int t_per_point, int64_t n,
+                           float* out, rdrf_stream_t stream);
+/* ray_valid &= alpha_mask for xyz [N][S][3], ts [N]: valid[N][S] keeps its 1 where mask0's or (nullable) mask1's sample
+ * is > 0 -- the static and the dynamic occupancy together, one launch. */
+int rdrf_alpha_mask_valid(const RdrfAlphaMask* mask0, const RdrfAlphaMask* mask1, const float* xyz, const float* ts, int N,
+                          int S, uint8_t* valid, rdrf_stream_t stream);
+
 /* timing hook: average device time (ms) of the dominant kernel launches recorded with HIP events
  * since the last reset; used by bench.py for the roofline figure. */
 void rdrf_prof_reset(void);

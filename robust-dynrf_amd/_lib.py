@@ -98,6 +98,10 @@ class BatchC(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in BATCH_OUTPUTS]
 
 
+class RdrfAlphaMask(C.Structure):   # include/rodynrf.h RdrfAlphaMask: a packed occupancy grid (alpha.AlphaGridMask)
+    _fields_ = [("bits", C.c_void_p), ("grid", C.c_int * 3), ("T", C.c_int), ("aabb", C.c_float * 6)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -165,6 +169,16 @@ def _load():
     lib.rdrf_ssim_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.rdrf_ssim.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.rdrf_compute_alpha_workspace_bytes.restype = C.c_size_t
+    lib.rdrf_compute_alpha_workspace_bytes.argtypes = [C.c_int, C.c_int]
+    lib.rdrf_compute_alpha.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float,
+                                       C.POINTER(RdrfAlphaMask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.rdrf_alpha_mask_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
+    lib.rdrf_alpha_mask_sample.argtypes = [C.POINTER(RdrfAlphaMask), C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
+                                           C.c_void_p]
+    lib.rdrf_alpha_mask_valid.argtypes = [C.POINTER(RdrfAlphaMask), C.POINTER(RdrfAlphaMask), C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_int, C.c_void_p, C.c_void_p]
     lib.rdrf_gather_batch.argtypes = [C.POINTER(SceneTablesC), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(BatchC), C.c_void_p]
     lib.rdrf_selftest_layer.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_size_t, C.c_void_p]
@@ -217,6 +231,8 @@ SYMBOLS = [
     "rdrf_render_maps_fwd", "rdrf_render_chunks_maps_fwd", "rdrf_camera_rays", "rdrf_ssim_workspace_bytes", "rdrf_ssim",
     "rdrf_render_motion_workspace_bytes", "rdrf_render_motion_fwd", "rdrf_flow_to_image_workspace_bytes", "rdrf_flow_to_image",
     "rdrf_gather_batch",
+    "rdrf_compute_alpha_workspace_bytes", "rdrf_compute_alpha", "rdrf_alpha_mask_build", "rdrf_alpha_mask_sample",
+    "rdrf_alpha_mask_valid",
     "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_selftest_layer", "rdrf_selftest_dw", "rdrf_selftest_dw_describe",
     "rdrf_selftest_sf_geometry", "rdrf_selftest_warp_geometry", "rdrf_selftest_warp_bwd_workspace_bytes", "rdrf_selftest_warp_bwd",
     "rdrf_selftest_sort_temp_bytes", "rdrf_selftest_sort", "rdrf_selftest_scatter_workspace_bytes", "rdrf_selftest_scatter",

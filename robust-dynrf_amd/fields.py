@@ -685,16 +685,40 @@ class TensorBase(nn.Module):
         kwargs = self.get_kwargs()
         kwargs["se3_poses"] = se3_poses
         kwargs["focal_ratio_refine"] = focal_ratio_refine
-        torch.save({"kwargs": kwargs, "state_dict": self.state_dict()}, path)
+        ckpt = {"kwargs": kwargs, "state_dict": self.state_dict()}
+        if self.alphaMask is not None:   # models/tensorBase.py:465-469: shape, np.packbits payload, aabb
+            from .alpha import mask_to_ckpt
+            ckpt.update(mask_to_ckpt(self.alphaMask))
+        torch.save(ckpt, path)
 
     def load(self, ckpt):
-        """models/tensorBase.py:472-485.  The alpha-mask machinery is dead in the reference (compute_alpha calls
-        compute_densityfeature with the wrong arity) and is not built here: a checkpoint
-        that carries one is refused instead of silently dropping it."""
-        if any(k.startswith("alphaMask") for k in ckpt) or any(k.startswith("alphaMask") for k in ckpt["state_dict"]):
-            raise NotImplementedError("checkpoint carries an alphaMask: AlphaGridMask is not built (dead code in "
-                                      "the reference, SURVEY.md section 0)")
+        """models/tensorBase.py:472-485; a checkpoint that carries an alpha mask rebuilds it (with the tSize the
+        reference forgets to hand to AlphaGridMask), one without leaves self.alphaMask as it is."""
+        if "alphaMask.aabb" in ckpt.keys():
+            from .alpha import mask_from_ckpt
+            self.alphaMask = mask_from_ckpt(ckpt, self.device, int(self.tSize.item()))
         self.load_state_dict(ckpt["state_dict"])
+
+    # ---- alpha volumes and alpha-grid masks (models/tensorBase.py:565-702; alpha.py, csrc/rdrf_alpha.hip) ----------
+    def compute_alpha(self, xyz_locs, t, length=1):
+        from .alpha import compute_alpha
+        return compute_alpha(self, xyz_locs, t, length)
+
+    def getDenseAlpha(self, gridSize=None, times=None):
+        from .alpha import get_dense_alpha
+        return get_dense_alpha(self, gridSize, times)
+
+    def updateAlphaMask(self, gridSize=(200, 200, 200)):
+        from .alpha import update_alpha_mask
+        return update_alpha_mask(self, gridSize)
+
+    def filtering_rays(self, all_rays, all_rgbs, all_ts=None, N_samples=256, chunk=10240 * 5, bbox_only=False):
+        from .alpha import filtering_rays
+        return filtering_rays(self, all_rays, all_rgbs, all_ts, N_samples, chunk, bbox_only)
+
+    def shrink(self, new_aabb, voxel_size=None):
+        raise NotImplementedError("shrink reallocates the VM factors under the flat optimiser buffers and is not built: "
+                                  "the new_aabb of updateAlphaMask is informational")
 
     # ---- samplers (models/tensorBase.py:487-559): device kernels, RNG stays in torch ----------
     def sample_ray_ndc(self, rays_o, rays_d, is_train=True, N_samples=-1):

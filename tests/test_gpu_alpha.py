@@ -1,0 +1,324 @@
+"""GPU tests of the alpha-mask layer (csrc/rdrf_alpha.hip, robust-dynrf_amd/alpha.py): compute_alpha / getDenseAlpha against
+the project's own forward, the mask build against the restatement of tests/_alpha_prim.py (pinned on the CPU against
+F.max_pool3d / np.packbits), sample_alpha against values the reference computed (tests/golden/alpha_mask.npz), the
+checkpoint keys against a file the reference wrote, updateAlphaMask / filtering_rays end to end."""
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import _alpha_prim as A
+from _gpu_util import COMMON
+from _util import GOLDEN, record_margin
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+GRID, T = [9, 11, 7], 3
+AABB = torch.tensor([[-1.5, -1.67, -1.0], [1.5, 1.67, 1.0]])
+LENGTH = 25.0
+BOUND = 2.0 ** -22   # alpha <= 1 and a 2-ulp exp, plus the roundings of the product and the subtraction
+_cache = {}
+
+
+def fields(act):
+    """the two fields on the small grid, tSize 3 (density_shift 0: softplus sigma of order 1, not e^-10)"""
+    if act not in _cache:
+        import rodynrf
+        torch.manual_seed(7)
+        kw = dict(COMMON, near_far=[0.0, 1.0], density_shift=0.0, fea2denseAct=act)
+        st = rodynrf.TensorVMSplit(AABB, GRID, T, DEV, shadingMode="MLP_Fea", fea_pe=2, **kw)
+        dy = rodynrf.TensorVMSplit_TimeEmbedding(AABB, GRID, T, DEV, shadingMode="MLP_Fea_late_view", fea_pe=0, **kw)
+        with torch.no_grad():   # the initialiser's density features are ~1e-2: spread sigma over (0, 1)
+            for p in list(st.density_line) + list(dy.density_line):
+                p.mul_(6.0)
+            dy.density_layer2.weight.mul_(4.0)
+        _cache[act] = (st, dy)
+    return _cache[act]
+
+
+def points(M, seed):
+    g = torch.Generator().manual_seed(seed)
+    p = AABB[0] + torch.rand(M, 3, generator=g) * (AABB[1] - AABB[0]) * 1.04 - 0.02 * (AABB[1] - AABB[0])
+    return p.to(DEV)
+
+
+def forward_sigma(field, xyz, times):
+    """sigma [M,T] of the field's own forward: ray k carries the M points as its samples at time k, all valid"""
+    Tn, M = times.numel(), xyz.shape[0]
+    rays = torch.tensor([0.0, 0.0, -1.0, 0.0, 0.0, 2.0], device=DEV).repeat(Tn, 1)
+    z = torch.linspace(0, 1, M, device=DEV).repeat(Tn, 1)
+    with torch.no_grad():
+        out = field(rays, times.to(DEV), None, xyz[None].repeat(Tn, 1, 1).contiguous(), z,
+                    torch.ones(Tn, M, dtype=torch.bool, device=DEV), is_train=False, ray_type="ndc", rgb=False)
+    return out[7].t().contiguous()
+
+
+def check_alpha(name, alpha, sigma_fwd, length):
+    want = 1.0 - torch.exp(-sigma_fwd.double().cpu() * length)
+    err = float((alpha.double().cpu() - want).abs().max())
+    print(f"{name}: max |alpha - f64(forward sigma)| = {err:.3e} (bound {BOUND:.3e}), alpha in [{float(alpha.min()):.3f}, {float(alpha.max()):.3f}]")
+    record_margin(name, err / BOUND)
+    assert err <= BOUND, (name, err)
+
+
+@pytest.mark.parametrize("act", ["relu", "softplus"])
+@pytest.mark.parametrize("which", ["static", "dynamic"])
+def test_compute_alpha_matches_forward_sigma(which, act):
+    from importlib import import_module
+    alpha_mod = import_module("robust-dynrf_amd.alpha")
+    field = fields(act)[which == "dynamic"]
+    for M in (1, 31, 32, 33, 65):
+        for Tn in (2, 3):
+            xyz = points(M, 100 * M + Tn)
+            times = torch.linspace(-1, 1, Tn)
+            alpha, sigma = alpha_mod.alpha_volume(field, xyz, times.to(DEV), LENGTH, want_sigma=True)
+            ref = forward_sigma(field, xyz, times)
+            assert alpha.shape == (M, Tn)
+            check_alpha(f"{which}-{act} M={M} T={Tn}", alpha, ref, LENGTH)
+            assert torch.equal(sigma, ref), (which, act, M, Tn)   # the same device functions in the same order: the same bits
+            if M == 33:
+                assert float(ref.max()) > 0.0 and float(alpha.max()) > 0.05   # the case is not trivially zero
+                got = field.compute_alpha(xyz, float(times[1]), LENGTH)      # the public scalar-time form
+                assert got.shape == (M,) and torch.equal(got, alpha[:, 1])
+
+
+@pytest.mark.parametrize("which", ["static", "dynamic"])
+def test_dense_alpha_with_a_partial_last_slab(which, monkeypatch):
+    from importlib import import_module
+    alpha_mod = import_module("robust-dynrf_amd.alpha")
+    field = fields("relu")[which == "dynamic"]
+    monkeypatch.setattr(alpha_mod, "SLAB_POINTS", 2 * GRID[1] * GRID[2])   # slabs of 2 rows: 9 = 4 x 2 + 1
+    alpha, dense = field.getDenseAlpha()
+    assert alpha.shape == (*GRID, T) and dense.shape == (*GRID, 3)
+    s = [torch.linspace(0, 1, g, device=DEV) for g in GRID]
+    want = torch.stack(torch.meshgrid(*s, indexing="ij"), -1)
+    assert torch.equal(dense, field.aabb[0] * (1 - want) + field.aabb[1] * want)
+    times = torch.tensor([k / (T - 1.0) * 2.0 - 1.0 for k in range(T)])
+    ref = forward_sigma(field, dense.reshape(-1, 3), times)
+    check_alpha(f"dense {which}", alpha.reshape(-1, T), ref, field._step_host)
+    monkeypatch.setattr(alpha_mod, "SLAB_POINTS", 1 << 21)
+    whole, _ = field.getDenseAlpha()
+    assert torch.equal(whole, alpha)
+    a2, _ = field.getDenseAlpha(gridSize=(4, 5, 3), times=[-1.0, 0.25])
+    assert a2.shape == (4, 5, 3, 2)
+    one = type(field)(AABB, GRID, 1, DEV, shadingMode=field.shadingMode, fea_pe=field.fea_pe,
+                      **dict(COMMON, near_far=[0.0, 1.0], density_shift=0.0, fea2denseAct="relu"))
+    with pytest.raises(ValueError):
+        one.getDenseAlpha()
+
+
+@pytest.mark.parametrize("which", ["static", "dynamic"])
+def test_compute_alpha_with_a_mask(which):
+    import rodynrf
+    field = fields("softplus")[which == "dynamic"]
+    vol = torch.rand(7, 11, 9, T, generator=torch.Generator().manual_seed(5)) < 0.3
+    xyz = points(333, 9)
+    times = torch.tensor([-1.0, 0.0, 1.0], device=DEV)
+    assert field.alphaMask is None
+    free = field.compute_alpha(xyz, times, LENGTH)
+    field.alphaMask = rodynrf.AlphaGridMask(DEV, AABB, vol.float(), T)
+    try:
+        got = field.compute_alpha(xyz, times, LENGTH)
+    finally:
+        field.alphaMask = None
+    assert got.shape == (333, T) and float(free.min()) > 0.0
+    for k in range(T):
+        keep = torch.from_numpy(A.sample_alpha(vol.numpy(), AABB.numpy(), xyz.cpu().numpy(), float(times[k])) > 0).to(DEV)
+        assert 30 < int(keep.sum()) < 320
+        assert bool((got[~keep, k] == 0).all())
+        assert torch.equal(got[keep, k], free[keep, k])
+
+
+def _build(alpha, thres):
+    from importlib import import_module
+    bits, stats = import_module("robust-dynrf_amd.alpha").build_mask(torch.from_numpy(alpha).to(DEV), thres)
+    return bits.cpu().numpy(), stats.cpu().tolist()
+
+
+@pytest.mark.parametrize("shape", [(9, 11, 7, 3), (3, 5, 7, 3), (1, 1, 1, 1), (17, 4, 33, 2)])
+def test_mask_build_matches_the_restatement(shape):
+    rng = np.random.default_rng(sum(shape))
+    thres = 0.3
+    alpha = (rng.random(shape) ** 3 * 1.4 - 0.2).astype(np.float32)
+    alpha.reshape(-1)[::5] = np.float32(thres)          # exactly at the threshold: occupied
+    alpha.reshape(-1)[1::11] = np.nextafter(np.float32(thres), np.float32(0))
+    bits, st = _build(alpha, thres)
+    occ = A.pool_threshold(alpha, thres)
+    assert np.array_equal(bits, A.pack(occ))
+    want = A.stats(occ)
+    assert st[0] == want[0] > 0 and st[1:] == want[1:]
+
+
+def test_mask_build_corner_voxel_and_empty_volume():
+    alpha = np.zeros((4, 5, 6, 2), dtype=np.float32)
+    alpha[3, 4, 5, 1] = 2.0   # clamped to 1
+    bits, st = _build(alpha, 1.0)
+    occ = A.pool_threshold(alpha, 1.0)
+    assert occ.sum() == 8 and np.array_equal(bits, A.pack(occ)) and st == [8, 2, 3, 4, 3, 4, 5]   # no wrap to the far side
+    alpha[:] = 0.0
+    bits, st = _build(alpha, 0.5)
+    assert st[0] == 0 and not bits.any()
+    import rodynrf
+    st_f = fields("relu")[0]
+    old = st_f.alphaMask_thres
+    st_f.alphaMask_thres = 2.0   # alpha never exceeds 1
+    try:
+        with pytest.raises(rodynrf.RdrfError):
+            st_f.updateAlphaMask((5, 4, 3))
+    finally:
+        st_f.alphaMask_thres = old
+    assert st_f.alphaMask is None
+
+
+def _fixture():
+    z = np.load(os.path.join(GOLDEN, "alpha_mask.npz"))
+    return {k: z[k] for k in z.files}
+
+
+def test_sample_alpha_matches_the_reference_fixture():
+    import rodynrf
+    g = _fixture()
+    m = rodynrf.AlphaGridMask(DEV, torch.from_numpy(g["aabb"]), torch.from_numpy(g["volume"]).float(), 3)
+    xyz, t = torch.from_numpy(g["xyz"]).to(DEV), torch.from_numpy(g["t"]).to(DEV)
+    got = m.sample_alpha(xyz, t).cpu().numpy()
+    err = float(np.abs(got - g["alpha"]).max())
+    record_margin("sample_alpha vs reference", err / 1e-6)
+    assert err <= 1e-6
+    assert np.array_equal(got > 0, g["alpha"] > 0)
+    for tv in np.unique(g["t"]):   # one time for all points == that time per point
+        sel = torch.from_numpy(g["t"] == tv).to(DEV)
+        assert torch.equal(m.sample_alpha(xyz[sel], float(tv)).cpu(), torch.from_numpy(got)[sel.cpu()])
+
+
+def test_valid_mode_ors_two_masks():
+    import rodynrf
+    g = _fixture()
+    aabb = torch.from_numpy(g["aabb"])
+    vol0 = torch.from_numpy(g["volume"])
+    vol1 = torch.rand(4, 3, 6, 3, generator=torch.Generator().manual_seed(2)) < 0.2
+    aabb1 = aabb * 0.8
+    m0, m1 = rodynrf.AlphaGridMask(DEV, aabb, vol0.float(), 3), rodynrf.AlphaGridMask(DEV, aabb1, vol1.float(), 3)
+    N, S = 3, 68   # 204 samples: not a multiple of 64
+    xyz = torch.from_numpy(g["xyz"]).view(N, S, 3).to(DEV)
+    ts = torch.tensor([-0.5, 0.3, 1.0], device=DEV)
+    valid = torch.rand(N, S, generator=torch.Generator().manual_seed(1)) < 0.8
+    tt = ts.cpu().numpy().repeat(S)
+    k0 = A.sample_alpha(vol0.numpy(), aabb.numpy(), g["xyz"], tt) > 0
+    k1 = A.sample_alpha(vol1.numpy(), aabb1.numpy(), g["xyz"], tt) > 0
+    assert (k0 != k1).sum() > 20
+    v = valid.to(DEV)
+    both = rodynrf.apply_alpha_mask(v, xyz, ts, m0, m1)
+    assert both.dtype == torch.bool and torch.equal(v.cpu(), valid)   # the input is not written
+    assert np.array_equal(both.cpu().numpy().reshape(-1), valid.numpy().reshape(-1) & (k0 | k1))
+    assert np.array_equal(rodynrf.apply_alpha_mask(v, xyz, ts, m0).cpu().numpy().reshape(-1), valid.numpy().reshape(-1) & k0)
+    assert np.array_equal(rodynrf.apply_alpha_mask(v, xyz, ts, None, m1).cpu().numpy().reshape(-1), valid.numpy().reshape(-1) & k1)
+    assert rodynrf.apply_alpha_mask(v, xyz, ts) is v
+
+
+def test_checkpoint_keys(tmp_path):
+    import rodynrf
+    g = _fixture()
+    ckpt = torch.load(os.path.join(GOLDEN, "alpha_mask_ckpt.th"), map_location="cpu", weights_only=False)
+    kw = dict(ckpt["kwargs"])
+    kw.pop("se3_poses"), kw.pop("focal_ratio_refine")
+    st = rodynrf.TensorVMSplit(device=DEV, **kw)
+    st.load(ckpt)                                                        # the reference-written file
+    m = st.alphaMask
+    assert m is not None and m.tSize == 3 and m.gridSize.tolist() == [7, 6, 5]
+    assert np.array_equal(m.packed.cpu().numpy(), g["ckpt.mask"])
+    xyz, t = torch.from_numpy(g["xyz"]).to(DEV), torch.from_numpy(g["t"]).to(DEV)
+    assert float((m.sample_alpha(xyz, t).cpu() - torch.from_numpy(g["alpha"])).abs().max()) <= 1e-6
+    path = str(tmp_path / "a.th")
+    st.save(ckpt["kwargs"]["se3_poses"], ckpt["kwargs"]["focal_ratio_refine"], path)
+    back = torch.load(path, map_location="cpu", weights_only=False)
+    assert tuple(back["alphaMask.shape"]) == tuple(ckpt["alphaMask.shape"]) == (1, 1, 5, 6, 7, 3)
+    assert isinstance(back["alphaMask.mask"], np.ndarray) and back["alphaMask.mask"].dtype == np.uint8
+    assert back["alphaMask.mask"].tobytes() == np.asarray(ckpt["alphaMask.mask"]).tobytes()      # byte for byte
+    assert torch.equal(back["alphaMask.aabb"], ckpt["alphaMask.aabb"])
+    st2 = rodynrf.TensorVMSplit(device=DEV, **kw)
+    st2.load(back)
+    assert torch.equal(st2.alphaMask.packed, m.packed)
+    for k, v in st.state_dict().items():
+        assert torch.equal(v, st2.state_dict()[k]), k
+    # a checkpoint without a mask loads as before
+    st2.alphaMask = None
+    st2.save(None, None, path)
+    plain = torch.load(path, map_location="cpu", weights_only=False)
+    assert not any(k.startswith("alphaMask") for k in plain)
+    st3 = rodynrf.TensorVMSplit(device=DEV, **kw)
+    st3.load(plain)
+    assert st3.alphaMask is None
+
+
+@pytest.mark.parametrize("which", ["static", "dynamic"])
+def test_update_alpha_mask_and_filtering_rays(which):
+    field = fields("relu")[which == "dynamic"]
+    lat = (9, 11, 7)
+    old = field.alphaMask_thres
+    try:
+        alpha, dense = field.getDenseAlpha(lat)
+        field.alphaMask_thres = float(alpha.flatten().kthvalue(int(alpha.numel() * 0.995)).values)   # ~0.5 % of the lattice above: the pooled grid stays sparse
+        new_aabb = field.updateAlphaMask(lat)
+        occ = A.pool_threshold(alpha.cpu().numpy(), field.alphaMask_thres)
+        st = A.stats(occ)
+        m = field.alphaMask
+        assert 0 < st[0] < occ.size and m.tSize == T and m.gridSize.tolist() == list(lat)
+        assert np.array_equal(m.packed.cpu().numpy(), A.pack(occ))
+        assert torch.equal(m.alpha_volume[0, 0].cpu(), torch.from_numpy(occ).float())
+        assert torch.equal(new_aabb, torch.stack((dense[st[1], st[2], st[3]], dense[st[4], st[5], st[6]])))
+        assert bool((new_aabb[0] >= field.aabb[0]).all()) and bool((new_aabb[1] <= field.aabb[1]).all())
+        # rays from outside towards the box, some missing it
+        g = torch.Generator().manual_seed(12)
+        N = 150
+        o = torch.randn(N, 3, generator=g)
+        o = o / o.norm(dim=-1, keepdim=True) * 4.0
+        d = -o + torch.randn(N, 3, generator=g) * 1.2
+        d = d / d.norm(dim=-1, keepdim=True)
+        rays, rgbs = torch.cat([o, d], -1), torch.rand(N, 3, generator=g)
+        ts = torch.tensor([-1.0, 0.0, 1.0])[torch.randint(0, 3, (N,), generator=g)]
+        nf = field.near_far
+        field.near_far = [0.5, 8.0]
+        r, c = field.filtering_rays(rays, rgbs, bbox_only=True, chunk=64)
+        want = A.bbox_filter(AABB, rays)
+        assert 0 < int(want.sum()) < N and torch.equal(r, rays[want]) and torch.equal(c, rgbs[want])
+        S = 40
+        r, c, tk = field.filtering_rays(rays, rgbs, ts, N_samples=S, chunk=64)
+        xyz, _, _ = field.sample_ray(rays[:, :3].to(DEV), rays[:, 3:].to(DEV), is_train=False, N_samples=S)
+        val = A.sample_alpha(occ, AABB.numpy(), xyz.cpu().numpy().reshape(-1, 3), ts.numpy().repeat(S)).reshape(N, S)
+        want = torch.from_numpy((val > 0).any(-1))
+        assert 0 < int(want.sum()) < N
+        assert torch.equal(r, rays[want]) and torch.equal(c, rgbs[want]) and torch.equal(tk, ts[want])
+        field.near_far = nf
+    finally:
+        field.alphaMask_thres = old
+        field.alphaMask = None
+
+
+def det_case():
+    """the compute_alpha case both libraries run (tests/_alpha_det_child.py)"""
+    from importlib import import_module
+    alpha_mod = import_module("robust-dynrf_amd.alpha")
+    out = {}
+    for which in (0, 1):
+        field = fields("softplus")[which]
+        a, s = alpha_mod.alpha_volume(field, points(65, 77), torch.tensor([-1.0, 0.0, 1.0], device=DEV), LENGTH, want_sigma=True)
+        out[f"alpha{which}"], out[f"sigma{which}"] = a, s
+    return out
+
+
+def test_deterministic_library_computes_the_same_alpha(tmp_path):
+    mine = det_case()
+    env = dict(os.environ, RDRF_DETERMINISTIC="1")
+    env.pop("RDRF_MARGINS", None)
+    env.pop("RDRF_LIB", None)
+    out = str(tmp_path / "det.pt")
+    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_alpha_det_child.py")
+    r = subprocess.run([sys.executable, child, out], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    det = torch.load(out)
+    for k, v in mine.items():
+        assert torch.equal(v.cpu(), det[k]), k
