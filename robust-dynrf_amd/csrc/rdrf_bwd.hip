@@ -17,9 +17,6 @@
 // rdrf_misc.hip beside its forward, the deterministic build's bind / finish in rdrf_det.hip.
 // References: autograd of /root/reference/models/tensorBase.py:704-850, models/tensoRF.py:118-196,
 // 446-462, 521-811 (grid_sample backward per SURVEY.md Appendix A).
-#ifdef RDRF_GROWS_TEMPORAL   // A/B: the gradient rows this file's kernels write (read back by k_dw3 within the pass) with plain stores
-#define RDRF_SAVE_TEMPORAL
-#endif
 #include "rdrf_bwd_dev.hpp"
 #include "rdrf_bwd_host.hpp"
 
@@ -1115,8 +1112,7 @@ static void fill_bwd_common(BwdArgs& a, const RdrfFieldCfg* cfg, const float* ra
   a.distance_scale = cfg->distance_scale; a.weight_thres = cfg->weight_thres;
   a.density_shift = cfg->density_shift; a.act = cfg->act; a.ray_type = cfg->ray_type;
   a.static_head = cfg->static_head;
-  static const int dynq = RDRF_ENV("RDRF_DYNQ") ? atoi(RDRF_ENV("RDRF_DYNQ")) : 1;   // 0: static tile stride (tools build)
-  a.dynq = dynq;
+  a.dynq = 1;   // per-workgroup tile queue (tile_queue_next)
 }
 
 // forward calls (either field, scene flow): pack area + counter + tout + xw + list -- what an inference-only caller needs
@@ -1185,7 +1181,7 @@ void add_density_phase_dw(DwJobs& D, const float* grows1, const float* act1, con
   }
   // small layers share one dz block: rows 0..2 -> layer5, row 3 -> density_layer2, row 4 -> blending_layer2.
   // On the ray path k_dyn_density_bwd forms these gradients itself (reduce_scatter32): as MFMA products they were 6 of
-  // the 40 per tile, 27 of 32 rows empty, and the 12 waves of k_dw2 take 34 products in 3 rounds instead of 4
+  // the 40 per tile, 27 of 32 rows empty, and the 12 waves of the dW kernel take 34 products in 3 rounds instead of 4
   if (!small_in_kernel) {
   dw_add(D, grows1, sv::K1G_ROWS, sv::K1G_SM, 1, 3, 0, act1, sv::K1_ROWS, 64, 64, G->l5w, G->l5b, nullptr, T1);
   dw_blk(D, sv::K1_H4, SEG_IDENT, 0);
@@ -1384,8 +1380,7 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
   fill_bwd_common(a, cfg, rays, ts, xyz, z, valid, N, S);
   a.g_rgb = g_rgb; a.g_sigma = g_sigma; a.g_weight = g_weight; a.g_blending = g_blending;
   a.g_xyz_prime = g_xyz_prime; a.g_xyz = g_xyz; a.g_rays = g_rays; a.g_dists = g_dists; a.g_z = g_z;
-  static const bool small_dw = !(RDRF_ENV("RDRF_DW_SMALL") && atoi(RDRF_ENV("RDRF_DW_SMALL")) == 0);   // 0: as k_dw2 products (tools build)
-  a.small_dw = small_dw ? 1 : 0;
+  a.small_dw = 1;
   // a buffer the forward filled under RDRF_SAVE_NO_APP has no appearance rows (a prefix of the full layout): told apart by its
   // size, on the host, before anything is launched
   const int saved_kind = carve_saved_bwd(a.sp, saved, saved_bytes, 1, N, S);

@@ -2,14 +2,8 @@
 // gradient-scatter kernels (rdrf_scatter.hip): the backward LDS images, the argument block of the backward kernels, the
 // small-layer / reduce-scatter helpers of the backward-data kernels, the sample-major d(feature) records, and the VM gather
 // backward per quad (run reduction in DPP, LDS line accumulators, plane windows).
-// A unit whose kernels write gradient rows maps RDRF_GROWS_TEMPORAL to RDRF_SAVE_TEMPORAL before it includes this header.
 #pragma once
 #include "rdrf_kernels.hpp"
-#ifdef RDRF_NO_BIAS_ATOMICS
-#define BIAS_ATOMIC(p, v) ((void)0)
-#else
-#define BIAS_ATOMIC(p, v) grad_add(p, v)
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // backward LDS images (transposed packs + small layers), float offsets inside each region
@@ -191,7 +185,7 @@ RDRF_D void acc_zero(f32x16 (&acc)[NB]) {
 // Reduce-scatter over the 32 lanes of a half-wave: on return lane s holds the sum over the half's 32 lanes of p[s]
 // (five butterfly stages: 31 lane exchanges + 31 adds).  Used for the weight gradients of the 3- and 1-row layers of the
 // density phase (layer5, density / blending layer2): dW[e] = sum over the tile's samples of dz(sample) * in_e(sample),
-// with dz a per-lane scalar and in_e the 32 slots the lane already holds -- as MFMA products in k_dw2 these were 6 of
+// with dz a per-lane scalar and in_e the 32 slots the lane already holds -- as MFMA products of the dW kernel these were 6 of
 // the 40 per tile, each 27/32 empty.  ALL lanes of the wave must call.
 RDRF_D float reduce_scatter32(const float (&p)[32], int s) {
   const bool b4 = s & 16, b3 = s & 8, b2 = s & 4, b1 = s & 2, b0 = s & 1;
@@ -245,9 +239,6 @@ RDRF_D void atomic_quad_k(float* base, unsigned off, float val, int c) {
   if (o != 0xffffffffu) grad_add(base + (size_t)o + c, val);
 }
 RDRF_D void atomic_add4(float* p_base, size_t p_off, f32x4 v, bool ok) {
-#if defined(RDRF_ABL_NOATOM) || defined(RDRF_ABL_NOGLOBAL)
-  return;
-#endif
   if (__ballot(ok) == 0ull) return;
   const int lane = threadIdx.x, c = lane & 3;
   const bool a = lane & 1, b = lane & 2;
@@ -289,9 +280,6 @@ RDRF_D Run run_of(int key, int s) {
 // inside each 16-lane row, then lane 15's row total is added to the lanes of the next row whose
 // run started at or before lane 15 (row_bcast:15, written to rows 1 and 3 only).
 RDRF_D f32x4 run_scan4(f32x4 v, int start, int s) {
-#ifdef RDRF_ABL_NOSCAN
-  return v;
-#endif
   const int sr = s & 15;
 #define RDRF_SCAN_STEP(D)                                                                   \
   {                                                                                         \
@@ -354,9 +342,6 @@ RDRF_D void lds_quad_k(float* base, int f64, int addr, float val, int c) {
 }
 // all lanes of the wave must call; `addr` = ELEMENT offset of the lane's quad inside the accumulator `ll`
 RDRF_D void lds_add4(const LdsLines& ll, int addr, f32x4 v, bool ok) {
-#if defined(RDRF_ABL_NOATOM) || defined(RDRF_ABL_NOLDS)
-  return;
-#endif
   if (__ballot(ok) == 0ull) return;
   const int lane = threadIdx.x, c = lane & 3;
   const bool a = lane & 1, b = lane & 2;
@@ -439,9 +424,6 @@ template <int C0Q, int C1Q, int MODE>
 RDRF_D void gather_quad_bwd(const RdrfVM& vm, const RdrfVM& gvm, int g, float x0, float x1,
                             float x2, f32x4 dq, bool live, int s, float& dx0, float& dx1,
                             float& dx2, const LdsLines ll = LdsLines{nullptr, {0, 0, 0}, 0, 0}) {
-#ifdef RDRF_ABL_NOGBWD
-  dx0 += dq.x; return;
-#endif
   QuadSel<C0Q, C1Q> sl = quad_sel<C0Q, C1Q>(g);
   const int pi = sl.pi;
   const float cx = pi == 2 ? x1 : x0;

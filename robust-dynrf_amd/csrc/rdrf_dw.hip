@@ -2,7 +2,7 @@
 // The backward-data kernels (rdrf_bwd.hip) wrote every dz as rows of 32 samples and the forward saved the layer inputs
 // in the same layout ([tile][row][32 samples], rdrf_kernels.hpp namespace sv): a lane reads 64 contiguous bytes of a row
 // (16 samples) straight into its operand registers, so nothing is transposed.  The entry points describe their products
-// as jobs (dw_add / dw_blk); dw_launch plans them into launches of k_dw3 (k_dw2: its A/B partner in the tools build).
+// as jobs (dw_add / dw_blk); dw_launch plans them into launches of k_dw3.
 // Host interface: rdrf_bwd_host.hpp.
 //
 // ROW CONTRACT.  k_dw3 multiplies whole 32-sample tiles: it knows no sample mask.  In every sample slot of every tile it walks,
@@ -45,15 +45,11 @@ void dw_blk(DwJobs& D, int row0, int seg, int e0) {
   j.nblk++;
 }
 // ------------------------------------------------------------------------------------------------
-// cooperative dW kernel (k_dw2).  k_dw above gives every (out-block, in-group) item its own wave and its
-// own copy of the rows it needs: a density-phase tile is requested 55 blocks at a time for 27 unique ones,
-// and each wave's 20 KB stage is written and read once per item.  Here ONE 8-wave workgroup owns a tile:
-// it stages every unique 32-row block of the tile in LDS once (27 x 4 KB = 108 KB for the density phase,
-// 30 for the appearance phases), then its waves form all (dz block) x (input block) products of all the
-// jobs from that stage -- 5 or 6 products per wave, accumulators resident for the whole launch.  The
-// global loads of the next tile are issued right after the stage is written (into registers: 14 x 16 B
-// per thread) and land while the MFMAs of the current tile run.  Per tile and CU: 108 KB of HBM traffic
-// (was ~220 KB of L2 traffic), 640 MFMAs spread over the four SIMDs.
+// cooperative dW plan (Dw2Plan; the names keep the spelling of the first kernel that ran it).  ONE 12-wave workgroup owns a
+// tile: it stages every unique 32-row block of the tile in LDS once (27 blocks for the density phase, 30 for the appearance
+// phases -- a density-phase tile would be requested 55 blocks at a time if every product fetched its own operands), then its
+// waves form all (dz block) x (input block) products of all the jobs from that stage -- up to DW2_MAX_PROD products per wave,
+// accumulators resident for the whole launch.  The rows of the next step are in flight while the MFMAs of the current one run.
 // ------------------------------------------------------------------------------------------------
 #define DW2_MAX_BLK 30
 #define DW2_MAX_PROD 4
@@ -73,7 +69,7 @@ struct Dw2Plan {
                                     // wave-uniform, so these are SCALAR loads (lgkmcnt); byte / short fields
                                     // compile to vector loads whose vmcnt(0) waits drain the data loads in flight
   // the staged blocks, sorted by (source, first row), form at most DW2_MAX_SEG runs of consecutive rows: a run
-  // is ONE contiguous byte range per tile, so a slot's address needs no per-block metadata (see k_dw2)
+  // is ONE contiguous byte range per tile, so a slot's address needs no per-block metadata (see k_dw3)
   int nseg;
   int seg_blk0[DW2_MAX_SEG];          // first staged block of the run
   int seg_src[DW2_MAX_SEG];           // 0 = A, 1 = B
@@ -85,159 +81,19 @@ struct Dw2Plan {
   DwJob job[RDRF_MAX_DW_JOBS];
 };
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#ifdef RDRF_TOOLS   // k_dw2 is the A/B partner of k_dw3 (RDRF_DW3=0) in the tools build; the product launches k_dw3 only
-__global__ __launch_bounds__(64 * DW2_WAVES) void k_dw2(Dw2Plan P) {
-  extern __shared__ __attribute__((aligned(16))) f32x4 dw2_stage[];   // nblk x 256 float4, XOR-swizzled per block
-  const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, li = lane & 31;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: indexes the plan in the kernel arguments
-  const int ntiles = P.count ? ((*P.count + 31) >> 5) : P.ntiles;
-  const int nf4 = P.nblk * 256;
-  constexpr int NT = 64 * DW2_WAVES, NPF = (DW2_MAX_BLK * 256 + NT - 1) / NT;
-  // this thread's slots of the tile image: float4 index i*NT + tid -> (block, row, 16-byte chunk)
-  f32x4 pf[NPF];
-  // Slot i of this thread is float4 number idx = i*NT + tid of the tile image; its staged block idx >> 8 is
-  // wave-uniform.  The blocks are sorted so that they form <= DW2_MAX_SEG runs of consecutive rows, each run one
-  // contiguous range of a tile: the address is (run base of this tile, scalar) + idx*16 bytes, selected with
-  // scalar compares.  (Looking the block up in the plan inside the loop cost two dependent scalar loads + waits
-  // in front of each of the 10 global loads: 2-4 thousand cycles per tile in which the wave issued no MFMA.)
-  static_assert(DW2_MAX_SEG == 2, "segment select below");
-  // every plan of this path is [dz rows 0..nA) | activation rows 0..nB): two runs (checked on the host)
-  const int sb1 = P.nseg > 1 ? P.seg_blk0[1] : 1 << 20;
-  const int s1 = P.nseg > 1 ? 1 : 0;
-  const float* seg0a = (P.seg_src[0] ? P.B : P.A) + (size_t)P.seg_row0[0] * 32;
-  const float* seg0b = (P.seg_src[s1] ? P.B : P.A) + (size_t)P.seg_row0[s1] * 32 - (size_t)P.seg_blk0[s1] * 1024;
-  const size_t st0 = (size_t)(P.seg_src[0] ? P.B_stride : P.A_stride) * 32,
-               st1 = (size_t)(P.seg_src[s1] ? P.B_stride : P.A_stride) * 32;
-  static_assert(NT == 768, "a slot is three 256-float4 blocks: slot i of wave w holds block 3*i + (w >> 2)");
-  const int wgrp = wave >> 2;   // scalar
-  const int voffb = tid * 16;   // the only per-thread part of an address
-  // Buffer loads: descriptor (scalar, rebuilt per tile from the run's tile base) + voffb + a per-slot scalar
-  // offset.  No vector address temporaries: with 64-bit flat addresses the compiler built them in the prefetch
-  // registers themselves and its waitcnt pass then put `s_waitcnt vmcnt(0)` in front of every load of the batch.
-  auto gload = [&](int t) {
-    const float* g0 = seg0a + (size_t)t * st0;
-    const float* g1 = seg0b + (size_t)t * st1;
-    const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc((void*)g0, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc((void*)g1, 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-    for (int i = 0; i < NPF; ++i) {
-      const int blk = 3 * i + wgrp;          // wave-uniform: uniform branches
-      if (blk < P.nblk) {
-#ifndef RDRF_ABL_DW_NOLOAD
-        u32x4 v;
-        if (blk < sb1) v = __builtin_amdgcn_raw_buffer_load_b128(r0, voffb, i * (NT * 16), 0);
-        else v = __builtin_amdgcn_raw_buffer_load_b128(r1, voffb, i * (NT * 16), 0);
-        pf[i] = __builtin_bit_cast(f32x4, v);
-#else
-        pf[i] = f32x4{(float)t, 1.f, 2.f, (float)i};
-#endif
-      }
-    }
-  };
-  int rpos[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) rpos[q] = li * 8 + ((4 * h + q) ^ ((li >> 1) & 7));
-  const int np = P.nprod[wave];
-  int pa[DW2_MAX_PROD], pb[DW2_MAX_PROD];   // staged block offsets of each product, bias flag in bit 30 of pa (scalars)
-#pragma unroll
-  for (int p = 0; p < DW2_MAX_PROD; ++p) {
-    pa[p] = __builtin_amdgcn_readfirstlane(P.prod[wave][p].a * 256 | (P.prod[wave][p].bias << 30));
-    pb[p] = __builtin_amdgcn_readfirstlane(P.prod[wave][p].b * 256);
-  }
-  f32x16 acc[DW2_MAX_PROD];
-  float bsum[DW2_MAX_PROD];
-#pragma unroll
-  for (int p = 0; p < DW2_MAX_PROD; ++p) {
-    bsum[p] = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[p][r] = 0.f;
-  }
-  int t = blockIdx.x;
-  if (t < ntiles) gload(t);
-  while (t < ntiles) {
-    __syncthreads();   // every wave is done reading the previous tile
-#pragma unroll
-    for (int i = 0; i < NPF; ++i) {
-      if (3 * i + wgrp < P.nblk) {   // uniform
-        const int idx = i * NT + tid;
-        const int blk = idx >> 8, w = idx & 255, row = w >> 3;
-        dw2_stage[blk * 256 + row * 8 + ((w & 7) ^ ((row >> 1) & 7))] = pf[i];
-      }
-    }
-    __syncthreads();
-    const int tn = t + gridDim.x;
-    if (tn < ntiles) gload(tn);   // lands while the MFMAs below run
-#ifndef RDRF_ABL_DW_NOMFMA
-#pragma unroll
-    for (int p = 0; p < DW2_MAX_PROD; ++p) {
-      if (p < np) {
-        int oa = pa[p] & 0xffffff, ob = pb[p];
-        // (opaque to the optimiser: with loop-invariant offsets it hoists all 32 LDS read addresses of the
-        // four products out of the tile loop and spills them -- reloads whose vmcnt(0) drain the prefetch)
-        asm volatile("" : "+s"(oa), "+s"(ob));
-        const f32x4* sa = dw2_stage + oa;
-        const f32x4* sb = dw2_stage + ob;
-        f32x4 av4[4], bv4[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { av4[q] = sa[rpos[q]]; bv4[q] = sb[rpos[q]]; }
-        if (pa[p] >> 30) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) bsum[p] += av4[q].x + av4[q].y + av4[q].z + av4[q].w;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av4[q].x, bv4[q].x, acc[p], 0, 0, 0);
-          acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av4[q].y, bv4[q].y, acc[p], 0, 0, 0);
-          acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av4[q].z, bv4[q].z, acc[p], 0, 0, 0);
-          acc[p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av4[q].w, bv4[q].w, acc[p], 0, 0, 0);
-        }
-      }
-    }
-#else
-    if (np > 0) acc[0][0] += dw2_stage[tid & 255].x;   // keep the stage alive
-#endif
-    t = tn;
-  }
-  // write-out: C row i = (rr&3) + 8*(rr>>2) + 4*h (out neuron), column = li (input element)
-#ifdef RDRF_ABL_DW_NOFLUSH
-  if (ntiles >= 0) return;
-#endif
-#pragma unroll
-  for (int p = 0; p < DW2_MAX_PROD; ++p) {
-    if (p < np) {
-      const Dw2Prod pr = P.prod[wave][p];
-      const DwJob& J = P.job[pr.job];
-      const int col = seg_imap(J.blk_seg[pr.k], J.blk_e0[pr.k] + li, J.in_dim);
-#pragma unroll
-      for (int rr = 0; rr < 16; ++rr) {
-        const int orow = pr.bo * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * h - J.out_row0;
-        if (col >= 0 && orow >= 0 && orow < J.out_dim) grad_add(J.dW + (size_t)orow * J.ld + col, acc[p][rr]);
-      }
-      if (pr.bias && J.db != nullptr) {
-        const float b = bsum[p] + __shfl_xor(bsum[p], 32, 64);
-        const int orow = pr.bo * 32 + li - J.out_row0;
-        if (h == 0 && orow >= 0 && orow < J.out_dim) grad_add(J.db + orow, b);
-      }
-    }
-  }
-}
-
-#endif   // RDRF_TOOLS (k_dw2)
-
 // ------------------------------------------------------------------------------------------------
-// k_dw3 (round 6): the same plan as k_dw2 on HALF stages with LDS-DMA.  k_dw2 stages a whole tile
-// (32 samples x all rows, 108-120 KB of the 160 KB LDS) through registers: barrier, ten ds_write_b128 per thread, barrier, the
-// products -- the matrix pipes wait during the write pass and both barriers (3 x (64 MFMA + 4 VALU cycles) account for 0.66
-// of its wave cycles), and nothing can be double-buffered.  Here a stage is 16 samples x all rows (64 bytes of every row,
-// 54-60 KB), there are two of them, and `buffer_load_dwordx4 ... lds` moves a half stage straight from HBM into the buffer
-// that is not being read: step s = barrier; issue the DMA of step s + 1; the products of step s (8 MFMAs each, K = 16
-// samples).  One barrier per half stage, no staging registers, no LDS write instructions.
+// k_dw3 (round 6): the plan above on HALF stages with LDS-DMA.  A stage is 16 samples x all rows (64 bytes of
+// every row, 54-60 KB), there are two of them, and `buffer_load_dwordx4 ... lds` moves a half stage straight from HBM into the
+// buffer that is not being read: step s = barrier; issue the DMA of step s + 1; the products of step s (8 MFMAs each, K = 16
+// samples).  One barrier per half stage, no staging registers, no LDS write instructions.  Its predecessor k_dw2 (removed)
+// staged a whole tile (32 samples x all rows, 108-120 KB of the 160 KB LDS) through registers: barrier, ten ds_write_b128 per
+// thread, barrier, the products -- the matrix pipes waited during the write pass and both barriers (3 x (64 MFMA + 4 VALU cycles)
+// accounted for 0.66 of its wave cycles), and nothing could be double-buffered.
 // Measured (profiles/r06_ab_dw3_*.txt): dw launches 2.02 -> 1.91 ms/step at stage 0, 4.40 -> 4.10 at the final stage.  Ablations:
 // MFMAs + barriers alone 1.05 ms (dw_dyn, stage 0), DMA + barriers alone 1.29 -- the memory side binds, and NOT through its
 // latency: a ring of 80 block slots that keeps two half stages in flight (counted vmcnt, raw s_barrier) left the DMA-only time
 // at 1.30 ms and made the kernel slower (1.56).  Nor through the 64-byte half rows: the same bytes fetched as full 128-byte
-// rows (RDRF_ABL_DW_FULLROW, wrong arithmetic, timing only: profiles/r06_ab_dw3_fullrow_timing.txt) take 1.18 instead of 1.25 ms
+// rows (wrong arithmetic, timing only: profiles/r06_ab_dw3_fullrow_timing.txt) take 1.18 instead of 1.25 ms
 // DMA-only and 1.43 instead of 1.47 ms in the whole kernel.  What is left is the per-step bubble of a 12-wave workgroup:
 // vmcnt(0) -> barrier -> ~5 DMA issues per wave, during which this CU has nothing in flight (~0.5 of each 2.7 us step).
 //   LDS image of a block (32 rows x 16 samples = 2 KB): float4 position p = row * 4 + (chunk ^ ((row >> 2) & 3)); a DMA
@@ -245,9 +101,6 @@ __global__ __launch_bounds__(64 * DW2_WAVES) void k_dw2(Dw2Plan P) {
 //   address of lane l (row = 16 sub + (l >> 2), chunk = (l & 3) ^ ((row >> 2) & 3)) and on the read (cdna guide, rule 21);
 //   the 16 lanes of a ds_read_b128 group then cover all 64 banks.
 // ------------------------------------------------------------------------------------------------
-#ifndef RDRF_DW_AUX
-#define RDRF_DW_AUX 0   // cache policy of the row DMA (2 = nt on gfx950: the rows are read once)
-#endif
 __global__ __launch_bounds__(64 * DW2_WAVES) void k_dw3(Dw2Plan P) {
   extern __shared__ __attribute__((aligned(16))) f32x4 dw3_stage[];   // 2 buffers x nblk x 128 float4
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, li = lane & 31;
@@ -268,9 +121,6 @@ __global__ __launch_bounds__(64 * DW2_WAVES) void k_dw3(Dw2Plan P) {
   const unsigned voff = (unsigned)(prow_ * 128 + (((lane & 3) ^ ((prow_ >> 2) & 3)) << 4));
   const int hbuf = P.nblk * 128;   // float4 per buffer
   auto dma = [&](int t, int hf, int buf) {
-#ifdef RDRF_DW_REV   // A/B: walk the tiles newest first (the rows the backward-data kernels touched last)
-    t = ntiles - 1 - t;
-#endif
     const float* g0 = seg0a + (size_t)t * st0;
     const float* g1 = seg0b + (size_t)t * st1;
     const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc((void*)g0, 0, 0x7fffffff, 0x00020000);
@@ -279,20 +129,11 @@ __global__ __launch_bounds__(64 * DW2_WAVES) void k_dw3(Dw2Plan P) {
     for (int i = 0; i < NPW; ++i) {
       const int pc = wave + DW2_WAVES * i;   // wave-uniform
       if (pc < npieces) {
-#ifndef RDRF_ABL_DW_NOLOAD
         const int blk = pc >> 1;
         __attribute__((address_space(3))) void* dst = (__attribute__((address_space(3))) void*)(dw3_stage + buf * hbuf + pc * 64);
-#ifdef RDRF_ABL_DW_FULLROW   // timing experiment (tools): the same bytes as FULL 128-byte rows (rows 16 hf .. 16 hf + 15 of the block,
-        const unsigned soff = (unsigned)(blk * 4096 + hf * 2048 + (pc & 1) * 1024);   // 1 KB contiguous per piece); WRONG results
-        const unsigned vo = (unsigned)(lane * 16);
-        if (blk < sb1) __builtin_amdgcn_raw_ptr_buffer_load_lds(r0, dst, 16, vo, soff, 0, 0);
-        else __builtin_amdgcn_raw_ptr_buffer_load_lds(r1, dst, 16, vo, soff, 0, 0);
-#else
         const unsigned soff = (unsigned)(blk * 4096 + hf * 64);
-        if (blk < sb1) __builtin_amdgcn_raw_ptr_buffer_load_lds(r0, dst, 16, voff, soff, 0, RDRF_DW_AUX);
-        else __builtin_amdgcn_raw_ptr_buffer_load_lds(r1, dst, 16, voff, soff, 0, RDRF_DW_AUX);
-#endif
-#endif
+        if (blk < sb1) __builtin_amdgcn_raw_ptr_buffer_load_lds(r0, dst, 16, voff, soff, 0, 0);
+        else __builtin_amdgcn_raw_ptr_buffer_load_lds(r1, dst, 16, voff, soff, 0, 0);
       }
     }
   };
@@ -325,13 +166,14 @@ __global__ __launch_bounds__(64 * DW2_WAVES) void k_dw3(Dw2Plan P) {
     if (hf) tn = t + gridDim.x;
     if (tn < ntiles) dma(tn, hn, buf ^ 1);   // lands while the MFMAs below run
     __builtin_amdgcn_sched_barrier(0);       // (issued BEFORE the products: hipcc is free to sink it below them otherwise)
-#ifndef RDRF_ABL_DW_NOMFMA
     const f32x4* stage = dw3_stage + buf * hbuf;
 #pragma unroll
     for (int p = 0; p < DW2_MAX_PROD; ++p) {
       if (p < np) {
         int oa = pa[p] & 0xffffff, ob = pb[p];
-        asm volatile("" : "+s"(oa), "+s"(ob));   // (as in k_dw2: keeps the read addresses out of the loop-invariant hoist)
+        // (opaque to the optimiser: with loop-invariant offsets it hoists the LDS read addresses of the four products out of
+        // the tile loop and spills them -- reloads whose vmcnt(0) drain the DMA in flight)
+        asm volatile("" : "+s"(oa), "+s"(ob));
         const f32x4* sa = stage + oa;
         const f32x4* sb = stage + ob;
         f32x4 av4[2], bv4[2];
@@ -350,14 +192,8 @@ __global__ __launch_bounds__(64 * DW2_WAVES) void k_dw3(Dw2Plan P) {
         }
       }
     }
-#else
-    if (np > 0) acc[0][0] += dw3_stage[buf * hbuf + (tid & 127)].x;
-#endif
     t = tn; hf = hn; buf ^= 1;
   }
-#ifdef RDRF_ABL_DW_NOFLUSH
-  if (ntiles >= 0) return;
-#endif
 #pragma unroll
   for (int p = 0; p < DW2_MAX_PROD; ++p) {
     if (p < np) {
@@ -431,32 +267,13 @@ int dw_launch(DwJobs& D, hipStream_t stream, const char* name) {
           }
         }
       }
-      if (RDRF_ENV("RDRF_DW_DEBUG")) {
-        fprintf(stderr, "dw plan %s: nblk %d products %d segs", name, P.nblk, tot);
-        for (int g = 0; g < P.nseg; ++g) {
-          const int end = g + 1 < P.nseg ? P.seg_blk0[g + 1] : P.nblk;
-          fprintf(stderr, " [%c rows %d..%d]", P.seg_src[g] ? 'B' : 'A', P.seg_row0[g], P.seg_row0[g] + 32 * (end - P.seg_blk0[g]) - 1);
-        }
-        fprintf(stderr, " strides A %d B %d\n", P.A_stride, P.B_stride);
-      }
-      const size_t lds = (size_t)P.nblk * 4096;   // two half stages of nblk x 2 KB (k_dw2: one whole stage of nblk x 4 KB)
+      const size_t lds = (size_t)P.nblk * 4096;   // two half stages of nblk x 2 KB
       int grid = 256;
       if (P.count == nullptr && P.ntiles < grid) grid = P.ntiles < 1 ? 1 : P.ntiles;
-#ifdef RDRF_TOOLS
-      static const int dw3 = RDRF_ENV("RDRF_DW3") ? atoi(RDRF_ENV("RDRF_DW3")) : 1;   // 0: k_dw2
-      if (lds > 48 * 1024) {
-        if (dw3) RDRF_HIP(hipFuncSetAttribute((const void*)k_dw3, hipFuncAttributeMaxDynamicSharedMemorySize, DW2_MAX_BLK * 4096));
-        else RDRF_HIP(hipFuncSetAttribute((const void*)k_dw2, hipFuncAttributeMaxDynamicSharedMemorySize, DW2_MAX_BLK * 4096));
-      }
-      rdrf_prof_begin(name, stream);
-      if (dw3) hipLaunchKernelGGL(k_dw3, dim3(grid), dim3(64 * DW2_WAVES), lds, stream, P);
-      else hipLaunchKernelGGL(k_dw2, dim3(grid), dim3(64 * DW2_WAVES), lds, stream, P);
-#else
       if (lds > 48 * 1024)
         RDRF_HIP(hipFuncSetAttribute((const void*)k_dw3, hipFuncAttributeMaxDynamicSharedMemorySize, DW2_MAX_BLK * 4096));
       rdrf_prof_begin(name, stream);
       hipLaunchKernelGGL(k_dw3, dim3(grid), dim3(64 * DW2_WAVES), lds, stream, P);
-#endif
       rdrf_prof_end(name, stream);
       RDRF_HIP(hipGetLastError());
       return 0;

@@ -10,9 +10,15 @@
 
 void rdrf_set_error(const char* fmt, ...);
 
-// A/B switches of tools/ab_*.sh and tools/abl_*.sh.  The product library never reads the caller's environment: a C-ABI
-// call's behaviour depends on its arguments (and on explicit rdrf_set_* calls) only.  `make tools` builds
-// librodynrf_tools.so with -DRDRF_TOOLS, where these lookups and the RDRF_ABL_* ablation blocks are live.
+// Environment switches.  The product library never reads the caller's environment: a C-ABI call's behaviour depends on its
+// arguments (and on explicit rdrf_set_* calls) only.  `make tools` builds librodynrf_tools.so with -DRDRF_TOOLS, where
+// RDRF_ENV is getenv and three switches select the earlier, independent implementation of a phase for the GPU tests that
+// compare the two:
+//   RDRF_FLAT=0        wave-per-ray density kernels                              (tests/test_gpu_flat_density.py)
+//   RDRF_SF_FUSED=0    k_scene_flow_bwd + dw_sf                                  (tests/test_gpu_scene_flow_fused.py)
+//   RDRF_WARP_FUSED=0  k_dyn_density_bwd<1, false, true> + its k_dw3 launches    (tests/test_gpu_warp_dw_fused.py)
+// The A/B switches and RDRF_ABL_* ablation blocks of the decided experiments (profiles/LABBOOK.md) were
+// removed; commit ea23fff is the last tree that has them.  tests/test_abi_cpu.py holds the list to these three.
 #ifdef RDRF_TOOLS
 #include <stdlib.h>
 #define RDRF_ENV(name) getenv(name)

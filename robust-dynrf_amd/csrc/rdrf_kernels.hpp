@@ -107,19 +107,12 @@ constexpr int SFG_DZ6 = 0, SFG_DZ4 = 32, SFG_DZ2 = 96, SFG_DZ0 = 160, SFG_ROWS =
 template <int KK>
 RDRF_D void save_rows(float* __restrict__ tile_base, int row0, const float (&v)[KK], int s, int h) {
   if (tile_base == nullptr) return;
-#ifdef RDRF_ABL_NOSAVE
-  return;
-#endif
 #pragma unroll
   for (int kk = 0; kk < KK; ++kk) {
     // streaming (non-temporal) store: the rows are written once and read back a whole pass later,
     // long after L2 eviction; keeping them out of L2 leaves it to the factor gathers (-15 % on the
     // forward kernels)
-#ifdef RDRF_SAVE_TEMPORAL
-    tile_base[(size_t)(row0 + elem_of(kk, h)) * 32 + s] = v[kk];
-#else
     __builtin_nontemporal_store(v[kk], tile_base + (size_t)(row0 + elem_of(kk, h)) * 32 + s);
-#endif
   }
 }
 template <int KK>
@@ -127,12 +120,8 @@ RDRF_D void load_rows(const float* __restrict__ tile_base, int row0, float (&v)[
 #pragma unroll
   // (non-temporal LOADS were measured too: the dW kernel, whose waves share rows through L2, got
   // 10 % slower, the backward-data kernels 2 % faster -- not adopted; re-measured in round 6 against k_dw3's
-  // row DMA with -DRDRF_NT_ROWS / -DRDRF_SAVE_TEMPORAL: same outcome, profiles/r06_ab_cache_policies.txt)
-#ifdef RDRF_NT_ROWS
-  for (int kk = 0; kk < KK; ++kk) v[kk] = __builtin_nontemporal_load(tile_base + (size_t)(row0 + elem_of(kk, h)) * 32 + s);
-#else
+  // row DMA, as were temporal stores in save_rows: same outcome, profiles/r06_ab_cache_policies.txt)
   for (int kk = 0; kk < KK; ++kk) v[kk] = tile_base[(size_t)(row0 + elem_of(kk, h)) * 32 + s];
-#endif
 }
 
 // header of the per-call saved buffer (device memory owned by the caller)

@@ -379,9 +379,8 @@ static int render_chunks(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, 
     // bit).  A group of g chunks pays the fixed costs of a launch sequence once -- ten launches, two 121-159 KB LDS weight
     // images per CU and MLP kernel -- instead of g times: the frame time of the 512-ray loop was the SUM of its chunks'
     // isolated kernel times (profiles/r05_render_chunk512_kernel_stats.csv), streams or not.
-    static const int coalesce = RDRF_ENV("RDRF_CHUNK_COALESCE") ? atoi(RDRF_ENV("RDRF_CHUNK_COALESCE")) : 1;   // 0: one sequence per chunk (tools build)
     int g = 1;
-    while (coalesce && g < 256 && (long)g * chunk < N && rdrf_render_workspace_bytes((g + 1) * chunk, S) <= ws_bytes &&
+    while (g < 256 && (long)g * chunk < N && rdrf_render_workspace_bytes((g + 1) * chunk, S) <= ws_bytes &&
            (size_t)(g + 1) * chunk * S * 3 < (size_t)INT32_MAX)
       ++g;
     if (g > 1) {

@@ -72,9 +72,6 @@ __global__ __launch_bounds__(512, 3) void k_scatter(ScatterArgs a) {
     for (int set = 0; set < a.nsets; ++set) {
       const float* rb = a.rows + ((size_t)t * a.stride + a.row0[set]) * 32;
       const LdsLines ll = make_lds_lines(use_lacc ? lacc : nullptr, set ? nl0 : 0, a.lds_f64, a.vm[set]);
-#ifndef RDRF_SC_UNROLL
-#define RDRF_SC_UNROLL 1
-#endif
       // Per level: the XY plane's C0Q quads go four at a time over 16-sample sub-tiles
       // (gather_xy4_bwd: a texel's four quads in one instruction = one 64-byte request); then the
       // XZ / YZ quads, either column-split over the half-waves (ZSPLIT: density / blending, one
@@ -83,12 +80,8 @@ __global__ __launch_bounds__(512, 3) void k_scatter(ScatterArgs a) {
       constexpr int QPL = C0Q + 2 * C1Q, NLV = (2 * NQ) / QPL;
       static_assert(C0Q % 4 == 0 && NLV * QPL == 2 * NQ, "quad layout");
       const int q = lane >> 4, s16 = lane & 15;
-#ifndef RDRF_ABL_SC_NLV
-#define RDRF_ABL_SC_NLV 99
-#endif
 #pragma unroll 1
-      for (int lv = 0; lv < NLV && lv < RDRF_ABL_SC_NLV; ++lv) {
-#ifndef RDRF_ABL_SC_NOXY
+      for (int lv = 0; lv < NLV; ++lv) {
 #pragma unroll 1
         for (int it = 0; it < C0Q / 2; ++it) {
           const int grp = it >> 1, j = it & 1;
@@ -100,8 +93,6 @@ __global__ __launch_bounds__(512, 3) void k_scatter(ScatterArgs a) {
           gather_xy4_bwd<C0Q, C1Q>(a.vm[set], a.gvm[set], lv, 4 * grp + q, j ? xb0 : xa0, j ? xb1 : xa1,
                                    j ? xb2 : xa2, dq, j ? liveb : livea, lane < 32 && q == j, dw0, dw1, dw2, ll);
         }
-#endif
-#ifndef RDRF_ABL_SC_NOZ
         if constexpr (ZSPLIT) {
 #pragma unroll 1
           for (int zq = 0; zq < 2 * C1Q; ++zq) {
@@ -121,7 +112,6 @@ __global__ __launch_bounds__(512, 3) void k_scatter(ScatterArgs a) {
             gather_quad_bwd<C0Q, C1Q, 1>(a.vm[set], a.gvm[set], g, x0, x1, x2, dq, live, s, dw0, dw1, dw2, ll);
           }
         }
-#endif
       }
     }
     dw0 += __shfl_xor(dw0, 32, 64); dw1 += __shfl_xor(dw1, 32, 64); dw2 += __shfl_xor(dw2, 32, 64);
@@ -230,9 +220,6 @@ __global__ void k_sort_counts(const unsigned* __restrict__ keys_sorted, int NS, 
   counts[p] = lo;
 }
 
-#ifndef RDRF_LINE_DIRECT_DEFAULT
-#define RDRF_LINE_DIRECT_DEFAULT 1   // measured: -0.1 ms / step on top of the double accumulators (profiles/r05_ab_lds_f64.txt)
-#endif
 struct SortedScatterArgs {
   RdrfVM vm[2], gvm[2];
   int set_mask;            // bit k: set k has a gradient
@@ -473,18 +460,14 @@ static int lines_floats_host(const RdrfVM& vm) {
 }
 // LDS line accumulators when both factor sets' lines fit SC_LINES_MAX_BYTES; launches with that much
 // dynamic LDS (the attribute call is needed above 64 KB and is idempotent)
-#ifndef RDRF_SC_THREADS2_DEFAULT
-#define RDRF_SC_THREADS2_DEFAULT 256
-#endif
 template <typename K>
 static int launch_scatter_k(const char* name, K kern, ScatterArgs& sa, long ntiles, hipStream_t stream) {
   const long n0 = lines_floats_host(sa.vm[0]), n1 = sa.nsets > 1 ? lines_floats_host(sa.vm[1]) : 0;
   // element type of the accumulators: doubles when they fit (ds_add_f64 retires 11 x the updates of ds_add_f32, see
   // LdsLines), also at the price of one launch per factor set; floats for lines too long for that; else global atomics
-  static const int f64_env = RDRF_ENV("RDRF_LDS_F64") ? atoi(RDRF_ENV("RDRF_LDS_F64")) : 1;   // 0: floats (tools build, A/B)
   int esz = 0;
   bool split = false;
-  for (int e = f64_env ? 8 : 4; e >= 4 && !esz; e -= 4) {
+  for (int e = 8; e >= 4 && !esz; e -= 4) {
     if (e * (n0 + n1) <= SC_LINES_MAX_BYTES) esz = e;
     else if (sa.nsets == 2 && e * n0 <= SC_LINES_MAX_BYTES && e * n1 <= SC_LINES_MAX_BYTES) { esz = e; split = true; }
   }
@@ -511,12 +494,10 @@ static int launch_scatter_k(const char* name, K kern, ScatterArgs& sa, long ntil
   // threads; the grid never exceeds what is resident at once (the tile loop is a static stride: a workgroup that starts
   // after the others have finished would run its share alone)
   const int per_cu = sa.lds_bytes > 80 * 1024 ? 1 : (sa.lds_bytes > 53 * 1024 ? 2 : 3);
-  static const int thr2_env = RDRF_ENV("RDRF_SC_THREADS2") ? atoi(RDRF_ENV("RDRF_SC_THREADS2")) : RDRF_SC_THREADS2_DEFAULT;
-  const int threads = per_cu == 1 ? 512 : (per_cu == 2 ? thr2_env : 256);   // two workgroups per CU: 512 threads each = 4 waves per SIMD
+  const int threads = per_cu == 1 ? 512 : 256;
   const int wpb = threads / 64;
   long g = (ntiles + wpb - 1) / wpb;
-  static const long cap_env = RDRF_ENV("RDRF_SC_CAP") ? atol(RDRF_ENV("RDRF_SC_CAP")) : 0;   // experiments (tools build)
-  const long cap = per_cu == 1 ? 256 : (cap_env > 0 ? cap_env : 256 * per_cu);
+  const long cap = 256 * per_cu;
   g = g < 1 ? 1 : (g > cap ? cap : g);
   record_launch(esz, threads, g, -1, 0, 0);
   rdrf_prof_begin(name, stream);
@@ -556,7 +537,6 @@ int scatter_mode_swap(int mode) {
 }
 int scatter_mode(size_t ns, hipStream_t stream) {   // 0 ray, 1 sorted
   int m = g_scatter_mode;
-  if (const char* e = RDRF_ENV("RDRF_SCATTER")) m = !strcmp(e, "sorted") ? RDRF_SCATTER_SORTED : (!strcmp(e, "ray") ? RDRF_SCATTER_RAY : m);
   // auto: with the hand-written radix sort (72 us for 1.4 M keys; rocPRIM took 150) the sorted path wins from the
   // Balloon1 stage-0 pass (4096 x 115 = 471 k samples: 12.57 vs 12.72 ms/step, interleaved A/B on one box) upwards, and
   // sends a tenth of the atomic requests; below ~300 k samples the fixed cost of its seven extra launches dominates
@@ -577,12 +557,10 @@ static int launch_scatter_sorted(SortedScatterArgs& sa, long max_samples, hipStr
   // pass PLANE accumulates line PLANE only: L x (C + 4) elements per factor set, doubles when they fit (see LdsLines)
   const long n = ((sa.set_mask & 1) ? (long)sa.vm[0].L[PLANE] * (sa.vm[0].C[PLANE] + 4) : 0) +
                  ((sa.set_mask & 2) ? (long)sa.vm[1].L[PLANE] * (sa.vm[1].C[PLANE] + 4) : 0);
-  static const int f64_env = RDRF_ENV("RDRF_LDS_F64") ? atoi(RDRF_ENV("RDRF_LDS_F64")) : 1;   // 0: floats (tools build, A/B)
-  const int esz = (f64_env && 8 * n <= SC_LINES_MAX_BYTES) ? 8 : (4 * n <= SC_LINES_MAX_BYTES ? 4 : 0);
+  const int esz = 8 * n <= SC_LINES_MAX_BYTES ? 8 : (4 * n <= SC_LINES_MAX_BYTES ? 4 : 0);
   sa.lds_bytes = (int)(esz * n);
   sa.lds_f64 = esz == 8;
-  static const int direct_env = RDRF_ENV("RDRF_LINE_DIRECT") ? atoi(RDRF_ENV("RDRF_LINE_DIRECT")) : RDRF_LINE_DIRECT_DEFAULT;
-  sa.line_direct = sa.lds_f64 && direct_env;
+  sa.line_direct = sa.lds_f64;   // measured: -0.1 ms / step on top of the double accumulators (profiles/r05_ab_lds_f64.txt)
 #ifdef RDRF_DETERMINISTIC
   sa.lds_bytes = 0;
 #endif
@@ -590,11 +568,8 @@ static int launch_scatter_sorted(SortedScatterArgs& sa, long max_samples, hipStr
     RDRF_HIP(hipFuncSetAttribute((const void*)k_scatter_sorted<PLANE, C0Q, C1Q>, hipFuncAttributeMaxDynamicSharedMemorySize, SC_LINES_MAX_BYTES));
   // 512 threads x 2 workgroups per CU = 4 waves per SIMD (the kernels need <= 116 VGPRs): 12.16 -> 11.98 ms / step against
   // 256 x 3 (profiles/r05_ab_sorted_occupancy.txt); one workgroup per CU when the accumulators take more than half the LDS
-  int per_cu = sa.lds_bytes > 80 * 1024 ? 1 : 2;
-  int threads = 512;
-  static const int thr_env = RDRF_ENV("RDRF_SS_THREADS") ? atoi(RDRF_ENV("RDRF_SS_THREADS")) : 0;   // experiments (tools build)
-  static const int pcu_env = RDRF_ENV("RDRF_SS_PER_CU") ? atoi(RDRF_ENV("RDRF_SS_PER_CU")) : 0;
-  if (thr_env > 0 && pcu_env > 0 && (long)pcu_env * sa.lds_bytes <= 160 * 1024) { threads = thr_env; per_cu = pcu_env; }
+  const int per_cu = sa.lds_bytes > 80 * 1024 ? 1 : 2;
+  const int threads = 512;
   const int wpb = threads / 64;
   const long ntiles = (max_samples + (PLANE == 0 ? 15 : 31)) / (PLANE == 0 ? 16 : 32);
   long g = (ntiles + wpb - 1) / wpb;
@@ -611,21 +586,15 @@ static int launch_scatter_sorted(SortedScatterArgs& sa, long max_samples, hipStr
 
 // the tiled form of pass PLANE (k_scatter_tiled) when its line accumulators and plane windows fit the LDS as doubles;
 // returns 1 if it was launched, 0 if the caller should take k_scatter_sorted, < 0 on error
-#ifndef RDRF_SS_TILED_DEFAULT
-#define RDRF_SS_TILED_DEFAULT 1
-#endif
 template <int PLANE, int C0Q, int C1Q>
 static int launch_scatter_tiled(SortedScatterArgs& sa, const unsigned* keys_sorted, int kb, long max_samples, hipStream_t stream) {
 #ifdef RDRF_DETERMINISTIC
   return 0;   // LDS sums form in wave-arrival order
 #endif
-  static const int tiled_env = RDRF_ENV("RDRF_SS_TILED") ? atoi(RDRF_ENV("RDRF_SS_TILED")) : RDRF_SS_TILED_DEFAULT;
-  if (!tiled_env || g_scatter_mode == RDRF_SCATTER_SORTED_PLAIN) return 0;
-  static const int tw_env = RDRF_ENV("RDRF_SS_TW") ? atoi(RDRF_ENV("RDRF_SS_TW")) : 0;
-  static const int steps_env = RDRF_ENV("RDRF_SS_STEPS") ? atoi(RDRF_ENV("RDRF_SS_STEPS")) : 0;
+  if (g_scatter_mode == RDRF_SCATTER_SORTED_PLAIN) return 0;
+  static_assert(C0Q == 4, "windows hold the 16- / 4-component texels of the density / blending sets");
   constexpr int CT = PLANE == 0 ? 4 * C0Q : 4 * C1Q;
-  int tw = tw_env > 0 ? tw_env : (CT > 16 ? 16 : 32);   // 48-component texels: narrower windows keep two workgroups per CU
-  tw = (tw < 8 ? 8 : (tw > 128 ? 128 : tw)) & ~3;
+  const int tw = 32;
   const long n0 = (sa.set_mask & 1) ? (long)sa.vm[0].L[PLANE] * (sa.vm[0].C[PLANE] + 4) : 0;
   const long n1 = (sa.set_mask & 2) ? (long)sa.vm[1].L[PLANE] * (sa.vm[1].C[PLANE] + 4) : 0;
   const long n = n0 + n1;
@@ -634,35 +603,21 @@ static int launch_scatter_tiled(SortedScatterArgs& sa, const unsigned* keys_sort
   // only where two 512-thread workgroups per CU still fit (at the final grids the z lines of two factor sets alone take
   // 70 KB: one workgroup per CU lost more than the windows gained, 3.46 -> 3.97 ms) and for the 16- / 4-component texels
   // of the density / blending sets (the 48-component appearance windows gained nothing: 0.71 -> 0.71 ms)
-  static const long max_env = RDRF_ENV("RDRF_SS_TILED_MAXB") ? atol(RDRF_ENV("RDRF_SS_TILED_MAXB")) : 80 * 1024;
-  if (C0Q > 4 && tiled_env < 2) return 0;   // (tiled_env >= 2 exists in the tools build only: RDRF_ENV is null in the product)
   // two workgroups per CU: each needs its dynamic bytes + the kernel's static LDS (s_geo: 96 B), rounded to the 512-byte
   // allocation granule (at exactly 80 KB of dynamic LDS the second workgroup did not fit)
   const long per_wg = ((bytes + 96 + 511) / 512) * 512;
-  if (per_wg > max_env) {
-    // both factor sets together do not leave room for two workgroups per CU, each alone does (final grids: 35 KB of z
-    // line + 20 KB of windows per set).  One tiled launch per set was measured and LOSES to the untiled two-set kernel
-    // (final stage, scatter_dyn_density 3.08 -> 3.24 ms / step, profiles/r05_ab_tiled_scatter.txt: every entry's taps and
-    // run structure are formed twice), so it stays an experiment switch of the tools build and the caller falls back
-    static const int split_env = RDRF_ENV("RDRF_SS_SPLIT") ? atoi(RDRF_ENV("RDRF_SS_SPLIT")) : 0;
-    const long one = 8L * ((n0 > n1 ? n0 : n1) + (long)tile_texels(tw) * CT);
-    if (sa.set_mask != 3 || one > max_env || !split_env) return 0;
-    SortedScatterArgs s0 = sa, s1 = sa;
-    s0.set_mask = 1; s1.set_mask = 2;
-    int rc = launch_scatter_tiled<PLANE, C0Q, C1Q>(s0, keys_sorted, kb, max_samples, stream);
-    if (rc != 1) return rc;
-    rc = launch_scatter_tiled<PLANE, C0Q, C1Q>(s1, keys_sorted, kb, max_samples, stream);
-    return rc == 0 ? -5 : rc;   // (cannot happen: the same size test passed for the larger of the two)
-  }
+  // where both factor sets together leave no room for two workgroups per CU the caller falls back: one tiled launch per set
+  // was measured and LOSES to the untiled two-set kernel (final stage, scatter_dyn_density 3.08 -> 3.24 ms / step,
+  // profiles/r05_ab_tiled_scatter.txt: every entry's taps and run structure are formed twice)
+  if (per_wg > 80 * 1024) return 0;
   sa.lds_bytes = (int)bytes; sa.lds_f64 = 1;
-  static const int direct_env = RDRF_ENV("RDRF_LINE_DIRECT") ? atoi(RDRF_ENV("RDRF_LINE_DIRECT")) : RDRF_LINE_DIRECT_DEFAULT;
-  sa.line_direct = direct_env;
+  sa.line_direct = 1;
   sa.keys = keys_sorted; sa.kb = kb; sa.tw = tw;
-  sa.slice_steps = steps_env > 0 ? steps_env : 16;   // 2 steps for each of the 8 waves (16: 1.51, 32: 1.55, 64: 1.68 ms / step)
+  sa.slice_steps = 16;   // 2 steps for each of the 8 waves (16: 1.51, 32: 1.55, 64: 1.68 ms / step)
   sa.Wk = sa.vm[0].W[PLANE] + 3;
   if (sa.lds_bytes > 48 * 1024)
     RDRF_HIP(hipFuncSetAttribute((const void*)k_scatter_tiled<PLANE, C0Q, C1Q>, hipFuncAttributeMaxDynamicSharedMemorySize, SC_LINES_MAX_BYTES));
-  const int per_cu = per_wg > 80 * 1024 ? 1 : 2;   // 512-thread workgroups, 4 waves per SIMD (__launch_bounds__(512, 4): HIP counts waves per SIMD)
+  const int per_cu = 2;   // 512-thread workgroups, 4 waves per SIMD (__launch_bounds__(512, 4): HIP counts waves per SIMD)
   const long nslices = (max_samples + (long)sa.slice_steps * (PLANE == 0 ? 16 : 32) - 1) / ((long)sa.slice_steps * (PLANE == 0 ? 16 : 32));
   long g = nslices < 256L * per_cu ? nslices : 256L * per_cu;
   g = g < 1 ? 1 : g;
@@ -724,12 +679,7 @@ int scatter_dyn_app_sorted(const BwdArgs& a, const BwdWs& b, const RdrfDynamicPa
   SortKeyArgs ka;
   memset(&ka, 0, sizeof(ka));
   ka.list = a.sp.list; ka.count = &a.sp.hdr->count;
-#ifdef RDRF_TOOLS   // (the windows experiment below addresses the sorted keys with the host-side stride N S)
-  static const int compact_env = RDRF_ENV("RDRF_SORT_COMPACT") ? atoi(RDRF_ENV("RDRF_SORT_COMPACT")) : 1;
-  ka.compact = compact_env && !(RDRF_ENV("RDRF_SS_TILED") && atoi(RDRF_ENV("RDRF_SS_TILED")) >= 2);
-#else
   ka.compact = 1;
-#endif
   int rc = sorted_scatter_prepare(ka, P->app, a, b, stream);
   if (rc) return rc;
   SortedScatterArgs sa;
@@ -739,16 +689,7 @@ int scatter_dyn_app_sorted(const BwdArgs& a, const BwdWs& b, const RdrfDynamicPa
   for (int p = 0; p < 3; ++p) {
     sa.order = b.order + (size_t)p * ns; sa.count = b.counts + p; sa.base = (unsigned)(p * ns);
     if (ka.compact) { sa.order = b.order; sa.seg = ka.count; }   // device-side segment starts (k_scatter_sorted)
-    const unsigned* ks = b.keys_out + (size_t)p * ns;
-#ifdef RDRF_TOOLS   // the 48-component windows gained nothing (0.713 -> 0.695 ms, profiles/r05_ab_tiled_scatter.txt): an experiment of the
-    rc = p == 0 ? launch_scatter_tiled<0, 12, 3>(sa, ks, ka.kb, (long)ns, stream)          // tools build (RDRF_SS_TILED=2), not
-                : (p == 1 ? launch_scatter_tiled<1, 12, 3>(sa, ks, ka.kb, (long)ns, stream)   // compiled into the product
-                          : launch_scatter_tiled<2, 12, 3>(sa, ks, ka.kb, (long)ns, stream));
-    if (rc < 0) return rc;
-    if (rc == 1) continue;
-#else
-    (void)ks;
-#endif
+    // (no windows here: for the 48-component texels they gained nothing, 0.713 -> 0.695 ms, profiles/r05_ab_tiled_scatter.txt)
     rc = p == 0 ? launch_scatter_sorted<0, 12, 3>(sa, (long)ns, stream)
                 : (p == 1 ? launch_scatter_sorted<1, 12, 3>(sa, (long)ns, stream) : launch_scatter_sorted<2, 12, 3>(sa, (long)ns, stream));
     if (rc) return rc;

@@ -22,10 +22,7 @@
 namespace {
 constexpr int RS_THREADS = 256;
 constexpr int RS_WAVES = RS_THREADS / 64;
-#ifndef RDRF_RS_TILE
-#define RDRF_RS_TILE 2048   // 8192 -> 2048: sort -11 % at stage 0, -12 % at the final stage (profiles/r06_ab_sort_tile.txt)
-#endif
-constexpr int RS_TILE = RDRF_RS_TILE;          // entries per workgroup
+constexpr int RS_TILE = 2048;                  // entries per workgroup (8192 -> 2048: sort -11 % at stage 0, -12 % at the final stage, profiles/r06_ab_sort_tile.txt)
 constexpr int RS_PER_WAVE = RS_TILE / RS_WAVES;
 constexpr int RS_ROUNDS = RS_PER_WAVE / 64;    // 64-entry rounds per wave
 constexpr int RS_MAX_DIGIT_BITS = 9;

@@ -185,6 +185,35 @@ def test_product_library_does_not_read_the_environment():
         assert "getenv" not in syms, f"{name} imports getenv"
 
 
+def test_only_the_kept_switches_remain_in_the_native_sources():
+    """The decided A/B experiments were retired from csrc: what is left are the three tools-build switches that GPU tests use
+    as the independent second implementation (tests/test_gpu_flat_density.py, test_gpu_scene_flow_fused.py,
+    test_gpu_warp_dw_fused.py), the deterministic twin, the wave count, the fp32 fallback builds of the bf16 x 3 layers and
+    the tools build itself.  A new environment switch or compile-time variant shows up here."""
+    import glob
+    csrc = os.path.join(ROOT, "robust-dynrf_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.hpp")))
+    assert len(files) >= 20, files
+    env, tested = set(), set()
+    for path in files:
+        text = open(path).read()
+        calls = re.findall(r"RDRF_ENV\(\s*([^)]*?)\s*\)", text)
+        for arg in calls:
+            if arg == "name":   # the macro's own definition (rdrf_host.hpp)
+                assert os.path.basename(path) == "rdrf_host.hpp", path
+                continue
+            assert re.fullmatch(r'"[A-Z0-9_]+"', arg), f"{path}: RDRF_ENV({arg}) is not called with a string literal"
+            env.add(arg.strip('"'))
+        for line in re.sub(r"\\\n", " ", text).split("\n"):
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if m:
+                tested |= set(re.findall(r"\bRDRF_[A-Z0-9_]+\b", re.sub(r"//.*|/\*.*?\*/", "", m.group(2))))
+    assert env == {"RDRF_FLAT", "RDRF_SF_FUSED", "RDRF_WARP_FUSED"}, sorted(env)
+    kept = {"RDRF_TOOLS", "RDRF_DETERMINISTIC", "RDRF_MAXW", "RDRF_APP_F32", "RDRF_HEADS_F32", "RDRF_HEADS_BWD_F32"}
+    assert tested, "no preprocessor conditional parsed"
+    assert tested <= kept, sorted(tested - kept)
+
+
 def test_sincos_double_formula():
     """csrc/rdrf_common.hpp sincos_double: the odd octaves of a positional encoding from the even ones,
     sin 2a = (s + s) c, cos 2a = fma(-(s + s), s, 1) with (s, c) = sincos_pe(a): bounded against fp64 sin / cos of the

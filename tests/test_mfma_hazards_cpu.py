@@ -31,7 +31,7 @@ pytestmark = pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc") or shu
 # six MFMAs per 32-neuron output block and K = 16 step (hi / mid / lo pieces): what the source implies per kernel.
 # (token of the mangled name, tokens that exclude, minimum per kernel, kernels at least)
 FAMILIES = {
-    "rdrf_fwd": [("k_static_app", ("bwd", "app16"), 4 * 18 * 6, 4),        # (16 + 64 + 64) / 8 steps, four blocks
+    "rdrf_fwd": [("k_static_app", ("bwd",), 4 * 18 * 6, 4),                 # (16 + 64 + 64) / 8 steps, four blocks
                  ("k_dyn_app", ("bwd",), 4 * 15 * 6, 2),                    # (16 + 32 + 8 + 64) / 8 steps
                  ("k_dyn_density", ("bwd",), 2 * 2 * 9 * 6, 5)],            # two heads x mfma_seg_b3<2, 72>
     "rdrf_bwd": [("k_static_app_bwd", (), 3 * 2 * 6, 3),                    # features only: <3, 16>; full: + <4, 64> + <5, 64>

@@ -1,7 +1,7 @@
 // Microbenchmark (round 6): what does the fp32 matrix pipe of one SIMD sustain for the two f32 MFMA shapes, in the operand
 // patterns of the MLP kernels, as a function of the waves per SIMD that share it?
 //   32x32x2, 4 accumulators  (k_static_app: four 32-neuron blocks of a 32-sample tile, weights streamed from LDS)
-//   16x16x4, 8 accumulators  (k_static_app16: eight 16-neuron blocks of a 16-sample tile)
+//   16x16x4, 8 accumulators  (the removed k_static_app16: eight 16-neuron blocks of a 16-sample tile)
 // variants: operands in registers only ("reg") or the A operand streamed from LDS exactly like mfma_seg / mfma16_seg ("lds").
 // Prints cycles per MFMA per SIMD from s_memtime (shader clock) and the TFLOP/s the wall clock gives.
 #include <hip/hip_runtime.h>
