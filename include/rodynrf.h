@@ -685,6 +685,10 @@ int rdrf_selftest_layer(int form, const float* x, const float* w, int M, int K, 
 int rdrf_selftest_dw(int plan, int flags, const float* A, size_t A_floats, const float* B, size_t B_floats, int ntiles,
                      const int* count, const void* grads, rdrf_stream_t stream);
 int rdrf_selftest_dw_describe(int plan, int flags, int* out, int cap);
+/* The kernel launches the host planner makes for a plan's job list at ntiles (>= 1) tiles, in resolved form (layout:
+ * csrc/rdrf_selftest.hip): grid, LDS bytes, accumulator sets, the runs of consecutive rows, the staged blocks and every wave's
+ * products.  Host code only: runs without a GPU.  Returns the number of ints written; -3 when cap is too small. */
+int rdrf_selftest_dw_plan(int plan, int flags, int ntiles, int* out, int cap);
 /* launch geometry of the scene-flow backward kernel that forms its weight gradients itself, for ntiles 32-sample tiles:
  * workgroups and waves per workgroup (a wave walks the tiles wg * waves + wave, + grid * waves, ...).  Host code only. */
 int rdrf_selftest_sf_geometry(int ntiles, int* grid, int* waves);

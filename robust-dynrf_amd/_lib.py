@@ -185,6 +185,7 @@ def _load():
     lib.rdrf_selftest_dw.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p]
     lib.rdrf_selftest_dw_describe.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]
+    lib.rdrf_selftest_dw_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]
     lib.rdrf_selftest_warp_geometry.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.rdrf_selftest_warp_bwd_workspace_bytes.restype = C.c_size_t
     lib.rdrf_selftest_warp_bwd_workspace_bytes.argtypes = [C.c_int, C.c_int]
@@ -234,6 +235,7 @@ SYMBOLS = [
     "rdrf_compute_alpha_workspace_bytes", "rdrf_compute_alpha", "rdrf_alpha_mask_build", "rdrf_alpha_mask_sample",
     "rdrf_alpha_mask_valid",
     "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_selftest_layer", "rdrf_selftest_dw", "rdrf_selftest_dw_describe",
+    "rdrf_selftest_dw_plan",
     "rdrf_selftest_sf_geometry", "rdrf_selftest_warp_geometry", "rdrf_selftest_warp_bwd_workspace_bytes", "rdrf_selftest_warp_bwd",
     "rdrf_selftest_sort_temp_bytes", "rdrf_selftest_sort", "rdrf_selftest_scatter_workspace_bytes", "rdrf_selftest_scatter",
     "rdrf_selftest_scatter_describe", "rdrf_selftest_scatter_last",

@@ -109,6 +109,8 @@ void dw_add(DwJobs& D, const float* A, int A_stride, int A_row0, int nbo, int ou
             int B_stride, int in_dim, int ld, float* dW, float* db, const int* count, int ntiles);
 void dw_blk(DwJobs& D, int row0, int seg, int e0);
 int dw_launch(DwJobs& D, hipStream_t stream, const char* name);
+// the launches dw_launch would make, written as ints (rdrf_selftest_dw_plan); host code only, no HIP call
+int dw_describe_launches(const DwJobs& D, int* out, int cap);
 
 // the job lists of the backward entry points, one builder per list (rdrf_bwd.hip); rdrf_selftest_dw (rdrf_selftest.hip) runs
 // the same lists on caller-supplied rows.  cnt / ntiles: the device sample count of a compacted phase, or the host tile count.

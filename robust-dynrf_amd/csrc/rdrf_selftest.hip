@@ -355,6 +355,28 @@ extern "C" int rdrf_selftest_dw_describe(int plan, int flags, int* out, int cap)
   return n;
 }
 
+// The launches dw_launch makes for a plan at ntiles tiles (host memory, ints; host code only, no HIP call):
+// [0] ints used, [1] launches; per launch: workgroups, dynamic LDS bytes, accumulator sets of the k_dw3 instantiation, staged
+// blocks, runs; per run: source (0 dz rows, 1 activation rows), first row, first staged block; per staged block: source, first
+// row; per wave (12): its number of products, and per product the staged block indices of its dz and its input block, then the
+// job, the out block and the input block of the job that it forms.  The plans with a compacted phase are planned with a device
+// count, as their entry points pass one.
+extern "C" int rdrf_selftest_dw_plan(int plan, int flags, int ntiles, int* out, int cap) {
+  constexpr size_t NSLOT = (sizeof(RdrfDynamicParams) > sizeof(RdrfStaticParams) ? sizeof(RdrfDynamicParams) : sizeof(RdrfStaticParams)) / 8;
+  uintptr_t slots[NSLOT];   // as in rdrf_selftest_dw_describe: only "is there a bias" is read of the gradient struct
+  for (size_t i = 0; i < NSLOT; ++i) slots[i] = (i + 1) * 8;
+  alignas(16) static const float rowsA[4] = {0.f}, rowsB[4] = {0.f};   // addresses only: never read
+  static const int cnt = 0;
+  RDRF_CHECK(ntiles >= 1 && ntiles <= (1 << 20), -1, "selftest_dw_plan: bad arguments (ntiles = %d)", ntiles);
+  DwJobs D;
+  DwPlanInfo I;
+  int rc = dw_plan_jobs(plan, flags, rowsA, rowsB, 0, &cnt, slots, D, I);   // (both regions at the same address: they differ in stride)
+  if (rc) return rc;
+  for (int j = 0; j < D.n; ++j)
+    if (D.j[j].count == nullptr) D.j[j].ntiles = ntiles;
+  return dw_describe_launches(D, out, cap);
+}
+
 extern "C" int rdrf_selftest_sf_geometry(int ntiles, int* grid, int* waves) {
   RDRF_CHECK(ntiles >= 0 && grid && waves, -1, "selftest_sf_geometry: bad arguments");
   fused_dw_geometry(ntiles, grid, waves);
