@@ -715,9 +715,20 @@ size_t rdrf_selftest_sort_temp_bytes(unsigned n, int bits);
 int rdrf_selftest_sort(const unsigned* keys, unsigned n, int bits, const int* count, unsigned n_mul, unsigned* keys_out,
                        unsigned* order, void* temp, size_t temp_bytes, rdrf_stream_t stream);
 
+/* The segmented form (the product's: the three planes' keys are three segments): nseg independent stable sorts of seg_len consecutive
+ * entries over the low `bits` bits, the bits above ride along; order = GLOBAL positions segment * L + index.  count (nullable,
+ * device): segments are L = min(seg_len, *count) entries long and L apart; entries beyond nseg * L are left alone.  temp: 256-byte
+ * aligned, rdrf_selftest_sort_seg_temp_bytes.  rdrf_selftest_sort_describe (host only) writes the plan: [0] values used, [1] passes,
+ * [2] bits per digit, [3] tiles per segment, [4] entries per tile, [5] bytes carved from temp, [6] the temp-size formula, [7] launches
+ * of such a sort, [8] launches of a sorted-scatter call (key kernel + sort); returns the values written, -1 / -3 on bad arguments. */
+size_t rdrf_selftest_sort_seg_temp_bytes(int nseg, unsigned seg_len, int bits);
+int rdrf_selftest_sort_seg(const unsigned* keys, int nseg, unsigned seg_len, int bits, const int* count, unsigned* keys_out,
+                           unsigned* order, void* temp, size_t temp_bytes, rdrf_stream_t stream);
+int rdrf_selftest_sort_describe(int nseg, unsigned seg_len, int bits, unsigned long long* out, int cap);
+
 /* The gradient scatter (VM gather backward) on data the caller supplies, through the launch functions of the backward entry
  * points: kind = one of the four instantiations in use, mode = RDRF_SCATTER_RAY (ray / flat / list tiles), _SORTED (samples
- * grouped by plane cell: key generation, sort, count search, then the windowed passes where the launch policy takes them) or
+ * grouped by plane cell: key generation, sort and counts, then the windowed passes where the launch policy takes them) or
  * _SORTED_PLAIN (the same without windows); the dynamic kinds have the sorted modes.  Layouts: rdrf_selftest_scatter_describe
  * (csrc/rdrf_selftest.hip).  -1 bad arguments, -2 a mode or tile form the kind does not have, -3 a buffer too small. */
 #define RDRF_SCK_STATIC_DENSITY 0 /* k_scatter<4,1,3>:   row 0 broadcast, xyz + box, g_xyz */

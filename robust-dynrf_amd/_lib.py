@@ -196,6 +196,12 @@ def _load():
     lib.rdrf_selftest_sort_temp_bytes.argtypes = [C.c_uint, C.c_int]
     lib.rdrf_selftest_sort.argtypes = [C.c_void_p, C.c_uint, C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_size_t, C.c_void_p]
+    if hasattr(lib, "rdrf_selftest_sort_seg"):   # (additions inside ABI 6: an A/B library of the same version may predate them)
+        lib.rdrf_selftest_sort_seg_temp_bytes.restype = C.c_size_t
+        lib.rdrf_selftest_sort_seg_temp_bytes.argtypes = [C.c_int, C.c_uint, C.c_int]
+        lib.rdrf_selftest_sort_seg.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_size_t, C.c_void_p]
+        lib.rdrf_selftest_sort_describe.argtypes = [C.c_int, C.c_uint, C.c_int, C.POINTER(C.c_ulonglong), C.c_int]
     lib.rdrf_selftest_scatter_workspace_bytes.restype = C.c_size_t
     lib.rdrf_selftest_scatter_workspace_bytes.argtypes = [C.c_int, C.c_int]
     lib.rdrf_selftest_scatter.argtypes = [C.c_int, C.c_int, C.POINTER(RdrfScatterTest), C.c_void_p]
@@ -237,7 +243,8 @@ SYMBOLS = [
     "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_selftest_layer", "rdrf_selftest_dw", "rdrf_selftest_dw_describe",
     "rdrf_selftest_dw_plan",
     "rdrf_selftest_sf_geometry", "rdrf_selftest_warp_geometry", "rdrf_selftest_warp_bwd_workspace_bytes", "rdrf_selftest_warp_bwd",
-    "rdrf_selftest_sort_temp_bytes", "rdrf_selftest_sort", "rdrf_selftest_scatter_workspace_bytes", "rdrf_selftest_scatter",
+    "rdrf_selftest_sort_temp_bytes", "rdrf_selftest_sort", "rdrf_selftest_sort_seg_temp_bytes", "rdrf_selftest_sort_seg",
+    "rdrf_selftest_sort_describe", "rdrf_selftest_scatter_workspace_bytes", "rdrf_selftest_scatter",
     "rdrf_selftest_scatter_describe", "rdrf_selftest_scatter_last",
     "rdrf_prof_reset",
     "rdrf_prof_enable", "rdrf_prof_get",

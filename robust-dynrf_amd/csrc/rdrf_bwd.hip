@@ -1128,7 +1128,7 @@ extern "C" size_t rdrf_workspace_bytes(int N, int S) {
   size_t bwd = (size_t)PACK_AREA_FLOATS * 4 + t1 * sv::K1G_ROWS * 32 * 4 + t3 * sv::K3G_ROWS * 32 * 4 +
                ns * 3 * 4 * 2 + (size_t)N * 32 * 4 + (1 << 14);
   // sorted scatter: sample-major d(feature) records, keys in / out, sorted positions, counters, radix-sort scratch
-  bwd += ns * DFS_FLOATS * 4 + ns * DFA_FLOATS * 4 + 3 * ns * 4 * 3 + 1024 + rdrf_sort_temp_bytes((unsigned)(3 * ns), 32) + (1 << 12);
+  bwd += ns * DFS_FLOATS * 4 + ns * DFA_FLOATS * 4 + 3 * ns * 4 * 3 + 1024 + rdrf_sort_seg_temp_bytes(3, (unsigned)ns, 32) + (1 << 12);
   // flat-tile density phase: total d(sigma) per sample + the d(tout) partial records of the tiles
   bwd += ns * 4 + t3 * 64 * 4 + 512;
   size_t sf = (size_t)PACK_AREA_FLOATS * 4 + t3 * sv::SFG_ROWS * 32 * 4 + (1 << 12);
@@ -1156,7 +1156,7 @@ static int carve_bwd(BwdWs& b, void* ws, size_t ws_bytes, int N, int S, int dyna
     b.keys_out = c.take<unsigned>(3 * ns);
     b.order = c.take<unsigned>(3 * ns);
     b.counts = c.take<int>(64);
-    b.sort_tmp_bytes = rdrf_sort_temp_bytes((unsigned)(3 * ns), 32);
+    b.sort_tmp_bytes = rdrf_sort_seg_temp_bytes(3, (unsigned)ns, 32);
     b.sort_tmp = c.take<char>(b.sort_tmp_bytes);
     b.gsig = c.take<float>(ns);
     b.dtp = c.take<float>(t3 * 64);

@@ -113,6 +113,17 @@ static inline bool vm_ok(const RdrfVM& v, int c0, int c1) {
 size_t rdrf_sort_temp_bytes(unsigned n, int bits);
 int rdrf_sort_positions(const unsigned* keys_in, unsigned* keys_out, unsigned* vals_out, unsigned n, int bits, void* temp,
                         size_t temp_bytes, hipStream_t stream, const int* n_dev = nullptr, unsigned n_mul = 0);
+// the segmented form: nseg independent sorts of seg_len entries (device-side length: *seg_len_dev) over the low `bits` bits,
+// values = global positions.  counts != nullptr: a key kernel has written the first pass's tile histograms and drop counts
+// into the tables rdrf_sort_tables names (layout: rdrf_sort_dev.hpp); the sort then starts at the scan, which also writes
+// counts[segment] = length - dropped
+struct RsTables;
+size_t rdrf_sort_seg_temp_bytes(int nseg, unsigned seg_len, int bits);
+size_t rdrf_sort_carved_bytes(int nseg, unsigned seg_len);   // what the sort carves out of its temporary storage
+void rdrf_sort_plan(int bits, int* passes, int* digit_bits);
+int rdrf_sort_tables(int nseg, unsigned seg_len, int bits, void* temp, size_t temp_bytes, RsTables* t, int* nbins);
+int rdrf_sort_positions_seg(const unsigned* keys_in, unsigned* keys_out, unsigned* vals_out, int nseg, unsigned seg_len, int bits,
+                            void* temp, size_t temp_bytes, hipStream_t stream, const int* seg_len_dev = nullptr, int* counts = nullptr);
 
 int rdrf_sort_ints_inplace(int* data, unsigned n, hipStream_t stream);   // deterministic build only
 

@@ -1,11 +1,12 @@
 // rdrf_scatter.hip -- VM gather backward as kernels of their own: the feature-gradient rows (or sample-major records) that
 // the backward-data kernels of rdrf_bwd.hip wrote are scattered into the factor planes / lines, and the coordinate
 // gradients are formed.  Three forms share the per-quad device functions of rdrf_bwd_dev.hpp: the ray-tile kernel
-// (k_scatter), the sorted kernels (k_sort_keys / k_sort_counts + k_scatter_sorted: samples grouped by plane cell first)
+// (k_scatter), the sorted kernels (k_sort_keys + k_scatter_sorted: samples grouped by plane cell first)
 // and the sorted kernel with LDS plane windows (k_scatter_tiled); the launch policy of each is here too.
 // Host interface: rdrf_bwd_host.hpp.
 #include "rdrf_bwd_dev.hpp"
 #include "rdrf_bwd_host.hpp"
+#include "rdrf_sort_dev.hpp"
 
 RDRF_DET_UNIT(scatter)
 
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(512, 3) void k_scatter(ScatterArgs a) {
 // With the reference initialiser the warp MLP moves the warped point by about a texel between consecutive samples of
 // a ray, so the ray-tile scatter above finds runs of 1-2 samples and pays ~13 M memory-side atomic requests per launch
 //  for gradient planes of a few MB.  Here the live samples are first grouped by the plane CELL they fall
-// into (one stable device-wide radix sort of (plane | level-0 cell) keys, rdrf_sort.hip), once per plane, and each
+// into (one stable radix sort of (plane | level-0 cell) keys per plane segment, rdrf_sort.hip), and each
 // plane is scattered in that order by the SAME per-quad device functions: consecutive lanes now hold samples of the
 // same or the neighbouring cell (~20-40 samples per level-0 cell at the benchmark shapes), so the in-register run
 // reduction collapses them and a run of lanes issues one request per tap.  Per plane: XY = 16 samples x 4 quads per
@@ -163,6 +164,12 @@ struct SortKeyArgs {
   int flat;              // the density-phase rows are addressed by flat 32-sample tile (rdrf_flat_density)
   int compact;           // list mode: the key arrays hold the *count compacted entries of each plane back to back (stride *count
                          // instead of N*S), so that the sort and the key generation touch live entries only (round 6)
+  // tables of the sort's first pass (rdrf_sort_dev.hpp): per tile of RS_TILE entries and plane, the histogram of the keys'
+  // lowest digit (nbins bins) and the number of dropped keys
+  unsigned* hist;
+  unsigned* drops;
+  unsigned tps;
+  int nbins;
 };
 
 RDRF_D int cell_axis(float c, int L, bool& any) {
@@ -172,52 +179,67 @@ RDRF_D int cell_axis(float c, int L, bool& any) {
   return min(max(t0.i0, -2), L) + 2;
 }
 
-__global__ __launch_bounds__(256) void k_sort_keys(SortKeyArgs a) {
+// A workgroup owns tiles of RS_TILE entries -- the tiles of the sort (a plane's keys are one segment of it) -- and writes,
+// besides the keys, what the sort's first pass needs of each tile: per plane the histogram of the lowest digit and the
+// number of dropped keys.  Plain stores into the tile's own table entries: the first pass starts at its scan, whose extra
+// workgroup per plane turns the drop counts into counts[plane] = entries - dropped (a per-wave atomic counter here
+// serialised 66 k same-address atomics: 240 us; a search of the sorted keys was a launch of its own).
+constexpr int SK_THREADS = 1024;
+__global__ __launch_bounds__(SK_THREADS) void k_sort_keys(SortKeyArgs a) {
+  __shared__ unsigned h[3 * RS_BINS];
+  __shared__ unsigned dr[3];
   const int NS = a.N * a.S, tpr = (a.S + 31) >> 5;
-  const int count = a.list ? *a.count : 0;
+  const int count = a.list ? min(*a.count, NS) : 0;
   const int nent = (a.list && a.compact) ? count : NS;   // entries per plane = the stride of the key arrays
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nent; e += gridDim.x * blockDim.x) {
-    bool live = false;
-    float x0 = 0.f, x1 = 0.f, x2 = 0.f;
-    if (a.list) {
-      live = e < count;
-      const int idx = live ? a.list[e] : 0;
-      x0 = a.xw[(size_t)idx * 3 + 0]; x1 = a.xw[(size_t)idx * 3 + 1]; x2 = a.xw[(size_t)idx * 3 + 2];
-    } else {
-      const int idx = e;
-      const int n = idx / a.S, j = idx - n * a.S;
-      const float* sm = a.grows1 + ((size_t)(a.flat ? idx >> 5 : n * tpr + (j >> 5)) * sv::K1G_ROWS + sv::K1G_SM) * 32 +
-                        (a.flat ? idx & 31 : j & 31);
-      live = a.valid[idx] != 0 && (sm[3 * 32] != 0.f || sm[4 * 32] != 0.f);
-      x0 = a.xw[(size_t)idx * 3 + 0]; x1 = a.xw[(size_t)idx * 3 + 1]; x2 = a.xw[(size_t)idx * 3 + 2];
-    }
+  const unsigned ntile = nent > 0 ? rs_tiles((unsigned)nent) : 0u, mask = (unsigned)a.nbins - 1u;
+  const int lane = threadIdx.x & 63;
+  for (unsigned t = blockIdx.x; t < ntile; t += gridDim.x) {
+    for (int i = threadIdx.x; i < 3 * RS_BINS; i += SK_THREADS) h[i] = 0u;
+    if (threadIdx.x < 3) dr[threadIdx.x] = 0u;
+    __syncthreads();
 #pragma unroll
-    for (int p = 0; p < 3; ++p) {
-      const float cx = p == 2 ? x1 : x0, cy = p == 0 ? x1 : x2;
-      bool ax, ay;
-      const int ix = cell_axis(cx, a.W[p], ax), iy = cell_axis(cy, a.H[p], ay);
-      const bool in = live && ax && ay;
-      const unsigned cell = in ? (unsigned)(iy * (a.W[p] + 3) + ix) : ((1u << a.kb) - 1u);
-      a.keys[(size_t)p * nent + e] = ((unsigned)p << a.kb) | cell;
+    for (int k = 0; k < RS_TILE / SK_THREADS; ++k) {
+      const int e = (int)(t * RS_TILE) + k * SK_THREADS + (int)threadIdx.x;
+      const bool have = e < nent;
+      bool live = false;
+      float x0 = 0.f, x1 = 0.f, x2 = 0.f;
+      if (have) {
+        if (a.list) {
+          live = e < count;
+          const int idx = live ? a.list[e] : 0;
+          x0 = a.xw[(size_t)idx * 3 + 0]; x1 = a.xw[(size_t)idx * 3 + 1]; x2 = a.xw[(size_t)idx * 3 + 2];
+        } else {
+          const int idx = e;
+          const int n = idx / a.S, j = idx - n * a.S;
+          const float* sm = a.grows1 + ((size_t)(a.flat ? idx >> 5 : n * tpr + (j >> 5)) * sv::K1G_ROWS + sv::K1G_SM) * 32 +
+                            (a.flat ? idx & 31 : j & 31);
+          live = a.valid[idx] != 0 && (sm[3 * 32] != 0.f || sm[4 * 32] != 0.f);
+          x0 = a.xw[(size_t)idx * 3 + 0]; x1 = a.xw[(size_t)idx * 3 + 1]; x2 = a.xw[(size_t)idx * 3 + 2];
+        }
+      }
+#pragma unroll
+      for (int p = 0; p < 3; ++p) {
+        const float cx = p == 2 ? x1 : x0, cy = p == 0 ? x1 : x2;
+        bool ax, ay;
+        const int ix = cell_axis(cx, a.W[p], ax), iy = cell_axis(cy, a.H[p], ay);
+        const bool in = live && ax && ay;
+        const unsigned cell = in ? (unsigned)(iy * (a.W[p] + 3) + ix) : ((1u << a.kb) - 1u);
+        if (have) {
+          a.keys[(size_t)p * nent + e] = ((unsigned)p << a.kb) | cell;
+          atomicAdd(&h[p * RS_BINS + (cell & mask)], 1u);
+        }
+        const unsigned long long dropped = __ballot(have && !in);
+        if (lane == 0 && dropped) atomicAdd(&dr[p], (unsigned)__popcll(dropped));
+      }
     }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 3 * a.nbins; i += SK_THREADS) {
+      const int p = i / a.nbins, d = i - p * a.nbins;
+      a.hist[rs_hist_at(p, a.nbins, (unsigned)d, a.tps, t)] = h[p * RS_BINS + d];
+    }
+    if (threadIdx.x < 3) a.drops[rs_drops_at((int)threadIdx.x, a.tps, t)] = dr[threadIdx.x];
+    __syncthreads();   // (the next tile zeroes the tables)
   }
-}
-
-// live entries per plane = position of the first dropped key of the plane in the sorted array (a per-wave atomic
-// counter in k_sort_keys serialised 66 k same-address atomics: 240 us)
-__global__ void k_sort_counts(const unsigned* __restrict__ keys_sorted, int NS, int kb, int* __restrict__ counts,
-                              const int* __restrict__ seg) {
-  const int p = threadIdx.x;
-  if (p >= 3) return;
-  const int stride = seg ? *seg : NS;   // compact key arrays: the planes' segments are *seg entries long
-  const unsigned drop = ((unsigned)p << kb) | ((1u << kb) - 1u);
-  const unsigned* k = keys_sorted + (size_t)p * stride;
-  int lo = 0, hi = stride;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (k[mid] < drop) lo = mid + 1; else hi = mid;
-  }
-  counts[p] = lo;
 }
 
 struct SortedScatterArgs {
@@ -649,22 +671,23 @@ static int sorted_scatter_prepare(SortKeyArgs& ka, const RdrfVM& vm, const BwdAr
   const int kb = sorted_key_bits(ka.W, ka.H);
   RDRF_CHECK(kb <= 29, -1, "sorted scatter: plane too large for 32-bit keys");
   ka.kb = kb; ka.keys = b.keys_in; ka.counts = b.counts;
+  // the keys of plane p are segment p of the key arrays and carry p above their kb cell bits: three independent sorts
+  // over kb bits give what one sort over kb + 2 bits gave.  The key kernel owns the sort's tiles and builds its first
+  // histograms and the drop counts behind counts[]
+  RsTables T;
+  int rc = rdrf_sort_tables(3, (unsigned)ns, kb, b.sort_tmp, b.sort_tmp_bytes, &T, &ka.nbins);
+  if (rc) return rc;
+  ka.hist = T.hist; ka.drops = T.drops; ka.tps = T.tps;
   rdrf_prof_begin("scatter_sort", stream);
-  {
-    long g = ((long)ns + 255) / 256;
-    g = g > 2048 ? 2048 : g;
-    rdrf_prof_begin("sort_keys", stream);
-    hipLaunchKernelGGL(k_sort_keys, dim3((unsigned)g), dim3(256), 0, stream, ka);
-    rdrf_prof_end("sort_keys", stream);
-  }
+  rdrf_prof_begin("sort_keys", stream);
+  hipLaunchKernelGGL(k_sort_keys, dim3(T.tps), dim3(SK_THREADS), 0, stream, ka);
+  rdrf_prof_end("sort_keys", stream);
   // compact: the sort covers the 3 x *count live-list entries only (launches sized for 3 N S; the appearance list holds
   // 35-60 % of the samples)
-  int rc = rdrf_sort_positions(b.keys_in, b.keys_out, b.order, (unsigned)(3 * ns), kb + 2, b.sort_tmp, b.sort_tmp_bytes, stream,
-                               ka.compact ? ka.count : nullptr, 3u);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_sort_counts, dim3(1), dim3(64), 0, stream, (const unsigned*)b.keys_out, (int)ns, kb, b.counts,
-                     ka.compact ? ka.count : (const int*)nullptr);
+  rc = rdrf_sort_positions_seg(b.keys_in, b.keys_out, b.order, 3, (unsigned)ns, kb, b.sort_tmp, b.sort_tmp_bytes, stream,
+                               ka.compact ? ka.count : nullptr, b.counts);
   rdrf_prof_end("scatter_sort", stream);
+  if (rc) return rc;
   RDRF_HIP(hipGetLastError());
   return 0;
 }

@@ -17,6 +17,7 @@
 
 #include "rdrf_bwd_dev.hpp"
 #include "rdrf_bwd_host.hpp"
+#include "rdrf_sort_dev.hpp"
 
 namespace {
 
@@ -434,9 +435,47 @@ extern "C" int rdrf_selftest_sort(const unsigned* keys, unsigned n, int bits, co
   return rdrf_sort_positions(keys, keys_out, order, n, bits, temp, temp_bytes, stream, count, count ? n_mul : 0u);
 }
 
+// rdrf_selftest_sort_seg: rdrf_sort_positions_seg on caller-owned arrays (nseg segments of seg_len entries, or of *count with a
+// device count; the sort builds its own first histograms here, as rdrf_selftest_sort does)
+extern "C" size_t rdrf_selftest_sort_seg_temp_bytes(int nseg, unsigned seg_len, int bits) {
+  return rdrf_sort_seg_temp_bytes(nseg, seg_len, bits);
+}
+
+extern "C" int rdrf_selftest_sort_seg(const unsigned* keys, int nseg, unsigned seg_len, int bits, const int* count, unsigned* keys_out,
+                                      unsigned* order, void* temp, size_t temp_bytes, rdrf_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RDRF_CHECK(bits >= 1 && bits <= 32, -1, "selftest_sort_seg: bits must be 1 .. 32 (got %d)", bits);
+  RDRF_CHECK(nseg >= 1 && (unsigned long long)nseg * seg_len <= 0xffffffffull, -1, "selftest_sort_seg: bad segments (%d x %u)", nseg, seg_len);
+  if (seg_len == 0) return 0;   // nothing to sort: a no-op
+  RDRF_CHECK(keys && keys_out && order, -1, "selftest_sort_seg: bad arguments (null keys, keys_out or order)");
+  RDRF_CHECK(temp != nullptr && (((uintptr_t)temp) & 255) == 0, -1, "selftest_sort_seg: the temporary storage must be 256-byte aligned");
+  if (count) {
+    int c = -1;
+    RDRF_HIP(hipMemcpyAsync(&c, count, sizeof(int), hipMemcpyDeviceToHost, stream));
+    RDRF_HIP(hipStreamSynchronize(stream));
+    RDRF_CHECK(c >= 0, -1, "selftest_sort_seg: device count %d out of range", c);
+  }
+  return rdrf_sort_positions_seg(keys, keys_out, order, nseg, seg_len, bits, temp, temp_bytes, stream, count, nullptr);
+}
+
+// The sort's plan in resolved form (host only): [0] values used, [1] passes, [2] bits per digit, [3] tiles per segment, [4] entries
+// per tile, [5] bytes the sort carves out of its temporary storage, [6] rdrf_selftest_sort_seg_temp_bytes, [7] launches of a sort
+// that builds its own first histograms, [8] launches of a sorted-scatter call (key kernel + sort, first histograms by the key kernel)
+extern "C" int rdrf_selftest_sort_describe(int nseg, unsigned seg_len, int bits, unsigned long long* out, int cap) {
+  RDRF_CHECK(bits >= 1 && bits <= 32 && nseg >= 1, -1, "selftest_sort_describe: bad arguments (bits %d, segments %d)", bits, nseg);
+  RDRF_CHECK(out != nullptr && cap >= 9, -3, "selftest_sort_describe: room for 9 values needed");
+  int passes, db;
+  rdrf_sort_plan(bits, &passes, &db);
+  out[0] = 9; out[1] = (unsigned long long)passes; out[2] = (unsigned long long)db;
+  out[3] = ((unsigned long long)seg_len + RS_TILE - 1) / RS_TILE; out[4] = RS_TILE;
+  out[5] = rdrf_sort_carved_bytes(nseg, seg_len); out[6] = rdrf_sort_seg_temp_bytes(nseg, seg_len, bits);
+  out[7] = 3ull * passes; out[8] = 3ull * passes;   // (key kernel + (3 passes - the first histogram))
+  return 9;
+}
+
 // ------------------------------------------------------------------------------------------------
 // rdrf_selftest_scatter: the four instantiations of the scatter in use, with the arguments their backward entry points give
-// them (rdrf_bwd.hip), through launch_scatter (ray tiles) or scatter_dyn_*_sorted (key generation, sort, count search, sorted /
+// them (rdrf_bwd.hip), through launch_scatter (ray tiles) or scatter_dyn_*_sorted (key generation, sort and counts, sorted /
 // tiled passes).
 // ------------------------------------------------------------------------------------------------
 namespace {
@@ -492,7 +531,7 @@ bool scatter_vm_ok(const RdrfVM& v, const RdrfVM& g, int c0, int c1) {
 extern "C" size_t rdrf_selftest_scatter_workspace_bytes(int N, int S) {
   const size_t ns = (size_t)(N > 0 ? N : 0) * (size_t)(S > 0 ? S : 0);
   const size_t arr = (3 * ns * 4 + 255) & ~(size_t)255;
-  return 3 * arr + 256 + ((rdrf_sort_temp_bytes((unsigned)(3 * ns), 32) + 255) & ~(size_t)255) + 512;
+  return 3 * arr + 256 + ((rdrf_sort_seg_temp_bytes(3, (unsigned)ns, 32) + 255) & ~(size_t)255) + 512;
 }
 
 extern "C" int rdrf_selftest_scatter(int kind, int mode, const RdrfScatterTest* t, rdrf_stream_t stream_) {
@@ -579,7 +618,7 @@ extern "C" int rdrf_selftest_scatter(int kind, int mode, const RdrfScatterTest* 
   b.keys_out = c.take<unsigned>(3 * ns);
   b.order = c.take<unsigned>(3 * ns);
   b.counts = c.take<int>(64);
-  b.sort_tmp_bytes = rdrf_sort_temp_bytes((unsigned)(3 * ns), 32);
+  b.sort_tmp_bytes = rdrf_sort_seg_temp_bytes(3, (unsigned)ns, 32);
   b.sort_tmp = c.take<char>(b.sort_tmp_bytes);
   RDRF_CHECK(c.ok(), -3, "selftest_scatter: workspace too small");
   b.dxw = t->dxw;
