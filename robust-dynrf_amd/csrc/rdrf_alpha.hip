@@ -12,13 +12,6 @@
 //                  into the `valid` bytes of a ray batch for up to two masks
 #include "rdrf_fwd_dev.hpp"
 
-// host helpers of rdrf_fwd.hip
-void dyn_pack_jobs_fwd(PackJobs& J, const RdrfDynamicParams* P);
-void fill_static_w(StaticW& w, const RdrfStaticParams* P);
-void fill_dyn_w(DynW& w, const RdrfDynamicParams* P);
-
-#define ALPHA_PACK_FLOATS (1 << 20) /* the pack area of the field entry points (rdrf_fwd.hip) */
-
 // ------------------------------------------------------------------------------------------------
 // the packed occupancy grid on the device: bit f = ((iz G1 + iy) G0 + ix) T + k of the buffer, most significant bit of
 // a byte first (np.packbits)
@@ -246,9 +239,17 @@ __global__ __launch_bounds__(256) void k_alpha_static(AlphaArgs a, StaticW w) {
   }
 }
 
+// workspace of the dynamic field's alpha: the pack area and the time branch of the T times (nothing is kept per point)
+static void carve_alpha(float*& pk, float*& tout, WsCarver& c, int T) {
+  pk = c.take<float>(PACK_AREA_FLOATS);
+  tout = c.take<float>((size_t)(T > 0 ? T : 0) * 32);
+}
 extern "C" size_t rdrf_compute_alpha_workspace_bytes(int M, int T) {
-  (void)M;   // the kernels keep nothing per point
-  return (size_t)ALPHA_PACK_FLOATS * 4 + (((size_t)(T > 0 ? T : 0) * 32 * 4 + 255) & ~(size_t)255) + 1024;
+  (void)M;
+  float *pk, *tout;
+  WsCarver c;
+  carve_alpha(pk, tout, c, T);
+  return c.off;
 }
 
 extern "C" int rdrf_compute_alpha(const void* params, int dynamic, const RdrfFieldCfg* cfg, const float* xyz, int M,
@@ -280,30 +281,17 @@ extern "C" int rdrf_compute_alpha(const void* params, int dynamic, const RdrfFie
              "compute_alpha: only density comps {16,4,4}, the planes and lines of a set spanning one grid, are built");
   RDRF_CHECK(ws != nullptr, -3, "compute_alpha: no workspace");
   WsCarver c(ws, ws_bytes);
-  float* pkbuf = c.take<float>(ALPHA_PACK_FLOATS);
-  float* tout = c.take<float>((size_t)T * 32);
+  float *pkbuf, *tout;
+  carve_alpha(pkbuf, tout, c, T);
   RDRF_CHECK(c.ok(), -3, "compute_alpha: workspace too small: need %zu have %zu", c.off, ws_bytes);
   DynW w;
   fill_dyn_w(w, P);
-  if (P->packed_fwd != nullptr) a.pk = P->packed_fwd;   // caller-packed image (rdrf_dynamic_pack)
-  else {
-    PackJobs J;
-    dyn_pack_jobs_fwd(J, P);
-    int rc = pack_launch(J, pkbuf, stream);
-    if (rc) return rc;
-    a.pk = pkbuf;
-  }
+  RDRF_TRY(pack_image(a.pk, P->packed_fwd, pkbuf, stream, dyn_pack_jobs_fwd, P));
   a.tout = tout;
   a.dynq = 1;
   RDRF_LAUNCH("time_branch", k_alpha_time_branch, dim3((T + 7) / 8), dim3(256), stream, times, w, T, tout);
-  // persistent geometry of the field kernels: one workgroup per CU (its LDS holds the image), up to 8 waves
-  const long tiles = ((long)M + 31) / 32;
-  const int ncu = 256;
-  long waves = (tiles + ncu - 1) / ncu;
-  waves = waves < 1 ? 1 : (waves > RDRF_MAXW ? RDRF_MAXW : waves);
-  long blocks = (tiles + waves - 1) / waves;
-  blocks = blocks < 1 ? 1 : (blocks > ncu ? ncu : blocks);
-  RDRF_LAUNCH("alpha_dyn", k_alpha_dyn, dim3((unsigned)blocks), dim3((unsigned)waves * 64), stream, a, w);
+  const Geo g = geo_for_units(((long)M + 31) / 32);   // the persistent geometry of the field kernels
+  RDRF_LAUNCH("alpha_dyn", k_alpha_dyn, dim3(g.grid), dim3(g.block), stream, a, w);
   return 0;
 }
 

@@ -1022,29 +1022,21 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_scene_flow_bwd(int N, int S,
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-void fill_static_w(StaticW& w, const RdrfStaticParams* P);
-void fill_dyn_w(DynW& w, const RdrfDynamicParams* P);
-
-static void dyn_pack_jobs_bwd(PackJobs& J, const RdrfDynamicParams* P) {
+void dyn_pack_jobs_bwd(PackJobs& J, const RdrfDynamicParams* P) {
   using namespace pkb;
   J.n = 0;
   const int kh = REG_K1H, kw = REG_K1W, k3 = REG_K3, sf = REG_SF;
   pack_add(J, P->l5w, 64, 3, 64, SEG_IDENT, 1, 3, 32, kw + K1W_W5);
 #ifdef RDRF_HEADS_BWD_F32
-  const int wm = 2;
+  const int wm = 2, hm = 2;
 #else
-  const int wm = 8;   // bf16 x 3 transposed fragments
+  const int wm = 8, hm = 8;   // bf16 x 3 transposed fragments
 #endif
   pack_add(J, P->l4w, 64, 64, 64, SEG_IDENT, wm, 2, 32, kw + K1W_W4T);
   pack_add(J, P->l3w, 93, 64, 93, SEG_WARP3_X0, wm, 2, 32, kw + K1W_W3T_X0);
   pack_add(J, P->l3w, 93, 64, 93, SEG_WARP3_T, wm, 1, 32, kw + K1W_W3T_T);
   pack_add(J, P->dw2, 64, 1, 64, SEG_IDENT, 1, 1, 32, kh + K1H_DEN2);
   pack_add(J, P->bw2, 64, 1, 64, SEG_IDENT, 1, 1, 32, kh + K1H_BLE2);
-#ifdef RDRF_HEADS_BWD_F32
-  const int hm = 2;
-#else
-  const int hm = 8;   // bf16 x 3 transposed fragments
-#endif
   pack_add(J, P->dw1, 152, 64, 72, SEG_IDENT, hm, 3, 32, kh + K1H_DEN1T_F);
   pack_add(J, P->dw1, 152, 64, 152, SEG_DEN1_X0, hm, 2, 32, kh + K1H_DEN1T_X0);
   pack_add(J, P->bw1, 152, 64, 72, SEG_IDENT, hm, 3, 32, kh + K1H_BLE1T_F);
@@ -1067,7 +1059,7 @@ static void dyn_pack_jobs_bwd(PackJobs& J, const RdrfDynamicParams* P) {
   pack_add(J, P->sfw[0], 36, 64, 36, SEG_SF_X, 2, 2, 32, sf + SF_W0T);
 }
 
-static void static_pack_jobs_bwd(PackJobs& J, const RdrfStaticParams* P, int head) {
+void static_pack_jobs_bwd(PackJobs& J, const RdrfStaticParams* P, int head) {
   using namespace pkb;
   J.n = 0;
   const bool fea = head == RDRF_HEAD_MLP_FEA;
@@ -1086,21 +1078,6 @@ static void static_pack_jobs_bwd(PackJobs& J, const RdrfStaticParams* P, int hea
 #endif
 }
 
-struct Geo {
-  int grid, block;
-};
-static Geo geo_for_units(long units) {
-  Geo g;
-  const int ncu = 256;
-  int waves = (int)((units + ncu - 1) / ncu);
-  waves = waves < 1 ? 1 : (waves > RDRF_MAXW ? RDRF_MAXW : waves);
-  g.block = waves * 64;
-  long blocks = (units + waves - 1) / waves;
-  g.grid = (int)(blocks < 1 ? 1 : (blocks > ncu ? ncu : blocks));
-  return g;
-}
-
-#define PACK_AREA_FLOATS (1 << 20)
 static_assert(pkb::REG_K3_LO + pkb::K3_LO_SIZE <= PACK_AREA_FLOATS && pkb::REG_S3_LO + pkb::S3_LO_SIZE <= PACK_AREA_FLOATS,
               "the backward images and their streamed lo pieces fit the pack area");
 
@@ -1115,29 +1092,44 @@ static void fill_bwd_common(BwdArgs& a, const RdrfFieldCfg* cfg, const float* ra
   a.dynq = 1;   // per-workgroup tile queue (tile_queue_next)
 }
 
-// forward calls (either field, scene flow): pack area + counter + tout + xw + list -- what an inference-only caller needs
-extern "C" size_t rdrf_forward_workspace_bytes(int N, int S) {
-  const size_t ns = (size_t)N * S;
-  return (size_t)PACK_AREA_FLOATS * 4 + 256 + (size_t)N * 32 * 4 + ns * 3 * 4 + ns * 4 + (1 << 12);
+static void fill_static_g(StaticG& g, const RdrfStaticParams* G) {
+  g.density = G->density; g.app = G->app; g.b3 = G->b3; g.w3 = G->w3;
+}
+static void fill_dyn_g(DynG& g, const RdrfDynamicParams* G) {
+  g.density = G->density; g.blending = G->blending; g.app = G->app;
+  g.rbv = G->rbv; g.rwv = G->rwv; g.l5b = G->l5b; g.db2 = G->db2; g.bb2 = G->bb2;
+  g.l5w = G->l5w; g.dw2 = G->dw2; g.bw2 = G->bw2;
 }
 
-extern "C" size_t rdrf_workspace_bytes(int N, int S) {
-  size_t ns = (size_t)N * S, t1 = (size_t)N * ((S + 31) / 32), t3 = (ns + 31) / 32;
-  size_t fwd = rdrf_forward_workspace_bytes(N, S);
-  // backward: pack area + dz rows of both phases + coordinate-gradient buffers + d(tout)
-  size_t bwd = (size_t)PACK_AREA_FLOATS * 4 + t1 * sv::K1G_ROWS * 32 * 4 + t3 * sv::K3G_ROWS * 32 * 4 +
-               ns * 3 * 4 * 2 + (size_t)N * 32 * 4 + (1 << 14);
-  // sorted scatter: sample-major d(feature) records, keys in / out, sorted positions, counters, radix-sort scratch
-  bwd += ns * DFS_FLOATS * 4 + ns * DFA_FLOATS * 4 + 3 * ns * 4 * 3 + 1024 + rdrf_sort_seg_temp_bytes(3, (unsigned)ns, 32) + (1 << 12);
-  // flat-tile density phase: total d(sigma) per sample + the d(tout) partial records of the tiles
-  bwd += ns * 4 + t3 * 64 * 4 + 512;
-  size_t sf = (size_t)PACK_AREA_FLOATS * 4 + t3 * sv::SFG_ROWS * 32 * 4 + (1 << 12);
-  size_t m = fwd > bwd ? fwd : bwd;
-  return m > sf ? m : sf;
+// `valid` of a feature-mode batch: 1 for the M points, 0 for the padding of the last 32-point tile
+static int pad_valid_tiles(uint8_t* valid, int M, size_t mp, hipStream_t stream) {
+  RDRF_FILL(valid, 0, mp, stream);
+  RDRF_FILL(valid, 1, (size_t)M, stream);
+  return 0;
 }
 
-static int carve_bwd(BwdWs& b, void* ws, size_t ws_bytes, int N, int S, int dynamic) {
-  WsCarver c(ws, ws_bytes);
+// ScatterArgs (after fill_scatter_common) of one appearance factor set: the DA rows of the appearance phase
+static void scatter_app_set(ScatterArgs& sa, const RdrfVM& vm, const RdrfVM& gvm, const float* grows3) {
+  sa.vm[0] = vm; sa.gvm[0] = gvm; sa.nsets = 1;
+  sa.rows = grows3; sa.stride = sv::K3G_ROWS; sa.row0[0] = sv::K3G_DA;
+}
+// ... and of the density / blending sets.  A head without an upstream gradient (passes B-D of the trainer carry none for the
+// blending head before the late mask terms) has d(features) == 0 and wrote no rows (k_dyn_density_bwd<0>): its factor set is
+// left out of the launch instead of being walked with zeros
+static void scatter_head_sets(ScatterArgs& sa, const BwdArgs& a, const RdrfDynamicParams* P, const RdrfDynamicParams* G,
+                              bool has_d, bool has_b, float* dxw) {
+  sa.nsets = 0;
+  if (has_d) { sa.vm[sa.nsets] = P->density; sa.gvm[sa.nsets] = G->density; sa.row0[sa.nsets] = sv::K1G_DFD; ++sa.nsets; }
+  if (has_b) { sa.vm[sa.nsets] = P->blending; sa.gvm[sa.nsets] = G->blending; sa.row0[sa.nsets] = sv::K1G_DFB; ++sa.nsets; }
+  sa.rows = a.grows1; sa.stride = sv::K1G_ROWS;
+  sa.xw = a.sp.xw;
+  sa.dxw = dxw; sa.dxw_accumulate = 1;
+}
+
+// backward workspace of either field.  dynamic: dz rows of both phases, coordinate-gradient buffers, d(tout); the sorted
+// scatter's sample-major d(feature) records and sort buffers; the flat-tile density phase's total d(sigma) per sample and
+// the d(tout) partial records of the tiles
+static void carve_bwd(BwdWs& b, WsCarver& c, int N, int S, int dynamic) {
   size_t ns = (size_t)N * S, t1 = (size_t)N * ((S + 31) / 32), t3 = (ns + 31) / 32;
   b.pk = c.take<float>(PACK_AREA_FLOATS);
   b.grows3 = c.take<float>(t3 * sv::K3G_ROWS * 32);
@@ -1152,17 +1144,39 @@ static int carve_bwd(BwdWs& b, void* ws, size_t ws_bytes, int N, int S, int dyna
   if (dynamic) {
     b.dfs = c.take<float>(ns * DFS_FLOATS);
     b.dfa = c.take<float>(ns * DFA_FLOATS);
-    b.keys_in = c.take<unsigned>(3 * ns);
-    b.keys_out = c.take<unsigned>(3 * ns);
-    b.order = c.take<unsigned>(3 * ns);
-    b.counts = c.take<int>(64);
-    b.sort_tmp_bytes = rdrf_sort_seg_temp_bytes(3, (unsigned)ns, 32);
-    b.sort_tmp = c.take<char>(b.sort_tmp_bytes);
+    carve_sorted_scatter(b, c, ns);
     b.gsig = c.take<float>(ns);
     b.dtp = c.take<float>(t3 * 64);
   }
+}
+static int carve_bwd(BwdWs& b, void* ws, size_t ws_bytes, int N, int S, int dynamic) {
+  WsCarver c(ws, ws_bytes);
+  carve_bwd(b, c, N, S, dynamic);
   RDRF_CHECK(c.ok(), -3, "backward workspace too small: need %zu have %zu", c.off, ws_bytes);
   return 0;
+}
+// scene flow backward: the two-kernel path (k_scene_flow_bwd + dw_sf) carries its dz rows through the workspace
+static void carve_sf_bwd(float*& pk, float*& grows, WsCarver& c, size_t tiles, bool fused) {
+  pk = c.take<float>(PACK_AREA_FLOATS);
+  grows = fused ? nullptr : c.take<float>(tiles * sv::SFG_ROWS * 32);
+}
+
+// One workspace serves every call of a training step: the largest of the three backward carves and the forward size.  The
+// dynamic carve decides at every shape -- it has the pack area and the appearance rows of the static one and t1 * K1G_ROWS
+// * 32 floats of density rows against t1 * 32, more appearance rows than the scene flow has rows at all (K3G_ROWS >
+// SFG_ROWS), and 28 N S bytes of coordinate and sigma buffers against the forward's 16 N S -- the others are kept in the
+// maximum so that this stays true by construction.
+extern "C" size_t rdrf_workspace_bytes(int N, int S) {
+  BwdWs b;
+  float *pk, *grows;
+  WsCarver st, dy, sf;
+  carve_bwd(b, st, N, S, 0);
+  carve_bwd(b, dy, N, S, 1);
+  carve_sf_bwd(pk, grows, sf, ((size_t)N * S + 31) / 32, false);
+  size_t m = rdrf_forward_workspace_bytes(N, S);
+  m = st.off > m ? st.off : m;
+  m = dy.off > m ? dy.off : m;
+  return sf.off > m ? sf.off : m;
 }
 
 // dW jobs of the dynamic field's density phase (warp MLP, density / blending heads)
@@ -1309,20 +1323,13 @@ extern "C" int rdrf_static_bwd(const RdrfStaticParams* P, const RdrfFieldCfg* cf
   RDRF_CHECK(saved_kind == 1 || g_rgb == nullptr, -1,
              "static_bwd: the forward saved no appearance rows (RDRF_SAVE_NO_APP): no gradient can flow through rgb");
   BwdWs b;
-  int rc = carve_bwd(b, ws, ws_bytes, N, S, 0);
-  if (rc) return rc;
-  a.pk = b.pk; a.grows3 = b.grows3;
+  RDRF_TRY(carve_bwd(b, ws, ws_bytes, N, S, 0));
+  a.grows3 = b.grows3;
   StaticW w;
   fill_static_w(w, P);
   StaticG gw;
-  gw.density = G->density; gw.app = G->app; gw.b3 = G->b3; gw.w3 = G->w3;
-  if (P->packed_bwd != nullptr) a.pk = P->packed_bwd;   // caller-packed image (rdrf_static_pack)
-  else {
-    PackJobs J;
-    static_pack_jobs_bwd(J, P, cfg->static_head);
-    rc = pack_launch(J, b.pk, stream);
-    if (rc) return rc;
-  }
+  fill_static_g(gw, G);
+  RDRF_TRY(pack_image(a.pk, P->packed_bwd, b.pk, stream, static_pack_jobs_bwd, P, cfg->static_head));
   const size_t t3 = ((size_t)N * S + 31) / 32;
   if (g_rgb != nullptr) {
     const Geo g = geo_for_units((long)t3);
@@ -1332,22 +1339,17 @@ extern "C" int rdrf_static_bwd(const RdrfStaticParams* P, const RdrfFieldCfg* cf
     else
       RDRF_LAUNCH("static_app_bwd", (k_static_app_bwd<RDRF_HEAD_MLP_FEA_TIMEEMBEDDING, false>), dim3(g.grid),
                   dim3(g.block), stream, a, w, gw);
-    {
-      ScatterArgs sa;
-      fill_scatter_common(sa, a);
-      sa.vm[0] = P->app; sa.gvm[0] = G->app; sa.nsets = 1;
-      sa.rows = b.grows3; sa.stride = sv::K3G_ROWS; sa.row0[0] = sv::K3G_DA;
-      sa.list = a.sp.list; sa.count = &a.sp.hdr->count;
-      sa.g_xyz = g_xyz;
-      { int rc_ = launch_scatter("scatter_static_app", SCATTER_12_3_9, sa, (long)t3, stream); if (rc_) return rc_; }
-    }
-    const bool fea = cfg->static_head == RDRF_HEAD_MLP_FEA;
     const int* cnt = &a.sp.hdr->count;
+    ScatterArgs sa;
+    fill_scatter_common(sa, a);
+    scatter_app_set(sa, P->app, G->app, b.grows3);
+    sa.list = a.sp.list; sa.count = cnt;
+    sa.g_xyz = g_xyz;
+    RDRF_TRY(launch_scatter("scatter_static_app", SCATTER_12_3_9, sa, (long)t3, stream));
     DwJobs D;
     D.n = 0;
-    add_static_app_dw(D, b.grows3, a.sp.act3, G, fea, cnt, 0);
-    rc = dw_launch(D, stream, "dw_static");
-    if (rc) return rc;
+    add_static_app_dw(D, b.grows3, a.sp.act3, G, cfg->static_head == RDRF_HEAD_MLP_FEA, cnt, 0);
+    RDRF_TRY(dw_launch(D, stream, "dw_static"));
   }
   if (g_sigma != nullptr || g_weight != nullptr || ((g_rays != nullptr || g_z != nullptr) && g_dists != nullptr)) {
     RDRF_LAUNCH("static_density_bwd", k_static_density_bwd, dim3(N), dim3(64), stream, a, w, b.gf);
@@ -1357,8 +1359,7 @@ extern "C" int rdrf_static_bwd(const RdrfStaticParams* P, const RdrfFieldCfg* cf
       sa.vm[0] = P->density; sa.gvm[0] = G->density; sa.nsets = 1;
       sa.rows = b.gf; sa.stride = 1; sa.row0[0] = 0; sa.bcast = 1;
       sa.g_xyz = g_xyz;
-      const long t1 = (long)N * ((S + 31) / 32);
-      { int rc_ = launch_scatter("scatter_static_density", SCATTER_4_1_3, sa, t1, stream); if (rc_) return rc_; }
+      RDRF_TRY(launch_scatter("scatter_static_density", SCATTER_4_1_3, sa, (long)N * ((S + 31) / 32), stream));
     }
   }
   return 0;
@@ -1388,9 +1389,8 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
   RDRF_CHECK(saved_kind == 1 || g_rgb == nullptr, -1,
              "dynamic_bwd: the forward saved no appearance rows (RDRF_SAVE_NO_APP): no gradient can flow through rgb");
   BwdWs b;
-  int rc = carve_bwd(b, ws, ws_bytes, N, S, 1);
-  if (rc) return rc;
-  a.pk = b.pk; a.grows1 = b.grows1; a.grows3 = b.grows3; a.dxw_app = b.dxw; a.dxn_app = b.dxn;
+  RDRF_TRY(carve_bwd(b, ws, ws_bytes, N, S, 1));
+  a.grows1 = b.grows1; a.grows3 = b.grows3; a.dxw_app = b.dxw; a.dxn_app = b.dxn;
   a.dtout = b.dtout;
   // the density phase on flat 32-sample tiles (the forward wrote its saved rows that way: rdrf_dynamic_fwd)
   const bool flat = rdrf_flat_density();
@@ -1398,16 +1398,8 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
   DynW w;
   fill_dyn_w(w, P);
   DynG gw;
-  gw.density = G->density; gw.blending = G->blending; gw.app = G->app;
-  gw.rbv = G->rbv; gw.rwv = G->rwv; gw.l5b = G->l5b; gw.db2 = G->db2; gw.bb2 = G->bb2;
-  gw.l5w = G->l5w; gw.dw2 = G->dw2; gw.bw2 = G->bw2;
-  if (P->packed_bwd != nullptr) a.pk = P->packed_bwd;   // caller-packed image (rdrf_dynamic_pack)
-  else {
-    PackJobs J;
-    dyn_pack_jobs_bwd(J, P);
-    rc = pack_launch(J, b.pk, stream);
-    if (rc) return rc;
-  }
+  fill_dyn_g(gw, G);
+  RDRF_TRY(pack_image(a.pk, P->packed_bwd, b.pk, stream, dyn_pack_jobs_bwd, P));
   const size_t ns = (size_t)N * S, t3 = (ns + 31) / 32, t1 = flat ? t3 : (size_t)N * ((S + 31) / 32);   // density-phase tiles
   RDRF_FILL(b.dxw, 0, ns * 3 * 4, stream);
   RDRF_FILL(b.dxn, 0, ns * 3 * 4, stream);
@@ -1422,17 +1414,16 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
     else RDRF_LAUNCH("dyn_app_bwd", (k_dyn_app_bwd<false, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
     if (smode_app != 0) {
       rdrf_prof_begin("scatter_dyn_app", stream);
-      rc = scatter_dyn_app_sorted(a, b, P, G, stream);
+      const int rc = scatter_dyn_app_sorted(a, b, P, G, stream);
       rdrf_prof_end("scatter_dyn_app", stream);
       if (rc) return rc;
     } else {
       ScatterArgs sa;
       fill_scatter_common(sa, a);
-      sa.vm[0] = P->app; sa.gvm[0] = G->app; sa.nsets = 1;
-      sa.rows = b.grows3; sa.stride = sv::K3G_ROWS; sa.row0[0] = sv::K3G_DA;
+      scatter_app_set(sa, P->app, G->app, b.grows3);
       sa.xw = a.sp.xw; sa.list = a.sp.list; sa.count = cnt;
       sa.dxw = b.dxw; sa.dxw_accumulate = 0;
-      { int rc_ = launch_scatter("scatter_dyn_app", SCATTER_12_3_27, sa, (long)t3, stream); if (rc_) return rc_; }
+      RDRF_TRY(launch_scatter("scatter_dyn_app", SCATTER_12_3_27, sa, (long)t3, stream));
     }
     add_dyn_app_dw(D, b.grows3, a.sp.act3, G, cnt, 0);
   }
@@ -1444,42 +1435,30 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
       RDRF_LAUNCH("ray_scan_bwd", k_ray_scan_bwd, dim3((N + 15) / 16), dim3(512), stream, a);   // 16 rays per workgroup
       RDRF_LAUNCH("dyn_heads_bwd", (k_dyn_density_bwd<0, false, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
     } else RDRF_LAUNCH("dyn_heads_bwd", (k_dyn_density_bwd<0, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+    const bool has_d = g_sigma != nullptr || g_weight != nullptr, has_b = g_blending != nullptr;
     if (smode != 0) {
-      const int set_mask = ((g_sigma != nullptr || g_weight != nullptr) ? 1 : 0) | (g_blending != nullptr ? 2 : 0);
-      if (set_mask != 0) {
+      if (has_d || has_b) {
         rdrf_prof_begin("scatter_dyn_density", stream);
-        rc = scatter_dyn_density_sorted(a, b, P, G, set_mask, stream);
+        const int rc = scatter_dyn_density_sorted(a, b, P, G, (has_d ? 1 : 0) | (has_b ? 2 : 0), stream);
         rdrf_prof_end("scatter_dyn_density", stream);
         if (rc) return rc;
       }
-    } else {
-      // a head without an upstream gradient (passes B-D of the trainer carry none for the blending head before the late
-      // mask terms) has d(features) == 0: its factor set is left out of the launch instead of being walked with zeros
-      const bool has_d = g_sigma != nullptr || g_weight != nullptr, has_b = g_blending != nullptr;
-      if (has_d || has_b) {
-        ScatterArgs sa;
-        fill_scatter_common(sa, a);
-        sa.nsets = 0;
-        if (has_d) { sa.vm[sa.nsets] = P->density; sa.gvm[sa.nsets] = G->density; sa.row0[sa.nsets] = sv::K1G_DFD; ++sa.nsets; }
-        if (has_b) { sa.vm[sa.nsets] = P->blending; sa.gvm[sa.nsets] = G->blending; sa.row0[sa.nsets] = sv::K1G_DFB; ++sa.nsets; }
-        sa.rows = b.grows1; sa.stride = sv::K1G_ROWS; sa.flat = flat ? 1 : 0;
-        sa.xw = a.sp.xw;
-        sa.dxw = b.dxw; sa.dxw_accumulate = 1;
-        { int rc_ = launch_scatter("scatter_dyn_density", SCATTER_4_1_9, sa, (long)t1, stream); if (rc_) return rc_; }
-      }
+    } else if (has_d || has_b) {
+      ScatterArgs sa;
+      fill_scatter_common(sa, a);
+      scatter_head_sets(sa, a, P, G, has_d, has_b, b.dxw);
+      sa.flat = flat ? 1 : 0;
+      RDRF_TRY(launch_scatter("scatter_dyn_density", SCATTER_4_1_9, sa, (long)t1, stream));
     }
     const bool warp_fused = warp_fused_path(flat, a.small_dw != 0);
-    if (warp_fused) { int rc_ = launch_warp_fused(a, gw, G, (long)t1, stream); if (rc_) return rc_; }
+    if (warp_fused) RDRF_TRY(launch_warp_fused(a, gw, G, (long)t1, stream));
     else if (flat) RDRF_LAUNCH("dyn_warp_bwd", (k_dyn_density_bwd<1, false, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
     else RDRF_LAUNCH("dyn_warp_bwd", (k_dyn_density_bwd<1, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
     RDRF_LAUNCH("time_branch_bwd", k_time_branch_bwd, dim3((N + TB_RPB - 1) / TB_RPB), dim3(128), stream, ts, w,
                 N, b.dtout, flat ? (const float*)b.dtp : nullptr, S, G->l1w, G->l1b, G->l2w, G->l2b);
-    const bool small_in_kernel = a.small_dw != 0;
-    add_density_phase_dw(D, b.grows1, a.sp.act1, G, (int)t1, g_sigma != nullptr || g_weight != nullptr, g_blending != nullptr,
-                         small_in_kernel, warp_fused);
+    add_density_phase_dw(D, b.grows1, a.sp.act1, G, (int)t1, has_d, has_b, a.small_dw != 0, warp_fused);
   }
-  rc = dw_launch(D, stream, "dw_dyn");
-  return rc;
+  return dw_launch(D, stream, "dw_dyn");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1490,8 +1469,7 @@ struct FeatWs {
   float *pk, *grows3, *grows1, *dxw, *dxn, *dtout, *gpad, *xpad;
   uint8_t* valid;
 };
-static int carve_feat_bwd(FeatWs& b, void* ws, size_t ws_bytes, int M, int dynamic) {
-  WsCarver c(ws, ws_bytes);
+static void carve_feat_bwd(FeatWs& b, WsCarver& c, int M, int dynamic) {
   const size_t t = ((size_t)M + 31) / 32, mp = t * 32;
   b.pk = c.take<float>(PACK_AREA_FLOATS);
   b.grows3 = c.take<float>(t * sv::K3G_ROWS * 32);
@@ -1502,13 +1480,19 @@ static int carve_feat_bwd(FeatWs& b, void* ws, size_t ws_bytes, int M, int dynam
   b.gpad = dynamic ? nullptr : c.take<float>(mp);
   b.xpad = dynamic ? nullptr : c.take<float>(mp * 3);
   b.valid = c.take<uint8_t>(mp);
+}
+static int carve_feat_bwd(FeatWs& b, void* ws, size_t ws_bytes, int M, int dynamic) {
+  WsCarver c(ws, ws_bytes);
+  carve_feat_bwd(b, c, M, dynamic);
   RDRF_CHECK(c.ok(), -3, "features backward: workspace too small: need %zu have %zu", c.off, ws_bytes);
   return 0;
 }
-extern "C" size_t rdrf_features_bwd_workspace_bytes(int M) {
-  const size_t t = ((size_t)M + 31) / 32, mp = t * 32;
-  return (size_t)PACK_AREA_FLOATS * 4 + t * (sv::K3G_ROWS + sv::K1G_ROWS) * 32 * 4 + mp * (6 + 32 + 4) * 4 + mp +
-         (1 << 14);
+extern "C" size_t rdrf_features_bwd_workspace_bytes(int M) {   // of either field: the dynamic carve is the larger one
+  FeatWs b;
+  WsCarver st, dy;
+  carve_feat_bwd(b, st, M, 0);
+  carve_feat_bwd(b, dy, M, 1);
+  return st.off > dy.off ? st.off : dy.off;
 }
 
 extern "C" int rdrf_static_features_bwd(const RdrfStaticParams* P, const RdrfFieldCfg* cfg, const float* xn,
@@ -1523,15 +1507,13 @@ extern "C" int rdrf_static_features_bwd(const RdrfStaticParams* P, const RdrfFie
   const int Np = (M + 31) / 32;
   const size_t mp = (size_t)Np * 32;
   FeatWs b;
-  int rc = carve_feat_bwd(b, ws, ws_bytes, M, 0);
-  if (rc) return rc;
+  RDRF_TRY(carve_feat_bwd(b, ws, ws_bytes, M, 0));
   BwdArgs a;
   fill_bwd_common(a, cfg, nullptr, nullptr, xn, nullptr, b.valid, Np, 32);
   a.M = M; a.in_norm = 1; a.g_feat = g_app; a.pk = b.pk; a.grows3 = b.grows3;
   if (saved != nullptr)
     RDRF_CHECK(carve_saved_feat(a.sp, saved, saved_bytes, 0, M), -3, "static_features_bwd: saved buffer too small");
-  RDRF_FILL(b.valid, 0, mp, stream);
-  RDRF_FILL(b.valid, 1, (size_t)M, stream);
+  RDRF_TRY(pad_valid_tiles(b.valid, M, mp, stream));
   RDRF_FILL(b.xpad, 0, mp * 3 * 4, stream);
   RDRF_HIP(hipMemcpyAsync(b.xpad, xn, (size_t)M * 3 * 4, hipMemcpyDeviceToDevice, stream));
   ScatterArgs sa0;
@@ -1545,32 +1527,24 @@ extern "C" int rdrf_static_features_bwd(const RdrfStaticParams* P, const RdrfFie
     ScatterArgs sa = sa0;
     sa.vm[0] = P->density; sa.gvm[0] = G->density; sa.nsets = 1;
     sa.rows = b.gpad; sa.stride = 1; sa.row0[0] = 0; sa.bcast = 1;
-    { int rc_ = launch_scatter("feat_scatter_static_density", SCATTER_4_1_3, sa, (long)Np, stream); if (rc_) return rc_; }
+    RDRF_TRY(launch_scatter("feat_scatter_static_density", SCATTER_4_1_3, sa, (long)Np, stream));
   }
   if (g_app != nullptr) {
     StaticW w;
     fill_static_w(w, P);
     StaticG gw;
-    gw.density = G->density; gw.app = G->app; gw.b3 = G->b3; gw.w3 = G->w3;
-    if (P->packed_bwd != nullptr) a.pk = P->packed_bwd;
-    else {
-      PackJobs J;
-      static_pack_jobs_bwd(J, P, cfg->static_head);
-      rc = pack_launch(J, b.pk, stream);
-      if (rc) return rc;
-    }
+    fill_static_g(gw, G);
+    RDRF_TRY(pack_image(a.pk, P->packed_bwd, b.pk, stream, static_pack_jobs_bwd, P, cfg->static_head));
     const Geo g = geo_for_units(Np);
     RDRF_LAUNCH("feat_static_app_bwd", (k_static_app_bwd<RDRF_HEAD_MLP_FEA, true>), dim3(g.grid), dim3(g.block),
                 stream, a, w, gw);
     ScatterArgs sa = sa0;
-    sa.vm[0] = P->app; sa.gvm[0] = G->app; sa.nsets = 1;
-    sa.rows = b.grows3; sa.stride = sv::K3G_ROWS; sa.row0[0] = sv::K3G_DA;
-    { int rc_ = launch_scatter("feat_scatter_static_app", SCATTER_12_3_9, sa, (long)Np, stream); if (rc_) return rc_; }
+    scatter_app_set(sa, P->app, G->app, b.grows3);
+    RDRF_TRY(launch_scatter("feat_scatter_static_app", SCATTER_12_3_9, sa, (long)Np, stream));
     DwJobs D;
     D.n = 0;
     add_feat_static_dw(D, b.grows3, a.sp.act3, G, Np);
-    rc = dw_launch(D, stream, "feat_dw_static");
-    if (rc) return rc;
+    RDRF_TRY(dw_launch(D, stream, "feat_dw_static"));
   }
   return 0;
 }
@@ -1587,29 +1561,19 @@ extern "C" int rdrf_dynamic_features_bwd(const RdrfDynamicParams* P, const RdrfF
   const int Np = (M + 31) / 32;
   const size_t mp = (size_t)Np * 32;
   FeatWs b;
-  int rc = carve_feat_bwd(b, ws, ws_bytes, M, 1);
-  if (rc) return rc;
+  RDRF_TRY(carve_feat_bwd(b, ws, ws_bytes, M, 1));
   BwdArgs a;
   fill_bwd_common(a, cfg, nullptr, t, x, nullptr, b.valid, Np, 32);
   a.M = M; a.in_norm = x_is_normalized ? 1 : 0;
   a.g_sigma = g_density; a.g_blending = g_blending; a.g_feat = g_app; a.g_xyz_prime = g_xyz_prime; a.g_xyz = g_x;
   RDRF_CHECK(carve_saved_feat(a.sp, saved, saved_bytes, 1, M), -3, "dynamic_features_bwd: saved buffer too small");
-  a.pk = b.pk; a.grows1 = b.grows1; a.grows3 = b.grows3; a.dxw_app = b.dxw; a.dxn_app = b.dxn; a.dtout = b.dtout;
+  a.grows1 = b.grows1; a.grows3 = b.grows3; a.dxw_app = b.dxw; a.dxn_app = b.dxn; a.dtout = b.dtout;
   DynW w;
   fill_dyn_w(w, P);
   DynG gw;
-  gw.density = G->density; gw.blending = G->blending; gw.app = G->app;
-  gw.rbv = G->rbv; gw.rwv = G->rwv; gw.l5b = G->l5b; gw.db2 = G->db2; gw.bb2 = G->bb2;
-  gw.l5w = G->l5w; gw.dw2 = G->dw2; gw.bw2 = G->bw2;
-  if (P->packed_bwd != nullptr) a.pk = P->packed_bwd;   // caller-packed image (rdrf_dynamic_pack)
-  else {
-    PackJobs J;
-    dyn_pack_jobs_bwd(J, P);
-    rc = pack_launch(J, b.pk, stream);
-    if (rc) return rc;
-  }
-  RDRF_FILL(b.valid, 0, mp, stream);
-  RDRF_FILL(b.valid, 1, (size_t)M, stream);
+  fill_dyn_g(gw, G);
+  RDRF_TRY(pack_image(a.pk, P->packed_bwd, b.pk, stream, dyn_pack_jobs_bwd, P));
+  RDRF_TRY(pad_valid_tiles(b.valid, M, mp, stream));
   RDRF_FILL(b.dxw, 0, mp * 3 * 4, stream);
   RDRF_FILL(b.dxn, 0, mp * 3 * 4, stream);
   const Geo g = geo_for_units(Np);
@@ -1619,24 +1583,18 @@ extern "C" int rdrf_dynamic_features_bwd(const RdrfDynamicParams* P, const RdrfF
     RDRF_LAUNCH("feat_dyn_app_bwd", k_dyn_app_bwd<true>, dim3(g.grid), dim3(g.block), stream, a, w, gw);
     ScatterArgs sa;
     fill_scatter_common(sa, a);
-    sa.vm[0] = P->app; sa.gvm[0] = G->app; sa.nsets = 1;
-    sa.rows = b.grows3; sa.stride = sv::K3G_ROWS; sa.row0[0] = sv::K3G_DA;
+    scatter_app_set(sa, P->app, G->app, b.grows3);
     sa.xw = a.sp.xw;
     sa.dxw = b.dxw; sa.dxw_accumulate = 0;
-    { int rc_ = launch_scatter("feat_scatter_dyn_app", SCATTER_12_3_27, sa, (long)Np, stream); if (rc_) return rc_; }
+    RDRF_TRY(launch_scatter("feat_scatter_dyn_app", SCATTER_12_3_27, sa, (long)Np, stream));
     add_feat_dyn_app_dw(D, b.grows3, a.sp.act3, G, Np);
   }
   RDRF_LAUNCH("feat_dyn_heads_bwd", (k_dyn_density_bwd<0, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
   if (g_density != nullptr || g_blending != nullptr) {
     ScatterArgs sa;
     fill_scatter_common(sa, a);
-    sa.nsets = 0;   // live heads only (see k_dyn_density_bwd<0>)
-    if (g_density != nullptr) { sa.vm[sa.nsets] = P->density; sa.gvm[sa.nsets] = G->density; sa.row0[sa.nsets] = sv::K1G_DFD; ++sa.nsets; }
-    if (g_blending != nullptr) { sa.vm[sa.nsets] = P->blending; sa.gvm[sa.nsets] = G->blending; sa.row0[sa.nsets] = sv::K1G_DFB; ++sa.nsets; }
-    sa.rows = b.grows1; sa.stride = sv::K1G_ROWS;
-    sa.xw = a.sp.xw;
-    sa.dxw = b.dxw; sa.dxw_accumulate = 1;
-    { int rc_ = launch_scatter("feat_scatter_dyn_density", SCATTER_4_1_9, sa, (long)Np, stream); if (rc_) return rc_; }
+    scatter_head_sets(sa, a, P, G, g_density != nullptr, g_blending != nullptr, b.dxw);
+    RDRF_TRY(launch_scatter("feat_scatter_dyn_density", SCATTER_4_1_9, sa, (long)Np, stream));
   }
   RDRF_LAUNCH("feat_dyn_warp_bwd", (k_dyn_density_bwd<1, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
   RDRF_LAUNCH("time_branch_bwd", k_time_branch_bwd, dim3((M + TB_RPB - 1) / TB_RPB), dim3(128), stream, t, w, M,
@@ -1661,36 +1619,25 @@ extern "C" int rdrf_scene_flow_bwd(const RdrfDynamicParams* P, const RdrfFieldCf
   // k_scene_flow_bwd + k_dw3, its A/B partner
   static const int fused = RDRF_ENV("RDRF_SF_FUSED") ? atoi(RDRF_ENV("RDRF_SF_FUSED")) : 1;
   WsCarver c(ws, ws_bytes);
-  float* pkbuf = c.take<float>(PACK_AREA_FLOATS);
-  float* grows = fused ? nullptr : c.take<float>(tiles * sv::SFG_ROWS * 32);
+  float *pkbuf, *grows;
+  carve_sf_bwd(pkbuf, grows, c, tiles, fused != 0);
   RDRF_CHECK(c.ok(), -3, "scene_flow_bwd: workspace too small: need %zu have %zu", c.off, ws_bytes);
-  const float* pkimg = pkbuf;
-  int rc = 0;
-  if (P->packed_bwd != nullptr) pkimg = P->packed_bwd;
-  else {
-    PackJobs J;
-    dyn_pack_jobs_bwd(J, P);
-    rc = pack_launch(J, pkbuf, stream);
-    if (rc) return rc;
-  }
+  const float* pkimg;
+  RDRF_TRY(pack_image(pkimg, P->packed_bwd, pkbuf, stream, dyn_pack_jobs_bwd, P));
   if (fused)
     return launch_scene_flow_fused(N, S, make_box(cfg), pkimg, (const float*)saved, g_sf_f, g_sf_b, G, g_pts, (long)tiles, stream);
   const Geo g = geo_for_units((long)tiles);
   RDRF_LAUNCH("scene_flow_bwd", k_scene_flow_bwd, dim3(g.grid), dim3(g.block), stream, N, S,
               make_box(cfg), pkimg, (const float*)saved, grows, g_sf_f, g_sf_b, G->sfb[3], g_pts);
-  const float* act = (const float*)saved;
-  const int T = (int)tiles;
   DwJobs D;
   D.n = 0;
-  add_scene_flow_dw(D, grows, act, G, T);
+  add_scene_flow_dw(D, grows, (const float*)saved, G, (int)tiles);
   return dw_launch(D, stream, "dw_sf");
 }
 
 // ------------------------------------------------------------------------------------------------
 // caller-managed packed weight images (include/rodynrf.h)
 // ------------------------------------------------------------------------------------------------
-void dyn_pack_jobs_fwd(PackJobs& J, const RdrfDynamicParams* P);
-void static_pack_jobs_fwd(PackJobs& J, const RdrfStaticParams* P, int head);
 extern "C" size_t rdrf_pack_floats(void) { return PACK_AREA_FLOATS; }
 extern "C" int rdrf_static_pack(const RdrfStaticParams* P, int static_head, int backward, float* image,
                                 rdrf_stream_t stream_) {
@@ -1709,7 +1656,6 @@ extern "C" int rdrf_dynamic_pack(const RdrfDynamicParams* P, int backward, float
 // ------------------------------------------------------------------------------------------------
 // the warp MLP backward alone on caller-supplied rows (rdrf_bwd_host.hpp; rdrf_selftest_warp_bwd)
 // ------------------------------------------------------------------------------------------------
-size_t warp_bwd_on_rows_pack_floats() { return PACK_AREA_FLOATS; }
 int warp_bwd_on_rows(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int N, int S, const float* act1, float* grows1,
                      float* dxw, float* dxn, const float* g_xyz_prime, const RdrfDynamicParams* G, float* g_xyz, float* dtout,
                      float* dtp, float* pk, uint8_t* valid, hipStream_t stream) {
@@ -1718,19 +1664,13 @@ int warp_bwd_on_rows(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int N,
   a.g_xyz_prime = g_xyz_prime; a.g_xyz = g_xyz;
   a.small_dw = 1;
   a.sp.act1 = const_cast<float*>(act1);
-  a.pk = pk; a.grows1 = grows1; a.dxw_app = dxw; a.dxn_app = dxn; a.dtout = dtout; a.dtp = dtp;
+  a.grows1 = grows1; a.dxw_app = dxw; a.dxn_app = dxn; a.dtout = dtout; a.dtp = dtp;
   DynW w;
   fill_dyn_w(w, P);
   DynG gw;
   memset(&gw, 0, sizeof(gw));
   gw.l5b = G->l5b; gw.l5w = G->l5w;
-  if (P->packed_bwd != nullptr) a.pk = P->packed_bwd;
-  else {
-    PackJobs J;
-    dyn_pack_jobs_bwd(J, P);
-    int rc = pack_launch(J, pk, stream);
-    if (rc) return rc;
-  }
+  RDRF_TRY(pack_image(a.pk, P->packed_bwd, pk, stream, dyn_pack_jobs_bwd, P));
   const size_t ns = (size_t)N * S, t1 = (ns + 31) / 32;
   RDRF_FILL(valid, 1, ns, stream);
   if (warp_fused_path(true, true)) return launch_warp_fused(a, gw, G, (long)t1, stream);

@@ -26,6 +26,15 @@ struct BwdWs {
   float* gsig;     // flat-tile density phase (BwdArgs::gsig, ::dtp)
   float* dtp;
 };
+// the sorted scatter's buffers over ns samples: keys in / out and sorted positions of the 3 planes, counters, radix-sort scratch
+static inline void carve_sorted_scatter(BwdWs& b, WsCarver& c, size_t ns) {
+  b.keys_in = c.take<unsigned>(3 * ns);
+  b.keys_out = c.take<unsigned>(3 * ns);
+  b.order = c.take<unsigned>(3 * ns);
+  b.counts = c.take<int>(64);
+  b.sort_tmp_bytes = rdrf_sort_seg_temp_bytes(3, (unsigned)ns, 32);
+  b.sort_tmp = c.take<char>(b.sort_tmp_bytes);
+}
 
 // ------------------------------------------------------------------------------------------------
 // gradient scatter (rdrf_scatter.hip)
@@ -128,7 +137,6 @@ void add_feat_dyn_app_dw(DwJobs& D, const float* grows3, const float* act3, cons
 int warp_bwd_on_rows(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int N, int S, const float* act1, float* grows1,
                      float* dxw, float* dxn, const float* g_xyz_prime, const RdrfDynamicParams* G, float* g_xyz, float* dtout,
                      float* dtp, float* pk, uint8_t* valid, hipStream_t stream);
-size_t warp_bwd_on_rows_pack_floats();
 
 // ------------------------------------------------------------------------------------------------
 // backward-data kernels with the weight gradients formed in the kernel (rdrf_bwd_fused.hip)

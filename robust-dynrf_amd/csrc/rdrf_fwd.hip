@@ -207,8 +207,12 @@ void fill_dyn_w(DynW& w, const RdrfDynamicParams* P) {
   w.sfb0 = P->sfb[0]; w.sfb2 = P->sfb[1]; w.sfb4 = P->sfb[2]; w.sfb6 = P->sfb[3];
 }
 
-#define PACK_AREA_FLOATS (1 << 20) /* 4 MiB: forward + transposed packs of either field */
-
+// forward calls (either field, scene flow): pack area + counter + tout + xw + list -- what an inference-only caller needs.
+// The render workspaces are cut in slices of this size (rdrf_render.hip), so it keeps its closed form.
+extern "C" size_t rdrf_forward_workspace_bytes(int N, int S) {
+  const size_t ns = (size_t)N * S;
+  return (size_t)PACK_AREA_FLOATS * 4 + 256 + (size_t)N * 32 * 4 + ns * 3 * 4 + ns * 4 + (1 << 12);
+}
 
 static int ws_carve_fwd_ex(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S, void* saved,
                            size_t saved_bytes, int dynamic, int flags) {
@@ -251,26 +255,6 @@ extern "C" size_t rdrf_saved_row_bytes(int phase) {
   return (size_t)4 * (phase == 0 ? sv::K1_ROWS : phase == 1 ? sv::K3_ROWS : phase == 2 ? sv::S3_ROWS : sv::SF_ROWS);
 }
 
-// persistent launch geometry: one workgroup per CU (its LDS holds the kernel's weight image),
-// up to 8 waves per workgroup, each wave walking its own rays / tiles.
-struct Geo {
-  int grid, block;
-};
-static Geo geo_for_units(long units) {
-  Geo g;
-  const int ncu = 256;
-  int waves = (int)((units + ncu - 1) / ncu);
-  waves = waves < 1 ? 1 : (waves > RDRF_MAXW ? RDRF_MAXW : waves);
-  g.block = waves * 64;
-  // one tile per wave: small launches (a 512-ray eval chunk = 1840 tiles) take proportionally fewer CUs -- every workgroup
-  // pays the 121-159 KB LDS fill of its weight image once per launch, and independent launches on other streams find free
-  // CUs (rdrf_render_chunks_fwd)
-  long blocks = (units + waves - 1) / waves;
-  g.grid = (int)(blocks < 1 ? 1 : (blocks > ncu ? ncu : blocks));
-  return g;
-}
-static Geo geo_for_tiles(int N, int S) { return geo_for_units(((long)N * S + 31) / 32); }
-
 // FieldArgs::dynq of the forward launches: bit 0 = per-workgroup tile queue (+1-2 % on the compacted-tile MLP kernels)
 int fwd_dynq() { return 1; }
 
@@ -289,20 +273,13 @@ extern "C" int rdrf_static_fwd_ex(const RdrfStaticParams* P, const RdrfFieldCfg*
   FieldArgs a;
   fill_common(a, cfg, rays, ts, xyz, z, valid, N, S);
   a.rgb = rgb; a.sigma = sigma; a.weight = weight; a.dists = dists;
-  int rc = ws_carve_fwd_ex(a, ws, ws_bytes, N, S, saved, saved_bytes, 0, flags);
-  if (rc) return rc;
+  RDRF_TRY(ws_carve_fwd_ex(a, ws, ws_bytes, N, S, saved, saved_bytes, 0, flags));
   // rows are saved only where a backward can read them: no buffer, or one without appearance rows (RDRF_SAVE_NO_APP: the
   // colours are values only) -> the inference instantiation of the appearance kernel
   const bool save_app = saved != nullptr && !(flags & RDRF_SAVE_NO_APP);
   StaticW w;
   fill_static_w(w, P);
-  if (P->packed_fwd != nullptr) a.pk = P->packed_fwd;   // caller-packed image (rdrf_static_pack)
-  else {
-    PackJobs J;
-    static_pack_jobs_fwd(J, P, cfg->static_head);
-    rc = pack_launch(J, (float*)a.pk, stream);
-    if (rc) return rc;
-  }
+  RDRF_TRY(pack_image(a.pk, P->packed_fwd, (float*)a.pk, stream, static_pack_jobs_fwd, P, cfg->static_head));
   RDRF_FILL(a.counter, 0, 256, stream);   // (the colours are zero-filled by k_static_density)
 #ifdef RDRF_DETERMINISTIC
   RDRF_FILL(a.list, 0x7f, (size_t)N * S * sizeof(int), stream);
@@ -310,7 +287,7 @@ extern "C" int rdrf_static_fwd_ex(const RdrfStaticParams* P, const RdrfFieldCfg*
   RDRF_LAUNCH("static_density", k_static_density<false>, dim3((N + 3) / 4), dim3(256), stream, a, w);   // 4 rays per workgroup: one list append
   if (rgb == nullptr) return 0;   // the caller does not consume the colours: the appearance phase is not run
 #ifdef RDRF_DETERMINISTIC
-  { int rc_ = rdrf_sort_ints_inplace(a.list, (unsigned)((size_t)N * S), stream); if (rc_) return rc_; }   // append order depends on wave timing
+  RDRF_TRY(rdrf_sort_ints_inplace(a.list, (unsigned)((size_t)N * S), stream));   // append order depends on wave timing
 #endif
   const Geo g = geo_for_tiles(N, S);
   const bool fea = cfg->static_head == RDRF_HEAD_MLP_FEA;
@@ -352,17 +329,10 @@ extern "C" int rdrf_dynamic_fwd_ex(const RdrfDynamicParams* P, const RdrfFieldCf
   a.rgb = rgb; a.sigma = sigma; a.weight = weight; a.dists = dists;
   a.blending = blending; a.xyz_prime = xyz_prime;
   a.dynq = fwd_dynq();
-  int rc = ws_carve_fwd_ex(a, ws, ws_bytes, N, S, saved, saved_bytes, 1, flags);
-  if (rc) return rc;
+  RDRF_TRY(ws_carve_fwd_ex(a, ws, ws_bytes, N, S, saved, saved_bytes, 1, flags));
   DynW w;
   fill_dyn_w(w, P);
-  if (P->packed_fwd != nullptr) a.pk = P->packed_fwd;   // caller-packed image (rdrf_dynamic_pack)
-  else {
-    PackJobs J;
-    dyn_pack_jobs_fwd(J, P);
-    rc = pack_launch(J, (float*)a.pk, stream);
-    if (rc) return rc;
-  }
+  RDRF_TRY(pack_image(a.pk, P->packed_fwd, (float*)a.pk, stream, dyn_pack_jobs_fwd, P));
   // the density phase runs at tile granularity (k_dyn_density_flat + k_ray_scan): no tile is padded to the end of its ray,
   // and a 512-ray eval chunk fills the chip.  In training the saved rows are addressed by flat tile, and the backward
   // (rdrf_dynamic_bwd) reads them the same way: both sides take the switch from rdrf_flat_density()
@@ -380,7 +350,7 @@ extern "C" int rdrf_dynamic_fwd_ex(const RdrfDynamicParams* P, const RdrfFieldCf
   } else if (saved != nullptr) RDRF_LAUNCH("dyn_density", (k_dyn_density<false, true>), dim3(g1.grid), dim3(g1.block), stream, a, w);
   else RDRF_LAUNCH("dyn_density", (k_dyn_density<false, false>), dim3(g1.grid), dim3(g1.block), stream, a, w);
 #ifdef RDRF_DETERMINISTIC
-  { int rc_ = rdrf_sort_ints_inplace(a.list, (unsigned)((size_t)N * S), stream); if (rc_) return rc_; }
+  RDRF_TRY(rdrf_sort_ints_inplace(a.list, (unsigned)((size_t)N * S), stream));
 #endif
   if (rgb == nullptr) return 0;   // the caller does not consume the colours: the appearance phase is not run
   // RDRF_SAVE_NO_APP: the density phase above saved as usual (list, xw, tout, raw, K1 rows, count); the colours are values
@@ -440,20 +410,13 @@ extern "C" int rdrf_static_features_fwd(const RdrfStaticParams* P, const RdrfFie
   FieldArgs a;
   fill_common(a, cfg, nullptr, nullptr, xn, nullptr, nullptr, Np, 32);
   a.M = M; a.in_norm = 1; a.sigma = density; a.feat = app;
-  int rc = feat_carve_fwd(a, ws, ws_bytes, M, saved, saved_bytes, 0);
-  if (rc) return rc;
+  RDRF_TRY(feat_carve_fwd(a, ws, ws_bytes, M, saved, saved_bytes, 0));
   StaticW w;
   fill_static_w(w, P);
   if (density != nullptr)
     RDRF_LAUNCH("feat_static_density", k_static_density<true>, dim3(Np), dim3(64), stream, a, w);
   if (app != nullptr) {
-    if (P->packed_fwd != nullptr) a.pk = P->packed_fwd;
-    else {
-      PackJobs J;
-      static_pack_jobs_fwd(J, P, cfg->static_head);
-      rc = pack_launch(J, (float*)a.pk, stream);
-      if (rc) return rc;
-    }
+    RDRF_TRY(pack_image(a.pk, P->packed_fwd, (float*)a.pk, stream, static_pack_jobs_fwd, P, cfg->static_head));
     const Geo g = geo_for_units(Np);
     RDRF_LAUNCH("feat_static_app", (k_static_app<RDRF_HEAD_MLP_FEA, true>), dim3(g.grid), dim3(g.block), stream,
                 a, w);
@@ -477,17 +440,10 @@ extern "C" int rdrf_dynamic_features_fwd(const RdrfDynamicParams* P, const RdrfF
   fill_common(a, cfg, nullptr, t, x, nullptr, nullptr, Np, 32);
   a.M = M; a.in_norm = x_is_normalized ? 1 : 0;
   a.sigma = density; a.blending = blending; a.feat = app; a.xyz_prime = xyz_prime;
-  int rc = feat_carve_fwd(a, ws, ws_bytes, M, saved, saved_bytes, 1);
-  if (rc) return rc;
+  RDRF_TRY(feat_carve_fwd(a, ws, ws_bytes, M, saved, saved_bytes, 1));
   DynW w;
   fill_dyn_w(w, P);
-  if (P->packed_fwd != nullptr) a.pk = P->packed_fwd;   // caller-packed image (rdrf_dynamic_pack)
-  else {
-    PackJobs J;
-    dyn_pack_jobs_fwd(J, P);
-    rc = pack_launch(J, (float*)a.pk, stream);
-    if (rc) return rc;
-  }
+  RDRF_TRY(pack_image(a.pk, P->packed_fwd, (float*)a.pk, stream, dyn_pack_jobs_fwd, P));
   RDRF_LAUNCH("time_branch", k_time_branch, dim3((M + 7) / 8), dim3(256), stream, t, w, M, a.tout, (int*)nullptr);
   const Geo g = geo_for_units(Np);
   RDRF_LAUNCH("feat_dyn_density", k_dyn_density<true>, dim3(g.grid), dim3(g.block), stream, a, w);
@@ -507,17 +463,10 @@ extern "C" int rdrf_scene_flow_fwd(const RdrfDynamicParams* P, const RdrfFieldCf
   memset(&a, 0, sizeof(a));
   RDRF_CHECK(saved == nullptr || saved_bytes >= rdrf_saved_bytes(2, N, S), -3,
              "scene_flow_fwd: saved buffer too small");
-  int rc = ws_carve_fwd(a, ws, ws_bytes, N, S, nullptr, 0, 1);
-  if (rc) return rc;
+  RDRF_TRY(ws_carve_fwd(a, ws, ws_bytes, N, S, nullptr, 0, 1));
   DynW w;
   fill_dyn_w(w, P);
-  if (P->packed_fwd != nullptr) a.pk = P->packed_fwd;   // caller-packed image (rdrf_dynamic_pack)
-  else {
-    PackJobs J;
-    dyn_pack_jobs_fwd(J, P);
-    rc = pack_launch(J, (float*)a.pk, stream);
-    if (rc) return rc;
-  }
+  RDRF_TRY(pack_image(a.pk, P->packed_fwd, (float*)a.pk, stream, dyn_pack_jobs_fwd, P));
   const Geo g = geo_for_tiles(N, S);
   RDRF_LAUNCH("scene_flow", k_scene_flow, dim3(g.grid), dim3(g.block), stream, pts, ts, N, S,
               make_box(cfg), a.pk, w, sf_f, sf_b, (float*)saved, fwd_dynq());

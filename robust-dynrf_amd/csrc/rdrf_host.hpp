@@ -51,6 +51,13 @@ inline bool rdrf_flat_density() {
     }                                                                              \
   } while (0)
 
+// a launch helper's return code, passed on
+#define RDRF_TRY(expr)        \
+  do {                        \
+    int rc_try_ = (expr);     \
+    if (rc_try_) return rc_try_; \
+  } while (0)
+
 // byte fill as a kernel launch (rdrf_pack.hip): the launch sequences use it instead of hipMemsetAsync, whose memset nodes do
 // not replay reliably inside a captured HIP graph
 int rdrf_fill_async(void* p, int byte_value, size_t bytes, hipStream_t stream);
@@ -82,20 +89,43 @@ static inline Box make_box(const RdrfFieldCfg* cfg) {
   return b;
 }
 
-// workspace carving (all offsets 256-byte aligned)
+// workspace carving (all offsets 256-byte aligned).  A layout is written once, as a function of a carver: the entry point
+// carves the caller's buffer with it, and the *_workspace_bytes function runs it on a carver without a buffer (measuring
+// mode: take() returns nullptr and only advances `off`) and returns the end offset.
 struct WsCarver {
   char* base;
   size_t off, cap;
   WsCarver(void* p, size_t c) : base((char*)p), off(0), cap(c) {}
+  WsCarver() : base(nullptr), off(0), cap(~(size_t)0) {}   // measuring mode
   template <typename T>
   T* take(size_t n) {
     size_t bytes = (n * sizeof(T) + 255) & ~(size_t)255;
-    T* r = (T*)(base + off);
+    T* r = base ? (T*)(base + off) : nullptr;
     off += bytes;
     return r;
   }
   bool ok() const { return off <= cap; }
 };
+
+// persistent launch geometry: one workgroup per CU (its LDS holds the kernel's weight image),
+// up to 8 waves per workgroup, each wave walking its own rays / tiles.
+struct Geo {
+  int grid, block;
+};
+static inline Geo geo_for_units(long units) {
+  Geo g;
+  const int ncu = 256;
+  int waves = (int)((units + ncu - 1) / ncu);
+  waves = waves < 1 ? 1 : (waves > RDRF_MAXW ? RDRF_MAXW : waves);
+  g.block = waves * 64;
+  // one tile per wave: small launches (a 512-ray eval chunk = 1840 tiles) take proportionally fewer CUs -- every workgroup
+  // pays the 121-159 KB LDS fill of its weight image once per launch, and independent launches on other streams find free
+  // CUs (rdrf_render_chunks_fwd)
+  long blocks = (units + waves - 1) / waves;
+  g.grid = (int)(blocks < 1 ? 1 : (blocks > ncu ? ncu : blocks));
+  return g;
+}
+static inline Geo geo_for_tiles(int N, int S) { return geo_for_units(((long)N * S + 31) / 32); }
 
 // component counts + the three planes / lines span ONE grid (plane XY <-> line Z, XZ <-> Y, YZ <-> X): the forward
 // kernels compute one tap per grid axis and share it between the planes (rdrf_common.hpp, shared-tap gather)
@@ -137,3 +167,28 @@ void pack_add_b3s(PackJobs& J, const float* src, int ld, int out_dim, int in_dim
 void pack_add_b3s_t(PackJobs& J, const float* src, int ld, int out_dim, int in_dim, int seg, int nbi, int kk, int dst, int dst_lo);
 void pack_add_from(PackJobs& J, const float* src, int ld, int out_dim, int in_dim, int seg, int nb, int kk, int seg_kk0, int dst);
 int pack_launch(const PackJobs& J, float* dst, hipStream_t stream);
+
+#define PACK_AREA_FLOATS (1 << 20) /* 4 MiB: forward + transposed packs of either field */
+
+// the job lists of the four weight images (forward: rdrf_fwd.hip, backward: rdrf_bwd.hip) and the kernels' weight-pointer
+// structs (rdrf_kernels.hpp; filled in rdrf_fwd.hip)
+struct StaticW;
+struct DynW;
+void static_pack_jobs_fwd(PackJobs& J, const RdrfStaticParams* P, int head);
+void dyn_pack_jobs_fwd(PackJobs& J, const RdrfDynamicParams* P);
+void static_pack_jobs_bwd(PackJobs& J, const RdrfStaticParams* P, int head);
+void dyn_pack_jobs_bwd(PackJobs& J, const RdrfDynamicParams* P);
+void fill_static_w(StaticW& w, const RdrfStaticParams* P);
+void fill_dyn_w(DynW& w, const RdrfDynamicParams* P);
+
+// The weight image an entry point reads: `packed`, the caller-packed one (rdrf_static_pack / rdrf_dynamic_pack), or the jobs
+// of build(J, args...) packed into `area` now.
+template <typename... A>
+static inline int pack_image(const float*& pk, const float* packed, float* area, hipStream_t stream,
+                             void (*build)(PackJobs&, A...), A... args) {
+  pk = packed != nullptr ? packed : area;
+  if (packed != nullptr) return 0;
+  PackJobs J;
+  build(J, args...);
+  return pack_launch(J, area, stream);
+}

@@ -6,11 +6,7 @@
 // host helpers of rdrf_fwd.hip
 void fill_common(FieldArgs& a, const RdrfFieldCfg* cfg, const float* rays, const float* ts, const float* xyz, const float* z,
                  const uint8_t* valid, int N, int S);
-void fill_static_w(StaticW& w, const RdrfStaticParams* P);
-void fill_dyn_w(DynW& w, const RdrfDynamicParams* P);
 int ws_carve_fwd(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S, void* saved, size_t saved_bytes, int dynamic);
-void dyn_pack_jobs_fwd(PackJobs& J, const RdrfDynamicParams* P);
-void static_pack_jobs_fwd(PackJobs& J, const RdrfStaticParams* P, int head);
 
 // ------------------------------------------------------------------------------------------------
 // FUSED render: sample -> static + dynamic density phases -> static + dynamic appearance phases -> compositor in ONE
@@ -204,20 +200,8 @@ static int render_fused(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, c
   if (rc) return rc;
   fill_static_w(r.ws, PS);
   fill_dyn_w(r.wd, PD);
-  if (PS->packed_fwd != nullptr) r.as.pk = PS->packed_fwd;
-  else {
-    PackJobs J;
-    static_pack_jobs_fwd(J, PS, cfg_s->static_head);
-    rc = pack_launch(J, (float*)r.as.pk, stream);
-    if (rc) return rc;
-  }
-  if (PD->packed_fwd != nullptr) r.ad.pk = PD->packed_fwd;
-  else {
-    PackJobs J;
-    dyn_pack_jobs_fwd(J, PD);
-    rc = pack_launch(J, (float*)r.ad.pk, stream);
-    if (rc) return rc;
-  }
+  RDRF_TRY(pack_image(r.as.pk, PS->packed_fwd, (float*)r.as.pk, stream, static_pack_jobs_fwd, PS, cfg_s->static_head));
+  RDRF_TRY(pack_image(r.ad.pk, PD->packed_fwd, (float*)r.ad.pk, stream, dyn_pack_jobs_fwd, PD));
   r.comp.rgb_s = b.rgb_s; r.comp.sigma_s = b.sigma_s; r.comp.rgb_d = b.rgb_d; r.comp.sigma_d = b.sigma_d;
   r.comp.dists = b.dists_d; r.comp.blending = b.blending; r.comp.z = b.z; r.comp.rays = rays;
   r.comp.N = N; r.comp.S = S; r.comp.ray_type = cfg_d->ray_type; r.comp.add_white_bg = 0; r.comp.white_dev = nullptr;

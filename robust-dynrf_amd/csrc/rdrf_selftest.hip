@@ -390,8 +390,16 @@ extern "C" int rdrf_selftest_warp_geometry(int ntiles, int* grid, int* waves) {
   return 0;
 }
 
+static void carve_warp_bwd(float*& pk, uint8_t*& valid, WsCarver& c, int N, int S) {
+  pk = c.take<float>(PACK_AREA_FLOATS);
+  valid = c.take<uint8_t>((size_t)N * S);
+}
 extern "C" size_t rdrf_selftest_warp_bwd_workspace_bytes(int N, int S) {
-  return warp_bwd_on_rows_pack_floats() * 4 + (((size_t)N * S + 255) & ~(size_t)255) + 512;
+  float* pk;
+  uint8_t* valid;
+  WsCarver c;
+  carve_warp_bwd(pk, valid, c, N, S);
+  return c.off;
 }
 extern "C" int rdrf_selftest_warp_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int N, int S, const float* act1,
                                       size_t act1_floats, float* grows1, size_t grows1_floats, float* dxw, float* dxn,
@@ -406,10 +414,11 @@ extern "C" int rdrf_selftest_warp_bwd(const RdrfDynamicParams* P, const RdrfFiel
   const size_t tiles = ((size_t)N * S + 31) / 32;
   RDRF_CHECK(act1_floats >= tiles * sv::K1_ROWS * 32 && grows1_floats >= tiles * sv::K1G_ROWS * 32, -3,
              "selftest_warp_bwd: rows too small for %zu tiles", tiles);
-  RDRF_CHECK(ws_bytes >= rdrf_selftest_warp_bwd_workspace_bytes(N, S), -3, "selftest_warp_bwd: workspace too small");
   WsCarver c(ws, ws_bytes);
-  float* pk = c.take<float>(warp_bwd_on_rows_pack_floats());
-  uint8_t* valid = c.take<uint8_t>((size_t)N * S);
+  float* pk;
+  uint8_t* valid;
+  carve_warp_bwd(pk, valid, c, N, S);
+  RDRF_CHECK(c.ok(), -3, "selftest_warp_bwd: workspace too small");
   return warp_bwd_on_rows(P, cfg, N, S, act1, grows1, dxw, dxn, g_xyz_prime, grads, g_xyz, dtout, dtp, pk, valid, stream);
 }
 
@@ -528,10 +537,11 @@ bool scatter_vm_ok(const RdrfVM& v, const RdrfVM& g, int c0, int c1) {
 
 }  // namespace
 
-extern "C" size_t rdrf_selftest_scatter_workspace_bytes(int N, int S) {
-  const size_t ns = (size_t)(N > 0 ? N : 0) * (size_t)(S > 0 ? S : 0);
-  const size_t arr = (3 * ns * 4 + 255) & ~(size_t)255;
-  return 3 * arr + 256 + ((rdrf_sort_seg_temp_bytes(3, (unsigned)ns, 32) + 255) & ~(size_t)255) + 512;
+extern "C" size_t rdrf_selftest_scatter_workspace_bytes(int N, int S) {   // of the sorted forms (carve_sorted_scatter)
+  BwdWs b;
+  WsCarver c;
+  carve_sorted_scatter(b, c, (size_t)(N > 0 ? N : 0) * (size_t)(S > 0 ? S : 0));
+  return c.off;
 }
 
 extern "C" int rdrf_selftest_scatter(int kind, int mode, const RdrfScatterTest* t, rdrf_stream_t stream_) {
@@ -614,12 +624,7 @@ extern "C" int rdrf_selftest_scatter(int kind, int mode, const RdrfScatterTest* 
   WsCarver c(t->ws, t->ws_bytes);
   BwdWs b;
   memset(&b, 0, sizeof(b));
-  b.keys_in = c.take<unsigned>(3 * ns);
-  b.keys_out = c.take<unsigned>(3 * ns);
-  b.order = c.take<unsigned>(3 * ns);
-  b.counts = c.take<int>(64);
-  b.sort_tmp_bytes = rdrf_sort_seg_temp_bytes(3, (unsigned)ns, 32);
-  b.sort_tmp = c.take<char>(b.sort_tmp_bytes);
+  carve_sorted_scatter(b, c, ns);
   RDRF_CHECK(c.ok(), -3, "selftest_scatter: workspace too small");
   b.dxw = t->dxw;
   b.grows1 = const_cast<float*>(t->rows);
