@@ -803,6 +803,23 @@ int rdrf_alpha_mask_sample(const RdrfAlphaMask* mask, const float* xyz, const fl
 int rdrf_alpha_mask_valid(const RdrfAlphaMask* mask0, const RdrfAlphaMask* mask1, const float* xyz, const float* ts, int N,
                           int S, uint8_t* valid, rdrf_stream_t stream);
 
+/* ---- masked render: the no-grad render of a ray chunk that skips what the alpha-grid masks leave empty ------------------
+ * The maps are those of: sample -> valid_s = valid & (mask_s > 0), valid_d = valid & (mask_d > 0) (rdrf_alpha_mask_valid with
+ * one mask) -> rdrf_static_fwd with valid_s, rdrf_dynamic_fwd with valid_d -> rdrf_composite_fwd, bit for bit in every map;
+ * the density phase of a field runs on the samples its mask keeps only (a kept-sample list per field, device-side lengths,
+ * no host sync).  mask_s / mask_d: each nullable (that field keeps every sample the sampler marks valid), not both.
+ * step > 0 exactly for the world-space march (ray_type RDRF_RAY_OTHER, as rdrf_render_world_fwd); all three ray types are
+ * served.  kept (nullable, device, [2]): the lengths of the static and the dynamic list.  The per-sample xyz_prime of a
+ * dropped sample is not written, so there are no motion maps on this path.  N == 0 is a no-op.
+ * rdrf_render_masked_ws_bytes is the end offset of the entry point's own carve (whole 256-byte blocks; it holds
+ * rdrf_render_workspace_bytes(N, S) and grows with N and S).  It does not carry the *_workspace_bytes suffix: those names are
+ * the closed set whose values tests/test_workspace_sizes_cpu.py holds to a table recorded from an earlier library. */
+size_t rdrf_render_masked_ws_bytes(int N, int S);
+int rdrf_render_masked_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                           const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near, float far,
+                           float step, const RdrfAlphaMask* mask_s, const RdrfAlphaMask* mask_d, const RdrfRenderMaps* maps,
+                           int64_t* kept, void* ws, size_t ws_bytes, rdrf_stream_t stream);
+
 /* timing hook: average device time (ms) of the dominant kernel launches recorded with HIP events
  * since the last reset; used by bench.py for the roofline figure. */
 void rdrf_prof_reset(void);

@@ -179,6 +179,13 @@ def _load():
                                            C.c_void_p]
     lib.rdrf_alpha_mask_valid.argtypes = [C.POINTER(RdrfAlphaMask), C.POINTER(RdrfAlphaMask), C.c_void_p, C.c_void_p, C.c_int,
                                           C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "rdrf_render_masked_fwd"):   # (an addition inside ABI 6, as above)
+        lib.rdrf_render_masked_ws_bytes.restype = C.c_size_t
+        lib.rdrf_render_masked_ws_bytes.argtypes = [C.c_int, C.c_int]
+        lib.rdrf_render_masked_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                               C.c_int, C.c_float, C.c_float, C.c_float, C.POINTER(RdrfAlphaMask),
+                                               C.POINTER(RdrfAlphaMask), C.POINTER(RenderMapsC), C.c_void_p, C.c_void_p,
+                                               C.c_size_t, C.c_void_p]
     lib.rdrf_gather_batch.argtypes = [C.POINTER(SceneTablesC), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(BatchC), C.c_void_p]
     lib.rdrf_selftest_layer.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_size_t, C.c_void_p]
@@ -239,7 +246,7 @@ SYMBOLS = [
     "rdrf_render_motion_workspace_bytes", "rdrf_render_motion_fwd", "rdrf_flow_to_image_workspace_bytes", "rdrf_flow_to_image",
     "rdrf_gather_batch",
     "rdrf_compute_alpha_workspace_bytes", "rdrf_compute_alpha", "rdrf_alpha_mask_build", "rdrf_alpha_mask_sample",
-    "rdrf_alpha_mask_valid",
+    "rdrf_alpha_mask_valid", "rdrf_render_masked_ws_bytes", "rdrf_render_masked_fwd",
     "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_selftest_layer", "rdrf_selftest_dw", "rdrf_selftest_dw_describe",
     "rdrf_selftest_dw_plan",
     "rdrf_selftest_sf_geometry", "rdrf_selftest_warp_geometry", "rdrf_selftest_warp_bwd_workspace_bytes", "rdrf_selftest_warp_bwd",

@@ -2,6 +2,7 @@
 // /root/reference/renderer.py:740-812: sampleXYZ -> static -> dynamic -> raw2outputs), and a
 // self-test of the MFMA layer primitive used by tests/.
 #include "rdrf_misc_dev.hpp"
+#include "rdrf_render_host.hpp"
 
 // host helpers of rdrf_fwd.hip
 void fill_common(FieldArgs& a, const RdrfFieldCfg* cfg, const float* rays, const float* ts, const float* xyz, const float* z,
@@ -114,18 +115,11 @@ extern "C" size_t rdrf_render_workspace_bytes(int N, int S) {
   return ns * 4 * (3 * 4 + 12) + ns + (size_t)N * 4 * 16 + 2 * rdrf_forward_workspace_bytes(N, S) + (1 << 14);
 }
 
-struct RenderBufs {
-  float *xyz, *z, *rgb_s, *sigma_s, *weight_s, *dists_s, *rgb_d, *sigma_d, *weight_d, *dists_d, *blending, *xyz_prime;
-  uint8_t* valid;
-  float* out[13];
-  void *fws_s, *fws_d;
-  unsigned* barrier;
-};
 // the per-ray outputs among the compositor's 13 (out13 order of rdrf_composite_fwd) and their widths; the three per-sample
 // weight planes (3, 7, 11) always stay in the workspace
 static const int kMapSlot[10] = {0, 1, 2, 4, 5, 6, 8, 9, 10, 12};
 static inline int map_width(int slot) { return (slot % 4 == 0 && slot < 12) ? 3 : 1; }
-static void maps_to_slots(float* out[13], const RdrfRenderMaps* m) {
+void maps_to_slots(float* out[13], const RdrfRenderMaps* m) {
   for (int i = 0; i < 13; ++i) out[i] = nullptr;
   if (!m) return;
   float* const p[10] = {m->rgb, m->depth, m->acc, m->rgb_s, m->depth_s, m->acc_s, m->rgb_d, m->depth_d, m->acc_d, m->blending};
@@ -134,7 +128,7 @@ static void maps_to_slots(float* out[13], const RdrfRenderMaps* m) {
 
 // want[13]: the caller's output buffers (NULL: the output goes to the workspace).  The legacy entry points pass rgb and
 // depth only, which carves the workspace exactly as before the maps existed.
-static int carve_render(RenderBufs& b, void* ws, size_t ws_bytes, int N, int S, float* const want[13]) {
+int carve_render(RenderBufs& b, void* ws, size_t ws_bytes, int N, int S, float* const want[13]) {
   WsCarver c(ws, ws_bytes);
   const size_t ns = (size_t)N * S;
   b.xyz = c.take<float>(ns * 3);

@@ -1,0 +1,433 @@
+// rdrf_render_masked.hip -- the no-grad render of a ray chunk with alpha-grid masks: the density phase of either field
+// runs on the samples its mask keeps and on no other.
+//
+// Meaning (what the launch sequence below reproduces bit for bit): sample -> valid_s = valid & (mask_s > 0),
+// valid_d = valid & (mask_d > 0) (rdrf_alpha_mask_valid) -> static forward with valid_s, dynamic forward with valid_d ->
+// compositor.  The dense density kernels evaluate a dropped sample in full and then force its sigma to 0; here
+//
+//   k_keep               : one pass over the [N * S] samples: both masks at (xyz, ts[ray]), the two valid planes, the flat
+//                          index of every kept sample appended to list_s / list_d (one append per workgroup and list), and
+//                          zeros where the later phases read a dropped sample (sigma of both fields, blending)
+//   k_static_density_list: a lane per listed sample, the gather of static_density_body -> sigma
+//   k_static_scan        : the per-ray half of static_density_body (wave per ray, 64-lane transmittance scan) over all
+//                          N * S sigmas: weight, dists, app-mask compaction, zero fill of the colours
+//   k_dyn_density_list   : 32-entry tiles of list_d through the device functions of dyn_density_body in its order (FLAT
+//                          form: time and tout through the sample's ray).  An MFMA column depends on its own sample only,
+//                          so a listed sample gets the bits k_dyn_density_flat gives it
+//   k_masked_ray_scan    : ray_scan_body, unchanged
+//   appearance kernels, compositor: the bodies / the entry point of the unmasked render
+//
+// The tile counts come from the device-side list lengths; the grids are sized for the worst case (no host sync).  A list's
+// order depends on the arrival of the workgroups; a sample's values depend on that sample alone, so no result depends on it
+// and the deterministic build runs the same path.
+#include "rdrf_fwd_dev.hpp"
+#include "rdrf_mask_dev.hpp"
+#include "rdrf_render_host.hpp"
+
+// host helpers of rdrf_fwd.hip
+void fill_common(FieldArgs& a, const RdrfFieldCfg* cfg, const float* rays, const float* ts, const float* xyz, const float* z,
+                 const uint8_t* valid, int N, int S);
+int ws_carve_fwd(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S, void* saved, size_t saved_bytes, int dynamic);
+int fwd_dynq();
+
+// the four device counters of a call, one 256-byte block cleared by the time-branch launch: a counter per 64-byte line
+constexpr int CTR_KEPT_S = 0, CTR_KEPT_D = 16, CTR_APP_S = 32, CTR_APP_D = 48;
+
+constexpr int KEEP_ROUNDS = 8;   // samples per thread of k_keep: a workgroup owns 2048 consecutive samples, appends once per list
+
+struct KeepArgs {
+  const float* xyz;       // [N * S][3]
+  const float* ts;        // [N]
+  const uint8_t* valid;   // [N * S] of the sampler
+  int ns, S;
+  MaskDev ms, md;         // bits == nullptr: the field keeps every valid sample
+  uint8_t *valid_s, *valid_d;
+  int *list_s, *list_d;
+  int* ctr;               // CTR_KEPT_S / CTR_KEPT_D
+  float *sigma_s, *sigma_d, *blending;
+};
+
+__global__ __launch_bounds__(256) void k_keep(KeepArgs a) {
+  __shared__ int s_cnt[16];
+  const int i0 = blockIdx.x * (256 * KEEP_ROUNDS) + threadIdx.x;
+  unsigned ks = 0, kd = 0;   // bit r: the thread's sample of round r is kept
+  int cnt_s = 0, cnt_d = 0;  // wave-uniform
+#pragma unroll 1
+  for (int r = 0; r < KEEP_ROUNDS; ++r) {
+    const int i = i0 + r * 256;
+    const bool act = i < a.ns;
+    bool keep_s = false, keep_d = false;
+    if (act && a.valid[i] != 0) {
+      keep_s = keep_d = true;
+      if (a.ms.bits != nullptr || a.md.bits != nullptr) {
+        const float x = a.xyz[(size_t)i * 3 + 0], y = a.xyz[(size_t)i * 3 + 1], z = a.xyz[(size_t)i * 3 + 2];
+        const float tt = a.ts[i / a.S];
+        if (a.ms.bits != nullptr) keep_s = mask_sample(a.ms, x, y, z, mask_slice(a.ms, tt)) > 0.0f;
+        if (a.md.bits != nullptr) keep_d = mask_sample(a.md, x, y, z, mask_slice(a.md, tt)) > 0.0f;
+      }
+    }
+    if (act) {
+      a.valid_s[i] = keep_s ? 1 : 0;
+      a.valid_d[i] = keep_d ? 1 : 0;
+      if (!keep_s) a.sigma_s[i] = 0.0f;
+      if (!keep_d) {
+        a.sigma_d[i] = 0.0f;
+        a.blending[i] = 0.0f;
+      }
+    }
+    ks |= (keep_s ? 1u : 0u) << r;
+    kd |= (keep_d ? 1u : 0u) << r;
+    cnt_s += __popcll(__ballot(keep_s));
+    cnt_d += __popcll(__ballot(keep_d));
+  }
+  int base_s = block_append_base(a.ctr + CTR_KEPT_S, cnt_s, s_cnt, threadIdx.x, blockDim.x);
+  int base_d = block_append_base(a.ctr + CTR_KEPT_D, cnt_d, s_cnt, threadIdx.x, blockDim.x);
+#pragma unroll 1
+  for (int r = 0; r < KEEP_ROUNDS; ++r) {
+    const int i = i0 + r * 256;
+    const bool m_s = ((ks >> r) & 1u) != 0, m_d = ((kd >> r) & 1u) != 0;
+    const unsigned long long bs = __ballot(m_s), bd = __ballot(m_d);
+    if (m_s) a.list_s[base_s + __builtin_amdgcn_mbcnt_hi((unsigned)(bs >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bs, 0u))] = i;
+    if (m_d) a.list_d[base_d + __builtin_amdgcn_mbcnt_hi((unsigned)(bd >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bd, 0u))] = i;
+    base_s += __popcll(bs);
+    base_d += __popcll(bd);
+  }
+}
+
+// the static field's sigma of the listed samples: a lane per entry, the gather of static_density_body.  Also hands the two
+// list lengths to the caller (`kept`, nullable)
+__global__ __launch_bounds__(256) void k_static_density_list(FieldArgs a, StaticW w, const int* __restrict__ klist,
+                                                             const int* __restrict__ ctr, long long* __restrict__ kept) {
+  if (kept != nullptr && blockIdx.x == 0 && threadIdx.x < 2) kept[threadIdx.x] = ctr[threadIdx.x == 0 ? CTR_KEPT_S : CTR_KEPT_D];
+  const int count = ctr[CTR_KEPT_S];
+  for (int li = blockIdx.x * blockDim.x + threadIdx.x; li < count; li += gridDim.x * blockDim.x) {
+    const int idx = klist[li];
+    float f = 0.0f;
+    {
+      float x0, x1, x2;
+      x0 = norm_c(a.xyz[idx * 3 + 0], a.box.lo[0], a.box.inv[0]);
+      x1 = norm_c(a.xyz[idx * 3 + 1], a.box.lo[1], a.box.inv[1]);
+      x2 = norm_c(a.xyz[idx * 3 + 2], a.box.lo[2], a.box.inv[2]);
+      {
+        const PointTaps pt = point_taps(w.density, x0, x1, x2, 0);
+        const PlaneTaps xy = plane_taps(w.density, 0, pt.x, pt.y, pt.z, 0);
+        float sp = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const f32x4 v = taps_quad(xy, 4 * q);
+          sp += v.x + v.y + v.z + v.w;
+        }
+        f += sp;
+        const f32x4 v1 = taps_quad(plane_taps(w.density, 1, pt.x, pt.z, pt.y, 0), 0);
+        f += v1.x + v1.y + v1.z + v1.w;
+        const f32x4 v2 = taps_quad(plane_taps(w.density, 2, pt.y, pt.z, pt.x, 0), 0);
+        f += v2.x + v2.y + v2.z + v2.w;
+      }
+    }
+    a.sigma[idx] = density_act(f, a.act, a.density_shift);
+  }
+}
+
+// the per-ray half of static_density_body over stored sigmas: a wave per ray, 64 samples per round -- its expressions and
+// the order of its multiplications (ray_scan_body scans 32 wide: other roundings), so weight, dists and the app mask come
+// out as the dense kernel's
+__global__ __launch_bounds__(256) void k_static_scan(FieldArgs a) {
+  __shared__ int s_cnt[16];
+  const int lane = threadIdx.x & 63;
+  const int wave_ = threadIdx.x >> 6, nwaves_ = blockDim.x >> 6;
+  for (int nb = blockIdx.x * nwaves_; nb < a.N; nb += gridDim.x * nwaves_) {   // uniform over the workgroup (block_append_base syncs)
+    const bool ray = nb + wave_ < a.N;
+    const int n = ray ? nb + wave_ : 0;
+    float vx, vy, vz;
+    const float nrm = ray_norm(a.rays, n, a.ray_type, vx, vy, vz);
+    float carry = 1.0f;
+    int cnt = 0;
+    for (int j0 = 0; j0 < a.S; j0 += 64) {
+      const int j = j0 + lane;
+      const bool act = ray && j < a.S;
+      const int idx = n * a.S + (act ? j : 0);
+      if (ray) {   // zero the round's colours (coalesced; the appearance phase writes the masked samples)
+        float* r = a.rgb + ((size_t)n * a.S + j0) * 3 + lane;
+        const int lim = (a.S - j0 < 64 ? a.S - j0 : 64) * 3;
+        if (lane < lim) r[0] = 0.f;
+        if (lane + 64 < lim) r[64] = 0.f;
+        if (lane + 128 < lim) r[128] = 0.f;
+      }
+      const float sigma = act ? a.sigma[idx] : 0.0f;
+      const float zj = act ? a.z[idx] : 0.f;
+      const float zn = (j + 1 < a.S) ? a.z[idx + 1] : zj;
+      const float ds = ((j + 1 < a.S) ? (zn - zj) : 0.0f) * nrm * a.distance_scale;
+      const float alpha = 1.0f - expf(-sigma * ds);
+      const float p = act ? one_minus_alpha_eps(alpha) : 1.0f;
+      const float incl = scan_mul64(p, lane);
+      float excl = __shfl_up(incl, 1, 64);
+      if (lane == 0) excl = 1.0f;
+      const float T = carry * excl;
+      const float wt = alpha * T;
+      carry *= __shfl(incl, 63, 64);
+      if (act) {
+        a.weight[idx] = wt;
+        a.dists[idx] = ds;
+      }
+      cnt += __popcll(__ballot(act && wt > a.weight_thres));
+    }
+    int base = block_append_base(a.counter, cnt, s_cnt, threadIdx.x, blockDim.x);
+    if (cnt) {
+      for (int j0 = 0; j0 < a.S; j0 += 64) {
+        const int j = j0 + lane;
+        const bool act = ray && j < a.S;
+        const int idx = n * a.S + (act ? j : 0);
+        const bool m = act && a.weight[idx] > a.weight_thres;   // the lane's own store above
+        const unsigned long long bal = __ballot(m);
+        if (m) a.list[base + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u))] = idx;   // rank among the set lanes below
+        base += __popcll(bal);
+      }
+    }
+  }
+}
+
+// 32-entry tiles of the kept list from the workgroup's queue: per tile the inference path of dyn_density_body<., ., ., FLAT>
+// (same device functions, same order), every entry a valid sample
+__global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_density_list(FieldArgs a, DynW w, const int* __restrict__ klist,
+                                                                    const int* __restrict__ kcount) {
+  __shared__ __attribute__((aligned(16))) float lds[pk::K1_SIZE];
+  __shared__ int s_next;
+  const int count = *kcount;
+  const int ntiles = (count + 31) >> 5;
+  if ((int)blockIdx.x >= ntiles) return;   // (uniform over the workgroup) nothing of the list is this workgroup's: no LDS fill
+  const int lane = threadIdx.x & 63, h = lane >> 5, s = lane & 31;
+  const int wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  if (threadIdx.x == 0) s_next = nwaves;
+  lds_fill(lds, a.pk + pk::REG_K1, pk::K1_SIZE);
+  const float* pkw = lds;
+  const bool dynq = (a.dynq & 1) != 0;
+  for (int k = wave, tile; (tile = blockIdx.x + k * gridDim.x) < ntiles; k = tile_queue_next(&s_next, k, nwaves, dynq)) {
+    const int li = tile * 32 + s;
+    const bool act = li < count;
+    const int idx = act ? klist[li] : 0;
+    float t;
+    float T[16];
+    float X1[8];
+    {
+      const int ti = idx / a.S;
+      t = a.ts[ti];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        f32x4 v = ld4(a.tout + (size_t)ti * 32 + 8 * q + 4 * h);
+        T[q * 4 + 0] = v.x; T[q * 4 + 1] = v.y; T[q * 4 + 2] = v.z; T[q * 4 + 3] = v.w;
+      }
+      fill_x1(X1, t, h);
+    }
+    const float px = a.xyz[idx * 3 + 0], py = a.xyz[idx * 3 + 1], pz = a.xyz[idx * 3 + 2];
+    const float xn0 = norm_c(px, a.box.lo[0], a.box.inv[0]);
+    const float xn1 = norm_c(py, a.box.lo[1], a.box.inv[1]);
+    const float xn2 = norm_c(pz, a.box.lo[2], a.box.inv[2]);
+    float X0[32];
+    fill_x0(X0, xn0, xn1, xn2, t, h);
+    // ---- warp MLP: [xn, PE10(xn), tout] -> 64 -> 64 -> 3  (models/tensoRF.py:521-541)
+    float d0, d1, d2;
+    {
+      f32x16 acc[2];
+      acc_bias<2>(acc, pkw + pk::K1_B3, h);
+      mfma_seg<2, 32>(acc, X0, pkw + pk::K1_W3_X0, lane);
+      mfma_seg<2, 16>(acc, T, pkw + pk::K1_W3_T, lane);
+      float H3[32];
+      acc_relu<2>(H3, acc);
+      acc_bias<2>(acc, pkw + pk::K1_B4, h);
+      mfma_seg<2, 32>(acc, H3, pkw + pk::K1_W4, lane);
+      acc_relu<2>(H3, acc);
+      d0 = dot_small<32>(H3, pkw + pk::K1_W5 + 0 * 64, h) + w.l5b[0];
+      d1 = dot_small<32>(H3, pkw + pk::K1_W5 + 1 * 64, h) + w.l5b[1];
+      d2 = dot_small<32>(H3, pkw + pk::K1_W5 + 2 * 64, h) + w.l5b[2];
+    }
+    const float xw0 = norm_c(unnorm_c(xn0, a.box.lo[0], a.box.inv[0]) + d0, a.box.lo[0], a.box.inv[0]);
+    const float xw1 = norm_c(unnorm_c(xn1, a.box.lo[1], a.box.inv[1]) + d1, a.box.lo[1], a.box.inv[1]);
+    const float xw2 = norm_c(unnorm_c(xn2, a.box.lo[2], a.box.inv[2]) + d2, a.box.lo[2], a.box.inv[2]);
+    if (act && h == 0) {
+      a.xyz_prime[(size_t)idx * 3 + 0] = px + d0;
+      a.xyz_prime[(size_t)idx * 3 + 1] = py + d1;
+      a.xyz_prime[(size_t)idx * 3 + 2] = pz + d2;
+      a.xw[(size_t)idx * 3 + 0] = xw0;
+      a.xw[(size_t)idx * 3 + 1] = xw1;
+      a.xw[(size_t)idx * 3 + 2] = xw2;
+    }
+    // ---- density and blending heads: 3-stride VM features (72) + X0 + X1 -> 64 -> 1
+    float fd, fb;
+    {
+      float Fv[36];
+      gather_level_den<0>(w.density, point_taps(w.density, xw0, xw1, xw2, 0), h, Fv);
+      gather_level_den<12>(w.density, point_taps(w.density, xw0, xw1, xw2, 1), h, Fv);
+      gather_level_den<24>(w.density, point_taps(w.density, xw0, xw1, xw2, 2), h, Fv);
+      if (!act) {
+#pragma unroll
+        for (int i = 0; i < 36; ++i) Fv[i] = 0.f;
+      }
+      f32x16 acc[2];
+      acc_bias<2>(acc, pkw + pk::K1_BD1, h);
+#ifdef RDRF_HEADS_F32
+      mfma_seg<2, 36>(acc, Fv, pkw + pk::K1_DEN1_F, lane);
+      mfma_seg<2, 32>(acc, X0, pkw + pk::K1_DEN1_X0, lane);
+      mfma_seg<2, 8>(acc, X1, pkw + pk::K1_DEN1_X1, lane);
+#else
+      head_layer1(acc, Fv, X0, X1, pkw + pk::K1_DEN1, pkw + pk::K1_DEN1_X1T, lane);
+#endif
+      float Hd[32];
+      acc_relu<2>(Hd, acc);
+      fd = dot_small<32>(Hd, pkw + pk::K1_DEN2, h) + w.db2[0];
+    }
+    {
+      float Fv[36];
+      gather_level_den<0>(w.blending, point_taps(w.blending, xw0, xw1, xw2, 0), h, Fv);
+      gather_level_den<12>(w.blending, point_taps(w.blending, xw0, xw1, xw2, 1), h, Fv);
+      gather_level_den<24>(w.blending, point_taps(w.blending, xw0, xw1, xw2, 2), h, Fv);
+      if (!act) {
+#pragma unroll
+        for (int i = 0; i < 36; ++i) Fv[i] = 0.f;
+      }
+      f32x16 acc[2];
+      acc_bias<2>(acc, pkw + pk::K1_BB1, h);
+#ifdef RDRF_HEADS_F32
+      mfma_seg<2, 36>(acc, Fv, pkw + pk::K1_BLE1_F, lane);
+      mfma_seg<2, 32>(acc, X0, pkw + pk::K1_BLE1_X0, lane);
+      mfma_seg<2, 8>(acc, X1, pkw + pk::K1_BLE1_X1, lane);
+#else
+      head_layer1(acc, Fv, X0, X1, pkw + pk::K1_BLE1, pkw + pk::K1_BLE1_X1T, lane);
+#endif
+      float Hd[32];
+      acc_relu<2>(Hd, acc);
+      fb = dot_small<32>(Hd, pkw + pk::K1_BLE2, h) + w.bb2[0];
+    }
+    if (act && h == 0) {
+      a.sigma[idx] = density_act(fd, a.act, a.density_shift);
+      a.blending[idx] = sigmoidf_(fb);
+    }
+  }
+}
+
+// the phases after the density kernels: the bodies of the unmasked render in kernels of this unit
+__global__ __launch_bounds__(256) void k_masked_time_branch(const float* __restrict__ ts, DynW w, int N, float* __restrict__ tout,
+                                                            int* __restrict__ zero64) {
+  __shared__ float s_h[8 * 64];
+  if (blockIdx.x == 0 && threadIdx.x < 64) zero64[threadIdx.x] = 0;   // the call's four counters
+  time_branch_body(ts, w, N, tout, s_h, grid_ctx());
+}
+__global__ __launch_bounds__(512) void k_masked_ray_scan(FieldArgs a) { ray_scan_body(a); }   // 16 rays per workgroup
+template <int HEAD>
+__global__ __launch_bounds__(64 * RDRF_MAXW) void k_masked_static_app(FieldArgs a, StaticW w) {
+  static_app_body<HEAD, false, false>(a, w, nullptr, grid_ctx());
+}
+__global__ __launch_bounds__(64 * RDRF_MAXW) void k_masked_dyn_app(FieldArgs a, DynW w) {
+  dyn_app_body<false, false>(a, w, nullptr, grid_ctx());
+}
+
+// ------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------
+struct MaskedBufs {
+  void* render;   // the unmasked render's workspace (carve_render)
+  size_t render_bytes;
+  uint8_t *valid_s, *valid_d;
+  int *list_s, *list_d;
+  int* ctr;
+};
+static void carve_masked(MaskedBufs& b, WsCarver& c, int N, int S) {
+  const size_t ns = (size_t)N * S;
+  b.render_bytes = rdrf_render_workspace_bytes(N, S);
+  b.render = c.take<char>(b.render_bytes);
+  b.valid_s = c.take<uint8_t>(ns);
+  b.valid_d = c.take<uint8_t>(ns);
+  b.list_s = c.take<int>(ns);
+  b.list_d = c.take<int>(ns);
+  b.ctr = c.take<int>(64);
+}
+extern "C" size_t rdrf_render_masked_ws_bytes(int N, int S) {
+  MaskedBufs b;
+  WsCarver c;
+  carve_masked(b, c, N < 0 ? 0 : N, S < 0 ? 0 : S);
+  return c.off;
+}
+
+extern "C" int rdrf_render_masked_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                                      const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near,
+                                      float far, float step, const RdrfAlphaMask* mask_s, const RdrfAlphaMask* mask_d,
+                                      const RdrfRenderMaps* maps, int64_t* kept, void* ws, size_t ws_bytes,
+                                      rdrf_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (N == 0) return 0;   // empty batch: a no-op, like torch ops on empty tensors (their data pointers are null)
+  RDRF_CHECK(PS && PD && cfg_s && cfg_d && rays && ts && ws && N > 0 && S > 0, -1, "render_masked: bad arguments");
+  RDRF_CHECK((cfg_d->ray_type == RDRF_RAY_NDC || cfg_d->ray_type == RDRF_RAY_CONTRACT) == !(step > 0.0f), -1,
+             "render_masked: step > 0 exactly for the world-space march (ray_type %d, step %g)", cfg_d->ray_type, (double)step);
+  RDRF_CHECK((size_t)N * S * 3 < (size_t)INT32_MAX, -1, "render_masked: N * S * 3 must stay below 2^31: render in chunks");
+  const bool has_s = mask_s != nullptr && mask_s->bits != nullptr, has_d = mask_d != nullptr && mask_d->bits != nullptr;
+  RDRF_CHECK(has_s || has_d, -1, "render_masked: at least one of the two masks must be given");
+  RDRF_CHECK(mask_ok(mask_s) && mask_ok(mask_d), -1, "render_masked: the masks' grids and slice counts must be positive");
+  RDRF_CHECK(vm_ok(PS->density, 16, 4) && vm_ok(PS->app, 48, 12) && vm_ok(PD->density, 16, 4) && vm_ok(PD->blending, 16, 4) &&
+             vm_ok(PD->app, 48, 12) && vm_same_grid(PD->density, PD->blending), -1,
+             "render_masked: only density comps {16,4,4} / app comps {48,12,12} of one grid are built");
+  MaskedBufs m;
+  WsCarver c(ws, ws_bytes);
+  carve_masked(m, c, N, S);
+  RDRF_CHECK(c.ok(), -3, "render_masked: workspace too small: need %zu have %zu", c.off, ws_bytes);
+  float* want[13];
+  maps_to_slots(want, maps);
+  RenderBufs b;
+  RDRF_TRY(carve_render(b, m.render, m.render_bytes, N, S, want));
+  const size_t fwb = rdrf_forward_workspace_bytes(N, S);
+  const int ns = N * S;
+
+  FieldArgs as, ad;
+  fill_common(as, cfg_s, rays, ts, b.xyz, b.z, m.valid_s, N, S);
+  as.rgb = b.rgb_s; as.sigma = b.sigma_s; as.weight = b.weight_s; as.dists = b.dists_s;
+  RDRF_TRY(ws_carve_fwd(as, b.fws_s, fwb, N, S, nullptr, 0, 0));
+  as.counter = m.ctr + CTR_APP_S;
+  as.dynq = fwd_dynq();
+  fill_common(ad, cfg_d, rays, ts, b.xyz, b.z, m.valid_d, N, S);
+  ad.rgb = b.rgb_d; ad.sigma = b.sigma_d; ad.weight = b.weight_d; ad.dists = b.dists_d;
+  ad.blending = b.blending; ad.xyz_prime = b.xyz_prime;
+  RDRF_TRY(ws_carve_fwd(ad, b.fws_d, fwb, N, S, nullptr, 0, 1));
+  ad.counter = m.ctr + CTR_APP_D;
+  ad.dynq = fwd_dynq();
+  StaticW wst;
+  DynW wdy;
+  fill_static_w(wst, PS);
+  fill_dyn_w(wdy, PD);
+  RDRF_TRY(pack_image(as.pk, PS->packed_fwd, (float*)as.pk, stream, static_pack_jobs_fwd, PS, cfg_s->static_head));
+  RDRF_TRY(pack_image(ad.pk, PD->packed_fwd, (float*)ad.pk, stream, dyn_pack_jobs_fwd, PD));
+
+  int rc;
+  if (cfg_d->ray_type == RDRF_RAY_NDC)
+    rc = rdrf_sample_ndc(rays, N, S, near, far, nullptr, cfg_d->aabb, b.xyz, b.z, b.valid, stream);
+  else if (cfg_d->ray_type == RDRF_RAY_CONTRACT)
+    rc = rdrf_sample_contract(rays, N, S, near, far, nullptr, nullptr, b.xyz, b.z, b.valid, stream);
+  else
+    rc = rdrf_sample_world(rays, N, S, near, far, step, nullptr, cfg_d->aabb, b.xyz, b.z, b.valid, stream);
+  if (rc) return rc;
+  // the time branch of every ray (a masked-out ray costs 17 -> 64 -> 30 once); clears the four counters on its way
+  RDRF_LAUNCH("time_branch", k_masked_time_branch, dim3((N + 7) / 8), dim3(256), stream, ts, wdy, N, ad.tout, m.ctr);
+
+  KeepArgs k;
+  memset(&k, 0, sizeof(k));
+  k.xyz = b.xyz; k.ts = ts; k.valid = b.valid; k.ns = ns; k.S = S;
+  k.ms = make_mask(mask_s); k.md = make_mask(mask_d);
+  k.valid_s = m.valid_s; k.valid_d = m.valid_d; k.list_s = m.list_s; k.list_d = m.list_d; k.ctr = m.ctr;
+  k.sigma_s = b.sigma_s; k.sigma_d = b.sigma_d; k.blending = b.blending;
+  RDRF_LAUNCH("mask_keep", k_keep, dim3((ns + 256 * KEEP_ROUNDS - 1) / (256 * KEEP_ROUNDS)), dim3(256), stream, k);
+
+  {
+    const int blocks = (ns + 255) / 256;
+    RDRF_LAUNCH("static_density_list", k_static_density_list, dim3(blocks > 4096 ? 4096 : blocks), dim3(256), stream, as, wst,
+                (const int*)m.list_s, (const int*)m.ctr, (long long*)kept);
+  }
+  RDRF_LAUNCH("static_scan", k_static_scan, dim3((N + 3) / 4), dim3(256), stream, as);   // 4 rays per workgroup: one list append
+  const Geo g3 = geo_for_tiles(N, S);
+  RDRF_LAUNCH("dyn_density_list", k_dyn_density_list, dim3(g3.grid), dim3(g3.block), stream, ad, wdy, (const int*)m.list_d,
+              (const int*)(m.ctr + CTR_KEPT_D));
+  RDRF_LAUNCH("ray_scan", k_masked_ray_scan, dim3((N + 15) / 16), dim3(512), stream, ad);
+  if (cfg_s->static_head == RDRF_HEAD_MLP_FEA)
+    RDRF_LAUNCH("static_app", k_masked_static_app<RDRF_HEAD_MLP_FEA>, dim3(g3.grid), dim3(g3.block), stream, as, wst);
+  else
+    RDRF_LAUNCH("static_app", k_masked_static_app<RDRF_HEAD_MLP_FEA_TIMEEMBEDDING>, dim3(g3.grid), dim3(g3.block), stream, as, wst);
+  RDRF_LAUNCH("dyn_app", k_masked_dyn_app, dim3(g3.grid), dim3(g3.block), stream, ad, wdy);
+  return rdrf_composite_fwd(b.rgb_s, b.sigma_s, b.rgb_d, b.sigma_d, b.dists_d, b.blending, b.z, rays, N, S, cfg_d->ray_type, 0,
+                            nullptr, b.out, stream);
+}

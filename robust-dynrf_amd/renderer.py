@@ -253,8 +253,23 @@ def _motion_request(motion, N, dev):
     return bufs, mm, cams, (focal, pose)
 
 
+def _mask_pair(tensorf_static, tensorf, alpha_masks):
+    """alpha_masks of render_rays -> None (no masks) or the pair (static, dynamic), at least one of them a mask"""
+    if alpha_masks is None or alpha_masks is False:
+        return None
+    if alpha_masks is True:
+        alpha_masks = (tensorf_static.alphaMask, tensorf.alphaMask)
+    pair = tuple(alpha_masks)
+    if len(pair) != 2:
+        raise ValueError("alpha_masks: True or a pair (mask_static, mask_dynamic)")
+    if pair[0] is None and pair[1] is None:
+        raise ValueError("alpha_masks: both masks are None (updateAlphaMask builds a field's mask)")
+    return pair
+
+
 @torch.no_grad()
-def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc", mode="auto", maps=False, motion=None):
+def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc", mode="auto", maps=False, motion=None,
+                alpha_masks=None, kept=None):
     """No-grad render of a ray chunk through ONE C-ABI call: the loop body of renderer.py:740-812.
     mode "auto" (rdrf_render_fwd: the per-phase launch sequence), "fused" (rdrf_render_fused_fwd:
     one cooperative launch) or "sequence" (rdrf_render_sequence_fwd); all three give the same bits.
@@ -266,8 +281,21 @@ def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc",
     With `motion` (a dict: H, W, focal, c2w_f, c2w_b -- the [3,4] poses of the next / previous frame --, first_pixel = flat
     pixel of ray 0 in the H x W image (default 0), maps = True or a subset of the MotionMaps field names) the call goes
     through rdrf_render_motion_fwd and returns (the above, MotionMaps): the induced-flow and warp-displacement maps of
-    renderer.py:487-537, :610 from the render's own workspace, the colour maps bit for bit as without `motion`."""
+    renderer.py:487-537, :610 from the render's own workspace, the colour maps bit for bit as without `motion`.
+    With `alpha_masks` -- a pair (mask_static, mask_dynamic) of AlphaGridMask or None, or True for
+    (tensorf_static.alphaMask, tensorf.alphaMask) -- the call goes through rdrf_render_masked_fwd: the maps are those of
+    apply_alpha_mask on the sampler's `valid` per field, the fields' forward and raw2outputs, bit for bit, and the density
+    phase of a field runs on the samples its mask keeps only.  `kept`: an int64 device tensor [2] that receives the kept
+    sample counts (static, dynamic).  No mode "fused" and no `motion` with masks."""
     from .fields import _attach_packed, _cfg_struct, _dynamic_struct, _static_struct
+    masks = _mask_pair(tensorf_static, tensorf, alpha_masks)
+    if masks is None and kept is not None:
+        raise ValueError("render_rays: `kept` is the masked render's output (alpha_masks)")
+    if masks is not None:
+        if mode == "fused":
+            raise NotImplementedError("render_rays: the single-launch render (mode='fused') reads no alpha masks.")
+        if motion is not None:
+            raise NotImplementedError("render_rays: no motion maps with alpha masks (xyz_prime of a dropped sample is undefined).")
     L.require_device(rays, ts)
     rays, ts = L.f32c(rays), L.f32c(ts)
     N = rays.shape[0]
@@ -284,6 +312,19 @@ def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc",
     _attach_packed(tensorf, PD, pd_list, False, True)
     cs, cd = _cfg_struct(tensorf_static, ray_type), _cfg_struct(tensorf, ray_type)
     near, far = tensorf.near_far
+    if masks is not None:
+        if kept is not None and (kept.dtype != torch.int64 or kept.numel() != 2 or not kept.is_cuda or not kept.is_contiguous()):
+            raise L.RdrfError("render_rays: `kept` is a contiguous int64 device tensor of two elements")
+        bufs = _alloc_maps(_map_names(maps), N, dev) if maps else {"rgb": rgb, "depth": depth}
+        M = _maps_struct(bufs)
+        ms, md = (None if m is None else m._struct() for m in masks)
+        ws = L.workspace(dev, int(L.lib.rdrf_render_masked_ws_bytes(N, S)))
+        step = 0.0 if ray_type in L.RAY_TYPES else tensorf._step_host
+        L.check(L.lib.rdrf_render_masked_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S,
+                                             near, far, step, None if ms is None else C.byref(ms),
+                                             None if md is None else C.byref(md), C.byref(M), L.ptr(kept), L.ptr(ws),
+                                             ws.numel(), L.stream_of(rays)), "rdrf_render_masked_fwd")
+        return RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS}) if maps else (rgb, depth)
     if motion is not None:
         if ray_type not in L.RAY_TYPES:
             raise NotImplementedError("motion maps: ray_type must be 'ndc' or 'contract' (the reference projects no other, "
@@ -323,14 +364,18 @@ _stream_pool = {}
 
 
 @torch.no_grad()
-def render_chunks(tensorf_static, tensorf, rays, ts, chunk, N_samples=-1, ray_type="ndc", streams=8, maps=False):
+def render_chunks(tensorf_static, tensorf, rays, ts, chunk, N_samples=-1, ray_type="ndc", streams=8, maps=False,
+                  alpha_masks=None):
     """The chunk loop of renderer.py:740-812 (`for chunk_idx in range(N_rays_all // chunk + ...)`, chunk = 512 at
     renderer.py:732) as ONE native call (rdrf_render_chunks_fwd): the chunks' launch sequences are issued from C,
     round-robin on `streams` HIP streams (0 / 1: all on the current stream).  Issued chunk by chunk from Python the loop
     is host-bound (~250 us of marshalling per chunk against ~190 us of GPU work); and one 512-ray chunk fills only
     64-110 of the 256 CUs, so independent chunks run side by side.  Same bits as render_rays on the whole batch.
-    Returns (rgb_map [N,3], depth_map [N]); with `maps`, a RenderMaps as render_rays (rdrf_render_chunks_maps_fwd)."""
+    Returns (rgb_map [N,3], depth_map [N]); with `maps`, a RenderMaps as render_rays (rdrf_render_chunks_maps_fwd).
+    `alpha_masks` is not built here (render_rays has it)."""
     from .fields import _attach_packed, _cfg_struct, _dynamic_struct, _static_struct
+    if alpha_masks is not None and alpha_masks is not False:
+        raise NotImplementedError("render_chunks: the native chunk loop reads no alpha masks (render_rays does).")
     L.require_device(rays, ts)
     rays, ts = L.f32c(rays), L.f32c(ts)
     N, dev = rays.shape[0], rays.device
@@ -377,9 +422,10 @@ def render_chunks(tensorf_static, tensorf, rays, ts, chunk, N_samples=-1, ray_ty
     return RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS}) if maps else (rgb, depth)
 
 
-def _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps, motion=None):
+def _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps, motion=None, alpha_masks=None):
     """the rays of one H x W image through render_rays in chunks (default: the whole image in one launch sequence);
-    `motion`: the dict of render_rays without first_pixel (every chunk passes its own) -> (images, MotionMaps of images)"""
+    `motion`: the dict of render_rays without first_pixel (every chunk passes its own) -> (images, MotionMaps of images);
+    `alpha_masks`: as render_rays"""
     dev = rays.device
     S_ = int(N_samples) if N_samples and N_samples > 0 else tensorf.nSamples
     if not chunk:   # whole frame in one launch sequence, bounded by the kernels' 32-bit sample indices
@@ -392,9 +438,10 @@ def _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, 
 
     def run(c0, want):
         if motion is None:
-            return render_rays(tensorf_static, tensorf, rays[c0:c0 + chunk], ts[c0:c0 + chunk], N_samples, ray_type, maps=want)
+            return render_rays(tensorf_static, tensorf, rays[c0:c0 + chunk], ts[c0:c0 + chunk], N_samples, ray_type, maps=want,
+                               alpha_masks=alpha_masks)
         part, mpart = render_rays(tensorf_static, tensorf, rays[c0:c0 + chunk], ts[c0:c0 + chunk], N_samples, ray_type,
-                                  maps=want, motion=dict(motion, first_pixel=c0))
+                                  maps=want, motion=dict(motion, first_pixel=c0), alpha_masks=alpha_masks)
         for n in mout:
             mout[n][c0:c0 + chunk] = getattr(mpart, n)
         return part
@@ -429,7 +476,7 @@ def _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, 
 
 @torch.no_grad()
 def render_frame(tensorf_static, tensorf, poses9, focal, frame, H, W, N_samples=-1, ray_type="ndc",
-                 chunk=None, t=None, maps=False, motion=False):
+                 chunk=None, t=None, maps=False, motion=False, alpha_masks=None):
     """Whole-frame no-grad render (the per-image body of renderer.py:661-966 `evaluation`): rays of
     every pixel of `frame` are generated on the device and pushed through rdrf_render_fwd in chunks
     (default: the whole frame in one launch sequence).  `t` overrides the frame's own time in [-1,1].
@@ -439,7 +486,8 @@ def render_frame(tensorf_static, tensorf, poses9, focal, frame, H, W, N_samples=
     transform is the caller's.)
     With `motion` (True, or a subset of the MotionMaps field names): returns (the above, MotionMaps) with the flows as
     [H,W,2] and delta_xyz as [H,W,3]; the neighbour cameras are the reference's, frames min(frame + 1, T - 1) and
-    max(frame - 1, 0) of `poses9` (renderer.py:386-387)."""
+    max(frame - 1, 0) of `poses9` (renderer.py:386-387).
+    `alpha_masks`: as render_rays (the masked render; not together with `motion`)."""
     from .ray_utils import generate_rays, pose_to_mtx
     dev = poses9.device
     T = poses9.shape[0]
@@ -451,7 +499,7 @@ def render_frame(tensorf_static, tensorf, poses9, focal, frame, H, W, N_samples=
     if motion:
         mtx = pose_to_mtx(poses9.detach().float())
         req = dict(H=H, W=W, focal=focal, c2w_f=mtx[min(int(frame) + 1, T - 1)], c2w_b=mtx[max(int(frame) - 1, 0)], maps=motion)
-    return _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps, req)
+    return _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps, req, alpha_masks)
 
 
 def _focal_per_camera(focal, B, dev):
@@ -482,13 +530,14 @@ def camera_rays(c2w, focal, H, W, ndc=True, near=1.0, first=0, n=None):
 
 @torch.no_grad()
 def render_view(tensorf_static, tensorf, c2w, focal, H, W, t, N_samples=-1, ray_type="ndc", maps=True, chunk=None,
-                c2w_f=None, c2w_b=None, motion=False):
+                c2w_f=None, c2w_b=None, motion=False, alpha_masks=None):
     """One arbitrary camera c2w [3,4] (host or device; moved to the fields' device) at time t in [-1,1]: the per-view body
     of renderer.py:970-1263 `evaluation_path` (eval rays: camera_rays, NDC with near = 1 for ndc scenes; ray_type "world":
     the camera's un-normalised world rays marched through the aabb, see sample_rays).  Returns a
     RenderMaps of [H,W,3] / [H,W] images (clamped as render_frame) with `maps`, else (rgb [H,W,3], depth [H,W]).
     With `motion` (True, or a subset of the MotionMaps field names) and the neighbour cameras c2w_f / c2w_b [3,4] (default:
-    the view's own camera): returns (the above, MotionMaps of [H,W,2] / [H,W,3] images) as render_frame."""
+    the view's own camera): returns (the above, MotionMaps of [H,W,2] / [H,W,3] images) as render_frame.
+    `alpha_masks`: as render_rays (the masked render; not together with `motion`)."""
     if motion and ray_type not in L.RAY_TYPES:
         raise NotImplementedError("motion maps: ray_type must be 'ndc' or 'contract' (the reference projects no other, "
                                   "renderer.py:1335-1351)")
@@ -503,7 +552,7 @@ def render_view(tensorf_static, tensorf, c2w, focal, H, W, t, N_samples=-1, ray_
         own = c2w.reshape(3, 4)
         req = dict(H=H, W=W, focal=focal, c2w_f=own if c2w_f is None else c2w_f, c2w_b=own if c2w_b is None else c2w_b,
                    maps=motion)
-    return _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps, req)
+    return _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps, req, alpha_masks)
 
 
 def flow_to_image(flow):
@@ -540,17 +589,18 @@ def path_time(change_time, idx, n):
 
 
 def render_path(tensorf_static, tensorf, c2ws, focal, H, W, change_time="change", N_samples=-1, ray_type="ndc",
-                maps=True, chunk=None):
+                maps=True, chunk=None, alpha_masks=None):
     """renderer.py:970-1263 `evaluation_path`: yields render_view(c2ws[idx], focal[idx] or focal, path_time(...)) per
     view, in order.  c2ws [n,3,4] (a tensor, an array or a list of [3,4]); focal a scalar or one per view (render_focal);
-    change_time "change" or a fixed time (path_time).  The image / video writing is the caller's."""
+    change_time "change" or a fixed time (path_time).  The image / video writing is the caller's.  `alpha_masks`: as
+    render_rays."""
     n = len(c2ws)
     per_view = (torch.is_tensor(focal) and focal.numel() > 1) or (not torch.is_tensor(focal) and hasattr(focal, "__len__"))
     if per_view and len(focal) != n:
         raise ValueError(f"render_path: {len(focal)} focal values for {n} views")
     for idx in range(n):
         yield render_view(tensorf_static, tensorf, c2ws[idx], focal[idx] if per_view else focal, H, W,
-                          path_time(change_time, idx, n), N_samples, ray_type, maps, chunk)
+                          path_time(change_time, idx, n), N_samples, ray_type, maps, chunk, alpha_masks=alpha_masks)
 
 
 def psnr(img, ref):

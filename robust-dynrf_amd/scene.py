@@ -233,11 +233,12 @@ class Scene:
 
 
 @torch.no_grad()
-def evaluate(trainer, scene, frames="heldout"):
+def evaluate(trainer, scene, frames="heldout", alpha_masks=None):
     """PSNR and SSIM of the trainer's fields against the scene's images: frames="heldout" renders the scene's held-out
     cameras through render_view, "train" every training frame through render_frame with the trainer's current poses and
     focal length (the per-image body of renderer.py:661-966 `evaluation`).  Everything stays on the device until one
-    transfer at the end.  Returns dict(psnr=[...], ssim=[...], psnr_mean, ssim_mean)."""
+    transfer at the end.  `alpha_masks`: as render_rays (True: the fields' own alphaMask; the masked render).
+    Returns dict(psnr=[...], ssim=[...], psnr_mean, ssim_mean)."""
     c = trainer.cfg
     st, dy, H, W, S, rt = trainer.st, trainer.dy, scene.H, scene.W, c["n_samples"], c["ray_type"]
     focal = trainer.focal()
@@ -247,12 +248,12 @@ def evaluate(trainer, scene, frames="heldout"):
         if not scene.heldout:
             raise ValueError("evaluate: the scene has no held-out views")
         for c2w, t, img in scene.heldout:
-            rgb, _ = render_view(st, dy, c2w, focal, H, W, t, N_samples=S, ray_type=rt, maps=False)
+            rgb, _ = render_view(st, dy, c2w, focal, H, W, t, N_samples=S, ray_type=rt, maps=False, alpha_masks=alpha_masks)
             pairs.append((rgb, img))
     elif frames == "train":
         poses = trainer.pose_table().detach()
         for f in range(scene.T):
-            rgb, _ = render_frame(st, dy, poses, focal, f, H, W, N_samples=S, ray_type=rt)
+            rgb, _ = render_frame(st, dy, poses, focal, f, H, W, N_samples=S, ray_type=rt, alpha_masks=alpha_masks)
             pairs.append((rgb, scene.image(f)))
     else:
         raise ValueError('evaluate: frames is "heldout" or "train"')

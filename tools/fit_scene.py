@@ -5,7 +5,9 @@ scene.npz holds the arguments of rodynrf.Scene under their own names (rgb [T,H,W
 heldout_c2w [K,3,4], heldout_t [K], heldout_rgb [K,H,W,3]).  The run follows the config's resolution schedule
 (rodynrf.resolution_stages) and writes out_dir/run.th, run_static.th (the reference's checkpoint format), run_state.th (what
 Trainer.load needs to continue the run) and metrics.json (PSNR / SSIM of the training frames and of the held-out views).
---resume continues from out_dir/run_state.th."""
+--resume continues from out_dir/run_state.th.  --alpha-mask G0,G1,G2: after the fit, updateAlphaMask on both fields at that
+lattice and a second evaluation through the masked render; metrics.json then also holds "alpha_mask" (the occupied
+fractions) and "train_masked" / "heldout_masked"."""
 import argparse
 import json
 import os
@@ -29,7 +31,14 @@ def main():
     ap.add_argument("--resume", action="store_true")
     ap.add_argument("--seed", type=int, default=20211202)
     ap.add_argument("--log-every", type=int, default=1000)
+    ap.add_argument("--alpha-mask", default=None, metavar="G0,G1,G2",
+                    help="build both fields' alpha masks on this lattice after the fit and evaluate with and without them")
     a = ap.parse_args()
+    mask_grid = None
+    if a.alpha_mask:
+        mask_grid = [int(v) for v in a.alpha_mask.split(",")]
+        if len(mask_grid) != 3 or min(mask_grid) < 1:
+            ap.error("--alpha-mask takes three positive lattice sizes: G0,G1,G2")
     dev = torch.device("cuda", 0)
     scene = rodynrf.Scene.from_npz(a.npz, device=dev, seed=a.seed)
     cfg = rodynrf.scene_config(a.config or ("nvidia" if scene.has_poses else "nvidia_no_poses"))
@@ -54,6 +63,15 @@ def main():
                    loss=[(it, float(l)) for it, l in log], train=rodynrf.evaluate(tr, scene, frames="train"))
     if scene.heldout:
         metrics["heldout"] = rodynrf.evaluate(tr, scene, frames="heldout")
+    if mask_grid is not None:
+        metrics["alpha_mask"] = dict(grid=mask_grid)
+        for name, field in (("static", tr.st), ("dynamic", tr.dy)):
+            field.updateAlphaMask(mask_grid)
+            st = field.alphaMask_stats
+            metrics["alpha_mask"][name] = dict(st, fraction=st["occupied"] / st["total"])
+        metrics["train_masked"] = rodynrf.evaluate(tr, scene, frames="train", alpha_masks=True)
+        if scene.heldout:
+            metrics["heldout_masked"] = rodynrf.evaluate(tr, scene, frames="heldout", alpha_masks=True)
     with open(os.path.join(a.out, "metrics.json"), "w") as f:
         json.dump(metrics, f, indent=1)
     print(json.dumps({k: (v if not isinstance(v, dict) else {"psnr_mean": v["psnr_mean"], "ssim_mean": v["ssim_mean"]})
