@@ -560,6 +560,42 @@ int rdrf_render_motion_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s
 size_t rdrf_flow_to_image_workspace_bytes(int H, int W);
 int rdrf_flow_to_image(const float* flow, int H, int W, uint8_t* rgb, void* ws, size_t ws_bytes, rdrf_stream_t stream);
 
+/* ---- point tracks: the scene-flow field chained across frames (no-grad) ----------------------------------------------
+ * M seed points p0[M][3] (un-normalised field coordinates, as rdrf_scene_flow_fwd takes them) at times t0[M] in [-1,1]
+ * are followed n_fwd frames forward and n_bwd frames backward, K = n_bwd + 1 + n_fwd slots per point, slot n_bwd = the seed:
+ *     forward   p_{k+1} = p_k + scene_flow_f(p_k, t_k),  t_{k+1} = t_k + dt
+ *     backward  p_{k-1} = p_k + scene_flow_b(p_k, t_k),  t_{k-1} = t_k - dt       (dt = 2 / (T - 1) for a T-frame video)
+ * fp32, no contraction; cfg_d->ray_type contract clamps every sum to [-2 + 1e-6, 2 - 1e-6] (train.py:1377-1378); ndc or
+ * contract only.  A step's scene flow has rdrf_scene_flow_fwd's bits for that point and time, so a track equals the chain of
+ * single calls bit for bit, and does not depend on M or on which other points share the call.
+ * cams (nullable): camera k of slot k.  pix = render_single_3d_point's pixel coordinates of p_k in camera k
+ * (renderer.py:1299-1325; contract: render_3d_point's contract2world leg, :1351-1366); disp = its second output, (z_ndc + 1) / 2
+ * for ndc, z_ndc for contract.  One nullable DEVICE pointer per output; pix / disp need `cams`.
+ * ws: rdrf_track_ws_bytes(M, K) (the pack area; not read when PD->packed_fwd is given).  M == 0 is a no-op. */
+typedef struct RdrfTrackCams {
+  int H, W;
+  int K;                  /* number of cameras: must equal n_bwd + 1 + n_fwd */
+  const float* focal;     /* DEVICE, one float (as rdrf_induce_flow_fwd) */
+  const float* c2w;       /* DEVICE [K][3][4] */
+} RdrfTrackCams;
+typedef struct RdrfTracks {
+  float* pts;    /* [M][K][3] */
+  float* pix;    /* [M][K][2] */
+  float* disp;   /* [M][K] */
+} RdrfTracks;
+size_t rdrf_track_ws_bytes(int M, int K);
+int rdrf_track_points_fwd(const RdrfDynamicParams* PD, const RdrfFieldCfg* cfg_d, const float* p0, const float* t0, int M,
+                          int n_fwd, int n_bwd, float dt, const RdrfTrackCams* cams, const RdrfTracks* out, void* ws,
+                          size_t ws_bytes, rdrf_stream_t stream);
+/* rdrf_render_maps_fwd (the launch sequence; same bits in every requested RdrfRenderMaps entry, `maps` may be NULL), then
+ * seeds[N][3] = sum_s weights_d xyz + (1 - acc_d) far from the render's workspace: the first half of render_3d_point
+ * (renderer.py:1333-1345, far point per ray type), the point a track of that pixel starts from.  ndc or contract.
+ * ws: rdrf_render_motion_workspace_bytes(N, S). */
+int rdrf_render_track_seeds_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                                const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near,
+                                float far, const RdrfRenderMaps* maps, float* seeds, void* ws, size_t ws_bytes,
+                                rdrf_stream_t stream);
+
 /* ---- rays of arbitrary cameras (evaluation_path, renderer.py:1013-1030; evaluation, :702-716) -----------------------
  * c2w[B][3][4] camera-to-world matrices, focal[B] per camera.  Ray k is flat pixel first + k over (B, H, W):
  * get_ray_directions_blender (pixel centre + 0.5, centre (W/2, H/2), focal on both axes, dataLoader/ray_utils.py:93-110),

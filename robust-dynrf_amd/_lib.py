@@ -98,6 +98,18 @@ class BatchC(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in BATCH_OUTPUTS]
 
 
+# RdrfTrackCams / RdrfTracks (include/rodynrf.h): the cameras a point track is projected into and its nullable outputs
+TRACK_OUTPUTS = ("pts", "pix", "disp")
+
+
+class TrackCamsC(C.Structure):
+    _fields_ = [("H", C.c_int), ("W", C.c_int), ("K", C.c_int), ("focal", C.c_void_p), ("c2w", C.c_void_p)]
+
+
+class TracksC(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in TRACK_OUTPUTS]
+
+
 class RdrfAlphaMask(C.Structure):   # include/rodynrf.h RdrfAlphaMask: a packed occupancy grid (alpha.AlphaGridMask)
     _fields_ = [("bits", C.c_void_p), ("grid", C.c_int * 3), ("T", C.c_int), ("aabb", C.c_float * 6)]
 
@@ -186,6 +198,14 @@ def _load():
                                                C.c_int, C.c_float, C.c_float, C.c_float, C.POINTER(RdrfAlphaMask),
                                                C.POINTER(RdrfAlphaMask), C.POINTER(RenderMapsC), C.c_void_p, C.c_void_p,
                                                C.c_size_t, C.c_void_p]
+    if hasattr(lib, "rdrf_track_points_fwd"):   # (an addition inside ABI 6, as above)
+        lib.rdrf_track_ws_bytes.restype = C.c_size_t
+        lib.rdrf_track_ws_bytes.argtypes = [C.c_int, C.c_int]
+        lib.rdrf_track_points_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                              C.POINTER(TrackCamsC), C.POINTER(TracksC), C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.rdrf_render_track_seeds_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                    C.c_int, C.c_float, C.c_float, C.POINTER(RenderMapsC), C.c_void_p, C.c_void_p,
+                                                    C.c_size_t, C.c_void_p]
     lib.rdrf_gather_batch.argtypes = [C.POINTER(SceneTablesC), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(BatchC), C.c_void_p]
     lib.rdrf_selftest_layer.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_size_t, C.c_void_p]
@@ -247,6 +267,7 @@ SYMBOLS = [
     "rdrf_gather_batch",
     "rdrf_compute_alpha_workspace_bytes", "rdrf_compute_alpha", "rdrf_alpha_mask_build", "rdrf_alpha_mask_sample",
     "rdrf_alpha_mask_valid", "rdrf_render_masked_ws_bytes", "rdrf_render_masked_fwd",
+    "rdrf_track_ws_bytes", "rdrf_track_points_fwd", "rdrf_render_track_seeds_fwd",
     "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_selftest_layer", "rdrf_selftest_dw", "rdrf_selftest_dw_describe",
     "rdrf_selftest_dw_plan",
     "rdrf_selftest_sf_geometry", "rdrf_selftest_warp_geometry", "rdrf_selftest_warp_bwd_workspace_bytes", "rdrf_selftest_warp_bwd",

@@ -261,8 +261,9 @@ RDRF_D int argmax_abs3(const float (&v)[3], float& n) {
   if (fabsf(v[2]) > n) { n = fabsf(v[2]); k = 2; }
   return k;
 }
-RDRF_D void flow_ray_fwd(FlowRay& r, const float* ray, const float* c2w, float acc, const float (&ps)[3],
-                         int H, int W, float f, int ray_type, float& u, float& v, float& disp) {
+// first half (renderer.py:1333-1345): P = ps + (1 - acc) far, the far point per ray type; also the seed of a point track
+// (k_track_seeds, rdrf_track.hip)
+RDRF_D void flow_ray_seed(FlowRay& r, const float* ray, float acc, const float (&ps)[3], int ray_type) {
 #pragma clang fp contract(off)
   r.acc = acc;
   if (ray_type == RDRF_RAY_NDC) {
@@ -282,6 +283,11 @@ RDRF_D void flow_ray_fwd(FlowRay& r, const float* ray, const float* c2w, float a
     }
   }
   for (int i = 0; i < 3; ++i) r.P[i] = ps[i] + (1.0f - acc) * r.far[i];
+}
+RDRF_D void flow_ray_fwd(FlowRay& r, const float* ray, const float* c2w, float acc, const float (&ps)[3],
+                         int H, int W, float f, int ray_type, float& u, float& v, float& disp) {
+#pragma clang fp contract(off)
+  flow_ray_seed(r, ray, acc, ps, ray_type);
   if (ray_type == RDRF_RAY_NDC) {
     r.c = fminf(fmaxf(r.P[2], -1.0f), 1.0f - 1e-6f);
     r.pz = 2.0f / (r.c - 1.0f);

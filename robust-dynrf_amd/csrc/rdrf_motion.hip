@@ -4,12 +4,10 @@
 //                     sum_s weights_d (xyz_prime - xyz) (:460, :610) from what the render left in its workspace
 //   k_flow_to_image : flow_viz.flow_to_image (flow_viz.py:107-136, defaults) -- the Middlebury colour wheel
 #include "rdrf_misc_dev.hpp"
+#include "rdrf_render_host.hpp"
 
-// host helpers of rdrf_fwd.hip / rdrf_render.hip
+// host helper of rdrf_fwd.hip
 int ws_carve_fwd(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S, void* saved, size_t saved_bytes, int dynamic);
-int render_motion_views(const RdrfRenderMaps* maps, void* ws, size_t ws_bytes, int N, int S, const float** xyz,
-                        const float** xyz_prime, const float** weights_s, const float** weights_d, const unsigned** barrier,
-                        void** fws_d);
 
 // ------------------------------------------------------------------------------------------------
 // k_motion_maps: one wave per ray, 32-sample tiles (sample s of the tile in lanes s and s + 32: the layout of mfma_seg).

@@ -14,3 +14,8 @@ struct RenderBufs {
 void maps_to_slots(float* out[13], const RdrfRenderMaps* m);
 // want[13]: the caller's output buffers (NULL: the output goes to the workspace)
 int carve_render(RenderBufs& b, void* ws, size_t ws_bytes, int N, int S, float* const want[13]);
+// where a render with these `maps` left what the kernels that run after it read (rdrf_motion.hip, rdrf_track.hip): the
+// carve of the render itself
+int render_motion_views(const RdrfRenderMaps* maps, void* ws, size_t ws_bytes, int N, int S, const float** xyz,
+                        const float** xyz_prime, const float** weights_s, const float** weights_d, const unsigned** barrier,
+                        void** fws_d);

@@ -1042,6 +1042,16 @@ class TensorVMSplit_TimeEmbedding(TensorBase):
     def get_forward_backward_scene_flow(self, unnormalized_pts, t_sampled):
         return _SceneFlowFn.apply(self, torch.is_grad_enabled(), unnormalized_pts, t_sampled, *self._param_list())
 
+    def get_forward_backward_scene_flow_point_single(self, pts_map_NDC, t_sampled):
+        """models/tensoRF.py:506-519: one point per ray, pts_map_NDC [N,3] un-normalised, t_sampled [N] ->
+        (pts + scene_flow_f, pts + scene_flow_b, scene_flow_f, scene_flow_b), each [N,3].  The S = 1 case of
+        get_forward_backward_scene_flow: the same kernel, the same bits, the same backward."""
+        if pts_map_NDC.dim() != 2 or pts_map_NDC.shape[-1] != 3 or t_sampled.shape != pts_map_NDC.shape[:1]:
+            raise L.RdrfError("get_forward_backward_scene_flow_point_single: expected pts_map_NDC [N,3] and t_sampled [N]")
+        sf_f, sf_b = self.get_forward_backward_scene_flow(pts_map_NDC.reshape(-1, 1, 3), t_sampled)
+        sf_f, sf_b = sf_f.reshape(-1, 3), sf_b.reshape(-1, 3)
+        return pts_map_NDC + sf_f, pts_map_NDC + sf_b, sf_f, sf_b
+
     def _features(self, want, x, t, normalized):
         x2 = x.reshape(-1, 3)
         t2 = t.reshape(-1)

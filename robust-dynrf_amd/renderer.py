@@ -15,6 +15,9 @@ RenderMaps = namedtuple("RenderMaps", L.RENDER_MAPS)
 # through the scene-flow MLP (flow_f, flow_b) and through camera motion alone (flow_s_f, flow_s_b), [N,2] pixels, and the
 # warp displacement sum_s weights_d (xyz_prime - xyz) [N,3]
 MotionMaps = namedtuple("MotionMaps", L.MOTION_MAPS)
+# point tracks (track_points): points [M,K,3] in field coordinates, pixels [M,K,2] and disp [M,K] in camera k (None without
+# cameras), frames_offset [K] = -n_bwd .. n_fwd: slot k is the seed's frame + frames_offset[k]
+Tracks = namedtuple("Tracks", ("points", "pixels", "disp", "frames_offset"))
 
 
 class _SampleFn(torch.autograd.Function):
@@ -553,6 +556,122 @@ def render_view(tensorf_static, tensorf, c2w, focal, H, W, t, N_samples=-1, ray_
         req = dict(H=H, W=W, focal=focal, c2w_f=own if c2w_f is None else c2w_f, c2w_b=own if c2w_b is None else c2w_b,
                    maps=motion)
     return _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps, req, alpha_masks)
+
+
+def _track_points_raw(tensorf, pts, ts, n_fwd, n_bwd, dt, cameras, focal, H, W, ray_type, want, bufs=None, ws=None):
+    """rdrf_track_points_fwd on checked arguments.  want: subset of L.TRACK_OUTPUTS; bufs / ws: caller-owned output
+    buffers by name and workspace (the tests poison them), else allocated here.  Returns the buffers by name."""
+    from .fields import _attach_packed, _cfg_struct, _dynamic_struct
+    L.require_device(pts, ts, cameras)
+    pts, ts = L.f32c(pts.detach()), L.f32c(ts.detach())
+    M, K, dev = pts.shape[0], n_bwd + 1 + n_fwd, pts.device
+    shapes = {"pts": (M, K, 3), "pix": (M, K, 2), "disp": (M, K)}
+    if bufs is None:
+        bufs = {n: torch.empty(shapes[n], device=dev) for n in want}
+    keep = None
+    cams = None
+    if cameras is not None:
+        cameras = L.f32c(cameras.detach())
+        f = _focal_tensor(focal.detach().to(dev) if torch.is_tensor(focal) else focal, dev).contiguous()
+        cams = L.TrackCamsC(int(H), int(W), int(cameras.shape[0]), f.data_ptr(), cameras.data_ptr())
+        keep = (cameras, f)
+    out = L.TracksC(*[bufs[n].data_ptr() if n in want else None for n in L.TRACK_OUTPUTS])
+    params = tensorf._param_list()
+    P = _dynamic_struct(params)
+    _attach_packed(tensorf, P, params, False, True)
+    cfg = _cfg_struct(tensorf, ray_type)
+    if ws is None:
+        ws = L.workspace(dev, int(L.lib.rdrf_track_ws_bytes(M, K)))
+    L.check(L.lib.rdrf_track_points_fwd(C.byref(P), C.byref(cfg), L.ptr(pts), L.ptr(ts), M, int(n_fwd), int(n_bwd), C.c_float(dt),
+                                        None if cams is None else C.byref(cams), C.byref(out), L.ptr(ws), ws.numel(),
+                                        L.stream_of(pts)), "rdrf_track_points_fwd")
+    del keep
+    return bufs
+
+
+def _track_args(pts, ts, n_fwd, n_bwd, T, cameras, focal, H, W, ray_type):
+    """argument checks of track_points (before any device work); returns (n_fwd, n_bwd, dt)"""
+    if ray_type not in L.RAY_TYPES:
+        raise NotImplementedError("track_points: ray_type must be 'ndc' or 'contract' (the reference projects no other, "
+                                  "renderer.py:1335-1351)")
+    n_fwd, n_bwd = int(n_fwd), int(n_bwd)
+    if n_fwd < 0 or n_bwd < 0:
+        raise ValueError(f"track_points: n_fwd and n_bwd are step counts >= 0, got {n_fwd}, {n_bwd}")
+    if pts.dim() != 2 or pts.shape[1] != 3 or ts.shape != pts.shape[:1]:
+        raise ValueError("track_points: pts [M,3] un-normalised field coordinates, ts [M] times in [-1,1]")
+    if int(T) < 2 and (n_fwd or n_bwd):
+        raise ValueError("track_points: a video of T < 2 frames has no time step")
+    if cameras is not None:
+        K = n_bwd + 1 + n_fwd
+        if cameras.dim() != 3 or tuple(cameras.shape[1:]) != (3, 4) or cameras.shape[0] != K:
+            raise ValueError(f"track_points: cameras must be [K,3,4] with K = n_bwd + 1 + n_fwd = {K}, got {tuple(cameras.shape)}")
+        if focal is None or H is None or W is None or int(H) <= 0 or int(W) <= 0:
+            raise ValueError("track_points: cameras need focal, H and W")
+    return n_fwd, n_bwd, (2.0 / (int(T) - 1) if int(T) >= 2 else 0.0)
+
+
+@torch.no_grad()
+def track_points(tensorf, pts, ts, n_fwd, n_bwd, T, cameras=None, focal=None, H=None, W=None, ray_type="ndc"):
+    """Follow M points through the video by chaining the scene-flow field natively (rdrf_track_points_fwd, ONE launch):
+    pts [M,3] un-normalised field coordinates (as get_forward_backward_scene_flow takes them) at times ts [M] in [-1,1],
+    n_fwd steps p + scene_flow_f forward and n_bwd steps p + scene_flow_b backward, the time moving by 2 / (T - 1) per
+    step; contract scenes clamp every step to [-2 + 1e-6, 2 - 1e-6] (train.py:1377-1378).  Bit for bit the chain of
+    get_forward_backward_scene_flow_point_single calls.  cameras [K,3,4] (K = n_bwd + 1 + n_fwd, camera k of slot k) with
+    focal, H, W: each point is projected into its slot's camera as render_single_3d_point does (contract:
+    render_3d_point's contract2world leg).  Returns Tracks(points [M,K,3], pixels [M,K,2] | None, disp [M,K] | None,
+    frames_offset [K]); slot n_bwd is the seed.  No gradients; no visibility along the track."""
+    n_fwd, n_bwd, dt = _track_args(pts, ts, n_fwd, n_bwd, T, cameras, focal, H, W, ray_type)
+    want = L.TRACK_OUTPUTS if cameras is not None else ("pts",)
+    b = _track_points_raw(tensorf, pts, ts, n_fwd, n_bwd, dt, cameras, focal, H, W, ray_type, want)
+    return Tracks(b["pts"], b.get("pix"), b.get("disp"), torch.arange(-n_bwd, n_fwd + 1, device=pts.device))
+
+
+@torch.no_grad()
+def render_tracks(tensorf_static, tensorf, poses9, focal, frame, pixels, H, W, span=None, N_samples=-1, ray_type="ndc"):
+    """Tracks of M query pixels of `frame`: pixels [M,2] integer (column, row).  Their rays are rendered by the no-grad
+    launch sequence (rdrf_render_track_seeds_fwd), the seed of a pixel is render_3d_point's point
+    sum_s weights_d xyz + (1 - acc_d) far of its ray, and track_points follows it through the frames
+    frame - span .. frame + span clipped to [0, T - 1] (span None: the whole video; a pair: (backward, forward)), projected
+    into those frames' cameras.  Returns (Tracks, acc_d [M]): a seed with a small acc_d sits in static or empty space."""
+    from .fields import _attach_packed, _cfg_struct, _dynamic_struct, _static_struct
+    from .ray_utils import generate_rays, pose_to_mtx
+    if ray_type not in L.RAY_TYPES:
+        raise NotImplementedError("render_tracks: ray_type must be 'ndc' or 'contract' (the reference projects no other, "
+                                  "renderer.py:1335-1351)")
+    T, frame = poses9.shape[0], int(frame)
+    if not 0 <= frame < T:
+        raise ValueError(f"render_tracks: frame {frame} of a {T}-frame video")
+    sb, sf_ = (T, T) if span is None else ((int(span[0]), int(span[1])) if isinstance(span, (tuple, list)) else (int(span), int(span)))
+    if sb < 0 or sf_ < 0:
+        raise ValueError("render_tracks: span >= 0")
+    n_bwd, n_fwd = min(sb, frame), min(sf_, T - 1 - frame)
+    L.require_device(poses9, pixels)
+    dev = poses9.device
+    pixels = pixels.to(dev).long()
+    if pixels.dim() != 2 or pixels.shape[1] != 2:
+        raise ValueError("render_tracks: pixels [M,2] integer (column, row)")
+    M = pixels.shape[0]
+    ids = pixels[:, 1] * W + pixels[:, 0] + frame * H * W
+    rays = L.f32c(generate_rays(ids, poses9, focal, H, W, ndc=ray_type == "ndc", near=1.0))
+    ts = torch.full((M,), 2.0 * frame / max(T - 1, 1) - 1.0, device=dev)
+    S = int(N_samples) if N_samples and N_samples > 0 else tensorf.nSamples
+    seeds = torch.empty(M, 3, device=dev)
+    bufs = _alloc_maps(("acc_d",), M, dev)
+    if M:
+        ws = L.workspace(dev, int(L.lib.rdrf_render_motion_workspace_bytes(M, S)))
+        ps_list, pd_list = tensorf_static._param_list(), tensorf._param_list()
+        PS, PD = _static_struct(ps_list), _dynamic_struct(pd_list)
+        _attach_packed(tensorf_static, PS, ps_list, False, False)
+        _attach_packed(tensorf, PD, pd_list, False, True)
+        cs, cd = _cfg_struct(tensorf_static, ray_type), _cfg_struct(tensorf, ray_type)
+        near, far = tensorf.near_far
+        Mp = _maps_struct(bufs)
+        L.check(L.lib.rdrf_render_track_seeds_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), M, S,
+                                                  near, far, C.byref(Mp), L.ptr(seeds), L.ptr(ws), ws.numel(),
+                                                  L.stream_of(rays)), "rdrf_render_track_seeds_fwd")
+    cams = pose_to_mtx(poses9.detach().float())[frame - n_bwd: frame + n_fwd + 1]
+    tracks = track_points(tensorf, seeds, ts, n_fwd, n_bwd, T, cameras=cams, focal=focal, H=H, W=W, ray_type=ray_type)
+    return tracks, bufs["acc_d"]
 
 
 def flow_to_image(flow):

@@ -7,17 +7,39 @@ heldout_c2w [K,3,4], heldout_t [K], heldout_rgb [K,H,W,3]).  The run follows the
 Trainer.load needs to continue the run) and metrics.json (PSNR / SSIM of the training frames and of the held-out views).
 --resume continues from out_dir/run_state.th.  --alpha-mask G0,G1,G2: after the fit, updateAlphaMask on both fields at that
 lattice and a second evaluation through the masked render; metrics.json then also holds "alpha_mask" (the occupied
-fractions) and "train_masked" / "heldout_masked"."""
+fractions) and "train_masked" / "heldout_masked".  --tracks N: after the fit, the point tracks of N grid-spaced pixels of
+the middle frame through the whole video (rodynrf.render_tracks) as out_dir/tracks.npz: points [N,T,3], pixels [N,T,2],
+disp [N,T], acc_d [N] (weight of the dynamic field at the seed), query [N,2] (column, row), frame."""
 import argparse
 import json
 import os
 import sys
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import rodynrf  # noqa: E402
+
+
+def track_queries(n, H, W):
+    """n grid-spaced query pixels of an H x W image, [n,2] integer (column, row): the centres of the cells of a
+    rows x cols lattice with cols / rows ~ W / H and rows * cols >= n, row-major, cut to n"""
+    n = max(1, min(int(n), H * W))
+    cols = max(1, min(W, round((n * W / H) ** 0.5)))
+    rows = min(H, -(-n // cols))
+    cols = min(W, -(-n // rows))      # (rows was capped by H: widen)
+    ys = ((torch.arange(rows) + 0.5) * H / rows).long()
+    xs = ((torch.arange(cols) + 0.5) * W / cols).long()
+    return torch.stack(torch.meshgrid(xs, ys, indexing="xy"), -1).reshape(-1, 2)[:n]
+
+
+def summary(metrics):
+    """the line printed at the end: evaluation entries (those that carry psnr_mean) cut to their two means, the loss
+    curve dropped, everything else as it is"""
+    return {k: ({"psnr_mean": v["psnr_mean"], "ssim_mean": v["ssim_mean"]} if isinstance(v, dict) and "psnr_mean" in v else v)
+            for k, v in metrics.items() if k != "loss"}
 
 
 def main():
@@ -33,6 +55,8 @@ def main():
     ap.add_argument("--log-every", type=int, default=1000)
     ap.add_argument("--alpha-mask", default=None, metavar="G0,G1,G2",
                     help="build both fields' alpha masks on this lattice after the fit and evaluate with and without them")
+    ap.add_argument("--tracks", type=int, default=0, metavar="N",
+                    help="write tracks.npz: point tracks of N grid-spaced pixels of the middle frame (drawing is the caller's)")
     a = ap.parse_args()
     mask_grid = None
     if a.alpha_mask:
@@ -72,10 +96,19 @@ def main():
         metrics["train_masked"] = rodynrf.evaluate(tr, scene, frames="train", alpha_masks=True)
         if scene.heldout:
             metrics["heldout_masked"] = rodynrf.evaluate(tr, scene, frames="heldout", alpha_masks=True)
+    if a.tracks > 0:
+        H, W, frame = scene.H, scene.W, scene.T // 2
+        query = track_queries(a.tracks, H, W).to(dev)
+        focal = tr.focal()
+        tracks, acc_d = rodynrf.render_tracks(tr.st, tr.dy, tr.pose_table().detach(), focal.detach() if torch.is_tensor(focal) else focal,
+                                              frame, query, H, W, N_samples=tr.cfg["n_samples"], ray_type=tr.cfg["ray_type"])
+        np.savez(os.path.join(a.out, "tracks.npz"), points=tracks.points.cpu().numpy(), pixels=tracks.pixels.cpu().numpy(),
+                 disp=tracks.disp.cpu().numpy(), acc_d=acc_d.cpu().numpy(), query=query.cpu().numpy(), frame=frame,
+                 frames_offset=tracks.frames_offset.cpu().numpy())
+        metrics["tracks"] = dict(n=int(query.shape[0]), frame=frame)
     with open(os.path.join(a.out, "metrics.json"), "w") as f:
         json.dump(metrics, f, indent=1)
-    print(json.dumps({k: (v if not isinstance(v, dict) else {"psnr_mean": v["psnr_mean"], "ssim_mean": v["ssim_mean"]})
-                      for k, v in metrics.items() if k != "loss"}))
+    print(json.dumps(summary(metrics)))
 
 
 if __name__ == "__main__":
