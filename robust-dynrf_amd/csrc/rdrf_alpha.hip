@@ -2,9 +2,10 @@
 // the rays, on a lattice, and the occupancy grid made from it.
 //
 //   k_alpha_dyn / k_alpha_static : compute_alpha (:684-702) for M points x T times.  sigma is the density phase of the
-//                  field's forward on the same point and time -- the device functions, the packed image and the order of
-//                  operations of dyn_density_body / static_density_body (rdrf_fwd_dev.hpp), an MFMA column depending on
-//                  its own sample only -- then alpha = 1 - exp(-sigma length).  A point's coordinate encoding is formed
+//                  field's forward on the same point and time -- the per-sample functions dyn_density_body /
+//                  static_density_body call (rdrf_fwd_dev.hpp: load_tout, warp_mlp, warp_point, head_raw<false>;
+//                  static_density_feature) on the same packed image, an MFMA column depending on its own sample
+//                  only -- then alpha = 1 - exp(-sigma length).  A point's coordinate encoding is formed
 //                  once and reused by the T times.
 //   k_alpha_mask_build  : the native part of updateAlphaMask (:592-629): clamp, 3x3x3 max pool per time slice, threshold,
 //                  bit packing in the order `save` (:465-469) flattens the volume, occupied count and lattice box
@@ -65,62 +66,19 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_alpha_dyn(AlphaArgs a, DynW 
       const float t = a.times[kt];
       if (h == 0) X0[3] = t;
       float T[16];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        f32x4 v = ld4(a.tout + (size_t)kt * 32 + 8 * q + 4 * h);
-        T[q * 4 + 0] = v.x; T[q * 4 + 1] = v.y; T[q * 4 + 2] = v.z; T[q * 4 + 3] = v.w;
-      }
-      // ---- warp MLP: [xn, PE10(xn), tout] -> 64 -> 64 -> 3  (models/tensoRF.py:521-541)
-      float d0, d1, d2;
-      {
-        f32x16 acc[2];
-        acc_bias<2>(acc, pkw + pk::K1_B3, h);
-        mfma_seg<2, 32>(acc, X0, pkw + pk::K1_W3_X0, lane);
-        mfma_seg<2, 16>(acc, T, pkw + pk::K1_W3_T, lane);
-        float H3[32];
-        acc_relu<2>(H3, acc);
-        acc_bias<2>(acc, pkw + pk::K1_B4, h);
-        mfma_seg<2, 32>(acc, H3, pkw + pk::K1_W4, lane);
-        acc_relu<2>(H3, acc);
-        d0 = dot_small<32>(H3, pkw + pk::K1_W5 + 0 * 64, h) + w.l5b[0];
-        d1 = dot_small<32>(H3, pkw + pk::K1_W5 + 1 * 64, h) + w.l5b[1];
-        d2 = dot_small<32>(H3, pkw + pk::K1_W5 + 2 * 64, h) + w.l5b[2];
-      }
+      load_tout(T, a.tout, (size_t)kt, h);
+      float d[3];
+      warp_mlp(d, X0, T, pkw, w.l5b, nullptr, s, h, lane);
       // (the point is read again here and at the mask lookup: six registers less across the layers; same loads, same bits)
       const float* pp = a.xyz + (size_t)idx * 3;
       asm volatile("" : "+v"(pp));
-      const float xn0 = norm_c(pp[0], a.box.lo[0], a.box.inv[0]);
-      const float xn1 = norm_c(pp[1], a.box.lo[1], a.box.inv[1]);
-      const float xn2 = norm_c(pp[2], a.box.lo[2], a.box.inv[2]);
-      const float xw0 = norm_c(unnorm_c(xn0, a.box.lo[0], a.box.inv[0]) + d0, a.box.lo[0], a.box.inv[0]);
-      const float xw1 = norm_c(unnorm_c(xn1, a.box.lo[1], a.box.inv[1]) + d1, a.box.lo[1], a.box.inv[1]);
-      const float xw2 = norm_c(unnorm_c(xn2, a.box.lo[2], a.box.inv[2]) + d2, a.box.lo[2], a.box.inv[2]);
-      // ---- density head: 3-stride VM features (72) + X0 + X1 -> 64 -> 1
-      float fd;
-      {
-        float Fv[36];
-        gather_level_den<0>(w.density, point_taps(w.density, xw0, xw1, xw2, 0), h, Fv);
-        gather_level_den<12>(w.density, point_taps(w.density, xw0, xw1, xw2, 1), h, Fv);
-        gather_level_den<24>(w.density, point_taps(w.density, xw0, xw1, xw2, 2), h, Fv);
-        if (!act) {
-#pragma unroll
-          for (int e = 0; e < 36; ++e) Fv[e] = 0.f;
-        }
-        float X1[8];
-        fill_x1(X1, t, h);
-        f32x16 acc[2];
-        acc_bias<2>(acc, pkw + pk::K1_BD1, h);
-#ifdef RDRF_HEADS_F32
-        mfma_seg<2, 36>(acc, Fv, pkw + pk::K1_DEN1_F, lane);
-        mfma_seg<2, 32>(acc, X0, pkw + pk::K1_DEN1_X0, lane);
-        mfma_seg<2, 8>(acc, X1, pkw + pk::K1_DEN1_X1, lane);
-#else
-        head_layer1(acc, Fv, X0, X1, pkw + pk::K1_DEN1, pkw + pk::K1_DEN1_X1T, lane);
-#endif
-        float Hd[32];
-        acc_relu<2>(Hd, acc);
-        fd = dot_small<32>(Hd, pkw + pk::K1_DEN2, h) + w.db2[0];
-      }
+      const float xn[3] = {norm_c(pp[0], a.box.lo[0], a.box.inv[0]), norm_c(pp[1], a.box.lo[1], a.box.inv[1]),
+                           norm_c(pp[2], a.box.lo[2], a.box.inv[2])};
+      float xw[3];
+      warp_point(xw, xn, d, a.box);
+      float X1[8];
+      fill_x1(X1, t, h);
+      const float fd = head_raw<false>(w, xw, act, X0, X1, pkw, nullptr, s, h, lane);
       if (act && h == 0) {
         // the mask is looked up here, where only fd is live: a masked point's column was computed and is dropped (no
         // column of an MFMA reads another's), which costs less than holding the lookup's registers across the layers
@@ -138,7 +96,7 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_alpha_dyn(AlphaArgs a, DynW 
   }
 }
 
-// the static field: a lane per point, the gather of static_density_body; sigma does not depend on the time (the mask does)
+// the static field: a lane per point, static_density_feature as in static_density_body; sigma does not depend on the time (the mask does)
 __global__ __launch_bounds__(256) void k_alpha_static(AlphaArgs a, StaticW w) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.M; i += (long long)gridDim.x * blockDim.x) {
     const size_t idx = (size_t)i;
@@ -146,22 +104,7 @@ __global__ __launch_bounds__(256) void k_alpha_static(AlphaArgs a, StaticW w) {
     const float x0 = norm_c(px, a.box.lo[0], a.box.inv[0]);
     const float x1 = norm_c(py, a.box.lo[1], a.box.inv[1]);
     const float x2 = norm_c(pz, a.box.lo[2], a.box.inv[2]);
-    float f = 0.0f;
-    {
-      const PointTaps pt = point_taps(w.density, x0, x1, x2, 0);
-      const PlaneTaps xy = plane_taps(w.density, 0, pt.x, pt.y, pt.z, 0);
-      float sp = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 v = taps_quad(xy, 4 * q);
-        sp += v.x + v.y + v.z + v.w;
-      }
-      f += sp;
-      const f32x4 v1 = taps_quad(plane_taps(w.density, 1, pt.x, pt.z, pt.y, 0), 0);
-      f += v1.x + v1.y + v1.z + v1.w;
-      const f32x4 v2 = taps_quad(plane_taps(w.density, 2, pt.y, pt.z, pt.x, 0), 0);
-      f += v2.x + v2.y + v2.z + v2.w;
-    }
+    const float f = static_density_feature(w.density, x0, x1, x2);
     const float sig = density_act(f, a.act, a.density_shift);
     for (int kt = 0; kt < a.T; ++kt) {
       bool vld = true;

@@ -10,6 +10,7 @@
 //                  compacted list: 216-feature gather -> basis -> 107->128->128->(131)->3)
 //   scene flow   : k_scene_flow (36->64->64->64->6, models/tensoRF.py:446-462)
 #include "rdrf_fwd_dev.hpp"
+#include "rdrf_render_host.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // per-phase kernels: thin wrappers over the bodies of rdrf_fwd_dev.hpp
@@ -77,27 +78,13 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_scene_flow(const float* __re
     fill_sf_x(X, xn0, xn1, xn2, t, h);
     float* svb = act_rows ? act_rows + (size_t)tile * sv::SF_ROWS * 32 : nullptr;
     save_rows<20>(svb, sv::SF_X, X, s, h);
-    f32x16 acc[2];
-    acc_bias<2>(acc, pkw + pk::SF_B0, h);
-    mfma_seg<2, 20>(acc, X, pkw + pk::SF_W0, lane);
-    float H[32];
-    acc_relu<2>(H, acc);
-    save_rows<32>(svb, sv::SF_H0, H, s, h);
-    acc_bias<2>(acc, pkw + pk::SF_B2, h);
-    mfma_seg<2, 32>(acc, H, pkw + pk::SF_W2, lane);
-    acc_relu<2>(H, acc);
-    save_rows<32>(svb, sv::SF_H2, H, s, h);
-    acc_bias<2>(acc, pkw + pk::SF_B4, h);
-    mfma_seg<2, 32>(acc, H, pkw + pk::SF_W4, lane);
-    acc_relu<2>(H, acc);
-    save_rows<32>(svb, sv::SF_H4, H, s, h);
+    float sf[6];
+    sf_mlp(sf, X, pkw, w.sfb6, svb, s, h, lane);
+    if (act && h == 0) {
 #pragma unroll
-    for (int o = 0; o < 6; ++o) {
-      const float v = dot_small<32>(H, pkw + pk::SF_W6 + o * 64, h) + w.sfb6[o];
-      if (act && h == 0) {
-        if (o < 3) sf_f[(size_t)idx * 3 + o] = v;
-        else sf_b[(size_t)idx * 3 + (o - 3)] = v;
-      }
+      for (int c = 0; c < 3; ++c) sf_f[(size_t)idx * 3 + c] = sf[c];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) sf_b[(size_t)idx * 3 + c] = sf[3 + c];
     }
   }
 }
@@ -241,7 +228,7 @@ static int ws_carve_fwd_ex(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S
 }
 
 int ws_carve_fwd(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S, void* saved,
-                 size_t saved_bytes, int dynamic) {   // (also rdrf_render.hip, rdrf_motion.hip)
+                 size_t saved_bytes, int dynamic) {
   return ws_carve_fwd_ex(a, ws, ws_bytes, N, S, saved, saved_bytes, dynamic, 0);
 }
 

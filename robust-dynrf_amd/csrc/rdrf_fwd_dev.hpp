@@ -2,6 +2,10 @@
 // tensorBase.py:704-850), shared by the per-phase kernels of rdrf_fwd.hip and the single-launch fused render of
 // rdrf_render.hip.  A body sees its position in the launch through GridCtx (workgroup id / count, thread id / count)
 // and gets its LDS weight image as a pointer, so the same code runs as its own kernel or as one phase of a larger one.
+// The evaluation of ONE sample -- load_tout, warp_mlp, warp_point, head_raw, static_density_feature, fill_sf_x + sf_mlp -- and
+// of one round of a ray -- weight_round, append_masked, zero_rgb_round -- are functions of their own: the kernels that
+// need the forward's bits off the training path (rdrf_alpha.hip, rdrf_render_masked.hip, rdrf_motion.hip, rdrf_track.hip)
+// call them too.
 #pragma once
 #include "rdrf_kernels.hpp"
 
@@ -15,6 +19,11 @@ RDRF_D GridCtx grid_ctx() { return GridCtx{(int)blockIdx.x, (int)gridDim.x, (int
 #define GC_NBLK (FUSED ? gc.nblk : (int)gridDim.x)
 #define GC_TID (FUSED ? gc.tid : (int)threadIdx.x)
 #define GC_NTHR (FUSED ? gc.nthr : (int)blockDim.x)
+
+// rank of the calling lane among the set lanes below it in a ballot
+RDRF_D unsigned ballot_rank(unsigned long long bal) {
+  return __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+}
 
 // App-mask compaction (models/tensorBase.py:773-790): the masked samples are appended to one list through one counter -- an
 // atomic with return on ONE address for the whole chip (~3.6 ns each, serialised at the memory side: 65 k appends of a
@@ -40,6 +49,71 @@ RDRF_D int block_append_base(int* counter, int cnt, int* s_cnt, int tid, int nth
   return s_cnt[wave];
 }
 
+// The static field's density feature at a normalised point (models/tensoRF.py:118-154): quads 0..3 plane XY, 4 plane XZ,
+// 5 plane YZ; one set of axis taps for all six (shared-tap gather).  The order of the sums is part of the result's bits.
+RDRF_D float static_density_feature(const RdrfVM& density, float x0, float x1, float x2) {
+  float f = 0.0f;
+  const PointTaps pt = point_taps(density, x0, x1, x2, 0);
+  const PlaneTaps xy = plane_taps(density, 0, pt.x, pt.y, pt.z, 0);
+  float sp = 0.f;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x4 v = taps_quad(xy, 4 * q);
+    sp += v.x + v.y + v.z + v.w;
+  }
+  f += sp;
+  const f32x4 v1 = taps_quad(plane_taps(density, 1, pt.x, pt.z, pt.y, 0), 0);
+  f += v1.x + v1.y + v1.z + v1.w;
+  const f32x4 v2 = taps_quad(plane_taps(density, 2, pt.y, pt.z, pt.x, 0), 0);
+  f += v2.x + v2.y + v2.z + v2.w;
+  return f;
+}
+
+// One transmittance round of a ray (models/tensorBase.py:755-772): W consecutive samples in the lanes l = 0 .. W - 1 of a
+// W-lane group, sample j of the ray at idx.  z -> dists -> alpha -> product scan -> weight; `carry` is the transmittance
+// behind the rounds before this one.  A 32-wide and a 64-wide scan multiply in different orders (other roundings), so a
+// field's every path scans at that field's width.  Returns the weight.
+template <int W>
+RDRF_D float weight_round(const FieldArgs& a, float sigma, bool act, int idx, int j, int l, float nrm, float& carry, float& ds) {
+  const float zj = act ? a.z[idx] : 0.f;
+  const float zn = (j + 1 < a.S) ? a.z[idx + 1] : zj;
+  ds = ((j + 1 < a.S) ? (zn - zj) : 0.0f) * nrm * a.distance_scale;
+  const float alpha = 1.0f - expf(-sigma * ds);
+  const float p = act ? one_minus_alpha_eps(alpha) : 1.0f;
+  const float incl = W == 64 ? scan_mul64(p, l) : scan_mul32(p, l);
+  float excl = __shfl_up(incl, 1, W);
+  if (l == 0) excl = 1.0f;
+  const float T = carry * excl;
+  const float wt = alpha * T;
+  carry *= __shfl(incl, W - 1, W);
+  return wt;
+}
+
+// The second sweep of the app-mask compaction: ray n's entries go to a.list from `base` on, read back from the weights the
+// lane stored in its rounds (same lane, program order).  `on`: the lane takes part (its ray exists; the writing half).
+template <int W>
+RDRF_D void append_masked(const FieldArgs& a, int base, int n, bool on, int l) {
+  for (int j0 = 0; j0 < a.S; j0 += W) {
+    const int j = j0 + l;
+    const bool act = on && j < a.S;
+    const int idx = n * a.S + (act ? j : 0);
+    const bool m = act && a.weight[idx] > a.weight_thres;   // the lane's own store above
+    const unsigned long long bal = __ballot(m);
+    if (m) a.list[base + ballot_rank(bal)] = idx;
+    base += __popcll(bal);
+  }
+}
+
+// The appearance phase writes the masked samples only: zero the colours of the round [j0, j0 + W) of ray n (coalesced)
+template <int W>
+RDRF_D void zero_rgb_round(float* rgb, int n, int S, int j0, int l) {
+  float* r = rgb + ((size_t)n * S + j0) * 3 + l;
+  const int lim = (S - j0 < W ? S - j0 : W) * 3;
+  if (l < lim) r[0] = 0.f;
+  if (l + W < lim) r[W] = 0.f;
+  if (l + 2 * W < lim) r[2 * W] = 0.f;
+}
+
 template <bool FEAT, bool FUSED = false>
 RDRF_D void static_density_body(const FieldArgs a, const StaticW w, const GridCtx gc) {
   __shared__ int s_cnt[16];
@@ -59,13 +133,7 @@ RDRF_D void static_density_body(const FieldArgs a, const StaticW w, const GridCt
     const int idx = n * a.S + (act ? j : 0);
     const bool vld = act && (FEAT || a.valid[idx] != 0);
     if constexpr (!FEAT) {
-      if (ray && a.rgb != nullptr) {   // the appearance phase writes the masked samples only: zero the round's colours (coalesced)
-        float* r = a.rgb + ((size_t)n * a.S + j0) * 3 + lane;
-        const int lim = (a.S - j0 < 64 ? a.S - j0 : 64) * 3;
-        if (lane < lim) r[0] = 0.f;
-        if (lane + 64 < lim) r[64] = 0.f;
-        if (lane + 128 < lim) r[128] = 0.f;
-      }
+      if (ray && a.rgb != nullptr) zero_rgb_round<64>(a.rgb, n, a.S, j0, lane);
     }
     float f = 0.0f;
     if (vld) {
@@ -77,38 +145,15 @@ RDRF_D void static_density_body(const FieldArgs a, const StaticW w, const GridCt
         x1 = norm_c(a.xyz[idx * 3 + 1], a.box.lo[1], a.box.inv[1]);
         x2 = norm_c(a.xyz[idx * 3 + 2], a.box.lo[2], a.box.inv[2]);
       }
-      {  // quads 0..3 plane XY, 4 plane XZ, 5 plane YZ; one set of axis taps for all six (shared-tap gather)
-        const PointTaps pt = point_taps(w.density, x0, x1, x2, 0);
-        const PlaneTaps xy = plane_taps(w.density, 0, pt.x, pt.y, pt.z, 0);
-        float sp = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 v = taps_quad(xy, 4 * q);
-          sp += v.x + v.y + v.z + v.w;
-        }
-        f += sp;
-        const f32x4 v1 = taps_quad(plane_taps(w.density, 1, pt.x, pt.z, pt.y, 0), 0);
-        f += v1.x + v1.y + v1.z + v1.w;
-        const f32x4 v2 = taps_quad(plane_taps(w.density, 2, pt.y, pt.z, pt.x, 0), 0);
-        f += v2.x + v2.y + v2.z + v2.w;
-      }
+      f = static_density_feature(w.density, x0, x1, x2);
     }
     if (a.raw != nullptr && act) a.raw[idx] = f;
     if constexpr (FEAT) {  // compute_densityfeature: the raw feature (models/tensoRF.py:118-154)
       if (act && a.sigma != nullptr) a.sigma[idx] = f;
     } else {
       const float sigma = vld ? density_act(f, a.act, a.density_shift) : 0.0f;
-      const float zj = act ? a.z[idx] : 0.f;
-      const float zn = (j + 1 < a.S) ? a.z[idx + 1] : zj;
-      const float ds = ((j + 1 < a.S) ? (zn - zj) : 0.0f) * nrm * a.distance_scale;
-      const float alpha = 1.0f - expf(-sigma * ds);
-      const float p = act ? one_minus_alpha_eps(alpha) : 1.0f;
-      const float incl = scan_mul64(p, lane);
-      float excl = __shfl_up(incl, 1, 64);
-      if (lane == 0) excl = 1.0f;
-      const float T = carry * excl;
-      const float wt = alpha * T;
-      carry *= __shfl(incl, 63, 64);
+      float ds;
+      const float wt = weight_round<64>(a, sigma, act, idx, j, lane, nrm, carry, ds);
       if (act) {
         a.sigma[idx] = sigma;
         a.weight[idx] = wt;
@@ -118,18 +163,8 @@ RDRF_D void static_density_body(const FieldArgs a, const StaticW w, const GridCt
     }
   }
   if constexpr (!FEAT) {
-    int base = block_append_base(a.counter, cnt, s_cnt, GC_TID, GC_NTHR);
-    if (cnt) {
-      for (int j0 = 0; j0 < a.S; j0 += 64) {
-        const int j = j0 + lane;
-        const bool act = ray && j < a.S;
-        const int idx = n * a.S + (act ? j : 0);
-        const bool m = act && a.weight[idx] > a.weight_thres;   // the lane's own store above
-        const unsigned long long bal = __ballot(m);
-        if (m) a.list[base + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u))] = idx;   // rank among the set lanes below
-        base += __popcll(bal);
-      }
-    }
+    const int base = block_append_base(a.counter, cnt, s_cnt, GC_TID, GC_NTHR);
+    if (cnt) append_masked<64>(a, base, n, ray, lane);
   }
   }  // ray loop
 }
@@ -256,23 +291,88 @@ RDRF_D void static_app_body(const FieldArgs a, const StaticW w, float* lds_fused
   }
 }
 
-#ifndef RDRF_HEADS_F32
-// first layer of the density / blending head (152 -> 64) on the bf16 matrix pipe: [features 36 | X0 32 | X1 0..3] as nine
-// K = 16 steps of mfma_seg_b3, X1[4..7] as an fp32 segment (pk::K1_DEN1)
-RDRF_D void head_layer1(f32x16 (&acc)[2], const float (&Fv)[36], const float (&X0)[32], const float (&X1)[8],
-                        const float* __restrict__ wb3, const float* __restrict__ wtail, int lane) {
-  float U[pk::K1_HEAD_KK];
+// ------------------------------------------------------------------------------------------------
+// One sample of the dynamic field's density phase, in the lane layout of mfma_seg (sample s of a 32-sample tile in the
+// lanes s and s + 32, half h).  pkw: the pk::REG_K1 image in LDS.  svb: the tile's block of saved rows, or nullptr
+// (save_rows on a null base is a no-op: the inference callers pass nullptr and the stores fold away).  An MFMA column
+// depends on its own sample only, so every caller gets the same bits for a sample whatever shares its tile.
+// ------------------------------------------------------------------------------------------------
+// row `row` of the time-branch outputs [.][32] in the slot order of SEG_WARP3_T (`row`: int or size_t, as the caller indexes)
+template <typename I>
+RDRF_D void load_tout(float (&T)[16], const float* tout, I row, int h) {
 #pragma unroll
-  for (int i = 0; i < 36; ++i) U[i] = Fv[i];
-#pragma unroll
-  for (int i = 0; i < 32; ++i) U[36 + i] = X0[i];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) U[68 + i] = X1[i];
-  mfma_seg_b3<2, pk::K1_HEAD_KK>(acc, U, wb3, lane);
-  const float V[4] = {X1[4], X1[5], X1[6], X1[7]};
-  mfma_seg<2, 4>(acc, V, wtail, lane);
+  for (int q = 0; q < 4; ++q) {
+    f32x4 v = ld4(tout + row * 32 + 8 * q + 4 * h);
+    T[q * 4 + 0] = v.x; T[q * 4 + 1] = v.y; T[q * 4 + 2] = v.z; T[q * 4 + 3] = v.w;
+  }
 }
+
+// warp MLP: [xn, PE10(xn), tout] -> 64 -> 64 -> 3  (models/tensoRF.py:521-541).  The callers off the training path
+// (k_alpha_dyn, k_dyn_density_list); dyn_density_body holds the same lines in place, see there.
+RDRF_D void warp_mlp(float (&d)[3], const float (&X0)[32], const float (&T)[16], const float* pkw, const float* l5b,
+                     float* svb, int s, int h, int lane) {
+  f32x16 acc[2];
+  acc_bias<2>(acc, pkw + pk::K1_B3, h);
+  mfma_seg<2, 32>(acc, X0, pkw + pk::K1_W3_X0, lane);
+  mfma_seg<2, 16>(acc, T, pkw + pk::K1_W3_T, lane);
+  float H3[32];
+  acc_relu<2>(H3, acc);
+  save_rows<32>(svb, sv::K1_H3, H3, s, h);
+  acc_bias<2>(acc, pkw + pk::K1_B4, h);
+  mfma_seg<2, 32>(acc, H3, pkw + pk::K1_W4, lane);
+  acc_relu<2>(H3, acc);
+  save_rows<32>(svb, sv::K1_H4, H3, s, h);
+#pragma unroll
+  for (int o = 0; o < 3; ++o) d[o] = dot_small<32>(H3, pkw + pk::K1_W5 + o * 64, h) + l5b[o];
+}
+
+// the warped point in normalised coordinates: the un-normalised round trip of xn (models/tensoRF.py:647-649)
+RDRF_D void warp_point(float (&xw)[3], const float (&xn)[3], const float (&d)[3], const Box& box) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) xw[c] = norm_c(unnorm_c(xn[c], box.lo[c], box.inv[c]) + d[c], box.lo[c], box.inv[c]);
+}
+
+// density (BLEND = false) or blending head at the warped point: 3-stride VM features (72) + X0 + X1 -> 64 -> 1, the raw
+// output.  vld = false zeroes the column's features.
+template <bool BLEND>
+RDRF_D float head_raw(const DynW& w, const float (&xw)[3], bool vld, const float (&X0)[32], const float (&X1)[8],
+                      const float* __restrict__ pkw, float* svb, int s, int h, int lane) {
+  const RdrfVM& set = BLEND ? w.blending : w.density;
+  float Fv[36];
+  gather_level_den<0>(set, point_taps(set, xw[0], xw[1], xw[2], 0), h, Fv);
+  gather_level_den<12>(set, point_taps(set, xw[0], xw[1], xw[2], 1), h, Fv);
+  gather_level_den<24>(set, point_taps(set, xw[0], xw[1], xw[2], 2), h, Fv);
+  if (!vld) {
+#pragma unroll
+    for (int i = 0; i < 36; ++i) Fv[i] = 0.f;
+  }
+  f32x16 acc[2];
+  acc_bias<2>(acc, pkw + (BLEND ? pk::K1_BB1 : pk::K1_BD1), h);
+#ifdef RDRF_HEADS_F32
+  mfma_seg<2, 36>(acc, Fv, pkw + (BLEND ? pk::K1_BLE1_F : pk::K1_DEN1_F), lane);
+  mfma_seg<2, 32>(acc, X0, pkw + (BLEND ? pk::K1_BLE1_X0 : pk::K1_DEN1_X0), lane);
+  mfma_seg<2, 8>(acc, X1, pkw + (BLEND ? pk::K1_BLE1_X1 : pk::K1_DEN1_X1), lane);
+#else
+  {  // the first layer (152 -> 64) on the bf16 matrix pipe: [features 36 | X0 32 | X1 0..3] as nine K = 16 steps of
+     // mfma_seg_b3, X1[4..7] as an fp32 segment (pk::K1_DEN1)
+    float U[pk::K1_HEAD_KK];
+#pragma unroll
+    for (int i = 0; i < 36; ++i) U[i] = Fv[i];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) U[36 + i] = X0[i];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) U[68 + i] = X1[i];
+    mfma_seg_b3<2, pk::K1_HEAD_KK>(acc, U, pkw + (BLEND ? pk::K1_BLE1 : pk::K1_DEN1), lane);
+    const float V[4] = {X1[4], X1[5], X1[6], X1[7]};
+    mfma_seg<2, 4>(acc, V, pkw + (BLEND ? pk::K1_BLE1_X1T : pk::K1_DEN1_X1T), lane);
+  }
 #endif
+  float Hd[32];
+  acc_relu<2>(Hd, acc);
+  save_rows<36>(svb, BLEND ? sv::K1_FB : sv::K1_FD, Fv, s, h);
+  save_rows<32>(svb, BLEND ? sv::K1_HB : sv::K1_HD, Hd, s, h);
+  return dot_small<32>(Hd, pkw + (BLEND ? pk::K1_BLE2 : pk::K1_DEN2), h) + (BLEND ? w.bb2 : w.db2)[0];
+}
 
 // FLAT: the unit of work is a 32-sample tile of the flattened [N * S] sample array instead of a ray, so no tile is padded
 // to the ray's end (S = 115: 3.6 tiles per ray instead of 4; S = 13: 0.41 instead of 1) and a 512-ray eval chunk is 1840
@@ -308,11 +408,7 @@ RDRF_D void dyn_density_body(const FieldArgs a, const DynW w, float* lds_fused, 
     t = a.ts[n];
     float vx, vy, vz;
     nrm = ray_norm(a.rays, n, a.ray_type, vx, vy, vz);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      f32x4 v = ld4(a.tout + n * 32 + 8 * q + 4 * h);
-      T[q * 4 + 0] = v.x; T[q * 4 + 1] = v.y; T[q * 4 + 2] = v.z; T[q * 4 + 3] = v.w;
-    }
+    load_tout(T, a.tout, n, h);
     fill_x1(X1, t, h);
   }
   float carry = 1.0f;
@@ -333,11 +429,7 @@ RDRF_D void dyn_density_body(const FieldArgs a, const DynW w, float* lds_fused, 
     if constexpr (FEAT || FLAT) {  // time is per point (FEAT) / looked up through the sample's ray (FLAT)
       const int ti = FLAT ? idx / a.S : idx;
       t = a.ts[ti];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        f32x4 v = ld4(a.tout + (size_t)ti * 32 + 8 * q + 4 * h);
-        T[q * 4 + 0] = v.x; T[q * 4 + 1] = v.y; T[q * 4 + 2] = v.z; T[q * 4 + 3] = v.w;
-      }
+      load_tout(T, a.tout, (size_t)ti, h);
       fill_x1(X1, t, h);
     }
     // the per-ray time-branch outputs are re-read per tile (L1 hits) instead of living in 16 registers across the tiles: the
@@ -346,25 +438,23 @@ RDRF_D void dyn_density_body(const FieldArgs a, const DynW w, float* lds_fused, 
     if constexpr (!FEAT && !FLAT) {
       int nn = n;
       asm volatile("" : "+v"(nn));
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        f32x4 v = ld4(a.tout + nn * 32 + 8 * q + 4 * h);
-        T[q * 4 + 0] = v.x; T[q * 4 + 1] = v.y; T[q * 4 + 2] = v.z; T[q * 4 + 3] = v.w;
-      }
+      load_tout(T, a.tout, nn, h);
     }
-    const float px = a.xyz[idx * 3 + 0], py = a.xyz[idx * 3 + 1], pz = a.xyz[idx * 3 + 2];
+    const float px[3] = {a.xyz[idx * 3 + 0], a.xyz[idx * 3 + 1], a.xyz[idx * 3 + 2]};
     const bool raw_in = FEAT && a.in_norm;   // compute_*: the caller hands normalised coordinates
-    const float xn0 = raw_in ? px : norm_c(px, a.box.lo[0], a.box.inv[0]);
-    const float xn1 = raw_in ? py : norm_c(py, a.box.lo[1], a.box.inv[1]);
-    const float xn2 = raw_in ? pz : norm_c(pz, a.box.lo[2], a.box.inv[2]);
+    float xn[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) xn[c] = raw_in ? px[c] : norm_c(px[c], a.box.lo[c], a.box.inv[c]);
     float X0[32];
-    fill_x0(X0, xn0, xn1, xn2, t, h);
+    fill_x0(X0, xn[0], xn[1], xn[2], t, h);
     float* svb = (SAVE && a.act1) ? a.act1 + (FLAT ? (size_t)n : (size_t)n * ((a.S + 31) >> 5) + (j0 >> 5)) * sv::K1_ROWS * 32 : nullptr;
     save_rows<32>(svb, sv::K1_X0, X0, s, h);
     save_rows<8>(svb, sv::K1_X1, X1, s, h);
     save_rows<16>(svb, sv::K1_T, T, s, h);
-    // ---- warp MLP: [xn, PE10(xn), tout] -> 64 -> 64 -> 3  (models/tensoRF.py:521-541)
-    float d0, d1, d2;
+    float d[3], xw[3];
+    // warp_mlp, written out: called as a function here, the compiler orders the bf16 MFMAs of the heads below differently and
+    // k_dyn_density<false, false> falls under the WAR distance tests/test_mfma_hazards_cpu.py holds it to (9 < 11).  Keep the
+    // two in step: tests/test_gpu_alpha.py and tests/test_gpu_masked_render.py compare their bits.
     {
       f32x16 acc[2];
       acc_bias<2>(acc, pkw + pk::K1_B3, h);
@@ -377,74 +467,22 @@ RDRF_D void dyn_density_body(const FieldArgs a, const DynW w, float* lds_fused, 
       mfma_seg<2, 32>(acc, H3, pkw + pk::K1_W4, lane);
       acc_relu<2>(H3, acc);
       save_rows<32>(svb, sv::K1_H4, H3, s, h);
-      d0 = dot_small<32>(H3, pkw + pk::K1_W5 + 0 * 64, h) + w.l5b[0];
-      d1 = dot_small<32>(H3, pkw + pk::K1_W5 + 1 * 64, h) + w.l5b[1];
-      d2 = dot_small<32>(H3, pkw + pk::K1_W5 + 2 * 64, h) + w.l5b[2];
+      d[0] = dot_small<32>(H3, pkw + pk::K1_W5 + 0 * 64, h) + w.l5b[0];
+      d[1] = dot_small<32>(H3, pkw + pk::K1_W5 + 1 * 64, h) + w.l5b[1];
+      d[2] = dot_small<32>(H3, pkw + pk::K1_W5 + 2 * 64, h) + w.l5b[2];
     }
-    // compute_* warp the un-normalised round trip of xn (models/tensoRF.py:647-649)
-    const float xw0 = norm_c(unnorm_c(xn0, a.box.lo[0], a.box.inv[0]) + d0, a.box.lo[0], a.box.inv[0]);
-    const float xw1 = norm_c(unnorm_c(xn1, a.box.lo[1], a.box.inv[1]) + d1, a.box.lo[1], a.box.inv[1]);
-    const float xw2 = norm_c(unnorm_c(xn2, a.box.lo[2], a.box.inv[2]) + d2, a.box.lo[2], a.box.inv[2]);
+    warp_point(xw, xn, d, a.box);
     if (act && h == 0) {
       if (!FEAT || a.xyz_prime != nullptr) {
-        a.xyz_prime[(size_t)idx * 3 + 0] = (raw_in ? unnorm_c(xn0, a.box.lo[0], a.box.inv[0]) : px) + d0;
-        a.xyz_prime[(size_t)idx * 3 + 1] = (raw_in ? unnorm_c(xn1, a.box.lo[1], a.box.inv[1]) : py) + d1;
-        a.xyz_prime[(size_t)idx * 3 + 2] = (raw_in ? unnorm_c(xn2, a.box.lo[2], a.box.inv[2]) : pz) + d2;
-      }
-      a.xw[(size_t)idx * 3 + 0] = xw0;
-      a.xw[(size_t)idx * 3 + 1] = xw1;
-      a.xw[(size_t)idx * 3 + 2] = xw2;
-    }
-    // ---- density and blending heads: 3-stride VM features (72) + X0 + X1 -> 64 -> 1
-    float fd, fb;
-    {
-      float Fv[36];
-      gather_level_den<0>(w.density, point_taps(w.density, xw0, xw1, xw2, 0), h, Fv);
-      gather_level_den<12>(w.density, point_taps(w.density, xw0, xw1, xw2, 1), h, Fv);
-      gather_level_den<24>(w.density, point_taps(w.density, xw0, xw1, xw2, 2), h, Fv);
-      if (!vld) {
 #pragma unroll
-        for (int i = 0; i < 36; ++i) Fv[i] = 0.f;
+        for (int c = 0; c < 3; ++c)
+          a.xyz_prime[(size_t)idx * 3 + c] = (raw_in ? unnorm_c(xn[c], a.box.lo[c], a.box.inv[c]) : px[c]) + d[c];
       }
-      f32x16 acc[2];
-      acc_bias<2>(acc, pkw + pk::K1_BD1, h);
-#ifdef RDRF_HEADS_F32
-      mfma_seg<2, 36>(acc, Fv, pkw + pk::K1_DEN1_F, lane);
-      mfma_seg<2, 32>(acc, X0, pkw + pk::K1_DEN1_X0, lane);
-      mfma_seg<2, 8>(acc, X1, pkw + pk::K1_DEN1_X1, lane);
-#else
-      head_layer1(acc, Fv, X0, X1, pkw + pk::K1_DEN1, pkw + pk::K1_DEN1_X1T, lane);
-#endif
-      float Hd[32];
-      acc_relu<2>(Hd, acc);
-      save_rows<36>(svb, sv::K1_FD, Fv, s, h);
-      save_rows<32>(svb, sv::K1_HD, Hd, s, h);
-      fd = dot_small<32>(Hd, pkw + pk::K1_DEN2, h) + w.db2[0];
-    }
-    {
-      float Fv[36];
-      gather_level_den<0>(w.blending, point_taps(w.blending, xw0, xw1, xw2, 0), h, Fv);
-      gather_level_den<12>(w.blending, point_taps(w.blending, xw0, xw1, xw2, 1), h, Fv);
-      gather_level_den<24>(w.blending, point_taps(w.blending, xw0, xw1, xw2, 2), h, Fv);
-      if (!vld) {
 #pragma unroll
-        for (int i = 0; i < 36; ++i) Fv[i] = 0.f;
-      }
-      f32x16 acc[2];
-      acc_bias<2>(acc, pkw + pk::K1_BB1, h);
-#ifdef RDRF_HEADS_F32
-      mfma_seg<2, 36>(acc, Fv, pkw + pk::K1_BLE1_F, lane);
-      mfma_seg<2, 32>(acc, X0, pkw + pk::K1_BLE1_X0, lane);
-      mfma_seg<2, 8>(acc, X1, pkw + pk::K1_BLE1_X1, lane);
-#else
-      head_layer1(acc, Fv, X0, X1, pkw + pk::K1_BLE1, pkw + pk::K1_BLE1_X1T, lane);
-#endif
-      float Hd[32];
-      acc_relu<2>(Hd, acc);
-      save_rows<36>(svb, sv::K1_FB, Fv, s, h);
-      save_rows<32>(svb, sv::K1_HB, Hd, s, h);
-      fb = dot_small<32>(Hd, pkw + pk::K1_BLE2, h) + w.bb2[0];
+      for (int c = 0; c < 3; ++c) a.xw[(size_t)idx * 3 + c] = xw[c];
     }
+    const float fd = head_raw<false>(w, xw, vld, X0, X1, pkw, svb, s, h, lane);
+    const float fb = head_raw<true>(w, xw, vld, X0, X1, pkw, svb, s, h, lane);
     if constexpr (FEAT) {  // compute_densityfeature / compute_blendingfeature: the raw head outputs
       if (act && h == 0) {
         if (a.sigma != nullptr) a.sigma[idx] = fd;
@@ -460,17 +498,8 @@ RDRF_D void dyn_density_body(const FieldArgs a, const DynW w, float* lds_fused, 
     } else {
     const float sigma = vld ? density_act(fd, a.act, a.density_shift) : 0.0f;
     const float blend = vld ? sigmoidf_(fb) : 0.0f;
-    const float zj = act ? a.z[idx] : 0.f;
-    const float zn = (j + 1 < a.S) ? a.z[idx + 1] : zj;
-    const float ds = ((j + 1 < a.S) ? (zn - zj) : 0.0f) * nrm * a.distance_scale;
-    const float alpha = 1.0f - expf(-sigma * ds);
-    const float p = act ? one_minus_alpha_eps(alpha) : 1.0f;
-    const float incl = scan_mul32(p, s);
-    float excl = __shfl_up(incl, 1, 32);
-    if (s == 0) excl = 1.0f;
-    const float Tr = carry * excl;
-    const float wt = alpha * Tr;
-    carry *= __shfl(incl, 31, 32);
+    float ds;
+    const float wt = weight_round<32>(a, sigma, act, idx, j, s, nrm, carry, ds);
     const bool m = act && h == 0 && wt > a.weight_thres;
     if (act && h == 0) {
       a.sigma[idx] = sigma;
@@ -485,20 +514,12 @@ RDRF_D void dyn_density_body(const FieldArgs a, const DynW w, float* lds_fused, 
   if constexpr (!FEAT && !FLAT) {
     // app-mask compaction (models/tensorBase.py:773-790), ONE append per ray: every append is an atomic with return on the
     // same address for the whole chip (~3.6 ns each, serialised at the memory side), so the ray's tiles count first and
-    // the entries are written in a second sweep over the weights just stored (same lane, program order)
+    // the entries are written in a second sweep over the weights just stored (append_masked)
     if (nmask) {
       int base = 0;
       if (lane == 0) base = atomicAdd(a.counter, nmask);
       base = __shfl(base, 0, 64);
-      for (int j0 = 0; j0 < a.S; j0 += 32) {
-        const int j = j0 + s;
-        const bool act = j < a.S && h == 0;
-        const int idx = n * a.S + (act ? j : 0);
-        const bool m = act && a.weight[idx] > a.weight_thres;
-        const unsigned long long bal = __ballot(m);
-        if (m) a.list[base + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u))] = idx;   // rank among the set lanes below
-        base += __popcll(bal);
-      }
+      append_masked<32>(a, base, n, h == 0, s);
     }
   }
   }  // ray loop
@@ -506,8 +527,8 @@ RDRF_D void dyn_density_body(const FieldArgs a, const DynW w, float* lds_fused, 
 
 // The per-ray half of the density phase for the flat-tile form: sigma -> alpha -> transmittance scan -> weight, dists, the
 // app-mask compaction (models/tensorBase.py:773-790) and the zero fill of the colours the appearance phase will not write.
-// A half-wave per ray (two rays per wave), 32 samples per round with the carry across rounds -- the expressions and the
-// order of the multiplications are those of dyn_density_body, so weight / dists / the mask come out bit-identical.
+// A half-wave per ray (two rays per wave), 32 samples per round with the carry across rounds -- weight_round<32>, the round
+// of the wave-per-ray dyn_density_body, so weight / dists / the mask come out bit-identical.
 // The compaction appends ONCE per workgroup (block_append_base).
 RDRF_D void ray_scan_body(const FieldArgs a) {
   __shared__ int s_cnt[16];
@@ -524,42 +545,17 @@ RDRF_D void ray_scan_body(const FieldArgs a) {
     const bool act = ray && j < a.S;
     const int idx = n * a.S + (act ? j : 0);
     const float sigma = act ? a.sigma[idx] : 0.0f;
-    const float zj = act ? a.z[idx] : 0.f;
-    const float zn = (j + 1 < a.S) ? a.z[idx + 1] : zj;
-    const float ds = ((j + 1 < a.S) ? (zn - zj) : 0.0f) * nrm * a.distance_scale;
-    const float alpha = 1.0f - expf(-sigma * ds);
-    const float p = act ? one_minus_alpha_eps(alpha) : 1.0f;
-    const float incl = scan_mul32(p, s);
-    float excl = __shfl_up(incl, 1, 32);
-    if (s == 0) excl = 1.0f;
-    const float Tr = carry * excl;
-    const float wt = alpha * Tr;
-    carry *= __shfl(incl, 31, 32);
+    float ds;
+    const float wt = weight_round<32>(a, sigma, act, idx, j, s, nrm, carry, ds);
     if (act) {
       a.weight[idx] = wt;
       a.dists[idx] = ds;
     }
-    if (ray && a.rgb != nullptr) {   // zero the round's colours (coalesced; the appearance phase writes the masked samples)
-      float* r = a.rgb + ((size_t)n * a.S + j0) * 3 + s;
-      const int lim = (a.S - j0 < 32 ? a.S - j0 : 32) * 3;
-      if (s < lim) r[0] = 0.f;
-      if (s + 32 < lim) r[32] = 0.f;
-      if (s + 64 < lim) r[64] = 0.f;
-    }
+    if (ray && a.rgb != nullptr) zero_rgb_round<32>(a.rgb, n, a.S, j0, s);
     cnt += __popcll(__ballot(act && wt > a.weight_thres));
   }
-  int base = block_append_base(a.counter, cnt, s_cnt, threadIdx.x, blockDim.x);
-  if (cnt) {
-    for (int j0 = 0; j0 < a.S; j0 += 32) {
-      const int j = j0 + s;
-      const bool act = ray && j < a.S;
-      const int idx = n * a.S + (act ? j : 0);
-      const bool m = act && a.weight[idx] > a.weight_thres;   // the lane's own store above
-      const unsigned long long bal = __ballot(m);
-      if (m) a.list[base + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u))] = idx;   // rank among the set lanes below
-      base += __popcll(bal);
-    }
-  }
+  const int base = block_append_base(a.counter, cnt, s_cnt, threadIdx.x, blockDim.x);
+  if (cnt) append_masked<32>(a, base, n, ray, s);
 }
 
 template <bool FEAT, bool SAVE = true, bool FUSED = false>
@@ -722,8 +718,9 @@ RDRF_D void time_branch_body(const float* __restrict__ ts, const DynW w, int N, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// scene-flow MLP input [xn3, PE4(xn), t, PE4(t)] in the slot order of SEG_SF_X (models/tensoRF.py:446-462): shared by
-// k_scene_flow (rdrf_fwd.hip) and the evaluation render's k_motion_maps (rdrf_motion.hip)
+// scene-flow MLP (models/tensoRF.py:446-462) of one sample in the lane layout of mfma_seg: shared by k_scene_flow
+// (rdrf_fwd.hip), the evaluation render's k_motion_maps (rdrf_motion.hip) and k_track_points (rdrf_track.hip).
+// fill_sf_x: the input [xn3, PE4(xn), t, PE4(t)] in the slot order of SEG_SF_X
 // ------------------------------------------------------------------------------------------------
 RDRF_D void fill_sf_x(float (&X)[20], float xn0, float xn1, float xn2, float t, int h) {
 #pragma unroll
@@ -751,4 +748,26 @@ RDRF_D void fill_sf_x(float (&X)[20], float xn0, float xn1, float xn2, float t, 
       }
     }
   }
+}
+
+// 36 -> 64 -> 64 -> 64 -> 6 on X = fill_sf_x(...): sf[0..2] forward, sf[3..5] backward flow, in both half-waves.  pkw: the
+// pk::REG_SF image in LDS; b6: the last layer's bias; svb: the tile's saved rows or nullptr (save_rows is then a no-op)
+RDRF_D void sf_mlp(float (&sf)[6], const float (&X)[20], const float* pkw, const float* b6, float* svb, int s, int h,
+                   int lane) {
+  f32x16 acc[2];
+  acc_bias<2>(acc, pkw + pk::SF_B0, h);
+  mfma_seg<2, 20>(acc, X, pkw + pk::SF_W0, lane);
+  float H[32];
+  acc_relu<2>(H, acc);
+  save_rows<32>(svb, sv::SF_H0, H, s, h);
+  acc_bias<2>(acc, pkw + pk::SF_B2, h);
+  mfma_seg<2, 32>(acc, H, pkw + pk::SF_W2, lane);
+  acc_relu<2>(H, acc);
+  save_rows<32>(svb, sv::SF_H2, H, s, h);
+  acc_bias<2>(acc, pkw + pk::SF_B4, h);
+  mfma_seg<2, 32>(acc, H, pkw + pk::SF_W4, lane);
+  acc_relu<2>(H, acc);
+  save_rows<32>(svb, sv::SF_H4, H, s, h);
+#pragma unroll
+  for (int o = 0; o < 6; ++o) sf[o] = dot_small<32>(H, pkw + pk::SF_W6 + o * 64, h) + b6[o];
 }

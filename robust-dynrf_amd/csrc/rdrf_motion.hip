@@ -6,15 +6,12 @@
 #include "rdrf_misc_dev.hpp"
 #include "rdrf_render_host.hpp"
 
-// host helper of rdrf_fwd.hip
-int ws_carve_fwd(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S, void* saved, size_t saved_bytes, int dynamic);
-
 // ------------------------------------------------------------------------------------------------
 // k_motion_maps: one wave per ray, 32-sample tiles (sample s of the tile in lanes s and s + 32: the layout of mfma_seg).
 //
-// Per sample the 36 -> 64 -> 64 -> 64 -> 6 scene-flow MLP runs exactly as in k_scene_flow (same packed image, same
-// mfma_seg / dot_small sequence: an MFMA column depends on its own sample only, so the per-sample values have
-// k_scene_flow's bits), and nothing per sample is written: lane s keeps the running sums of the samples s, s + 32,
+// Per sample the 36 -> 64 -> 64 -> 64 -> 6 scene-flow MLP is k_scene_flow's: fill_sf_x and sf_mlp (rdrf_fwd_dev.hpp) on the
+// same packed image -- an MFMA column depends on its own sample only, so the per-sample values have k_scene_flow's
+// bits -- and nothing per sample is written: lane s keeps the running sums of the samples s, s + 32,
 // s + 64, ... of its ray, in that order; after the last tile the 32 lane sums are added by a fixed xor tree (16, 8, 4, 2,
 // 1).  The order depends on S alone -- not on N, on where a chunk starts, on which maps are requested or on timing --
 // and no atomic is involved: the maps are bit-identical run after run, chunked or not, in either library build.
@@ -69,19 +66,7 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_motion_maps(MotionArgs a, co
           float X[20];
           fill_sf_x(X, norm_c(p[0], a.box.lo[0], a.box.inv[0]), norm_c(p[1], a.box.lo[1], a.box.inv[1]),
                     norm_c(p[2], a.box.lo[2], a.box.inv[2]), t, h);
-          f32x16 acc[2];
-          acc_bias<2>(acc, pkw + pk::SF_B0, h);
-          mfma_seg<2, 20>(acc, X, pkw + pk::SF_W0, lane);
-          float Hh[32];
-          acc_relu<2>(Hh, acc);
-          acc_bias<2>(acc, pkw + pk::SF_B2, h);
-          mfma_seg<2, 32>(acc, Hh, pkw + pk::SF_W2, lane);
-          acc_relu<2>(Hh, acc);
-          acc_bias<2>(acc, pkw + pk::SF_B4, h);
-          mfma_seg<2, 32>(acc, Hh, pkw + pk::SF_W4, lane);
-          acc_relu<2>(Hh, acc);
-#pragma unroll
-          for (int o = 0; o < 6; ++o) sf[o] = dot_small<32>(Hh, pkw + pk::SF_W6 + o * 64, h) + sfb6[o];
+          sf_mlp(sf, X, pkw, sfb6, nullptr, s, h, lane);
         }
       }
       if (!act) { p[0] = 0.f; p[1] = 0.f; p[2] = 0.f; q[0] = 0.f; q[1] = 0.f; q[2] = 0.f; }

@@ -4,11 +4,6 @@
 #include "rdrf_misc_dev.hpp"
 #include "rdrf_render_host.hpp"
 
-// host helpers of rdrf_fwd.hip
-void fill_common(FieldArgs& a, const RdrfFieldCfg* cfg, const float* rays, const float* ts, const float* xyz, const float* z,
-                 const uint8_t* valid, int N, int S);
-int ws_carve_fwd(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S, void* saved, size_t saved_bytes, int dynamic);
-
 // ------------------------------------------------------------------------------------------------
 // FUSED render: sample -> static + dynamic density phases -> static + dynamic appearance phases -> compositor in ONE
 // cooperative launch (/root/reference/renderer.py:740-812 loop body).  The persistent workgroups (one per CU, 8

@@ -8,12 +8,15 @@
 //   k_keep               : one pass over the [N * S] samples: both masks at (xyz, ts[ray]), the two valid planes, the flat
 //                          index of every kept sample appended to list_s / list_d (one append per workgroup and list), and
 //                          zeros where the later phases read a dropped sample (sigma of both fields, blending)
-//   k_static_density_list: a lane per listed sample, the gather of static_density_body -> sigma
-//   k_static_scan        : the per-ray half of static_density_body (wave per ray, 64-lane transmittance scan) over all
-//                          N * S sigmas: weight, dists, app-mask compaction, zero fill of the colours
-//   k_dyn_density_list   : 32-entry tiles of list_d through the device functions of dyn_density_body in its order (FLAT
-//                          form: time and tout through the sample's ray).  An MFMA column depends on its own sample only,
-//                          so a listed sample gets the bits k_dyn_density_flat gives it
+//   k_static_density_list: a lane per listed sample, static_density_feature -> sigma
+//   k_static_scan        : the per-ray half of static_density_body (wave per ray; zero_rgb_round<64>, weight_round<64>,
+//                          append_masked<64>) over all N * S sigmas: weight, dists, app-mask compaction, zero fill of the
+//                          colours
+//   k_dyn_density_list   : 32-entry tiles of list_d through the per-sample functions dyn_density_body calls (load_tout,
+//                          warp_mlp, warp_point, head_raw; FLAT form: time and tout through the sample's ray).  An MFMA
+//                          column depends on its own sample only, so a listed sample gets the bits k_dyn_density_flat
+//                          gives it
+// (the shared functions: rdrf_fwd_dev.hpp)
 //   k_masked_ray_scan    : ray_scan_body, unchanged
 //   appearance kernels, compositor: the bodies / the entry point of the unmasked render
 //
@@ -23,12 +26,6 @@
 #include "rdrf_fwd_dev.hpp"
 #include "rdrf_mask_dev.hpp"
 #include "rdrf_render_host.hpp"
-
-// host helpers of rdrf_fwd.hip
-void fill_common(FieldArgs& a, const RdrfFieldCfg* cfg, const float* rays, const float* ts, const float* xyz, const float* z,
-                 const uint8_t* valid, int N, int S);
-int ws_carve_fwd(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S, void* saved, size_t saved_bytes, int dynamic);
-int fwd_dynq();
 
 // the four device counters of a call, one 256-byte block cleared by the time-branch launch: a counter per 64-byte line
 constexpr int CTR_KEPT_S = 0, CTR_KEPT_D = 16, CTR_APP_S = 32, CTR_APP_D = 48;
@@ -87,14 +84,14 @@ __global__ __launch_bounds__(256) void k_keep(KeepArgs a) {
     const int i = i0 + r * 256;
     const bool m_s = ((ks >> r) & 1u) != 0, m_d = ((kd >> r) & 1u) != 0;
     const unsigned long long bs = __ballot(m_s), bd = __ballot(m_d);
-    if (m_s) a.list_s[base_s + __builtin_amdgcn_mbcnt_hi((unsigned)(bs >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bs, 0u))] = i;
-    if (m_d) a.list_d[base_d + __builtin_amdgcn_mbcnt_hi((unsigned)(bd >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bd, 0u))] = i;
+    if (m_s) a.list_s[base_s + ballot_rank(bs)] = i;
+    if (m_d) a.list_d[base_d + ballot_rank(bd)] = i;
     base_s += __popcll(bs);
     base_d += __popcll(bd);
   }
 }
 
-// the static field's sigma of the listed samples: a lane per entry, the gather of static_density_body.  Also hands the two
+// the static field's sigma of the listed samples: a lane per entry, static_density_feature as in static_density_body.  Also hands the two
 // list lengths to the caller (`kept`, nullable)
 __global__ __launch_bounds__(256) void k_static_density_list(FieldArgs a, StaticW w, const int* __restrict__ klist,
                                                              const int* __restrict__ ctr, long long* __restrict__ kept) {
@@ -102,35 +99,15 @@ __global__ __launch_bounds__(256) void k_static_density_list(FieldArgs a, Static
   const int count = ctr[CTR_KEPT_S];
   for (int li = blockIdx.x * blockDim.x + threadIdx.x; li < count; li += gridDim.x * blockDim.x) {
     const int idx = klist[li];
-    float f = 0.0f;
-    {
-      float x0, x1, x2;
-      x0 = norm_c(a.xyz[idx * 3 + 0], a.box.lo[0], a.box.inv[0]);
-      x1 = norm_c(a.xyz[idx * 3 + 1], a.box.lo[1], a.box.inv[1]);
-      x2 = norm_c(a.xyz[idx * 3 + 2], a.box.lo[2], a.box.inv[2]);
-      {
-        const PointTaps pt = point_taps(w.density, x0, x1, x2, 0);
-        const PlaneTaps xy = plane_taps(w.density, 0, pt.x, pt.y, pt.z, 0);
-        float sp = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 v = taps_quad(xy, 4 * q);
-          sp += v.x + v.y + v.z + v.w;
-        }
-        f += sp;
-        const f32x4 v1 = taps_quad(plane_taps(w.density, 1, pt.x, pt.z, pt.y, 0), 0);
-        f += v1.x + v1.y + v1.z + v1.w;
-        const f32x4 v2 = taps_quad(plane_taps(w.density, 2, pt.y, pt.z, pt.x, 0), 0);
-        f += v2.x + v2.y + v2.z + v2.w;
-      }
-    }
+    const float f = static_density_feature(w.density, norm_c(a.xyz[idx * 3 + 0], a.box.lo[0], a.box.inv[0]),
+                                           norm_c(a.xyz[idx * 3 + 1], a.box.lo[1], a.box.inv[1]),
+                                           norm_c(a.xyz[idx * 3 + 2], a.box.lo[2], a.box.inv[2]));
     a.sigma[idx] = density_act(f, a.act, a.density_shift);
   }
 }
 
-// the per-ray half of static_density_body over stored sigmas: a wave per ray, 64 samples per round -- its expressions and
-// the order of its multiplications (ray_scan_body scans 32 wide: other roundings), so weight, dists and the app mask come
-// out as the dense kernel's
+// the per-ray half of static_density_body over stored sigmas: a wave per ray, 64 samples per round -- its weight_round<64>
+// (ray_scan_body scans 32 wide: other roundings), so weight, dists and the app mask come out as the dense kernel's
 __global__ __launch_bounds__(256) void k_static_scan(FieldArgs a) {
   __shared__ int s_cnt[16];
   const int lane = threadIdx.x & 63;
@@ -146,48 +123,23 @@ __global__ __launch_bounds__(256) void k_static_scan(FieldArgs a) {
       const int j = j0 + lane;
       const bool act = ray && j < a.S;
       const int idx = n * a.S + (act ? j : 0);
-      if (ray) {   // zero the round's colours (coalesced; the appearance phase writes the masked samples)
-        float* r = a.rgb + ((size_t)n * a.S + j0) * 3 + lane;
-        const int lim = (a.S - j0 < 64 ? a.S - j0 : 64) * 3;
-        if (lane < lim) r[0] = 0.f;
-        if (lane + 64 < lim) r[64] = 0.f;
-        if (lane + 128 < lim) r[128] = 0.f;
-      }
+      if (ray) zero_rgb_round<64>(a.rgb, n, a.S, j0, lane);
       const float sigma = act ? a.sigma[idx] : 0.0f;
-      const float zj = act ? a.z[idx] : 0.f;
-      const float zn = (j + 1 < a.S) ? a.z[idx + 1] : zj;
-      const float ds = ((j + 1 < a.S) ? (zn - zj) : 0.0f) * nrm * a.distance_scale;
-      const float alpha = 1.0f - expf(-sigma * ds);
-      const float p = act ? one_minus_alpha_eps(alpha) : 1.0f;
-      const float incl = scan_mul64(p, lane);
-      float excl = __shfl_up(incl, 1, 64);
-      if (lane == 0) excl = 1.0f;
-      const float T = carry * excl;
-      const float wt = alpha * T;
-      carry *= __shfl(incl, 63, 64);
+      float ds;
+      const float wt = weight_round<64>(a, sigma, act, idx, j, lane, nrm, carry, ds);
       if (act) {
         a.weight[idx] = wt;
         a.dists[idx] = ds;
       }
       cnt += __popcll(__ballot(act && wt > a.weight_thres));
     }
-    int base = block_append_base(a.counter, cnt, s_cnt, threadIdx.x, blockDim.x);
-    if (cnt) {
-      for (int j0 = 0; j0 < a.S; j0 += 64) {
-        const int j = j0 + lane;
-        const bool act = ray && j < a.S;
-        const int idx = n * a.S + (act ? j : 0);
-        const bool m = act && a.weight[idx] > a.weight_thres;   // the lane's own store above
-        const unsigned long long bal = __ballot(m);
-        if (m) a.list[base + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u))] = idx;   // rank among the set lanes below
-        base += __popcll(bal);
-      }
-    }
+    const int base = block_append_base(a.counter, cnt, s_cnt, threadIdx.x, blockDim.x);
+    if (cnt) append_masked<64>(a, base, n, ray, lane);
   }
 }
 
 // 32-entry tiles of the kept list from the workgroup's queue: per tile the inference path of dyn_density_body<., ., ., FLAT>
-// (same device functions, same order), every entry a valid sample
+// (the same per-sample functions in the same order, no saved rows), every entry a valid sample
 __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_density_list(FieldArgs a, DynW w, const int* __restrict__ klist,
                                                                     const int* __restrict__ kcount) {
   __shared__ __attribute__((aligned(16))) float lds[pk::K1_SIZE];
@@ -205,98 +157,29 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_density_list(FieldArgs a
     const int li = tile * 32 + s;
     const bool act = li < count;
     const int idx = act ? klist[li] : 0;
-    float t;
+    const int ti = idx / a.S;
+    const float t = a.ts[ti];
     float T[16];
     float X1[8];
-    {
-      const int ti = idx / a.S;
-      t = a.ts[ti];
+    load_tout(T, a.tout, (size_t)ti, h);
+    fill_x1(X1, t, h);
+    const float px[3] = {a.xyz[idx * 3 + 0], a.xyz[idx * 3 + 1], a.xyz[idx * 3 + 2]};
+    float xn[3];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        f32x4 v = ld4(a.tout + (size_t)ti * 32 + 8 * q + 4 * h);
-        T[q * 4 + 0] = v.x; T[q * 4 + 1] = v.y; T[q * 4 + 2] = v.z; T[q * 4 + 3] = v.w;
-      }
-      fill_x1(X1, t, h);
-    }
-    const float px = a.xyz[idx * 3 + 0], py = a.xyz[idx * 3 + 1], pz = a.xyz[idx * 3 + 2];
-    const float xn0 = norm_c(px, a.box.lo[0], a.box.inv[0]);
-    const float xn1 = norm_c(py, a.box.lo[1], a.box.inv[1]);
-    const float xn2 = norm_c(pz, a.box.lo[2], a.box.inv[2]);
+    for (int c = 0; c < 3; ++c) xn[c] = norm_c(px[c], a.box.lo[c], a.box.inv[c]);
     float X0[32];
-    fill_x0(X0, xn0, xn1, xn2, t, h);
-    // ---- warp MLP: [xn, PE10(xn), tout] -> 64 -> 64 -> 3  (models/tensoRF.py:521-541)
-    float d0, d1, d2;
-    {
-      f32x16 acc[2];
-      acc_bias<2>(acc, pkw + pk::K1_B3, h);
-      mfma_seg<2, 32>(acc, X0, pkw + pk::K1_W3_X0, lane);
-      mfma_seg<2, 16>(acc, T, pkw + pk::K1_W3_T, lane);
-      float H3[32];
-      acc_relu<2>(H3, acc);
-      acc_bias<2>(acc, pkw + pk::K1_B4, h);
-      mfma_seg<2, 32>(acc, H3, pkw + pk::K1_W4, lane);
-      acc_relu<2>(H3, acc);
-      d0 = dot_small<32>(H3, pkw + pk::K1_W5 + 0 * 64, h) + w.l5b[0];
-      d1 = dot_small<32>(H3, pkw + pk::K1_W5 + 1 * 64, h) + w.l5b[1];
-      d2 = dot_small<32>(H3, pkw + pk::K1_W5 + 2 * 64, h) + w.l5b[2];
-    }
-    const float xw0 = norm_c(unnorm_c(xn0, a.box.lo[0], a.box.inv[0]) + d0, a.box.lo[0], a.box.inv[0]);
-    const float xw1 = norm_c(unnorm_c(xn1, a.box.lo[1], a.box.inv[1]) + d1, a.box.lo[1], a.box.inv[1]);
-    const float xw2 = norm_c(unnorm_c(xn2, a.box.lo[2], a.box.inv[2]) + d2, a.box.lo[2], a.box.inv[2]);
+    fill_x0(X0, xn[0], xn[1], xn[2], t, h);
+    float d[3], xw[3];
+    warp_mlp(d, X0, T, pkw, w.l5b, nullptr, s, h, lane);
+    warp_point(xw, xn, d, a.box);
     if (act && h == 0) {
-      a.xyz_prime[(size_t)idx * 3 + 0] = px + d0;
-      a.xyz_prime[(size_t)idx * 3 + 1] = py + d1;
-      a.xyz_prime[(size_t)idx * 3 + 2] = pz + d2;
-      a.xw[(size_t)idx * 3 + 0] = xw0;
-      a.xw[(size_t)idx * 3 + 1] = xw1;
-      a.xw[(size_t)idx * 3 + 2] = xw2;
-    }
-    // ---- density and blending heads: 3-stride VM features (72) + X0 + X1 -> 64 -> 1
-    float fd, fb;
-    {
-      float Fv[36];
-      gather_level_den<0>(w.density, point_taps(w.density, xw0, xw1, xw2, 0), h, Fv);
-      gather_level_den<12>(w.density, point_taps(w.density, xw0, xw1, xw2, 1), h, Fv);
-      gather_level_den<24>(w.density, point_taps(w.density, xw0, xw1, xw2, 2), h, Fv);
-      if (!act) {
 #pragma unroll
-        for (int i = 0; i < 36; ++i) Fv[i] = 0.f;
-      }
-      f32x16 acc[2];
-      acc_bias<2>(acc, pkw + pk::K1_BD1, h);
-#ifdef RDRF_HEADS_F32
-      mfma_seg<2, 36>(acc, Fv, pkw + pk::K1_DEN1_F, lane);
-      mfma_seg<2, 32>(acc, X0, pkw + pk::K1_DEN1_X0, lane);
-      mfma_seg<2, 8>(acc, X1, pkw + pk::K1_DEN1_X1, lane);
-#else
-      head_layer1(acc, Fv, X0, X1, pkw + pk::K1_DEN1, pkw + pk::K1_DEN1_X1T, lane);
-#endif
-      float Hd[32];
-      acc_relu<2>(Hd, acc);
-      fd = dot_small<32>(Hd, pkw + pk::K1_DEN2, h) + w.db2[0];
-    }
-    {
-      float Fv[36];
-      gather_level_den<0>(w.blending, point_taps(w.blending, xw0, xw1, xw2, 0), h, Fv);
-      gather_level_den<12>(w.blending, point_taps(w.blending, xw0, xw1, xw2, 1), h, Fv);
-      gather_level_den<24>(w.blending, point_taps(w.blending, xw0, xw1, xw2, 2), h, Fv);
-      if (!act) {
+      for (int c = 0; c < 3; ++c) a.xyz_prime[(size_t)idx * 3 + c] = px[c] + d[c];
 #pragma unroll
-        for (int i = 0; i < 36; ++i) Fv[i] = 0.f;
-      }
-      f32x16 acc[2];
-      acc_bias<2>(acc, pkw + pk::K1_BB1, h);
-#ifdef RDRF_HEADS_F32
-      mfma_seg<2, 36>(acc, Fv, pkw + pk::K1_BLE1_F, lane);
-      mfma_seg<2, 32>(acc, X0, pkw + pk::K1_BLE1_X0, lane);
-      mfma_seg<2, 8>(acc, X1, pkw + pk::K1_BLE1_X1, lane);
-#else
-      head_layer1(acc, Fv, X0, X1, pkw + pk::K1_BLE1, pkw + pk::K1_BLE1_X1T, lane);
-#endif
-      float Hd[32];
-      acc_relu<2>(Hd, acc);
-      fb = dot_small<32>(Hd, pkw + pk::K1_BLE2, h) + w.bb2[0];
+      for (int c = 0; c < 3; ++c) a.xw[(size_t)idx * 3 + c] = xw[c];
     }
+    const float fd = head_raw<false>(w, xw, act, X0, X1, pkw, nullptr, s, h, lane);
+    const float fb = head_raw<true>(w, xw, act, X0, X1, pkw, nullptr, s, h, lane);
     if (act && h == 0) {
       a.sigma[idx] = density_act(fd, a.act, a.density_shift);
       a.blending[idx] = sigmoidf_(fb);

@@ -13,8 +13,8 @@
 // k_track_points: persistent workgroups with the scene-flow image (pk::REG_SF, 45 KB) in LDS; a wave owns a 32-point tile
 // (point s of the tile in lanes s and s + 32: the layout of mfma_seg) and runs the whole chain of its tile with the points
 // in registers -- the forward steps, then, from the reloaded seed, the backward steps.  Per step the 36 -> 64 -> 64 -> 64 -> 6
-// MLP runs exactly as in k_scene_flow (same image, same mfma_seg / dot_small sequence; an MFMA column depends on its own
-// point only, so a point gets k_scene_flow's bits whatever shares its tile), dot_small leaves the six outputs in both
+// MLP is k_scene_flow's: fill_sf_x and sf_mlp (rdrf_fwd_dev.hpp) on the same image; an MFMA column depends on its own
+// point only, so a point gets k_scene_flow's bits whatever shares its tile.  sf_mlp leaves the six outputs in both
 // half-waves, both add them to their copy of the point, and the lower half writes the slot.  Nothing in the step loop
 // writes LDS.  A lane past M holds the point 0 at time 0 (finite MFMA operands) and writes nothing.
 // ------------------------------------------------------------------------------------------------
@@ -87,19 +87,7 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_track_points(TrackArgs a, co
           float X[20];
           fill_sf_x(X, norm_c(p[0], a.box.lo[0], a.box.inv[0]), norm_c(p[1], a.box.lo[1], a.box.inv[1]),
                     norm_c(p[2], a.box.lo[2], a.box.inv[2]), t, h);
-          f32x16 acc[2];
-          acc_bias<2>(acc, pkw + pk::SF_B0, h);
-          mfma_seg<2, 20>(acc, X, pkw + pk::SF_W0, lane);
-          float Hh[32];
-          acc_relu<2>(Hh, acc);
-          acc_bias<2>(acc, pkw + pk::SF_B2, h);
-          mfma_seg<2, 32>(acc, Hh, pkw + pk::SF_W2, lane);
-          acc_relu<2>(Hh, acc);
-          acc_bias<2>(acc, pkw + pk::SF_B4, h);
-          mfma_seg<2, 32>(acc, Hh, pkw + pk::SF_W4, lane);
-          acc_relu<2>(Hh, acc);
-#pragma unroll
-          for (int o = 0; o < 6; ++o) sf[o] = dot_small<32>(Hh, pkw + pk::SF_W6 + o * 64, h) + sfb6[o];
+          sf_mlp(sf, X, pkw, sfb6, nullptr, s, h, lane);
         }
         track_step(p, t, sf, dir, a.dt, a.ray_type);
         if (!act) { p[0] = 0.f; p[1] = 0.f; p[2] = 0.f; t = 0.f; }
