@@ -15,72 +15,23 @@
 //   4. k_dw3 (rdrf_dw.hip) forms dW = sum_samples dz (x) in on the MFMA from the dz rows and the saved rows.
 // The entry points call 3, 4 and the fused kernels through the host interface of rdrf_bwd_host.hpp.  The ray-generation backward is in
 // rdrf_misc.hip beside its forward, the deterministic build's bind / finish in rdrf_det.hip.
+// The kernels here are the launch geometry, the tile queues, the loops, the LDS and the sums; the per-sample and per-tile steps --
+// the ray scan backward at both widths, the heads' and the warp MLP's tile, the shared steps of the two appearance kernels, the
+// positional-encoding backwards -- are the device functions of rdrf_bwd_mlp_dev.hpp, one copy each, which the fused kernels of
+// rdrf_bwd_fused.hip call too.  Three steps are written out in place because hipcc punishes the function (comments at the sites): the
+// appearance output layer (spills), the load of the heads' K1G_DX0 rows in front of the warp's layer 3 (MFMA hazard distance) and
+// the 64-wide ray scan of k_static_density_bwd (time).
 // References: autograd of /root/reference/models/tensorBase.py:704-850, models/tensoRF.py:118-196,
 // 446-462, 521-811 (grid_sample backward per SURVEY.md Appendix A).
-#include "rdrf_bwd_dev.hpp"
+#include "rdrf_bwd_mlp_dev.hpp"
 #include "rdrf_bwd_host.hpp"
 
 RDRF_DET_UNIT(bwd)
 
-// d(X0)/d(xn): X0 = [xn, t | (sin q, cos q) pairs], q_j = xn[j/10] * 2^(j%10); returns this lane
-// half's partial (combine with __shfl_xor 32)
-// (no contraction in here: left to hipcc, which products of `a cv - b sv` fuse depends on the kernel around the call, and
-// the fused warp kernel of rdrf_bwd_fused.hip, through its x0_bwd_flat, has to give the bits of k_dyn_density_bwd<1>)
-RDRF_D void x0_bwd(const float (&X0)[32], const float (&dX0)[32], int h, float& d0, float& d1,
-                   float& d2) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int o = 0; o < 8; ++o) {
-    if (o == 0 && h == 0) {
-      d0 += dX0[0]; d1 += dX0[1]; d2 += dX0[2];
-    } else {
-      const int k = 2 * o + h - 1;
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const int j = 2 * k + p;
-        const int d = j / 10, f = j - d * 10;
-        const float sv = X0[o * 4 + 2 * p], cv = X0[o * 4 + 2 * p + 1];
-        const float dq = ldexpf(dX0[o * 4 + 2 * p] * cv - dX0[o * 4 + 2 * p + 1] * sv, f);
-        // (selects: d differs between the lane halves, and a branchy update makes d0..2 a scratch array indexed per lane)
-        d0 += d == 0 ? dq : 0.f; d1 += d == 1 ? dq : 0.f; d2 += d == 2 ? dq : 0.f;
-      }
-    }
-  }
-}
-
-RDRF_D float act_grad(float f, int act, float shift) {
-  return act == RDRF_ACT_RELU ? (f > 0.0f ? 1.0f : 0.0f) : sigmoidf_(f + shift);
-}
-
 // ------------------------------------------------------------------------------------------------
 // appearance phase backward-data (dynamic: MLP_Fea_late_view; static: MLP_Fea | TimeEmbedding)
 // ------------------------------------------------------------------------------------------------
-// FEAT: the features ARE the basis output: d(features) arrive in g_feat, only the basis backward runs
-template <bool FEAT>
-RDRF_D void feat_dF(float (&dF)[16], const float* g_feat, int idx, bool act, int h) {
-#pragma unroll
-  for (int kk = 0; kk < 16; ++kk) {
-    const int e = elem_of(kk, h);
-    dF[kk] = (act && e < 27) ? g_feat[(size_t)idx * 27 + e] : 0.f;
-  }
-}
-
 // REC: d(app features) go out as sample-major records for the sorted scatter (a.dfa) instead of DA rows
-
-// one backward-data layer of the appearance phases: NBI input blocks from one dz vector, fp32 pipe (A/B builds) or split-storage
-// bf16 x 3 (the lo pieces of step 0 are requested here: callers place the call so that row loads / VALU work follow the request)
-template <int NBI, int KK>
-RDRF_D void app_bwd_seg(f32x16 (&acc)[NBI], const float (&dz)[KK], const float* __restrict__ whm, const float* __restrict__ pk,
-                        int lo_reg, int lo_off, int lane) {
-#ifdef RDRF_APP_F32
-  mfma_seg<NBI, KK>(acc, dz, whm, lane);
-#else
-  const B3sLo st = b3s_lo_stream(pk + lo_reg, lane);
-  u32x4 lo[NBI];
-  b3s_lo_load<NBI>(lo, st, lo_off, KK / 8, 0);
-  mfma_seg_b3s<NBI, KK, 0>(acc, dz, whm, st, lo_off, 0, lo, lane);
-#endif
-}
 template <bool FEAT, bool REC = false>
 __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_app_bwd(BwdArgs a, DynW w, DynG gw) {
   __shared__ int s_next;
@@ -93,27 +44,18 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_app_bwd(BwdArgs a, DynW 
   const int count = FEAT ? a.M : a.sp.hdr->count;
   const int ntiles = (count + 31) >> 5;
   for (int k = wave, tile; (tile = blockIdx.x + k * gridDim.x) < ntiles; k = tile_queue_next(&s_next, k, nwaves, a.dynq != 0)) {
-    const int li = tile * 32 + s;
-    const bool act = li < count;
-    const int idx = act ? (FEAT ? li : a.sp.list[li]) : 0;
-    const int n = idx / a.S;
+    const AppTile t = app_tile<FEAT>(a, tile, s, count);
     const float* svb = a.sp.act3 + (size_t)tile * sv::K3_ROWS * 32;
     float* gb = a.grows3 + (size_t)tile * sv::K3G_ROWS * 32;
     if constexpr (FEAT) {
-      float dF[16];
-      feat_dF<true>(dF, a.g_feat, idx, act, h);
-      save_rows<16>(gb, sv::K3G_DF, dF, s, h);
-      f32x16 acc[7];
-      acc_zero<7>(acc);
-      app_bwd_seg<7, 16>(acc, dF, basisT, a.pk, pkb::REG_K3_LO, pkb::K3_LO_BASIST, lane);
-      float dA[112];
-      acc_copy<7>(dA, acc);
-      save_rows<112>(gb, sv::K3G_DA, dA, s, h);
+      app_feat_only<7>(a, gb, t, basisT, pkb::REG_K3_LO, pkb::K3_LO_BASIST, s, h, lane);
       continue;
     }
     float vx, vy, vz;
-    ray_norm(a.rays, n, a.ray_type, vx, vy, vz);
-    // ---- output layer: v = Wv [H2, vd] + b ; rgb = sigmoid(v)
+    ray_norm(a.rays, t.n, a.ray_type, vx, vy, vz);
+    // ---- output layer: v = Wv [H2, vd] + b ; rgb = sigmoid(v).  Written out here and in k_static_app_bwd: as a function
+    // shared by the two (whole, or the dzv loop alone, H2 loaded inside or passed in) hipcc spills 39 to 56 registers in all
+    // four ray-path instantiations of the appearance kernels, which hold 223 to 236 without it
     float H2[64];
     load_rows<64>(svb, sv::K3_H2, H2, s, h);
     float dzv[3];
@@ -122,25 +64,15 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_app_bwd(BwdArgs a, DynW 
       float v = dot_small<64>(H2, lds + pkb::K3_RGBV + o * 128, h) + w.rbv[o];
       v += w.rwv[o * 131 + 128] * vx + w.rwv[o * 131 + 129] * vy + w.rwv[o * 131 + 130] * vz;
       const float r = sigmoidf_(v);
-      const float g = (act && a.g_rgb) ? a.g_rgb[(size_t)idx * 3 + o] : 0.f;
+      const float g = (t.act && a.g_rgb) ? a.g_rgb[(size_t)t.idx * 3 + o] : 0.f;
       dzv[o] = g * r * (1.0f - r);
       if (h == 0) gb[(size_t)(sv::K3G_DZV + o) * 32 + s] = dzv[o];
     }
     float dz2[64];
     small_layer_bwd<64, 3>(dz2, H2, lds + pkb::K3_RGBV, h, dzv);
     save_rows<64>(gb, sv::K3G_DZ2, dz2, s, h);
-    // ---- layer 2 backward: dH1 = W2^T dz2
     float dz1[64];
-    {
-      f32x16 acc[4];
-      acc_zero<4>(acc);
-      app_bwd_seg<4, 64>(acc, dz2, lds + pkb::K3_RGB2T, a.pk, pkb::REG_K3_LO, pkb::K3_LO_RGB2T, lane);
-      float H1[64];
-      load_rows<64>(svb, sv::K3_H1, H1, s, h);
-#pragma unroll
-      for (int kk = 0; kk < 64; ++kk) dz1[kk] = H1[kk] > 0.f ? acc[kk >> 4][kk & 15] : 0.f;
-    }
-    save_rows<64>(gb, sv::K3G_DZ1, dz1, s, h);
+    app_l2_bwd(dz1, dz2, a, svb, gb, sv::K3_H1, lds + pkb::K3_RGB2T, pkb::REG_K3_LO, pkb::K3_LO_RGB2T, s, h, lane);
     // ---- layer 1 backward: feature block and X0 block (t / PE(t) carry no gradient)
     float dF[16], dX0[32];
     {
@@ -173,19 +105,16 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_app_bwd(BwdArgs a, DynW 
     dn0 += __shfl_xor(dn0, 32, 64); dn1 += __shfl_xor(dn1, 32, 64); dn2 += __shfl_xor(dn2, 32, 64);
     // ---- basis backward: d(app features) rows for the scatter kernel
     {
-      f32x16 acc[7];
-      acc_zero<7>(acc);
-      app_bwd_seg<7, 16>(acc, dF, basisT, a.pk, pkb::REG_K3_LO, pkb::K3_LO_BASIST, lane);
       float dA[112];
-      acc_copy<7>(dA, acc);
+      app_basis_bwd<7>(dA, dF, basisT, a.pk, pkb::REG_K3_LO, pkb::K3_LO_BASIST, lane);
       if constexpr (REC) {
         // sample-major record for the sorted scatter: this lane half holds the feature quads Q = 2 m + h (slots
         // 4m..4m+3) of compacted sample li; one 16-byte store per quad, the two halves write adjacent quads
-        if (act) {
+        if (t.act) {
           // quad 2 m + 1 sits 4 floats after quad 2 m in the record, except for the (XZ quad 2 | YZ quad 0) pair of
           // every level: one base pointer per half + immediate offsets
-          float* rec = a.dfa + (size_t)li * DFA_FLOATS + 4 * h;
-          float* recx = a.dfa + (size_t)li * DFA_FLOATS + (h ? dfa_off(15) - dfa_off(14) : 0);
+          float* rec = a.dfa + (size_t)t.li * DFA_FLOATS + 4 * h;
+          float* recx = a.dfa + (size_t)t.li * DFA_FLOATS + (h ? dfa_off(15) - dfa_off(14) : 0);
 #pragma unroll
           for (int m = 0; m < 27; ++m) {
             static_assert(dfa_off(1) == dfa_off(0) + 4 && dfa_off(13) == dfa_off(12) + 4 && dfa_off(17) == dfa_off(16) + 4, "record layout");
@@ -197,9 +126,9 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_app_bwd(BwdArgs a, DynW 
         save_rows<112>(gb, sv::K3G_DA, dA, s, h);
       }
     }
-    if (act && h == 0) {
-      a.dxn_app[(size_t)idx * 3 + 0] = dn0; a.dxn_app[(size_t)idx * 3 + 1] = dn1;
-      a.dxn_app[(size_t)idx * 3 + 2] = dn2;
+    if (t.act && h == 0) {
+      a.dxn_app[(size_t)t.idx * 3 + 0] = dn0; a.dxn_app[(size_t)t.idx * 3 + 1] = dn1;
+      a.dxn_app[(size_t)t.idx * 3 + 2] = dn2;
     }
   }
 }
@@ -215,26 +144,16 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_static_app_bwd(BwdArgs a, St
   const int count = FEAT ? a.M : a.sp.hdr->count;
   const int ntiles = (count + 31) >> 5;
   for (int k = wave, tile; (tile = blockIdx.x + k * gridDim.x) < ntiles; k = tile_queue_next(&s_next, k, nwaves, a.dynq != 0)) {
-    const int li = tile * 32 + s;
-    const bool act = li < count;
-    const int idx = act ? (FEAT ? li : a.sp.list[li]) : 0;
-    const int n = idx / a.S;
+    const AppTile t = app_tile<FEAT>(a, tile, s, count);
     const float* svb = a.sp.act3 + (size_t)tile * sv::S3_ROWS * 32;
     float* gb = a.grows3 + (size_t)tile * sv::K3G_ROWS * 32;
     if constexpr (FEAT) {
-      float dF[16];
-      feat_dF<true>(dF, a.g_feat, idx, act, h);
-      save_rows<16>(gb, sv::K3G_DF, dF, s, h);
-      f32x16 acc[3];
-      acc_zero<3>(acc);
-      app_bwd_seg<3, 16>(acc, dF, lds + pkb::S3_BASIST, a.pk, pkb::REG_S3_LO, pkb::S3_LO_BASIST, lane);
-      float dG[48];
-      acc_copy<3>(dG, acc);
-      save_rows<48>(gb, sv::K3G_DA, dG, s, h);
+      app_feat_only<3>(a, gb, t, lds + pkb::S3_BASIST, pkb::REG_S3_LO, pkb::S3_LO_BASIST, s, h, lane);
       continue;
     }
     float vx, vy, vz;
-    ray_norm(a.rays, n, a.ray_type, vx, vy, vz);
+    ray_norm(a.rays, t.n, a.ray_type, vx, vy, vz);
+    // ---- output layer (in place: see k_dyn_app_bwd)
     float H2[64];
     load_rows<64>(svb, sv::S3_H2, H2, s, h);
     float dzv[3];
@@ -244,7 +163,7 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_static_app_bwd(BwdArgs a, St
       if (HEAD == RDRF_HEAD_MLP_FEA_TIMEEMBEDDING)
         v += w.w3[o * 131 + 128] * vx + w.w3[o * 131 + 129] * vy + w.w3[o * 131 + 130] * vz;
       const float r = sigmoidf_(v);
-      const float g = (act && a.g_rgb) ? a.g_rgb[(size_t)idx * 3 + o] : 0.f;
+      const float g = (t.act && a.g_rgb) ? a.g_rgb[(size_t)t.idx * 3 + o] : 0.f;
       dzv[o] = g * r * (1.0f - r);
       if (h == 0) gb[(size_t)(sv::K3G_DZV + o) * 32 + s] = dzv[o];
     }
@@ -252,16 +171,7 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_static_app_bwd(BwdArgs a, St
     small_layer_bwd<64, 3>(dz2, H2, lds + pkb::S3_W3, h, dzv);
     save_rows<64>(gb, sv::K3G_DZ2, dz2, s, h);
     float dz1[64];
-    {
-      f32x16 acc[4];
-      acc_zero<4>(acc);
-      app_bwd_seg<4, 64>(acc, dz2, lds + pkb::S3_W2T, a.pk, pkb::REG_S3_LO, pkb::S3_LO_W2T, lane);
-      float H1[64];
-      load_rows<64>(svb, sv::S3_H1, H1, s, h);
-#pragma unroll
-      for (int kk = 0; kk < 64; ++kk) dz1[kk] = H1[kk] > 0.f ? acc[kk >> 4][kk & 15] : 0.f;
-    }
-    save_rows<64>(gb, sv::K3G_DZ1, dz1, s, h);
+    app_l2_bwd(dz1, dz2, a, svb, gb, sv::S3_H1, lds + pkb::S3_W2T, pkb::REG_S3_LO, pkb::S3_LO_W2T, s, h, lane);
     float dF[16];
     {
 #ifdef RDRF_APP_F32
@@ -293,6 +203,8 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_static_app_bwd(BwdArgs a, St
     // the view-direction slots (27..29) of the feature block are not features: they carry
     // d(loss)/d(viewdir); viewdir = d/|d|  =>  g_d = (g_v - (g_v.v) v) / |d|
     {
+      const int n = t.n;
+      const bool act = t.act;
       float gv0 = 0.f, gv1 = 0.f, gv2 = 0.f;
       if (HEAD == RDRF_HEAD_MLP_FEA) {
         if (h == 0) { gv0 = dF[15]; dF[15] = 0.f; }
@@ -319,25 +231,16 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_static_app_bwd(BwdArgs a, St
       }
     }
     save_rows<16>(gb, sv::K3G_DF, dF, s, h);
-    {
-      f32x16 acc[3];
-      acc_zero<3>(acc);
-      app_bwd_seg<3, 16>(acc, dF, lds + pkb::S3_BASIST, a.pk, pkb::REG_S3_LO, pkb::S3_LO_BASIST, lane);
-      float dG[48];
-      acc_copy<3>(dG, acc);
-      save_rows<48>(gb, sv::K3G_DA, dG, s, h);
-    }
+    float dG[48];
+    app_basis_bwd<3>(dG, dF, lds + pkb::S3_BASIST, a.pk, pkb::REG_S3_LO, pkb::S3_LO_BASIST, lane);
+    save_rows<48>(gb, sv::K3G_DA, dG, s, h);
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// d(weight)/d(alpha) along a ray.  weight_k = alpha_k T_k, T_k = prod_{j<k} p_j, p = 1-alpha+1e-10
-//   dL/dalpha_k = gw_k T_k - (sum_{m>k} gw_m w_m) / p_k
-// ------------------------------------------------------------------------------------------------
-
-// static field, density phase backward: wave per ray, lane per sample.  The suffix sum is formed
-// directly by walking the ray LAST tile first (transmittance carries of each tile start come from a
-// forward pre-pass); total - prefix would cancel catastrophically when p -> 1e-10.
+// static field, density phase backward: wave per ray, lane per sample.  This is the ray scan backward of rdrf_bwd_mlp_dev.hpp
+// (scan_sample, tile_carries, suffix_g_alpha, dist_grads) 64 wide, written out in place: built from those functions the kernel
+// gave the same bits with the same 37 registers, and took 0.0185 ms against 0.0176 ms at the bench's final stage (ten
+// alternating runs each: new 0.0183 .. 0.0188, parent 0.0174 .. 0.0178), 0.0109 against 0.0107 ms at stage 0.
 __global__ __launch_bounds__(64) void k_static_density_bwd(BwdArgs a, StaticW w, float* __restrict__ gf_rows) {
   __shared__ float carr[64];   // transmittance carries at each 64-sample step (S <= 4096)
   const int lane = threadIdx.x;
@@ -423,16 +326,16 @@ __global__ __launch_bounds__(64) void k_static_density_bwd(BwdArgs a, StaticW w,
 // dynamic field, density / blending / warp backward-data: wave per ray, 32-sample tiles, in two
 // phases around the scatter kernel:
 //   PHASE 0 (heads): weight/sigma/blending backward, density + blending head backward ->
-//                    d(feature) rows for k_scatter, d(X0) partial rows, dz rows
+//                    d(feature) rows for k_scatter, d(X0) partial rows, dz rows        (dyn_heads_bwd_tile)
 //   PHASE 1 (warp) : coordinate gradients (appearance + density + blending scatter) ->
-//                    warp MLP backward, positional-encoding backward, g_xyz, d(tout)
+//                    warp MLP backward, positional-encoding backward, g_xyz, d(tout)  (dyn_warp_bwd_tile)
 // ------------------------------------------------------------------------------------------------
 
 // The scan half of the heads' backward on the flat-tile path (rdrf_flat_density): per ray, the transmittance carries at
 // the tile starts (pre-pass) and the reverse suffix sweep of d(weight) -> d(alpha); per sample the total
 // g_sigma = the caller's g_sigma + g_alpha ds (1 - alpha) (BwdArgs::gsig), the g_z updates, and the ray norm's share of
-// g_rays.  A half-wave per ray (two rays per wave, as ray_scan_body).  The expressions and the order of every sum are
-// those of the wave-per-ray k_dyn_density_bwd<0>, so g_sigma comes out bit-identical.
+// g_rays.  A half-wave per ray (two rays per wave, as ray_scan_body).  It runs the functions the wave-per-ray
+// k_dyn_density_bwd<0> runs, at the same width, so g_sigma comes out bit-identical.
 __global__ __launch_bounds__(512) void k_ray_scan_bwd(BwdArgs a) {
   __shared__ float carr[16][128];   // per half-wave: transmittance at the tile starts (S <= 4096)
   const int lane = threadIdx.x & 63, h = lane >> 5, s = lane & 31;
@@ -443,65 +346,15 @@ __global__ __launch_bounds__(512) void k_ray_scan_bwd(BwdArgs a) {
   const int tpr = (a.S + 31) >> 5;
   float vx, vy, vz;
   const float nrm = ray_norm(a.rays, n, a.ray_type, vx, vy, vz);
-  if (a.g_weight) {  // pre-pass: transmittance at each tile start
-    float carry = 1.0f;
-    for (int j0 = 0; j0 < a.S; j0 += 32) {
-      if (s == 0) carr[hw][j0 >> 5] = carry;
-      const int j = j0 + s;
-      const bool act = ray && j < a.S;
-      const int idx = n * a.S + (act ? j : 0);
-      const bool vld = act && a.valid[idx] != 0;
-      const float sigma = vld ? density_act(a.sp.raw[(size_t)idx * 2], a.act, a.density_shift) : 0.f;
-      const float zj = act ? a.z[idx] : 0.f;
-      const float zn = (j + 1 < a.S) ? a.z[idx + 1] : zj;
-      const float ds = ((j + 1 < a.S) ? (zn - zj) : 0.0f) * nrm * a.distance_scale;
-      const float alpha = 1.0f - expf(-sigma * ds);
-      const float p = act ? one_minus_alpha_eps(alpha) : 1.0f;
-      carry *= __shfl(scan_mul32(p, s), 31, 32);
-    }
-  }
+  if (a.g_weight) tile_carries<32>(a, carr[hw], 2, n, ray, s == 0, s, nrm);
   float sufcarry = 0.f, g_nrm = 0.f;
   for (int tli = tpr - 1; tli >= 0; --tli) {  // LAST tile first: direct suffix sums
     const int j = (tli << 5) + s;
     const bool act = ray && j < a.S;
     const int idx = n * a.S + (act ? j : 0);
     const bool vld = act && a.valid[idx] != 0;
-    const float sigma = vld ? density_act(a.sp.raw[(size_t)idx * 2], a.act, a.density_shift) : 0.f;
-    const float zj = act ? a.z[idx] : 0.f;
-    const float zn = (j + 1 < a.S) ? a.z[idx + 1] : zj;
-    const float ds = ((j + 1 < a.S) ? (zn - zj) : 0.0f) * nrm * a.distance_scale;
-    const float alpha = 1.0f - expf(-sigma * ds);
-    const float p = act ? one_minus_alpha_eps(alpha) : 1.0f;
-    float g_alpha = 0.f;
-    if (a.g_weight) {
-      const float incl = scan_mul32(p, s);
-      float excl = __shfl_up(incl, 1, 32);
-      if (s == 0) excl = 1.0f;
-      const float T = carr[hw][tli] * excl;
-      const float gwv = act ? a.g_weight[idx] : 0.f;
-      float rinc = gwv * alpha * T;
-#pragma unroll
-      for (int d = 1; d < 32; d <<= 1) {
-        const float o = __shfl_down(rinc, d, 32);
-        if (s + d < 32) rinc += o;
-      }
-      float rex = __shfl_down(rinc, 1, 32);
-      if (s == 31) rex = 0.f;
-      g_alpha = gwv * T - (sufcarry + rex) / p;
-      sufcarry += __shfl(rinc, 0, 32);
-    }
-    float g_sigma = (act && a.g_sigma) ? a.g_sigma[idx] : 0.f;
-    g_sigma += g_alpha * ds * (1.0f - alpha);
+    const float g_sigma = scan_bwd_step<32>(a, a.sp.raw[(size_t)idx * 2], carr[hw] + tli, act, vld, act, idx, j, s, nrm, sufcarry, g_nrm);
     if (act) a.gsig[idx] = g_sigma;
-    if ((a.g_rays || a.g_z) && act) {
-      const float g_ds = (a.g_dists ? a.g_dists[idx] : 0.f) + g_alpha * sigma * (1.0f - alpha);
-      if (a.g_rays) g_nrm += g_ds * ((j + 1 < a.S) ? (zn - zj) : 0.0f) * a.distance_scale;
-      if (a.g_z && j + 1 < a.S) {
-        const float gz = g_ds * nrm * a.distance_scale;
-        atomicAdd(a.g_z + idx, -gz);
-        atomicAdd(a.g_z + idx + 1, gz);
-      }
-    }
   }
   if (a.g_rays && a.ray_type != RDRF_RAY_OTHER) {   // the half-wave owns its ray: one update per component
 #pragma unroll
@@ -531,23 +384,7 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_density_bwd(BwdArgs a, D
     float vx = 0.f, vy = 0.f, vz = 0.f;
     float nrm = 1.0f;
     if constexpr (!FEAT && !FLAT) nrm = ray_norm(a.rays, n, a.ray_type, vx, vy, vz);
-    if (!FEAT && !FLAT && PHASE == 0 && a.g_weight) {  // pre-pass: transmittance at each tile start
-      float carry = 1.0f;
-      for (int j0 = 0; j0 < a.S; j0 += 32) {
-        if (lane == 0) carr[wave][j0 >> 5] = carry;
-        const int j = j0 + s;
-        const bool act = j < a.S;
-        const int idx = n * a.S + (act ? j : 0);
-        const bool vld = act && a.valid[idx] != 0;
-        const float sigma = vld ? density_act(a.sp.raw[(size_t)idx * 2], a.act, a.density_shift) : 0.f;
-        const float zj = act ? a.z[idx] : 0.f;
-        const float zn = (j + 1 < a.S) ? a.z[idx + 1] : zj;
-        const float ds = ((j + 1 < a.S) ? (zn - zj) : 0.0f) * nrm * a.distance_scale;
-        const float alpha = 1.0f - expf(-sigma * ds);
-        const float p = act ? one_minus_alpha_eps(alpha) : 1.0f;
-        carry *= __shfl(scan_mul32(p, s), 31, 32);
-      }
-    }
+    if (!FEAT && !FLAT && PHASE == 0 && a.g_weight) tile_carries<32>(a, carr[wave], 2, n, true, lane == 0, s, nrm);
     float sufcarry = 0.f, g_nrm = 0.f;
     float dTacc[16];
 #pragma unroll
@@ -561,256 +398,21 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_dyn_density_bwd(BwdArgs a, D
       const size_t tl = FLAT ? (size_t)n : (size_t)n * tpr + tli;
       const float* svb = a.sp.act1 + tl * sv::K1_ROWS * 32;
       float* gb = a.grows1 + tl * sv::K1G_ROWS * 32;
-      if (PHASE == 0) {
-        float g_fd, g_fb;
-        if constexpr (FEAT) {  // the gradients of the raw head outputs arrive directly
-          g_fd = (act && a.g_sigma) ? a.g_sigma[idx] : 0.f;
-          g_fb = (act && a.g_blending) ? a.g_blending[idx] : 0.f;
-        } else if constexpr (FLAT) {   // the scan half ran in k_ray_scan_bwd
-          const float fd = a.sp.raw[(size_t)idx * 2], fb = a.sp.raw[(size_t)idx * 2 + 1];
-          const float g_sigma = act ? a.gsig[idx] : 0.f;
-          g_fd = vld ? g_sigma * act_grad(fd, a.act, a.density_shift) : 0.f;
-          const float bl = sigmoidf_(fb);
-          g_fb = (vld && a.g_blending) ? a.g_blending[idx] * bl * (1.0f - bl) : 0.f;
-        } else {
-        const float fd = a.sp.raw[(size_t)idx * 2], fb = a.sp.raw[(size_t)idx * 2 + 1];
-        const float sigma = vld ? density_act(fd, a.act, a.density_shift) : 0.f;
-        const float zj = act ? a.z[idx] : 0.f;
-        const float zn = (j + 1 < a.S) ? a.z[idx + 1] : zj;
-        const float ds = ((j + 1 < a.S) ? (zn - zj) : 0.0f) * nrm * a.distance_scale;
-        const float alpha = 1.0f - expf(-sigma * ds);
-        const float p = act ? one_minus_alpha_eps(alpha) : 1.0f;
-        float g_alpha = 0.f;
-        if (a.g_weight) {
-          const float incl = scan_mul32(p, s);
-          float excl = __shfl_up(incl, 1, 32);
-          if (s == 0) excl = 1.0f;
-          const float T = carr[wave][tli] * excl;
-          const float gwv = act ? a.g_weight[idx] : 0.f;
-          float rinc = gwv * alpha * T;
-#pragma unroll
-          for (int d = 1; d < 32; d <<= 1) {
-            const float o = __shfl_down(rinc, d, 32);
-            if (s + d < 32) rinc += o;
-          }
-          float rex = __shfl_down(rinc, 1, 32);
-          if (s == 31) rex = 0.f;
-          g_alpha = gwv * T - (sufcarry + rex) / p;
-          sufcarry += __shfl(rinc, 0, 32);
-        }
-        float g_sigma = (act && a.g_sigma) ? a.g_sigma[idx] : 0.f;
-        g_sigma += g_alpha * ds * (1.0f - alpha);
-        if ((a.g_rays || a.g_z) && act && h == 0) {
-          const float g_ds = (a.g_dists ? a.g_dists[idx] : 0.f) + g_alpha * sigma * (1.0f - alpha);
-          if (a.g_rays) g_nrm += g_ds * ((j + 1 < a.S) ? (zn - zj) : 0.0f) * a.distance_scale;
-          if (a.g_z && j + 1 < a.S) {
-            const float gz = g_ds * nrm * a.distance_scale;
-            atomicAdd(a.g_z + idx, -gz);
-            atomicAdd(a.g_z + idx + 1, gz);
-          }
-        }
-        g_fd = vld ? g_sigma * act_grad(fd, a.act, a.density_shift) : 0.f;
-        const float bl = sigmoidf_(fb);
-        g_fb = (vld && a.g_blending) ? a.g_blending[idx] * bl * (1.0f - bl) : 0.f;
-        }
-        f32x16 accX[2];  // d(X0) of the density and blending heads
-        acc_zero<2>(accX);
-        // head liveness (wave-uniform): a head whose output no loss reaches is not differentiated -- the reference's
-        // autograd never visits that subgraph either (passes B-D of the trainer: no term depends on the blending head
-        // before the late mask terms) -- so its 160 MFMAs per tile, its dz / d(feature) rows, its scatter set and its
-        // dW products (host side) all drop out
-        const bool live_d = FEAT ? a.g_sigma != nullptr : (a.g_sigma != nullptr || a.g_weight != nullptr);
-        const bool live_b = a.g_blending != nullptr;
-#pragma unroll
-        for (int head = 0; head < 2; ++head) {
-          if (!(head == 0 ? live_d : live_b)) continue;
-          const float gfh = head == 0 ? g_fd : g_fb;
-          float Hh[32], dzh[32];
-          load_rows<32>(svb, head == 0 ? sv::K1_HD : sv::K1_HB, Hh, s, h);
-          const float* w2 = lds + (head == 0 ? pkb::K1H_DEN2 : pkb::K1H_BLE2) + h * 32;
-          float w2r[32];   // eight 16-byte LDS reads up front (element-wise reads were 32 x {ds_read_b32, lgkmcnt(0)})
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(w2 + 4 * q);
-            w2r[4 * q] = v.x; w2r[4 * q + 1] = v.y; w2r[4 * q + 2] = v.z; w2r[4 * q + 3] = v.w;
-          }
-#pragma unroll
-          for (int kk = 0; kk < 32; ++kk) dzh[kk] = Hh[kk] > 0.f ? w2r[kk] * gfh : 0.f;
-          save_rows<32>(gb, head == 0 ? sv::K1G_DZD : sv::K1G_DZB, dzh, s, h);
-          if (!FEAT && a.small_dw) {   // d(layer2 weight) = sum over the samples of g * (layer2 input = the saved activation)
-            float pw[32];
-#pragma unroll
-            for (int kk = 0; kk < 32; ++kk) pw[kk] = gfh * Hh[kk];
-            sw[head] += reduce_scatter32(pw, s);
-            sb[head] += gfh;
-          }
-          f32x16 accF[3];
-          acc_zero<3>(accF);
-#ifdef RDRF_HEADS_BWD_F32
-          mfma_seg<3, 32>(accF, dzh, lds + (head == 0 ? pkb::K1H_DEN1T_F : pkb::K1H_BLE1T_F), lane);
-          mfma_seg<2, 32>(accX, dzh, lds + (head == 0 ? pkb::K1H_DEN1T_X0 : pkb::K1H_BLE1T_X0), lane);
-#else
-          mfma_seg_b3_pair<3, 2, 32>(accF, accX, dzh, lds + (head == 0 ? pkb::K1H_DEN1T_F : pkb::K1H_BLE1T_F),
-                                     lds + (head == 0 ? pkb::K1H_DEN1T_X0 : pkb::K1H_BLE1T_X0), lane);
-#endif
-          float dFh[48];
-          acc_copy<3>(dFh, accF);
-          if (!FEAT && a.dfs != nullptr) {
-            // sample-major record for the sorted scatter: this lane half holds the feature quads Q = 2 m + h
-            // (slots 4m..4m+3), Q = 6 level + {0..3: XY quad, 4: XZ, 5: YZ}; one 16-byte store per quad
-            if (act) {
-              float* rec = a.dfs + (size_t)idx * DFS_FLOATS + head * 72;
-#pragma unroll
-              for (int m = 0; m < 9; ++m) {
-                const int off = h ? dfs_off(2 * m + 1) : dfs_off(2 * m);
-                *reinterpret_cast<f32x4*>(rec + off) = f32x4{dFh[4 * m], dFh[4 * m + 1], dFh[4 * m + 2], dFh[4 * m + 3]};
-              }
-            }
-          } else {
-            save_rows<48>(gb, head == 0 ? sv::K1G_DFD : sv::K1G_DFB, dFh, s, h);
-          }
-        }
-        float dXh[32];
-        acc_copy<2>(dXh, accX);
-        save_rows<32>(gb, sv::K1G_DX0, dXh, s, h);
-        if (h == 0) {
-          gb[(size_t)(sv::K1G_SM + 3) * 32 + s] = g_fd;
-          gb[(size_t)(sv::K1G_SM + 4) * 32 + s] = g_fb;
-        }
-      } else {
-        // coordinate gradients: appearance phase + density/blending scatter (already summed)
-        float dw0 = act ? a.dxw_app[(size_t)idx * 3 + 0] : 0.f, dw1 = act ? a.dxw_app[(size_t)idx * 3 + 1] : 0.f,
-              dw2 = act ? a.dxw_app[(size_t)idx * 3 + 2] : 0.f;
-        float dn0 = act ? a.dxn_app[(size_t)idx * 3 + 0] : 0.f, dn1 = act ? a.dxn_app[(size_t)idx * 3 + 1] : 0.f,
-              dn2 = act ? a.dxn_app[(size_t)idx * 3 + 2] : 0.f;
-        // xw = normalize(unnormalize(xn) + delta); xyz_prime = xyz + delta
-        float dd0 = dw0 * a.box.inv[0], dd1 = dw1 * a.box.inv[1], dd2 = dw2 * a.box.inv[2];
-        float gp0 = 0.f, gp1 = 0.f, gp2 = 0.f;
-        if (act && a.g_xyz_prime) {
-          gp0 = a.g_xyz_prime[(size_t)idx * 3 + 0]; gp1 = a.g_xyz_prime[(size_t)idx * 3 + 1];
-          gp2 = a.g_xyz_prime[(size_t)idx * 3 + 2];
-        }
-        dd0 += gp0; dd1 += gp1; dd2 += gp2;
-        if (!act) { dd0 = dd1 = dd2 = 0.f; }
-        if (h == 0) {  // small-layer dz rows 0..2 (rows 3,4 were written by phase 0)
-          gb[(size_t)(sv::K1G_SM + 0) * 32 + s] = dd0; gb[(size_t)(sv::K1G_SM + 1) * 32 + s] = dd1;
-          gb[(size_t)(sv::K1G_SM + 2) * 32 + s] = dd2;
-        }
-        // ---- warp MLP backward: layer5 (VALU) -> layer4 -> layer3
-        float dz4[32];
-        {
-          float H4[32];
-          load_rows<32>(svb, sv::K1_H4, H4, s, h);
-          const float* w5 = lds + pkb::K1W_W5 + h * 32;
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {   // 16-byte LDS reads (see the heads above)
-            const f32x4 wa = *reinterpret_cast<const f32x4*>(w5 + 4 * q);
-            const f32x4 wb = *reinterpret_cast<const f32x4*>(w5 + 64 + 4 * q);
-            const f32x4 wc = *reinterpret_cast<const f32x4*>(w5 + 128 + 4 * q);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-              const float d = wa[c] * dd0 + wb[c] * dd1 + wc[c] * dd2;
-              dz4[4 * q + c] = H4[4 * q + c] > 0.f ? d : 0.f;
-            }
-          }
-          if (!FEAT && a.small_dw) {   // d(layer5 weight): three output rows against the 64 saved inputs
-            sb[0] += dd0; sb[1] += dd1; sb[2] += dd2;
-#pragma unroll 1
-            for (int o = 0; o < 3; ++o) {   // one row at a time: the three butterflies unrolled together spill
-              const float dd = o == 0 ? dd0 : (o == 1 ? dd1 : dd2);
-              float pw[32];
-#pragma unroll
-              for (int kk = 0; kk < 32; ++kk) pw[kk] = dd * H4[kk];
-              const float r = reduce_scatter32(pw, s);
-              sw[0] += o == 0 ? r : 0.f; sw[1] += o == 1 ? r : 0.f; sw[2] += o == 2 ? r : 0.f;
-            }
-          }
-        }
-        save_rows<32>(gb, sv::K1G_DZ4, dz4, s, h);
-        float dz3[32];
-        {
-          f32x16 acc[2];
-          acc_zero<2>(acc);
-#ifdef RDRF_HEADS_BWD_F32
-          mfma_seg<2, 32>(acc, dz4, lds + pkb::K1W_W4T, lane);
-#else
-          mfma_seg_b3<2, 32>(acc, dz4, lds + pkb::K1W_W4T, lane);
-#endif
-          float H3[32];
-          load_rows<32>(svb, sv::K1_H3, H3, s, h);
-#pragma unroll
-          for (int kk = 0; kk < 32; ++kk) dz3[kk] = H3[kk] > 0.f ? acc[kk >> 4][kk & 15] : 0.f;
-        }
-        save_rows<32>(gb, sv::K1G_DZ3, dz3, s, h);
-        f32x16 accX[2];  // d(X0): heads (from rows) + warp layer 3
-        {
-          float dXh[32];
-          load_rows<32>(gb, sv::K1G_DX0, dXh, s, h);
-#pragma unroll
-          for (int kk = 0; kk < 32; ++kk) accX[kk >> 4][kk & 15] = dXh[kk];
-        }
-#ifdef RDRF_HEADS_BWD_F32
-        mfma_seg<2, 32>(accX, dz3, lds + pkb::K1W_W3T_X0, lane);
-#endif
-        {
-          f32x16 accT[1];
-          acc_zero<1>(accT);
-#ifdef RDRF_HEADS_BWD_F32
-          mfma_seg<1, 32>(accT, dz3, lds + pkb::K1W_W3T_T, lane);
-#else
-          mfma_seg_b3_pair<2, 1, 32>(accX, accT, dz3, lds + pkb::K1W_W3T_X0, lds + pkb::K1W_W3T_T, lane);
-#endif
-#pragma unroll
-          for (int i = 0; i < 16; ++i) dTacc[i] += accT[0][i];
-        }
-        // ---- positional encoding backward -> d(xn); plus the identity path xw <- xn
-        {
-          float X0[32], dX0[32];
-          load_rows<32>(svb, sv::K1_X0, X0, s, h);
-          acc_copy<2>(dX0, accX);
-          float e0 = 0.f, e1 = 0.f, e2 = 0.f;
-          x0_bwd(X0, dX0, h, e0, e1, e2);
-          e0 += __shfl_xor(e0, 32, 64); e1 += __shfl_xor(e1, 32, 64); e2 += __shfl_xor(e2, 32, 64);
-          dn0 += e0 + dw0; dn1 += e1 + dw1; dn2 += e2 + dw2;
-        }
-        if (act && h == 0 && a.g_xyz) {
-          if (FEAT && a.in_norm) {   // compute_*: gradient wrt the NORMALISED input coordinates
-            a.g_xyz[(size_t)idx * 3 + 0] += dn0; a.g_xyz[(size_t)idx * 3 + 1] += dn1;
-            a.g_xyz[(size_t)idx * 3 + 2] += dn2;
-          } else {
-            a.g_xyz[(size_t)idx * 3 + 0] += dn0 * a.box.inv[0] + gp0;
-            a.g_xyz[(size_t)idx * 3 + 1] += dn1 * a.box.inv[1] + gp1;
-            a.g_xyz[(size_t)idx * 3 + 2] += dn2 * a.box.inv[2] + gp2;
-          }
-        }
-        if constexpr (FEAT) {  // time is per point: d(tout) of this sample, no reduction over the tile
-          if (act) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) a.dtout[(size_t)idx * 32 + elem_of(i, h)] = dTacc[i];
-          }
-#pragma unroll
-          for (int i = 0; i < 16; ++i) dTacc[i] = 0.f;
-        }
-      }
+      if constexpr (PHASE == 0) dyn_heads_bwd_tile<FEAT, FLAT>(a, lds, svb, gb, act, vld, idx, j, s, h, lane, nrm, carr[wave] + tli, sufcarry, g_nrm, sw, sb);
+      else dyn_warp_bwd_tile<FEAT>(a, lds, svb, gb, act, idx, s, h, lane, dTacc, sw, sb);
     }
     if (PHASE == 1 && !FEAT && FLAT) {
-      // d(tout) of the tile's rays: segmented suffix sums over the lanes of each half (keys: the lane's ray, contiguous);
-      // the first lane of a segment ends up with the segment's sum
-      const int i0 = n * 32 + s, nl = i0 / a.S;
-      const int rb = nl * a.S - n * 32, re = rb + a.S - 1;   // the lane's ray: first / last sample relative to the tile
-      const int end = re < 31 ? re : 31;
-      const bool head = i0 < a.N * a.S && (s == 0 || rb == s);
-      float* dst = (rb >= 0 && re <= 31) ? a.dtout + (size_t)nl * 32           // the ray lies inside the tile
-                                         : a.dtp + ((size_t)n * 2 + (s == 0 ? 0 : 1)) * 32;
+      const DtoutSeg g = dtout_segments(a, n, s);
+      float* dst = g.inside ? a.dtout + (size_t)g.nl * 32 : a.dtp + ((size_t)n * 2 + (s == 0 ? 0 : 1)) * 32;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         float v = dTacc[i];
 #pragma unroll
         for (int d = 1; d < 32; d <<= 1) {
           const float o = __shfl_down(v, d, 32);
-          if (s + d <= end) v += o;
+          if (s + d <= g.end) v += o;
         }
-        if (head) dst[elem_of(i, h)] = v;
+        if (g.head) dst[elem_of(i, h)] = v;
       }
     }
     if (PHASE == 1 && !FEAT && !FLAT) {  // per-ray d(tout): sum over the samples (lanes of each half)
@@ -934,28 +536,6 @@ __global__ __launch_bounds__(128) void k_time_branch_bwd(const float* __restrict
 // ------------------------------------------------------------------------------------------------
 // scene flow backward-data
 // ------------------------------------------------------------------------------------------------
-RDRF_D void sf_x_bwd(const float (&X)[20], const float (&dX)[20], int h, float& d0, float& d1,
-                     float& d2) {
-#pragma unroll
-  for (int o = 0; o < 5; ++o) {
-    if (o == 0 && h == 0) {
-      d0 += dX[0]; d1 += dX[1]; d2 += dX[2];
-    } else {
-      const int k = 2 * o + h - 1;
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const int pr = 2 * k + p;
-        if (pr < 12) {
-          const int d = pr >> 2, f = pr & 3;
-          const float dq = ldexpf(dX[o * 4 + 2 * p] * X[o * 4 + 2 * p + 1] -
-                                  dX[o * 4 + 2 * p + 1] * X[o * 4 + 2 * p], f);
-          d0 += d == 0 ? dq : 0.f; d1 += d == 1 ? dq : 0.f; d2 += d == 2 ? dq : 0.f;   // selects, see x0_bwd
-        }
-      }
-    }
-  }
-}
-
 __global__ __launch_bounds__(64 * RDRF_MAXW) void k_scene_flow_bwd(int N, int S, Box box,
                                                         const float* __restrict__ pkg,
                                                         const float* __restrict__ act_rows,
@@ -991,14 +571,12 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_scene_flow_bwd(int N, int S,
     acc_zero<2>(acc);
     mfma_seg<2, 32>(acc, dz, lds + pkb::SF_W4T, lane);
     load_rows<32>(svb, sv::SF_H2, Hh, s, h);
-#pragma unroll
-    for (int kk = 0; kk < 32; ++kk) dz[kk] = Hh[kk] > 0.f ? acc[kk >> 4][kk & 15] : 0.f;
+    relu_gate<32>(dz, Hh, acc);
     save_rows<32>(gb, sv::SFG_DZ2, dz, s, h);
     acc_zero<2>(acc);
     mfma_seg<2, 32>(acc, dz, lds + pkb::SF_W2T, lane);
     load_rows<32>(svb, sv::SF_H0, Hh, s, h);
-#pragma unroll
-    for (int kk = 0; kk < 32; ++kk) dz[kk] = Hh[kk] > 0.f ? acc[kk >> 4][kk & 15] : 0.f;
+    relu_gate<32>(dz, Hh, acc);
     save_rows<32>(gb, sv::SFG_DZ0, dz, s, h);
     if (g_pts) {
       acc_zero<2>(acc);

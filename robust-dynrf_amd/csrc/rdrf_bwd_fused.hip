@@ -1,7 +1,10 @@
 // rdrf_bwd_fused.hip -- the backward-data kernels that form their layers' weight gradients themselves, for gfx950:
 // k_scene_flow_bwd_dw (scene-flow MLP) and k_dyn_warp_bwd_dw (warp MLP of the dynamic field on flat tiles), the device code
 // only they use, and the host functions that launch them (rdrf_bwd_host.hpp).  Their two-kernel partners -- k_scene_flow_bwd /
-// k_dyn_density_bwd<1> followed by k_dw3 -- and the entry points that choose between the two forms are in rdrf_bwd.hip.
+// k_dyn_density_bwd<1> followed by k_dw3 -- and the entry points that choose between the two forms are in rdrf_bwd.hip.  The data
+// steps a kernel here shares with its partner (warp_coord_grads, warp_layer5_bwd, warp_layer4_bwd, warp_layer3_bwd, warp_x0_bwd,
+// dtout_segments, relu_gate, the *_bwd_flat encoders beside their branchy twins) are the partner's functions, rdrf_bwd_mlp_dev.hpp;
+// the kernels here keep their own stores (buffer stores, where the partner has plain ones: the one-basic-block rule below).
 // The family's design.  A backward-data kernel writes each layer's dz as rows only for k_dw3 to read them back, together with
 // the activation rows the data kernel had just loaded.  Here the wave that owns a 32-sample tile keeps going: the data gradient
 // runs the calls of the partner kernel on the same values (its outputs keep their bits), and after each 64-row layer the wave
@@ -28,7 +31,7 @@
 //     own): left free, hipcc gathers the LDS reads of every block in front of the first product and spills.
 // Row contract (head of rdrf_dw.hip): a lane past N * S stages dz = 0 behind finite activations (0 x finite = 0); tiles past
 // ceil(N * S / 32) are never read; every stage row that is read was written by the same wave for the same tile.
-#include "rdrf_bwd_dev.hpp"
+#include "rdrf_bwd_mlp_dev.hpp"
 #include "rdrf_bwd_host.hpp"
 
 RDRF_DET_UNIT(bwd_fused)
@@ -164,23 +167,6 @@ constexpr int NSM = 18;                                             // 6-output 
 constexpr int LDS = pkb::SF_SIZE + FUSED_WAVES * ST_SIZE;
 static_assert(fused_red_floats(NPROD, NDZ, NSM) <= LDS && LDS * 4 <= 160 * 1024, "the cross-wave sum reuses the kernel's LDS");
 }  // namespace sfd
-// sf_x_bwd (rdrf_bwd.hip) without a branch (see the head comment): every lane runs the pair path of every octet -- where
-// sf_x_bwd skips it (h == 0 in octet 0: pair -2 / -1; pairs 12 ..) nothing is selected and 0.f is added -- and the lanes h == 0
-// add dX[0..2] first, as there.  The same values in the same order, plus additions of 0.f.
-RDRF_D void sf_x_bwd_flat(const float (&X)[20], const float (&dX)[20], int h, float& d0, float& d1, float& d2) {
-  d0 += h == 0 ? dX[0] : 0.f; d1 += h == 0 ? dX[1] : 0.f; d2 += h == 0 ? dX[2] : 0.f;
-#pragma unroll
-  for (int o = 0; o < 5; ++o) {
-    const int k = 2 * o + h - 1;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int pr = 2 * k + p;
-      const int d = (pr >= 0 && pr < 12) ? pr >> 2 : -1, f = pr & 3;
-      const float dq = ldexpf(dX[o * 4 + 2 * p] * X[o * 4 + 2 * p + 1] - dX[o * 4 + 2 * p + 1] * X[o * 4 + 2 * p], f);
-      d0 += d == 0 ? dq : 0.f; d1 += d == 1 ? dq : 0.f; d2 += d == 2 ? dq : 0.f;
-    }
-  }
-}
 template <bool PTS>   // PTS: the caller takes the point gradient (g_pts); without it the first layer's data product is skipped
 __global__ __launch_bounds__(64 * FUSED_WAVES) void k_scene_flow_bwd_dw(int N, int S, Box box,
                                                         const float* __restrict__ pkg,
@@ -248,8 +234,7 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_scene_flow_bwd_dw(int N, i
     mfma_seg<2, 32>(acc, dz, lds + pkb::SF_W4T, lane);
     load_rows<32>(svb, sv::SF_H2, Hh, s, h);
     dzs_layer<2, 2, 0, 0>(accW, bsum, st, pos, b0, b1, b1);   // sfw[2]: dz4 x H2
-#pragma unroll
-    for (int kk = 0; kk < 32; ++kk) dz[kk] = Hh[kk] > 0.f ? acc[kk >> 4][kk & 15] : 0.f;
+    relu_gate<32>(dz, Hh, acc);
     dzs_wave_sync();
     dzs_write(st, dz, pos);
     dzs_wave_sync();
@@ -259,8 +244,7 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_scene_flow_bwd_dw(int N, i
     mfma_seg<2, 32>(acc, dz, lds + pkb::SF_W2T, lane);
     load_rows<32>(svb, sv::SF_H0, Hh, s, h);
     dzs_layer<2, 2, 4, 2>(accW, bsum, st, pos, b0, b1, b1);   // sfw[1]: dz2 x H0
-#pragma unroll
-    for (int kk = 0; kk < 32; ++kk) dz[kk] = Hh[kk] > 0.f ? acc[kk >> 4][kk & 15] : 0.f;
+    relu_gate<32>(dz, Hh, acc);
     dzs_wave_sync();
     dzs_write(st, dz, pos);
     dzs_wave_sync();
@@ -337,23 +321,6 @@ constexpr int LDS = pkb::K1W_SIZE + FUSED_WAVES * DZS_FLOATS;
 static_assert(pkb::K1W_SIZE % 4 == 0 && fused_red_floats(NPROD, NDZ, NSM) <= LDS && LDS * 4 <= 160 * 1024,
               "the stages are 16-byte aligned; the cross-wave sum reuses the kernel's LDS");
 }  // namespace wpd
-// x0_bwd (rdrf_bwd.hip) without the branch on the lane half, as sf_x_bwd_flat (no contraction: see x0_bwd)
-RDRF_D void x0_bwd_flat(const float (&X0)[32], const float (&dX0)[32], int h, float& d0, float& d1, float& d2) {
-#pragma clang fp contract(off)
-  d0 += h == 0 ? dX0[0] : 0.f; d1 += h == 0 ? dX0[1] : 0.f; d2 += h == 0 ? dX0[2] : 0.f;
-#pragma unroll
-  for (int o = 0; o < 8; ++o) {
-    const int k = 2 * o + h - 1;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const int j = 2 * k + p;
-      const int d = j >= 0 ? j / 10 : -1, f = j >= 0 ? j - d * 10 : 0;
-      const float sv = X0[o * 4 + 2 * p], cv = X0[o * 4 + 2 * p + 1];
-      const float dq = ldexpf(dX0[o * 4 + 2 * p] * cv - dX0[o * 4 + 2 * p + 1] * sv, f);
-      d0 += d == 0 ? dq : 0.f; d1 += d == 1 ? dq : 0.f; d2 += d == 2 ? dq : 0.f;
-    }
-  }
-}
 template <bool GX>   // GX: the caller takes g_xyz
 __global__ __launch_bounds__(64 * FUSED_WAVES) void k_dyn_warp_bwd_dw(BwdArgs a, DynG gw, WarpGrads G) {
   __shared__ __attribute__((aligned(16))) float lds[wpd::LDS];
@@ -375,49 +342,9 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_dyn_warp_bwd_dw(BwdArgs a,
     const int idx = act ? n * 32 + s : 0;
     const float* svb = a.sp.act1 + (size_t)n * sv::K1_ROWS * 32;
     float* gb = a.grows1 + (size_t)n * sv::K1G_ROWS * 32;
-    float dw0 = act ? a.dxw_app[(size_t)idx * 3 + 0] : 0.f, dw1 = act ? a.dxw_app[(size_t)idx * 3 + 1] : 0.f,
-          dw2 = act ? a.dxw_app[(size_t)idx * 3 + 2] : 0.f;
-    float dn0 = act ? a.dxn_app[(size_t)idx * 3 + 0] : 0.f, dn1 = act ? a.dxn_app[(size_t)idx * 3 + 1] : 0.f,
-          dn2 = act ? a.dxn_app[(size_t)idx * 3 + 2] : 0.f;
-    float dd0 = dw0 * a.box.inv[0], dd1 = dw1 * a.box.inv[1], dd2 = dw2 * a.box.inv[2];
-    float gp0 = 0.f, gp1 = 0.f, gp2 = 0.f;
-    if (act && a.g_xyz_prime) {
-      gp0 = a.g_xyz_prime[(size_t)idx * 3 + 0]; gp1 = a.g_xyz_prime[(size_t)idx * 3 + 1];
-      gp2 = a.g_xyz_prime[(size_t)idx * 3 + 2];
-    }
-    dd0 += gp0; dd1 += gp1; dd2 += gp2;
-    if (!act) { dd0 = dd1 = dd2 = 0.f; }
-    if (h == 0) {
-      gb[(size_t)(sv::K1G_SM + 0) * 32 + s] = dd0; gb[(size_t)(sv::K1G_SM + 1) * 32 + s] = dd1;
-      gb[(size_t)(sv::K1G_SM + 2) * 32 + s] = dd2;
-    }
+    WarpIn g = warp_coord_grads(a, gb, act, idx, s, h);
     float dz4[32];
-    {
-      float H4[32];
-      load_rows<32>(svb, sv::K1_H4, H4, s, h);
-      const float* w5 = lds + pkb::K1W_W5 + h * 32;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const f32x4 wa = *reinterpret_cast<const f32x4*>(w5 + 4 * q);
-        const f32x4 wb = *reinterpret_cast<const f32x4*>(w5 + 64 + 4 * q);
-        const f32x4 wc = *reinterpret_cast<const f32x4*>(w5 + 128 + 4 * q);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float d = wa[c] * dd0 + wb[c] * dd1 + wc[c] * dd2;
-          dz4[4 * q + c] = H4[4 * q + c] > 0.f ? d : 0.f;
-        }
-      }
-      sb[0] += dd0; sb[1] += dd1; sb[2] += dd2;
-#pragma unroll 1
-      for (int o = 0; o < 3; ++o) {   // one row at a time: the three butterflies unrolled together spill
-        const float dd = o == 0 ? dd0 : (o == 1 ? dd1 : dd2);
-        float pw[32];
-#pragma unroll
-        for (int kk = 0; kk < 32; ++kk) pw[kk] = dd * H4[kk];
-        const float r = reduce_scatter32(pw, s);
-        sw[0] += o == 0 ? r : 0.f; sw[1] += o == 1 ? r : 0.f; sw[2] += o == 2 ? r : 0.f;
-      }
-    }
+    warp_layer5_bwd(dz4, lds, svb, g, true, s, h, sw, sb);
     // ---- one basic block from here to the end of the pass
     f32x4 b0[4], b1[4], b2[4];
     dzs_wave_sync();   // the previous tile's reads of the stage are done
@@ -428,17 +355,11 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_dyn_warp_bwd_dw(BwdArgs a,
     float dz3[32];
     {
       f32x16 acc[2];
-      acc_zero<2>(acc);
-#ifdef RDRF_HEADS_BWD_F32
-      mfma_seg<2, 32>(acc, dz4, lds + pkb::K1W_W4T, lane);
-#else
-      mfma_seg_b3<2, 32>(acc, dz4, lds + pkb::K1W_W4T, lane);
-#endif
+      warp_layer4_bwd(acc, dz4, lds, lane);
       float H3[32];
       load_rows<32>(svb, sv::K1_H3, H3, s, h);
       dzs_layer<2, 2, 0, 0>(accW, bsum, st, pos, b0, b1, b1);   // layer4: dz4 x H3
-#pragma unroll
-      for (int kk = 0; kk < 32; ++kk) dz3[kk] = H3[kk] > 0.f ? acc[kk >> 4][kk & 15] : 0.f;
+      relu_gate<32>(dz3, H3, acc);
     }
     dzs_wave_sync();
     dzs_write(st, dz3, pos);
@@ -446,54 +367,36 @@ __global__ __launch_bounds__(64 * FUSED_WAVES) void k_dyn_warp_bwd_dw(BwdArgs a,
     row16_load(b0, svb, sv::K1_X0 + s, h);
     row16_load(b1, svb, sv::K1_X0 + 32 + s, h);
     row16_load(b2, svb, sv::K1_T + s, h);
-    f32x16 accX[2];  // d(X0): heads (from rows) + warp layer 3
+    f32x16 accX[2], accT[1];
     {
       float dXh[32];
       load_rows<32>(gb, sv::K1G_DX0, dXh, s, h);
 #pragma unroll
       for (int kk = 0; kk < 32; ++kk) accX[kk >> 4][kk & 15] = dXh[kk];
     }
-    f32x16 accT[1];
-    acc_zero<1>(accT);
-#ifdef RDRF_HEADS_BWD_F32
-    mfma_seg<2, 32>(accX, dz3, lds + pkb::K1W_W3T_X0, lane);
-    mfma_seg<1, 32>(accT, dz3, lds + pkb::K1W_W3T_T, lane);
-#else
-    mfma_seg_b3_pair<2, 1, 32>(accX, accT, dz3, lds + pkb::K1W_W3T_X0, lds + pkb::K1W_W3T_T, lane);
-#endif
+    warp_layer3_bwd(accX, accT, dz3, lds, lane);
     dzs_layer<2, 3, 4, 2>(accW, bsum, st, pos, b0, b1, b2);   // layer3: dz3 x [X0 | T]
-    {
-      float X0[32], dX0[32];
-      load_rows<32>(svb, sv::K1_X0, X0, s, h);
-      acc_copy<2>(dX0, accX);
-      float e0 = 0.f, e1 = 0.f, e2 = 0.f;
-      x0_bwd_flat(X0, dX0, h, e0, e1, e2);
-      e0 += __shfl_xor(e0, 32, 64); e1 += __shfl_xor(e1, 32, 64); e2 += __shfl_xor(e2, 32, 64);
-      dn0 += e0 + dw0; dn1 += e1 + dw1; dn2 += e2 + dw2;
-    }
+    warp_x0_bwd<true>(g, accX, svb, s, h);
     if constexpr (GX)
-      tile_add3(a.g_xyz + (size_t)n * 96, act && h == 0, s, dn0 * a.box.inv[0] + gp0, dn1 * a.box.inv[1] + gp1, dn2 * a.box.inv[2] + gp2);
+      tile_add3(a.g_xyz + (size_t)n * 96, act && h == 0, s, g.dn0 * a.box.inv[0] + g.gp0, g.dn1 * a.box.inv[1] + g.gp1, g.dn2 * a.box.inv[2] + g.gp2);
     {
-      // d(tout) of the tile's rays, as k_dyn_density_bwd<1, false, true>: segmented suffix sums over the lanes of each half; the
-      // first lane of a segment stores -- to dtout (ray inside the tile: a buffer over the tile's rays) or to one of the tile's two
-      // partial records in dtp (a buffer over the tile's 256 bytes); the other lanes and the other buffer: out of range
-      const int i0 = n * 32 + s, nl = i0 / a.S, nl0 = (n * 32) / a.S;
-      const int rb = nl * a.S - n * 32, re = rb + a.S - 1;
-      const int end = re < 31 ? re : 31;
-      const bool head = i0 < total && (s == 0 || rb == s);
-      const bool inside = rb >= 0 && re <= 31;
+      // d(tout) of the tile's rays, as k_dyn_density_bwd<1, false, true> (dtout_segments); the first lane of a segment stores -- to
+      // dtout (ray inside the tile: a buffer over the tile's rays) or to one of the tile's two partial records in dtp (a buffer
+      // over the tile's 256 bytes); the other lanes and the other buffer: out of range
+      const DtoutSeg sg = dtout_segments(a, n, s);
+      const int nl0 = (n * 32) / a.S;
       const int nrays = a.N - nl0 < 32 ? a.N - nl0 : 32;
       const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc((void*)(a.dtout + (size_t)nl0 * 32), 0, nrays * 128, 0x00020000);
       const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc((void*)(a.dtp + (size_t)n * 64), 0, 256, 0x00020000);
-      const int offt = (head && inside) ? (nl - nl0) * 128 + h * 16 : 1 << 20;
-      const int offq = (head && !inside) ? (s == 0 ? 0 : 128) + h * 16 : 1 << 20;
+      const int offt = (sg.head && sg.inside) ? (sg.nl - nl0) * 128 + h * 16 : 1 << 20;
+      const int offq = (sg.head && !sg.inside) ? (s == 0 ? 0 : 128) + h * 16 : 1 << 20;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         float v = 0.f + accT[0][i];   // (dTacc of the other kernel: 0.f + the tile's product)
 #pragma unroll
         for (int d = 1; d < 32; d <<= 1) {
           const float o = __shfl_down(v, d, 32);
-          v += s + d <= end ? o : 0.f;
+          v += s + d <= sg.end ? o : 0.f;
         }
         const int eo = (8 * (i >> 2) + (i & 3)) * 4;   // elem_of(i, h) = 8 (i >> 2) + 4 h + (i & 3)
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rt, offt, eo, 0);

@@ -398,17 +398,15 @@ def test_fused_grad_accumulation_matches_autograd():
         assert all(float(p.grad.abs().max()) == 0.0 for p in m._param_list())
 
 
-@pytest.mark.parametrize("rt", ["ndc", "contract"])
-def test_z_vals_gradient_matches_oracle(rt):
-    """d(loss)/d(z_vals): z enters the fields through dists = (z[j+1]-z[j]) |d| scale (-> alpha, weight,
-    the returned dists) and the compositor through the depth maps; no reference loss uses it, but
-    autograd must reach it (SURVEY 8b).  Compared with the oracle's autograd."""
+def z_vals_gradient_check(rt, N, S, ray_seed=21):
+    """body of test_z_vals_gradient_matches_oracle for N rays of S samples (also run at the tile edges of the ray scans by
+    tests/test_gpu_ray_scan_bwd_edges.py)"""
     import rodynrf
     from _gpu_util import COMMON, make_rays, oracle_cfg, oracle_sd
     from oracle import rodynrf_oracle as O
     torch.manual_seed(11)
     contract = rt == "contract"
-    N, S, grid = 40, 45, [24, 26, 16]
+    grid = [24, 26, 16]
     aabb = torch.tensor([[-2.0, -2.0, -2.0], [2.0, 2.0, 2.0]] if contract else [[-1.5, -1.67, -1.0], [1.5, 1.67, 1.0]])
     nf = [0.05, 256.0] if contract else [0.0, 1.0]
     kw = dict(COMMON, near_far=nf, density_shift=-1.0 if contract else -10.0,
@@ -416,7 +414,7 @@ def test_z_vals_gradient_matches_oracle(rt):
     st = rodynrf.TensorVMSplit(aabb, grid, 12, "cuda", shadingMode="MLP_Fea", fea_pe=2, **kw)
     dy = rodynrf.TensorVMSplit_TimeEmbedding(aabb, grid, 12, "cuda", shadingMode="MLP_Fea_late_view",
                                              fea_pe=0, **kw)
-    rays, ts = make_rays(N, 21, rt)
+    rays, ts = make_rays(N, ray_seed, rt)
     xyz, z0, valid = O.sampleXYZ(rays, aabb, nf, S, rt, None, None)
     gl = torch.Generator().manual_seed(3)
     w_dep, w_w = torch.rand(N, generator=gl), torch.rand(N, S, generator=gl)
@@ -443,6 +441,14 @@ def test_z_vals_gradient_matches_oracle(rt):
     gg, = torch.autograd.grad(Lg, zg)
     assert float(gref.abs().max()) > 0
     assert_close(gg, gref, "d loss / d z_vals", rtol=1e-4)
+
+
+@pytest.mark.parametrize("rt", ["ndc", "contract"])
+def test_z_vals_gradient_matches_oracle(rt):
+    """d(loss)/d(z_vals): z enters the fields through dists = (z[j+1]-z[j]) |d| scale (-> alpha, weight,
+    the returned dists) and the compositor through the depth maps; no reference loss uses it, but
+    autograd must reach it (SURVEY 8b).  Compared with the oracle's autograd."""
+    z_vals_gradient_check(rt, 40, 45)
 
 
 def test_sorted_scatter_passes_the_same_parity_tests():
