@@ -303,6 +303,7 @@ struct CompBArgs {
 
 struct CompSample {
   float ad, as, b, di, zz, pd, ps, pf, Td, Ts, Tf, sd, ss;
+  float ed, es;   // exp(-sigma dist) = d alpha / d(sigma dist): NOT 1 - alpha, which is 0 once alpha rounds to 1
   float cd[3], cs[3];
 };
 
@@ -312,8 +313,9 @@ RDRF_D CompSample comp_load(const CompBArgs& a, int n, int j, int lane, float& c
   const size_t idx = (size_t)n * a.S + (act ? j : 0);
   q.di = a.dists[idx]; q.b = a.blending[idx]; q.zz = a.z[idx];
   q.sd = a.sigma_d[idx]; q.ss = a.sigma_s[idx];
-  q.ad = act ? alpha_of(q.sd, q.di) : 0.f;
-  q.as = act ? alpha_of(q.ss, q.di) : 0.f;
+  q.ed = expf(-q.sd * q.di); q.es = expf(-q.ss * q.di);
+  q.ad = act ? 1.0f - q.ed : 0.f;   // alpha_of
+  q.as = act ? 1.0f - q.es : 0.f;
   q.pd = act ? one_minus_alpha_eps(q.ad) : 1.f;
   q.ps = act ? one_minus_alpha_eps(q.as) : 1.f;
   q.pf = act ? tfull_factor(q.ad, q.as, q.b) : 1.f;
@@ -446,9 +448,9 @@ __global__ __launch_bounds__(64) void k_composite_bwd(CompBArgs a) {
         g_as += g_cfs * (1.0f - q.b) - g_pf * uu * (1.0f - q.b);
         const float g_b = Gdyn * wf + g_cfd * q.ad - g_cfs * q.as + g_pf * (-q.ad * vv + uu * q.as);
         const float wdn = u / Ue;
-        if (a.gi[1]) a.gi[1][idx] += g_as * q.di * (1.0f - q.as);
-        if (a.gi[3]) a.gi[3][idx] += g_ad * q.di * (1.0f - q.ad);
-        if (a.gi[4]) a.gi[4][idx] += g_ad * q.sd * (1.0f - q.ad) + g_as * q.ss * (1.0f - q.as);
+        if (a.gi[1]) a.gi[1][idx] += g_as * q.di * q.es;
+        if (a.gi[3]) a.gi[3][idx] += g_ad * q.di * q.ed;
+        if (a.gi[4]) a.gi[4][idx] += g_ad * q.sd * q.ed + g_as * q.ss * q.es;
         if (a.gi[5]) a.gi[5][idx] += g_b;
         if (a.gi[6]) a.gi[6][idx] += Gdep_d * wdn + Gdep_s * ws + Gdep_f * wf;
         for (int c = 0; c < 3; ++c) {

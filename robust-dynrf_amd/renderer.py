@@ -171,6 +171,10 @@ class _CompositeFn(torch.autograd.Function):
         # on it, so a loss on depth_map_d / weights_d alone (passes B-D of the trainer) sends the blending head NO
         # gradient -- and the field's backward then leaves that head, its scatter set and its dW products out
         need[5] = need[5] and have((0, 1, 2, 3, 12))
+        # z_vals only enters the three depth maps (renderer.py:283-285), the rays only their NDC far-plane term
+        # (renderer.py:287-291): without a depth cotangent -- or, for the rays, outside NDC -- autograd gives them NO gradient
+        need[6] = need[6] and have((1, 5, 9))
+        need[7] = need[7] and ctx.ray_type == "ndc" and have((1, 5, 9))
         g_in = L.zeros_like_many(ins, need)   # one fill for the (up to eight) gradient tensors
         ga = (C.c_void_p * 13)(*[0 if g is None else g.data_ptr() for g in g_out])
         gi = (C.c_void_p * 8)(*[0 if g is None else g.data_ptr() for g in g_in])
