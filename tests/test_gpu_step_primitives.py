@@ -1,0 +1,409 @@
+"""The kernels that run once per iteration next to the ray path, on inputs of their own, against the float64 references of
+tests/_step_prim.py: k_adam, k_upsample, k_dense_l1 (csrc/rdrf_optim.hip), k_loss_* and k_frame_depth_loss (csrc/rdrf_loss.hip),
+k_distloss*, k_tv_*, k_rows_scatter_add (csrc/rdrf_misc.hip).  Through the trainer's entries (LossTerms with a fake reducer,
+frame_depth_loss, flatten_eff_distloss, TVLoss and accumulate_grad_, gather_rows) and, where the edge is only reachable there
+(pre-filled accumulators, split, step, the two-stage loss statistics, out-of-range indices, arbitrary strides), through the C ABI.
+
+Bound of EVERY comparison (derived per family in tests/_step_prim.py from the kernel's own operation count):
+    |err| <= k 2^-24 (condition scale) [+ half an ulp of a stored result],  element by element
+and torch.equal for the exact cases (integer scatter, identity resize, zero Adam update, zero gradients).  The float32 torch /
+oracle evaluation meets the same bounds on the same cases (test_step_primitives_cpu.py); profiles/step_kernels_margins.txt
+holds both sets of ratios and the fault table."""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+import _step_prim as P
+from _util import record_margin
+
+pytestmark = pytest.mark.gpu
+
+
+def _L():
+    return importlib.import_module("robust-dynrf_amd._lib")
+
+
+def _cu(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _check(got, ref, cond, k, tag, extra=0.0):
+    ratio = P.error_ratio(got, ref, cond, k, extra)
+    record_margin(tag, ratio)
+    assert ratio <= 1.0, f"{tag}: |err| is {ratio:.3f} x (k 2^-24 cond + half ulp), k = {k}"
+
+
+# ---- Adam -------------------------------------------------------------------------------------------------------------------
+def _adam_gpu(p, g, m, v, split, step, gs):
+    L = _L()
+    h = P.ADAM_HYPER
+    tp, tg, tm, tv = _cu(p), _cu(g), _cu(m), _cu(v)
+    L.check(L.lib.rdrf_adam_step(L.ptr(tp), L.ptr(tg), L.ptr(tm), L.ptr(tv), C.c_size_t(p.size), C.c_size_t(split), h["lr0"], h["lr1"],
+                                 h["beta1"], h["beta2"], h["eps"], step, gs, L.stream_of(tp)), "adam")
+    return tp.cpu().numpy(), tm.cpu().numpy(), tv.cpu().numpy()
+
+
+def _adam_check(p, g, m, v, z, split, step, gs, tag):
+    r = P.adam_ref(p, g, m, v, split, step, gs, **P.ADAM_HYPER)
+    p1, m1, v1 = _adam_gpu(p, g, m, v, split, step, gs)
+    _check(m1, r["m"], r["cond_m"], P.K_ADAM_M, tag + " m")
+    _check(v1, r["v"], r["cond_v"], P.K_ADAM_V, tag + " v")
+    _check(P.f64(p1) - P.f64(p), r["upd"], r["cond_upd"], P.K_ADAM_UPD, tag + " update", P.half_ulp(r["p"]))
+    assert np.array_equal(p1[z], p[z]) and not m1[z].any() and not v1[z].any(), f"{tag}: g = m = v = 0 must leave p, m, v untouched"
+    return p1, m1, v1
+
+
+@pytest.mark.parametrize("state", ["zero", "warm"])
+def test_adam_single_steps_match_float64(state):
+    """m', v' and the UPDATE p' - p (not p against max|p|) for step 1 / 2 / 1000, grad_scale 1 / 0.5, split 0 / 4 / n - 4 / n"""
+    for n in P.ADAM_SIZES[:2]:
+        for step in (1, 2, 1000):
+            for gs in (1.0, 0.5):
+                for split in P.adam_splits(n):
+                    p, g, m, v, z = P.adam_inputs(n, step, state)
+                    _adam_check(p, g, m, v, z, split, step, gs, f"adam n={n} {state} step={step} gs={gs} split={split}")
+
+
+def test_adam_grid_stride_loop_matches_float64():
+    n = P.ADAM_SIZES[2]
+    p, g, m, v, z = P.adam_inputs(n, 3, "warm")
+    _adam_check(p, g, m, v, z, P.ADAM_GRID + 4, 2, 0.5, f"adam n={n} warm step=2")   # the split lies in the second pass of the loop
+
+
+def test_adam_seven_chained_steps_match_float64():
+    n, split = 1028, 512
+    p, _, m, v, z = P.adam_inputs(n, 0)
+    for step in range(1, 8):
+        g = P.adam_inputs(n, 100 + step)[1]
+        p, m, v = _adam_check(p, g, m, v, z, split, step, 0.5, f"adam chained step={step}")
+
+
+# ---- loss terms -------------------------------------------------------------------------------------------------------------
+def _terms(reducer=None):
+    return importlib.import_module("robust-dynrf_amd.losses").LossTerms(reducer)
+
+
+LOSS_COMBOS = (("plain", "mean", False, -1.0), ("plain", "mean", True, 1.0), ("plain", "weight", True, -1.0),
+               ("zero_w", "weight", True, -1.0), ("tie", "mean", True, -1.0))
+
+
+@pytest.mark.parametrize("shape", P.LOSS_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_loss_terms_match_float64(shape):
+    """one LossTerms group per (regime, normaliser): the three rho as three terms; value, per-term values, gradients with
+    only x, only y, or both requiring one"""
+    rows, cols = shape
+    for ci, (regime, norm, use_w, ysign) in enumerate(LOSS_COMBOS):
+        x, y, w = P.loss_inputs(rows, cols, 0, regime)
+        need = (("x", "y"), ("x",), ("y",))[ci % 3]
+        tx, ty = _cu(x).requires_grad_("x" in need), _cu(y).requires_grad_("y" in need)
+        T = _terms()
+        refs = []
+        for j, kind in enumerate(P.LOSS_KINDS):
+            coef = 0.7 + 0.3 * j
+            T.add(coef, kind, tx, ty, ysign=ysign, w=_cu(w) if use_w else None, norm=norm)
+            refs.append(P.loss_ref(kind, norm, x, y, ysign, w if use_w else None, coef=coef))
+        loss = T.total()
+        (loss * 1.7).backward()
+        tag = f"loss {rows}x{cols} {regime} {norm} w={use_w}"
+        k = P.k_loss(rows * cols)
+        for j, r in enumerate(refs):
+            _check(T.values[j], r["value"], r["cond"], k, f"{tag} term {P.LOSS_KINDS[j]}")
+        _check(loss, sum(r["value"] for r in refs), sum(r["cond"] for r in refs), k + 3, tag + " total")
+        kg = P.k_loss_grad(rows * cols) + 3          # + the sum of the three terms' gradients (autograd) and the factor 1.7
+        for t, key in ((tx, "gx"), (ty, "gy")):
+            if key[1] in need:
+                _check(t.grad, 1.7 * sum(r[key] for r in refs), 1.7 * sum(np.abs(r[key]) for r in refs), kg, f"{tag} {key}")
+            else:
+                assert t.grad is None
+        if regime == "tie":   # residual exactly 0: square and abs give exactly 0, value and gradient
+            assert float(T.values[0]) == 0.0 and float(T.values[1]) == 0.0
+            T2 = _terms()
+            t2 = _cu(x).requires_grad_(True)
+            T2.add(1.0, "abs", t2, _cu(y), w=_cu(w)).total().backward()
+            assert not bool(t2.grad.any()), "d|r| at r == 0 is 0"
+
+
+def test_loss_terms_device_coefficient_and_shared_tensor():
+    x, y, w = P.loss_inputs(777, 111, 2)
+    tx, ty = _cu(x).requires_grad_(True), _cu(y).requires_grad_(True)
+    cdev = torch.tensor([0.37], device="cuda")
+    T = _terms()
+    T.add((2.0, cdev), "square", tx, ty, w=_cu(w), norm="weight")
+    T.add(0.5, "abs", tx, None)                                     # the same tensor in a second term, no y
+    T.add(1.0, "identity", ty, tx, ysign=1.0)
+    loss = T.total()
+    loss.backward()
+    c0 = 2.0 * float(np.float32(0.37))
+    r = [P.loss_ref("square", "weight", x, y, -1.0, w, coef=c0), P.loss_ref("abs", "mean", x, None, coef=0.5),
+         P.loss_ref("identity", "mean", y, x, 1.0, None, coef=1.0)]
+    k, kg = P.k_loss(x.size) + 3, P.k_loss_grad(x.size) + 3
+    _check(loss, sum(a["value"] for a in r), sum(a["cond"] for a in r), k, "loss coef_dev + shared total")
+    _check(tx.grad, r[0]["gx"] + r[1]["gx"] + r[2]["gy"], sum(np.abs(a) for a in (r[0]["gx"], r[1]["gx"], r[2]["gy"])), kg, "loss shared gx")
+    _check(ty.grad, r[0]["gy"] + r[2]["gx"], np.abs(r[0]["gy"]) + np.abs(r[2]["gx"]), kg, "loss shared gy")
+
+
+@pytest.mark.parametrize("norm", ["mean", "weight"])
+def test_loss_terms_two_rank_statistics_recombine(norm):
+    """the data-parallel path in one process: rdrf_loss_terms_stats on each half, the statistics added, rdrf_loss_terms_finish
+    with world = 2 on each half (LossTerms with a fake reducer).  The mean of the two losses is the float64 single-batch loss and
+    each half's gradient / world the matching slice of the single-batch gradient."""
+    rows, cols, h = 778, 3, 389
+    x, y, w = P.loss_inputs(rows, cols, 1)
+    w[:h] *= 0.25                                                    # unequal weight sums on the two ranks
+    halves = (slice(0, h), slice(h, None))
+    stats, held = [], []
+
+    def build(s, reducer):
+        tx = _cu(x[s]).requires_grad_(True)
+        T = _terms(reducer)
+        for kind in P.LOSS_KINDS:
+            T.add(1.3, kind, tx, _cu(y[s]), w=_cu(w[s]), norm=norm)
+        return T, tx
+    for s in halves:   # first pass: collect each rank's statistics
+        T, _ = build(s, lambda st: (stats.append(st.clone()) or st, 1))
+        T.total()
+    glob = stats[0] + stats[1]
+    for i, s in enumerate(halves):
+        for j, kind in enumerate(P.LOSS_KINDS):
+            sm, ws, sa = P.loss_stats(kind, x[s], y[s], -1.0, w[s])
+            _check(stats[i][2 * j], sm, sa, P.k_loss(rows * cols), f"loss stats rank {i} {kind} sum")
+            if norm == "weight":
+                _check(stats[i][2 * j + 1], ws, ws, P.k_loss(rows * cols), f"loss stats rank {i} {kind} weight sum")
+    for s in halves:
+        T, tx = build(s, lambda st: (glob, 2))
+        loss = T.total()
+        loss.backward()
+        held.append((loss, tx.grad, T.values.clone()))
+    whole = [P.loss_ref(kind, norm, x, y, -1.0, w, coef=1.3) for kind in P.LOSS_KINDS]
+    k = P.k_loss(rows * cols) + 3
+    for j, r in enumerate(whole):
+        mean = 0.5 * (P.f64(held[0][2][j]) + P.f64(held[1][2][j]))
+        _check(mean, r["value"], r["cond"], k, f"loss two-rank {norm} {P.LOSS_KINDS[j]}")
+    _check(0.5 * (P.f64(held[0][0]) + P.f64(held[1][0])), sum(r["value"] for r in whole), sum(r["cond"] for r in whole), k,
+           f"loss two-rank {norm} total")
+    got = np.concatenate([P.f64(held[0][1]), P.f64(held[1][1])]) / 2
+    _check(got, sum(r["gx"] for r in whole), sum(np.abs(r["gx"]) for r in whole), P.k_loss_grad(rows * cols) + 3, f"loss two-rank {norm} gx")
+
+
+# ---- frame depth loss ----------------------------------------------------------------------------------------------------------
+def _fdl(pred, gt, frame, T, mask, coef=0.04):
+    LS = importlib.import_module("robust-dynrf_amd.losses")
+    p = _cu(pred).requires_grad_(True)
+    loss = LS.frame_depth_loss(p, _cu(gt), _cu(frame), T, mask=None if mask is None else _cu(mask), coef=coef)
+    (loss * 1.7).backward()
+    return loss, p.grad
+
+
+@pytest.mark.parametrize("N", P.FDL_BATCHES)
+def test_frame_depth_loss_matches_float64(N):
+    for ties in (False, True):
+        for use_mask in (False, True):
+            pred, gt, frame, mask, T = P.fdl_inputs(N, 0, ties)
+            mk = mask if use_mask else None
+            r = P.fdl_ref(pred, gt, frame, T, mk, coef=0.04)
+            loss, g = _fdl(pred, gt, frame, T, mk)
+            tag = f"fdl N={N} ties={ties} mask={use_mask}"
+            _check(loss, r["value"], r["cond"], P.k_fdl(N, T), tag)
+            _check(g, 1.7 * r["grad"], 1.7 * r["gcond"], P.k_fdl_grad(N) + 1, tag + " grad")
+            dead = (frame < 0) | (frame >= T) | (frame == 1) | (False if mk is None else ~mk)
+            assert not bool(g.cpu()[torch.from_numpy(dead)].any()), f"{tag}: ids outside [0, T), single-ray frames, masked rays: exactly 0"
+
+
+def test_frame_depth_loss_every_frame_skipped_is_pinned():
+    """No frame holds two rays: the reference divides 0 by 0 and the oracle raises (int / float of an empty sum).  The kernel
+    returns coef * 0 / 0 = NaN for the loss, and the backward scales the zero raw gradient by coef / 0 = inf: NaN for every ray.
+    Outside the reference's domain: documented and pinned here, not defined by this test."""
+    N = 64
+    pred, gt = P.rng(9).standard_normal(N).astype(np.float32), P.rng(10).uniform(0, 1, N).astype(np.float32)
+    loss, g = _fdl(pred, gt, np.arange(N, dtype=np.int64), N, None)
+    assert bool(torch.isnan(loss)) and bool(torch.isnan(g).all())
+    assert np.isnan(P.fdl_ref(pred, gt, np.arange(N), N)["value"])
+
+
+# ---- distortion loss ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("S", P.DIST_SIZES)
+def test_distortion_loss_matches_float64(S):
+    """per ray through the C ABI (with g_w pre-filled: the backward accumulates), and the mean through flatten_eff_distloss"""
+    import rodynrf
+    L = _L()
+    w, m, iv = P.dist_inputs(S, 0)
+    N = w.shape[0]
+    pre = P.rng(11, S).standard_normal((N, S)).astype(np.float32)
+    g_ray = P.rng(12, S).uniform(0.5, 2, N).astype(np.float32)
+    for interval in (float(np.float32(1.0 / S)), iv):
+        per_pt = isinstance(interval, np.ndarray)
+        r = P.dist_ref(w, m, interval)
+        tw, tm, ti = _cu(w), _cu(m), (_cu(interval) if per_pt else None)
+        ray, gw, tgr = torch.empty(N, device="cuda"), _cu(pre), _cu(g_ray)
+        L.check(L.lib.rdrf_distloss_fwd(L.ptr(tw), L.ptr(tm), C.c_float(0.0 if per_pt else interval), L.ptr(ti), N, S, L.ptr(ray),
+                                        L.stream_of(tw)), "distloss_fwd")
+        L.check(L.lib.rdrf_distloss_bwd(L.ptr(tw), L.ptr(tm), C.c_float(0.0 if per_pt else interval), L.ptr(ti), N, S, L.ptr(tgr),
+                                        L.ptr(gw), L.stream_of(tw)), "distloss_bwd")
+        tag = f"distloss S={S} {'per-point' if per_pt else 'scalar'} interval"
+        _check(ray, r["ray"], r["cond"], P.k_dist(S), tag)
+        want = P.f64(pre) + P.f64(g_ray)[:, None] * r["grad"]
+        _check(gw, want, P.f64(g_ray)[:, None] * r["gcond"], P.k_dist_grad(S), tag + " g_w +=", P.half_ulp(want))
+        assert float(ray[0]) == 0.0 and torch.equal(gw[0], _cu(pre)[0]), "an all-zero ray: loss 0, g_w untouched"
+        wg = _cu(w).requires_grad_(True)
+        ray_id = torch.arange(N, device="cuda")[:, None].expand(N, S).reshape(-1)
+        got = rodynrf.flatten_eff_distloss(wg.reshape(-1), tm.reshape(-1), ti.reshape(-1) if per_pt else interval, ray_id)
+        got.backward()
+        _check(got, r["ray"].mean(), r["cond"].mean(), P.k_dist(S) + 5, tag + " mean")      # + the sum over 12 rays and / N
+        _check(wg.grad, r["grad"] / N, r["gcond"] / N, P.k_dist_grad(S) + 1, tag + " d mean / dw")
+
+
+# ---- TV -------------------------------------------------------------------------------------------------------------------------
+class _PlainField:
+    fused_grad = False
+
+
+@pytest.mark.parametrize("shape", P.TV_SHAPES, ids=str)
+def test_tv_matches_float64(shape):
+    """the two sums and their gradient through TVLoss (k_tv_fwd / k_tv_bwd), and the one-pass gradient through
+    TVLoss.accumulate_grad_ (k_tv_grad, quad and scalar paths) into PRE-FILLED gradients, in three storage orders"""
+    R = importlib.import_module("robust-dynrf_amd.regularizers")
+    L = _L()
+    C_, H, W = shape
+    x, pre = P.tv_inputs(C_, H, W, 0)
+    reg = R.TVLoss(1.0)
+    for layout in P.TV_LAYOUTS:
+        tag = f"tv {shape} {layout}"
+        t = P.tv_tensor(x, layout).cuda().requires_grad_(True)
+        sums = R._TVSumsFn.apply(None, t)
+        r1 = P.tv_ref(x, 0.37, 1.9)
+        _check(sums[0], r1["sums"], r1["sums"], P.k_tv_sum(C_, H, W), tag + " sums")
+        (sums * torch.tensor([0.37, 1.9], device="cuda")).sum().backward()
+        _check(t.grad[0], r1["grad"], r1["gcond"], P.K_TV_G + 2, tag + " d sums")
+        # rdrf_tv_bwd accumulates: the same call through the C ABI into a pre-filled buffer
+        g = P.tv_tensor(pre, layout).cuda()
+        arr, gsum = (L.RdrfTensor4 * 1)(R._tensor4(t.detach(), g)), torch.tensor([0.37, 1.9], device="cuda")
+        L.check(L.lib.rdrf_tv_bwd(arr, 1, L.ptr(gsum), L.stream_of(g)), "tv_bwd")
+        want = P.f64(pre) + r1["grad"]
+        _check(g[0], want, r1["gcond"], P.K_TV_G, tag + " tv_bwd +=", P.half_ulp(want))
+        # accumulate_grad_: the tensor as a "plane" (family coefficient 1e-2) of weight 0.8
+        p = P.tv_tensor(x, layout).cuda().requires_grad_(True)
+        p.grad = P.tv_tensor(pre, layout).cuda()
+        reg.accumulate_grad_(_PlainField(), [([p], [])], [0.8])
+        ch = 0.8 * 1e-2 * 2.0 / (C_ * (H - 1) * W) if H > 1 else 0.0
+        cw = 0.8 * 1e-2 * 2.0 / (C_ * H * (W - 1)) if W > 1 else 0.0
+        r2 = P.tv_ref(x, float(np.float32(ch)), float(np.float32(cw)))
+        want = P.f64(pre) + r2["grad"]
+        _check(p.grad[0], want, r2["gcond"], P.K_TV_G, tag + " tv_grad +=", P.half_ulp(want))
+        if H == 1 and W == 1:
+            assert torch.equal(p.grad[0].cpu(), torch.from_numpy(pre)) and float(sums.detach().abs().max()) == 0.0
+
+
+def test_tv_grad_more_tensors_than_one_launch_holds():
+    """20 tensors (RDRF_TV_MAX is 16) in one accumulate_grad_ call: the second launch's coefficients and tensors line up"""
+    R = importlib.import_module("robust-dynrf_amd.regularizers")
+    assert _L().TV_MAX == 16
+    planes, refs = [], []
+    for i in range(20):
+        C_, H, W = P.TV_SHAPES[3 + i % 4]
+        x, pre = P.tv_inputs(C_, H, W, 10 + i)
+        p = P.tv_tensor(x, P.TV_LAYOUTS[i % 3]).cuda().requires_grad_(True)
+        p.grad = P.tv_tensor(pre, P.TV_LAYOUTS[i % 3]).cuda()
+        planes.append(p)
+        ch = 1.5 * 1e-2 * 2.0 / (C_ * (H - 1) * W) if H > 1 else 0.0
+        cw = 1.5 * 1e-2 * 2.0 / (C_ * H * (W - 1)) if W > 1 else 0.0
+        refs.append((pre, P.tv_ref(x, float(np.float32(ch)), float(np.float32(cw)))))
+    R.TVLoss(1.0).accumulate_grad_(_PlainField(), [(planes, [])], [1.5])
+    for i, (p, (pre, r)) in enumerate(zip(planes, refs)):
+        want = P.f64(pre) + r["grad"]
+        _check(p.grad[0], want, r["gcond"], P.K_TV_G, f"tv_grad tensor {i} of 20", P.half_ulp(want))
+
+
+# ---- dense L1 -------------------------------------------------------------------------------------------------------------------
+def _cl(a):
+    """[C, A, B] -> (1, C, A, B) channel-last on the GPU; [C, L] -> (1, C, L, 1) stored [L][C]; the strides are the canonical
+    channel-last ones for extents of 1 too (torch leaves those unspecified)"""
+    t = torch.from_numpy(a).cuda()
+    if t.dim() == 2:
+        Cc, Ln = t.shape
+        return t.t().contiguous().as_strided((1, Cc, Ln, 1), (Cc * Ln, 1, Cc, 1))
+    Cc, A, B = t.shape
+    return t.permute(1, 2, 0).contiguous().as_strided((1, Cc, A, B), (Cc * A * B, 1, B * Cc, Cc))
+
+
+@pytest.mark.parametrize("grid", P.L1_GRIDS, ids=str)
+def test_dense_l1_matches_float64(grid):
+    """rdrf_dense_l1_fwd / bwd as density_L1 / blending_L1 call them (fields._vm_struct on channel-last factors), both
+    activations, normal and small-integer factors (f == 0 exactly under ReLU), gradients accumulated into pre-filled buffers"""
+    L = _L()
+    F = importlib.import_module("robust-dynrf_amd.fields")
+    X, Y, Z = grid
+    for act in ("relu", "softplus"):
+        for regime in ("normal", "integer"):
+            fs, pre = P.l1_inputs(grid, 0, regime)
+            r = P.l1_ref(fs, act, g=1.7)
+            ts, gs = [_cl(a) for a in fs], [_cl(a) for a in pre]
+            vm, gvm = F._vm_struct(ts[:3], ts[3:]), F._vm_struct(gs[:3], gs[3:])
+            out, gm = torch.empty(1, device="cuda"), torch.tensor([1.7], device="cuda")
+            if L.DETERMINISTIC:   # these buffers belong to no field: no fixed-point shadow may be bound over them
+                for slot in (0, 1):
+                    L.check(L.lib.rdrf_det_bind(slot, L.ptr(None), C.c_size_t(0), L.ptr(None), L.stream_of(out)), "det_bind")
+            L.check(L.lib.rdrf_dense_l1_fwd(C.byref(vm), L.ACTS[act], C.c_float(P.L1_SHIFT), L.ptr(out), L.stream_of(out)), "dense_l1_fwd")
+            L.check(L.lib.rdrf_dense_l1_bwd(C.byref(vm), C.byref(gvm), L.ACTS[act], C.c_float(P.L1_SHIFT), L.ptr(gm), L.stream_of(out)),
+                    "dense_l1_bwd")
+            tag = f"dense_l1 {grid} {act} {regime}"
+            _check(out[0] / (X * Y * Z), r["value"], r["cond"], P.k_l1(grid) + 1, tag)
+            for i in range(6):
+                want = P.f64(pre[i]) + r["grads"][i]
+                got = gs[i][0, :, :, 0] if i >= 3 else gs[i][0]
+                stores = P.l1_stores(grid)[i] * P.half_ulp(np.abs(P.f64(pre[i])) + r["gconds"][i])
+                _check(got, want, r["gconds"][i], P.k_l1(grid, True), f"{tag} g{i} +=", r["flips"][i] + stores)
+
+
+# ---- upsample -------------------------------------------------------------------------------------------------------------------
+def test_upsample_matches_float64_and_identity_is_bit_exact():
+    """rdrf_upsample_bilinear as up_sampling_VM calls it (regularizers._tensor4 on channel-last tensors), all size pairs of
+    both axes in launches of up to 16 tensors.  Pinned points (rounded source index integral on both axes, the exact product not
+    above it: every point of an identity resize, and row / column 121 of 157 -> 133, where the fused lambda falls below 0 and
+    only the clamp gives 0) are the source texel bit for bit."""
+    L = _L()
+    R = importlib.import_module("robust-dynrf_amd.regularizers")
+    jobs = []
+    for (hi, ho) in P.UP_PAIRS:
+        for (wi, wo) in P.UP_PAIRS:
+            x = P.rng(8, hi, wi).standard_normal((4, hi, wi)).astype(np.float32)
+            src = _cl(x)
+            dst = torch.full((1, ho, wo, 4), float("nan"), device="cuda").permute(0, 3, 1, 2)
+            jobs.append((x, src, dst, (hi, wi, ho, wo)))
+    for i0 in range(0, len(jobs), 16):
+        part = jobs[i0:i0 + 16]
+        sa = (L.RdrfTensor4 * len(part))(*[R._tensor4(j[1]) for j in part])
+        da = (L.RdrfTensor4 * len(part))(*[R._tensor4(j[2]) for j in part])
+        L.check(L.lib.rdrf_upsample_bilinear(sa, da, len(part), L.stream_of(part[0][1])), "upsample")
+    for x, src, dst, (hi, wi, ho, wo) in jobs:
+        r = P.up_ref(x, ho, wo)
+        _check(dst[0], r["out"], r["cond"], P.K_UP, f"upsample {hi}x{wi} -> {ho}x{wo}", r["lam"])
+        if (hi, wi) == (ho, wo):
+            assert torch.equal(dst, src), f"identity resize {hi}x{wi} is not bit-exact"
+        pin = torch.from_numpy(r["pin"])
+        assert torch.equal(dst[0].cpu()[:, pin], torch.from_numpy(r["src"].astype(np.float32))[:, pin]), \
+            f"upsample {hi}x{wi} -> {ho}x{wo}: a point with lambda 0 on both axes is not the source texel"
+        if (hi, ho) == (157, 133) and (wi == wo or wi == 1 or wo == 1):
+            assert bool(pin[121].all()), "row 121 of 157 -> 133 is pinned"
+
+
+# ---- rows_scatter_add -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", P.RSA_CASES, ids=str)
+def test_rows_scatter_add_is_exact(case):
+    """integer-valued gradients: exact in any order.  Through the C ABI with a pre-filled table and indices -1 / R (skipped:
+    torch refuses them in the forward gather), and through gather_rows' backward with the indices in range"""
+    L = _L()
+    RU = importlib.import_module("robust-dynrf_amd.ray_utils")
+    R_, C_, N = case
+    idx, g, pre = P.rsa_inputs(R_, C_, N, 0)
+    table, ti, tg = _cu(pre), _cu(idx), _cu(g)
+    L.check(L.lib.rdrf_rows_scatter_add(L.ptr(ti), L.ptr(tg), N, R_, C_, L.ptr(table), L.stream_of(table)), "rows_scatter_add")
+    assert torch.equal(table.cpu().double(), torch.from_numpy(P.rsa_ref(idx, g, pre))), f"{case}: C ABI, pre-filled, out-of-range ids"
+    idx, g, pre = P.rsa_inputs(R_, C_, N, 1, out_of_range=False)
+    t = _cu(pre).requires_grad_(True)
+    rows = RU.gather_rows(t, _cu(idx))
+    assert torch.equal(rows, t.detach()[_cu(idx)])
+    rows.backward(_cu(g))
+    assert torch.equal(t.grad.cpu().double(), torch.from_numpy(P.rsa_ref(idx, g, np.zeros_like(pre)))), f"{case}: gather_rows backward"
