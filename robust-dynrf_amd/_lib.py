@@ -114,6 +114,134 @@ class RdrfAlphaMask(C.Structure):   # include/rodynrf.h RdrfAlphaMask: a packed 
     _fields_ = [("bits", C.c_void_p), ("grid", C.c_int * 3), ("T", C.c_int), ("aabb", C.c_float * 6)]
 
 
+# Every function include/rodynrf.h declares, in header order: name -> (restype, argtypes).  This is the one place a C
+# signature is written down on the Python side; tests/test_abi_cpu.py holds it to the header's prototypes.  A pointer is
+# c_void_p (it takes byref(struct), ptr(tensor), None, a raw data_ptr() and ctypes arrays alike) unless callers hand in a
+# typed host pointer.
+i32, u32, f32, usz, i64, vp = C.c_int, C.c_uint, C.c_float, C.c_size_t, C.c_int64, C.c_void_p
+SIGNATURES = {
+    "rdrf_abi_version": (i32, []),
+    "rdrf_last_error": (C.c_char_p, []),
+    "rdrf_workspace_bytes": (usz, [i32, i32]),
+    "rdrf_forward_workspace_bytes": (usz, [i32, i32]),
+    "rdrf_saved_bytes": (usz, [i32, i32, i32]),
+    "rdrf_saved_bytes_ex": (usz, [i32, i32, i32, i32]),
+    "rdrf_saved_row_bytes": (usz, [i32]),
+    "rdrf_generate_rays": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp]),
+    "rdrf_generate_rays_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
+    "rdrf_generate_rays_uv": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp]),
+    "rdrf_generate_rays_uv_bwd": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
+    "rdrf_sample_ndc": (i32, [vp, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp]),
+    "rdrf_sample_contract": (i32, [vp, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp]),
+    "rdrf_sample_bwd": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
+    "rdrf_sample_world": (i32, [vp, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp, vp]),
+    "rdrf_sample_world_bwd": (i32, [vp, vp, i32, i32, f32, f32, vp, vp, vp, vp, vp]),
+    "rdrf_static_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, usz, vp, usz, vp]),
+    "rdrf_static_fwd_ex": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, usz, vp, usz, vp, i32]),
+    "rdrf_static_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, usz, vp, usz,
+                             vp]),
+    "rdrf_dynamic_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, usz, vp, usz, vp]),
+    "rdrf_dynamic_fwd_ex": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, usz, vp, usz, vp,
+                                 i32]),
+    "rdrf_dynamic_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, usz,
+                              vp, usz, vp]),
+    "rdrf_features_saved_bytes": (usz, [i32, i32]),
+    "rdrf_features_workspace_bytes": (usz, [i32]),
+    "rdrf_features_bwd_workspace_bytes": (usz, [i32]),
+    "rdrf_static_features_fwd": (i32, [vp, vp, vp, i32, vp, vp, vp, usz, vp, usz, vp]),
+    "rdrf_static_features_bwd": (i32, [vp, vp, vp, i32, vp, vp, vp, vp, vp, usz, vp, usz, vp]),
+    "rdrf_dynamic_features_fwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, usz, vp, usz, vp]),
+    "rdrf_dynamic_features_bwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, usz, vp, usz, vp]),
+    "rdrf_scene_flow_fwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, usz, vp, usz, vp]),
+    "rdrf_scene_flow_bwd": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, usz, vp, usz, vp]),
+    "rdrf_composite_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "rdrf_composite_bwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "rdrf_induce_flow_fwd": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
+    "rdrf_induce_flow_bwd": (i32, [i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "rdrf_rows_scatter_add": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "rdrf_distloss_fwd": (i32, [vp, vp, f32, vp, i32, i32, vp, vp]),
+    "rdrf_distloss_bwd": (i32, [vp, vp, f32, vp, i32, i32, vp, vp, vp]),
+    "rdrf_tv_fwd": (i32, [vp, i32, vp, vp]),
+    "rdrf_tv_bwd": (i32, [vp, i32, vp, vp]),
+    "rdrf_tv_grad": (i32, [vp, i32, vp, vp]),
+    "rdrf_adam_step": (i32, [vp, vp, vp, vp, usz, usz, f32, f32, f32, f32, f32, i32, f32, vp]),
+    "rdrf_upsample_bilinear": (i32, [vp, vp, i32, vp]),
+    "rdrf_dense_l1_fwd": (i32, [vp, i32, f32, vp, vp]),
+    "rdrf_dense_l1_bwd": (i32, [vp, vp, i32, f32, vp, vp]),
+    "rdrf_pack_floats": (usz, []),
+    "rdrf_static_pack": (i32, [vp, i32, i32, vp, vp]),
+    "rdrf_dynamic_pack": (i32, [vp, i32, vp, vp]),
+    "rdrf_loss_terms_workspace_floats": (usz, [i32]),
+    "rdrf_loss_terms_fwd": (i32, [vp, i32, vp, vp, vp]),
+    "rdrf_loss_terms_stats": (i32, [vp, i32, vp, vp, vp]),
+    "rdrf_loss_terms_finish": (i32, [vp, i32, vp, vp, i32, vp, vp]),
+    "rdrf_loss_terms_bwd": (i32, [vp, i32, vp, vp, vp]),
+    "rdrf_frame_depth_loss_workspace_bytes": (usz, [i32, i32]),
+    "rdrf_frame_depth_loss_fwd": (i32, [vp, vp, vp, vp, i32, i32, f32, vp, vp, vp, usz, vp]),
+    "rdrf_frame_depth_loss_bwd": (i32, [vp, vp, vp, i32, f32, vp, vp]),
+    "rdrf_render_workspace_bytes": (usz, [i32, i32]),
+    "rdrf_render_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, usz, vp]),
+    "rdrf_render_fused_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, usz, vp]),
+    "rdrf_render_sequence_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp, usz, vp]),
+    "rdrf_render_chunks_workspace_bytes": (usz, [i32, i32, i32]),
+    "rdrf_render_chunks_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, usz, vp, vp, i32]),
+    "rdrf_render_maps_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, i32, C.POINTER(RenderMapsC), vp, usz,
+                                  vp]),
+    "rdrf_render_chunks_maps_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, C.POINTER(RenderMapsC), vp,
+                                         usz, vp, vp, i32]),
+    "rdrf_render_world_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, i32, C.POINTER(RenderMapsC),
+                                   vp, usz, vp, vp, i32]),
+    "rdrf_render_motion_workspace_bytes": (usz, [i32, i32]),
+    "rdrf_render_motion_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, i32, C.POINTER(RenderMapsC),
+                                    C.POINTER(MotionCamsC), C.POINTER(MotionMapsC), vp, usz, vp]),
+    "rdrf_flow_to_image_workspace_bytes": (usz, [i32, i32]),
+    "rdrf_flow_to_image": (i32, [vp, i32, i32, vp, vp, usz, vp]),
+    "rdrf_track_ws_bytes": (usz, [i32, i32]),
+    "rdrf_track_points_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, C.POINTER(TrackCamsC), C.POINTER(TracksC), vp,
+                                   usz, vp]),
+    "rdrf_render_track_seeds_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, C.POINTER(RenderMapsC), vp, vp,
+                                         usz, vp]),
+    "rdrf_camera_rays": (i32, [vp, vp, i32, i32, i32, i32, f32, i64, i32, vp, vp]),
+    "rdrf_ssim_workspace_bytes": (usz, [i32, i32, i32]),
+    "rdrf_ssim": (i32, [vp, vp, i32, i32, i32, f32, vp, vp, vp, usz, vp]),
+    "rdrf_gather_batch": (i32, [C.POINTER(SceneTablesC), vp, vp, i32, C.POINTER(BatchC), vp]),
+    "rdrf_set_scatter_mode": (i32, [i32]),
+    "rdrf_deterministic": (i32, []),
+    "rdrf_det_bind": (i32, [i32, vp, usz, vp, vp]),
+    "rdrf_det_finish": (i32, [i32, vp]),
+    "rdrf_selftest_mlp": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, usz, vp]),
+    "rdrf_selftest_layer": (i32, [i32, vp, vp, i32, i32, i32, vp, vp, usz, vp]),
+    "rdrf_selftest_dw": (i32, [i32, i32, vp, usz, vp, usz, i32, vp, vp, vp]),
+    "rdrf_selftest_dw_describe": (i32, [i32, i32, C.POINTER(C.c_int), i32]),
+    "rdrf_selftest_dw_plan": (i32, [i32, i32, i32, C.POINTER(C.c_int), i32]),
+    "rdrf_selftest_sf_geometry": (i32, [i32, vp, vp]),
+    "rdrf_selftest_warp_geometry": (i32, [i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rdrf_selftest_warp_bwd_workspace_bytes": (usz, [i32, i32]),
+    "rdrf_selftest_warp_bwd": (i32, [vp, vp, i32, i32, vp, usz, vp, usz, vp, vp, vp, vp, vp, vp, vp, vp, usz, vp]),
+    "rdrf_selftest_sort_temp_bytes": (usz, [u32, i32]),
+    "rdrf_selftest_sort": (i32, [vp, u32, i32, vp, u32, vp, vp, vp, usz, vp]),
+    "rdrf_selftest_sort_seg_temp_bytes": (usz, [i32, u32, i32]),
+    "rdrf_selftest_sort_seg": (i32, [vp, i32, u32, i32, vp, vp, vp, vp, usz, vp]),
+    "rdrf_selftest_sort_describe": (i32, [i32, u32, i32, C.POINTER(C.c_ulong), i32]),
+    "rdrf_selftest_scatter_workspace_bytes": (usz, [i32, i32]),
+    "rdrf_selftest_scatter": (i32, [i32, i32, C.POINTER(RdrfScatterTest), vp]),
+    "rdrf_selftest_scatter_describe": (i32, [i32, C.POINTER(C.c_int), C.POINTER(C.c_int), i32]),
+    "rdrf_selftest_scatter_last": (i32, [C.POINTER(C.c_int), i32]),
+    "rdrf_compute_alpha_workspace_bytes": (usz, [i32, i32]),
+    "rdrf_compute_alpha": (i32, [vp, i32, vp, vp, i32, vp, i32, f32, C.POINTER(RdrfAlphaMask), vp, vp, vp, usz, vp]),
+    "rdrf_alpha_mask_build": (i32, [vp, i32, i32, i32, i32, f32, vp, vp, vp]),
+    "rdrf_alpha_mask_sample": (i32, [C.POINTER(RdrfAlphaMask), vp, vp, i32, i64, vp, vp]),
+    "rdrf_alpha_mask_valid": (i32, [C.POINTER(RdrfAlphaMask), C.POINTER(RdrfAlphaMask), vp, vp, i32, i32, vp, vp]),
+    "rdrf_render_masked_ws_bytes": (usz, [i32, i32]),
+    "rdrf_render_masked_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, C.POINTER(RdrfAlphaMask),
+                                    C.POINTER(RdrfAlphaMask), C.POINTER(RenderMapsC), vp, vp, usz, vp]),
+    "rdrf_prof_reset": (None, []),
+    "rdrf_prof_enable": (i32, [i32]),
+    "rdrf_prof_get": (i32, [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+}
+SYMBOLS = list(SIGNATURES)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -122,161 +250,21 @@ def _load():
     lib = C.CDLL(LIB_PATH)
     # the version check comes FIRST: a library of another version may lack symbols bound below, and the caller should see
     # "version mismatch", not a raw AttributeError
-    if not hasattr(lib, "rdrf_abi_version") or lib.rdrf_abi_version() != ABI_VERSION:
-        got = lib.rdrf_abi_version() if hasattr(lib, "rdrf_abi_version") else None
+    version = getattr(lib, "rdrf_abi_version", None)
+    got = version() if version is not None else None
+    if got != ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {got}, this binding is built against {ABI_VERSION} (include/rodynrf.h): rebuild "
                           "with make -C robust-dynrf_amd/csrc")
-    lib.rdrf_last_error.restype = C.c_char_p
-    lib.rdrf_workspace_bytes.restype = C.c_size_t
-    lib.rdrf_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.rdrf_forward_workspace_bytes.restype = C.c_size_t
-    lib.rdrf_forward_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.rdrf_saved_bytes.restype = C.c_size_t
-    lib.rdrf_saved_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.rdrf_saved_bytes_ex.restype = C.c_size_t
-    lib.rdrf_saved_bytes_ex.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-    lib.rdrf_saved_row_bytes.restype = C.c_size_t
-    lib.rdrf_saved_row_bytes.argtypes = [C.c_int]
-    for name, args in (("rdrf_features_saved_bytes", [C.c_int, C.c_int]),
-                       ("rdrf_features_workspace_bytes", [C.c_int]),
-                       ("rdrf_features_bwd_workspace_bytes", [C.c_int])):
-        getattr(lib, name).restype = C.c_size_t
-        getattr(lib, name).argtypes = args
-    lib.rdrf_adam_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
-                                   C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float,
-                                   C.c_void_p]
-    lib.rdrf_pack_floats.restype = C.c_size_t
-    lib.rdrf_pack_floats.argtypes = []
-    lib.rdrf_loss_terms_workspace_floats.restype = C.c_size_t
-    lib.rdrf_loss_terms_workspace_floats.argtypes = [C.c_int]
-    lib.rdrf_frame_depth_loss_workspace_bytes.restype = C.c_size_t
-    lib.rdrf_frame_depth_loss_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.rdrf_frame_depth_loss_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float,
-                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.rdrf_frame_depth_loss_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
-    lib.rdrf_render_workspace_bytes.restype = C.c_size_t
-    lib.rdrf_render_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.rdrf_render_chunks_workspace_bytes.restype = C.c_size_t
-    lib.rdrf_render_chunks_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.rdrf_render_maps_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                         C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(RenderMapsC), C.c_void_p,
-                                         C.c_size_t, C.c_void_p]
-    lib.rdrf_render_chunks_maps_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.POINTER(RenderMapsC),
-                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
-    lib.rdrf_render_world_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                          C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.POINTER(RenderMapsC),
-                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
-    lib.rdrf_render_motion_workspace_bytes.restype = C.c_size_t
-    lib.rdrf_render_motion_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.rdrf_render_motion_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                           C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(RenderMapsC),
-                                           C.POINTER(MotionCamsC), C.POINTER(MotionMapsC), C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.rdrf_flow_to_image_workspace_bytes.restype = C.c_size_t
-    lib.rdrf_flow_to_image_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.rdrf_flow_to_image.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.rdrf_camera_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int64,
-                                     C.c_int, C.c_void_p, C.c_void_p]
-    lib.rdrf_ssim_workspace_bytes.restype = C.c_size_t
-    lib.rdrf_ssim_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.rdrf_ssim.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
-                              C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.rdrf_compute_alpha_workspace_bytes.restype = C.c_size_t
-    lib.rdrf_compute_alpha_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.rdrf_compute_alpha.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float,
-                                       C.POINTER(RdrfAlphaMask), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.rdrf_alpha_mask_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
-                                          C.c_void_p]
-    lib.rdrf_alpha_mask_sample.argtypes = [C.POINTER(RdrfAlphaMask), C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p,
-                                           C.c_void_p]
-    lib.rdrf_alpha_mask_valid.argtypes = [C.POINTER(RdrfAlphaMask), C.POINTER(RdrfAlphaMask), C.c_void_p, C.c_void_p, C.c_int,
-                                          C.c_int, C.c_void_p, C.c_void_p]
-    if hasattr(lib, "rdrf_render_masked_fwd"):   # (an addition inside ABI 6, as above)
-        lib.rdrf_render_masked_ws_bytes.restype = C.c_size_t
-        lib.rdrf_render_masked_ws_bytes.argtypes = [C.c_int, C.c_int]
-        lib.rdrf_render_masked_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                               C.c_int, C.c_float, C.c_float, C.c_float, C.POINTER(RdrfAlphaMask),
-                                               C.POINTER(RdrfAlphaMask), C.POINTER(RenderMapsC), C.c_void_p, C.c_void_p,
-                                               C.c_size_t, C.c_void_p]
-    if hasattr(lib, "rdrf_track_points_fwd"):   # (an addition inside ABI 6, as above)
-        lib.rdrf_track_ws_bytes.restype = C.c_size_t
-        lib.rdrf_track_ws_bytes.argtypes = [C.c_int, C.c_int]
-        lib.rdrf_track_points_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
-                                              C.POINTER(TrackCamsC), C.POINTER(TracksC), C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.rdrf_render_track_seeds_fwd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                                    C.c_int, C.c_float, C.c_float, C.POINTER(RenderMapsC), C.c_void_p, C.c_void_p,
-                                                    C.c_size_t, C.c_void_p]
-    lib.rdrf_gather_batch.argtypes = [C.POINTER(SceneTablesC), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(BatchC), C.c_void_p]
-    lib.rdrf_selftest_layer.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                        C.c_size_t, C.c_void_p]
-    lib.rdrf_selftest_dw.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
-                                     C.c_void_p, C.c_void_p]
-    lib.rdrf_selftest_dw_describe.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]
-    lib.rdrf_selftest_dw_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]
-    lib.rdrf_selftest_warp_geometry.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    lib.rdrf_selftest_warp_bwd_workspace_bytes.restype = C.c_size_t
-    lib.rdrf_selftest_warp_bwd_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.rdrf_selftest_warp_bwd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.rdrf_selftest_sort_temp_bytes.restype = C.c_size_t
-    lib.rdrf_selftest_sort_temp_bytes.argtypes = [C.c_uint, C.c_int]
-    lib.rdrf_selftest_sort.argtypes = [C.c_void_p, C.c_uint, C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_size_t, C.c_void_p]
-    if hasattr(lib, "rdrf_selftest_sort_seg"):   # (additions inside ABI 6: an A/B library of the same version may predate them)
-        lib.rdrf_selftest_sort_seg_temp_bytes.restype = C.c_size_t
-        lib.rdrf_selftest_sort_seg_temp_bytes.argtypes = [C.c_int, C.c_uint, C.c_int]
-        lib.rdrf_selftest_sort_seg.argtypes = [C.c_void_p, C.c_int, C.c_uint, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_size_t, C.c_void_p]
-        lib.rdrf_selftest_sort_describe.argtypes = [C.c_int, C.c_uint, C.c_int, C.POINTER(C.c_ulonglong), C.c_int]
-    lib.rdrf_selftest_scatter_workspace_bytes.restype = C.c_size_t
-    lib.rdrf_selftest_scatter_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    lib.rdrf_selftest_scatter.argtypes = [C.c_int, C.c_int, C.POINTER(RdrfScatterTest), C.c_void_p]
-    lib.rdrf_selftest_scatter_describe.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]
-    lib.rdrf_selftest_scatter_last.argtypes = [C.POINTER(C.c_int), C.c_int]
-    lib.rdrf_prof_get.argtypes = [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]
-    lib.rdrf_det_bind.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-    lib.rdrf_det_finish.argtypes = [C.c_int, C.c_void_p]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name, None)   # an A/B library of this version may predate an addition made inside it: skipped
+        if fn is not None:
+            fn.restype, fn.argtypes = restype, argtypes
     if DETERMINISTIC and not lib.rdrf_deterministic():
         raise ImportError(f"RDRF_DETERMINISTIC=1 but {LIB_PATH} is the product build")
     return lib
 
 
 lib = _load()
-
-# every symbol include/rodynrf.h declares (tests check that the library exports all of them)
-SYMBOLS = [
-    "rdrf_abi_version", "rdrf_last_error", "rdrf_workspace_bytes", "rdrf_forward_workspace_bytes", "rdrf_saved_bytes", "rdrf_saved_bytes_ex", "rdrf_saved_row_bytes",
-    "rdrf_generate_rays",
-    "rdrf_generate_rays_bwd", "rdrf_generate_rays_uv", "rdrf_generate_rays_uv_bwd", "rdrf_sample_ndc", "rdrf_sample_contract", "rdrf_sample_bwd",
-    "rdrf_sample_world", "rdrf_sample_world_bwd", "rdrf_render_world_fwd",
-    "rdrf_static_fwd", "rdrf_static_fwd_ex", "rdrf_static_bwd", "rdrf_dynamic_fwd", "rdrf_dynamic_fwd_ex", "rdrf_dynamic_bwd",
-    "rdrf_features_saved_bytes", "rdrf_features_workspace_bytes", "rdrf_features_bwd_workspace_bytes",
-    "rdrf_static_features_fwd", "rdrf_static_features_bwd", "rdrf_dynamic_features_fwd",
-    "rdrf_dynamic_features_bwd",
-    "rdrf_scene_flow_fwd", "rdrf_scene_flow_bwd", "rdrf_composite_fwd", "rdrf_composite_bwd",
-    "rdrf_induce_flow_fwd", "rdrf_induce_flow_bwd", "rdrf_rows_scatter_add", "rdrf_distloss_fwd", "rdrf_distloss_bwd",
-    "rdrf_tv_fwd", "rdrf_tv_bwd", "rdrf_tv_grad", "rdrf_adam_step", "rdrf_upsample_bilinear", "rdrf_dense_l1_fwd",
-    "rdrf_dense_l1_bwd", "rdrf_pack_floats", "rdrf_static_pack", "rdrf_dynamic_pack", "rdrf_loss_terms_workspace_floats", "rdrf_loss_terms_fwd", "rdrf_loss_terms_bwd",
-    "rdrf_loss_terms_stats", "rdrf_loss_terms_finish", "rdrf_deterministic", "rdrf_det_bind", "rdrf_det_finish",
-    "rdrf_render_fused_fwd", "rdrf_render_sequence_fwd",
-    "rdrf_frame_depth_loss_workspace_bytes", "rdrf_frame_depth_loss_fwd", "rdrf_frame_depth_loss_bwd",
-    "rdrf_render_workspace_bytes", "rdrf_render_fwd", "rdrf_render_chunks_workspace_bytes", "rdrf_render_chunks_fwd",
-    "rdrf_render_maps_fwd", "rdrf_render_chunks_maps_fwd", "rdrf_camera_rays", "rdrf_ssim_workspace_bytes", "rdrf_ssim",
-    "rdrf_render_motion_workspace_bytes", "rdrf_render_motion_fwd", "rdrf_flow_to_image_workspace_bytes", "rdrf_flow_to_image",
-    "rdrf_gather_batch",
-    "rdrf_compute_alpha_workspace_bytes", "rdrf_compute_alpha", "rdrf_alpha_mask_build", "rdrf_alpha_mask_sample",
-    "rdrf_alpha_mask_valid", "rdrf_render_masked_ws_bytes", "rdrf_render_masked_fwd",
-    "rdrf_track_ws_bytes", "rdrf_track_points_fwd", "rdrf_render_track_seeds_fwd",
-    "rdrf_set_scatter_mode", "rdrf_selftest_mlp", "rdrf_selftest_layer", "rdrf_selftest_dw", "rdrf_selftest_dw_describe",
-    "rdrf_selftest_dw_plan",
-    "rdrf_selftest_sf_geometry", "rdrf_selftest_warp_geometry", "rdrf_selftest_warp_bwd_workspace_bytes", "rdrf_selftest_warp_bwd",
-    "rdrf_selftest_sort_temp_bytes", "rdrf_selftest_sort", "rdrf_selftest_sort_seg_temp_bytes", "rdrf_selftest_sort_seg",
-    "rdrf_selftest_sort_describe", "rdrf_selftest_scatter_workspace_bytes", "rdrf_selftest_scatter",
-    "rdrf_selftest_scatter_describe", "rdrf_selftest_scatter_last",
-    "rdrf_prof_reset",
-    "rdrf_prof_enable", "rdrf_prof_get",
-]
 
 
 # rdrf_selftest_layer forms (include/rodynrf.h RDRF_ST_*)

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._params import field_structs
 
 SLAB_POINTS = 1 << 21   # lattice points per native alpha call of getDenseAlpha (a bound on what one launch holds busy)
 
@@ -129,23 +130,18 @@ def apply_alpha_mask(valid, xyz, ts, *masks):
 
 def alpha_volume(field, xyz, times, length, mask=None, want_sigma=False, out=None):
     """rdrf_compute_alpha: xyz [M,3] un-normalised, times [T] -> alpha [M,T] (and sigma [M,T])"""
-    from .fields import TensorVMSplit_TimeEmbedding, _attach_packed, _cfg_struct, _dynamic_struct, _static_struct
     L.require_device(xyz, times)
     xyz, times = L.f32c(xyz).reshape(-1, 3), L.f32c(times).reshape(-1)
     M, T = xyz.shape[0], times.numel()
     dev = xyz.device
     alpha = torch.empty(M, T, device=dev) if out is None else out
     sigma = torch.empty(M, T, device=dev) if want_sigma else None
-    dynamic = isinstance(field, TensorVMSplit_TimeEmbedding)
-    params = [p.detach() for p in field._param_list()]
-    P = _dynamic_struct(params) if dynamic else _static_struct(params)
-    _attach_packed(field, P, params, False, dynamic)
-    cfg = _cfg_struct(field, "ndc")
+    P, cfg = field_structs(field, field._param_list(), "ndc")
     ws = L.workspace(dev, L.lib.rdrf_compute_alpha_workspace_bytes(M, T))
     m = mask._struct() if mask is not None else None
-    L.check(L.lib.rdrf_compute_alpha(C.byref(P), int(dynamic), C.byref(cfg), L.ptr(xyz), M, L.ptr(times), T, float(length),
+    L.check(L.lib.rdrf_compute_alpha(C.byref(P), int(field.DYNAMIC), C.byref(cfg), L.ptr(xyz), M, L.ptr(times), T, float(length),
                                      C.byref(m) if m is not None else None, L.ptr(alpha), L.ptr(sigma), L.ptr(ws),
-                                     C.c_size_t(ws.numel()), L.stream_of(xyz)), "rdrf_compute_alpha")
+                                     ws.numel(), L.stream_of(xyz)), "rdrf_compute_alpha")
     return (alpha, sigma) if want_sigma else alpha
 
 

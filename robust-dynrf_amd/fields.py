@@ -21,9 +21,13 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
-from .regularizers import dense_l1, tv_family, vector_diffs
+# the struct builders live in _params; tests and tools reach them as fields._vm_struct, fields._attach_packed, ...
+from ._params import _attach_packed, _cfg_struct, _dynamic_struct, _static_struct, _vm_struct, field_structs  # noqa: F401
+from .regularizers import _tensor4, dense_l1, tv_family, vector_diffs
 
 MAT_MODE = [[0, 1], [0, 2], [1, 2]]
+# packed weight images (_params._attach_packed): handed to the entry points instead of a re-pack per call; 0 switches them off
+PACK_CACHE = os.environ.get("RDRF_PACK_CACHE", "1") == "1"
 VEC_MODE = [2, 1, 0]
 
 
@@ -98,364 +102,194 @@ def _is_channel_last(t):
 # --------------------------------------------------------------------------------------------
 # autograd bridges
 # --------------------------------------------------------------------------------------------
-def _vm_struct(planes, lines):
-    vm = L.RdrfVM()
-    for i in range(3):
-        p, l = planes[i], lines[i]
-        # the kernels read components with stride 1 (16-byte quads) and lines as [L][C]: a factor that
-        # lost its channel-last storage (user-assigned parameter, .contiguous(), external resampling)
-        # would be read with the wrong layout -- fail loudly instead
-        if p.stride(1) != 1 or l.stride(1) != 1 or l.stride(2) != l.shape[1] or p.shape[1] % 4 != 0:
-            raise L.RdrfError(f"VM factor {i} is not channel-last (plane strides {tuple(p.stride())}, line strides "
-                              f"{tuple(l.stride())}): use fields.channel_last_()")
-        vm.plane[i] = p.data_ptr()
-        vm.line[i] = l.data_ptr()
-        vm.C[i] = p.shape[1]
-        vm.H[i] = p.shape[2]
-        vm.W[i] = p.shape[3]
-        vm.L[i] = l.shape[2]
-        vm.sH[i] = p.stride(2)
-        vm.sW[i] = p.stride(3)
-    return vm
-
-
-def _cfg_struct(field, ray_type, weight_thres=None):
-    c = L.RdrfFieldCfg()
-    ab = field._aabb_host
-    for i in range(6):
-        c.aabb[i] = ab[i]
-    c.distance_scale = float(field.distance_scale)
-    c.weight_thres = float(field.rayMarch_weight_thres if weight_thres is None else weight_thres)
-    c.density_shift = float(field.density_shift)
-    c.act = L.ACTS[field.fea2denseAct]
-    c.ray_type = L.RAY_TYPES.get(ray_type, 2)
-    c.static_head = L.HEADS.get(field.shadingMode, 0)
-    return c
-
-
-STATIC_KEYS = (["density_plane.%d" % i for i in range(3)] + ["density_line.%d" % i for i in range(3)]
-               + ["app_plane.%d" % i for i in range(3)] + ["app_line.%d" % i for i in range(3)]
-               + ["basis_mat.weight"])
-DYN_VM = (["density_plane.%d" % i for i in range(3)] + ["density_line.%d" % i for i in range(3)]
-          + ["blending_plane.%d" % i for i in range(3)] + ["blending_line.%d" % i for i in range(3)]
-          + ["app_plane.%d" % i for i in range(3)] + ["app_line.%d" % i for i in range(3)])
-
-
-def _static_struct(t):
-    """t: list of tensors in TensorVMSplit._param_list() order."""
-    P = L.RdrfStaticParams()
-    P.density = _vm_struct(t[0:3], t[3:6])
-    P.app = _vm_struct(t[6:9], t[9:12])
-    for name, ten in zip(("basis", "w1", "b1", "w2", "b2", "w3", "b3"), t[12:19]):
-        setattr(P, name, ten.data_ptr())
-    return P
-
-
-def _dynamic_struct(t):
-    P = L.RdrfDynamicParams()
-    P.density = _vm_struct(t[0:3], t[3:6])
-    P.blending = _vm_struct(t[6:9], t[9:12])
-    P.app = _vm_struct(t[12:15], t[15:18])
-    names = ("basis", "rw1", "rb1", "rw2", "rb2", "rwv", "rbv", "l1w", "l1b", "l2w", "l2b", "l3w",
-             "l3b", "l4w", "l4b", "l5w", "l5b", "dw1", "db1", "dw2", "db2", "bw1", "bb1", "bw2", "bb2")
-    for name, ten in zip(names, t[18:43]):
-        setattr(P, name, ten.data_ptr())
-    for i in range(4):
-        P.sfw[i] = t[43 + 2 * i].data_ptr()
-        P.sfb[i] = t[44 + 2 * i].data_ptr()
-    return P
-
-
-# Packed weight images (rdrf_static_pack / rdrf_dynamic_pack): the MLP weights of a field do not change between the
-# passes of an iteration or the chunks of a render, so the image is packed once per (weights, stream) and handed to
-# the entry points through packed_fwd / packed_bwd instead of being re-packed by every call (~40 launches of ~6 us
-# per training iteration).  The key is every MLP tensor's (data_ptr, torch version counter) plus the field's
-# `_pack_epoch`, which optim.FlatAdam bumps because rdrf_adam_step writes the parameters through raw pointers.
-PACK_CACHE = os.environ.get("RDRF_PACK_CACHE", "1") == "1"
-
-
-def _attach_packed(field, P, params, backward, dynamic):
-    if not PACK_CACHE or field is None:
-        return
-    first = 18 if dynamic else 12
-    stream = torch.cuda.current_stream(params[0].device).cuda_stream
-    key = (tuple((p.data_ptr(), p._version) for p in params[first:]), field._pack_epoch)
-    cache = field.__dict__.setdefault("_pack_cache", {})
-    # one image per (direction, stream): a re-pack into an image is ordered behind that stream's earlier readers;
-    # another stream gets its own image instead of racing with kernels still reading this one
-    slot = cache.get((backward, stream))
-    if slot is None or slot[0] != key:
-        img = slot[1] if slot is not None else torch.empty(int(L.lib.rdrf_pack_floats()), device=params[0].device)
-        if dynamic:
-            L.check(L.lib.rdrf_dynamic_pack(C.byref(P), int(backward), L.ptr(img), C.c_void_p(stream)), "rdrf_dynamic_pack")
-        else:
-            L.check(L.lib.rdrf_static_pack(C.byref(P), L.HEADS.get(field.shadingMode, 0), int(backward), L.ptr(img),
-                                           C.c_void_p(stream)), "rdrf_static_pack")
-        cache[(backward, stream)] = slot = (key, img)
-    if backward:
-        P.packed_bwd = slot[1].data_ptr()
-    else:
-        P.packed_fwd = slot[1].data_ptr()
-
-
 # Saved-byte accounting: per kind of call (0 static field, 1 dynamic field, 2 scene flow, "feat0" / "feat1" the
 # per-point entry points) the number of forwards that saved "full" rows, "no_app" rows (RDRF_SAVE_NO_APP) or "none", and the
 # bytes allocated for them -- what the trainer's tests read to see which forward saved what.
 SAVE_STATS = collections.Counter()
 
 
-def _grad_mode(grad_mode):
-    """Rows are saved only where a backward can read them.  Under torch.no_grad() none can exist, yet
-    ctx.needs_input_grad still reports True for parameters there -- and inside Function.forward grad mode is always
-    off -- so the modules capture the CALLER's mode and hand it in; None = the mode right here."""
-    return torch.is_grad_enabled() if grad_mode is None else bool(grad_mode)
+def _call_modes(rgb):
+    """-> (rgb mode, grad mode): what the field modules hand to their autograd Function next to the ray type.  rgb mode:
+    forward()'s `rgb`, True, False or "value".  Grad mode: rows are saved only where a backward can read them.  Under
+    torch.no_grad() none can exist, yet ctx.needs_input_grad still reports True for parameters there -- and inside
+    Function.forward grad mode is always off -- so the modules capture the CALLER's mode here and hand it in."""
+    rgb = rgb if isinstance(rgb, str) else bool(rgb)
+    if rgb not in (True, False, "value"):
+        raise ValueError(f"forward(..., rgb=...) takes True, False or 'value', not {rgb!r}")
+    return rgb, torch.is_grad_enabled()
 
 
-def _alloc_saved(ctx, kind, N, S, dev, grad_mode=None, flags=0):
-    """training mode: a per-call buffer the forward fills with the activations its backward needs
-    (inference -- the caller runs under no_grad, or no input requires grad -- keeps nothing).
-    flags: RDRF_SAVE_* of rdrf_saved_bytes_ex (L.SAVE_NO_APP: the colours are values only, no appearance rows)."""
-    if not _grad_mode(grad_mode) or not any(ctx.needs_input_grad):
-        SAVE_STATS[(kind, "none")] += 1
+def _saved(ctx, key, nbytes, dev, grad_mode, rows="full"):
+    """training mode: a per-call buffer the forward fills with the activations its backward needs (inference -- the caller
+    runs under no_grad, or no input requires grad -- keeps nothing).  grad_mode None = the mode right here."""
+    if not (torch.is_grad_enabled() if grad_mode is None else grad_mode) or not any(ctx.needs_input_grad):
+        SAVE_STATS[(key, "none")] += 1
         return None, 0
-    nbytes = int(L.lib.rdrf_saved_bytes_ex(kind, N, S, flags))
-    SAVE_STATS[(kind, "no_app" if flags & L.SAVE_NO_APP else "full")] += 1
-    SAVE_STATS[(kind, "bytes")] += nbytes
+    nbytes = int(nbytes())
+    SAVE_STATS[(key, rows)] += 1
+    SAVE_STATS[(key, "bytes")] += nbytes
     return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
 
 
-_RGB_SUFFIX = {True: "", False: "-norgb", "value": "-valrgb"}
+def _alloc_saved(ctx, kind, N, S, dev, grad_mode=None, flags=0):
+    """the saved buffer of a field / scene-flow forward (see _saved).  flags: RDRF_SAVE_* of rdrf_saved_bytes_ex
+    (L.SAVE_NO_APP: the colours are values only, no appearance rows)."""
+    return _saved(ctx, kind, lambda: L.lib.rdrf_saved_bytes_ex(kind, N, S, flags), dev, grad_mode,
+                  "no_app" if flags & L.SAVE_NO_APP else "full")
 
 
-def _call_mode(ray_type, rgb):
-    """what the field modules hand to their autograd Function next to the ray type, as suffixes of that string: the rgb
-    mode of forward() ("-norgb": rgb=False, "-valrgb": rgb="value") and "-nograd" when the caller runs under no_grad"""
-    rgb = rgb if isinstance(rgb, str) else bool(rgb)
-    if rgb not in _RGB_SUFFIX:
-        raise ValueError(f"forward(..., rgb=...) takes True, False or 'value', not {rgb!r}")
-    return ray_type + _RGB_SUFFIX[rgb] + ("" if torch.is_grad_enabled() else "-nograd")
+def _feat_saved(ctx, dynamic, M, dev, grad_mode=None):
+    """the saved buffer of a per-point forward (see _saved)"""
+    return _saved(ctx, "feat%d" % int(dynamic), lambda: L.lib.rdrf_features_saved_bytes(int(dynamic), M), dev, grad_mode)
 
 
-def _parse_mode(mode):
-    """-> (ray_type, rgb: True | False | "value", grad mode of the caller); see _call_mode"""
-    grad_mode = not mode.endswith("-nograd")
-    mode = mode.replace("-nograd", "")
-    rgb = "value" if mode.endswith("-valrgb") else not mode.endswith("-norgb")
-    return mode.replace("-valrgb", "").replace("-norgb", ""), rgb, grad_mode
+def _input(t):
+    """a tensor as the entry points read it: contiguous fp32, masks as uint8"""
+    if t.dtype in (torch.bool, torch.uint8):
+        t = t.contiguous()
+        return t.view(torch.uint8) if t.dtype == torch.bool else t
+    return L.f32c(t)
 
 
-def _prep_inputs(rays, ts, xyz, z, valid):
-    L.require_device(rays, ts, xyz, z, valid)
-    rays, ts, xyz, z = L.f32c(rays), L.f32c(ts), L.f32c(xyz), L.f32c(z)
-    valid = valid.contiguous()
-    if valid.dtype == torch.bool:
-        valid = valid.view(torch.uint8)
-    return rays, ts, xyz, z, valid
+def _begin_forward(ctx, field, params, ray_type, inputs, dims, saved, ws_bytes):
+    """What the five forwards share.  Checks and converts `inputs`, takes the saved buffer (`saved(dev)`: _alloc_saved or
+    _feat_saved of this call) and the workspace (`ws_bytes(saved is not None)` bytes), builds the structs and stashes in ctx
+    what the backward reads.  Returns (head, tail, saved buffer): every forward entry point is called as
+    fn(*head, *dims, outputs..., *tail) with head = P, cfg, the inputs and tail = saved, saved_bytes, ws, ws_bytes, stream."""
+    ctx.set_materialize_grads(False)   # unused outputs arrive as None: their branch is skipped
+    L.require_device(*inputs)
+    inputs = [_input(t) for t in inputs]
+    dev = inputs[0].device
+    buf, sbytes = saved(dev)
+    ws = L.workspace(dev, ws_bytes(buf is not None))
+    P, cfg = field_structs(field, params, ray_type)
+    ctx.field, ctx.ray_type, ctx.dims, ctx.saved = field, ray_type, dims, buf
+    ctx.save_for_backward(*inputs, *params)
+    return ((C.byref(P), C.byref(cfg), *[L.ptr(t) for t in inputs]),
+            (L.ptr(buf), sbytes, L.ptr(ws), ws.numel(), L.stream_of(inputs[0])), buf)
+
+
+def _begin_backward(ctx, n_inputs, twice, cotangents, ws_bytes):
+    """What the five backwards share once they know there is something to differentiate.  Refuses a second backward (with
+    the message `twice`), binds the deterministic build's shadow, takes the gradient buffers (the field's flat buffer when
+    fused_grad) and the workspace (`ws_bytes(*dims)` bytes) and builds the structs.  Returns (inputs, head, cot, G, tail,
+    grads): every backward entry point is called as fn(*head, *dims, cotangents..., G, input gradients..., *tail) with `cot`
+    the contiguous cotangents; `grads` goes through _end_backward into the return tuple."""
+    tensors = ctx.saved_tensors
+    inputs, params = tensors[:n_inputs], tensors[n_inputs:]
+    if ctx.saved is None:
+        raise L.RdrfError(twice)
+    field = ctx.field
+    field._det_bind()
+    grads = field.fused_grads() if field.fused_grad else [torch.zeros_like(p) for p in params]
+    G = (_dynamic_struct if field.DYNAMIC else _static_struct)(grads)
+    P, cfg = field_structs(field, params, ctx.ray_type, True)
+    ws = L.workspace(inputs[0].device, ws_bytes(*ctx.dims))
+    return (inputs, (C.byref(P), C.byref(cfg), *[L.ptr(t) for t in inputs]), [None if g is None else L.f32c(g) for g in cotangents],
+            C.byref(G), (L.ptr(ctx.saved), ctx.saved.numel(), L.ptr(ws), ws.numel(), L.stream_of(inputs[0])), grads)
+
+
+def _end_backward(ctx, grads):
+    """release the saved activations; the parameter gradients to return: None when fused (already accumulated into
+    p.grad, views of the field's flat buffer)"""
+    ctx.saved = None
+    return [None] * len(grads) if ctx.field.fused_grad else grads
+
+
+def _field_forward(ctx, kind, field, ray_type, rgb_mode, grad_mode, inputs, params):
+    """the forward of _StaticFn / _DynamicFn up to the entry point -> (N, S, rgb, flags, head, tail).  rgb=False -- the
+    colours are not wanted; rgb="value" -- computed, but no gradient will be asked for them: no appearance rows are saved.
+    A call that saves nothing takes the smaller forward workspace."""
+    N, S = inputs[3].shape
+    flags = L.SAVE_NO_APP if rgb_mode == "value" else 0
+    head, tail, _ = _begin_forward(
+        ctx, field, params, ray_type, inputs, (N, S), lambda dev: _alloc_saved(ctx, kind, N, S, dev, grad_mode, flags),
+        lambda saving: (L.lib.rdrf_workspace_bytes if saving else L.lib.rdrf_forward_workspace_bytes)(N, S))
+    rgb = torch.empty(N, S, 3, device=inputs[3].device) if rgb_mode is not False else None
+    if rgb_mode == "value":
+        ctx.mark_non_differentiable(rgb)
+    ctx.want_rgb = rgb_mode is True
+    return N, S, rgb, flags, head, tail
+
+
+def _field_backward(ctx, entry, what, twice, cotangents, g_rgb):
+    """the backward of _StaticFn / _DynamicFn: they differ in the entry point and its cotangents, g_dists last"""
+    if g_rgb is not None and not ctx.want_rgb:
+        raise L.RdrfError("forward(..., rgb=False | 'value') saved no appearance rows: no gradient can flow through rgb")
+    need = ctx.needs_input_grad   # field, ray_type, rgb_mode, grad_mode, rays, ts, xyz, z, valid, *params
+    if all(g is None for g in cotangents[:-1]) and not (need[4] or need[7]):
+        # only `dists` is consumed downstream (pass E of the trainer feeds the dynamic field's dists to the compositor): it
+        # depends on z_vals and |d| alone, no parameter (and here neither rays nor z_vals want a gradient) -- nothing to
+        # differentiate, exactly as in the reference where dists has no parameter ancestry
+        ctx.saved = None
+        return (None,) * len(need)
+    (rays, _, xyz, z, _), head, cot, G, tail, grads = _begin_backward(ctx, 5, twice, cotangents, L.lib.rdrf_workspace_bytes)
+    g_rays, g_xyz, g_z = L.zeros_like_many([rays, xyz, z], [need[4], need[6], need[7]])
+    L.check(entry(*head, *ctx.dims, *map(L.ptr, cot), G, L.ptr(g_xyz), L.ptr(g_z), L.ptr(g_rays), *tail), what)
+    return (None, None, None, None, g_rays, None, g_xyz, g_z, None, *_end_backward(ctx, grads))
 
 
 class _StaticFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, field, ray_type, rays, ts, xyz, z, valid, *params):
-        ctx.set_materialize_grads(False)   # unused outputs arrive as None: their branch is skipped
-        rays, ts, xyz, z, valid = _prep_inputs(rays, ts, xyz, z, valid)
-        N, S = z.shape
-        dev = z.device
-        # ray_type "ndc" / "contract" + the suffixes of _call_mode: rgb=False -- the colours are not wanted; rgb="value" --
-        # computed, but no gradient will be asked for them: no appearance rows are saved
-        ray_type, rgb_mode, grad_mode = _parse_mode(ray_type)
-        want_rgb, flags = rgb_mode is not False, L.SAVE_NO_APP if rgb_mode == "value" else 0
-        rgb = torch.empty(N, S, 3, device=dev) if want_rgb else None
-        sigma = torch.empty(N, S, device=dev)
-        weight = torch.empty(N, S, device=dev)
-        dists = torch.empty(N, S, device=dev)
-        saved, sbytes = _alloc_saved(ctx, 0, N, S, dev, grad_mode, flags)
-        ws = L.workspace(dev, (L.lib.rdrf_workspace_bytes if saved is not None else L.lib.rdrf_forward_workspace_bytes)(N, S))
-        P = _static_struct(params)
-        _attach_packed(field, P, params, False, False)
-        cfg = _cfg_struct(field, ray_type)
-        L.check(L.lib.rdrf_static_fwd_ex(C.byref(P), C.byref(cfg), L.ptr(rays), L.ptr(ts), L.ptr(xyz),
-                                         L.ptr(z), L.ptr(valid), N, S, L.ptr(rgb), L.ptr(sigma),
-                                         L.ptr(weight), L.ptr(dists), L.ptr(saved), C.c_size_t(sbytes),
-                                         L.ptr(ws), C.c_size_t(ws.numel()), L.stream_of(z), flags),
+    def forward(ctx, field, ray_type, rgb_mode, grad_mode, rays, ts, xyz, z, valid, *params):
+        N, S, rgb, flags, head, tail = _field_forward(ctx, 0, field, ray_type, rgb_mode, grad_mode, (rays, ts, xyz, z, valid), params)
+        sigma, weight, dists = (torch.empty(N, S, device=z.device) for _ in range(3))
+        L.check(L.lib.rdrf_static_fwd_ex(*head, N, S, L.ptr(rgb), L.ptr(sigma), L.ptr(weight), L.ptr(dists), *tail, flags),
                 "rdrf_static_fwd")
-        if rgb_mode == "value":
-            ctx.mark_non_differentiable(rgb)
-        ctx.field, ctx.ray_type, ctx.saved, ctx.want_rgb = field, ray_type, saved, rgb_mode is True
-        ctx.save_for_backward(rays, ts, xyz, z, valid, *params)
         return rgb, sigma, weight, dists
 
     @staticmethod
     def backward(ctx, g_rgb, g_sigma, g_weight, g_dists):
-        rays, ts, xyz, z, valid, *params = ctx.saved_tensors
-        if g_rgb is not None and not ctx.want_rgb:
-            raise L.RdrfError("forward(..., rgb=False | 'value') saved no appearance rows: no gradient can flow through rgb")
-        need = ctx.needs_input_grad
-        if g_rgb is None and g_sigma is None and g_weight is None and not (need[2] or need[5]):
-            # only `dists` is consumed downstream: it depends on z_vals and |d| alone, no parameter
-            # (and here neither rays nor z_vals want a gradient) -- nothing to differentiate, exactly
-            # as in the reference where dists has no parameter ancestry
-            ctx.saved = None
-            return (None,) * (7 + len(params))
-        if ctx.saved is None:
-            raise L.RdrfError("TensorVMSplit.forward: backward called twice (the saved activations are released "
-                              "after the first backward; retain_graph is not supported)")
-        N, S = z.shape
-        dev = z.device
-        fused = ctx.field.fused_grad
-        ctx.field._det_bind()
-        grads = ctx.field.fused_grads() if fused else [torch.zeros_like(p) for p in params]
-        G = _static_struct(grads)
-        P = _static_struct(params)
-        _attach_packed(ctx.field, P, params, True, False)
-        cfg = _cfg_struct(ctx.field, ctx.ray_type)
-        need = ctx.needs_input_grad
-        g_rays, g_xyz, g_z = L.zeros_like_many([rays, xyz, z], [need[2], need[4], need[5]])
-        cont = lambda g: None if g is None else L.f32c(g)
-        g_rgb, g_sigma, g_weight, g_dists = cont(g_rgb), cont(g_sigma), cont(g_weight), cont(g_dists)
-        ws = L.workspace(dev, L.lib.rdrf_workspace_bytes(N, S))
-        L.check(L.lib.rdrf_static_bwd(C.byref(P), C.byref(cfg), L.ptr(rays), L.ptr(ts), L.ptr(xyz),
-                                      L.ptr(z), L.ptr(valid), N, S, L.ptr(g_rgb), L.ptr(g_sigma),
-                                      L.ptr(g_weight), L.ptr(g_dists), C.byref(G), L.ptr(g_xyz),
-                                      L.ptr(g_z), L.ptr(g_rays), L.ptr(ctx.saved),
-                                      C.c_size_t(ctx.saved.numel()), L.ptr(ws), C.c_size_t(ws.numel()),
-                                      L.stream_of(z)), "rdrf_static_bwd")
-        ctx.saved = None
-        if fused:   # already accumulated into p.grad (views of the field's flat buffer)
-            grads = [None] * len(params)
-        return (None, None, g_rays, None, g_xyz, g_z, None, *grads)
+        return _field_backward(ctx, L.lib.rdrf_static_bwd, "rdrf_static_bwd",
+                               "TensorVMSplit.forward: backward called twice (the saved activations are released "
+                               "after the first backward; retain_graph is not supported)",
+                               (g_rgb, g_sigma, g_weight, g_dists), g_rgb)
 
 
 class _DynamicFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, field, ray_type, rays, ts, xyz, z, valid, *params):
-        ctx.set_materialize_grads(False)   # unused outputs arrive as None: their branch is skipped
-        rays, ts, xyz, z, valid = _prep_inputs(rays, ts, xyz, z, valid)
-        N, S = z.shape
-        dev = z.device
-        ray_type, rgb_mode, grad_mode = _parse_mode(ray_type)   # see _StaticFn
-        want_rgb, flags = rgb_mode is not False, L.SAVE_NO_APP if rgb_mode == "value" else 0
-        rgb = torch.empty(N, S, 3, device=dev) if want_rgb else None
-        xyz_prime = torch.empty(N, S, 3, device=dev)
-        sigma, weight, dists, blending = (torch.empty(N, S, device=dev) for _ in range(4))
-        saved, sbytes = _alloc_saved(ctx, 1, N, S, dev, grad_mode, flags)
-        ws = L.workspace(dev, (L.lib.rdrf_workspace_bytes if saved is not None else L.lib.rdrf_forward_workspace_bytes)(N, S))
-        P = _dynamic_struct(params)
-        _attach_packed(field, P, params, False, True)
-        cfg = _cfg_struct(field, ray_type)
-        L.check(L.lib.rdrf_dynamic_fwd_ex(C.byref(P), C.byref(cfg), L.ptr(rays), L.ptr(ts), L.ptr(xyz),
-                                          L.ptr(z), L.ptr(valid), N, S, L.ptr(blending), L.ptr(weight),
-                                          L.ptr(xyz_prime), L.ptr(rgb), L.ptr(sigma), L.ptr(dists),
-                                          L.ptr(saved), C.c_size_t(sbytes), L.ptr(ws),
-                                          C.c_size_t(ws.numel()), L.stream_of(z), flags), "rdrf_dynamic_fwd")
-        if rgb_mode == "value":
-            ctx.mark_non_differentiable(rgb)
-        ctx.field, ctx.ray_type, ctx.saved, ctx.want_rgb = field, ray_type, saved, rgb_mode is True
-        ctx.save_for_backward(rays, ts, xyz, z, valid, *params)
+    def forward(ctx, field, ray_type, rgb_mode, grad_mode, rays, ts, xyz, z, valid, *params):
+        N, S, rgb, flags, head, tail = _field_forward(ctx, 1, field, ray_type, rgb_mode, grad_mode, (rays, ts, xyz, z, valid), params)
+        xyz_prime = torch.empty(N, S, 3, device=z.device)
+        sigma, weight, dists, blending = (torch.empty(N, S, device=z.device) for _ in range(4))
+        L.check(L.lib.rdrf_dynamic_fwd_ex(*head, N, S, L.ptr(blending), L.ptr(weight), L.ptr(xyz_prime), L.ptr(rgb), L.ptr(sigma),
+                                          L.ptr(dists), *tail, flags), "rdrf_dynamic_fwd")
         return blending, weight, xyz_prime, rgb, sigma, dists
 
     @staticmethod
     def backward(ctx, g_blending, g_weight, g_xyz_prime, g_rgb, g_sigma, g_dists):
-        rays, ts, xyz, z, valid, *params = ctx.saved_tensors
-        if g_rgb is not None and not ctx.want_rgb:
-            raise L.RdrfError("forward(..., rgb=False | 'value') saved no appearance rows: no gradient can flow through rgb")
-        need = ctx.needs_input_grad
-        if all(g is None for g in (g_blending, g_weight, g_xyz_prime, g_rgb, g_sigma)) and not (need[2] or need[5]):
-            # only `dists` is consumed (pass E of the trainer feeds the dynamic field's dists to the
-            # compositor): no parameter ancestry, nothing to differentiate
-            ctx.saved = None
-            return (None,) * (7 + len(params))
-        if ctx.saved is None:
-            raise L.RdrfError("TensorVMSplit_TimeEmbedding.forward: backward called twice (the saved activations "
-                              "are released after the first backward; retain_graph is not supported)")
-        N, S = z.shape
-        dev = z.device
-        fused = ctx.field.fused_grad
-        ctx.field._det_bind()
-        grads = ctx.field.fused_grads() if fused else [torch.zeros_like(p) for p in params]
-        G = _dynamic_struct(grads)
-        P = _dynamic_struct(params)
-        _attach_packed(ctx.field, P, params, True, True)
-        cfg = _cfg_struct(ctx.field, ctx.ray_type)
-        need = ctx.needs_input_grad
-        g_rays, g_xyz, g_z = L.zeros_like_many([rays, xyz, z], [need[2], need[4], need[5]])
-        cont = lambda g: None if g is None else L.f32c(g)
-        gb, gw, gxp, gr, gs, gd = (cont(g) for g in (g_blending, g_weight, g_xyz_prime, g_rgb,
-                                                      g_sigma, g_dists))
-        ws = L.workspace(dev, L.lib.rdrf_workspace_bytes(N, S))
-        L.check(L.lib.rdrf_dynamic_bwd(C.byref(P), C.byref(cfg), L.ptr(rays), L.ptr(ts), L.ptr(xyz),
-                                       L.ptr(z), L.ptr(valid), N, S, L.ptr(gb), L.ptr(gw),
-                                       L.ptr(gxp), L.ptr(gr), L.ptr(gs), L.ptr(gd), C.byref(G),
-                                       L.ptr(g_xyz), L.ptr(g_z), L.ptr(g_rays), L.ptr(ctx.saved),
-                                       C.c_size_t(ctx.saved.numel()), L.ptr(ws),
-                                       C.c_size_t(ws.numel()), L.stream_of(z)), "rdrf_dynamic_bwd")
-        ctx.saved = None
-        if fused:   # already accumulated into p.grad (views of the field's flat buffer)
-            grads = [None] * len(params)
-        return (None, None, g_rays, None, g_xyz, g_z, None, *grads)
+        return _field_backward(ctx, L.lib.rdrf_dynamic_bwd, "rdrf_dynamic_bwd",
+                               "TensorVMSplit_TimeEmbedding.forward: backward called twice (the saved activations "
+                               "are released after the first backward; retain_graph is not supported)",
+                               (g_blending, g_weight, g_xyz_prime, g_rgb, g_sigma, g_dists), g_rgb)
 
 
 class _SceneFlowFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, field, grad_mode, pts, ts, *params):
-        ctx.set_materialize_grads(False)
-        L.require_device(pts, ts)
-        pts, ts = L.f32c(pts), L.f32c(ts)
         N, S, _ = pts.shape
+        head, tail, _ = _begin_forward(ctx, field, params, "ndc", (pts, ts), (N, S),
+                                       lambda dev: _alloc_saved(ctx, 2, N, S, dev, grad_mode),
+                                       lambda saving: L.lib.rdrf_workspace_bytes(N, S))
         sf_f = torch.empty(N, S, 3, device=pts.device)
         sf_b = torch.empty(N, S, 3, device=pts.device)
-        ws = L.workspace(pts.device, L.lib.rdrf_workspace_bytes(N, S))
-        saved, sbytes = _alloc_saved(ctx, 2, N, S, pts.device, grad_mode)
-        P = _dynamic_struct(params)
-        _attach_packed(field, P, params, False, True)
-        cfg = _cfg_struct(field, "ndc")
-        L.check(L.lib.rdrf_scene_flow_fwd(C.byref(P), C.byref(cfg), L.ptr(pts), L.ptr(ts), N, S,
-                                          L.ptr(sf_f), L.ptr(sf_b), L.ptr(saved), C.c_size_t(sbytes),
-                                          L.ptr(ws), C.c_size_t(ws.numel()), L.stream_of(pts)),
-                "rdrf_scene_flow_fwd")
-        ctx.field, ctx.saved = field, saved
-        ctx.save_for_backward(pts, ts, *params)
+        L.check(L.lib.rdrf_scene_flow_fwd(*head, N, S, L.ptr(sf_f), L.ptr(sf_b), *tail), "rdrf_scene_flow_fwd")
         return sf_f, sf_b
 
     @staticmethod
     def backward(ctx, g_f, g_b):
-        pts, ts, *params = ctx.saved_tensors
-        if ctx.saved is None:
-            raise L.RdrfError("get_forward_backward_scene_flow: backward called twice (retain_graph is not supported)")
-        N, S, _ = pts.shape
-        fused = ctx.field.fused_grad
-        ctx.field._det_bind()
-        grads = ctx.field.fused_grads() if fused else [torch.zeros_like(p) for p in params]
-        G = _dynamic_struct(grads)
-        P = _dynamic_struct(params)
-        _attach_packed(ctx.field, P, params, True, True)
-        cfg = _cfg_struct(ctx.field, "ndc")
+        (pts, _), head, cot, G, tail, grads = _begin_backward(
+            ctx, 2, "get_forward_backward_scene_flow: backward called twice (retain_graph is not supported)", (g_f, g_b),
+            L.lib.rdrf_workspace_bytes)
         g_pts = torch.zeros_like(pts) if ctx.needs_input_grad[2] else None
-        g_f = None if g_f is None else L.f32c(g_f)
-        g_b = None if g_b is None else L.f32c(g_b)
-        ws = L.workspace(pts.device, L.lib.rdrf_workspace_bytes(N, S))
-        L.check(L.lib.rdrf_scene_flow_bwd(C.byref(P), C.byref(cfg), L.ptr(pts), L.ptr(ts), N, S,
-                                          L.ptr(g_f), L.ptr(g_b), C.byref(G), L.ptr(g_pts),
-                                          L.ptr(ctx.saved), C.c_size_t(ctx.saved.numel()), L.ptr(ws),
-                                          C.c_size_t(ws.numel()), L.stream_of(pts)),
-                "rdrf_scene_flow_bwd")
-        ctx.saved = None
-        if fused:
-            grads = [None] * len(params)
-        return (None, None, g_pts, None, *grads)
+        L.check(L.lib.rdrf_scene_flow_bwd(*head, *ctx.dims, *map(L.ptr, cot), G, L.ptr(g_pts), *tail), "rdrf_scene_flow_bwd")
+        return (None, None, g_pts, None, *_end_backward(ctx, grads))
 
 
 # --------------------------------------------------------------------------------------------
 # compute_* / warp_coordinate: the per-point building blocks (rdrf_*_features_fwd/bwd)
 # --------------------------------------------------------------------------------------------
-def _feat_saved(ctx, dynamic, M, dev, grad_mode=None):
-    """see _alloc_saved"""
-    if not _grad_mode(grad_mode) or not any(ctx.needs_input_grad):
-        SAVE_STATS[("feat%d" % int(dynamic), "none")] += 1
-        return None, 0
-    nbytes = int(L.lib.rdrf_features_saved_bytes(int(dynamic), M))
-    SAVE_STATS[("feat%d" % int(dynamic), "full")] += 1
-    SAVE_STATS[("feat%d" % int(dynamic), "bytes")] += nbytes
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+_FEAT_TWICE = "compute_*: backward called twice (the saved activations were released)"
 
 
 class _StaticFeatFn(torch.autograd.Function):
@@ -463,51 +297,23 @@ class _StaticFeatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, field, grad_mode, want_density, want_app, xn, *params):
-        ctx.set_materialize_grads(False)
-        L.require_device(xn)
-        xn = L.f32c(xn)
         M, dev = xn.shape[0], xn.device
+        head, tail, _ = _begin_forward(ctx, field, params, "ndc", (xn,), (M,), lambda dev: _feat_saved(ctx, 0, M, dev, grad_mode),
+                                       lambda saving: L.lib.rdrf_features_workspace_bytes(M))
         dens = torch.empty(M, device=dev) if want_density else None
         app = torch.empty(M, 27, device=dev) if want_app else None
-        ws = L.workspace(dev, L.lib.rdrf_features_workspace_bytes(M))
-        saved, sbytes = _feat_saved(ctx, 0, M, dev, grad_mode)
-        P = _static_struct(params)
-        _attach_packed(field, P, params, False, False)
-        cfg = _cfg_struct(field, "ndc")
-        L.check(L.lib.rdrf_static_features_fwd(C.byref(P), C.byref(cfg), L.ptr(xn), M, L.ptr(dens), L.ptr(app),
-                                               L.ptr(saved), C.c_size_t(sbytes), L.ptr(ws),
-                                               C.c_size_t(ws.numel()), L.stream_of(xn)),
-                "rdrf_static_features_fwd")
-        ctx.field, ctx.saved = field, saved
-        ctx.save_for_backward(xn, *params)
+        L.check(L.lib.rdrf_static_features_fwd(*head, M, L.ptr(dens), L.ptr(app), *tail), "rdrf_static_features_fwd")
         return dens, app
 
     @staticmethod
     def backward(ctx, g_dens, g_app):
-        xn, *params = ctx.saved_tensors
-        if ctx.saved is None:
-            raise L.RdrfError("compute_*: backward called twice (the saved activations were released)")
-        M, dev = xn.shape[0], xn.device
-        fused = ctx.field.fused_grad
-        ctx.field._det_bind()
-        grads = ctx.field.fused_grads() if fused else [torch.zeros_like(p) for p in params]
         if g_dens is None and g_app is None:
-            return (None,) * (5 + len(params))
-        G, P = _static_struct(grads), _static_struct(params)
-        _attach_packed(ctx.field, P, params, True, False)
-        cfg = _cfg_struct(ctx.field, "ndc")
+            return (None,) * len(ctx.needs_input_grad)
+        (xn,), head, cot, G, tail, grads = _begin_backward(ctx, 1, _FEAT_TWICE, (g_dens, g_app),
+                                                           L.lib.rdrf_features_bwd_workspace_bytes)
         g_xn = torch.zeros_like(xn) if ctx.needs_input_grad[4] else None
-        g_dens = None if g_dens is None else L.f32c(g_dens)
-        g_app = None if g_app is None else L.f32c(g_app)
-        ws = L.workspace(dev, L.lib.rdrf_features_bwd_workspace_bytes(M))
-        L.check(L.lib.rdrf_static_features_bwd(C.byref(P), C.byref(cfg), L.ptr(xn), M, L.ptr(g_dens),
-                                               L.ptr(g_app), C.byref(G), L.ptr(g_xn), L.ptr(ctx.saved),
-                                               C.c_size_t(ctx.saved.numel()), L.ptr(ws), C.c_size_t(ws.numel()),
-                                               L.stream_of(xn)), "rdrf_static_features_bwd")
-        ctx.saved = None
-        if fused:
-            grads = [None] * len(params)
-        return (None, None, None, None, g_xn, *grads)
+        L.check(L.lib.rdrf_static_features_bwd(*head, *ctx.dims, *map(L.ptr, cot), G, L.ptr(g_xn), *tail), "rdrf_static_features_bwd")
+        return (None, None, None, None, g_xn, *_end_backward(ctx, grads))
 
 
 class _DynFeatFn(torch.autograd.Function):
@@ -516,55 +322,27 @@ class _DynFeatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, field, grad_mode, want, x_is_normalized, x, t, *params):
-        ctx.set_materialize_grads(False)
-        L.require_device(x, t)
-        x, t = L.f32c(x), L.f32c(t)
         M, dev = x.shape[0], x.device
+        head, tail, _ = _begin_forward(ctx, field, params, "ndc", (x, t), (M, int(x_is_normalized)),
+                                       lambda dev: _feat_saved(ctx, 1, M, dev, grad_mode),
+                                       lambda saving: L.lib.rdrf_features_workspace_bytes(M))
         dens = torch.empty(M, device=dev) if "density" in want else None
         blend = torch.empty(M, device=dev) if "blending" in want else None
         app = torch.empty(M, 27, device=dev) if "app" in want else None
         xp = torch.empty(M, 3, device=dev) if "warp" in want else None
-        ws = L.workspace(dev, L.lib.rdrf_features_workspace_bytes(M))
-        saved, sbytes = _feat_saved(ctx, 1, M, dev, grad_mode)
-        P = _dynamic_struct(params)
-        _attach_packed(field, P, params, False, True)
-        cfg = _cfg_struct(field, "ndc")
-        L.check(L.lib.rdrf_dynamic_features_fwd(C.byref(P), C.byref(cfg), L.ptr(x), L.ptr(t), M,
-                                                int(x_is_normalized), L.ptr(dens), L.ptr(blend), L.ptr(app),
-                                                L.ptr(xp), L.ptr(saved), C.c_size_t(sbytes), L.ptr(ws),
-                                                C.c_size_t(ws.numel()), L.stream_of(x)),
+        L.check(L.lib.rdrf_dynamic_features_fwd(*head, *ctx.dims, L.ptr(dens), L.ptr(blend), L.ptr(app), L.ptr(xp), *tail),
                 "rdrf_dynamic_features_fwd")
-        ctx.field, ctx.saved, ctx.norm = field, saved, int(x_is_normalized)
-        ctx.save_for_backward(x, t, *params)
         return dens, blend, app, xp
 
     @staticmethod
     def backward(ctx, g_dens, g_blend, g_app, g_xp):
-        x, t, *params = ctx.saved_tensors
         if all(g is None for g in (g_dens, g_blend, g_app, g_xp)):
-            return (None,) * (6 + len(params))
-        if ctx.saved is None:
-            raise L.RdrfError("compute_*: backward called twice (the saved activations were released)")
-        M, dev = x.shape[0], x.device
-        fused = ctx.field.fused_grad
-        ctx.field._det_bind()
-        grads = ctx.field.fused_grads() if fused else [torch.zeros_like(p) for p in params]
-        G, P = _dynamic_struct(grads), _dynamic_struct(params)
-        _attach_packed(ctx.field, P, params, True, True)
-        cfg = _cfg_struct(ctx.field, "ndc")
+            return (None,) * len(ctx.needs_input_grad)
+        (x, _), head, cot, G, tail, grads = _begin_backward(ctx, 2, _FEAT_TWICE, (g_dens, g_blend, g_app, g_xp),
+                                                            lambda M, norm: L.lib.rdrf_features_bwd_workspace_bytes(M))
         g_x = torch.zeros_like(x) if ctx.needs_input_grad[4] else None
-        c = lambda g: None if g is None else L.f32c(g)
-        g_dens, g_blend, g_app, g_xp = c(g_dens), c(g_blend), c(g_app), c(g_xp)
-        ws = L.workspace(dev, L.lib.rdrf_features_bwd_workspace_bytes(M))
-        L.check(L.lib.rdrf_dynamic_features_bwd(C.byref(P), C.byref(cfg), L.ptr(x), L.ptr(t), M, ctx.norm,
-                                                L.ptr(g_dens), L.ptr(g_blend), L.ptr(g_app), L.ptr(g_xp),
-                                                C.byref(G), L.ptr(g_x), L.ptr(ctx.saved),
-                                                C.c_size_t(ctx.saved.numel()), L.ptr(ws), C.c_size_t(ws.numel()),
-                                                L.stream_of(x)), "rdrf_dynamic_features_bwd")
-        ctx.saved = None
-        if fused:
-            grads = [None] * len(params)
-        return (None, None, None, None, g_x, None, *grads)
+        L.check(L.lib.rdrf_dynamic_features_bwd(*head, *ctx.dims, *map(L.ptr, cot), G, L.ptr(g_x), *tail), "rdrf_dynamic_features_bwd")
+        return (None, None, None, None, g_x, None, *_end_backward(ctx, grads))
 
 
 # --------------------------------------------------------------------------------------------
@@ -744,7 +522,6 @@ class TensorBase(nn.Module):
     def up_sampling_VM(self, plane_coef, line_coef, res_target):
         """models/tensoRF.py:199-221 / 814-836: bilinear (align_corners) resampling of a factor family to
         the new grid -- rdrf_upsample_bilinear, one launch for the six tensors, channel-last in and out."""
-        from .regularizers import _tensor4
         srcs, dsts = [], []
         for i in range(3):
             vec_id = VEC_MODE[i]
@@ -772,7 +549,13 @@ class TensorBase(nn.Module):
     # exchange all-reduces the flat buffer in place.  Off by default: plain autograd semantics
     # (torch.autograd.grad, retain_graph, ...) need freshly returned gradients.
     fused_grad = False
+    DYNAMIC = False    # which parameter struct and entry points this field takes (_params.field_structs)
     _pack_epoch = 0    # bumped by whoever writes the parameters through raw pointers (optim.FlatAdam): see _attach_packed
+
+    @property
+    def pack_cache(self):
+        """whether _params._attach_packed keeps packed weight images for this field: the module switch PACK_CACHE, read per call"""
+        return PACK_CACHE
 
     def invalidate_packed(self):
         """Drop the cached packed weight images.  Needed only after an MLP weight was edited in a way torch's version
@@ -823,16 +606,14 @@ class TensorBase(nn.Module):
             raise L.RdrfError("RDRF_DETERMINISTIC=1 needs the fused gradient buffers (field.fused_grad = True): only additions "
                               "into a bound flat buffer are order-independent")
         self.fused_grads()
-        L.check(L.lib.rdrf_det_bind(1 if isinstance(self, TensorVMSplit_TimeEmbedding) else 0, L.ptr(self._gflat),
-                                    C.c_size_t(self._gflat.numel()), L.ptr(self._det_shadow), L.stream_of(self._gflat)),
-                "rdrf_det_bind")
+        L.check(L.lib.rdrf_det_bind(int(self.DYNAMIC), L.ptr(self._gflat), self._gflat.numel(), L.ptr(self._det_shadow),
+                                    L.stream_of(self._gflat)), "rdrf_det_bind")
 
     def det_fold_(self):
         """fold the fixed-point shadow into the fp32 gradients (call before anything reads .grad); no-op otherwise"""
         if L.DETERMINISTIC and getattr(self, "_det_shadow", None) is not None:
             self._det_bind()
-            L.check(L.lib.rdrf_det_finish(1 if isinstance(self, TensorVMSplit_TimeEmbedding) else 0,
-                                          L.stream_of(self._gflat)), "rdrf_det_finish")
+            L.check(L.lib.rdrf_det_finish(int(self.DYNAMIC), L.stream_of(self._gflat)), "rdrf_det_finish")
 
     def flatten_params_(self):
         """Make every parameter a view of ONE flat fp32 buffer (same layout as the fused gradient buffer):
@@ -941,7 +722,7 @@ class TensorVMSplit(TensorBase):
         Under torch.no_grad() no backward can exist and nothing at all is saved."""
         if timeembeddings_chunk is not None:
             raise NotImplementedError("timeembeddings_chunk is None at every reference call site")
-        rgb, sigma, weight, dists = _StaticFn.apply(self, _call_mode(ray_type, rgb), rays_chunk, ts_chunk,
+        rgb, sigma, weight, dists = _StaticFn.apply(self, ray_type, *_call_modes(rgb), rays_chunk, ts_chunk,
                                                     xyz_sampled, z_vals, ray_valid, *self._param_list())
         return (None, None, None, xyz_sampled, weight, None, rgb, sigma, z_vals, dists)
 
@@ -955,6 +736,7 @@ class TensorVMSplit(TensorBase):
 
 class TensorVMSplit_TimeEmbedding(TensorBase):
     """Dynamic field (models/tensoRF.py:277-892)."""
+    DYNAMIC = True
 
     def __init__(self, aabb, gridSize, tSize, device, **kargs):
         super().__init__(aabb, gridSize, tSize, device, **kargs)
@@ -1018,7 +800,7 @@ class TensorVMSplit_TimeEmbedding(TensorBase):
         if timeembeddings_chunk is not None:
             raise NotImplementedError("timeembeddings_chunk is None at every reference call site")
         blending, weight, xyz_prime, rgb, sigma, dists = _DynamicFn.apply(
-            self, _call_mode(ray_type, rgb), rays_chunk, ts_chunk, xyz_sampled, z_vals, ray_valid,
+            self, ray_type, *_call_modes(rgb), rays_chunk, ts_chunk, xyz_sampled, z_vals, ray_valid,
             *self._param_list())
         return (None, None, blending, xyz_sampled, weight, xyz_prime, rgb, sigma, z_vals, dists)
 

@@ -2,7 +2,6 @@
 iteration -- each `coef * reduce(rho(x -+ y) * w) / Z` -- collected with LossTerms.add(...) and evaluated by
 LossTerms.total() in one reduction launch forward and one launch backward, instead of the 5-15 elementwise
 torch launches per term the expressions of train.py:1323-1421, 1522-1627, 1828-1832, 2293-2299 cost."""
-import ctypes as C
 
 import torch
 
@@ -85,7 +84,7 @@ class _FrameDepthLossFn(torch.autograd.Function):
         nb = int(L.lib.rdrf_frame_depth_loss_workspace_bytes(N, int(T)))
         ws = L.workspace(pred.device, nb)
         L.check(L.lib.rdrf_frame_depth_loss_fwd(L.ptr(pred), L.ptr(gt), L.ptr(frame), L.ptr(mask), N, int(T), float(coef),
-                                                L.ptr(out), L.ptr(g_raw), L.ptr(ws), C.c_size_t(nb), L.stream_of(pred)),
+                                                L.ptr(out), L.ptr(g_raw), L.ptr(ws), nb, L.stream_of(pred)),
                 "rdrf_frame_depth_loss_fwd")
         ctx.save_for_backward(g_raw, out)
         ctx.gscale = float(gscale)
@@ -96,7 +95,7 @@ class _FrameDepthLossFn(torch.autograd.Function):
         g_raw, out = ctx.saved_tensors
         g_pred = torch.empty_like(g_raw)
         L.check(L.lib.rdrf_frame_depth_loss_bwd(L.ptr(g_raw), L.ptr(out), L.ptr(L.f32c(g_loss.reshape(1))), g_raw.numel(),
-                                                C.c_float(ctx.gscale), L.ptr(g_pred), L.stream_of(g_raw)),
+                                                ctx.gscale, L.ptr(g_pred), L.stream_of(g_raw)),
                 "rdrf_frame_depth_loss_bwd")
         return g_pred, None, None, None, None, None, None
 

@@ -12,7 +12,6 @@ reduce-scatter -> Adam on the owned 1/G slice -> all-gather form: each rank keep
 only and updates 1/G of the parameters; both produce the same parameters.  The exchange of a field can be
 started as soon as that field's backward is complete (``begin_exchange(i)``), so the static field's
 reduce-scatter runs on RCCL's stream while the dynamic passes are still in their backward."""
-import ctypes as C
 
 import torch
 import torch.distributed as dist
@@ -95,8 +94,8 @@ class FlatAdam:
                                   "p.data = ... after construction): call FlatAdam.rebuild()")
             g, lo, n = self.ex.grads(i, st["g"])
             p = st["p"][lo: lo + n]
-            L.check(L.lib.rdrf_adam_step(L.ptr(p), L.ptr(g), L.ptr(st["m"]), L.ptr(st["v"]), C.c_size_t(n),
-                                         C.c_size_t(st["split"]), self.lr0, self.lr1, self.betas[0], self.betas[1],
+            L.check(L.lib.rdrf_adam_step(L.ptr(p), L.ptr(g), L.ptr(st["m"]), L.ptr(st["v"]), n,
+                                         st["split"], self.lr0, self.lr1, self.betas[0], self.betas[1],
                                          self.eps, self.t, scale, L.stream_of(p)), "rdrf_adam_step")
             gathers.append(self.ex.gather(i, st["p"]))
         for w in gathers:

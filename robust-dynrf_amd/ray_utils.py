@@ -1,6 +1,5 @@
 """Ray generation for the training path (train.py:96-103,1062-1077; dataLoader/ray_utils.py:53-140;
 camera.py:8-15) as one HIP kernel: flat ray ids + 6-D poses + focal -> NDC rays[N,6]."""
-import ctypes as C
 
 import torch
 
@@ -23,7 +22,7 @@ class _RayGenFn(torch.autograd.Function):
         N, T = ids.shape[0], poses9.shape[0]
         rays = torch.empty(N, 6, device=ids.device)
         L.check(L.lib.rdrf_generate_rays_uv(L.ptr(ids), L.ptr(uv), int(view_shift), L.ptr(poses9), L.ptr(focal), N, T,
-                                            H, W, int(ndc), C.c_float(near), L.ptr(rays), L.stream_of(rays)),
+                                            H, W, int(ndc), near, L.ptr(rays), L.stream_of(rays)),
                 "rdrf_generate_rays")
         ctx.meta = (H, W, int(ndc), float(near), int(view_shift))
         ctx.save_for_backward(ids, poses9, focal, uv)
@@ -38,7 +37,7 @@ class _RayGenFn(torch.autograd.Function):
         gp = torch.zeros_like(poses9)
         gf = torch.zeros_like(focal)
         L.check(L.lib.rdrf_generate_rays_uv_bwd(L.ptr(ids), L.ptr(uv), shift, L.ptr(poses9), L.ptr(focal), N, T, H, W,
-                                                ndc, C.c_float(near), L.ptr(g_rays), L.ptr(gp), L.ptr(gf),
+                                                ndc, near, L.ptr(g_rays), L.ptr(gp), L.ptr(gf),
                                                 L.stream_of(g_rays)), "rdrf_generate_rays_bwd")
         return None, gp, gf.reshape(ctx.focal_shape), None, None, None, None, None, None
 

@@ -11,6 +11,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from ._params import _vm_struct
 
 
 def _tensor4(x, g=None):
@@ -168,12 +169,11 @@ class _DenseL1Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, field, *xs):
-        from .fields import _vm_struct
         L.require_device(*xs)
         planes, lines = xs[:3], xs[3:]
         vm = _vm_struct(planes, lines)
         out = torch.empty(1, device=xs[0].device)
-        L.check(L.lib.rdrf_dense_l1_fwd(C.byref(vm), L.ACTS[field.fea2denseAct], C.c_float(float(field.density_shift)),
+        L.check(L.lib.rdrf_dense_l1_fwd(C.byref(vm), L.ACTS[field.fea2denseAct], float(field.density_shift),
                                         L.ptr(out), L.stream_of(xs[0])), "rdrf_dense_l1_fwd")
         ctx.field = field
         ctx.save_for_backward(*xs)
@@ -182,7 +182,6 @@ class _DenseL1Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .fields import _vm_struct
         xs = ctx.saved_tensors
         field = ctx.field
         fused = field.fused_grad
@@ -195,8 +194,7 @@ class _DenseL1Fn(torch.autograd.Function):
         vm, gvm = _vm_struct(xs[:3], xs[3:]), _vm_struct(grads[:3], grads[3:])
         g = L.f32c(g.reshape(1))
         L.check(L.lib.rdrf_dense_l1_bwd(C.byref(vm), C.byref(gvm), L.ACTS[field.fea2denseAct],
-                                        C.c_float(float(field.density_shift)), L.ptr(g), L.stream_of(xs[0])),
-                "rdrf_dense_l1_bwd")
+                                        float(field.density_shift), L.ptr(g), L.stream_of(xs[0])), "rdrf_dense_l1_bwd")
         return (None, *([None] * len(xs) if fused else grads))
 
 

@@ -7,6 +7,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib as L
+from ._params import field_structs, render_structs
 
 # the per-ray outputs of raw2outputs (renderer.py:173-315) that the eval loop keeps per frame (renderer.py:745-826):
 # rgb / depth / acc of the full, static (_s) and dynamic (_d) renders and the blending ("dynamicness") map
@@ -33,17 +34,17 @@ class _SampleFn(torch.autograd.Function):
         valid = torch.empty(N, S, dtype=torch.uint8, device=dev)
         if ray_type == "ndc":
             ab = (C.c_float * 6)(*aabb_host)
-            L.check(L.lib.rdrf_sample_ndc(L.ptr(rays), N, S, C.c_float(near), C.c_float(far),
+            L.check(L.lib.rdrf_sample_ndc(L.ptr(rays), N, S, near, far,
                                           L.ptr(jitter), ab, L.ptr(xyz), L.ptr(z), L.ptr(valid),
                                           L.stream_of(rays)), "rdrf_sample_ndc")
         elif ray_type == "contract":
-            L.check(L.lib.rdrf_sample_contract(L.ptr(rays), N, S, C.c_float(near), C.c_float(far),
+            L.check(L.lib.rdrf_sample_contract(L.ptr(rays), N, S, near, far,
                                                L.ptr(jitter), L.ptr(jitter_outer), L.ptr(xyz),
                                                L.ptr(z), L.ptr(valid), L.stream_of(rays)),
                     "rdrf_sample_contract")
         else:   # every other ray_type marches in world space (models/tensorBase.py:501-522); jitter: one value per ray
             ab = (C.c_float * 6)(*aabb_host)
-            L.check(L.lib.rdrf_sample_world(L.ptr(rays), N, S, C.c_float(near), C.c_float(far), C.c_float(step),
+            L.check(L.lib.rdrf_sample_world(L.ptr(rays), N, S, near, far, step,
                                             L.ptr(jitter), ab, L.ptr(xyz), L.ptr(z), L.ptr(valid),
                                             L.stream_of(rays)), "rdrf_sample_world")
             ctx.world = (ab, near, far)
@@ -67,7 +68,7 @@ class _SampleFn(torch.autograd.Function):
             g_xyz = None if g_xyz is None else L.f32c(g_xyz)
             g_z = None if g_z is None else L.f32c(g_z)
             ab, near, far = ctx.world
-            L.check(L.lib.rdrf_sample_world_bwd(L.ptr(rays), L.ptr(z), N, S, C.c_float(near), C.c_float(far), ab,
+            L.check(L.lib.rdrf_sample_world_bwd(L.ptr(rays), L.ptr(z), N, S, near, far, ab,
                                                 L.ptr(g_xyz), L.ptr(g_z), L.ptr(g_rays), L.stream_of(rays)),
                     "rdrf_sample_world_bwd")
             return (g_rays,) + none[1:]
@@ -235,6 +236,17 @@ def _maps_struct(bufs):
     return L.RenderMapsC(*[bufs[n].data_ptr() if n in bufs else None for n in L.RENDER_MAPS])
 
 
+def _map_outputs(maps, N, dev):
+    """the output buffers of a render by name -- the requested `maps`, else rgb and depth -- and the RdrfRenderMaps of them"""
+    bufs = _alloc_maps(_map_names(maps) if maps else ("rgb", "depth"), N, dev)
+    return bufs, _maps_struct(bufs)
+
+
+def _map_result(bufs, maps):
+    """what a render returns of _map_outputs' buffers: a RenderMaps with `maps`, else (rgb, depth)"""
+    return RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS}) if maps else (bufs["rgb"], bufs["depth"])
+
+
 def _motion_names(want):
     """True: all five; else an iterable of MotionMaps field names (the others are not computed)"""
     names = L.MOTION_MAPS if want is True else tuple(want)
@@ -294,7 +306,6 @@ def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc",
     apply_alpha_mask on the sampler's `valid` per field, the fields' forward and raw2outputs, bit for bit, and the density
     phase of a field runs on the samples its mask keeps only.  `kept`: an int64 device tensor [2] that receives the kept
     sample counts (static, dynamic).  No mode "fused" and no `motion` with masks."""
-    from .fields import _attach_packed, _cfg_struct, _dynamic_struct, _static_struct
     masks = _mask_pair(tensorf_static, tensorf, alpha_masks)
     if masks is None and kept is not None:
         raise ValueError("render_rays: `kept` is the masked render's output (alpha_masks)")
@@ -308,63 +319,45 @@ def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc",
     N = rays.shape[0]
     S = int(N_samples) if N_samples and N_samples > 0 else tensorf.nSamples
     dev = rays.device
-    if not maps:
-        rgb = torch.empty(N, 3, device=dev)
-        depth = torch.empty(N, device=dev)
-    nbytes = int(L.lib.rdrf_render_motion_workspace_bytes(N, S) if motion is not None else L.lib.rdrf_render_workspace_bytes(N, S))
-    ws = L.workspace(dev, nbytes)
-    ps_list, pd_list = tensorf_static._param_list(), tensorf._param_list()
-    PS, PD = _static_struct(ps_list), _dynamic_struct(pd_list)
-    _attach_packed(tensorf_static, PS, ps_list, False, False)   # packed once per (weights, stream), not per chunk
-    _attach_packed(tensorf, PD, pd_list, False, True)
-    cs, cd = _cfg_struct(tensorf_static, ray_type), _cfg_struct(tensorf, ray_type)
+    ws = L.workspace(dev, (L.lib.rdrf_render_motion_workspace_bytes if motion is not None else L.lib.rdrf_render_workspace_bytes)(N, S))
+    PS, cs, PD, cd = render_structs(tensorf_static, tensorf, ray_type)
+    head = (C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S)
     near, far = tensorf.near_far
     if masks is not None:
         if kept is not None and (kept.dtype != torch.int64 or kept.numel() != 2 or not kept.is_cuda or not kept.is_contiguous()):
             raise L.RdrfError("render_rays: `kept` is a contiguous int64 device tensor of two elements")
-        bufs = _alloc_maps(_map_names(maps), N, dev) if maps else {"rgb": rgb, "depth": depth}
-        M = _maps_struct(bufs)
+        bufs, M = _map_outputs(maps, N, dev)
         ms, md = (None if m is None else m._struct() for m in masks)
-        ws = L.workspace(dev, int(L.lib.rdrf_render_masked_ws_bytes(N, S)))
+        ws = L.workspace(dev, L.lib.rdrf_render_masked_ws_bytes(N, S))
         step = 0.0 if ray_type in L.RAY_TYPES else tensorf._step_host
-        L.check(L.lib.rdrf_render_masked_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S,
-                                             near, far, step, None if ms is None else C.byref(ms),
+        L.check(L.lib.rdrf_render_masked_fwd(*head, near, far, step, None if ms is None else C.byref(ms),
                                              None if md is None else C.byref(md), C.byref(M), L.ptr(kept), L.ptr(ws),
                                              ws.numel(), L.stream_of(rays)), "rdrf_render_masked_fwd")
-        return RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS}) if maps else (rgb, depth)
+        return _map_result(bufs, maps)
     if motion is not None:
         if ray_type not in L.RAY_TYPES:
             raise NotImplementedError("motion maps: ray_type must be 'ndc' or 'contract' (the reference projects no other, "
                                       "renderer.py:1335-1351)")
-        bufs = _alloc_maps(_map_names(maps), N, dev) if maps else {"rgb": rgb, "depth": depth}
-        M = _maps_struct(bufs)
+        bufs, M = _map_outputs(maps, N, dev)
         mbufs, MM, cams, keep = _motion_request(motion, N, dev)
-        L.check(L.lib.rdrf_render_motion_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S,
-                                             near, far, L.RENDER_MODES[mode], C.byref(M), C.byref(cams), C.byref(MM),
+        L.check(L.lib.rdrf_render_motion_fwd(*head, near, far, L.RENDER_MODES[mode], C.byref(M), C.byref(cams), C.byref(MM),
                                              L.ptr(ws), ws.numel(), L.stream_of(rays)), "rdrf_render_motion_fwd")
         del keep
-        out = RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS}) if maps else (rgb, depth)
-        return out, MotionMaps(**{n: mbufs.get(n) for n in L.MOTION_MAPS})
+        return _map_result(bufs, maps), MotionMaps(**{n: mbufs.get(n) for n in L.MOTION_MAPS})
     if ray_type not in L.RAY_TYPES:   # world-space rays: one entry point for the family, it carries the sampler's step
-        bufs = _alloc_maps(_map_names(maps), N, dev) if maps else {"rgb": rgb, "depth": depth}
-        M = _maps_struct(bufs)
-        L.check(L.lib.rdrf_render_world_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S, 0,
-                                            near, far, tensorf._step_host, L.RENDER_MODES[mode], C.byref(M), L.ptr(ws),
+        bufs, M = _map_outputs(maps, N, dev)
+        L.check(L.lib.rdrf_render_world_fwd(*head, 0, near, far, tensorf._step_host, L.RENDER_MODES[mode], C.byref(M), L.ptr(ws),
                                             ws.numel(), L.stream_of(rays), None, 0), "rdrf_render_world_fwd")
-        return RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS}) if maps else (rgb, depth)
+        return _map_result(bufs, maps)
+    bufs, M = _map_outputs(maps, N, dev)
     if maps:
-        names = _map_names(maps)
-        bufs = _alloc_maps(names, N, dev)
-        M = _maps_struct(bufs)
-        L.check(L.lib.rdrf_render_maps_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S,
-                                           near, far, L.RENDER_MODES[mode], C.byref(M), L.ptr(ws), ws.numel(),
+        L.check(L.lib.rdrf_render_maps_fwd(*head, near, far, L.RENDER_MODES[mode], C.byref(M), L.ptr(ws), ws.numel(),
                                            L.stream_of(rays)), "rdrf_render_maps_fwd")
-        return RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS})
-    fn = {"auto": L.lib.rdrf_render_fwd, "fused": L.lib.rdrf_render_fused_fwd, "sequence": L.lib.rdrf_render_sequence_fwd}[mode]
-    L.check(fn(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S, C.c_float(near),
-               C.c_float(far), L.ptr(rgb), L.ptr(depth), L.ptr(ws), C.c_size_t(ws.numel()), L.stream_of(rays)),
-            "rdrf_render_" + mode)
-    return rgb, depth
+    else:
+        fn = {"auto": L.lib.rdrf_render_fwd, "fused": L.lib.rdrf_render_fused_fwd, "sequence": L.lib.rdrf_render_sequence_fwd}[mode]
+        L.check(fn(*head, near, far, L.ptr(bufs["rgb"]), L.ptr(bufs["depth"]), L.ptr(ws), ws.numel(), L.stream_of(rays)),
+                "rdrf_render_" + mode)
+    return _map_result(bufs, maps)
 
 
 _stream_pool = {}
@@ -380,7 +373,6 @@ def render_chunks(tensorf_static, tensorf, rays, ts, chunk, N_samples=-1, ray_ty
     64-110 of the 256 CUs, so independent chunks run side by side.  Same bits as render_rays on the whole batch.
     Returns (rgb_map [N,3], depth_map [N]); with `maps`, a RenderMaps as render_rays (rdrf_render_chunks_maps_fwd).
     `alpha_masks` is not built here (render_rays has it)."""
-    from .fields import _attach_packed, _cfg_struct, _dynamic_struct, _static_struct
     if alpha_masks is not None and alpha_masks is not False:
         raise NotImplementedError("render_chunks: the native chunk loop reads no alpha masks (render_rays does).")
     L.require_device(rays, ts)
@@ -388,45 +380,32 @@ def render_chunks(tensorf_static, tensorf, rays, ts, chunk, N_samples=-1, ray_ty
     N, dev = rays.shape[0], rays.device
     S = int(N_samples) if N_samples and N_samples > 0 else tensorf.nSamples
     chunk = int(chunk)
-    if maps:
-        bufs = _alloc_maps(_map_names(maps), N, dev)
-        outs = list(bufs.values())
-    else:
-        rgb = torch.empty(N, 3, device=dev)
-        depth = torch.empty(N, device=dev)
-        outs = [rgb, depth]
+    bufs, M = _map_outputs(maps, N, dev)
     if N == 0:
-        return RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS}) if maps else (rgb, depth)
+        return _map_result(bufs, maps)
     ns = int(streams) if streams and streams > 1 and N > chunk else 0
-    ws = L.workspace(dev, int(L.lib.rdrf_render_chunks_workspace_bytes(min(chunk, N), S, max(ns, 1))))
-    ps_list, pd_list = tensorf_static._param_list(), tensorf._param_list()
-    PS, PD = _static_struct(ps_list), _dynamic_struct(pd_list)
-    _attach_packed(tensorf_static, PS, ps_list, False, False)   # one image each, packed on the current stream, shared
-    _attach_packed(tensorf, PD, pd_list, False, True)           # read-only by every side stream
-    cs, cd = _cfg_struct(tensorf_static, ray_type), _cfg_struct(tensorf, ray_type)
+    ws = L.workspace(dev, L.lib.rdrf_render_chunks_workspace_bytes(min(chunk, N), S, max(ns, 1)))
+    # one packed image per field, packed on the current stream, shared read-only by every side stream
+    PS, cs, PD, cd = render_structs(tensorf_static, tensorf, ray_type)
+    head = (C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S)
     near, far = tensorf.near_far
     pool = _stream_pool.get((dev, ns))
     if pool is None:
         pool = _stream_pool[(dev, ns)] = [torch.cuda.Stream(device=dev) for _ in range(ns)]
     arr = (C.c_void_p * max(ns, 1))(*[st.cuda_stream for st in pool]) if ns else None
     if ray_type not in L.RAY_TYPES:   # world-space rays (see render_rays)
-        M = _maps_struct(bufs if maps else {"rgb": rgb, "depth": depth})
-        L.check(L.lib.rdrf_render_world_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S,
-                                            chunk, near, far, tensorf._step_host, 0, C.byref(M), L.ptr(ws), ws.numel(),
+        L.check(L.lib.rdrf_render_world_fwd(*head, chunk, near, far, tensorf._step_host, 0, C.byref(M), L.ptr(ws), ws.numel(),
                                             L.stream_of(rays), arr, ns), "rdrf_render_world_fwd")
     elif maps:
-        M = _maps_struct(bufs)
-        L.check(L.lib.rdrf_render_chunks_maps_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N,
-                                                  S, chunk, near, far, C.byref(M), L.ptr(ws), ws.numel(), L.stream_of(rays),
+        L.check(L.lib.rdrf_render_chunks_maps_fwd(*head, chunk, near, far, C.byref(M), L.ptr(ws), ws.numel(), L.stream_of(rays),
                                                   arr, ns), "rdrf_render_chunks_maps_fwd")
     else:
-        L.check(L.lib.rdrf_render_chunks_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S,
-                                             chunk, C.c_float(near), C.c_float(far), L.ptr(rgb), L.ptr(depth), L.ptr(ws),
-                                             C.c_size_t(ws.numel()), L.stream_of(rays), arr, ns), "rdrf_render_chunks_fwd")
+        L.check(L.lib.rdrf_render_chunks_fwd(*head, chunk, near, far, L.ptr(bufs["rgb"]), L.ptr(bufs["depth"]), L.ptr(ws),
+                                             ws.numel(), L.stream_of(rays), arr, ns), "rdrf_render_chunks_fwd")
     for st in pool:   # the caching allocator must not hand these buffers to another stream's request while the side
-        for t in [rays, ts, ws] + outs:   # streams may still read / write them
+        for t in [rays, ts, ws, *bufs.values()]:   # streams may still read / write them
             t.record_stream(st)
-    return RenderMaps(**{n: bufs.get(n) for n in L.RENDER_MAPS}) if maps else (rgb, depth)
+    return _map_result(bufs, maps)
 
 
 def _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, chunk, maps, motion=None, alpha_masks=None):
@@ -565,7 +544,6 @@ def render_view(tensorf_static, tensorf, c2w, focal, H, W, t, N_samples=-1, ray_
 def _track_points_raw(tensorf, pts, ts, n_fwd, n_bwd, dt, cameras, focal, H, W, ray_type, want, bufs=None, ws=None):
     """rdrf_track_points_fwd on checked arguments.  want: subset of L.TRACK_OUTPUTS; bufs / ws: caller-owned output
     buffers by name and workspace (the tests poison them), else allocated here.  Returns the buffers by name."""
-    from .fields import _attach_packed, _cfg_struct, _dynamic_struct
     L.require_device(pts, ts, cameras)
     pts, ts = L.f32c(pts.detach()), L.f32c(ts.detach())
     M, K, dev = pts.shape[0], n_bwd + 1 + n_fwd, pts.device
@@ -580,13 +558,10 @@ def _track_points_raw(tensorf, pts, ts, n_fwd, n_bwd, dt, cameras, focal, H, W, 
         cams = L.TrackCamsC(int(H), int(W), int(cameras.shape[0]), f.data_ptr(), cameras.data_ptr())
         keep = (cameras, f)
     out = L.TracksC(*[bufs[n].data_ptr() if n in want else None for n in L.TRACK_OUTPUTS])
-    params = tensorf._param_list()
-    P = _dynamic_struct(params)
-    _attach_packed(tensorf, P, params, False, True)
-    cfg = _cfg_struct(tensorf, ray_type)
+    P, cfg = field_structs(tensorf, tensorf._param_list(), ray_type)
     if ws is None:
-        ws = L.workspace(dev, int(L.lib.rdrf_track_ws_bytes(M, K)))
-    L.check(L.lib.rdrf_track_points_fwd(C.byref(P), C.byref(cfg), L.ptr(pts), L.ptr(ts), M, int(n_fwd), int(n_bwd), C.c_float(dt),
+        ws = L.workspace(dev, L.lib.rdrf_track_ws_bytes(M, K))
+    L.check(L.lib.rdrf_track_points_fwd(C.byref(P), C.byref(cfg), L.ptr(pts), L.ptr(ts), M, int(n_fwd), int(n_bwd), dt,
                                         None if cams is None else C.byref(cams), C.byref(out), L.ptr(ws), ws.numel(),
                                         L.stream_of(pts)), "rdrf_track_points_fwd")
     del keep
@@ -637,7 +612,6 @@ def render_tracks(tensorf_static, tensorf, poses9, focal, frame, pixels, H, W, s
     sum_s weights_d xyz + (1 - acc_d) far of its ray, and track_points follows it through the frames
     frame - span .. frame + span clipped to [0, T - 1] (span None: the whole video; a pair: (backward, forward)), projected
     into those frames' cameras.  Returns (Tracks, acc_d [M]): a seed with a small acc_d sits in static or empty space."""
-    from .fields import _attach_packed, _cfg_struct, _dynamic_struct, _static_struct
     from .ray_utils import generate_rays, pose_to_mtx
     if ray_type not in L.RAY_TYPES:
         raise NotImplementedError("render_tracks: ray_type must be 'ndc' or 'contract' (the reference projects no other, "
@@ -662,12 +636,8 @@ def render_tracks(tensorf_static, tensorf, poses9, focal, frame, pixels, H, W, s
     seeds = torch.empty(M, 3, device=dev)
     bufs = _alloc_maps(("acc_d",), M, dev)
     if M:
-        ws = L.workspace(dev, int(L.lib.rdrf_render_motion_workspace_bytes(M, S)))
-        ps_list, pd_list = tensorf_static._param_list(), tensorf._param_list()
-        PS, PD = _static_struct(ps_list), _dynamic_struct(pd_list)
-        _attach_packed(tensorf_static, PS, ps_list, False, False)
-        _attach_packed(tensorf, PD, pd_list, False, True)
-        cs, cd = _cfg_struct(tensorf_static, ray_type), _cfg_struct(tensorf, ray_type)
+        ws = L.workspace(dev, L.lib.rdrf_render_motion_workspace_bytes(M, S))
+        PS, cs, PD, cd = render_structs(tensorf_static, tensorf, ray_type)
         near, far = tensorf.near_far
         Mp = _maps_struct(bufs)
         L.check(L.lib.rdrf_render_track_seeds_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), M, S,
@@ -850,7 +820,7 @@ class _DistLossFn(torch.autograd.Function):
                 L.require_device(interval)
                 ipt, interval = L.f32c(interval).reshape(N, S), 0.0
         loss_ray = torch.empty(N, device=w.device)
-        L.check(L.lib.rdrf_distloss_fwd(L.ptr(w), L.ptr(m), C.c_float(float(interval)), L.ptr(ipt), N, S,
+        L.check(L.lib.rdrf_distloss_fwd(L.ptr(w), L.ptr(m), float(interval), L.ptr(ipt), N, S,
                                         L.ptr(loss_ray), L.stream_of(w)), "rdrf_distloss_fwd")
         ctx.interval, ctx.ipt = float(interval), ipt
         ctx.save_for_backward(w, m)
@@ -861,7 +831,7 @@ class _DistLossFn(torch.autograd.Function):
         w, m = ctx.saved_tensors
         N, S = w.shape
         g_w = torch.zeros_like(w)
-        L.check(L.lib.rdrf_distloss_bwd(L.ptr(w), L.ptr(m), C.c_float(ctx.interval), L.ptr(ctx.ipt), N, S,
+        L.check(L.lib.rdrf_distloss_bwd(L.ptr(w), L.ptr(m), ctx.interval, L.ptr(ctx.ipt), N, S,
                                         L.ptr(L.f32c(g_ray)), L.ptr(g_w), L.stream_of(w)), "rdrf_distloss_bwd")
         return g_w, None, None
 

@@ -22,11 +22,11 @@ def test_entry_points_are_declared_bound_and_exported():
     hdr = open(os.path.join(ROOT, "include", "rodynrf.h")).read()
     declared = set(re.findall(r"\b(rdrf_[a-z0-9_]+)\s*\(", hdr))
     src = _lib_source()
-    symbols = re.search(r"SYMBOLS = \[(.*?)\]", src, re.S).group(1)
+    table = re.search(r"^SIGNATURES = \{\n(.*?)^\}", src, re.S | re.M).group(1)   # name -> (restype, argtypes); _load applies it
+    assert re.search(r"^SYMBOLS = list\(SIGNATURES\)$", src, re.M), "_lib.SYMBOLS is not the signature table's key list"
     for sym in NEW:
         assert sym in declared, f"{sym} is not declared in include/rodynrf.h"
-        assert f'"{sym}"' in symbols, f"{sym} is not listed in _lib.SYMBOLS"
-        assert f"lib.{sym}.argtypes" in src, f"{sym} has no ctypes signature"
+        assert re.search(rf'^    "{sym}": \(\w+, \[\w', table, re.M), f"{sym} has no ctypes signature (and so is not in _lib.SYMBOLS)"
     for so in ("librodynrf.so", "librodynrf_det.so"):
         lib = C.CDLL(os.path.join(PKG, so))
         for sym in NEW:

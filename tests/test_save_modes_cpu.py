@@ -56,11 +56,12 @@ def test_no_app_buffer_is_the_full_one_minus_the_appearance_block(N, S):
 
 
 def test_call_mode_round_trip():
+    """the (rgb mode, grad mode) pair the field modules hand to their autograd Function as arguments of their own: the
+    rgb mode as given, the grad mode of the caller"""
     F, _ = _mods()
-    for rt in ("ndc", "contract"):
-        for rgb in (True, False, "value"):
-            assert F._parse_mode(F._call_mode(rt, rgb)) == (rt, rgb, True)
-            with torch.no_grad():
-                assert F._parse_mode(F._call_mode(rt, rgb)) == (rt, rgb, False)
+    for rgb in (True, False, "value"):
+        assert F._call_modes(rgb) == (rgb, True) and F._call_modes(rgb)[0] is rgb
+        with torch.no_grad():
+            assert F._call_modes(rgb) == (rgb, False) and F._call_modes(rgb)[0] is rgb
     with pytest.raises(ValueError):
-        F._call_mode("ndc", "values")
+        F._call_modes("values")
