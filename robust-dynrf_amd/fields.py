@@ -29,6 +29,10 @@ MAT_MODE = [[0, 1], [0, 2], [1, 2]]
 # packed weight images (_params._attach_packed): handed to the entry points instead of a re-pack per call; 0 switches them off
 PACK_CACHE = os.environ.get("RDRF_PACK_CACHE", "1") == "1"
 VEC_MODE = [2, 1, 0]
+# the 10-tuple both fields' forward returns, in the reference's order (models/tensorBase.py:814-850): per-sample tensors
+# [N,S(,3)]; the static field has no blending / xyz_prime (None), rgb is None under forward(rgb=False)
+FieldOut = collections.namedtuple("FieldOut", ("unused0", "unused1", "blending", "xyz_sampled", "weight", "xyz_prime", "rgb",
+                                               "sigma", "z_vals", "dists"))
 
 
 # --------------------------------------------------------------------------------------------
@@ -724,7 +728,7 @@ class TensorVMSplit(TensorBase):
             raise NotImplementedError("timeembeddings_chunk is None at every reference call site")
         rgb, sigma, weight, dists = _StaticFn.apply(self, ray_type, *_call_modes(rgb), rays_chunk, ts_chunk,
                                                     xyz_sampled, z_vals, ray_valid, *self._param_list())
-        return (None, None, None, xyz_sampled, weight, None, rgb, sigma, z_vals, dists)
+        return FieldOut(None, None, None, xyz_sampled, weight, None, rgb, sigma, z_vals, dists)
 
     @torch.no_grad()
     def upsample_volume_grid(self, res_target):
@@ -802,7 +806,7 @@ class TensorVMSplit_TimeEmbedding(TensorBase):
         blending, weight, xyz_prime, rgb, sigma, dists = _DynamicFn.apply(
             self, ray_type, *_call_modes(rgb), rays_chunk, ts_chunk, xyz_sampled, z_vals, ray_valid,
             *self._param_list())
-        return (None, None, blending, xyz_sampled, weight, xyz_prime, rgb, sigma, z_vals, dists)
+        return FieldOut(None, None, blending, xyz_sampled, weight, xyz_prime, rgb, sigma, z_vals, dists)
 
     # models/tensoRF.py:378-416 (the reference's dynamic class has no vector_comp_diffs)
     def density_L1(self):

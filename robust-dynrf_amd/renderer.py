@@ -12,6 +12,10 @@ from ._params import field_structs, render_structs
 # the per-ray outputs of raw2outputs (renderer.py:173-315) that the eval loop keeps per frame (renderer.py:745-826):
 # rgb / depth / acc of the full, static (_s) and dynamic (_d) renders and the blending ("dynamicness") map
 RenderMaps = namedtuple("RenderMaps", L.RENDER_MAPS)
+# the thirteen per-ray outputs of raw2outputs in the reference's order (renderer.py:301-315): colour [N,3], depth [N], acc [N]
+# and sample weights [N,S] of the full, the static (_s) and the dynamic (_d) render, then the blending map
+RayMaps = namedtuple("RayMaps", ("rgb", "depth", "acc", "weights", "rgb_s", "depth_s", "acc_s", "weights_s", "rgb_d", "depth_d",
+                                 "acc_d", "weights_d", "dynamicness"))
 # the motion maps of the per-frame render (renderer.py:487-537, :610): induced optical flow to the next / previous frame
 # through the scene-flow MLP (flow_f, flow_b) and through camera motion alone (flow_s_f, flow_s_b), [N,2] pixels, and the
 # warp displacement sum_s weights_d (xyz_prime - xyz) [N,3]
@@ -192,8 +196,8 @@ def raw2outputs(rgb_s, sigma_s, rgb_d, sigma_d, dists, blending, z_vals, rays_ch
     kernels read when they run."""
     if add_white_bg is None:
         add_white_bg = bool(is_train and (torch.rand((1,)) < 0.5).item())
-    return _CompositeFn.apply(rgb_s, sigma_s, rgb_d, sigma_d, dists, blending, z_vals, rays_chunk,
-                              ray_type, add_white_bg if torch.is_tensor(add_white_bg) else bool(add_white_bg))
+    return RayMaps(*_CompositeFn.apply(rgb_s, sigma_s, rgb_d, sigma_d, dists, blending, z_vals, rays_chunk,
+                                       ray_type, add_white_bg if torch.is_tensor(add_white_bg) else bool(add_white_bg)))
 
 
 def OctreeRender_trilinear_fast(rays, ts, timeembeddings, tensorf, xyz_sampled, z_vals_input,

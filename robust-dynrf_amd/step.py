@@ -30,20 +30,22 @@ Trainer.fit / save / load are the run around the iteration (resolution schedule,
 every term that decides which hot-path outputs carry gradient; there is no per-iteration host sync (``.item()``): losses and the per-frame medians stay on the device.
 """
 import collections
+import itertools
 import math
 import os
 import types
+from typing import NamedTuple, Optional, Union
 
 import torch
 import torch.nn as nn
 
-from .fields import TensorVMSplit, TensorVMSplit_TimeEmbedding
+from .fields import FieldOut, TensorVMSplit, TensorVMSplit_TimeEmbedding
 from .optim import FlatAdam
 from .parallel import require_even_shards
 from .ray_utils import gather_rows, generate_rays, ids2pixel, pose_to_mtx
 from .regularizers import TVLoss
 from .losses import LossTerms, frame_depth_loss
-from .renderer import distloss_rays, induce_flow, raw2outputs, sampleXYZ
+from .renderer import RayMaps, distloss_rays, induce_flow, raw2outputs, sampleXYZ
 
 NDC_AABB = [[-1.5, -1.67, -1.0], [1.5, 1.67, 1.0]]
 
@@ -170,7 +172,7 @@ def sparsify_(st, dy, cfg, device, target=0.10, n_probe=1024):
         with torch.no_grad():
             xyz, z, valid = sampleXYZ(dy, rays, cfg["n_samples"], ray_type=cfg["ray_type"], is_train=False)
             o = field(rays, ts, None, xyz, z, valid, ray_type=cfg["ray_type"])
-            return float((o[4] > 1e-4).float().mean())
+            return float((o.weight > 1e-4).float().mean())
 
     with torch.no_grad():
         base = [p.detach().clone() for p in st.density_plane]
@@ -335,44 +337,31 @@ def _rgb_or_zeros(rgb, like):
     return rgb if rgb is not None else torch.zeros(*like.shape, 3, device=like.device)
 
 
-def ray_pass(st, dy, rays, ts, n_samples, ray_type, rng, is_train=True, static_grad=False, dynamic=True, rgb_s=True,
-             rgb_d=True):
-    """sampleXYZ -> static -> dynamic -> raw2outputs (one ray-pass).  The static field runs value-only unless
-    `static_grad`; with dynamic=False (dead work of passes E / P3 / P4 skipped) zeros stand in for the dynamic
-    outputs, which the static maps do not depend on; rgb_s / rgb_d = False: that field's colours are not consumed by
-    any loss of this pass (passes B-D, P1-P4) and its appearance phase is not run; "value": computed, as values only
-    (fields.TensorVMSplit.forward).  With static_grad the dynamic evaluation is the dead work of passes E / P3 / P4: its
-    outputs feed maps no loss reads, and the only gradient that can reach it is that of `dists` for the rays / z_vals.  It
-    then saves no appearance rows, and when neither rays nor z_vals require grad (fixed poses) it runs under no_grad and
-    saves nothing -- rows are saved only where a backward can read them."""
-    jit, jit_o = rng.jitter(n_samples, ray_type, rays.device) if is_train else (None, None)
-    xyz, z, valid = sampleXYZ(dy, rays, n_samples, ray_type=ray_type, is_train=is_train, jitter=jit,
-                              jitter_outer=jit_o)
-    PASSES.update(static=1, static_grad=int(static_grad), dynamic=int(dynamic), dynamic_dead=int(dynamic and static_grad))
-    if static_grad:
-        o_s = st(rays, ts, None, xyz, z, valid, is_train=is_train, ray_type=ray_type, rgb=rgb_s)
-    else:
-        with torch.no_grad():
-            o_s = st(rays, ts, None, xyz, z, valid, is_train=is_train, ray_type=ray_type, rgb=rgb_s)
-    sigma_s = o_s[7]
-    rgb_s = _rgb_or_zeros(o_s[6], sigma_s)
-    if dynamic:   # in passes E / P3 / P4 this evaluation is dead work the reference performs (autograd graph and all)
-        dead = static_grad
-        if dead and rgb_d is True:
-            rgb_d = "value"
-        with torch.set_grad_enabled(torch.is_grad_enabled() and (not dead or rays.requires_grad or z.requires_grad)):
-            o_d = dy(rays, ts, None, xyz, z, valid, is_train=is_train, ray_type=ray_type, rgb=rgb_d)
-        rgb_d, sigma_d, dists, blending, zv = _rgb_or_zeros(o_d[6], o_d[7]), o_d[7], o_d[9], o_d[2], o_d[8]
-    else:
-        o_d = None
-        rgb_d = torch.zeros_like(rgb_s)
-        sigma_d = torch.zeros_like(sigma_s)
-        blending = torch.zeros_like(sigma_s)
-        dists, zv = o_s[9], z
-    white = rng.coin() if is_train else False
-    outs = raw2outputs(rgb_s, sigma_s, rgb_d, sigma_d, dists, blending, zv, rays, is_train=is_train,
-                       ray_type=ray_type, add_white_bg=white)
-    return o_s, o_d, outs, xyz
+class Pass(NamedTuple):
+    """One ray-pass as run_passes evaluates it: sample the rays, static field, dynamic field, composite."""
+    rays: torch.Tensor
+    ts: torch.Tensor
+    static_grad: bool = False   # the static call: value-only (under no_grad) or with gradient
+    # the dynamic call: "live"; "dead" -- the dead work of passes E / P3 / P4 the reference performs: its outputs feed maps no
+    # loss reads, the only gradient that can reach it is that of `dists` for the rays / z_vals, so its colours are values at
+    # most and it runs under no_grad unless the rays or z_vals require grad; None -- absent, zeros stand in for its outputs
+    dynamic: Optional[str] = "live"
+    # colour flag of each field's call (fields.TensorVMSplit.forward): False -- no loss of this pass consumes that field's
+    # colours and its appearance phase is not run (passes B-D, P1-P4); "value" -- computed, as values only
+    rgb_s: Union[bool, str] = True
+    rgb_d: Union[bool, str] = True
+    static_box: bool = False    # the rays are sampled in the static field's box (P1 / P2), not in the dynamic field's
+    composite: bool = True      # raw2outputs and its white-background coin; P1 / P2 read the static weights only
+
+
+class PassOut(NamedTuple):
+    """What run_passes returns per pass; the first four entries are ray_pass's tuple."""
+    o_s: FieldOut
+    o_d: Optional[FieldOut]     # None: no dynamic call
+    maps: Optional[RayMaps]     # None: the pass does not composite
+    xyz: torch.Tensor
+    z: torch.Tensor
+    rays: torch.Tensor
 
 
 # samples one batched field call may cover: beyond a few million the per-call buffers (saved rows: ~6 KB per sample)
@@ -389,67 +378,90 @@ def batch_groups(idxs, n_samples_per_pass):
     return [idxs[i:i + per] for i in range(0, len(idxs), per)]
 
 
-def batched_field(field, rays_list, ts_list, samples, idxs, ray_type, grad=True, rgb=True):
-    """`field` over the concatenated rays / samples of the passes `idxs` in ONE call; returns the 10-tuple of each pass
+def batched_field(field, rays_list, ts_list, samples, idxs, ray_type, grad=True, rgb=True, is_train=True):
+    """`field` over the concatenated rays / samples of the passes `idxs` in ONE call; returns the FieldOut of each pass
     (views of the batched outputs: unbind, whose backward stacks the per-pass gradients)"""
     if len(idxs) == 1:
         k = idxs[0]
         with torch.set_grad_enabled(grad and torch.is_grad_enabled()):
-            return [field(rays_list[k], ts_list[k], None, *samples[k], is_train=True, ray_type=ray_type, rgb=rgb)]
+            return [field(rays_list[k], ts_list[k], None, *samples[k], is_train=is_train, ray_type=ray_type, rgb=rgb)]
     N = rays_list[idxs[0]].shape[0]
     cat = lambda ts: torch.cat([ts[k] for k in idxs])
     with torch.set_grad_enabled(grad and torch.is_grad_enabled()):
         o = field(cat(rays_list), cat(ts_list), None, *(torch.cat([samples[k][i] for k in idxs]) for i in range(3)),
-                  is_train=True, ray_type=ray_type, rgb=rgb)
+                  is_train=is_train, ray_type=ray_type, rgb=rgb)
     parts = [None if t is None else t.view(len(idxs), N, *t.shape[1:]).unbind(0) for t in o]
-    return [tuple(None if pt is None else pt[j] for pt in parts) for j in range(len(idxs))]
+    return [FieldOut(*(None if pt is None else pt[j] for pt in parts)) for j in range(len(idxs))]
 
 
-def ray_passes(st, dy, rays_list, ts_list, n_samples, ray_type, rng, groups, rgb=None):
-    """Several ray-passes whose inputs do not depend on each other's outputs (passes A-D of an iteration: the rays of
-    C / D come from the data's optical flow, not from pass A), evaluated as ONE value-only static forward over all their
-    rays and one dynamic forward per GROUP of passes (lists of consecutive pass indices with the same gradient
-    liveness, so that a batched call prunes what each of its passes would).  Same arithmetic and the same draw order
-    (jitter, coin per pass, in pass order) as one ray_pass per entry; the persistent MLP kernels see 3-4x the tiles per
-    launch (tail quantisation: 2.4 -> 3 tile rounds per wave becomes 7.3 -> 8) and fill their LDS images once.
-    Calls are capped at BATCH_MAX_SAMPLES samples.  rgb (list of True | False | "value" per pass, default all True): passes
-    whose colours no loss consumes run both fields without their appearance phase (False) or with colours that are values
-    only and save no appearance rows ("value"); the static call is cut at the flag changes.
-    Returns one (o_s, o_d, outs, xyz) per pass; the per-pass tensors are views (unbind) of the batched outputs."""
-    P, N, dev = len(rays_list), rays_list[0].shape[0], rays_list[0].device
-    PASSES.update(static=P, dynamic=P)
+def run_passes(st, dy, plan, n_samples, ray_type, rng, groups=None, batch=True, is_train=True):
+    """The ray-passes `plan` (a list of Pass) whose inputs do not depend on each other's outputs (passes A-D of an
+    iteration: the rays of C / D come from the data's optical flow, not from pass A; P1-P4 of the pose block), evaluated
+    as few, large field calls: the persistent MLP kernels see 3-4x the tiles per launch (tail quantisation: 2.4 -> 3 tile
+    rounds per wave becomes 7.3 -> 8) and fill their LDS images once.  Same arithmetic as one call per pass and field.
+    Draws: up front in pass order, the jitter of every pass, then the coin of a compositing one (none with is_train=False).
+    Static calls: one per maximal run of passes with the same gradient mode and colour flag (a value-only call computes
+    "value" and True alike).  Dynamic calls: one per entry of `groups`, lists of consecutive pass indices of equal gradient
+    liveness, so that a batched call prunes what each of its passes would (default: every pass with a dynamic call alone).
+    Every call is capped at BATCH_MAX_SAMPLES samples; batch=False cuts every run and group into single passes (per-pass
+    calls take the ray-tile scatter, batched ones the sorted one).  Returns one PassOut per pass; the per-pass tensors of a
+    batched call are views (unbind) of its outputs."""
+    P = len(plan)
+    rays_list, ts_list = [p.rays for p in plan], [p.ts for p in plan]
     samples, coins = [], []
-    for rays in rays_list:
-        jit, jit_o = rng.jitter(n_samples, ray_type, dev)
-        samples.append(sampleXYZ(dy, rays, n_samples, ray_type=ray_type, is_train=True, jitter=jit, jitter_outer=jit_o))
-        coins.append(rng.coin())
-    ns = N * samples[0][1].shape[1]
-    rgb = [True] * P if rgb is None else list(rgb)
-    o_ss, o_ds = [None] * P, [None] * P
-    runs, lo = [], 0   # maximal runs of passes with the same colour flag: one static call each
-    want_s = [bool(f) for f in rgb]   # (the static call is value-only: "value" and True are the same call there)
-    for p in range(1, P + 1):
-        if p == P or want_s[p] != want_s[lo]:
-            runs.append(list(range(lo, p)))
-            lo = p
-    for run in runs:
-        for g in batch_groups(run, ns):
-            for k, o in zip(g, batched_field(st, rays_list, ts_list, samples, g, ray_type, grad=False, rgb=want_s[run[0]])):
-                o_ss[k] = o
+    for p in plan:
+        jit, jit_o = rng.jitter(n_samples, ray_type, p.rays.device) if is_train else (None, None)
+        samples.append(sampleXYZ(st if p.static_box else dy, p.rays, n_samples, ray_type=ray_type, is_train=is_train,
+                                 jitter=jit, jitter_outer=jit_o))
+        coins.append(rng.coin() if is_train and p.composite else False)
+        PASSES.update(static=1, static_grad=int(p.static_grad), dynamic=int(p.dynamic is not None),
+                      dynamic_dead=int(p.dynamic == "dead"))
+    ns = rays_list[0].shape[0] * samples[0][1].shape[1]
+    cut = (lambda idxs: batch_groups(idxs, ns)) if batch else (lambda idxs: [[k] for k in idxs])
+    o_s, o_d = [None] * P, [None] * P
+
+    def call(field, outs, idxs, grad, rgb, dead=False):
+        for g in cut(idxs):
+            if dead:   # gradient only where `dists` can carry one to the rays / z_vals
+                grad = any(rays_list[k].requires_grad or samples[k][1].requires_grad for k in g)
+            outs[g[0]: g[-1] + 1] = batched_field(field, rays_list, ts_list, samples, g, ray_type, grad=grad, rgb=rgb,
+                                                  is_train=is_train)
+
+    mode_s = lambda k: (plan[k].static_grad, plan[k].rgb_s if plan[k].static_grad else bool(plan[k].rgb_s))
+    for (grad, rgb), run in itertools.groupby(range(P), key=mode_s):
+        call(st, o_s, list(run), grad, rgb)
+    mode_d = lambda k: (plan[k].dynamic, "value" if plan[k].dynamic == "dead" and plan[k].rgb_d is True else plan[k].rgb_d)
+    groups = [[k] for k in range(P) if plan[k].dynamic is not None] if groups is None else groups
+    assert [k for g in groups for k in g] == [k for k in range(P) if plan[k].dynamic is not None], "every dynamic call in one group"
     for group in groups:
         assert list(group) == list(range(group[0], group[0] + len(group)))
-        assert all(rgb[k] == rgb[group[0]] for k in group), "a dynamic group must agree on its colour flag"
-        for g in batch_groups(group, ns):
-            for k, o in zip(g, batched_field(dy, rays_list, ts_list, samples, g, ray_type, rgb=rgb[group[0]])):
-                o_ds[k] = o
+        assert all(mode_d(k) == mode_d(group[0]) for k in group), "a dynamic group must agree on liveness and colour flag"
+        kind, rgb = mode_d(group[0])
+        call(dy, o_d, group, True, rgb, dead=kind == "dead")
     out = []
-    for p in range(P):
-        o_sp, o_d = o_ss[p], o_ds[p]
-        outs = raw2outputs(_rgb_or_zeros(o_sp[6], o_sp[7]), o_sp[7], _rgb_or_zeros(o_d[6], o_d[7]), o_d[7], o_d[9], o_d[2],
-                           o_d[8], rays_list[p], is_train=True,
-                           ray_type=ray_type, add_white_bg=coins[p])
-        out.append((o_sp, o_d, outs, samples[p][0]))
+    for k, p in enumerate(plan):
+        s, d, (xyz, z, _) = o_s[k], o_d[k], samples[k]
+        maps = None
+        if p.composite:
+            if d is None:   # zeros stand in for the dynamic outputs, which the static maps do not depend on
+                zero = torch.zeros_like(s.sigma)
+                dyn = (_rgb_or_zeros(None, zero), zero, s.dists, zero, z)
+            else:
+                dyn = (_rgb_or_zeros(d.rgb, d.sigma), d.sigma, d.dists, d.blending, d.z_vals)
+            maps = raw2outputs(_rgb_or_zeros(s.rgb, s.sigma), s.sigma, *dyn, p.rays, is_train=is_train, ray_type=ray_type,
+                               add_white_bg=coins[k])
+        out.append(PassOut(s, d, maps, xyz, z, p.rays))
     return out
+
+
+def ray_pass(st, dy, rays, ts, n_samples, ray_type, rng, is_train=True, static_grad=False, dynamic=True, rgb_s=True,
+             rgb_d=True):
+    """sampleXYZ -> static -> dynamic -> raw2outputs: one ray-pass through run_passes -> (o_s, o_d, outs, xyz).  The static
+    field runs value-only unless `static_grad`; with static_grad the dynamic evaluation is the dead work of passes E / P3 /
+    P4 (Pass.dynamic "dead"), dynamic=False skips it; rgb_s / rgb_d: Pass.  is_train=False takes no draw."""
+    kind = ("dead" if static_grad else "live") if dynamic else None
+    out, = run_passes(st, dy, [Pass(rays, ts, static_grad, kind, rgb_s, rgb_d)], n_samples, ray_type, rng, is_train=is_train)
+    return tuple(out[:4])
 
 
 def masked_mean(x, m):
@@ -465,14 +477,14 @@ class Trainer:
         dead_work: also run what the reference computes although nothing consumes it (SURVEY.md 3.1 liveness table):
         the dynamic-field forward of passes E / P3 / P4, and the appearance phase (colours) of both fields in passes B-D
         and P1-P4, whose rgb maps no loss term reads; off = skipped, losses and gradients identical.  Dead work is computed
-        but never saved for a backward that cannot read it (forward(rgb="value"), no_grad: see ray_pass).
+        but never saved for a backward that cannot read it (forward(rgb="value"), no_grad: see Pass).
         dp_exact_stats (data-parallel runs): the batch statistics of the losses -- the mask sums of the masked means
         (train.py:1391-1394, 1522-1524, 1828-1832, 1277-1291) and the per-frame medians / deviations / ray counts of
         the monocular depth losses (train.py:797-807) -- are those of the WHOLE batch (one all-reduce of ~30 pairs of
         floats per loss group, one all-gather of the per-ray depths), so that an N-rank run optimises exactly the
         single-process objective; off: per-shard statistics.
         batch_passes (default on; RDRF_BATCH_PASSES=0): passes A-D share one static forward and passes of equal gradient
-        liveness one dynamic forward / backward (ray_passes); off = one launch sequence per pass, same arithmetic.
+        liveness one dynamic forward / backward (run_passes); off = one launch sequence per pass, same arithmetic.
         graph (single-process runs): batch gather, every forward pass and both backward phases of an iteration are captured
         ONCE per shape / gate combination as a HIP graph (torch.cuda.CUDAGraph) and replayed -- the coarse stages of
         Nvidia_no_poses.txt / DAVIS.txt (S = 13) spend ~9.5 ms per iteration enqueueing ~300 launches of a few
@@ -618,96 +630,88 @@ class Trainer:
             return torch.mean(-(m2 * torch.log(m2) + (1 - m2) * torch.log(1 - m2)))
 
         def order_terms(outs):   # adaptive order loss, train.py:1277-1291 / 1666-1683
-            return to_depth(outs[9]), to_depth(outs[5].detach()), (1.0 - outs[12].detach())
+            return to_depth(outs.depth_d), to_depth(outs.depth_s.detach()), (1.0 - outs.dynamicness.detach())
 
-        # ---- pass A (and, batched with it where their inputs allow, passes B-D: see ray_passes)
-        if full and self.batch_passes:
-            rays_n_of = {sgn: self.rays_for(ids, poses_d, focal_d, uv=grid + b["flow_f" if sgn > 0 else "flow_b"], view_shift=sgn)
-                         for sgn in (1, -1)}
+        run = lambda plan, groups=None: run_passes(self.st, self.dy, plan, S, rt, rng, groups, batch=self.batch_passes)
+        # ---- passes A-D: their inputs do not depend on one another (run_passes)
+        plan, groups = [Pass(rays_d, ts)], [[0]]
+        if full:
+            # passes B-D read depths, weights and the dynamicness only (train.py:1248-1312, 1515-1524): their colours are
+            # dead work the reference computes (self.dead_work keeps it)
+            dead = dict(rgb_s=self._dead_rgb(), rgb_d=self._dead_rgb())
+            plan += [Pass(rays_d, b["ts_rand"], **dead)]
+            plan += [Pass(self.rays_for(ids, poses_d, focal_d, uv=grid + b[flow], view_shift=sgn), ts + sgn * dt, **dead)
+                     for sgn, flow in ((1, "flow_f"), (-1, "flow_b"))]
             # groups of equal gradient liveness: A (everything live) | B, C, D (no appearance gradient; before
             # upsamp_list[3] no blending gradient either -- later only B has the dynamicness terms)
             groups = [[0], [1, 2, 3]] if not late else [[0], [1], [2, 3]]
-            # passes B-D read depths, weights and the dynamicness only (train.py:1248-1312, 1515-1524): their colours are
-            # dead work the reference computes (self.dead_work keeps it)
-            pA, pB, pC, pD = ray_passes(self.st, self.dy, [rays_d, rays_d, rays_n_of[1], rays_n_of[-1]],
-                                        [ts, b["ts_rand"], ts + dt, ts - dt], S, rt, rng, groups,
-                                        rgb=[True] + [self._dead_rgb()] * 3)
-            osA, oA, outA, xyzA = pA
-            batched = {"B": pB, 1: pC, -1: pD}
-        else:
-            osA, oA, outA, xyzA = ray_pass(self.st, self.dy, rays_d, ts, S, rt, rng)
-            batched = None
+        A, *BCD = run(plan, groups)
+        oA, outA = A.o_d, A.maps
         if capture is not None:
-            capture["A"] = (osA, oA, outA, xyzA)
-        Ld.add(3.0, "square", outA[0], rgb_t).add(1.0, "square", outA[8], rgb_t)      # train.py:1323, 1331
+            capture["A"] = tuple(A[:4])
+        Ld.add(3.0, "square", outA.rgb, rgb_t).add(1.0, "square", outA.rgb_d, rgb_t)   # train.py:1323, 1331
+        # ---- pass E: static field with gradient, rays with gradient (pose / focal); its dynamic evaluation is dead work
+        pass_E = Pass(rays, ts, static_grad=True, dynamic="dead" if self.dead_work else None)
         if not full:
-            oE, oEd, outE, xyzE = ray_pass(self.st, self.dy, rays, ts, S, rt, rng, static_grad=True, dynamic=self.dead_work)
+            E, = run([pass_E])
             if capture is not None:
-                capture["E"] = (oE, oEd, outE, xyzE)
-            Ls = self._loss_terms().add(1.0 / 3.0, "square", outE[4], rgb_t, w=(1.0 - fg)[:, None], norm="weight")
+                capture["E"] = tuple(E[:4])
+            Ls = self._loss_terms().add(1.0 / 3.0, "square", E.maps.rgb_s, rgb_t, w=(1.0 - fg)[:, None], norm="weight")
             self.terms = (Ld, Ls)
             return Ld.total(), Ls.total()
         if early:
-            Ld.add(0.1 * temp_disp_tv, "abs", outA[12], fg)                             # mask loss, :1338-1346
+            Ld.add(0.1 * temp_disp_tv, "abs", outA.dynamicness, fg)                     # mask loss, :1338-1346
         if late:
-            Ld.add(0.01, "identity", skewed(outA[12]))                                  # :1349-1364
-            Ld.add(0.01, "abs", outA[12])                                               # mask_L1_reg_loss, :1366
+            Ld.add(0.01, "identity", skewed(outA.dynamicness))                          # :1349-1364
+            Ld.add(0.01, "abs", outA.dynamicness)                                       # mask_L1_reg_loss, :1366
         xo, yo, wo = order_terms(outA)
         Ld.add(10.0, "square", xo, yo, w=wo, norm="weight")                             # order_loss, :1666-1683
-        Ld.add(1.0, "identity", frame_depth_loss(to_depth(outA[9]), gt_depth, view, T, coef=c["monodepth_dynamic"] * temp,
+        Ld.add(1.0, "identity", frame_depth_loss(to_depth(outA.depth_d), gt_depth, view, T, coef=c["monodepth_dynamic"] * temp,
                                                  dp=self._dp()))
         # distortion loss of the dynamic weights (train.py:1299-1312, 1685-1716), ramped by iteration / n_iters
         w_dist = c["dist_dynamic"] * (it / c["n_iters"])
         k_dist = self._coef(c["dist_dynamic"], "ramp", it / c["n_iters"])   # == w_dist (a device scalar in graph mode)
         if w_dist > 0:   # mean over the rays of the per-ray loss (eff_distloss), weighted
-            Ld.add(k_dist, "identity", distloss_rays(outA[11], oA[8].detach(), 1.0 / S))
+            Ld.add(k_dist, "identity", distloss_rays(outA.weights_d, oA.z_vals.detach(), 1.0 / S))
         # ---- pass B (second random time)
-        _, oB, outB, _ = batched["B"] if batched else ray_pass(self.st, self.dy, rays_d, b["ts_rand"], S, rt, rng,
-                                                               rgb_s=self._dead_rgb(), rgb_d=self._dead_rgb())
+        B, outB = BCD[0], BCD[0].maps
         if late:
-            Ld.add(0.01, "identity", skewed(outB[12]))                                  # :1248-1266
-            Ld.add(0.01, "abs", outB[12])                                               # novel_view_time_mask_loss, :1267
+            Ld.add(0.01, "identity", skewed(outB.dynamicness))                          # :1248-1266
+            Ld.add(0.01, "abs", outB.dynamicness)                                       # novel_view_time_mask_loss, :1267
         xo, yo, wo = order_terms(outB)
         Ld.add(10.0, "square", xo, yo, w=wo, norm="weight")                             # novel_order_loss, :1277-1291
         if w_dist > 0:
-            Ld.add(k_dist, "identity", distloss_rays(outB[11], oB[8].detach(), 1.0 / S))
+            Ld.add(k_dist, "identity", distloss_rays(outB.weights_d, B.o_d.z_vals.detach(), 1.0 / S))
         # ---- scene flow on pass A's sample points
-        sf_f, sf_b = self.dy.get_forward_backward_scene_flow(oA[3], ts)
+        sf_f, sf_b = self.dy.get_forward_backward_scene_flow(oA.xyz_sampled, ts)
         Ld.add(c["small_scene_flow_weight"], "abs", sf_f).add(c["small_scene_flow_weight"], "abs", sf_b)   # :1421-1424
         Ld.add(c["smooth_scene_flow_weight"], "abs", sf_f, sf_b, ysign=1.0)             # :1627-1628
         # ---- induced flow of the dynamic field into the neighbour frames (train.py:1373-1413)
-        weights_d, pts_ref = outA[11], oA[3]
+        weights_d, pts_ref = outA.weights_d, oA.xyz_sampled
         disp_A = {}
         for sgn, sf, flow_t, mask_t in ((1, sf_f, b["flow_f"], b["mask_f"]), (-1, sf_b, b["flow_b"], b["mask_b"])):
             pose_n = c2w_all[(view + sgn).clamp(0, T - 1)].detach()
             pts_n = pts_ref + sf if rt == "ndc" else torch.clamp(pts_ref + sf, min=-2.0 + 1e-6, max=2.0 - 1e-6)
             ind_flow, ind_disp = induce_flow(H, W, focal_d, pose_n, weights_d, pts_n, px, rays_d, ray_type=rt)
             Ld.add(0.01 * temp, "abs", ind_flow, flow_t, w=mask_t, norm="weight")       # :1392-1410 (x 0.02 / 2)
-            disp_A[sgn] = (ind_disp, mask_t, pose_n, flow_t)
+            disp_A[sgn] = (ind_disp, mask_t, pose_n)
         # ---- pass C / D: the flow-displaced rays of the neighbour frames (train.py:1433-1528, 1530-1625)
-        for sgn in (1, -1):
-            ind_disp, mask_t, pose_n, flow_t = disp_A[sgn]
-            if batched:
-                rays_n = rays_n_of[sgn]
-                _, oN, outN, _ = batched[sgn]
-            else:
-                rays_n = self.rays_for(ids, poses_d, focal_d, uv=grid + flow_t, view_shift=sgn)
-                _, oN, outN, _ = ray_pass(self.st, self.dy, rays_n, ts + sgn * dt, S, rt, rng, rgb_s=self._dead_rgb(),
-                                          rgb_d=self._dead_rgb())
-            _, ind_disp_n = induce_flow(H, W, focal_d, pose_n, outN[11], oN[3], px, rays_n, ray_type=rt)
+        for sgn, N_ in ((1, BCD[1]), (-1, BCD[2])):
+            ind_disp, mask_t, pose_n = disp_A[sgn]
+            _, ind_disp_n = induce_flow(H, W, focal_d, pose_n, N_.maps.weights_d, N_.o_d.xyz_sampled, px, N_.rays, ray_type=rt)
             Ld.add(0.04 * temp, "abs", ind_disp, ind_disp_n, w=mask_t, norm="weight")   # :1522-1524, 1619-1621
             if w_dist > 0:
-                Ld.add(k_dist, "identity", distloss_rays(outN[11], oN[8].detach(), 1.0 / S))
-        # ---- pass E: static field with gradient, rays with gradient (pose / focal)
-        oE, _, outE, _ = ray_pass(self.st, self.dy, rays, ts, S, rt, rng, static_grad=True, dynamic=self.dead_work)
+                Ld.add(k_dist, "identity", distloss_rays(N_.maps.weights_d, N_.o_d.z_vals.detach(), 1.0 / S))
+        # ---- pass E
+        E, = run([pass_E])
         m = (1.0 - fg)[:, None]
         Ls = self._loss_terms()
-        Ls.add(1.0 / 3.0, "square", outE[4], rgb_t, w=m, norm="weight")                  # :1828-1832
+        Ls.add(1.0 / 3.0, "square", E.maps.rgb_s, rgb_t, w=m, norm="weight")            # :1828-1832
         if c["dist_static"] > 0 and it > 0:       # train.py:1841-1861
             Ls.add(self._coef(c["dist_static"], "ramp", it / c["n_iters"]), "identity",
-                   distloss_rays(outE[7], oE[8].detach(), 1.0 / S))
+                   distloss_rays(E.maps.weights_s, E.o_s.z_vals.detach(), 1.0 / S))
         if self.optimize_poses:
-            self._pose_block(b, rays, oE, outE, poses, focal, c2w_all, grid, px, view, m, temp_disp_tv, temp_static, gt_depth,
+            self._pose_block(b, rays, E, poses, focal, c2w_all, grid, px, view, m, temp_disp_tv, temp_static, gt_depth,
                              to_depth, Ls)
         # ---- factor-space regularisers (train.py:1718-1754, 1863-1885)
         if c["l1_weight"] > 0:
@@ -719,60 +723,32 @@ class Trainer:
         # while the gradients are finite; only the gradient is taken (step(): TVLoss.accumulate_grad_)
         return loss_d, loss_s
 
-    def _pose_block(self, b, rays, oE, outE, poses, focal, c2w_all, grid, px, view, m, temp_disp_tv, temp_static, gt_depth,
+    def _pose_block(self, b, rays, E, poses, focal, c2w_all, grid, px, view, m, temp_disp_tv, temp_static, gt_depth,
                     to_depth, Ls):
         """train.py:1895-2311 (optimize_poses): every term reaches the static field, the poses and the focal."""
         c = self.cfg
         S, rt, T, H, W = c["n_samples"], c["ray_type"], c["T"], c["H"], c["W"]
         ids, ts, fg = b["ids"], b["ts"], b["fg"]
-        rng = self.rng
-        weights_s, pts_ref_s, depth_s = outE[7], oE[3], outE[5]
+        weights_s, pts_ref_s, depth_s = E.maps.weights_s, E.o_s.xyz_sampled, E.maps.depth_s
         col, row = grid[:, 0], grid[:, 1]
         uv_P34 = (torch.stack([torch.clamp(col + 1.0, max=W - 0.5), row], -1),
                   torch.stack([col, torch.clamp(row + 1.0, max=H - 0.5)], -1))
-        batched = None
-        if self.batch_passes:
-            # P1-P4 are independent of each other and have the same gradient liveness (density branch of the static field
-            # only): one static forward / backward over their 4 N rays, the draws in pass order (ray_passes)
-            rays_P = [self.rays_for(ids, poses, focal, uv=grid + b["flow_f"], view_shift=1),
-                      self.rays_for(ids, poses, focal, uv=grid + b["flow_b"], view_shift=-1),
-                      self.rays_for(ids, poses, focal, uv=uv_P34[0]), self.rays_for(ids, poses, focal, uv=uv_P34[1])]
-            smp, coins = [], []
-            for k, r in enumerate(rays_P):
-                jit, jit_o = rng.jitter(S, rt, rays.device)
-                smp.append(sampleXYZ(self.st if k < 2 else self.dy, r, S, ray_type=rt, is_train=True, jitter=jit,
-                                     jitter_outer=jit_o))
-                coins.append(rng.coin() if k >= 2 else None)
-            PASSES.update(static=4, static_grad=4)
-            ts_P = [ts] * 4
-            ns = rays.shape[0] * smp[0][1].shape[1]
-            o_P = [None] * 4
-            for g in batch_groups(range(4), ns):
-                for k, o in zip(g, batched_field(self.st, rays_P, ts_P, smp, g, rt, rgb=self._dead_rgb())):
-                    o_P[k] = o   # (P1-P4 read weights / depths only: train.py:1951-2311)
-            d_P = [None, None]
-            if self.dead_work:   # the dynamic forwards of P3 / P4: dead work the reference performs
-                PASSES.update(dynamic=2, dynamic_dead=2)
-                for g in batch_groups((2, 3), ns):
-                    live = any(rays_P[k].requires_grad or smp[k][1].requires_grad for k in g)   # `dists` -> rays / z_vals
-                    for k, o in zip(g, batched_field(self.dy, rays_P, ts_P, smp, g, rt, grad=live, rgb="value")):
-                        d_P[k - 2] = o
-            batched = (rays_P, smp, coins, o_P, d_P)
-        for k, (sgn, flow_t, mask_t) in enumerate(((1, b["flow_f"], b["mask_f"]), (-1, b["flow_b"], b["mask_b"]))):
+        # P1-P4 are independent of each other and have the same gradient liveness (density branch of the static field only:
+        # they read weights / depths, train.py:1951-2311): one static forward / backward over their 4 N rays (run_passes).
+        # P1 / P2: the static field alone along the flow-displaced rays of the neighbour frames; P3 / P4: the x+1 / y+1
+        # pixel rays, composited, their dynamic forwards dead work the reference performs
+        static = dict(static_grad=True, rgb_s=self._dead_rgb())
+        plan = [Pass(self.rays_for(ids, poses, focal, uv=grid + b[flow], view_shift=sgn), ts, dynamic=None, static_box=True,
+                     composite=False, **static) for sgn, flow in ((1, "flow_f"), (-1, "flow_b"))]
+        plan += [Pass(self.rays_for(ids, poses, focal, uv=uv), ts, dynamic="dead" if self.dead_work else None, **static)
+                 for uv in uv_P34]
+        P = run_passes(self.st, self.dy, plan, S, rt, self.rng, [[2, 3]] if self.dead_work else [], batch=self.batch_passes)
+        for N_, (sgn, flow_t, mask_t) in zip(P, ((1, b["flow_f"], b["mask_f"]), (-1, b["flow_b"], b["mask_b"]))):
             pose_n = gather_rows(c2w_all, (view + sgn).clamp(0, T - 1))         # live: allposes_refine_f / _b
             mm = mask_t * m
             ind_flow, ind_disp = induce_flow(H, W, focal, pose_n, weights_s, pts_ref_s, px, rays, ray_type=rt)
             Ls.add(self._coef(0.01, "temp_static", temp_static), "abs", ind_flow, flow_t, w=mm, norm="weight")    # :1909-1941 (x 0.02 / 2)
-            # P1 / P2: the static field along the flow-displaced ray of the neighbour frame
-            if batched:
-                rays_n, o, xyz = batched[0][k], batched[3][k], batched[1][k][0]
-            else:
-                rays_n = self.rays_for(ids, poses, focal, uv=grid + flow_t, view_shift=sgn)
-                jit, jit_o = rng.jitter(S, rt, rays.device)
-                xyz, z, valid = sampleXYZ(self.st, rays_n, S, ray_type=rt, is_train=True, jitter=jit, jitter_outer=jit_o)
-                PASSES.update(static=1, static_grad=1)
-                o = self.st(rays_n, ts, None, xyz, z, valid, is_train=True, ray_type=rt, rgb=self._dead_rgb())
-            _, ind_disp_n = induce_flow(H, W, focal, pose_n, o[4], xyz, px, rays_n, ray_type=rt)
+            _, ind_disp_n = induce_flow(H, W, focal, pose_n, N_.o_s.weight, N_.xyz, px, N_.rays, ray_type=rt)   # P1 / P2
             Ls.add(self._coef(0.04, "temp_static", temp_static), "abs", ind_disp, ind_disp_n, w=mm, norm="weight")  # :2012-2017, 2079-2084
         # per-frame median-normalised monocular depth of the static field on the background rays
         if self._dyn is None:
@@ -783,21 +759,8 @@ class Trainer:
                    frame_depth_loss(to_depth(depth_s), gt_depth, view, T, mask=fg < 0.5, coef=c["monodepth_static"], dp=self._dp()))
         # P3 / P4: disparity smoothness against the x+1 / y+1 pixel neighbours (train.py:2123-2311)
         inv_d = 1.0 / torch.clamp(depth_s, min=1e-6)
-        for k, uv_n in enumerate(uv_P34):
-            if batched:
-                rays_n, o_s, o_d, z = batched[0][2 + k], batched[3][2 + k], batched[4][k], batched[1][2 + k][1]
-                if o_d is None:
-                    zero = torch.zeros_like(o_s[7])
-                    dyn = (_rgb_or_zeros(None, zero), zero, o_s[9], zero, z)
-                else:
-                    dyn = (_rgb_or_zeros(o_d[6], o_d[7]), o_d[7], o_d[9], o_d[2], o_d[8])
-                outN = raw2outputs(_rgb_or_zeros(o_s[6], o_s[7]), o_s[7], *dyn, rays_n, is_train=True, ray_type=rt,
-                                   add_white_bg=batched[2][2 + k])
-            else:
-                rays_n = self.rays_for(ids, poses, focal, uv=uv_n)
-                _, _, outN, _ = ray_pass(self.st, self.dy, rays_n, ts, S, rt, rng, static_grad=True, dynamic=self.dead_work,
-                                         rgb_s=self._dead_rgb())
-            Ls.add(50.0 * temp_disp_tv, "square", inv_d, 1.0 / torch.clamp(outN[5], min=1e-6))  # :2293-2305
+        for N_ in P[2:]:
+            Ls.add(50.0 * temp_disp_tv, "square", inv_d, 1.0 / torch.clamp(N_.maps.depth_s, min=1e-6))  # :2293-2305
 
     def step(self, shard=None):
         """One iteration on this rank's shard of the batch: forward of every pass, two-phase backward (static
@@ -1062,4 +1025,4 @@ class Trainer:
 def render_chunk(st, dy, rays, ts, n_samples, ray_type="ndc"):
     """renderer.py:740-812 loop body (no-grad eval pass): returns rgb_map_full, depth_map_full."""
     _, _, outs, _ = ray_pass(st, dy, rays, ts, n_samples, ray_type, StepRng(), is_train=False)
-    return outs[0], outs[1]
+    return outs.rgb, outs.depth

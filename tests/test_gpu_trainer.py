@@ -1,6 +1,7 @@
 """End-to-end trainer harness (robust-dynrf_amd/step.py): a short run of the Nvidia.txt-shaped step on
 a small synthetic scene stays finite and reduces the loss -- catches sign / accumulation mistakes in
 the fused-gradient, pruning and optimiser wiring that per-kernel parity tests cannot see."""
+import functools
 import importlib
 
 import numpy as np
@@ -444,7 +445,7 @@ def test_upsample_restarts_learning_rates_like_the_reference():
 @pytest.mark.parametrize("name,stage,it", [("nvidia", "stage0", 5000), ("nvidia", "final", 30000),
                                            ("nvidia_no_poses", "final", 30000), ("davis", "stage0", 5000)])
 def test_batched_passes_match_one_pass_per_launch(name, stage, it, monkeypatch):
-    """step.ray_passes (passes A-D through one static forward, passes of equal gradient liveness through one dynamic
+    """step.run_passes batched (passes A-D through one static forward, passes of equal gradient liveness through one dynamic
     forward / backward) against one launch sequence per pass: the same draws, the same loss values, gradients equal up to the order of the atomic accumulation -- at the benchmark shape, at the
     late stage (B alone, C + D batched), at [706,786,471] / S = 578 with 3 x 4096 rays in one dynamic call (7.1 M
     samples: the batched buffers pass 2^32 floats, the per-pass ones do not) and 4 x 4096 in the static call of the pose
@@ -488,11 +489,32 @@ def test_batched_passes_match_one_pass_per_launch(name, stage, it, monkeypatch):
         assert_close(a, b_, "batched vs per-pass gradient", rtol=1e-4)
 
 
-@pytest.mark.parametrize("name", ["nvidia", "nvidia_late", "nvidia_no_poses", "davis"])
-def test_trainer_step_matches_reference_trainer_iteration(name):
-    """SURVEY 8a row 13, the whole iteration pinned to the REFERENCE: Trainer.step (batched passes, fused loss terms,
-    two-phase backward, TV gradient) against the gradients the reference's own train.reconstruction() produced at
-    iteration 0 (tests/golden/trainer_iter_*.npz, make_golden_trainer.py) -- passes A-E, the pose block P1-P4, every loss
+@functools.lru_cache(maxsize=None)
+def _oracle_step_gradients(name):
+    """the oracle's fp32 and fp64 gradients of the trainer_iter fixture `name` (shared by the cases on one fixture)"""
+    from _util import load_trainer_iter
+    from oracle import rodynrf_oracle_step as OS
+    _, cfg, batch, sd_s, sd_d, poses, focal, draws = load_trainer_iter(name)
+    _, g32 = OS.step_gradients(cfg, sd_s, sd_d, batch, poses, focal, 0, OS.ReplayRng(*draws), dead_work=True)
+    torch.set_default_dtype(torch.float64)
+    try:
+        cv = lambda v: v.double() if torch.is_tensor(v) and v.is_floating_point() else v
+        _, g64 = OS.step_gradients(cfg, {k: cv(v.detach()) for k, v in sd_s.items()}, {k: cv(v.detach()) for k, v in sd_d.items()},
+                                   {k: cv(v) for k, v in batch.items()}, cv(poses), cv(focal), 0, OS.ReplayRng(*draws),
+                                   dead_work=True)
+    finally:
+        torch.set_default_dtype(torch.float32)
+    return g32, g64
+
+
+@pytest.mark.parametrize("name,batched", [pytest.param("nvidia", True, id="nvidia"), pytest.param("nvidia_late", True, id="nvidia_late"),
+                                          pytest.param("nvidia_no_poses", True, id="nvidia_no_poses"),
+                                          pytest.param("davis", True, id="davis"),
+                                          pytest.param("nvidia_no_poses", False, id="nvidia_no_poses-per_pass")])
+def test_trainer_step_matches_reference_trainer_iteration(name, batched):
+    """SURVEY 8a row 13, the whole iteration pinned to the REFERENCE: Trainer.step (batched passes -- and, on the fixture
+    with the pose block, one call per pass -- fused loss terms, two-phase backward, TV gradient) against the gradients
+    the reference's own train.reconstruction() produced at iteration 0 (tests/golden/trainer_iter_*.npz, make_golden_trainer.py) -- passes A-E, the pose block P1-P4, every loss
     term with its gate and weight -- on the same weights, batch, jitter vectors and coins: every parameter of both
     fields, the pose table and the field of view at 1e-4 of each tensor's max, element by element.  Where two fp32
     evaluation orders of the same iteration legitimately differ (a relu unit on its kink: see
@@ -503,7 +525,7 @@ def test_trainer_step_matches_reference_trainer_iteration(name):
     S_ = importlib.import_module("robust-dynrf_amd.step")
     p, cfg, batch, sd_s, sd_d, poses, focal, draws = load_trainer_iter(name)
     dev = torch.device("cuda", 0)
-    tr = S_.Trainer(dict(cfg), dev, dead_work=True)
+    tr = S_.Trainer(dict(cfg), dev, dead_work=True, batch_passes=batched)
     tr.st.load_state_dict(sd_s)
     tr.dy.load_state_dict(sd_d)
     for f in (tr.st, tr.dy):
@@ -525,15 +547,7 @@ def test_trainer_step_matches_reference_trainer_iteration(name):
     tr.step()
     assert not tr.rng.jitters and not tr.rng.coins, "the trainer consumed a different number of draws than the reference"
     # the oracle's fp32 / fp64 evaluations of the same iteration: their distance is the kink / conditioning allowance
-    _, g32 = OS.step_gradients(cfg, sd_s, sd_d, batch, poses, focal, 0, OS.ReplayRng(*draws), dead_work=True)
-    torch.set_default_dtype(torch.float64)
-    try:
-        cv = lambda v: v.double() if torch.is_tensor(v) and v.is_floating_point() else v
-        _, g64 = OS.step_gradients(cfg, {k: cv(v.detach()) for k, v in sd_s.items()}, {k: cv(v.detach()) for k, v in sd_d.items()},
-                                   {k: cv(v) for k, v in batch.items()}, cv(poses), cv(focal), 0, OS.ReplayRng(*draws),
-                                   dead_work=True)
-    finally:
-        torch.set_default_dtype(torch.float32)
+    g32, g64 = _oracle_step_gradients(name)
     bad, n = [], 0
 
     def check(label, got, ref, o32, o64, scale, rtol):
@@ -563,7 +577,8 @@ def test_trainer_step_matches_reference_trainer_iteration(name):
     assert n > 60 and not bad, "\n".join(bad)
 
 
-@pytest.mark.parametrize("name,batched", [("nvidia", True), ("nvidia", False), ("nvidia_no_poses", True), ("davis", True)])
+@pytest.mark.parametrize("name,batched", [("nvidia", True), ("nvidia", False), ("nvidia_no_poses", True), ("nvidia_no_poses", False),
+                                          ("davis", True)])
 def test_dead_work_pruning_changes_nothing(name, batched):
     """Trainer(dead_work=False) (the default) skips what the reference computes and nothing consumes -- the dynamic forward
     of passes E / P3 / P4 and the appearance phase (colours) of both fields in passes B-D and P1-P4 (forward(rgb=False)) --

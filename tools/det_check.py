@@ -1,4 +1,5 @@
-"""One training step of a small (or the benchmark) scene; saves the two flat gradient buffers.  Run with
+"""One training step of a small (or the benchmark) scene; saves the loss, the two flat gradient buffers and, where the
+trainer optimises them, the gradients of the pose table and the field of view.  Run with
 RDRF_DETERMINISTIC=1 for the fixed-point build:   python tools/det_check.py out.pt [small|bench] [config]"""
 import importlib
 import os
@@ -20,4 +21,7 @@ tr = S_.Trainer(cfg, torch.device("cuda", 0))
 tr.it = 9000
 loss = tr.step()
 torch.cuda.synchronize()
-torch.save({"loss": loss.cpu(), "flats": [f.detach().cpu() for f in tr.grad_flats]}, out)
+got = {"loss": loss.cpu(), "flats": [f.detach().cpu() for f in tr.grad_flats]}
+if tr.optimize_poses:
+    got.update(poses_grad=tr.poses.grad.cpu(), fov_grad=tr.fov.grad.cpu())
+torch.save(got, out)
