@@ -839,6 +839,25 @@ int rdrf_alpha_mask_sample(const RdrfAlphaMask* mask, const float* xyz, const fl
 int rdrf_alpha_mask_valid(const RdrfAlphaMask* mask0, const RdrfAlphaMask* mask1, const float* xyz, const float* ts, int N,
                           int S, uint8_t* valid, rdrf_stream_t stream);
 
+/* ---- isosurface meshes: marching tetrahedra over one time slice of a dense volume ------------------------------------------
+ * vol is [G0][G1][G2][T] (the alpha volume of getDenseAlpha, used in place; T = 1: a plain 3-D volume) and slice t_index is
+ * meshed at `level`: a sample is inside iff v >= level.  Every lattice cube is cut into the six Kuhn tetrahedra
+ * v0, v0 + e_a, v0 + e_a + e_b, v0 + (1,1,1); a lattice edge (3 axis edges, 3 face diagonals, the body diagonal; owned by its
+ * lower end) with exactly one end inside carries one vertex at p_lo + t (p_hi - p_lo), t = (level - v_lo) / (v_hi - v_lo), lo
+ * the outside end, lattice positions aabb_min + idx / (G - 1) (aabb_max - aabb_min).  Vertices come in ascending (point, edge
+ * kind) order, faces in ascending (cube, tetrahedron, triangle) order, counter-clockwise seen from the outside (flip: the
+ * reverse); no atomics, the same bits from every build.  normals (nullable): -grad v by central differences (one-sided at the
+ * boundary) at the two ends, interpolated with t and normalised.  Shapes with a side below 2, with 7 G0 G1 G2 >= 2^31 or with
+ * 12 (G0-1)(G1-1)(G2-1) >= 2^31 are refused before any launch (rdrf_iso_ws_bytes returns 0 for them).
+ * rdrf_iso_count writes the per-point edge flags and the vertex / triangle prefixes into ws and counts = {vertices, faces}
+ * (device); the caller reads the two counts, allocates, and hands the same ws to rdrf_iso_emit.  aabb6: host, min xyz then
+ * max xyz.  rdrf_iso_ws_bytes does not carry the *_workspace_bytes suffix for the reason given at rdrf_render_masked_ws_bytes. */
+size_t rdrf_iso_ws_bytes(int G0, int G1, int G2);
+int rdrf_iso_count(const float* vol, int G0, int G1, int G2, int T, int t_index, float level, void* ws, size_t ws_bytes,
+                   int64_t* counts, rdrf_stream_t stream);
+int rdrf_iso_emit(const float* vol, int G0, int G1, int G2, int T, int t_index, float level, const float* aabb6, int flip,
+                  const void* ws, float* verts, float* normals, int* faces, int64_t nv, int64_t nf, rdrf_stream_t stream);
+
 /* ---- masked render: the no-grad render of a ray chunk that skips what the alpha-grid masks leave empty ------------------
  * The maps are those of: sample -> valid_s = valid & (mask_s > 0), valid_d = valid & (mask_d > 0) (rdrf_alpha_mask_valid with
  * one mask) -> rdrf_static_fwd with valid_s, rdrf_dynamic_fwd with valid_d -> rdrf_composite_fwd, bit for bit in every map;

@@ -232,6 +232,9 @@ SIGNATURES = {
     "rdrf_alpha_mask_build": (i32, [vp, i32, i32, i32, i32, f32, vp, vp, vp]),
     "rdrf_alpha_mask_sample": (i32, [C.POINTER(RdrfAlphaMask), vp, vp, i32, i64, vp, vp]),
     "rdrf_alpha_mask_valid": (i32, [C.POINTER(RdrfAlphaMask), C.POINTER(RdrfAlphaMask), vp, vp, i32, i32, vp, vp]),
+    "rdrf_iso_ws_bytes": (usz, [i32, i32, i32]),
+    "rdrf_iso_count": (i32, [vp, i32, i32, i32, i32, i32, f32, vp, usz, vp, vp]),
+    "rdrf_iso_emit": (i32, [vp, i32, i32, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, i64, i64, vp]),
     "rdrf_render_masked_ws_bytes": (usz, [i32, i32]),
     "rdrf_render_masked_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, C.POINTER(RdrfAlphaMask),
                                     C.POINTER(RdrfAlphaMask), C.POINTER(RenderMapsC), vp, vp, usz, vp]),

@@ -498,6 +498,11 @@ class TensorBase(nn.Module):
         from .alpha import filtering_rays
         return filtering_rays(self, all_rays, all_rgbs, all_ts, N_samples, chunk, bbox_only)
 
+    def export_mesh(self, ply_path, t=None, level=0.005, **kw):
+        """train.py:107-118 on the kernels of csrc/rdrf_iso.hip (mesh.py)"""
+        from .mesh import export_mesh
+        return export_mesh(self, ply_path, t, level, **kw)
+
     def shrink(self, new_aabb, voxel_size=None):
         raise NotImplementedError("shrink reallocates the VM factors under the flat optimiser buffers and is not built: "
                                   "the new_aabb of updateAlphaMask is informational")

@@ -1,0 +1,251 @@
+"""Isosurface meshes of dense alpha volumes (the reference's --export_mesh, train.py:107-118 -> utils.py:188-247
+convert_sdf_samples_to_ply) on the kernels of csrc/rdrf_iso.hip: marching tetrahedra on the device, an indexed mesh in a
+fixed order, PLY through numpy.
+
+Where this departs from the reference on purpose: the lattice positions are the dense_xyz points getDenseAlpha sampled
+(spacing extent / (G - 1); the reference's voxel_size = extent / G is off by G / (G - 1)), and triangles are
+counter-clockwise seen from the low-value side (the reference reverses skimage's faces; pass flip=True for the other
+winding).  DESIGN.md, "Isosurface meshes", has the algorithm and the ordering rules.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+CAP_VALUE = -1.0e30   # "minus infinity" of cap=True: finite, so t = (level - v_lo) / (v_hi - v_lo) rounds to exactly 1
+
+
+def _aabb6(aabb):
+    a = torch.as_tensor(aabb, dtype=torch.float32).detach().cpu().reshape(-1)
+    if a.numel() != 6:
+        raise L.RdrfError(f"aabb must hold min xyz and max xyz, not {a.numel()} values")
+    return a
+
+
+def _cap(volume, aabb):
+    """a [G0,G1,G2] volume with one sample of CAP_VALUE around it, the aabb grown by one cell per side"""
+    G = volume.shape
+    padded = volume.new_full((G[0] + 2, G[1] + 2, G[2] + 2), CAP_VALUE)
+    padded[1:-1, 1:-1, 1:-1] = volume
+    a = aabb.double().view(2, 3)
+    cell = (a[1] - a[0]) / torch.tensor([g - 1 for g in G], dtype=torch.float64)
+    return padded, torch.stack((a[0] - cell, a[1] + cell)).float().reshape(-1)
+
+
+@torch.no_grad()
+def extract_isosurface(volume, level, aabb, t_index=0, normals=False, flip=False, cap=False):
+    """volume: device tensor [G0,G1,G2] or [G0,G1,G2,T] (slice t_index is meshed, in place) -> (verts [nv,3] float32,
+    faces [nf,3] int32[, normals [nv,3]]).  A sample is inside iff v >= level; verts ascend in (lattice point, edge kind),
+    faces in (cube, tetrahedron, triangle).  cap=True closes the surface where it reaches the volume boundary.
+    One host read (the two counts) between the counting and the emitting launches; an empty mesh skips the second."""
+    L.require_device(volume)
+    if volume.dim() not in (3, 4):
+        raise L.RdrfError(f"extract_isosurface: the volume must be [G0,G1,G2] or [G0,G1,G2,T], not {tuple(volume.shape)}")
+    vol = L.f32c(volume)
+    T = 1 if vol.dim() == 3 else int(vol.shape[3])
+    t_index = int(t_index)
+    if not 0 <= t_index < T:
+        raise L.RdrfError(f"extract_isosurface: t_index {t_index} of {T} slices")
+    box = _aabb6(aabb)
+    if cap:   # only the slice that is meshed is copied
+        vol, box = _cap(vol if vol.dim() == 3 else vol[..., t_index], box)
+        T, t_index = 1, 0
+    G0, G1, G2 = (int(v) for v in vol.shape[:3])
+    dev, stream = vol.device, L.stream_of(vol)
+    nbytes = L.lib.rdrf_iso_ws_bytes(G0, G1, G2)
+    ws = L.workspace(dev, nbytes) if nbytes else None   # 0: a refused shape, which rdrf_iso_count reports by name
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    L.check(L.lib.rdrf_iso_count(L.ptr(vol), G0, G1, G2, T, t_index, float(level), L.ptr(ws), 0 if ws is None else ws.numel(),
+                                 L.ptr(counts), stream), "rdrf_iso_count")
+    nv, nf = (int(v) for v in counts.cpu().tolist())   # the one sync
+    verts = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    nrm = torch.empty(nv, 3, dtype=torch.float32, device=dev) if normals else None
+    if nv > 0:
+        box_c = (C.c_float * 6)(*[float(v) for v in box])
+        L.check(L.lib.rdrf_iso_emit(L.ptr(vol), G0, G1, G2, T, t_index, float(level), box_c, int(bool(flip)), L.ptr(ws),
+                                    L.ptr(verts), L.ptr(nrm), L.ptr(faces), nv, nf, stream), "rdrf_iso_emit")
+    return (verts, faces, nrm) if normals else (verts, faces)
+
+
+def ndc_to_world(pts, H, W, focal):
+    """the reference's NDC2world (renderer.py:1266-1274)"""
+    pts_z = 2 / (torch.clamp(pts[..., 2:], min=-1.0, max=1 - 1e-6) - 1)
+    pts_x = -pts[..., 0:1] * pts_z * W / 2 / focal
+    pts_y = -pts[..., 1:2] * pts_z * H / 2 / focal
+    return torch.cat([pts_x, pts_y, pts_z], -1)
+
+
+def face_vertex_normals(verts, faces):
+    """area-weighted vertex normals from the faces (a vertex without a non-degenerate face keeps a zero normal)"""
+    f = faces.long()
+    a, b, c = verts[f[:, 0]], verts[f[:, 1]], verts[f[:, 2]]
+    fn = torch.cross(b - a, c - a, dim=-1)
+    n = torch.zeros_like(verts)
+    for col in range(3):
+        n.index_add_(0, f[:, col], fn)
+    length = n.norm(dim=-1, keepdim=True)
+    return torch.where(length > 0, n / length.clamp_min(1e-30), n)
+
+
+def _to_world(field, verts, faces, space, H, W, focal):
+    if space == "field":
+        return verts, None
+    if space != "world":
+        raise L.RdrfError(f"space must be \"field\" or \"world\", not {space!r}")
+    if H is None or W is None or focal is None:
+        raise L.RdrfError("space=\"world\" maps NDC vertices through NDC2world and needs H, W and focal")
+    world = ndc_to_world(verts, H, W, focal)
+    return world, face_vertex_normals(world, faces)
+
+
+def _mesh_of_slice(field, alpha, k, level, space, H, W, focal, kw):
+    want_normals = bool(kw.get("normals", False))
+    out = extract_isosurface(alpha, level, field.aabb, t_index=k, **kw)
+    verts, faces = out[0], out[1]
+    world, wn = _to_world(field, verts, faces, space, H, W, focal)
+    if not want_normals:
+        return world, faces
+    return world, faces, (out[2] if wn is None else wn)
+
+
+def _check_kw(kw):
+    if "colors" in kw:
+        raise L.RdrfError("vertex colours are not built: the appearance head has no per-point entry on the call surface "
+                          "(write_ply takes colours a caller computed)")
+    bad = set(kw) - {"normals", "flip", "cap"}
+    if bad:
+        raise TypeError(f"unexpected arguments {sorted(bad)}")
+
+
+@torch.no_grad()
+def field_mesh(field, t=None, level=0.005, gridSize=None, space="field", H=None, W=None, focal=None, **kw):
+    """getDenseAlpha(gridSize, times=[t]) -> extract_isosurface.  t=None only for the static field (its alpha does not
+    depend on the time).  space="world": the vertices of an ndc field through NDC2world (needs H, W, focal); normals are then
+    recomputed from the transformed faces.  kw: normals, flip, cap."""
+    _check_kw(kw)
+    if t is None:
+        if field.DYNAMIC:
+            raise L.RdrfError("field_mesh: the dynamic field's alpha depends on the time: pass t")
+        t = 0.0
+    alpha, _ = field.getDenseAlpha(gridSize, times=[float(t)])
+    return _mesh_of_slice(field, alpha, 0, level, space, H, W, focal, kw)
+
+
+def mesh_sequence(field, times, level=0.005, gridSize=None, space="field", H=None, W=None, focal=None, **kw):
+    """an iterator of one mesh per time: a single getDenseAlpha over all times, then one extraction per slice of the
+    [G0,G1,G2,T] volume.  The arguments are checked here, at the call, not at the first next()."""
+    _check_kw(kw)
+    times = [float(v) for v in torch.as_tensor(times, dtype=torch.float32).reshape(-1).tolist()]
+    if space not in ("field", "world"):
+        raise L.RdrfError(f"space must be \"field\" or \"world\", not {space!r}")
+
+    @torch.no_grad()
+    def meshes():
+        if not times:
+            return
+        alpha, _ = field.getDenseAlpha(gridSize, times=times)
+        for k in range(len(times)):
+            yield _mesh_of_slice(field, alpha, k, level, space, H, W, focal, kw)
+
+    return meshes()
+
+
+# ---- PLY (binary little-endian), numpy only ----------------------------------------------------------------------------
+def _np(x, dtype):
+    if torch.is_tensor(x):
+        x = x.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(x), dtype=dtype)
+
+
+def _vertex_dtype(normals, colors):
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    if colors:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    return np.dtype(fields)
+
+
+def write_ply(path, verts, faces, normals=None, colors=None):
+    """vertex: x y z [nx ny nz] [red green blue]; face: vertex_indices as uchar count + int indices"""
+    v, f = _np(verts, "<f4").reshape(-1, 3), _np(faces, "<i4").reshape(-1, 3)
+    vd = _vertex_dtype(normals is not None, colors is not None)
+    rec = np.zeros(len(v), dtype=vd)
+    rec["x"], rec["y"], rec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        n = _np(normals, "<f4").reshape(-1, 3)
+        rec["nx"], rec["ny"], rec["nz"] = n[:, 0], n[:, 1], n[:, 2]
+    if colors is not None:
+        c = _np(colors, "u1").reshape(-1, 3)
+        rec["red"], rec["green"], rec["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    frec = np.zeros(len(f), dtype=np.dtype([("n", "u1"), ("idx", "<i4", (3,))]))
+    frec["n"], frec["idx"] = 3, f
+    kinds = {"<f4": "float", "|u1": "uchar"}
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
+    header += [f"property {kinds[vd[name].str]} {name}" for name in vd.names]
+    header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as out:
+        out.write(("\n".join(header) + "\n").encode("ascii"))
+        out.write(rec.tobytes())
+        out.write(frec.tobytes())
+
+
+def read_ply(path):
+    """what write_ply writes -> dict(verts [nv,3] f32, faces [nf,3] i32, normals / colors or None)"""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").split("\n")
+    if lines[:2] != ["ply", "format binary_little_endian 1.0"]:
+        raise ValueError(f"{path}: not a binary little-endian PLY")
+    nv = nf = None
+    props = []
+    for line in lines[2:]:
+        w = line.split()
+        if w[:2] == ["element", "vertex"]:
+            nv = int(w[2])
+        elif w[:2] == ["element", "face"]:
+            nf = int(w[2])
+        elif w[:1] == ["property"] and nf is None:
+            props.append(w[2])
+    names = tuple(props)
+    has_n, has_c = "nx" in names, "red" in names
+    vd = _vertex_dtype(has_n, has_c)
+    if names != vd.names:
+        raise ValueError(f"{path}: vertex properties {names} are not what write_ply writes")
+    rec = np.frombuffer(data, dtype=vd, count=nv, offset=end)
+    frec = np.frombuffer(data, dtype=np.dtype([("n", "u1"), ("idx", "<i4", (3,))]), count=nf, offset=end + nv * vd.itemsize)
+    if nf and not (frec["n"] == 3).all():
+        raise ValueError(f"{path}: only triangles are read")
+    stack = lambda keys, dt: np.stack([rec[k] for k in keys], -1).astype(dt) if nv else np.zeros((0, 3), dtype=dt)
+    return {"verts": stack(("x", "y", "z"), np.float32), "faces": np.array(frec["idx"], dtype=np.int32).reshape(-1, 3),
+            "normals": stack(("nx", "ny", "nz"), np.float32) if has_n else None,
+            "colors": stack(("red", "green", "blue"), np.uint8) if has_c else None}
+
+
+def load_field(path, device="cuda"):
+    """the reload recipe of train.py:433-447 on this package's classes; the class is told from the state dict"""
+    from .fields import TensorVMSplit, TensorVMSplit_TimeEmbedding
+    ckpt = torch.load(path, map_location="cpu", weights_only=False)
+    kwargs = dict(ckpt["kwargs"])
+    kwargs.pop("se3_poses", None)
+    kwargs.pop("focal_ratio_refine", None)
+    kwargs.update({"device": device})
+    cls = TensorVMSplit_TimeEmbedding if "density_layer1.weight" in ckpt["state_dict"] else TensorVMSplit
+    field = cls(**kwargs)
+    field.load(ckpt)
+    return field
+
+
+@torch.no_grad()
+def export_mesh(field_or_ckpt_path, ply_path, t=None, level=0.005, gridSize=None, space="field", H=None, W=None, focal=None,
+                device="cuda", **kw):
+    """train.py:107-118: the field (or the checkpoint at a path) -> dense alpha -> isosurface -> PLY.  Returns the mesh."""
+    field = load_field(field_or_ckpt_path, device) if isinstance(field_or_ckpt_path, (str, bytes)) or hasattr(
+        field_or_ckpt_path, "__fspath__") else field_or_ckpt_path
+    out = field_mesh(field, t, level, gridSize, space, H, W, focal, **kw)
+    write_ply(ply_path, out[0], out[1], normals=out[2] if len(out) > 2 else None)
+    return out

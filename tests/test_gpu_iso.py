@@ -1,0 +1,387 @@
+"""GPU tests of the isosurface layer (csrc/rdrf_iso.hip, robust-dynrf_amd/mesh.py) against the float64 restatement of
+tests/_iso_prim.py evaluated on the same float32 inputs.
+
+Topology is exact: vertex count, face count and the face array are equal, in order (vertex i of both meshes is the vertex
+of the same (lattice point, edge kind), so equal index triples are equal (point, kind) triples; the positions confirm the
+vertex order).
+
+Float bounds, u = 2^-24, every operation of the kernel counted as one rounding (a contraction into an fma rounds less):
+  lattice coordinate  lo + (idx / (G-1)) (hi - lo): 3 u |hi - lo| + u |P| <= 7 u M, M = max(|lo|, |hi|) of the axis
+  t = (level - v_lo) / (v_hi - v_lo): the inputs are exact floats, so 3 roundings, |dt| <= 3 u
+  p = p_lo + t (p_hi - p_lo): 7 u M + (14 u M + u h + 3 u h + u h) + u M = 22 u M + 5 u h, h the edge's extent on the axis
+  -> POS_K = 24 on the scale the issue sets: cond * edge length + M, cond = (|level| + |v_lo| + |v_hi|) / |v_hi - v_lo| >= 1.
+  gradient component (v_a - v_b) / (c h), h = (hi - lo) / (G-1): 4 u relative; weights 1 - t and t: 4 u and 3 u absolute;
+  n_c = (1-t) g_lo + t g_hi: <= 10 u (|g_lo,c| + |g_hi,c|), so |dn| <= 10 u S, S = gscale; normalising divides by |n| (first
+  order, |dn| / |n| <= 10 * 2^-14 under the floor) and adds 5 u of its own (scale, squares, sums, root, quotient)
+  -> NRM_K = 12 on the scale S / |n| + 1, for vertices with |n| >= GRADIENT_FLOOR * S (the others, capped at 1 %, are skipped).
+
+Scan levels: a point's prefix is local + s0[p >> 8] + s1[p >> 16] + s2[p >> 24].  (40,40,40) has 250 count blocks under one
+second-level chunk.  (48,40,41) = 78 720 points -- added, since 64 000 points fit one second-level chunk here -- carries a noisy
+slab that crosses every i plane, so vertices and cubes lie on both sides of point 65 536 and s1[1] is a nonzero prefix that is
+read.  (260,256,256) = 17 039 360 points is the smallest convenient shape past 2^24 points, where s2[1] comes into play: a
+fault in that term can show at no smaller size.  It is zero but for two small noisy blobs, one at the start and one across
+point 2^24, so the restatement walks a few hundred cubes.  The tests assert where the owners lie."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import _iso_prim as P
+from _util import GOLDEN, load_case, record_margin
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+U = 2.0 ** -24
+POS_K, NRM_K = 24.0, 12.0
+BOX = np.array([[-1.5, -1.25, 0.5], [1.0, 1.75, 2.0]], dtype=np.float32)
+
+
+def gpu_mesh(vol, level, aabb, **kw):
+    import rodynrf
+    out = rodynrf.extract_isosurface(torch.from_numpy(np.ascontiguousarray(vol)).to(DEV), level, torch.from_numpy(np.asarray(aabb, dtype=np.float32)), **kw)
+    assert out[0].dtype == torch.float32 and out[1].dtype == torch.int32 and out[0].shape[1:] == (3,) and out[1].shape[1:] == (3,)
+    return [o.cpu().numpy() for o in out]
+
+
+def seeded_volume(shape, seed):
+    """uniform [0, 1) on the small shapes.  On the large ones the restatement's Python loops could not walk 60 000 cubes in a
+    test's time, so the noise rides on a shape: a ball on (40,40,40); on (48,40,41) a slab |y| < 0.35 along the middle axis,
+    whose two sheets cross every i plane (every sample is still random, every case of the rules still occurs)"""
+    rng = np.random.default_rng(seed)
+    noise = rng.random(shape)
+    if np.prod(shape) < 10000:
+        return noise.astype(np.float32)
+    if np.prod(shape) > 65536:
+        y = np.linspace(-1, 1, shape[1])[None, :, None]
+        return (0.5 + 0.35 - np.abs(y) + 0.1 * (noise - 0.5)).astype(np.float32)
+    x = np.stack(np.meshgrid(*[np.linspace(-1, 1, g) for g in shape], indexing="ij"), -1)
+    return (0.5 + 0.7 - np.linalg.norm(x, axis=-1) + 0.1 * (noise - 0.5)).astype(np.float32)
+
+
+def assert_owners_on_both_sides(ref, shape, boundary):
+    """vertices and cubes with triangles below and at or above point `boundary`: the prefix table entry of the chunk that
+    starts there is nonzero and is read.  A face's cube corner p satisfies p <= owner <= p + G1 G2 + G2 + 1 for its vertices' owners."""
+    own = ref["keys"][:, 0]
+    reach = shape[1] * shape[2] + shape[2] + 1
+    f_own = own[ref["faces"]]
+    assert (own < boundary).sum() > 100 and (own >= boundary).sum() > 100, ((own < boundary).sum(), (own >= boundary).sum())
+    assert (f_own.max(1) < boundary).sum() > 100 and (f_own.min(1) >= boundary + reach).sum() > 100
+
+
+def position_bounds(ref, vol, level, aabb):
+    """per vertex and axis: POS_K u (cond * edge length + M)"""
+    aabb = np.asarray(aabb, dtype=np.float64).reshape(2, 3)
+    v = np.asarray(vol, dtype=np.float64)
+    lo, hi = ref["ends"][:, 0], ref["ends"][:, 1]
+    v_lo, v_hi = v[tuple(lo.T)], v[tuple(hi.T)]
+    cell = (aabb[1] - aabb[0]) / (np.array(v.shape) - 1)
+    edge = np.linalg.norm((hi - lo) * cell, axis=1)
+    cond = (abs(float(level)) + np.abs(v_lo) + np.abs(v_hi)) / np.abs(v_hi - v_lo)
+    M = np.abs(aabb).max(0)
+    return POS_K * U * ((cond * edge)[:, None] + M[None, :]), edge, v_lo, v_hi
+
+
+def check_against_restatement(name, vol, level, aabb, got, ref, normals=True):
+    verts, faces = got[0], got[1]
+    assert verts.shape[0] == len(ref["verts"]) and faces.shape[0] == len(ref["faces"]), (name, verts.shape, faces.shape,
+                                                                                          len(ref["verts"]), len(ref["faces"]))
+    assert np.array_equal(faces.astype(np.int64), ref["faces"]), name            # the same triples in the same order
+    if verts.shape[0] == 0:
+        return
+    bound, edge, v_lo, v_hi = position_bounds(ref, vol, level, aabb)
+    err = np.abs(verts.astype(np.float64) - ref["verts"])
+    ratio = float((err / bound).max())
+    print(f"{name}: nv {len(verts)} nf {len(faces)} position err/bound {ratio:.3f} (max err {err.max():.3e})")
+    record_margin(name + " positions", ratio)
+    assert ratio <= 1.0, (name, ratio)
+    # residual: the edge's linear interpolant at the GPU vertex is the level
+    aabb64 = np.asarray(aabb, dtype=np.float64).reshape(2, 3)
+    cell = (aabb64[1] - aabb64[0]) / (np.array(vol.shape[:3]) - 1)
+    p_lo = aabb64[0] + ref["ends"][:, 0] * cell
+    d = (ref["ends"][:, 1] - ref["ends"][:, 0]) * cell
+    t_gpu = np.einsum("ij,ij->i", verts.astype(np.float64) - p_lo, d) / edge ** 2
+    resid = np.abs(v_lo + t_gpu * (v_hi - v_lo) - float(level))
+    rb = np.linalg.norm(bound, axis=1) / edge * np.abs(v_hi - v_lo)
+    ratio = float((resid / rb).max())
+    print(f"{name}: residual/bound {ratio:.3f}")
+    record_margin(name + " residual", ratio)
+    assert ratio <= 1.0, (name, ratio)
+    if normals and len(got) > 2:
+        keep = ref["gnorm"] >= P.GRADIENT_FLOOR * ref["gscale"]
+        assert (~keep).mean() <= 0.01, (name, (~keep).mean())
+        nb = NRM_K * U * (ref["gscale"][keep] / ref["gnorm"][keep] + 1.0)
+        nerr = np.abs(got[2].astype(np.float64)[keep] - ref["normals"][keep]).max(1)
+        ratio = float((nerr / nb).max())
+        print(f"{name}: normal err/bound {ratio:.3f} ({int((~keep).sum())} of {len(keep)} under the gradient floor)")
+        record_margin(name + " normals", ratio)
+        assert ratio <= 1.0, (name, ratio)
+
+
+@pytest.mark.parametrize("shape", [(2, 2, 2), (3, 2, 5), (9, 17, 33), (65, 4, 3), (40, 40, 40), (48, 40, 41)])
+def test_random_volumes_match_the_restatement(shape):
+    vol = seeded_volume(shape, sum(shape))
+    ref = P.marching_tets(vol, 0.5, BOX, normals=True)
+    assert len(ref["faces"]) > 0
+    if np.prod(shape) > 60000:
+        assert len(ref["faces"]) > 5000 and len(ref["verts"]) > 2 * 1792   # more vertices than two count blocks can hold
+    if np.prod(shape) > 65536:
+        assert_owners_on_both_sides(ref, shape, 65536)
+    got = gpu_mesh(vol, 0.5, BOX, normals=True)
+    check_against_restatement(f"random {shape}", vol, 0.5, BOX, got, ref)
+    plain = gpu_mesh(vol, 0.5, BOX)
+    assert len(plain) == 2 and plain[0].tobytes() == got[0].tobytes() and np.array_equal(plain[1], got[1])
+
+
+@pytest.mark.parametrize("t_index", [0, 2])
+def test_time_slice_of_a_4d_volume(t_index):
+    vol4 = np.random.default_rng(5).random((9, 17, 33, 3)).astype(np.float32)
+    sliced = np.ascontiguousarray(vol4[..., t_index])
+    got = gpu_mesh(vol4, 0.5, BOX, t_index=t_index, normals=True)
+    want = gpu_mesh(sliced, 0.5, BOX, normals=True)
+    for a, b in zip(got, want):
+        assert a.shape == b.shape and a.tobytes() == b.tobytes()
+    check_against_restatement(f"slice {t_index} of T=3", sliced, 0.5, BOX, got, P.marching_tets(sliced, 0.5, BOX), normals=False)
+
+
+def test_a_volume_past_2_to_the_24_points():
+    """the third term of the prefix, s2[p >> 24], is zero for every volume below 16 777 216 points"""
+    shape = (260, 256, 256)
+    rng = np.random.default_rng(24)
+    vol = np.zeros(shape, dtype=np.float32)
+    for ci, rad in ((3, 2.5), (257, 2.2)):       # point 2^24 is (256, 0, 0): the second blob lies across it
+        idx = np.stack(np.meshgrid(np.arange(ci - 3, ci + 3), np.arange(124, 132), np.arange(124, 132), indexing="ij"), -1)
+        d = np.linalg.norm(idx - np.array([ci, 127.5, 127.5]), axis=-1)
+        vol[ci - 3:ci + 3, 124:132, 124:132] = (0.5 + 0.25 * (rad - d) + 0.1 * (rng.random(d.shape) - 0.5)).astype(np.float32)
+    ref = P.marching_tets(vol, 0.5, BOX, normals=True)
+    own = ref["keys"][:, 0]
+    f_own = own[ref["faces"]]
+    reach = shape[1] * shape[2] + shape[2] + 1
+    assert (own < 1 << 24).sum() > 100 and (own >= 1 << 24).sum() > 100
+    assert (f_own.max(1) < 1 << 24).sum() > 100 and (f_own.min(1) >= (1 << 24) + reach).sum() > 50
+    got = gpu_mesh(vol, 0.5, BOX, normals=True)
+    check_against_restatement(f"blobs {shape}", vol, 0.5, BOX, got, ref)
+
+
+def test_all_256_sign_patterns_of_one_cube():
+    worst = 0.0
+    for pattern, vol in enumerate(P.all_sign_patterns(np.random.default_rng(256))):
+        ref = P.marching_tets(vol, 0.5, BOX)
+        verts, faces = gpu_mesh(vol, 0.5, BOX)
+        assert verts.shape[0] == len(ref["verts"]) and np.array_equal(faces.astype(np.int64), ref["faces"]), pattern
+        if len(verts):
+            bound = position_bounds(ref, vol, 0.5, BOX)[0]
+            worst = max(worst, float((np.abs(verts - ref["verts"]) / bound).max()))
+    record_margin("256 patterns positions", worst)
+    assert worst <= 1.0
+
+
+@pytest.mark.parametrize("name", ["sphere", "torus", "two_spheres"])
+def test_analytic_volumes(name):
+    vol, chi, analytic = P.analytic_cases()[name]
+    ref = P.reference(name)
+    got = gpu_mesh(vol, 0.0, P.AABB, normals=True)
+    check_against_restatement(name, vol, 0.0, P.AABB, got, ref)
+    verts, faces = got[0], got[1]
+    assert P.is_closed(faces) and P.is_oriented(faces)
+    assert P.euler_characteristic(len(verts), faces) == chi
+    V, V_ref = P.signed_volume(verts, faces), P.signed_volume(ref["verts"], ref["faces"])
+    # a vertex moved by e changes the volume by at most e x (a third of the area of the faces around it); summed: area x max |e|
+    f = ref["faces"]
+    area = 0.5 * np.linalg.norm(np.cross(ref["verts"][f[:, 1]] - ref["verts"][f[:, 0]], ref["verts"][f[:, 2]] - ref["verts"][f[:, 0]]), axis=1).sum()
+    float_bound = area * float(np.linalg.norm(position_bounds(ref, vol, 0.0, P.AABB)[0], axis=1).max())
+    tol = abs(V_ref - analytic) + float_bound
+    print(f"{name}: V {V:.6f} restatement {V_ref:.6f} analytic {analytic:.6f}; |V - analytic| {abs(V - analytic):.3e} tol {tol:.3e}; "
+          f"|V - V_ref| {abs(V - V_ref):.3e} float bound {float_bound:.3e}")
+    record_margin(name + " volume", abs(V - V_ref) / float_bound)
+    assert V > 0 and abs(V - analytic) <= tol and abs(V - V_ref) <= float_bound
+    flipped = gpu_mesh(vol, 0.0, P.AABB, flip=True)
+    assert flipped[0].tobytes() == verts.tobytes() and np.array_equal(flipped[1], faces[:, [0, 2, 1]])
+    assert P.signed_volume(flipped[0], flipped[1]) == -V
+
+
+def test_cap_closes_a_sphere_cut_by_the_boundary():
+    vol = P.sphere_volume(P.SHAPE, P.AABB, (0.8, -0.1, 0.2), 0.5).astype(np.float32)   # centre 0.2 from the face x = 1
+    verts, faces = gpu_mesh(vol, 0.0, P.AABB)
+    open_edges = P.boundary_edges(faces)
+    assert len(open_edges) > 10 and not P.is_closed(faces) and P.is_oriented(faces)
+    assert all(n <= 2 for n in P.edge_use_counts(faces).values())
+    on_wall = np.abs(verts[np.unique(np.array(open_edges))][:, 0] - 1.0) < 1e-6
+    assert on_wall.all()                                            # it is open exactly where it meets the boundary
+    cv, cf, cn = gpu_mesh(vol, 0.0, P.AABB, cap=True, normals=True)
+    assert P.is_closed(cf) and P.is_oriented(cf) and P.euler_characteristic(len(cv), cf) == 2
+    assert np.isfinite(cv).all() and np.isfinite(cn).all() and float(cv[:, 0].max()) <= 1.0 + 1e-6
+    assert float(cv[:, 0].max()) > 1.0 - 1e-6                       # the cap lies in the wall
+    pad = np.full((26, 26, 26), -1.0e30, dtype=np.float32)
+    pad[1:-1, 1:-1, 1:-1] = vol
+    cell = (P.AABB[1].astype(np.float64) - P.AABB[0]) / 23
+    pad_box = np.stack((P.AABB[0] - cell, P.AABB[1] + cell)).astype(np.float32)
+    ref = P.marching_tets(pad, 0.0, pad_box)
+    check_against_restatement("capped sphere", pad, 0.0, pad_box, [cv, cf], ref)
+    # the part of the ball inside the box is a ball minus a spherical cap of height 0.3; tolerance as for the analytic cases:
+    # the restatement's own deviation at this lattice plus area x the largest position bound
+    exact = 4 / 3 * np.pi * 0.5 ** 3 - np.pi * 0.3 ** 2 * (3 * 0.5 - 0.3) / 3
+    V_cap, V_ref = P.signed_volume(cv, cf), P.signed_volume(ref["verts"], ref["faces"])
+    f = ref["faces"]
+    area = 0.5 * np.linalg.norm(np.cross(ref["verts"][f[:, 1]] - ref["verts"][f[:, 0]], ref["verts"][f[:, 2]] - ref["verts"][f[:, 0]]), axis=1).sum()
+    float_bound = area * float(np.linalg.norm(position_bounds(ref, pad, 0.0, pad_box)[0], axis=1).max())
+    print(f"capped sphere: V {V_cap:.6f} restatement {V_ref:.6f} exact {exact:.6f} float bound {float_bound:.3e}")
+    assert V_cap > 0 and abs(V_cap - V_ref) <= float_bound and abs(V_cap - exact) <= abs(V_ref - exact) + float_bound
+    # a 4-D volume: only the meshed slice is padded, and the result is that of the slice alone
+    vol4 = np.stack((np.zeros_like(vol), vol, np.ones_like(vol)), -1)
+    for a4, a3 in zip(gpu_mesh(vol4, 0.0, P.AABB, t_index=1, cap=True, normals=True), (cv, cf, cn)):
+        assert a4.tobytes() == a3.tobytes()
+
+
+def test_empty_and_full_volumes():
+    for fill in (0.0, 1.0):
+        vol = np.full((5, 6, 7), fill, dtype=np.float32)
+        verts, faces, normals = gpu_mesh(vol, 0.5, BOX, normals=True)
+        assert verts.shape == (0, 3) and faces.shape == (0, 3) and normals.shape == (0, 3)
+    vol = np.full((5, 6, 7), 0.5, dtype=np.float32)      # v == level everywhere: all inside
+    assert gpu_mesh(vol, 0.5, BOX)[0].shape == (0, 3)
+    vol[2, 3, 4] = 0.25                                   # one outside sample among v == level: t = 1, degenerate triangles are legal
+    verts, faces = gpu_mesh(vol, 0.5, BOX)
+    ref = P.marching_tets(vol, 0.5, BOX)
+    assert len(verts) == len(ref["verts"]) == 14 and np.array_equal(faces.astype(np.int64), ref["faces"])
+    assert P.is_closed(faces) and P.euler_characteristic(len(verts), faces) == 2
+
+
+def det_case():
+    """what both libraries run (tests/_iso_det_child.py)"""
+    vol = seeded_volume((9, 17, 33), 3)
+    out = {}
+    for k, o in enumerate(gpu_mesh(vol, 0.5, BOX, normals=True)):
+        out[f"random{k}"] = torch.from_numpy(o)
+    for k, o in enumerate(gpu_mesh(P.analytic_cases()["torus"][0], 0.0, P.AABB, normals=True, flip=True)):
+        out[f"torus{k}"] = torch.from_numpy(o)
+    return out
+
+
+def test_two_runs_and_a_poisoned_workspace_give_the_same_bits():
+    from importlib import import_module
+    L = import_module("robust-dynrf_amd._lib")
+    first = det_case()
+    again = det_case()
+    for k in first:
+        assert first[k].numpy().tobytes() == again[k].numpy().tobytes(), k
+    for byte in (0xFF, 0x00, 0x7F):                        # 0xFF: NaNs as floats, all ones as counts
+        for buf in L._ws.values():
+            buf.fill_(byte)
+        poisoned = det_case()
+        for k in first:
+            assert first[k].numpy().tobytes() == poisoned[k].numpy().tobytes(), (k, byte)
+
+
+def test_deterministic_library_extracts_the_same_mesh(tmp_path):
+    mine = det_case()
+    env = dict(os.environ, RDRF_DETERMINISTIC="1")
+    env.pop("RDRF_MARGINS", None)
+    env.pop("RDRF_LIB", None)
+    out = str(tmp_path / "det.pt")
+    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_iso_det_child.py")
+    r = subprocess.run([sys.executable, child, out], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    det = torch.load(out)
+    assert set(det) == set(mine)
+    for k, v in mine.items():
+        assert v.numpy().tobytes() == det[k].numpy().tobytes(), k
+
+
+# ---- end to end on the ndc_relu fixture fields ---------------------------------------------------------------------------
+_fields = {}
+
+
+def fixture_fields():
+    if not _fields:
+        import rodynrf
+        g, sd_s, _, sd_d, _ = load_case("ndc_relu")
+        grid = [int(v) for v in g["meta.grid"]]
+        kw = dict(density_n_comp=[16, 4, 4], appearance_n_comp=[48, 12, 12], app_dim=27, near_far=[0.0, 1.0], alphaMask_thres=1e-4,
+                  density_shift=-10, distance_scale=25, pos_pe=6, view_pe=0, featureC=128, step_ratio=2.0, fea2denseAct="relu")
+        aabb = torch.from_numpy(g["aabb"])
+        st = rodynrf.TensorVMSplit(aabb, grid, 12, DEV, shadingMode="MLP_Fea", fea_pe=2, **kw)
+        dy = rodynrf.TensorVMSplit_TimeEmbedding(aabb, grid, 12, DEV, shadingMode="MLP_Fea_late_view", fea_pe=0, **kw)
+        st.load_state_dict(sd_s)
+        dy.load_state_dict(sd_d)
+        _fields["static"], _fields["dynamic"] = st, dy
+    return _fields
+
+
+LATTICE = (12, 10, 9)
+
+
+def mid_level(field, times):
+    alpha, _ = field.getDenseAlpha(LATTICE, times=times)
+    lo, hi = float(alpha.min()), float(alpha.max())
+    assert hi > lo, (lo, hi)
+    return alpha, 0.5 * (lo + hi)
+
+
+@pytest.mark.parametrize("which", ["static", "dynamic"])
+def test_field_mesh_is_the_extraction_of_the_dense_alpha(which, tmp_path):
+    import rodynrf
+    field = fixture_fields()[which]
+    t = None if which == "static" else 0.25
+    alpha, level = mid_level(field, [0.0 if t is None else t])
+    want = rodynrf.extract_isosurface(alpha[..., 0], level, field.aabb, normals=True)
+    assert want[0].shape[0] > 0 and want[1].shape[0] > 0
+    got = rodynrf.field_mesh(field, t, level, LATTICE, normals=True)
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+    if which == "dynamic":
+        with pytest.raises(rodynrf.RdrfError):
+            rodynrf.field_mesh(field, None, level, LATTICE)
+    with pytest.raises(rodynrf.RdrfError):
+        rodynrf.field_mesh(field, t, level, LATTICE, colors=torch.zeros(3))
+    path = str(tmp_path / "mesh.ply")
+    out = field.export_mesh(path, t, level, gridSize=LATTICE, normals=True)
+    back = rodynrf.read_ply(path)
+    for key, o in zip(("verts", "faces", "normals"), out):
+        assert torch.equal(o, want[("verts", "faces", "normals").index(key)])
+        assert back[key].tobytes() == o.cpu().numpy().tobytes()
+    ckpt = str(tmp_path / "field.th")
+    field.save(torch.eye(3, 4)[None].repeat(12, 1, 1), torch.tensor(1.0), ckpt)
+    path2 = str(tmp_path / "from_ckpt.ply")
+    rodynrf.export_mesh(ckpt, path2, t, level, gridSize=LATTICE, normals=True, device=DEV)
+    assert open(path2, "rb").read() == open(path, "rb").read()
+
+
+def test_mesh_sequence_equals_single_calls():
+    import rodynrf
+    field = fixture_fields()["dynamic"]
+    times = [-1.0, 0.25, 1.0]
+    _, level = mid_level(field, times)
+    with pytest.raises(rodynrf.RdrfError):          # refused at the call, not at the first next()
+        rodynrf.mesh_sequence(field, times, level, LATTICE, colors=torch.zeros(3))
+    with pytest.raises(TypeError):
+        rodynrf.mesh_sequence(field, times, level, LATTICE, smooth=True)
+    seq = list(rodynrf.mesh_sequence(field, times, level, LATTICE, normals=True))
+    assert len(seq) == 3 and sum(m[1].shape[0] for m in seq) > 0
+    for t, m in zip(times, seq):
+        one = rodynrf.field_mesh(field, t, level, LATTICE, normals=True)
+        for a, b in zip(m, one):
+            assert torch.equal(a, b), t
+
+
+def test_world_space_vertices_follow_ndc2world():
+    import rodynrf
+    field = fixture_fields()["static"]
+    _, level = mid_level(field, [0.0])
+    H, W, focal = 27.0, 48.0, 41.5                       # exact in float32
+    v_ndc, f_ndc = rodynrf.field_mesh(field, None, level, LATTICE)
+    v_w, f_w, n_w = rodynrf.field_mesh(field, None, level, LATTICE, space="world", H=H, W=W, focal=focal, normals=True)
+    assert torch.equal(f_w, f_ndc) and v_w.shape == v_ndc.shape and v_ndc.shape[0] > 0
+    p = v_ndc.double().cpu()
+    z = 2 / (torch.clamp(p[:, 2:], min=-1.0, max=float(np.float32(1 - 1e-6))) - 1)
+    want = torch.cat([-p[:, 0:1] * z * W / 2 / focal, -p[:, 1:2] * z * H / 2 / focal, z], -1)
+    # z: a subtraction and a quotient (2 roundings); x, y: a negation (exact), a product, three scalings (4 more): 8 u |value| covers both
+    ratio = float(((v_w.double().cpu() - want).abs() / (8 * U * want.abs() + 1e-300)).max())
+    record_margin("NDC2world", ratio)
+    assert ratio <= 1.0, ratio
+    ln = n_w.norm(dim=-1)
+    assert bool(((ln - 1).abs() < 1e-5).logical_or(ln == 0).all())
+    with pytest.raises(rodynrf.RdrfError):
+        rodynrf.field_mesh(field, None, level, LATTICE, space="world")

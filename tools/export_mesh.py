@@ -1,0 +1,36 @@
+#!/usr/bin/env python
+"""Checkpoint -> isosurface mesh (the reference's --export_mesh, train.py:107-118), on the device.
+
+    python tools/export_mesh.py ckpt.th out.ply [--time T] [--level L] [--grid G0 G1 G2] [--cap] [--normals] [--flip]
+                                                [--world H W focal]
+
+--time is required for a dynamic field (times run over [-1, 1]); --world maps the vertices of an ndc field to world space."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("ckpt")
+    ap.add_argument("ply")
+    ap.add_argument("--time", type=float, default=None)
+    ap.add_argument("--level", type=float, default=0.005)
+    ap.add_argument("--grid", type=int, nargs=3, default=None, metavar=("G0", "G1", "G2"))
+    ap.add_argument("--cap", action="store_true")
+    ap.add_argument("--normals", action="store_true")
+    ap.add_argument("--flip", action="store_true")
+    ap.add_argument("--world", type=float, nargs=3, default=None, metavar=("H", "W", "focal"))
+    a = ap.parse_args()
+    import rodynrf
+    kw = dict(cap=a.cap, normals=a.normals, flip=a.flip)
+    if a.world is not None:
+        kw.update(space="world", H=a.world[0], W=a.world[1], focal=a.world[2])
+    out = rodynrf.export_mesh(a.ckpt, a.ply, t=a.time, level=a.level, gridSize=a.grid, **kw)
+    print(f"{a.ply}: {out[0].shape[0]} vertices, {out[1].shape[0]} faces")
+
+
+if __name__ == "__main__":
+    main()
