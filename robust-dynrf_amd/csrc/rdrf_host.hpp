@@ -126,6 +126,14 @@ static inline Geo geo_for_units(long units) {
   return g;
 }
 static inline Geo geo_for_tiles(int N, int S) { return geo_for_units(((long)N * S + 31) / 32); }
+// the CU count of the CURRENT device (a process may drive several), for the launches that size themselves by it
+static inline int current_cu_count(int* ncu) {
+  int dev = 0;
+  RDRF_HIP(hipGetDevice(&dev));
+  RDRF_HIP(hipDeviceGetAttribute(ncu, hipDeviceAttributeMultiprocessorCount, dev));
+  if (*ncu <= 0) *ncu = 256;
+  return 0;
+}
 
 // component counts + the three planes / lines span ONE grid (plane XY <-> line Z, XZ <-> Y, YZ <-> X): the forward
 // kernels compute one tap per grid axis and share it between the planes (rdrf_common.hpp, shared-tap gather)

@@ -129,15 +129,15 @@ extern "C" int rdrf_render_motion_fwd(const RdrfStaticParams* PS, const RdrfFiel
   RDRF_CHECK(cfg_d && (cfg_d->ray_type == RDRF_RAY_NDC || cfg_d->ray_type == RDRF_RAY_CONTRACT), -1,
              "render_motion: ray_type must be ndc or contract (renderer.py:1335-1351)");
   // the render itself: same launches, same bits (the workspace carve does not depend on the motion request)
-  int rc = rdrf_render_maps_fwd(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, mode, maps, ws, ws_bytes, stream_);
-  if (rc) return rc;
+  RenderCall c = {PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, 0.f, {}, ws, ws_bytes};
+  maps_to_slots(c.want, maps);
+  RenderBufs b;
+  RDRF_TRY(render_run(c, mode, "render_maps", b, stream_));
   if (!motion->flow_f && !motion->flow_b && !motion->flow_s_f && !motion->flow_s_b && !motion->delta_xyz) return 0;
   MotionArgs a;
   memset(&a, 0, sizeof(a));
-  void* fws_d = nullptr;
-  rc = render_motion_views(maps, ws, ws_bytes, N, S, &a.xyz, &a.xyz_prime, &a.w_s, &a.w_d, &a.barrier, &fws_d);
-  if (rc) return rc;
-  if (mode != RDRF_RENDER_FUSED) a.barrier = nullptr;   // only the cooperative launch has a barrier (and clears it)
+  a.xyz = b.xyz; a.xyz_prime = b.xyz_prime; a.w_s = b.out[7]; a.w_d = b.out[11];
+  a.barrier = mode == RDRF_RENDER_FUSED ? b.barrier : nullptr;   // only the cooperative launch has a barrier (and clears it)
   a.rays = rays; a.ts = ts;
   a.focal = cams->focal; a.c2w_f = cams->c2w_f; a.c2w_b = cams->c2w_b;
   a.flow_f = motion->flow_f; a.flow_b = motion->flow_b; a.flow_s_f = motion->flow_s_f; a.flow_s_b = motion->flow_s_b;
@@ -150,14 +150,11 @@ extern "C" int rdrf_render_motion_fwd(const RdrfStaticParams* PS, const RdrfFiel
   if (pkg == nullptr) {   // the image the dynamic field's forward packed into its workspace on this stream
     FieldArgs fa;
     memset(&fa, 0, sizeof(fa));
-    rc = ws_carve_fwd(fa, fws_d, rdrf_forward_workspace_bytes(N, S), N, S, nullptr, 0, 1);
-    if (rc) return rc;
+    RDRF_TRY(ws_carve_fwd(fa, b.fws_d, rdrf_forward_workspace_bytes(N, S), N, S, nullptr, 0, 1));
     pkg = fa.pk;
   }
-  int ncu = 0, dev = 0;
-  RDRF_HIP(hipGetDevice(&dev));
-  RDRF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  if (ncu <= 0) ncu = 256;
+  int ncu = 0;
+  RDRF_TRY(current_cu_count(&ncu));
   // persistent workgroups (the MLP form fills 45 KB of LDS once per workgroup): two per CU, or fewer for few rays
   long g = ((long)N + RDRF_MAXW - 1) / RDRF_MAXW;
   const long cap = (long)ncu * (mlp ? 2 : 8);

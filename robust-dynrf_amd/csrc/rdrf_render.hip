@@ -1,6 +1,6 @@
 // rdrf_render.hip -- no-grad render of a ray chunk in one launch sequence (the loop body of
-// /root/reference/renderer.py:740-812: sampleXYZ -> static -> dynamic -> raw2outputs), and a
-// self-test of the MFMA layer primitive used by tests/.
+// the reference's renderer.py:740-812: sampleXYZ -> static -> dynamic -> raw2outputs), and the host steps the render
+// units share (rdrf_render_host.hpp).
 #include "rdrf_misc_dev.hpp"
 #include "rdrf_render_host.hpp"
 
@@ -121,8 +121,14 @@ void maps_to_slots(float* out[13], const RdrfRenderMaps* m) {
   for (int i = 0; i < 10; ++i) out[kMapSlot[i]] = p[i];
 }
 
-// want[13]: the caller's output buffers (NULL: the output goes to the workspace).  The legacy entry points pass rgb and
-// depth only, which carves the workspace exactly as before the maps existed.
+int want_rgb_depth(float* want[13], float* rgb_map, float* depth_map, const char* who) {
+  RDRF_CHECK(rgb_map && depth_map, -1, "%s: bad arguments", who);
+  maps_to_slots(want, nullptr);
+  want[0] = rgb_map;
+  want[1] = depth_map;
+  return 0;
+}
+
 int carve_render(RenderBufs& b, void* ws, size_t ws_bytes, int N, int S, float* const want[13]) {
   WsCarver c(ws, ws_bytes);
   const size_t ns = (size_t)N * S;
@@ -149,66 +155,83 @@ int carve_render(RenderBufs& b, void* ws, size_t ws_bytes, int N, int S, float* 
   return 0;
 }
 
-static int render_check(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
-                        const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float step,
-                        size_t ws_bytes) {
-  RDRF_CHECK(PS && PD && cfg_s && cfg_d && rays && ts && N > 0 && S > 0, -1, "render: bad arguments");
-  // `step` > 0 comes from rdrf_render_world_fwd alone: the world march needs it, the other two samplers have no use for it
-  RDRF_CHECK((cfg_d->ray_type == RDRF_RAY_NDC || cfg_d->ray_type == RDRF_RAY_CONTRACT) == !(step > 0.0f), -1,
-             "render: ray_type ndc / contract through rdrf_render_*_fwd, any other through rdrf_render_world_fwd with "
-             "step > 0 (ray_type %d, step %g)", cfg_d->ray_type, (double)step);
-  RDRF_CHECK((size_t)N * S * 3 < (size_t)INT32_MAX, -1, "render: N * S * 3 must stay below 2^31: render in chunks");
-  RDRF_CHECK(ws_bytes >= rdrf_render_workspace_bytes(N, S), -3, "render: workspace too small");
+int render_check_args(const RenderCall& c, const char* who, const char* step_rule) {
+  RDRF_CHECK(c.PS && c.PD && c.cfg_s && c.cfg_d && c.rays && c.ts && c.N > 0 && c.S > 0, -1, "%s: bad arguments", who);
+  const int ray_type = c.cfg_d->ray_type;
+  RDRF_CHECK((ray_type == RDRF_RAY_NDC || ray_type == RDRF_RAY_CONTRACT) == !(c.step > 0.0f), -1, "%s: %s (ray_type %d, step %g)",
+             who, step_rule, ray_type, (double)c.step);
+  RDRF_CHECK((size_t)c.N * c.S * 3 < (size_t)INT32_MAX, -1, "%s: N * S * 3 must stay below 2^31: render in chunks", who);
+  return 0;
+}
+int render_check_fields(const RenderCall& c, const char* who) {
+  const RdrfStaticParams* PS = c.PS;
+  const RdrfDynamicParams* PD = c.PD;
   RDRF_CHECK(vm_ok(PS->density, 16, 4) && vm_ok(PS->app, 48, 12) && vm_ok(PD->density, 16, 4) && vm_ok(PD->blending, 16, 4) &&
              vm_ok(PD->app, 48, 12) && vm_same_grid(PD->density, PD->blending), -1,
-             "render: only density comps {16,4,4} / app comps {48,12,12} of one grid are built");
+             "%s: only density comps {16,4,4} / app comps {48,12,12} of one grid are built", who);
+  return 0;
+}
+// the checks of this unit's runners and the carve behind them
+static int render_begin(const RenderCall& c, RenderBufs& b) {
+  // `step` > 0 comes from rdrf_render_world_fwd alone: the world march needs it, the other two samplers have no use for it
+  RDRF_TRY(render_check_args(c, "render", "ray_type ndc / contract through rdrf_render_*_fwd, any other through "
+                                          "rdrf_render_world_fwd with step > 0"));
+  RDRF_CHECK(c.ws_bytes >= rdrf_render_workspace_bytes(c.N, c.S), -3, "render: workspace too small");
+  RDRF_TRY(render_check_fields(c, "render"));
+  return carve_render(b, c.ws, c.ws_bytes, c.N, c.S, c.want);
+}
+
+int render_sample(const RenderCall& c, const RenderBufs& b, rdrf_stream_t stream) {
+  const RdrfFieldCfg* cfg = c.cfg_d;
+  if (cfg->ray_type == RDRF_RAY_NDC)
+    return rdrf_sample_ndc(c.rays, c.N, c.S, c.near, c.far, nullptr, cfg->aabb, b.xyz, b.z, b.valid, stream);
+  if (cfg->ray_type == RDRF_RAY_CONTRACT)
+    return rdrf_sample_contract(c.rays, c.N, c.S, c.near, c.far, nullptr, nullptr, b.xyz, b.z, b.valid, stream);
+  return rdrf_sample_world(c.rays, c.N, c.S, c.near, c.far, c.step, nullptr, cfg->aabb, b.xyz, b.z, b.valid, stream);
+}
+
+int render_fields(const RenderCall& c, const RenderBufs& b, const uint8_t* valid_s, const uint8_t* valid_d, FieldArgs& as,
+                  FieldArgs& ad, StaticW& wst, DynW& wdy, hipStream_t stream) {
+  const int N = c.N, S = c.S;
+  const size_t fwb = rdrf_forward_workspace_bytes(N, S);
+  fill_common(as, c.cfg_s, c.rays, c.ts, b.xyz, b.z, valid_s, N, S);
+  as.rgb = b.rgb_s; as.sigma = b.sigma_s; as.weight = b.weight_s; as.dists = b.dists_s;
+  RDRF_TRY(ws_carve_fwd(as, b.fws_s, fwb, N, S, nullptr, 0, 0));
+  fill_common(ad, c.cfg_d, c.rays, c.ts, b.xyz, b.z, valid_d, N, S);
+  ad.rgb = b.rgb_d; ad.sigma = b.sigma_d; ad.weight = b.weight_d; ad.dists = b.dists_d;
+  ad.blending = b.blending; ad.xyz_prime = b.xyz_prime;
+  RDRF_TRY(ws_carve_fwd(ad, b.fws_d, fwb, N, S, nullptr, 0, 1));
+  fill_static_w(wst, c.PS);
+  fill_dyn_w(wdy, c.PD);
+  RDRF_TRY(pack_image(as.pk, c.PS->packed_fwd, (float*)as.pk, stream, static_pack_jobs_fwd, c.PS, c.cfg_s->static_head));
+  RDRF_TRY(pack_image(ad.pk, c.PD->packed_fwd, (float*)ad.pk, stream, dyn_pack_jobs_fwd, c.PD));
   return 0;
 }
 
 /* one cooperative launch (see k_render_fused) */
-static int render_fused(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
-                        const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near, float far,
-                        float step, float* const want[13], void* ws, size_t ws_bytes, rdrf_stream_t stream_) {
+static int render_fused(const RenderCall& c, RenderBufs& b, rdrf_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  if (N == 0) return 0;
-  int rc = render_check(PS, cfg_s, PD, cfg_d, rays, ts, N, S, step, ws_bytes);
-  if (rc) return rc;
-  RenderBufs b;
-  rc = carve_render(b, ws, ws_bytes, N, S, want);
-  if (rc) return rc;
+  RDRF_TRY(render_begin(c, b));
+  const int N = c.N, S = c.S;
   RenderFusedArgs r;
   memset(&r, 0, sizeof(r));
-  fill_common(r.as, cfg_s, rays, ts, b.xyz, b.z, b.valid, N, S);
-  r.as.rgb = b.rgb_s; r.as.sigma = b.sigma_s; r.as.weight = b.weight_s; r.as.dists = b.dists_s;
-  rc = ws_carve_fwd(r.as, b.fws_s, rdrf_forward_workspace_bytes(N, S), N, S, nullptr, 0, 0);
-  if (rc) return rc;
-  fill_common(r.ad, cfg_d, rays, ts, b.xyz, b.z, b.valid, N, S);
-  r.ad.rgb = b.rgb_d; r.ad.sigma = b.sigma_d; r.ad.weight = b.weight_d; r.ad.dists = b.dists_d;
-  r.ad.blending = b.blending; r.ad.xyz_prime = b.xyz_prime;
-  rc = ws_carve_fwd(r.ad, b.fws_d, rdrf_forward_workspace_bytes(N, S), N, S, nullptr, 0, 1);
-  if (rc) return rc;
-  fill_static_w(r.ws, PS);
-  fill_dyn_w(r.wd, PD);
-  RDRF_TRY(pack_image(r.as.pk, PS->packed_fwd, (float*)r.as.pk, stream, static_pack_jobs_fwd, PS, cfg_s->static_head));
-  RDRF_TRY(pack_image(r.ad.pk, PD->packed_fwd, (float*)r.ad.pk, stream, dyn_pack_jobs_fwd, PD));
+  RDRF_TRY(render_fields(c, b, b.valid, b.valid, r.as, r.ad, r.ws, r.wd, stream));
   r.comp.rgb_s = b.rgb_s; r.comp.sigma_s = b.sigma_s; r.comp.rgb_d = b.rgb_d; r.comp.sigma_d = b.sigma_d;
-  r.comp.dists = b.dists_d; r.comp.blending = b.blending; r.comp.z = b.z; r.comp.rays = rays;
-  r.comp.N = N; r.comp.S = S; r.comp.ray_type = cfg_d->ray_type; r.comp.add_white_bg = 0; r.comp.white_dev = nullptr;
+  r.comp.dists = b.dists_d; r.comp.blending = b.blending; r.comp.z = b.z; r.comp.rays = c.rays;
+  r.comp.N = N; r.comp.S = S; r.comp.ray_type = c.cfg_d->ray_type; r.comp.add_white_bg = 0; r.comp.white_dev = nullptr;
   for (int i = 0; i < 13; ++i) r.comp.out[i] = b.out[i];
-  r.near = near; r.far = far; r.step = step; r.barrier = b.barrier;
+  r.near = c.near; r.far = c.far; r.step = c.step; r.barrier = b.barrier;
   RDRF_FILL(b.barrier, 0, 256, stream);
   // one workgroup per CU at most (its LDS holds a whole weight image); fewer when the chunk has fewer units of work
   const long tiles = ((long)N * S + 31) / 32;
   const long units = tiles > N ? tiles : N;
-  int ncu = 0, dev = 0;   // of the CURRENT device (a process may drive several)
-  RDRF_HIP(hipGetDevice(&dev));
-  RDRF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  if (ncu <= 0) ncu = 256;
+  int ncu = 0;
+  RDRF_TRY(current_cu_count(&ncu));
   long g = (units + RDRF_MAXW - 1) / RDRF_MAXW;
   g = g < 1 ? 1 : (g > ncu ? ncu : g);
   const size_t lds_bytes = (size_t)(pk::S3_SIZE > pk::K3_SIZE ? (pk::S3_SIZE > pk::K1_SIZE ? pk::S3_SIZE : pk::K1_SIZE)
                                                             : (pk::K3_SIZE > pk::K1_SIZE ? pk::K3_SIZE : pk::K1_SIZE)) * 4;
-  const void* kern = cfg_s->static_head == RDRF_HEAD_MLP_FEA ? (const void*)k_render_fused<RDRF_HEAD_MLP_FEA>
+  const void* kern = c.cfg_s->static_head == RDRF_HEAD_MLP_FEA ? (const void*)k_render_fused<RDRF_HEAD_MLP_FEA>
                                                             : (const void*)k_render_fused<RDRF_HEAD_MLP_FEA_TIMEEMBEDDING>;
   RDRF_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
   void* kargs[] = {(void*)&r};
@@ -218,52 +241,47 @@ static int render_fused(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, c
   RDRF_CHECK(e == hipSuccess, -5, "render_fused: cooperative launch failed: %s", hipGetErrorString(e));
   return 0;
 }
+
+/* launch sequence of the per-phase kernels (whole frames: every kernel fills the chip, nothing to gain from fusion) */
+static int render_sequence(const RenderCall& c, RenderBufs& b, rdrf_stream_t stream) {
+  RDRF_TRY(render_begin(c, b));
+  RDRF_TRY(render_sample(c, b, stream));
+  // (a side stream for the static density phase under the dynamic field's density kernel does not overlap: the MLP kernels
+  // hold all 512 VGPRs of every SIMD, so no other wave becomes resident; measured, DESIGN.md section 9)
+  const int N = c.N, S = c.S;
+  const size_t fwb = rdrf_forward_workspace_bytes(N, S);
+  RDRF_TRY(rdrf_static_fwd(c.PS, c.cfg_s, c.rays, c.ts, b.xyz, b.z, b.valid, N, S, b.rgb_s, b.sigma_s, b.weight_s, b.dists_s,
+                           nullptr, 0, b.fws_s, fwb, stream));
+  RDRF_TRY(rdrf_dynamic_fwd(c.PD, c.cfg_d, c.rays, c.ts, b.xyz, b.z, b.valid, N, S, b.blending, b.weight_d, b.xyz_prime,
+                            b.rgb_d, b.sigma_d, b.dists_d, nullptr, 0, b.fws_d, fwb, stream));
+  return rdrf_composite_fwd(b.rgb_s, b.sigma_s, b.rgb_d, b.sigma_d, b.dists_d, b.blending, b.z, c.rays, N, S,
+                            c.cfg_d->ray_type, 0, nullptr, b.out, stream);
+}
+
+int render_run(const RenderCall& c, int mode, const char* who, RenderBufs& b, rdrf_stream_t stream) {
+  RDRF_CHECK(mode == RDRF_RENDER_AUTO || mode == RDRF_RENDER_SEQUENCE || mode == RDRF_RENDER_FUSED, -1, "%s: unknown mode %d",
+             who, mode);
+  return mode == RDRF_RENDER_FUSED ? render_fused(c, b, stream) : render_sequence(c, b, stream);
+}
+
 extern "C" int rdrf_render_fused_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
                                      const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near,
                                      float far, float* rgb_map, float* depth_map, void* ws, size_t ws_bytes,
                                      rdrf_stream_t stream) {
   if (N == 0) return 0;
-  RDRF_CHECK(rgb_map && depth_map, -1, "render: bad arguments");
-  float* want[13] = {rgb_map, depth_map};
-  return render_fused(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, 0.f, want, ws, ws_bytes, stream);
-}
-
-/* launch sequence of the per-phase kernels (whole frames: every kernel fills the chip, nothing to gain from fusion) */
-static int render_sequence(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
-                           const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near,
-                           float far, float step, float* const want[13], void* ws, size_t ws_bytes, rdrf_stream_t stream) {
-  if (N == 0) return 0;
-  int rc = render_check(PS, cfg_s, PD, cfg_d, rays, ts, N, S, step, ws_bytes);
-  if (rc) return rc;
+  RenderCall c = {PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, 0.f, {}, ws, ws_bytes};
+  RDRF_TRY(want_rgb_depth(c.want, rgb_map, depth_map, "render"));
   RenderBufs b;
-  rc = carve_render(b, ws, ws_bytes, N, S, want);
-  if (rc) return rc;
-  if (cfg_d->ray_type == RDRF_RAY_NDC)
-    rc = rdrf_sample_ndc(rays, N, S, near, far, nullptr, cfg_d->aabb, b.xyz, b.z, b.valid, stream);
-  else if (cfg_d->ray_type == RDRF_RAY_CONTRACT)
-    rc = rdrf_sample_contract(rays, N, S, near, far, nullptr, nullptr, b.xyz, b.z, b.valid, stream);
-  else
-    rc = rdrf_sample_world(rays, N, S, near, far, step, nullptr, cfg_d->aabb, b.xyz, b.z, b.valid, stream);
-  if (rc) return rc;
-  // (a side stream for the static density phase under the dynamic field's density kernel does not overlap: the MLP kernels
-  // hold all 512 VGPRs of every SIMD, so no other wave becomes resident; measured, DESIGN.md section 9)
-  const size_t fwb = rdrf_forward_workspace_bytes(N, S);
-  rc = rdrf_static_fwd(PS, cfg_s, rays, ts, b.xyz, b.z, b.valid, N, S, b.rgb_s, b.sigma_s, b.weight_s, b.dists_s,
-                       nullptr, 0, b.fws_s, fwb, stream);
-  if (rc) return rc;
-  rc = rdrf_dynamic_fwd(PD, cfg_d, rays, ts, b.xyz, b.z, b.valid, N, S, b.blending, b.weight_d, b.xyz_prime, b.rgb_d,
-                        b.sigma_d, b.dists_d, nullptr, 0, b.fws_d, fwb, stream);
-  if (rc) return rc;
-  return rdrf_composite_fwd(b.rgb_s, b.sigma_s, b.rgb_d, b.sigma_d, b.dists_d, b.blending, b.z, rays, N, S,
-                            cfg_d->ray_type, 0, nullptr, b.out, stream);
+  return render_fused(c, b, stream);
 }
 extern "C" int rdrf_render_sequence_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
                            const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near,
                            float far, float* rgb_map, float* depth_map, void* ws, size_t ws_bytes, rdrf_stream_t stream) {
   if (N == 0) return 0;
-  RDRF_CHECK(rgb_map && depth_map, -1, "render: bad arguments");
-  float* want[13] = {rgb_map, depth_map};
-  return render_sequence(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, 0.f, want, ws, ws_bytes, stream);
+  RenderCall c = {PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, 0.f, {}, ws, ws_bytes};
+  RDRF_TRY(want_rgb_depth(c.want, rgb_map, depth_map, "render"));
+  RenderBufs b;
+  return render_sequence(c, b, stream);
 }
 
 // Measured on MI355X (tools/render_bench.py, Balloon1 stage-0 shape, 240 x 135 frame): whole frame 7.7 ms either way (the
@@ -287,25 +305,10 @@ extern "C" int rdrf_render_maps_fwd(const RdrfStaticParams* PS, const RdrfFieldC
                                     float far, int mode, const RdrfRenderMaps* maps, void* ws, size_t ws_bytes,
                                     rdrf_stream_t stream) {
   if (N == 0) return 0;
-  RDRF_CHECK(mode == RDRF_RENDER_AUTO || mode == RDRF_RENDER_SEQUENCE || mode == RDRF_RENDER_FUSED, -1,
-             "render_maps: unknown mode %d", mode);
-  float* want[13];
-  maps_to_slots(want, maps);
-  return mode == RDRF_RENDER_FUSED ? render_fused(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, 0.f, want, ws, ws_bytes, stream)
-                                   : render_sequence(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, 0.f, want, ws, ws_bytes, stream);
-}
-
-// where a render with these `maps` left what the motion maps read (rdrf_motion.hip): the carve of the render itself
-int render_motion_views(const RdrfRenderMaps* maps, void* ws, size_t ws_bytes, int N, int S, const float** xyz,
-                        const float** xyz_prime, const float** weights_s, const float** weights_d, const unsigned** barrier,
-                        void** fws_d) {
-  float* want[13];
-  maps_to_slots(want, maps);
+  RenderCall c = {PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, 0.f, {}, ws, ws_bytes};
+  maps_to_slots(c.want, maps);
   RenderBufs b;
-  const int rc = carve_render(b, ws, ws_bytes, N, S, want);
-  if (rc) return rc;
-  *xyz = b.xyz; *xyz_prime = b.xyz_prime; *weights_s = b.out[7]; *weights_d = b.out[11]; *barrier = b.barrier; *fws_d = b.fws_d;
-  return 0;
+  return render_run(c, mode, "render_maps", b, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -321,18 +324,26 @@ int render_motion_views(const RdrfRenderMaps* maps, void* ws, size_t ws_bytes, i
 extern "C" size_t rdrf_render_chunks_workspace_bytes(int chunk, int S, int nstreams) {
   return (size_t)(nstreams < 1 ? 1 : nstreams) * ((rdrf_render_workspace_bytes(chunk, S) + 255) & ~(size_t)255);
 }
-// the requested outputs of the rays from r0 on
-static void offset_slots(float* dst[13], float* const src[13], int r0) {
-  for (int i = 0; i < 13; ++i) dst[i] = src[i] ? src[i] + (size_t)r0 * map_width(i) : nullptr;
+// the call for the n rays from r0 on, with the scratch it may use
+static RenderCall rays_of(const RenderCall& c, int r0, int n, void* ws, size_t ws_bytes) {
+  RenderCall p = c;
+  p.rays = c.rays + (size_t)r0 * 6;
+  p.ts = c.ts + r0;
+  p.N = n;
+  for (int i = 0; i < 13; ++i) p.want[i] = c.want[i] ? c.want[i] + (size_t)r0 * map_width(i) : nullptr;
+  p.ws = ws;
+  p.ws_bytes = ws_bytes;
+  return p;
 }
-static int render_chunks(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
-                         const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, int chunk,
-                         float near, float far, float step, float* const want[13], void* ws, size_t ws_bytes,
-                         rdrf_stream_t main_stream_, const rdrf_stream_t* streams, int nstreams) {
+static int render_chunks(const RenderCall& c, int chunk, rdrf_stream_t main_stream_, const rdrf_stream_t* streams,
+                         int nstreams) {
+  const int N = c.N, S = c.S;
+  void* const ws = c.ws;
+  const size_t ws_bytes = c.ws_bytes;
   if (N == 0) return 0;
-  RDRF_CHECK(PS && PD && cfg_s && cfg_d && rays && ts && ws && chunk > 0 && S > 0, -1,
+  RDRF_CHECK(c.PS && c.PD && c.cfg_s && c.cfg_d && c.rays && c.ts && ws && chunk > 0 && S > 0, -1,
              "render_chunks: bad arguments");
-  RDRF_CHECK(PS->packed_fwd != nullptr && PD->packed_fwd != nullptr, -1,
+  RDRF_CHECK(c.PS->packed_fwd != nullptr && c.PD->packed_fwd != nullptr, -1,
              "render_chunks: both packed weight images are required (rdrf_static_pack / rdrf_dynamic_pack)");
   RDRF_CHECK(nstreams >= 0 && nstreams <= 16 && (nstreams == 0 || streams != nullptr), -1, "render_chunks: 0..16 streams");
   hipStream_t main_stream = (hipStream_t)main_stream_;
@@ -352,19 +363,16 @@ static int render_chunks(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, 
     // bit).  A group of g chunks pays the fixed costs of a launch sequence once -- ten launches, two 121-159 KB LDS weight
     // images per CU and MLP kernel -- instead of g times: the frame time of the 512-ray loop was the SUM of its chunks'
     // isolated kernel times (profiles/r05_render_chunk512_kernel_stats.csv), streams or not.
+    // (the 32-bit sample index bound first: behind it (g + 1) * chunk is an int)
     int g = 1;
-    while (g < 256 && (long)g * chunk < N && rdrf_render_workspace_bytes((g + 1) * chunk, S) <= ws_bytes &&
-           (size_t)(g + 1) * chunk * S * 3 < (size_t)INT32_MAX)
+    while (g < 256 && (long)g * chunk < N && (size_t)(g + 1) * chunk * S * 3 < (size_t)INT32_MAX &&
+           rdrf_render_workspace_bytes((int)((long)(g + 1) * chunk), S) <= ws_bytes)
       ++g;
     if (g > 1) {
       const int super = g * chunk;
       for (int c0 = 0; c0 < N; c0 += super) {
-        const int n = N - c0 < super ? N - c0 : super;
-        float* part[13];
-        offset_slots(part, want, c0);
-        const int rc = render_sequence(PS, cfg_s, PD, cfg_d, rays + (size_t)c0 * 6, ts + c0, n, S, near, far, step, part, ws,
-                                       ws_bytes, main_stream_);
-        if (rc) return rc;
+        RenderBufs b;
+        RDRF_TRY(render_sequence(rays_of(c, c0, N - c0 < super ? N - c0 : super, ws, ws_bytes), b, main_stream_));
       }
       return 0;
     }
@@ -384,10 +392,8 @@ static int render_chunks(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, 
     const int n = N - c0 < chunk ? N - c0 : chunk;
     const int si = k % ns;
     rdrf_stream_t st = nstreams >= 1 ? streams[si] : main_stream_;
-    float* part[13];
-    offset_slots(part, want, c0);
-    rc = render_sequence(PS, cfg_s, PD, cfg_d, rays + (size_t)c0 * 6, ts + c0, n, S, near, far, step, part,
-                         (char*)ws + slice * si, slice, st);
+    RenderBufs b;
+    rc = render_sequence(rays_of(c, c0, n, (char*)ws + slice * si, slice), b, st);
   }
   if (nstreams >= 1) {   // join (also on error: the streams must not run past the caller's buffers unobserved)
     for (int q = 0; q < nstreams; ++q) {
@@ -405,20 +411,18 @@ extern "C" int rdrf_render_chunks_fwd(const RdrfStaticParams* PS, const RdrfFiel
                                       float near, float far, float* rgb_map, float* depth_map, void* ws, size_t ws_bytes,
                                       rdrf_stream_t main_stream, const rdrf_stream_t* streams, int nstreams) {
   if (N == 0) return 0;
-  RDRF_CHECK(rgb_map && depth_map, -1, "render_chunks: bad arguments");
-  float* want[13] = {rgb_map, depth_map};
-  return render_chunks(PS, cfg_s, PD, cfg_d, rays, ts, N, S, chunk, near, far, 0.f, want, ws, ws_bytes, main_stream, streams,
-                       nstreams);
+  RenderCall c = {PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, 0.f, {}, ws, ws_bytes};
+  RDRF_TRY(want_rgb_depth(c.want, rgb_map, depth_map, "render_chunks"));
+  return render_chunks(c, chunk, main_stream, streams, nstreams);
 }
 extern "C" int rdrf_render_chunks_maps_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
                                            const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S,
                                            int chunk, float near, float far, const RdrfRenderMaps* maps, void* ws,
                                            size_t ws_bytes, rdrf_stream_t main_stream, const rdrf_stream_t* streams,
                                            int nstreams) {
-  float* want[13];
-  maps_to_slots(want, maps);
-  return render_chunks(PS, cfg_s, PD, cfg_d, rays, ts, N, S, chunk, near, far, 0.f, want, ws, ws_bytes, main_stream, streams,
-                       nstreams);
+  RenderCall c = {PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, 0.f, {}, ws, ws_bytes};
+  maps_to_slots(c.want, maps);
+  return render_chunks(c, chunk, main_stream, streams, nstreams);
 }
 
 // World-space rays (RDRF_RAY_OTHER): the family above behind one entry point that carries the sampler's `step`.
@@ -428,54 +432,9 @@ extern "C" int rdrf_render_world_fwd(const RdrfStaticParams* PS, const RdrfField
                                      size_t ws_bytes, rdrf_stream_t main_stream, const rdrf_stream_t* streams, int nstreams) {
   if (N == 0) return 0;
   RDRF_CHECK(step > 0.0f, -1, "render_world: step must be positive (the field's stepSize)");
-  float* want[13];
-  maps_to_slots(want, maps);
-  if (chunk > 0)
-    return render_chunks(PS, cfg_s, PD, cfg_d, rays, ts, N, S, chunk, near, far, step, want, ws, ws_bytes, main_stream, streams,
-                         nstreams);
-  RDRF_CHECK(mode == RDRF_RENDER_AUTO || mode == RDRF_RENDER_SEQUENCE || mode == RDRF_RENDER_FUSED, -1,
-             "render_world: unknown mode %d", mode);
-  return mode == RDRF_RENDER_FUSED ? render_fused(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, step, want, ws, ws_bytes, main_stream)
-                                   : render_sequence(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, step, want, ws, ws_bytes,
-                                                     main_stream);
-}
-
-// ------------------------------------------------------------------------------------------------
-// self-test: y[M][64] = relu(x[M][64] W^T + b) through pack + LDS + mfma_seg, one tile per wave
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_selftest(const float* __restrict__ x,
-                                                 const float* __restrict__ pkw, int M,
-                                                 float* __restrict__ y) {
-  __shared__ __attribute__((aligned(16))) float lds[2 * 32 * 64 + 64];
-  lds_fill(lds, pkw, 2 * 32 * 64 + 64);
-  const int lane = threadIdx.x & 63, h = lane >> 5, s = lane & 31;
-  const int row = blockIdx.x * 32 + s;
-  float in[32];
-#pragma unroll
-  for (int kk = 0; kk < 32; ++kk) in[kk] = row < M ? x[(size_t)row * 64 + elem_of(kk, h)] : 0.f;
-  f32x16 acc[2];
-  acc_bias<2>(acc, lds + 2 * 32 * 64, h);
-  mfma_seg<2, 32>(acc, in, lds, lane);
-  float out[32];
-  acc_relu<2>(out, acc);
-  if (row < M)
-#pragma unroll
-    for (int kk = 0; kk < 32; ++kk) y[(size_t)row * 64 + elem_of(kk, h)] = out[kk];
-}
-
-extern "C" int rdrf_selftest_mlp(const float* x, const float* w, const float* b, int M, int K,
-                                 int OUT, float* y, void* ws, size_t ws_bytes, rdrf_stream_t stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  if (M == 0) return 0;   // empty batch: a no-op, like torch ops on empty tensors (their data pointers are null)
-  RDRF_CHECK(x && w && b && y && M > 0, -1, "selftest_mlp: bad arguments");
-  RDRF_CHECK(K == 64 && OUT == 64, -1, "selftest_mlp: the self-test layer is 64 -> 64");
-  RDRF_CHECK(ws_bytes >= (2 * 32 * 64 + 64) * sizeof(float), -3, "selftest_mlp: workspace too small");
-  PackJobs J;
-  J.n = 0;
-  pack_add(J, w, 64, 64, 64, SEG_IDENT, 0, 2, 32, 0);
-  pack_add(J, b, 0, 64, 0, 0, 3, 0, 32, 2 * 32 * 64);
-  int rc = pack_launch(J, (float*)ws, stream);
-  if (rc) return rc;
-  RDRF_LAUNCH("selftest", k_selftest, dim3((M + 31) / 32), dim3(64), stream, x, (const float*)ws, M, y);
-  return 0;
+  RenderCall c = {PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, step, {}, ws, ws_bytes};
+  maps_to_slots(c.want, maps);
+  if (chunk > 0) return render_chunks(c, chunk, main_stream, streams, nstreams);
+  RenderBufs b;
+  return render_run(c, mode, "render_world", b, main_stream);
 }

@@ -1,6 +1,11 @@
-// rdrf_render_host.hpp -- the workspace layout of the no-grad render (rdrf_render.hip), shared with the masked render
-// (rdrf_render_masked.hip): both cut their buffers with one carve.  And the host helpers of the forward entry points
-// (rdrf_fwd.hip) that the render units set their field launches up with.
+// rdrf_render_host.hpp -- the host side of the no-grad render, one copy of each step for the four units that run it
+// (rdrf_render.hip, rdrf_render_masked.hip, rdrf_motion.hip, rdrf_track.hip):
+//   RenderCall     what every entry point of the family is called with; each builds it once
+//   RenderBufs     the workspace carve of a render; the runner hands it back, and the kernels that run after a render
+//                  (motion maps, track seeds) read it
+//   render_check_* the argument checks; render_sample, render_fields: the sampler dispatch and the fields' launch set-up
+//   render_run     the render itself, as a launch sequence or as the one cooperative launch
+// (all defined in rdrf_render.hip).  And the host helpers of the forward entry points (rdrf_fwd.hip) that the field set-up uses.
 #pragma once
 #include "rdrf_host.hpp"
 
@@ -12,6 +17,24 @@ void fill_common(FieldArgs& a, const RdrfFieldCfg* cfg, const float* rays, const
 int ws_carve_fwd(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S, void* saved, size_t saved_bytes, int dynamic);
 int fwd_dynq();   // FieldArgs::dynq of the forward launches
 
+struct RenderCall {
+  const RdrfStaticParams* PS;
+  const RdrfFieldCfg* cfg_s;
+  const RdrfDynamicParams* PD;
+  const RdrfFieldCfg* cfg_d;
+  const float *rays, *ts;
+  int N, S;
+  float near, far;
+  float step;        // > 0: the world-space march (RDRF_RAY_OTHER); 0 for ndc / contract
+  float* want[13];   // the caller's output buffers in the compositor's slot order (NULL: the output goes to the workspace)
+  void* ws;          // the caller's scratch
+  size_t ws_bytes;
+};
+// RdrfRenderMaps -> the compositor's 13 output slots (NULL: not requested)
+void maps_to_slots(float* out[13], const RdrfRenderMaps* m);
+// the legacy entry points: rgb and depth only, which carves the workspace exactly as before the maps existed
+int want_rgb_depth(float* want[13], float* rgb_map, float* depth_map, const char* who);
+
 struct RenderBufs {
   float *xyz, *z, *rgb_s, *sigma_s, *weight_s, *dists_s, *rgb_d, *sigma_d, *weight_d, *dists_d, *blending, *xyz_prime;
   uint8_t* valid;
@@ -19,12 +42,25 @@ struct RenderBufs {
   void *fws_s, *fws_d;
   unsigned* barrier;
 };
-// RdrfRenderMaps -> the compositor's 13 output slots (NULL: not requested)
-void maps_to_slots(float* out[13], const RdrfRenderMaps* m);
-// want[13]: the caller's output buffers (NULL: the output goes to the workspace)
 int carve_render(RenderBufs& b, void* ws, size_t ws_bytes, int N, int S, float* const want[13]);
-// where a render with these `maps` left what the kernels that run after it read (rdrf_motion.hip, rdrf_track.hip): the
-// carve of the render itself
-int render_motion_views(const RdrfRenderMaps* maps, void* ws, size_t ws_bytes, int N, int S, const float** xyz,
-                        const float** xyz_prime, const float** weights_s, const float** weights_d, const unsigned** barrier,
-                        void** fws_d);
+
+// The checks of the shared prefix in two halves, `who` the message prefix ("render", "render_masked").  A unit puts its own
+// checks between them, where a caller has always met them: the render its workspace size, the masked render its masks.
+//   render_check_args  : no null pointer, N, S > 0; `step` > 0 exactly for the world-space march (`step_rule`: the unit's
+//                        wording of that rule); N * S * 3 < 2^31
+//   render_check_fields: the component counts and the one grid the kernels are built for
+int render_check_args(const RenderCall& c, const char* who, const char* step_rule);
+int render_check_fields(const RenderCall& c, const char* who);
+
+// xyz, z, valid of every sample by the sampler of cfg_d->ray_type
+int render_sample(const RenderCall& c, const RenderBufs& b, rdrf_stream_t stream);
+// Both fields' launch arguments over the carve (`valid_s`, `valid_d`: the plane each field reads), their forward workspaces,
+// weight pointers and packed images (packed on `stream` where the caller brought none)
+struct StaticW;
+struct DynW;
+int render_fields(const RenderCall& c, const RenderBufs& b, const uint8_t* valid_s, const uint8_t* valid_d, FieldArgs& as,
+                  FieldArgs& ad, StaticW& wst, DynW& wdy, hipStream_t stream);
+
+// The render: checks, carve (handed back in `b`), launches.  mode: RDRF_RENDER_FUSED is the cooperative launch, the two
+// others the launch sequence; an unknown one is refused under the prefix `who`.
+int render_run(const RenderCall& c, int mode, const char* who, RenderBufs& b, rdrf_stream_t stream);

@@ -237,54 +237,33 @@ extern "C" int rdrf_render_masked_fwd(const RdrfStaticParams* PS, const RdrfFiel
                                       rdrf_stream_t stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (N == 0) return 0;   // empty batch: a no-op, like torch ops on empty tensors (their data pointers are null)
-  RDRF_CHECK(PS && PD && cfg_s && cfg_d && rays && ts && ws && N > 0 && S > 0, -1, "render_masked: bad arguments");
-  RDRF_CHECK((cfg_d->ray_type == RDRF_RAY_NDC || cfg_d->ray_type == RDRF_RAY_CONTRACT) == !(step > 0.0f), -1,
-             "render_masked: step > 0 exactly for the world-space march (ray_type %d, step %g)", cfg_d->ray_type, (double)step);
-  RDRF_CHECK((size_t)N * S * 3 < (size_t)INT32_MAX, -1, "render_masked: N * S * 3 must stay below 2^31: render in chunks");
+  RenderCall call = {PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, step, {}, ws, ws_bytes};
+  maps_to_slots(call.want, maps);
+  RDRF_CHECK(ws != nullptr, -1, "render_masked: bad arguments");
+  RDRF_TRY(render_check_args(call, "render_masked", "step > 0 exactly for the world-space march"));
   const bool has_s = mask_s != nullptr && mask_s->bits != nullptr, has_d = mask_d != nullptr && mask_d->bits != nullptr;
   RDRF_CHECK(has_s || has_d, -1, "render_masked: at least one of the two masks must be given");
   RDRF_CHECK(mask_ok(mask_s) && mask_ok(mask_d), -1, "render_masked: the masks' grids and slice counts must be positive");
-  RDRF_CHECK(vm_ok(PS->density, 16, 4) && vm_ok(PS->app, 48, 12) && vm_ok(PD->density, 16, 4) && vm_ok(PD->blending, 16, 4) &&
-             vm_ok(PD->app, 48, 12) && vm_same_grid(PD->density, PD->blending), -1,
-             "render_masked: only density comps {16,4,4} / app comps {48,12,12} of one grid are built");
+  RDRF_TRY(render_check_fields(call, "render_masked"));
   MaskedBufs m;
   WsCarver c(ws, ws_bytes);
   carve_masked(m, c, N, S);
   RDRF_CHECK(c.ok(), -3, "render_masked: workspace too small: need %zu have %zu", c.off, ws_bytes);
-  float* want[13];
-  maps_to_slots(want, maps);
   RenderBufs b;
-  RDRF_TRY(carve_render(b, m.render, m.render_bytes, N, S, want));
-  const size_t fwb = rdrf_forward_workspace_bytes(N, S);
+  RDRF_TRY(carve_render(b, m.render, m.render_bytes, N, S, call.want));
   const int ns = N * S;
 
+  // each field reads its own mask's valid plane and counts its appearance list in this call's counter block
   FieldArgs as, ad;
-  fill_common(as, cfg_s, rays, ts, b.xyz, b.z, m.valid_s, N, S);
-  as.rgb = b.rgb_s; as.sigma = b.sigma_s; as.weight = b.weight_s; as.dists = b.dists_s;
-  RDRF_TRY(ws_carve_fwd(as, b.fws_s, fwb, N, S, nullptr, 0, 0));
-  as.counter = m.ctr + CTR_APP_S;
-  as.dynq = fwd_dynq();
-  fill_common(ad, cfg_d, rays, ts, b.xyz, b.z, m.valid_d, N, S);
-  ad.rgb = b.rgb_d; ad.sigma = b.sigma_d; ad.weight = b.weight_d; ad.dists = b.dists_d;
-  ad.blending = b.blending; ad.xyz_prime = b.xyz_prime;
-  RDRF_TRY(ws_carve_fwd(ad, b.fws_d, fwb, N, S, nullptr, 0, 1));
-  ad.counter = m.ctr + CTR_APP_D;
-  ad.dynq = fwd_dynq();
   StaticW wst;
   DynW wdy;
-  fill_static_w(wst, PS);
-  fill_dyn_w(wdy, PD);
-  RDRF_TRY(pack_image(as.pk, PS->packed_fwd, (float*)as.pk, stream, static_pack_jobs_fwd, PS, cfg_s->static_head));
-  RDRF_TRY(pack_image(ad.pk, PD->packed_fwd, (float*)ad.pk, stream, dyn_pack_jobs_fwd, PD));
+  RDRF_TRY(render_fields(call, b, m.valid_s, m.valid_d, as, ad, wst, wdy, stream));
+  as.counter = m.ctr + CTR_APP_S;
+  as.dynq = fwd_dynq();
+  ad.counter = m.ctr + CTR_APP_D;
+  ad.dynq = fwd_dynq();
 
-  int rc;
-  if (cfg_d->ray_type == RDRF_RAY_NDC)
-    rc = rdrf_sample_ndc(rays, N, S, near, far, nullptr, cfg_d->aabb, b.xyz, b.z, b.valid, stream);
-  else if (cfg_d->ray_type == RDRF_RAY_CONTRACT)
-    rc = rdrf_sample_contract(rays, N, S, near, far, nullptr, nullptr, b.xyz, b.z, b.valid, stream);
-  else
-    rc = rdrf_sample_world(rays, N, S, near, far, step, nullptr, cfg_d->aabb, b.xyz, b.z, b.valid, stream);
-  if (rc) return rc;
+  RDRF_TRY(render_sample(call, b, stream));
   // the time branch of every ray (a masked-out ray costs 17 -> 64 -> 30 once); clears the four counters on its way
   RDRF_LAUNCH("time_branch", k_masked_time_branch, dim3((N + 7) / 8), dim3(256), stream, ts, wdy, N, ad.tout, m.ctr);
 

@@ -1,9 +1,9 @@
 // rdrf_selftest.hip -- every MLP layer primitive of rdrf_common.hpp, stand-alone, with the template arguments the product
 // kernels use and the product's own pack code (tests/test_gpu_mlp_primitives.py compares the results with float64).
 //
-// One wave per 32-row tile, as k_selftest (rdrf_render.hip): the wave's workgroup copies the packed image into LDS, lane
-// (h, s) loads its half of row s in the canonical layout, the primitive runs on ZERO accumulators and the raw accumulators
-// are stored: no bias, no relu, so the result is linear in x and w.  Rows past M read as zero and are not stored.
+// One wave per 32-row tile, as k_selftest (end of the file: a layer with bias and relu): the wave's workgroup copies the packed
+// image into LDS, lane (h, s) loads its half of row s in the canonical layout, the primitive runs on ZERO accumulators and
+// the raw accumulators are stored: no bias, no relu, so the result is linear in x and w.  Rows past M read as zero and are not stored.
 //   forward forms     x[M][K]   , w[OUT][K]  ->  y[M][OUT] = x w^T
 //   transposed forms  x[M][OUT] , w[OUT][K]  ->  y[M][K]   = x w      (the backward-data product of the same layer)
 //
@@ -703,4 +703,45 @@ extern "C" int rdrf_selftest_scatter_last(int* out, int cap) {
     out[n++] = r.l[i].tw; out[n++] = r.l[i].slice_steps;
   }
   return n;
+}
+
+// ------------------------------------------------------------------------------------------------
+// rdrf_selftest_mlp: y[M][64] = relu(x[M][64] W^T + b) through pack + LDS + mfma_seg, one tile per wave -- a whole fp32
+// layer with its bias and relu (tests/test_gpu_forward.py)
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_selftest(const float* __restrict__ x,
+                                                 const float* __restrict__ pkw, int M,
+                                                 float* __restrict__ y) {
+  __shared__ __attribute__((aligned(16))) float lds[2 * 32 * 64 + 64];
+  lds_fill(lds, pkw, 2 * 32 * 64 + 64);
+  const int lane = threadIdx.x & 63, h = lane >> 5, s = lane & 31;
+  const int row = blockIdx.x * 32 + s;
+  float in[32];
+#pragma unroll
+  for (int kk = 0; kk < 32; ++kk) in[kk] = row < M ? x[(size_t)row * 64 + elem_of(kk, h)] : 0.f;
+  f32x16 acc[2];
+  acc_bias<2>(acc, lds + 2 * 32 * 64, h);
+  mfma_seg<2, 32>(acc, in, lds, lane);
+  float out[32];
+  acc_relu<2>(out, acc);
+  if (row < M)
+#pragma unroll
+    for (int kk = 0; kk < 32; ++kk) y[(size_t)row * 64 + elem_of(kk, h)] = out[kk];
+}
+
+extern "C" int rdrf_selftest_mlp(const float* x, const float* w, const float* b, int M, int K,
+                                 int OUT, float* y, void* ws, size_t ws_bytes, rdrf_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (M == 0) return 0;   // empty batch: a no-op, like torch ops on empty tensors (their data pointers are null)
+  RDRF_CHECK(x && w && b && y && M > 0, -1, "selftest_mlp: bad arguments");
+  RDRF_CHECK(K == 64 && OUT == 64, -1, "selftest_mlp: the self-test layer is 64 -> 64");
+  RDRF_CHECK(ws_bytes >= (2 * 32 * 64 + 64) * sizeof(float), -3, "selftest_mlp: workspace too small");
+  PackJobs J;
+  J.n = 0;
+  pack_add(J, w, 64, 64, 64, SEG_IDENT, 0, 2, 32, 0);
+  pack_add(J, b, 0, 64, 0, 0, 3, 0, 32, 2 * 32 * 64);
+  int rc = pack_launch(J, (float*)ws, stream);
+  if (rc) return rc;
+  RDRF_LAUNCH("selftest", k_selftest, dim3((M + 31) / 32), dim3(64), stream, x, (const float*)ws, M, y);
+  return 0;
 }

@@ -187,14 +187,11 @@ extern "C" int rdrf_render_track_seeds_fwd(const RdrfStaticParams* PS, const Rdr
   RDRF_CHECK(cfg_d && (cfg_d->ray_type == RDRF_RAY_NDC || cfg_d->ray_type == RDRF_RAY_CONTRACT), -1,
              "render_track_seeds: ray_type must be ndc or contract (renderer.py:1335-1351)");
   // the render itself: the launch sequence, same bits in every requested map (the workspace carve does not depend on `seeds`)
-  int rc = rdrf_render_maps_fwd(PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, RDRF_RENDER_AUTO, maps, ws, ws_bytes, stream_);
-  if (rc) return rc;
-  const float *xyz, *xyz_prime, *w_s, *w_d;
-  const unsigned* barrier;
-  void* fws_d = nullptr;
-  rc = render_motion_views(maps, ws, ws_bytes, N, S, &xyz, &xyz_prime, &w_s, &w_d, &barrier, &fws_d);
-  if (rc) return rc;
-  RDRF_LAUNCH("track_seeds", k_track_seeds, dim3((N + kSeedWaves - 1) / kSeedWaves), dim3(64 * kSeedWaves), stream, w_d, xyz, rays,
-              N, S, cfg_d->ray_type, seeds);
+  RenderCall c = {PS, cfg_s, PD, cfg_d, rays, ts, N, S, near, far, 0.f, {}, ws, ws_bytes};
+  maps_to_slots(c.want, maps);
+  RenderBufs b;
+  RDRF_TRY(render_run(c, RDRF_RENDER_AUTO, "render_maps", b, stream_));
+  RDRF_LAUNCH("track_seeds", k_track_seeds, dim3((N + kSeedWaves - 1) / kSeedWaves), dim3(64 * kSeedWaves), stream,
+              (const float*)b.out[11], (const float*)b.xyz, rays, N, S, cfg_d->ray_type, seeds);
   return 0;
 }

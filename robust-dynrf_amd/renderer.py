@@ -290,6 +290,11 @@ def _mask_pair(tensorf_static, tensorf, alpha_masks):
     return pair
 
 
+def _n_samples(tensorf, N_samples):
+    """samples per ray of a render: the caller's count, or the dynamic field's"""
+    return int(N_samples) if N_samples and N_samples > 0 else tensorf.nSamples
+
+
 @torch.no_grad()
 def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc", mode="auto", maps=False, motion=None,
                 alpha_masks=None, kept=None):
@@ -321,16 +326,16 @@ def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc",
     L.require_device(rays, ts)
     rays, ts = L.f32c(rays), L.f32c(ts)
     N = rays.shape[0]
-    S = int(N_samples) if N_samples and N_samples > 0 else tensorf.nSamples
+    S = _n_samples(tensorf, N_samples)
     dev = rays.device
     ws = L.workspace(dev, (L.lib.rdrf_render_motion_workspace_bytes if motion is not None else L.lib.rdrf_render_workspace_bytes)(N, S))
     PS, cs, PD, cd = render_structs(tensorf_static, tensorf, ray_type)
     head = (C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S)
     near, far = tensorf.near_far
+    bufs, M = _map_outputs(maps, N, dev)
     if masks is not None:
         if kept is not None and (kept.dtype != torch.int64 or kept.numel() != 2 or not kept.is_cuda or not kept.is_contiguous()):
             raise L.RdrfError("render_rays: `kept` is a contiguous int64 device tensor of two elements")
-        bufs, M = _map_outputs(maps, N, dev)
         ms, md = (None if m is None else m._struct() for m in masks)
         ws = L.workspace(dev, L.lib.rdrf_render_masked_ws_bytes(N, S))
         step = 0.0 if ray_type in L.RAY_TYPES else tensorf._step_host
@@ -342,18 +347,15 @@ def render_rays(tensorf_static, tensorf, rays, ts, N_samples=-1, ray_type="ndc",
         if ray_type not in L.RAY_TYPES:
             raise NotImplementedError("motion maps: ray_type must be 'ndc' or 'contract' (the reference projects no other, "
                                       "renderer.py:1335-1351)")
-        bufs, M = _map_outputs(maps, N, dev)
         mbufs, MM, cams, keep = _motion_request(motion, N, dev)
         L.check(L.lib.rdrf_render_motion_fwd(*head, near, far, L.RENDER_MODES[mode], C.byref(M), C.byref(cams), C.byref(MM),
                                              L.ptr(ws), ws.numel(), L.stream_of(rays)), "rdrf_render_motion_fwd")
         del keep
         return _map_result(bufs, maps), MotionMaps(**{n: mbufs.get(n) for n in L.MOTION_MAPS})
     if ray_type not in L.RAY_TYPES:   # world-space rays: one entry point for the family, it carries the sampler's step
-        bufs, M = _map_outputs(maps, N, dev)
         L.check(L.lib.rdrf_render_world_fwd(*head, 0, near, far, tensorf._step_host, L.RENDER_MODES[mode], C.byref(M), L.ptr(ws),
                                             ws.numel(), L.stream_of(rays), None, 0), "rdrf_render_world_fwd")
         return _map_result(bufs, maps)
-    bufs, M = _map_outputs(maps, N, dev)
     if maps:
         L.check(L.lib.rdrf_render_maps_fwd(*head, near, far, L.RENDER_MODES[mode], C.byref(M), L.ptr(ws), ws.numel(),
                                            L.stream_of(rays)), "rdrf_render_maps_fwd")
@@ -382,7 +384,7 @@ def render_chunks(tensorf_static, tensorf, rays, ts, chunk, N_samples=-1, ray_ty
     L.require_device(rays, ts)
     rays, ts = L.f32c(rays), L.f32c(ts)
     N, dev = rays.shape[0], rays.device
-    S = int(N_samples) if N_samples and N_samples > 0 else tensorf.nSamples
+    S = _n_samples(tensorf, N_samples)
     chunk = int(chunk)
     bufs, M = _map_outputs(maps, N, dev)
     if N == 0:
@@ -417,7 +419,7 @@ def _render_image(tensorf_static, tensorf, rays, ts, H, W, N_samples, ray_type, 
     `motion`: the dict of render_rays without first_pixel (every chunk passes its own) -> (images, MotionMaps of images);
     `alpha_masks`: as render_rays"""
     dev = rays.device
-    S_ = int(N_samples) if N_samples and N_samples > 0 else tensorf.nSamples
+    S_ = _n_samples(tensorf, N_samples)
     if not chunk:   # whole frame in one launch sequence, bounded by the kernels' 32-bit sample indices
         chunk = max(1, min(H * W, (2 ** 31 - 1) // (3 * S_) - 1))
     chunk = int(chunk)
@@ -636,7 +638,7 @@ def render_tracks(tensorf_static, tensorf, poses9, focal, frame, pixels, H, W, s
     ids = pixels[:, 1] * W + pixels[:, 0] + frame * H * W
     rays = L.f32c(generate_rays(ids, poses9, focal, H, W, ndc=ray_type == "ndc", near=1.0))
     ts = torch.full((M,), 2.0 * frame / max(T - 1, 1) - 1.0, device=dev)
-    S = int(N_samples) if N_samples and N_samples > 0 else tensorf.nSamples
+    S = _n_samples(tensorf, N_samples)
     seeds = torch.empty(M, 3, device=dev)
     bufs = _alloc_maps(("acc_d",), M, dev)
     if M:

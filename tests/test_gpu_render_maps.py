@@ -95,6 +95,64 @@ def test_render_maps_agree_with_every_render_path(case, N, S):
     _maps_equal(seq, part, sub)
 
 
+def test_every_entry_point_of_the_family_gives_the_bits_of_the_maps_sequence():
+    """70 rays (no multiple of 4, 16, 32 or 64) x 37 samples (no multiple of 32) through every no-grad render entry point:
+    rgb and depth equal those of rdrf_render_maps_fwd in sequence mode bit for bit.  Chunks of 32 (a partial last chunk) on no
+    side stream and on two (the workspace of two streams lets chunks coalesce); the masked render with all-ones masks; of the
+    motion and track-seed calls, their render maps.  rdrf_render_world_fwd takes world-space rays only and the sequence of
+    rdrf_render_maps_fwd refuses them, so the world fields are held to that entry point's own sequence mode, and so is the
+    masked render on world rays."""
+    import importlib
+    import rodynrf
+    import test_gpu_masked_render as MR
+    import ctypes as C
+    R = importlib.import_module("robust-dynrf_amd.renderer")
+    L = importlib.import_module("robust-dynrf_amd._lib")
+    N, S = 70, 37
+
+    def family(case, world):
+        st, dy, rt = MR.fields(case)
+        rays, ts = MR.make_rays(case, N)
+        ref = rodynrf.render_rays(st, dy, rays, ts, S, ray_type=rt, mode="sequence", maps=True)
+        assert torch.isfinite(ref.rgb).all() and float(ref.acc.max()) > 0.1, case
+
+        def same(got, what):
+            rgb, depth = (got.rgb, got.depth) if isinstance(got, rodynrf.RenderMaps) else got
+            torch.cuda.synchronize()
+            assert torch.equal(rgb, ref.rgb) and torch.equal(depth, ref.depth), f"{case}: {what}"
+
+        for mode in ("auto", "sequence", "fused"):   # rdrf_render_fwd / _sequence_fwd / _fused_fwd; world: rdrf_render_world_fwd
+            same(rodynrf.render_rays(st, dy, rays, ts, S, ray_type=rt, mode=mode), mode)
+            same(rodynrf.render_rays(st, dy, rays, ts, S, ray_type=rt, mode=mode, maps=True), mode + " maps")
+        for streams in (0, 2):   # rdrf_render_chunks_fwd / _chunks_maps_fwd
+            same(rodynrf.render_chunks(st, dy, rays, ts, 32, S, ray_type=rt, streams=streams), f"chunks, {streams} streams")
+            same(rodynrf.render_chunks(st, dy, rays, ts, 32, S, ray_type=rt, streams=streams, maps=True), f"chunk maps, {streams} streams")
+        lo, hi = dy.aabb.detach().cpu()
+        big = torch.stack([lo - 0.05 * (hi - lo), hi + 0.05 * (hi - lo)])
+        ones = (MR.make_mask("ones", st, box=big), MR.make_mask("ones", dy, box=big))
+        same(rodynrf.render_rays(st, dy, rays, ts, S, ray_type=rt, maps=True, alpha_masks=ones), "masked")   # rdrf_render_masked_fwd
+        if world:
+            return
+        eye = torch.eye(4)[:3]
+        for mode in ("sequence", "fused"):   # rdrf_render_motion_fwd
+            m, _ = rodynrf.render_rays(st, dy, rays, ts, S, ray_type=rt, mode=mode, maps=True,
+                                       motion=dict(H=7, W=10, focal=10.0, c2w_f=eye, c2w_b=eye))
+            same(m, "motion " + mode)
+        bufs, seeds = R._alloc_maps(("rgb", "depth"), N, rays.device), torch.empty(N, 3, device=rays.device)   # rdrf_render_track_seeds_fwd
+        ws = L.workspace(rays.device, L.lib.rdrf_render_motion_workspace_bytes(N, S))
+        PS, cs, PD, cd = R.render_structs(st, dy, rt)
+        near, far = dy.near_far
+        Mp = R._maps_struct(bufs)
+        L.check(L.lib.rdrf_render_track_seeds_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S, near,
+                                                  far, C.byref(Mp), L.ptr(seeds), L.ptr(ws), ws.numel(), L.stream_of(rays)),
+                "rdrf_render_track_seeds_fwd")
+        same((bufs["rgb"], bufs["depth"]), "track seeds")
+        assert torch.isfinite(seeds).all()
+
+    family("ndc_relu", False)
+    family("world", True)
+
+
 def _camera_rays_f64(c2w, focal, H, W, ndc, near=1.0):
     """dataLoader/ray_utils.py: get_ray_directions_blender -> get_rays -> ndc_rays_blender, float64, per camera"""
     out = []
