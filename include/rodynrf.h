@@ -875,6 +875,23 @@ int rdrf_render_masked_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s
                            float step, const RdrfAlphaMask* mask_s, const RdrfAlphaMask* mask_d, const RdrfRenderMaps* maps,
                            int64_t* kept, void* ws, size_t ws_bytes, rdrf_stream_t stream);
 
+/* ---- point queries: a field evaluated at M points off the rays -------------------------------------------------------------
+ * Point i gets what the field's forward gives a sample at xyz[i] with valid = 1 whose ray has the time ts[i] (ts[0] with
+ * t_per_point = 0) and the normalised view direction viewdirs[i], bit for bit: sigma after the density activation, rgb,
+ * and for the dynamic field blending (after the sigmoid) and xyz_prime (un-normalised).  rgb is computed for every point: there
+ * is no weight threshold off the rays, no alpha-mask lookup and no aabb test -- the caller filters.  viewdirs are used as given,
+ * not normalised.  params: RdrfStaticParams (dynamic = 0; ts may be NULL) or RdrfDynamicParams (dynamic = 1).  Every output is
+ * nullable; rgb == NULL skips the appearance phase (viewdirs may then be NULL); blending and xyz_prime belong to the dynamic
+ * field.  M == 0 is a no-op; M above RDRF_QUERY_POINTS_MAX is refused (the kernels index points with 32-bit ints): query in
+ * chunks.  No allocation, no synchronisation, no read-back: the call can be captured into a graph.  The size function is the
+ * end offset of the entry point's own carve; it does not carry the *_workspace_bytes suffix for the reason given at
+ * rdrf_render_masked_ws_bytes. */
+#define RDRF_QUERY_POINTS_MAX (1 << 24)
+size_t rdrf_query_points_ws_bytes(int dynamic, int M, int t_per_point);
+int rdrf_query_points(const void* params, int dynamic, const RdrfFieldCfg* cfg, const float* xyz, int M, const float* ts,
+                      int t_per_point, const float* viewdirs, float* sigma, float* rgb, float* blending, float* xyz_prime,
+                      void* ws, size_t ws_bytes, rdrf_stream_t stream);
+
 /* timing hook: average device time (ms) of the dominant kernel launches recorded with HIP events
  * since the last reset; used by bench.py for the roofline figure. */
 void rdrf_prof_reset(void);

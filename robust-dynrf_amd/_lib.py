@@ -19,6 +19,7 @@ RAY_TYPES = {"ndc": 0, "contract": 1}   # any other name ("world") is RDRF_RAY_O
 ACTS = {"relu": 0, "softplus": 1}
 HEADS = {"MLP_Fea": 0, "MLP_Fea_TimeEmbedding": 1}
 SAVE_NO_APP = 1   # include/rodynrf.h RDRF_SAVE_NO_APP (flags of rdrf_saved_bytes_ex / rdrf_*_fwd_ex)
+QUERY_POINTS_MAX = 1 << 24   # include/rodynrf.h RDRF_QUERY_POINTS_MAX: the largest batch of one rdrf_query_points call
 
 fp = C.POINTER(C.c_float)
 
@@ -238,6 +239,8 @@ SIGNATURES = {
     "rdrf_render_masked_ws_bytes": (usz, [i32, i32]),
     "rdrf_render_masked_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, C.POINTER(RdrfAlphaMask),
                                     C.POINTER(RdrfAlphaMask), C.POINTER(RenderMapsC), vp, vp, usz, vp]),
+    "rdrf_query_points_ws_bytes": (usz, [i32, i32, i32]),
+    "rdrf_query_points": (i32, [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, usz, vp]),
     "rdrf_prof_reset": (None, []),
     "rdrf_prof_enable": (i32, [i32]),
     "rdrf_prof_get": (i32, [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),

@@ -503,6 +503,77 @@ class TensorBase(nn.Module):
         from .mesh import export_mesh
         return export_mesh(self, ply_path, t, level, **kw)
 
+    # ---- point queries (csrc/rdrf_point.hip) ---------------------------------------------------------------------------
+    @torch.no_grad()
+    def query_points(self, xyz, t=None, viewdirs=None, want=("sigma", "rgb"), _chunk=None):
+        """The field at points off the rays: what forward() gives a sample with ray_valid = 1 at `xyz`, bit for bit, as a
+        dict of tensors shaped like xyz.shape[:-1] (+ (3,) for "rgb" and "xyz_prime").
+
+        xyz      [..., 3] un-normalised points on the device
+        t        a float, or a tensor shaped xyz.shape[:-1] (a time per point).  Required for the dynamic field; the static
+                 field does not read it
+        viewdirs [..., 3] like xyz, or one 3-vector for all points; used AS GIVEN (forward() hands in normalised ray
+                 directions).  Required exactly when "rgb" is wanted
+        want     names out of "sigma" (after the density activation), "rgb" and, for the dynamic field, "blending" (after the
+                 sigmoid) and "xyz_prime".  Without "rgb" no appearance kernel is launched
+
+        Every point gets a colour: there is no weight threshold, no alpha-mask lookup and no aabb test here -- filter the
+        points first where that matters.  Runs under no_grad semantics: nothing is differentiable, and inputs that require
+        a gradient are detached.  Batches above the native limit (_lib.QUERY_POINTS_MAX) are queried in chunks."""
+        names = ("sigma", "rgb", "blending", "xyz_prime") if self.DYNAMIC else ("sigma", "rgb")
+        want = (want,) if isinstance(want, str) else tuple(want)
+        bad = [w for w in want if w not in names]
+        if bad:
+            raise L.RdrfError(f"query_points: {bad} not among the outputs of this field, {names}")
+        if not torch.is_tensor(xyz) or xyz.dim() < 1 or xyz.shape[-1] != 3:
+            raise L.RdrfError("query_points: xyz must be a tensor [..., 3]")
+        L.require_device(xyz)
+        lead, dev = tuple(xyz.shape[:-1]), xyz.device
+        pts = L.f32c(xyz.detach()).reshape(-1, 3)
+        M = pts.shape[0]
+        tt, per_point = None, 0
+        if torch.is_tensor(t) and t.dim() > 0:
+            if tuple(t.shape) != lead:
+                raise L.RdrfError(f"query_points: t must be a float or shaped {lead}, not {tuple(t.shape)}")
+            L.require_device(t)
+            tt, per_point = L.f32c(t.detach()).reshape(-1), 1
+        elif t is not None:
+            tt = torch.full((1,), float(t), dtype=torch.float32, device=dev)
+        if self.DYNAMIC and tt is None:
+            raise L.RdrfError("query_points: the dynamic field depends on the time: pass t")
+        if not self.DYNAMIC:
+            tt, per_point = None, 0
+        vd = None
+        if "rgb" in want:
+            if viewdirs is None:
+                raise L.RdrfError("query_points: \"rgb\" depends on the view direction: pass viewdirs")
+            v = torch.as_tensor(viewdirs, dtype=torch.float32)
+            if not torch.is_tensor(viewdirs):   # a tuple or a list: host numbers, not a CPU tensor handed in by mistake
+                v = v.to(dev)
+            if tuple(v.shape) == (3,) and lead != ():
+                v = v.expand(M, 3)
+            elif tuple(v.shape) != lead + (3,):
+                raise L.RdrfError(f"query_points: viewdirs must be one 3-vector or shaped {lead + (3,)}, not {tuple(v.shape)}")
+            L.require_device(v)
+            vd = L.f32c(v.detach()).reshape(-1, 3)
+        out = {w: torch.empty((M, 3) if w in ("rgb", "xyz_prime") else (M,), device=dev) for w in want}
+        chunk = int(_chunk) if _chunk else L.QUERY_POINTS_MAX
+        if not 0 < chunk <= L.QUERY_POINTS_MAX:
+            raise L.RdrfError(f"query_points: chunk {chunk} outside (0, {L.QUERY_POINTS_MAX}]")
+        if M > 0:
+            P, cfg = field_structs(self, self._param_list(), "ndc")
+            dyn = int(self.DYNAMIC)
+            ws = L.workspace(dev, L.lib.rdrf_query_points_ws_bytes(dyn, min(M, chunk), per_point))
+            part = lambda x, a, b: L.ptr(None if x is None else x[a:b])
+            for a in range(0, M, chunk):
+                b = min(M, a + chunk)
+                L.check(L.lib.rdrf_query_points(C.byref(P), dyn, C.byref(cfg), L.ptr(pts[a:b]), b - a,
+                                                part(tt, a, b) if per_point else L.ptr(tt), per_point, part(vd, a, b),
+                                                part(out.get("sigma"), a, b), part(out.get("rgb"), a, b),
+                                                part(out.get("blending"), a, b), part(out.get("xyz_prime"), a, b), L.ptr(ws),
+                                                ws.numel(), L.stream_of(pts)), "rdrf_query_points")
+        return {w: o.view(lead + tuple(o.shape[1:])) for w, o in out.items()}
+
     def shrink(self, new_aabb, voxel_size=None):
         raise NotImplementedError("shrink reallocates the VM factors under the flat optimiser buffers and is not built: "
                                   "the new_aabb of updateAlphaMask is informational")
@@ -656,6 +727,11 @@ class TensorBase(nn.Module):
         for n, p in self.named_parameters():
             if ("_plane." in n or "_line." in n) and not _is_channel_last(p):
                 raise L.RdrfError(f"{n} lost its channel-last layout")
+
+
+def query_points(field, xyz, t=None, viewdirs=None, want=("sigma", "rgb")):
+    """field.query_points(xyz, t, viewdirs, want): see TensorBase.query_points"""
+    return field.query_points(xyz, t, viewdirs, want)
 
 
 class TensorVMSplit(TensorBase):

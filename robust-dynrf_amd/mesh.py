@@ -113,8 +113,8 @@ def _mesh_of_slice(field, alpha, k, level, space, H, W, focal, kw):
 
 def _check_kw(kw):
     if "colors" in kw:
-        raise L.RdrfError("vertex colours are not built: the appearance head has no per-point entry on the call surface "
-                          "(write_ply takes colours a caller computed)")
+        raise L.RdrfError("field_mesh / mesh_sequence take no colors=: colours come from colored_mesh, vertex_colors and "
+                          "export_mesh(..., color_view=) (write_ply takes colours a caller computed)")
     bad = set(kw) - {"normals", "flip", "cap"}
     if bad:
         raise TypeError(f"unexpected arguments {sorted(bad)}")
@@ -151,6 +151,33 @@ def mesh_sequence(field, times, level=0.005, gridSize=None, space="field", H=Non
             yield _mesh_of_slice(field, alpha, k, level, space, H, W, focal, kw)
 
     return meshes()
+
+
+# ---- vertex colours: the appearance head at the vertices (fields.TensorBase.query_points, csrc/rdrf_point.hip) --------------
+@torch.no_grad()
+def vertex_colors(field, verts, t=None, view=(0, 0, 1)):
+    """[nv,3] uint8 colours of FIELD-SPACE vertices (what field_mesh(space="field") returns): the field's rgb at each vertex
+    at time t, seen along the one direction `view` (used as given), quantised as round(clamp(rgb, 0, 1) * 255)."""
+    if t is None and field.DYNAMIC:
+        raise L.RdrfError("vertex_colors: the dynamic field's colours depend on the time: pass t")
+    rgb = field.query_points(verts, None if t is None else float(t), tuple(float(v) for v in view), want=("rgb",))["rgb"]
+    return torch.round(rgb.clamp(0.0, 1.0) * 255.0).to(torch.uint8)
+
+
+@torch.no_grad()
+def colored_mesh(field, t=None, level=0.005, gridSize=None, view=(0, 0, 1), space="field", H=None, W=None, focal=None,
+                 normals=False, flip=False, cap=False):
+    """field_mesh with colours: (verts, faces[, normals], colors [nv,3] uint8).  The colours are those of the field-space
+    vertices (vertex_colors), taken before any NDC2world mapping, so space="world" moves the vertices and keeps the colours."""
+    if space not in ("field", "world"):
+        raise L.RdrfError(f"space must be \"field\" or \"world\", not {space!r}")
+    out = field_mesh(field, t, level, gridSize, "field", normals=normals, flip=flip, cap=cap)
+    verts, faces = out[0], out[1]
+    colors = vertex_colors(field, verts, t, view)
+    world, wn = _to_world(field, verts, faces, space, H, W, focal)
+    if not normals:
+        return world, faces, colors
+    return world, faces, (out[2] if wn is None else wn), colors
 
 
 # ---- PLY (binary little-endian), numpy only ----------------------------------------------------------------------------
@@ -242,10 +269,16 @@ def load_field(path, device="cuda"):
 
 @torch.no_grad()
 def export_mesh(field_or_ckpt_path, ply_path, t=None, level=0.005, gridSize=None, space="field", H=None, W=None, focal=None,
-                device="cuda", **kw):
-    """train.py:107-118: the field (or the checkpoint at a path) -> dense alpha -> isosurface -> PLY.  Returns the mesh."""
+                device="cuda", color_view=None, **kw):
+    """train.py:107-118: the field (or the checkpoint at a path) -> dense alpha -> isosurface -> PLY.  Returns the mesh.
+    color_view: a view direction; the PLY then carries the vertex colours of colored_mesh, which come last in the mesh."""
     field = load_field(field_or_ckpt_path, device) if isinstance(field_or_ckpt_path, (str, bytes)) or hasattr(
         field_or_ckpt_path, "__fspath__") else field_or_ckpt_path
-    out = field_mesh(field, t, level, gridSize, space, H, W, focal, **kw)
-    write_ply(ply_path, out[0], out[1], normals=out[2] if len(out) > 2 else None)
+    if color_view is None:
+        out = field_mesh(field, t, level, gridSize, space, H, W, focal, **kw)
+        write_ply(ply_path, out[0], out[1], normals=out[2] if len(out) > 2 else None)
+        return out
+    _check_kw(kw)
+    out = colored_mesh(field, t, level, gridSize, color_view, space, H, W, focal, **kw)
+    write_ply(ply_path, out[0], out[1], normals=out[2] if len(out) > 3 else None, colors=out[-1])
     return out
