@@ -595,6 +595,38 @@ int rdrf_render_track_seeds_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* 
                                 const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near,
                                 float far, const RdrfRenderMaps* maps, float* seeds, void* ws, size_t ws_bytes,
                                 rdrf_stream_t stream);
+/* Per-slot visibility of a track: vis[M][K], the transmittance T_full of raw2outputs (renderer.py:236-245) from camera k to
+ * the point p = pts[i][k] (field coordinates, as rdrf_track_points_fwd writes them).  No-grad; ndc or contract only.
+ *   time    t_k: t0[i] stepped by dt as rdrf_track_points_fwd steps it (one rounded sum per step), so it has the chain's bits.
+ *   ray     world = NDC2world(p) (ndc) or contract2world(p) (contract), cam = R_k^T (world - c_k): the arithmetic of pix above.
+ *           The slot's ray is camera k's ray through the slot's own fractional pixel pix[i][k]: origin c_k, direction
+ *           R_k ((u - W/2) / f, -(v - H/2) / f, -1), for ndc followed by ndc_rays_blender with near = 1 -- rdrf_camera_rays'
+ *           arithmetic at (u, v) in the place of a pixel centre.
+ *   depth   z* = (clamp(p_z, -1, 1 - 1e-6) + 1) / 2 for ndc, -cam_z for contract: where the point lies on that ray in z_vals
+ *           units.  The query depth is zq = z* - margin; `margin` is the caller's, in z_vals units.  A seed made by
+ *           rdrf_render_track_seeds_fwd sits INSIDE the density that defines it, so its value at margin = 0 is well below 1:
+ *           a caller that wants "is the surface seen" picks a margin of a few sample steps.
+ *   samples the field's no-jitter sampler for the ray type with S samples and (near, far): z_s, valid_s,
+ *           dists_s = (z_{s+1} - z_s) |d| cfg_d->distance_scale (the last 0); sigma_s, sigma_d and blending of a sample have
+ *           the bits rdrf_static_fwd / rdrf_dynamic_fwd give it on that ray at time t_k (0 where not valid).
+ *   vis     with F_s(d) = (1 - (1 - exp(-sigma_d d)) b) (1 - (1 - exp(-sigma_s d)) (1 - b)) + 1e-10 and j the last sample
+ *           with z_j <= zq:   vis = prod_{s < j} F_s(dists_s) * F_j(min(zq - z_j, z_{j+1} - z_j) |d| distance_scale).
+ *           At zq = z_j this is T_full[j] of raw2outputs, formed in rdrf_composite_fwd's scan order; between samples it is
+ *           continuous (the piecewise-constant density the compositor assumes); zq <= z_0 gives exactly 1.0, zq beyond the
+ *           last sample the full product; a point behind its camera (cam_z >= 0) gives 0.0; a NaN depth gives NaN.  vis
+ *           never rises with zq, bit for bit: where rounding would let the scan's T_full[j + 1] exceed T_full[j] F_j by an
+ *           ulp, the running minimum of T_full is taken.  Pixels outside the frame are computed like any other: clipping
+ *           to the frame is the caller's.
+ * Only the samples with valid_s and z_s < zq reach a density kernel (the list kernels of rdrf_render_masked_fwd); no
+ * appearance phase runs.  The product is formed in a fixed order that depends on S and j alone: a slot's bits do not depend
+ * on M, on the other slots of the call or on the run, in the deterministic build too.
+ * cams: required, cams->K == n_bwd + 1 + n_fwd.  ws: rdrf_track_visibility_ws_bytes(M, K, S); M * K * S * 3 < 2^31.
+ * No allocation, no synchronisation.  M == 0 is a no-op. */
+size_t rdrf_track_visibility_ws_bytes(int M, int K, int S);
+int rdrf_track_visibility_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                              const RdrfFieldCfg* cfg_d, const float* pts, const float* t0, int M, int n_fwd, int n_bwd,
+                              float dt, const RdrfTrackCams* cams, int S, float near, float far, float margin, float* vis,
+                              void* ws, size_t ws_bytes, rdrf_stream_t stream);
 
 /* ---- rays of arbitrary cameras (evaluation_path, renderer.py:1013-1030; evaluation, :702-716) -----------------------
  * c2w[B][3][4] camera-to-world matrices, focal[B] per camera.  Ray k is flat pixel first + k over (B, H, W):

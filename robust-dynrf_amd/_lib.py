@@ -202,6 +202,9 @@ SIGNATURES = {
                                    usz, vp]),
     "rdrf_render_track_seeds_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, C.POINTER(RenderMapsC), vp, vp,
                                          usz, vp]),
+    "rdrf_track_visibility_ws_bytes": (usz, [i32, i32, i32]),
+    "rdrf_track_visibility_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, C.POINTER(TrackCamsC), i32, f32, f32,
+                                       f32, vp, vp, usz, vp]),
     "rdrf_camera_rays": (i32, [vp, vp, i32, i32, i32, i32, f32, i64, i32, vp, vp]),
     "rdrf_ssim_workspace_bytes": (usz, [i32, i32, i32]),
     "rdrf_ssim": (i32, [vp, vp, i32, i32, i32, f32, vp, vp, vp, usz, vp]),

@@ -3,7 +3,7 @@
 //                 `evaluation_path`; dataLoader/ray_utils.py:93-110 get_ray_directions_blender, :143-160 get_rays,
 //                 :197-218 ndc_rays_blender)
 //   SSIM        : utils.py:98-151 rgb_ssim (reported beside PSNR by `evaluation`, renderer.py:869-883), in fp64
-#include "rdrf_host.hpp"
+#include "rdrf_misc_dev.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // camera rays: ray k = flat pixel first + k over (B, H, W)
@@ -17,32 +17,10 @@ __global__ __launch_bounds__(256) void k_camera_rays(const float* __restrict__ c
   const int64_t id = first + k;
   const int col = (int)(id % W), row = (int)((id / W) % H);
   const int64_t b = id / ((int64_t)W * H);
-  const float focal = focal_p[b];
-  // get_ray_directions_blender: meshgrid + 0.5, centre (W / 2, H / 2), [focal, focal]
-  const float i = (float)col + 0.5f, j = (float)row + 0.5f;
-  const float cx = (float)((double)W / 2), cy = (float)((double)H / 2);
-  const float dir[3] = {(i - cx) / focal, -(j - cy) / focal, -1.0f};
-  // get_rays: rays_d = directions @ c2w[:3, :3].T, rays_o = c2w[:3, 3]
-  const float* M = c2w + b * 12;
-  float d[3], o[3];
-  for (int r = 0; r < 3; ++r) {
-    d[r] = dir[0] * M[r * 4 + 0] + dir[1] * M[r * 4 + 1] + dir[2] * M[r * 4 + 2];
-    o[r] = M[r * 4 + 3];
-  }
-  if (ndc) {  // ndc_rays_blender
-    const float t = -(near + o[2]) / d[2];
-    o[0] = o[0] + t * d[0]; o[1] = o[1] + t * d[1]; o[2] = o[2] + t * d[2];
-    const float kw = -1.0f / ((float)W / (2.0f * focal)), kh = -1.0f / ((float)H / (2.0f * focal));
-    const float o0 = kw * o[0] / o[2];
-    const float o1 = kh * o[1] / o[2];
-    const float o2 = 1.0f + 2.0f * near / o[2];
-    const float d0 = kw * (d[0] / d[2] - o[0] / o[2]);
-    const float d1 = kh * (d[1] / d[2] - o[1] / o[2]);
-    const float d2 = -2.0f * near / o[2];
-    o[0] = o0; o[1] = o1; o[2] = o2; d[0] = d0; d[1] = d1; d[2] = d2;
-  }
-  float* r = rays + (size_t)k * 6;
-  r[0] = o[0]; r[1] = o[1]; r[2] = o[2]; r[3] = d[0]; r[4] = d[1]; r[5] = d[2];
+  float r[6];
+  camera_ray(c2w + b * 12, focal_p[b], (float)col + 0.5f, (float)row + 0.5f, H, W, ndc, near, r);   // pixel centre: meshgrid + 0.5
+  float* out = rays + (size_t)k * 6;
+  for (int q = 0; q < 6; ++q) out[q] = r[q];
 }
 
 extern "C" int rdrf_camera_rays(const float* c2w, const float* focal, int B, int H, int W, int ndc, float near, int64_t first,

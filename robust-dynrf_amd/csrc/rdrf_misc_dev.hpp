@@ -137,6 +137,39 @@ RDRF_D void sample_world_body(const float* __restrict__ rays, int N, int S, floa
 }
 
 // ------------------------------------------------------------------------------------------------
+// the ray of camera c2w [3][4] through the pixel coordinates (i, j) (a pixel centre is column + 0.5, row + 0.5):
+// get_ray_directions_blender, get_rays and, with `ndc`, ndc_rays_blender with `near` (dataLoader/ray_utils.py:93-110,
+// :143-160, :197-218).  One copy for k_camera_rays (rdrf_eval.hip) and the slot rays of k_track_vis_rays
+// (rdrf_track_vis.hip).  r: origin, direction.
+// ------------------------------------------------------------------------------------------------
+RDRF_D void camera_ray(const float* __restrict__ M, float focal, float i, float j, int H, int W, int ndc, float near,
+                       float (&r)[6]) {
+#pragma clang fp contract(off)
+  // get_ray_directions_blender: centre (W / 2, H / 2), [focal, focal]
+  const float cx = (float)((double)W / 2), cy = (float)((double)H / 2);
+  const float dir[3] = {(i - cx) / focal, -(j - cy) / focal, -1.0f};
+  // get_rays: rays_d = directions @ c2w[:3, :3].T, rays_o = c2w[:3, 3]
+  float d[3], o[3];
+  for (int q = 0; q < 3; ++q) {
+    d[q] = dir[0] * M[q * 4 + 0] + dir[1] * M[q * 4 + 1] + dir[2] * M[q * 4 + 2];
+    o[q] = M[q * 4 + 3];
+  }
+  if (ndc) {  // ndc_rays_blender
+    const float t = -(near + o[2]) / d[2];
+    o[0] = o[0] + t * d[0]; o[1] = o[1] + t * d[1]; o[2] = o[2] + t * d[2];
+    const float kw = -1.0f / ((float)W / (2.0f * focal)), kh = -1.0f / ((float)H / (2.0f * focal));
+    const float o0 = kw * o[0] / o[2];
+    const float o1 = kh * o[1] / o[2];
+    const float o2 = 1.0f + 2.0f * near / o[2];
+    const float d0 = kw * (d[0] / d[2] - o[0] / o[2]);
+    const float d1 = kh * (d[1] / d[2] - o[1] / o[2]);
+    const float d2 = -2.0f * near / o[2];
+    o[0] = o0; o[1] = o1; o[2] = o2; d[0] = d0; d[1] = d1; d[2] = d2;
+  }
+  r[0] = o[0]; r[1] = o[1]; r[2] = o[2]; r[3] = d[0]; r[4] = d[1]; r[5] = d[2];
+}
+
+// ------------------------------------------------------------------------------------------------
 // compositor (raw2outputs)
 // ------------------------------------------------------------------------------------------------
 struct CompArgs {

@@ -1,5 +1,5 @@
 // rdrf_render_host.hpp -- the host side of the no-grad render, one copy of each step for the four units that run it
-// (rdrf_render.hip, rdrf_render_masked.hip, rdrf_motion.hip, rdrf_track.hip):
+// (rdrf_render.hip, rdrf_render_masked.hip, rdrf_motion.hip, rdrf_track.hip) and the per-slot visibility (rdrf_track_vis.hip):
 //   RenderCall     what every entry point of the family is called with; each builds it once
 //   RenderBufs     the workspace carve of a render; the runner hands it back, and the kernels that run after a render
 //                  (motion maps, track seeds) read it
@@ -64,3 +64,17 @@ int render_fields(const RenderCall& c, const RenderBufs& b, const uint8_t* valid
 // The render: checks, carve (handed back in `b`), launches.  mode: RDRF_RENDER_FUSED is the cooperative launch, the two
 // others the launch sequence; an unknown one is refused under the prefix `who`.
 int render_run(const RenderCall& c, int mode, const char* who, RenderBufs& b, rdrf_stream_t stream);
+
+// The list-driven density phase (kernels and launchers: rdrf_render_masked.hip): a field's density kernel runs on the listed
+// samples [N * S flat indices] and on no other.  The device counters of a call are one block of 64 ints, a counter per
+// 64-byte line: the two list lengths and the two appearance-list lengths.
+//   launch_list_time_branch    : the dynamic field's time branch of every ray; clears the counter block on its way
+//   launch_static_density_list : sigma of the listed samples (as.xyz, as.sigma; length ctr[CTR_KEPT_S]); `kept` (nullable)
+//                                receives both list lengths
+//   launch_dyn_density_list    : sigma, blending, xyz_prime, xw of the listed samples (ad.ts, ad.tout, ad.pk; length *count);
+//                                the grid is sized for ad.N * ad.S entries
+constexpr int CTR_KEPT_S = 0, CTR_KEPT_D = 16, CTR_APP_S = 32, CTR_APP_D = 48;
+int launch_list_time_branch(const float* ts, const DynW& wdy, int N, float* tout, int* ctr, hipStream_t stream);
+int launch_static_density_list(const FieldArgs& as, const StaticW& wst, const int* list_s, const int* ctr, long long* kept,
+                               hipStream_t stream);
+int launch_dyn_density_list(const FieldArgs& ad, const DynW& wdy, const int* list_d, const int* count, hipStream_t stream);

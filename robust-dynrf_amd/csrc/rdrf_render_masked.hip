@@ -27,8 +27,7 @@
 #include "rdrf_mask_dev.hpp"
 #include "rdrf_render_host.hpp"
 
-// the four device counters of a call, one 256-byte block cleared by the time-branch launch: a counter per 64-byte line
-constexpr int CTR_KEPT_S = 0, CTR_KEPT_D = 16, CTR_APP_S = 32, CTR_APP_D = 48;
+// the four device counters of a call (CTR_*: rdrf_render_host.hpp), one 256-byte block cleared by the time-branch launch
 
 constexpr int KEEP_ROUNDS = 8;   // samples per thread of k_keep: a workgroup owns 2048 consecutive samples, appends once per list
 
@@ -206,6 +205,25 @@ __global__ __launch_bounds__(64 * RDRF_MAXW) void k_masked_dyn_app(FieldArgs a, 
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+// the launchers of the list-driven density phase (rdrf_render_host.hpp): the masked render below and the per-slot visibility
+// of a point track (rdrf_track_vis.hip) issue them
+int launch_list_time_branch(const float* ts, const DynW& wdy, int N, float* tout, int* ctr, hipStream_t stream) {
+  RDRF_LAUNCH("time_branch", k_masked_time_branch, dim3((N + 7) / 8), dim3(256), stream, ts, wdy, N, tout, ctr);
+  return 0;
+}
+int launch_static_density_list(const FieldArgs& as, const StaticW& wst, const int* list_s, const int* ctr, long long* kept,
+                               hipStream_t stream) {
+  const int blocks = (as.N * as.S + 255) / 256;
+  RDRF_LAUNCH("static_density_list", k_static_density_list, dim3(blocks > 4096 ? 4096 : blocks), dim3(256), stream, as, wst,
+              list_s, ctr, kept);
+  return 0;
+}
+int launch_dyn_density_list(const FieldArgs& ad, const DynW& wdy, const int* list_d, const int* count, hipStream_t stream) {
+  const Geo g3 = geo_for_tiles(ad.N, ad.S);
+  RDRF_LAUNCH("dyn_density_list", k_dyn_density_list, dim3(g3.grid), dim3(g3.block), stream, ad, wdy, list_d, count);
+  return 0;
+}
+
 struct MaskedBufs {
   void* render;   // the unmasked render's workspace (carve_render)
   size_t render_bytes;
@@ -265,7 +283,7 @@ extern "C" int rdrf_render_masked_fwd(const RdrfStaticParams* PS, const RdrfFiel
 
   RDRF_TRY(render_sample(call, b, stream));
   // the time branch of every ray (a masked-out ray costs 17 -> 64 -> 30 once); clears the four counters on its way
-  RDRF_LAUNCH("time_branch", k_masked_time_branch, dim3((N + 7) / 8), dim3(256), stream, ts, wdy, N, ad.tout, m.ctr);
+  RDRF_TRY(launch_list_time_branch(ts, wdy, N, ad.tout, m.ctr, stream));
 
   KeepArgs k;
   memset(&k, 0, sizeof(k));
@@ -275,15 +293,10 @@ extern "C" int rdrf_render_masked_fwd(const RdrfStaticParams* PS, const RdrfFiel
   k.sigma_s = b.sigma_s; k.sigma_d = b.sigma_d; k.blending = b.blending;
   RDRF_LAUNCH("mask_keep", k_keep, dim3((ns + 256 * KEEP_ROUNDS - 1) / (256 * KEEP_ROUNDS)), dim3(256), stream, k);
 
-  {
-    const int blocks = (ns + 255) / 256;
-    RDRF_LAUNCH("static_density_list", k_static_density_list, dim3(blocks > 4096 ? 4096 : blocks), dim3(256), stream, as, wst,
-                (const int*)m.list_s, (const int*)m.ctr, (long long*)kept);
-  }
+  RDRF_TRY(launch_static_density_list(as, wst, m.list_s, m.ctr, (long long*)kept, stream));
   RDRF_LAUNCH("static_scan", k_static_scan, dim3((N + 3) / 4), dim3(256), stream, as);   // 4 rays per workgroup: one list append
   const Geo g3 = geo_for_tiles(N, S);
-  RDRF_LAUNCH("dyn_density_list", k_dyn_density_list, dim3(g3.grid), dim3(g3.block), stream, ad, wdy, (const int*)m.list_d,
-              (const int*)(m.ctr + CTR_KEPT_D));
+  RDRF_TRY(launch_dyn_density_list(ad, wdy, m.list_d, m.ctr + CTR_KEPT_D, stream));
   RDRF_LAUNCH("ray_scan", k_masked_ray_scan, dim3((N + 15) / 16), dim3(512), stream, ad);
   if (cfg_s->static_head == RDRF_HEAD_MLP_FEA)
     RDRF_LAUNCH("static_app", k_masked_static_app<RDRF_HEAD_MLP_FEA>, dim3(g3.grid), dim3(g3.block), stream, as, wst);

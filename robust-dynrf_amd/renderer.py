@@ -604,11 +604,110 @@ def track_points(tensorf, pts, ts, n_fwd, n_bwd, T, cameras=None, focal=None, H=
     get_forward_backward_scene_flow_point_single calls.  cameras [K,3,4] (K = n_bwd + 1 + n_fwd, camera k of slot k) with
     focal, H, W: each point is projected into its slot's camera as render_single_3d_point does (contract:
     render_3d_point's contract2world leg).  Returns Tracks(points [M,K,3], pixels [M,K,2] | None, disp [M,K] | None,
-    frames_offset [K]); slot n_bwd is the seed.  No gradients; no visibility along the track."""
+    frames_offset [K]); slot n_bwd is the seed.  No gradients.  Whether slot k's camera sees the point: track_visibility."""
     n_fwd, n_bwd, dt = _track_args(pts, ts, n_fwd, n_bwd, T, cameras, focal, H, W, ray_type)
     want = L.TRACK_OUTPUTS if cameras is not None else ("pts",)
     b = _track_points_raw(tensorf, pts, ts, n_fwd, n_bwd, dt, cameras, focal, H, W, ray_type, want)
     return Tracks(b["pts"], b.get("pix"), b.get("disp"), torch.arange(-n_bwd, n_fwd + 1, device=pts.device))
+
+
+def _track_vis_args(points, ts, n_fwd, n_bwd, T, cameras, focal, H, W, ray_type, margin):
+    """argument checks of track_visibility (before any device work); returns (n_fwd, n_bwd, dt)"""
+    if ray_type not in L.RAY_TYPES:
+        raise NotImplementedError("track_visibility: ray_type must be 'ndc' or 'contract' (the reference projects no other, "
+                                  "renderer.py:1335-1351)")
+    n_fwd, n_bwd = int(n_fwd), int(n_bwd)
+    if n_fwd < 0 or n_bwd < 0:
+        raise ValueError(f"track_visibility: n_fwd and n_bwd are step counts >= 0, got {n_fwd}, {n_bwd}")
+    K = n_bwd + 1 + n_fwd
+    if not torch.is_tensor(points) or points.dim() != 3 or tuple(points.shape[1:]) != (K, 3):
+        raise ValueError(f"track_visibility: points must be [M,K,3] with K = n_bwd + 1 + n_fwd = {K} (Tracks.points), got "
+                         f"{tuple(points.shape) if torch.is_tensor(points) else type(points).__name__}")
+    if not torch.is_tensor(ts) or ts.shape != points.shape[:1]:
+        raise ValueError("track_visibility: ts [M] times of the seeds in [-1,1]")
+    if int(T) < 2 and (n_fwd or n_bwd):
+        raise ValueError("track_visibility: a video of T < 2 frames has no time step")
+    if cameras is None or not torch.is_tensor(cameras) or cameras.dim() != 3 or tuple(cameras.shape) != (K, 3, 4):
+        raise ValueError(f"track_visibility: cameras must be [K,3,4] with K = n_bwd + 1 + n_fwd = {K}, got "
+                         f"{tuple(cameras.shape) if torch.is_tensor(cameras) else cameras!r}")
+    if focal is None or H is None or W is None or int(H) <= 0 or int(W) <= 0:
+        raise ValueError("track_visibility: cameras need focal, H and W")
+    if not float(margin) == float(margin):
+        raise ValueError("track_visibility: margin is a depth in z_vals units, got NaN")
+    return n_fwd, n_bwd, (2.0 / (int(T) - 1) if int(T) >= 2 else 0.0)
+
+
+def _track_vis_chunk(M, K, S, H, W):
+    """points per rdrf_track_visibility_fwd call: as many as keep the workspace within what render_rays takes for one H x W
+    frame of S samples (one point at least), and the 32-bit sample indices in range"""
+    budget = int(L.lib.rdrf_render_workspace_bytes(int(H) * int(W), S))
+    fixed = int(L.lib.rdrf_track_visibility_ws_bytes(0, K, S))
+    per = max(int(L.lib.rdrf_track_visibility_ws_bytes(1024, K, S)) - fixed, 1) / 1024.0   # bytes per point (256-byte rounding aside)
+    m = int(max(budget - fixed, 0) / per)
+    m = min(m, (2 ** 31 - 1) // (3 * S * K) - 1)
+    while m > 1 and int(L.lib.rdrf_track_visibility_ws_bytes(m, K, S)) > budget:
+        m -= max(m // 64, 1)
+    return max(1, min(m, max(M, 1)))
+
+
+def _track_visibility_raw(tensorf_static, tensorf, points, ts, n_fwd, n_bwd, dt, cameras, focal, H, W, S, ray_type, margin,
+                          vis=None, ws=None):
+    """rdrf_track_visibility_fwd on checked arguments, ONE call for all M points.  vis / ws: caller-owned output buffer
+    [M,K] and workspace (the tests poison them), else allocated here.  Returns vis."""
+    L.require_device(points, ts, cameras)
+    points, ts = L.f32c(points.detach()), L.f32c(ts.detach())
+    M, K, dev = points.shape[0], n_bwd + 1 + n_fwd, points.device
+    if vis is None:
+        vis = torch.empty(M, K, device=dev)
+    if M == 0:
+        return vis
+    cameras = L.f32c(cameras.detach().to(dev))
+    f = _focal_tensor(focal.detach().to(dev) if torch.is_tensor(focal) else focal, dev).contiguous()
+    cams = L.TrackCamsC(int(H), int(W), K, f.data_ptr(), cameras.data_ptr())
+    PS, cs, PD, cd = render_structs(tensorf_static, tensorf, ray_type)
+    if ws is None:
+        ws = L.workspace(dev, L.lib.rdrf_track_visibility_ws_bytes(M, K, S))
+    near, far = tensorf.near_far
+    L.check(L.lib.rdrf_track_visibility_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(points), L.ptr(ts), M,
+                                            int(n_fwd), int(n_bwd), dt, C.byref(cams), S, near, far, float(margin), L.ptr(vis),
+                                            L.ptr(ws), ws.numel(), L.stream_of(points)), "rdrf_track_visibility_fwd")
+    del cameras, f
+    return vis
+
+
+@torch.no_grad()
+def track_visibility(tensorf_static, tensorf, tracks_or_points, ts, n_fwd, n_bwd, T, cameras, focal, H, W, N_samples=-1,
+                     ray_type="ndc", margin=0.0):
+    """Per-slot visibility of point tracks, natively (rdrf_track_visibility_fwd): vis [M,K], the transmittance T_full of
+    raw2outputs (renderer.py:236-245) from camera k to the point of slot k.  tracks_or_points: a Tracks, or its points [M,K,3]
+    (field coordinates); ts [M] the seeds' times, n_fwd, n_bwd, T as track_points takes them (slot k's time is the chain's);
+    cameras [K,3,4] with focal, H, W: camera k of slot k.
+    The slot's ray is camera k's ray through the slot's own fractional pixel (Tracks.pixels[i,k]), sampled by the field's
+    no-jitter sampler with N_samples (default: the dynamic field's nSamples); sigma of both fields and the blending are
+    forward()'s for that ray and time; vis is the compositor's product of (1 - alpha_d b)(1 - alpha_s (1 - b)) + 1e-10 over
+    the samples in front of the query depth zq = z* - margin, the interval that holds zq counted for the part in front of it
+    (at a sample position: T_full[j] of raw2outputs exactly; continuous in between).  z* is the point's depth on the ray in
+    z_vals units: (clamp(p_z, -1, 1 - 1e-6) + 1) / 2 for ndc, -cam_z for contract.
+    margin (z_vals units, default 0): a seed made by render_tracks sits inside the density that defines it, so at margin 0
+    its value is well below 1; to ask "is the surface seen from camera k" pass a margin of a few sample steps (ndc: a step
+    is (far - near) / (N_samples - 1)).
+    zq in front of the first sample gives exactly 1, a point behind its camera exactly 0.  Pixels outside the frame are
+    computed like any other: clip with Tracks.pixels.  Only the samples in front of the points reach a density kernel and no
+    colour is computed.  A slot's bits do not depend on M or on the other slots; large M is processed in chunks of points
+    whose workspace stays within render_rays' for one H x W frame.  No gradients."""
+    points = tracks_or_points.points if isinstance(tracks_or_points, Tracks) else tracks_or_points
+    n_fwd, n_bwd, dt = _track_vis_args(points, ts, n_fwd, n_bwd, T, cameras, focal, H, W, ray_type, margin)
+    S = _n_samples(tensorf, N_samples)
+    M, K = points.shape[0], n_bwd + 1 + n_fwd
+    L.require_device(points, ts, cameras)
+    vis = torch.empty(M, K, device=points.device)
+    if M == 0:
+        return vis
+    chunk = _track_vis_chunk(M, K, S, H, W)
+    for m0 in range(0, M, chunk):
+        _track_visibility_raw(tensorf_static, tensorf, points[m0:m0 + chunk], ts[m0:m0 + chunk], n_fwd, n_bwd, dt, cameras,
+                              focal, H, W, S, ray_type, margin, vis=vis[m0:m0 + chunk])
+    return vis
 
 
 @torch.no_grad()
@@ -617,7 +716,11 @@ def render_tracks(tensorf_static, tensorf, poses9, focal, frame, pixels, H, W, s
     launch sequence (rdrf_render_track_seeds_fwd), the seed of a pixel is render_3d_point's point
     sum_s weights_d xyz + (1 - acc_d) far of its ray, and track_points follows it through the frames
     frame - span .. frame + span clipped to [0, T - 1] (span None: the whole video; a pair: (backward, forward)), projected
-    into those frames' cameras.  Returns (Tracks, acc_d [M]): a seed with a small acc_d sits in static or empty space."""
+    into those frames' cameras.  Returns (Tracks, acc_d [M]): a seed with a small acc_d sits in static or empty space.
+    Their visibility: track_visibility(tensorf_static, tensorf, tracks, ts, n_fwd, n_bwd, T, cameras, ...) with ts = the
+    frame's time 2 frame / (T - 1) - 1 for every pixel, n_bwd = -frames_offset[0], n_fwd = frames_offset[-1] and
+    cameras = pose_to_mtx(poses9)[frame - n_bwd: frame + n_fwd + 1] (see there: a seed sits inside its own density, so pass a
+    margin of a few sample steps)."""
     from .ray_utils import generate_rays, pose_to_mtx
     if ray_type not in L.RAY_TYPES:
         raise NotImplementedError("render_tracks: ray_type must be 'ndc' or 'contract' (the reference projects no other, "
