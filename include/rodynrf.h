@@ -628,6 +628,59 @@ int rdrf_track_visibility_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cf
                               float dt, const RdrfTrackCams* cams, int S, float near, float far, float margin, float* vis,
                               void* ws, size_t ws_bytes, rdrf_stream_t stream);
 
+/* ---- surface hits: per ray the depth at which the opacity 1 - T_full reaches a level tau (no-grad) ---------------------
+ * The depth maps above are expected depths, sum_s w_s z_s: a blend that lies between foreground and background at an
+ * occlusion edge and inside a semi-transparent floater.  A hit is where the ray's transmittance falls to L = 1 - tau
+ * (tau = 0.5: the median depth).  For one ray with samples z_0 < ... < z_{S-1}, dists_s = (z_{s+1} - z_s) |d| distance_scale
+ * (the last 0; ndc, contract: |d| the norm of the ray's direction), sigma_s, sigma_d, blending b:
+ *   factor  F_s(d) = (1 - (1 - exp(-sigma_d d)) b) (1 - (1 - exp(-sigma_s d)) (1 - b)) + 1e-10, the one of the visibility above
+ *   T_s     T_full[s] of raw2outputs as rdrf_composite_fwd forms it (rounds of 64 samples, Hillis-Steele product scan, carry)
+ *   m_s     min_{i <= s} T_i, the running minimum rdrf_track_visibility_fwd takes: it never rises with s, bit for bit
+ *   level   L = 1 - tau, rounded once in fp32
+ *   sample  j = the first s < S - 1 with m_{s+1} <= L.  (The last sample has no width and the factor 1 + 1e-10: it cannot be
+ *           the first to cross and is not looked at.)  None: the ray is a MISS.
+ *   depth   z_hit = min(z_j + t (z_{j+1} - z_j), z_{j+1}) with t = the smallest fp32 number in [0, 1] at which
+ *           m_j F_j(t dists_j) <= L in the compositor's own fp32 arithmetic (t = 1 counts as crossed, the scan having said
+ *           so; t = 0 where m_j <= L already, which happens at j = 0 or through the 1e-10).  It is found by a 64-section over
+ *           the bit pattern of t, 5 rounds whatever the data; t is exact to one ulp of ITSELF, so the transmittance at z_hit
+ *           equals L to rounding however steep the density.  F_j does not rise with d, so z_hit does not fall as tau rises.
+ *   xyz     the sampler's own arithmetic for the ray type (rdrf_sample_ndc / rdrf_sample_contract) at depth z_hit in the place
+ *           of a sample's z: field coordinates; for z_hit == z_s the bits of that sample's xyz
+ *   owner   a_d b / (a_d b + a_s (1 - b)) with a = 1 - exp(-sigma dists_j) of the hit sample, 0 where the denominator is 0:
+ *           the dynamic field's share -- 1 a moving surface, 0 the static scene
+ *   miss    hit = 0, z = z_{S-1}, xyz = the last sample's point, owner = 0
+ *   NaN     a NaN in sigma_s, sigma_d, blending or z of a sample at or before the one a level would cross in: hit = 0 and NaN
+ *           in z, xyz and owner of that level; a NaN behind the crossing has no effect
+ * taus[n_tau]: HOST array, 1 <= n_tau <= 8, each in (0, 1), strictly ascending; all are answered from one scan of the ray.
+ * RdrfHits: DEVICE pointers, each nullable (not wanted: not written), level-major.
+ * Bit for bit: z_j <= z_hit <= z_{j+1}; z_hit does not fall and hit does not rise as tau rises; a ray's outputs do not depend
+ * on N, on the other rays or levels of the call, on the run or on the build (the deterministic library included): every
+ * product is formed in an order that depends on S and j alone.  No allocation, no synchronisation; N == 0 is a no-op. */
+typedef struct RdrfHits {
+  float* z;        /* [n_tau][N] */
+  uint8_t* hit;    /* [n_tau][N] 0 / 1 */
+  float* xyz;      /* [n_tau][N][3] */
+  float* owner;    /* [n_tau][N] */
+} RdrfHits;
+/* the kernel alone, on the caller's planes: rays [N][6], z, sigma_s, sigma_d, blending [N][S] (device); ray_type ndc or
+ * contract (it selects |d| and the point's arithmetic); N * S * 3 < 2^31 */
+int rdrf_hits_from_planes(const float* rays, const float* z, const float* sigma_s, const float* sigma_d, const float* blending,
+                          int N, int S, int ray_type, float distance_scale, const float* taus, int n_tau, const RdrfHits* out,
+                          rdrf_stream_t stream);
+/* The hits of rendered rays: z and valid of the field's no-jitter sampler for (near, far), sigma_s, sigma_d and blending with
+ * the bits rdrf_static_fwd / rdrf_dynamic_fwd give the samples at the rays' times, distance_scale = cfg_d's.
+ *   maps != NULL  rdrf_render_maps_fwd as the launch sequence (same bits in every requested RdrfRenderMaps entry), then the
+ *                 hits from the render's own planes
+ *   maps == NULL  the density-only path: sampler, time branch, both list-driven density kernels of rdrf_render_masked_fwd on
+ *                 every valid sample, the hits; no appearance phase
+ * Both paths give the same bits in every RdrfHits output.  ndc or contract only (alpha masks and world-space rays are not
+ * built here).  ws: rdrf_render_hits_ws_bytes(N, S); N * S * 3 < 2^31.  Every check comes before any device work. */
+size_t rdrf_render_hits_ws_bytes(int N, int S);
+int rdrf_render_hits_fwd(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                         const RdrfFieldCfg* cfg_d, const float* rays, const float* ts, int N, int S, float near, float far,
+                         const float* taus, int n_tau, const RdrfRenderMaps* maps, const RdrfHits* out, void* ws,
+                         size_t ws_bytes, rdrf_stream_t stream);
+
 /* ---- rays of arbitrary cameras (evaluation_path, renderer.py:1013-1030; evaluation, :702-716) -----------------------
  * c2w[B][3][4] camera-to-world matrices, focal[B] per camera.  Ray k is flat pixel first + k over (B, H, W):
  * get_ray_directions_blender (pixel centre + 0.5, centre (W/2, H/2), focal on both axes, dataLoader/ray_utils.py:93-110),

@@ -111,6 +111,15 @@ class TracksC(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in TRACK_OUTPUTS]
 
 
+# RdrfHits (include/rodynrf.h): the nullable outputs of the surface hits, level-major
+HIT_OUTPUTS = ("z", "hit", "xyz", "owner")
+HITS_MAX_TAU = 8
+
+
+class HitsC(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in HIT_OUTPUTS]
+
+
 class RdrfAlphaMask(C.Structure):   # include/rodynrf.h RdrfAlphaMask: a packed occupancy grid (alpha.AlphaGridMask)
     _fields_ = [("bits", C.c_void_p), ("grid", C.c_int * 3), ("T", C.c_int), ("aabb", C.c_float * 6)]
 
@@ -205,6 +214,10 @@ SIGNATURES = {
     "rdrf_track_visibility_ws_bytes": (usz, [i32, i32, i32]),
     "rdrf_track_visibility_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, C.POINTER(TrackCamsC), i32, f32, f32,
                                        f32, vp, vp, usz, vp]),
+    "rdrf_hits_from_planes": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, fp, i32, C.POINTER(HitsC), vp]),
+    "rdrf_render_hits_ws_bytes": (usz, [i32, i32]),
+    "rdrf_render_hits_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, fp, i32, C.POINTER(RenderMapsC),
+                                  C.POINTER(HitsC), vp, usz, vp]),
     "rdrf_camera_rays": (i32, [vp, vp, i32, i32, i32, i32, f32, i64, i32, vp, vp]),
     "rdrf_ssim_workspace_bytes": (usz, [i32, i32, i32]),
     "rdrf_ssim": (i32, [vp, vp, i32, i32, i32, f32, vp, vp, vp, usz, vp]),

@@ -17,6 +17,23 @@ RDRF_D float linspace_at(float start, float end, int steps, int i) {
   return __builtin_fmaf(-step, (float)(steps - i - 1), end);
 }
 
+// The point of a ray at depth t in field coordinates, as the ndc and the contract sampler place a sample: o + d t, and for
+// contract scenes the L-inf contraction of it.  One copy for the two sampler bodies below and for the surface hits
+// (k_render_hits, rdrf_hits.hip), whose point at a sample's own depth so has that sample's bits.
+RDRF_D void ray_point(const float* __restrict__ r, float t, int contract, float (&p)[3]) {
+#pragma clang fp contract(off)
+  float nrm = 0.f;
+  for (int k = 0; k < 3; ++k) {
+    const float m = r[3 + k] * t;
+    p[k] = r[k] + m;
+    nrm = fmaxf(nrm, fabsf(p[k]));
+  }
+  if (contract && nrm > 1.0f) {
+    const float sc = 2.0f - 1.0f / nrm;
+    for (int k = 0; k < 3; ++k) p[k] = sc * (p[k] / nrm);
+  }
+}
+
 RDRF_D void sample_ndc_body(const float* __restrict__ rays, int N, int S, float near, float far,
                             const float* __restrict__ jitter, Box box, float* __restrict__ xyz,
                             float* __restrict__ z, uint8_t* __restrict__ valid, const GridCtx gc) {
@@ -29,13 +46,12 @@ RDRF_D void sample_ndc_body(const float* __restrict__ rays, int N, int S, float 
     const float jj = jitter[j] * c;
     t = t + jj;
   }
-  const float* r = rays + (size_t)n * 6;
+  float p[3];
+  ray_point(rays + (size_t)n * 6, t, 0, p);
   bool out = false;
   for (int k = 0; k < 3; ++k) {
-    const float m = r[3 + k] * t;
-    const float p = r[k] + m;
-    xyz[i * 3 + k] = p;
-    out = out || (box.lo[k] > p) || (p > box.hi[k]);
+    xyz[i * 3 + k] = p[k];
+    out = out || (box.lo[k] > p[k]) || (p[k] > box.hi[k]);
   }
   z[i] = t;
   valid[i] = out ? 0 : 1;
@@ -73,18 +89,8 @@ RDRF_D void sample_contract_body(const float* __restrict__ rays, int N, int S, f
     const float den = inv_far + (c2 * mid) / (float)outer;
     t = 1.0f / den;
   }
-  const float* r = rays + (size_t)n * 6;
   float p[3];
-  float nrm = 0.f;
-  for (int k = 0; k < 3; ++k) {
-    const float m = r[3 + k] * t;
-    p[k] = r[k] + m;
-    nrm = fmaxf(nrm, fabsf(p[k]));
-  }
-  if (nrm > 1.0f) {
-    const float sc = 2.0f - 1.0f / nrm;
-    for (int k = 0; k < 3; ++k) p[k] = sc * (p[k] / nrm);
-  }
+  ray_point(rays + (size_t)n * 6, t, 1, p);
   for (int k = 0; k < 3; ++k) xyz[i * 3 + k] = p[k];
   z[i] = t;
   valid[i] = 1;
@@ -185,6 +191,47 @@ RDRF_D float tfull_factor(float ad, float as, float b) {
   const float u = 1.0f - ad * b;
   const float v = 1.0f - as * (1.0f - b);
   return u * v + 1e-10f;
+}
+
+// ------------------------------------------------------------------------------------------------
+// One round of 64 samples of the T_full scan with its running minimum, for the kernels that walk a ray's transmittance after
+// the compositor (k_track_vis_scan, rdrf_track_vis.hip; k_render_hits, rdrf_hits.hip).  Sample s of the round sits in lane
+// s - j0.  ray_sample: the sample's planes and its dists as the fields form them, (z_{s+1} - z_s) |d| distance_scale, 0 for
+// the last; pf = F_s(dists_s).  tfull_min_round: with pf the lane's factor (1.0 where the caller wants none), Tf = T_s as
+// composite_body forms T_full[s] (scan_mul64, carry cf), Tn = T_{s+1}, mn = m_s = min_{i <= s} T_i (a min scan of the same
+// Hillis-Steele shape, carry mc); cf and mc move on to the next round.
+// ------------------------------------------------------------------------------------------------
+struct RaySample {
+  float zs, zn, width, b, sg_d, sg_s, ds, pf;
+};
+RDRF_D RaySample ray_sample(const float* __restrict__ z, const float* __restrict__ sigma_s, const float* __restrict__ sigma_d,
+                            const float* __restrict__ blending, int n, int S, int s, float nrm, float distance_scale) {
+  RaySample q;
+  const bool act = s < S;
+  const size_t idx = (size_t)n * S + (act ? s : 0);
+  q.zs = z[idx];
+  q.zn = (act && s + 1 < S) ? z[idx + 1] : q.zs;
+  q.width = (s + 1 < S) ? (q.zn - q.zs) : 0.0f;
+  q.b = blending[idx]; q.sg_d = sigma_d[idx]; q.sg_s = sigma_s[idx];
+  q.ds = q.width * nrm * distance_scale;
+  q.pf = tfull_factor(alpha_of(q.sg_d, q.ds), alpha_of(q.sg_s, q.ds), q.b);
+  return q;
+}
+RDRF_D void tfull_min_round(float pf, int lane, float& cf, float& mc, float& Tf, float& Tn, float& mn) {
+  const float ifl = scan_mul64(pf, lane);
+  float ef = __shfl_up(ifl, 1, 64);
+  if (lane == 0) ef = 1.0f;
+  Tf = cf * ef;
+  Tn = cf * ifl;
+  cf *= __shfl(ifl, 63, 64);
+  mn = Tf;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const float o = __shfl_up(mn, d, 64);
+    if (lane >= d) mn = fminf(mn, o);
+  }
+  mn = fminf(mn, mc);
+  mc = __shfl(mn, 63, 64);
 }
 
 RDRF_D void composite_body(const CompArgs a, const GridCtx gc) {

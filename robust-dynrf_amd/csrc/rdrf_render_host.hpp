@@ -78,3 +78,17 @@ int launch_list_time_branch(const float* ts, const DynW& wdy, int N, float* tout
 int launch_static_density_list(const FieldArgs& as, const StaticW& wst, const int* list_s, const int* ctr, long long* kept,
                                hipStream_t stream);
 int launch_dyn_density_list(const FieldArgs& ad, const DynW& wdy, const int* list_d, const int* count, hipStream_t stream);
+
+// The density-only run (defined in rdrf_track_vis.hip; also the maps == NULL path of rdrf_render_hits_fwd, rdrf_hits.hip):
+// sampler of c.rays, time branch, ONE list of the samples with valid (and, with `zq` [N], z < zq of their ray), both
+// list-driven density kernels.  Afterwards sigma_s, sigma_d and blending of a listed sample have forward()'s bits and those
+// of every other sample are zero.  No appearance phase.
+struct DensityBufs {
+  float *xyz, *z;
+  uint8_t* valid;
+  float *sigma_s, *sigma_d, *blending, *xyz_prime, *xw, *tout;
+  int *list, *ctr;
+  float* pk;   // the dynamic field's weight image, packed here when the caller brings none
+};
+void carve_density_only(DensityBufs& b, WsCarver& c, size_t N, size_t S);
+int density_only_run(const RenderCall& c, const DensityBufs& b, const float* zq, rdrf_stream_t stream);

@@ -66,14 +66,15 @@ __global__ __launch_bounds__(256) void k_track_vis_rays(VisRayArgs a) {
 
 // ------------------------------------------------------------------------------------------------
 // k_track_vis_keep: k_keep's shape (rdrf_render_masked.hip) with the point's depth in the place of the masks -- a workgroup
-// owns 2048 consecutive samples and appends once.  A NaN zq keeps nothing.
+// owns 2048 consecutive samples and appends once.  A NaN zq keeps nothing; without zq (the density-only surface hits,
+// rdrf_hits.hip) every valid sample is kept.
 // ------------------------------------------------------------------------------------------------
 constexpr int VIS_KEEP_ROUNDS = 8;
 
 struct VisKeepArgs {
   const float* z;         // [MK * S]
   const uint8_t* valid;   // [MK * S] of the sampler
-  const float* zq;        // [MK]
+  const float* zq;        // [MK]; nullptr: no depth test
   int ns, S;
   int *list, *count;
   float *sigma_s, *sigma_d, *blending;
@@ -88,7 +89,7 @@ __global__ __launch_bounds__(256) void k_track_vis_keep(VisKeepArgs a) {
   for (int r = 0; r < VIS_KEEP_ROUNDS; ++r) {
     const int i = i0 + r * 256;
     const bool act = i < a.ns;
-    const bool keep = act && a.valid[i] != 0 && a.z[i] < a.zq[i / a.S];
+    const bool keep = act && a.valid[i] != 0 && (a.zq == nullptr || a.z[i] < a.zq[i / a.S]);
     if (act && !keep) {
       a.sigma_s[i] = 0.0f;
       a.sigma_d[i] = 0.0f;
@@ -162,31 +163,12 @@ __global__ __launch_bounds__(64 * VIS_SCAN_WAVES) void k_track_vis_scan(VisScanA
     float cf = 1.0f, mc = 1.0f;   // carries: the product and the smallest T of the rounds before
     for (int j0 = 0; j0 <= j; j0 += 64) {
       const int s = j0 + lane;
-      const bool act = s < S;
-      const size_t idx = (size_t)n * S + (act ? s : 0);
-      const float zs = a.z[idx];
-      const float zn = (act && s + 1 < S) ? a.z[idx + 1] : zs;
-      const float width = (s + 1 < S) ? (zn - zs) : 0.0f;
-      const float b = a.blending[idx], sg_d = a.sigma_d[idx], sg_s = a.sigma_s[idx];
-      const float ds = width * nrm * a.distance_scale;
-      const float pf = tfull_factor(alpha_of(sg_d, ds), alpha_of(sg_s, ds), b);
-      const float ifl = scan_mul64(s <= j ? pf : 1.0f, lane);
-      float ef = __shfl_up(ifl, 1, 64);
-      if (lane == 0) ef = 1.0f;
-      const float Tf = cf * ef;       // T_s (T_{j+1} in the lanes behind j)
-      const float Tn = cf * ifl;      // T_{s+1}
-      cf *= __shfl(ifl, 63, 64);
-      float mn = Tf;                  // min scan, Hillis-Steele as scan_mul64
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const float o = __shfl_up(mn, d, 64);
-        if (lane >= d) mn = fminf(mn, o);
-      }
-      mn = fminf(mn, mc);
-      mc = __shfl(mn, 63, 64);
+      const RaySample q = ray_sample(a.z, a.sigma_s, a.sigma_d, a.blending, n, S, s, nrm, a.distance_scale);
+      float Tf, Tn, mn;   // T_s (T_{j+1} in the lanes behind j), T_{s+1}, m_s
+      tfull_min_round(s <= j ? q.pf : 1.0f, lane, cf, mc, Tf, Tn, mn);
       if (s == j) {
-        const float dq = fminf(zq - zs, width) * nrm * a.distance_scale;
-        const float pq = tfull_factor(alpha_of(sg_d, dq), alpha_of(sg_s, dq), b);
+        const float dq = fminf(zq - q.zs, q.width) * nrm * a.distance_scale;
+        const float pq = tfull_factor(alpha_of(q.sg_d, dq), alpha_of(q.sg_s, dq), q.b);
         const float v = mn * pq;
         a.vis[n] = j + 1 < S ? fmaxf(v, fminf(mn, Tn)) : v;
       }
@@ -197,21 +179,8 @@ __global__ __launch_bounds__(64 * VIS_SCAN_WAVES) void k_track_vis_scan(VisScanA
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-struct VisBufs {
-  float *rays, *ts, *zq;
-  uint8_t* behind;
-  float *xyz, *z;
-  uint8_t* valid;
-  float *sigma_s, *sigma_d, *blending, *xyz_prime, *xw, *tout;
-  int *list, *ctr;
-  float* pk;   // the dynamic field's weight image, packed here when the caller brings none
-};
-static void carve_track_vis(VisBufs& b, WsCarver& c, size_t MK, size_t S) {
-  const size_t ns = MK * S;
-  b.rays = c.take<float>(MK * 6);
-  b.ts = c.take<float>(MK);
-  b.zq = c.take<float>(MK);
-  b.behind = c.take<uint8_t>(MK);
+void carve_density_only(DensityBufs& b, WsCarver& c, size_t N, size_t S) {
+  const size_t ns = N * S;
   b.xyz = c.take<float>(ns * 3);
   b.z = c.take<float>(ns);
   b.valid = c.take<uint8_t>(ns);
@@ -220,10 +189,59 @@ static void carve_track_vis(VisBufs& b, WsCarver& c, size_t MK, size_t S) {
   b.blending = c.take<float>(ns);
   b.xyz_prime = c.take<float>(ns * 3);
   b.xw = c.take<float>(ns * 3);
-  b.tout = c.take<float>(MK * 32);
+  b.tout = c.take<float>(N * 32);
   b.list = c.take<int>(ns);
   b.ctr = c.take<int>(64);
   b.pk = c.take<float>(PACK_AREA_FLOATS);
+}
+
+int density_only_run(const RenderCall& call, const DensityBufs& b, const float* zq, rdrf_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  const int N = call.N, S = call.S, ns = N * S;
+  RenderBufs rb;
+  memset(&rb, 0, sizeof(rb));
+  rb.xyz = b.xyz; rb.z = b.z; rb.valid = b.valid;
+  RDRF_TRY(render_sample(call, rb, stream_));
+
+  // the fields' launch arguments: the static list kernel reads xyz and writes sigma; the dynamic one also reads the rays'
+  // times and time branches and its weight image, and writes blending, xyz_prime and xw of the listed samples
+  FieldArgs as, ad;
+  StaticW wst;
+  DynW wdy;
+  fill_common(as, call.cfg_s, call.rays, call.ts, b.xyz, b.z, b.valid, N, S);
+  as.sigma = b.sigma_s;
+  fill_common(ad, call.cfg_d, call.rays, call.ts, b.xyz, b.z, b.valid, N, S);
+  ad.sigma = b.sigma_d; ad.blending = b.blending; ad.xyz_prime = b.xyz_prime; ad.xw = b.xw; ad.tout = b.tout;
+  ad.dynq = fwd_dynq();
+  fill_static_w(wst, call.PS);
+  fill_dyn_w(wdy, call.PD);
+  RDRF_TRY(pack_image(ad.pk, call.PD->packed_fwd, b.pk, stream, dyn_pack_jobs_fwd, call.PD));
+
+  RDRF_TRY(launch_list_time_branch(call.ts, wdy, N, b.tout, b.ctr, stream));   // clears the counter block
+  VisKeepArgs k;
+  memset(&k, 0, sizeof(k));
+  k.z = b.z; k.valid = b.valid; k.zq = zq; k.ns = ns; k.S = S;
+  k.list = b.list; k.count = b.ctr + CTR_KEPT_S;
+  k.sigma_s = b.sigma_s; k.sigma_d = b.sigma_d; k.blending = b.blending;
+  RDRF_LAUNCH("track_vis_keep", k_track_vis_keep, dim3((ns + 256 * VIS_KEEP_ROUNDS - 1) / (256 * VIS_KEEP_ROUNDS)), dim3(256),
+              stream, k);
+  // one list, one length (at CTR_KEPT_S) for both fields
+  RDRF_TRY(launch_static_density_list(as, wst, b.list, b.ctr, nullptr, stream));
+  RDRF_TRY(launch_dyn_density_list(ad, wdy, b.list, b.ctr + CTR_KEPT_S, stream));
+  return 0;
+}
+
+struct VisBufs {
+  float *rays, *ts, *zq;
+  uint8_t* behind;
+  DensityBufs d;
+};
+static void carve_track_vis(VisBufs& b, WsCarver& c, size_t MK, size_t S) {
+  b.rays = c.take<float>(MK * 6);
+  b.ts = c.take<float>(MK);
+  b.zq = c.take<float>(MK);
+  b.behind = c.take<uint8_t>(MK);
+  carve_density_only(b.d, c, MK, S);
 }
 
 extern "C" size_t rdrf_track_visibility_ws_bytes(int M, int K, int S) {
@@ -252,7 +270,6 @@ extern "C" int rdrf_track_visibility_fwd(const RdrfStaticParams* PS, const RdrfF
   RDRF_CHECK((size_t)M * (size_t)K * (size_t)S * 3 < (size_t)INT32_MAX, -1,
              "track_visibility: M * K * S * 3 must stay below 2^31 (32-bit sample indices): call in chunks of points");
   const int MK = (int)((long long)M * K);
-  const int ns = MK * S;
   VisBufs b;
   WsCarver c(ws, ws_bytes);
   carve_track_vis(b, c, (size_t)MK, (size_t)S);
@@ -268,41 +285,13 @@ extern "C" int rdrf_track_visibility_fwd(const RdrfStaticParams* PS, const RdrfF
   ra.rays = b.rays; ra.ts = b.ts; ra.zq = b.zq; ra.behind = b.behind;
   RDRF_LAUNCH("track_vis_rays", k_track_vis_rays, dim3((MK + 255) / 256), dim3(256), stream, ra);
 
-  RenderBufs rb;
-  memset(&rb, 0, sizeof(rb));
-  rb.xyz = b.xyz; rb.z = b.z; rb.valid = b.valid;
-  RDRF_TRY(render_sample(call, rb, stream_));
-
-  // the fields' launch arguments: the static list kernel reads xyz and writes sigma; the dynamic one also reads the rays'
-  // times and time branches and its weight image, and writes blending, xyz_prime and xw of the listed samples
-  FieldArgs as, ad;
-  StaticW wst;
-  DynW wdy;
-  fill_common(as, cfg_s, b.rays, b.ts, b.xyz, b.z, b.valid, MK, S);
-  as.sigma = b.sigma_s;
-  fill_common(ad, cfg_d, b.rays, b.ts, b.xyz, b.z, b.valid, MK, S);
-  ad.sigma = b.sigma_d; ad.blending = b.blending; ad.xyz_prime = b.xyz_prime; ad.xw = b.xw; ad.tout = b.tout;
-  ad.dynq = fwd_dynq();
-  fill_static_w(wst, PS);
-  fill_dyn_w(wdy, PD);
-  RDRF_TRY(pack_image(ad.pk, PD->packed_fwd, b.pk, stream, dyn_pack_jobs_fwd, PD));
-
-  RDRF_TRY(launch_list_time_branch(b.ts, wdy, MK, b.tout, b.ctr, stream));   // clears the counter block
-  VisKeepArgs k;
-  memset(&k, 0, sizeof(k));
-  k.z = b.z; k.valid = b.valid; k.zq = b.zq; k.ns = ns; k.S = S;
-  k.list = b.list; k.count = b.ctr + CTR_KEPT_S;
-  k.sigma_s = b.sigma_s; k.sigma_d = b.sigma_d; k.blending = b.blending;
-  RDRF_LAUNCH("track_vis_keep", k_track_vis_keep, dim3((ns + 256 * VIS_KEEP_ROUNDS - 1) / (256 * VIS_KEEP_ROUNDS)), dim3(256),
-              stream, k);
-  // one list, one length (at CTR_KEPT_S) for both fields
-  RDRF_TRY(launch_static_density_list(as, wst, b.list, b.ctr, nullptr, stream));
-  RDRF_TRY(launch_dyn_density_list(ad, wdy, b.list, b.ctr + CTR_KEPT_S, stream));
+  // sampler, time branch, keep pass (valid && z < zq) and both list-driven density kernels
+  RDRF_TRY(density_only_run(call, b.d, b.zq, stream_));
 
   VisScanArgs sa;
   memset(&sa, 0, sizeof(sa));
-  sa.rays = b.rays; sa.z = b.z; sa.zq = b.zq; sa.behind = b.behind;
-  sa.sigma_s = b.sigma_s; sa.sigma_d = b.sigma_d; sa.blending = b.blending;
+  sa.rays = b.rays; sa.z = b.d.z; sa.zq = b.zq; sa.behind = b.behind;
+  sa.sigma_s = b.d.sigma_s; sa.sigma_d = b.d.sigma_d; sa.blending = b.d.blending;
   sa.MK = MK; sa.S = S; sa.ray_type = cfg_d->ray_type;
   sa.distance_scale = cfg_d->distance_scale;   // the compositor reads the dynamic field's dists
   sa.vis = vis;

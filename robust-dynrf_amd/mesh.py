@@ -78,6 +78,40 @@ def ndc_to_world(pts, H, W, focal):
     return torch.cat([pts_x, pts_y, pts_z], -1)
 
 
+def contract_to_world(pts):
+    """the inverse of the samplers' L-inf contraction (the reference's contract2world): a point of norm n > 1 goes back to
+    p / n / (2 - n); the clamp keeps the shell's outer face finite"""
+    n = pts.abs().amax(-1, keepdim=True)
+    return torch.where(n > 1.0, pts / n * (-1.0 / (n.clamp(max=2.0 - 1e-6) - 2.0)), pts)
+
+
+@torch.no_grad()
+def point_cloud(tensorf_static, tensorf, c2w, focal, H, W, t, tau=0.5, space="field", min_owner=None, max_owner=None,
+                N_samples=-1, ray_type="ndc"):
+    """The coloured point cloud one camera sees at time t: the surface hits (renderer.hit_view) of its H x W rays at the
+    opacity level `tau`, one point per ray that hits.  Returns (xyz [M,3], rgb [M,3] in [0,1], owner [M]); the colours are
+    the `rgb` map of the same call, owner is the dynamic field's share of the hit sample.  min_owner / max_owner keep the
+    points with owner >= / <= the bound (0.5 and None: the moving surfaces; None and 0.5: the static scene).
+    space "field": the fields' coordinates (ndc or contracted); "world": through ndc_to_world / contract_to_world."""
+    from .renderer import hit_view
+    if space not in ("field", "world"):
+        raise L.RdrfError(f"space must be \"field\" or \"world\", not {space!r}")
+    if not isinstance(tau, (int, float)):
+        raise ValueError("point_cloud: one opacity level per cloud")
+    h = hit_view(tensorf_static, tensorf, c2w, focal, H, W, t, float(tau), N_samples, ray_type, maps=("rgb",))
+    keep = h["hit"].reshape(-1)
+    owner = h["owner"].reshape(-1)
+    if min_owner is not None:
+        keep = keep & (owner >= float(min_owner))
+    if max_owner is not None:
+        keep = keep & (owner <= float(max_owner))
+    xyz = h["xyz"].reshape(-1, 3)[keep]
+    if space == "world":
+        f = focal.to(xyz.device) if torch.is_tensor(focal) else focal
+        xyz = ndc_to_world(xyz, H, W, f) if ray_type == "ndc" else contract_to_world(xyz)
+    return xyz, h["rgb"].reshape(-1, 3)[keep].clamp(0.0, 1.0), owner[keep]
+
+
 def face_vertex_normals(verts, faces):
     """area-weighted vertex normals from the faces (a vertex without a non-degenerate face keeps a zero normal)"""
     f = faces.long()
@@ -196,9 +230,11 @@ def _vertex_dtype(normals, colors):
     return np.dtype(fields)
 
 
-def write_ply(path, verts, faces, normals=None, colors=None):
-    """vertex: x y z [nx ny nz] [red green blue]; face: vertex_indices as uchar count + int indices"""
-    v, f = _np(verts, "<f4").reshape(-1, 3), _np(faces, "<i4").reshape(-1, 3)
+def write_ply(path, verts, faces=None, normals=None, colors=None):
+    """vertex: x y z [nx ny nz] [red green blue]; face: vertex_indices as uchar count + int indices.  faces=None: a point
+    cloud, a vertex-only file without a face element."""
+    v = _np(verts, "<f4").reshape(-1, 3)
+    f = None if faces is None else _np(faces, "<i4").reshape(-1, 3)
     vd = _vertex_dtype(normals is not None, colors is not None)
     rec = np.zeros(len(v), dtype=vd)
     rec["x"], rec["y"], rec["z"] = v[:, 0], v[:, 1], v[:, 2]
@@ -208,20 +244,24 @@ def write_ply(path, verts, faces, normals=None, colors=None):
     if colors is not None:
         c = _np(colors, "u1").reshape(-1, 3)
         rec["red"], rec["green"], rec["blue"] = c[:, 0], c[:, 1], c[:, 2]
-    frec = np.zeros(len(f), dtype=np.dtype([("n", "u1"), ("idx", "<i4", (3,))]))
-    frec["n"], frec["idx"] = 3, f
     kinds = {"<f4": "float", "|u1": "uchar"}
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
     header += [f"property {kinds[vd[name].str]} {name}" for name in vd.names]
-    header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+    if f is not None:
+        frec = np.zeros(len(f), dtype=np.dtype([("n", "u1"), ("idx", "<i4", (3,))]))
+        frec["n"], frec["idx"] = 3, f
+        header += [f"element face {len(f)}", "property list uchar int vertex_indices"]
+    header += ["end_header"]
     with open(path, "wb") as out:
         out.write(("\n".join(header) + "\n").encode("ascii"))
         out.write(rec.tobytes())
-        out.write(frec.tobytes())
+        if f is not None:
+            out.write(frec.tobytes())
 
 
 def read_ply(path):
-    """what write_ply writes -> dict(verts [nv,3] f32, faces [nf,3] i32, normals / colors or None)"""
+    """what write_ply writes -> dict(verts [nv,3] f32, faces [nf,3] i32, normals / colors or None); a vertex-only file (a
+    point cloud) comes back with an empty face array"""
     with open(path, "rb") as f:
         data = f.read()
     end = data.index(b"end_header\n") + len(b"end_header\n")
@@ -244,6 +284,7 @@ def read_ply(path):
     if names != vd.names:
         raise ValueError(f"{path}: vertex properties {names} are not what write_ply writes")
     rec = np.frombuffer(data, dtype=vd, count=nv, offset=end)
+    nf = nf or 0
     frec = np.frombuffer(data, dtype=np.dtype([("n", "u1"), ("idx", "<i4", (3,))]), count=nf, offset=end + nv * vd.itemsize)
     if nf and not (frec["n"] == 3).all():
         raise ValueError(f"{path}: only triangles are read")

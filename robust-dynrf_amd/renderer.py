@@ -710,6 +710,143 @@ def track_visibility(tensorf_static, tensorf, tracks_or_points, ts, n_fwd, n_bwd
     return vis
 
 
+def _hit_taus(tau, who):
+    """the opacity levels of a hits call (checked before any device work) -> (list of floats, whether `tau` was a scalar)"""
+    scalar = not isinstance(tau, (list, tuple)) and not (hasattr(tau, "__len__") and getattr(tau, "ndim", 1) > 0)
+    taus = [float(tau)] if scalar else [float(t) for t in tau]
+    if not 1 <= len(taus) <= L.HITS_MAX_TAU:
+        raise ValueError(f"{who}: 1 to {L.HITS_MAX_TAU} opacity levels per call, got {len(taus)}")
+    if any(not 0.0 < t < 1.0 for t in taus):
+        raise ValueError(f"{who}: every tau must lie in (0, 1), got {taus}")
+    if any(b <= a for a, b in zip(taus, taus[1:])):
+        raise ValueError(f"{who}: the levels must ascend strictly, got {taus}")
+    return taus, scalar
+
+
+def _hits_chunk(N, S):
+    """rays per rdrf_render_hits_fwd call: as many as keep the 32-bit sample indices in range (N S 3 < 2^31)"""
+    return max(1, min(max(int(N), 1), (2 ** 31 - 1) // (3 * int(S)) - 1))
+
+
+def _hits_struct(bufs):
+    return L.HitsC(*[bufs[n].data_ptr() if n in bufs else None for n in L.HIT_OUTPUTS])
+
+
+def _alloc_hits(n_tau, N, dev, want=L.HIT_OUTPUTS):
+    shapes = {"z": (n_tau, N), "hit": (n_tau, N), "xyz": (n_tau, N, 3), "owner": (n_tau, N)}
+    return {n: torch.empty(shapes[n], device=dev, dtype=torch.uint8 if n == "hit" else torch.float32) for n in want}
+
+
+def _render_hits_raw(tensorf_static, tensorf, rays, ts, taus, S, ray_type, map_names, bufs=None, mbufs=None, ws=None):
+    """rdrf_render_hits_fwd on checked arguments, ONE call for all N rays.  map_names: the RenderMaps fields to write (empty:
+    the density-only path).  bufs / mbufs / ws: caller-owned hit buffers [n_tau,N..] and map buffers by name and workspace
+    (the tests poison them), else allocated here.  Returns (bufs, mbufs)."""
+    L.require_device(rays, ts)
+    rays, ts = L.f32c(rays), L.f32c(ts)
+    N, dev = rays.shape[0], rays.device
+    if bufs is None:
+        bufs = _alloc_hits(len(taus), N, dev)
+    if mbufs is None:
+        mbufs = _alloc_maps(map_names, N, dev)
+    if N == 0:
+        return bufs, mbufs
+    PS, cs, PD, cd = render_structs(tensorf_static, tensorf, ray_type)
+    if ws is None:
+        ws = L.workspace(dev, L.lib.rdrf_render_hits_ws_bytes(N, S))
+    near, far = tensorf.near_far
+    arr = (C.c_float * len(taus))(*taus)
+    Mp = _maps_struct(mbufs) if map_names else None
+    out = _hits_struct(bufs)
+    L.check(L.lib.rdrf_render_hits_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), N, S, near, far,
+                                       arr, len(taus), None if Mp is None else C.byref(Mp), C.byref(out), L.ptr(ws), ws.numel(),
+                                       L.stream_of(rays)), "rdrf_render_hits_fwd")
+    return bufs, mbufs
+
+
+def hits_from_planes(rays, z, sigma_s, sigma_d, blending, tau=0.5, ray_type="ndc", distance_scale=1.0):
+    """rdrf_hits_from_planes: the hits kernel alone on the caller's device planes z, sigma_s, sigma_d, blending [N,S] of the
+    rays [N,6] (dists are formed from z and the ray norm as the fields form them).  Returns the dict of render_hits without
+    maps."""
+    taus, scalar = _hit_taus(tau, "hits_from_planes")
+    if ray_type not in L.RAY_TYPES:
+        raise NotImplementedError("hits_from_planes: ray_type must be 'ndc' or 'contract'")
+    L.require_device(rays, z, sigma_s, sigma_d, blending)
+    rays, z, sigma_s, sigma_d, blending = (L.f32c(t) for t in (rays, z, sigma_s, sigma_d, blending))
+    N, S = z.shape
+    if rays.shape != (N, 6) or any(t.shape != (N, S) for t in (sigma_s, sigma_d, blending)):
+        raise ValueError("hits_from_planes: rays [N,6]; z, sigma_s, sigma_d, blending [N,S]")
+    bufs = _alloc_hits(len(taus), N, z.device)
+    out = _hits_struct(bufs)
+    arr = (C.c_float * len(taus))(*taus)
+    L.check(L.lib.rdrf_hits_from_planes(L.ptr(rays), L.ptr(z), L.ptr(sigma_s), L.ptr(sigma_d), L.ptr(blending), N, S,
+                                        L.RAY_TYPES[ray_type], float(distance_scale), arr, len(taus), C.byref(out),
+                                        L.stream_of(z)), "rdrf_hits_from_planes")
+    return _hits_result(bufs, {}, scalar)
+
+
+def _hits_result(bufs, mbufs, scalar):
+    out = {n: (bufs[n][0] if scalar else bufs[n]) for n in L.HIT_OUTPUTS}
+    out["hit"] = out["hit"].bool()
+    out.update(mbufs)
+    return out
+
+
+@torch.no_grad()
+def render_hits(tensorf_static, tensorf, rays, ts, tau=0.5, N_samples=-1, ray_type="ndc", maps=False):
+    """Surface hits of a ray batch, natively (rdrf_render_hits_fwd): per ray the depth at which the opacity 1 - T_full of
+    raw2outputs (renderer.py:236-245) reaches `tau` -- tau = 0.5 is the median depth -- where the depth maps of render_rays
+    are expected depths, which lie between the surfaces at an occlusion edge and inside a floater.
+    Returns a dict: z [N] the hit depth in z_vals units (between the two samples the crossing lies in, exact for the
+    compositor's piecewise-constant density), hit [N] bool (False: the ray never gets that opaque; z is then the last
+    sample's depth), xyz [N,3] the point at z in field coordinates (the sampler's arithmetic, as sampleXYZ's xyz), owner [N]
+    the dynamic field's share of the hit sample (1: a moving surface, 0: the static scene).  `tau` may be a sequence of up
+    to 8 strictly ascending levels in (0, 1): every output gains a leading axis, and all levels come from one scan.
+    maps: False -- the density-only path, no colour is computed --, or True / a subset of the RenderMaps field names: the
+    render runs as render_rays(maps=...) does and the dict also holds those maps by name, bit for bit.  Both paths give the
+    same hits.  A ray's bits do not depend on the batch: large N is processed in chunks.  ndc or contract; no gradients."""
+    taus, scalar = _hit_taus(tau, "render_hits")
+    if ray_type not in L.RAY_TYPES:
+        raise NotImplementedError("render_hits: ray_type must be 'ndc' or 'contract' (world-space rays are not built here)")
+    names = _map_names(maps) if maps else ()
+    L.require_device(rays, ts)
+    N, dev = rays.shape[0], rays.device
+    S = _n_samples(tensorf, N_samples)
+    chunk = _hits_chunk(N, S)
+    if chunk >= N:
+        bufs, mbufs = _render_hits_raw(tensorf_static, tensorf, rays, ts, taus, S, ray_type, names)
+        return _hits_result(bufs, mbufs, scalar)
+    bufs, mbufs = _alloc_hits(len(taus), N, dev), _alloc_maps(names, N, dev)
+    for c0 in range(0, N, chunk):
+        b, m = _render_hits_raw(tensorf_static, tensorf, rays[c0:c0 + chunk], ts[c0:c0 + chunk], taus, S, ray_type, names)
+        for n in bufs:
+            bufs[n][:, c0:c0 + chunk] = b[n]
+        for n in mbufs:
+            mbufs[n][c0:c0 + chunk] = m[n]
+    return _hits_result(bufs, mbufs, scalar)
+
+
+@torch.no_grad()
+def hit_view(tensorf_static, tensorf, c2w, focal, H, W, t, tau=0.5, N_samples=-1, ray_type="ndc", maps=False):
+    """render_hits on the rays of one camera c2w [3,4] at time t in [-1,1] (camera_rays, as render_view): the same dict as
+    images -- z, hit, owner [H,W], xyz [H,W,3] (a leading level axis for a sequence of taus), maps [H,W] / [H,W,3], raw."""
+    taus, scalar = _hit_taus(tau, "hit_view")
+    if ray_type not in L.RAY_TYPES:
+        raise NotImplementedError("hit_view: ray_type must be 'ndc' or 'contract' (world-space rays are not built here)")
+    dev = tensorf.aabb.device
+    c2w = torch.as_tensor(c2w, dtype=torch.float32).to(dev)
+    if torch.is_tensor(focal) and focal.device != dev:
+        focal = focal.to(dev)
+    rays = camera_rays(c2w.reshape(1, 3, 4), focal, H, W, ndc=ray_type == "ndc", near=1.0)
+    ts = torch.full((H * W,), float(t), device=dev)
+    out = render_hits(tensorf_static, tensorf, rays, ts, taus[0] if scalar else taus, N_samples, ray_type, maps)
+
+    def image(n, v):
+        k = 1 if n in L.HIT_OUTPUTS and not scalar else 0   # the level axis stays in front
+        return v.view(*v.shape[:k], H, W, *v.shape[k + 1:])
+
+    return {n: image(n, v) for n, v in out.items()}
+
+
 @torch.no_grad()
 def render_tracks(tensorf_static, tensorf, poses9, focal, frame, pixels, H, W, span=None, N_samples=-1, ray_type="ndc"):
     """Tracks of M query pixels of `frame`: pixels [M,2] integer (column, row).  Their rays are rendered by the no-grad
@@ -720,7 +857,24 @@ def render_tracks(tensorf_static, tensorf, poses9, focal, frame, pixels, H, W, s
     Their visibility: track_visibility(tensorf_static, tensorf, tracks, ts, n_fwd, n_bwd, T, cameras, ...) with ts = the
     frame's time 2 frame / (T - 1) - 1 for every pixel, n_bwd = -frames_offset[0], n_fwd = frames_offset[-1] and
     cameras = pose_to_mtx(poses9)[frame - n_bwd: frame + n_fwd + 1] (see there: a seed sits inside its own density, so pass a
-    margin of a few sample steps)."""
+    margin of a few sample steps).  Seeds ON the surface: render_hit_tracks."""
+    return _render_tracks(tensorf_static, tensorf, poses9, focal, frame, pixels, H, W, span, N_samples, ray_type, None)
+
+
+@torch.no_grad()
+def render_hit_tracks(tensorf_static, tensorf, poses9, focal, frame, pixels, H, W, span=None, N_samples=-1, ray_type="ndc",
+                      tau=0.5):
+    """render_tracks with the seeds on the surface: the seed of a pixel is the surface hit of its ray at the opacity level
+    `tau` (render_hits' xyz: where the ray's opacity reaches tau, not a blend of depths inside the density), and a ray that
+    misses keeps render_tracks' expected-depth seed.  Same arguments and returns otherwise: (Tracks, acc_d [M])."""
+    taus, scalar = _hit_taus(tau, "render_hit_tracks")
+    if not scalar:
+        raise ValueError("render_hit_tracks: one opacity level seeds the tracks")
+    return _render_tracks(tensorf_static, tensorf, poses9, focal, frame, pixels, H, W, span, N_samples, ray_type, taus[0])
+
+
+def _render_tracks(tensorf_static, tensorf, poses9, focal, frame, pixels, H, W, span, N_samples, ray_type, tau):
+    """render_tracks (tau None) / render_hit_tracks (the seeds' opacity level)"""
     from .ray_utils import generate_rays, pose_to_mtx
     if ray_type not in L.RAY_TYPES:
         raise NotImplementedError("render_tracks: ray_type must be 'ndc' or 'contract' (the reference projects no other, "
@@ -752,7 +906,10 @@ def render_tracks(tensorf_static, tensorf, poses9, focal, frame, pixels, H, W, s
         L.check(L.lib.rdrf_render_track_seeds_fwd(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(rays), L.ptr(ts), M, S,
                                                   near, far, C.byref(Mp), L.ptr(seeds), L.ptr(ws), ws.numel(),
                                                   L.stream_of(rays)), "rdrf_render_track_seeds_fwd")
-    cams = pose_to_mtx(poses9.detach().float())[frame - n_bwd: frame + n_fwd + 1]
+        if tau is not None:
+            h = render_hits(tensorf_static, tensorf, rays, ts, tau, S, ray_type)
+            seeds = torch.where(h["hit"][:, None], h["xyz"], seeds)
+    cams =pose_to_mtx(poses9.detach().float())[frame - n_bwd: frame + n_fwd + 1]
     tracks = track_points(tensorf, seeds, ts, n_fwd, n_bwd, T, cameras=cams, focal=focal, H=H, W=W, ray_type=ray_type)
     return tracks, bufs["acc_d"]
 
