@@ -885,6 +885,19 @@ int rdrf_selftest_scatter(int kind, int mode, const RdrfScatterTest* t, rdrf_str
 int rdrf_selftest_scatter_describe(int kind, const int* grid, int* out, int cap);
 int rdrf_selftest_scatter_last(int* out, int cap);
 
+/* The forward VM gather with shared taps on points the caller supplies, through the device functions of the forward kernels
+ * unchanged (one wave per 32 points, lane = 32 h + s as there).  kind = RDRF_SCK_*: STATIC_DENSITY static_density_feature, one
+ * float per point; STATIC_APP gather_level_app at level 0, 72 features; DYN_DENSITY gather_level_den at levels 0, 1, 2 as the
+ * density / blending heads call it, 72 features; DYN_APP gather_level_app at levels 0, 1, 2, 216 features.  xn [M][3] normalised
+ * coordinates (any float, non-finite included: every address is clamped).  out [nsets][M][features], the raw products in logical
+ * order [level][plane][component], moved there from the lane layout by the index maps that lay out the first-layer weight columns.
+ * vm: nsets (1 or 2) factor sets of the kind's component counts on one grid, axes of at least one texel.  M = 0 is a no-op.
+ *
+ * rdrf_selftest_encodings: fill_x0 / fill_x1 per half-wave on (xn [M][3], t [M]) -> x0_out [M][64] = [xn 3 | sin(2^k xn_d), d-major,
+ * k = 0..9 | cos likewise | t], x1_out [M][16] = [sin(2^k t), k = 0..7 | cos likewise]: the column order of the heads' first layer. */
+int rdrf_selftest_gather(int kind, const RdrfVM* vm, int nsets, const float* xn, int M, float* out, rdrf_stream_t stream);
+int rdrf_selftest_encodings(const float* xn, const float* t, int M, float* x0_out, float* x1_out, rdrf_stream_t stream);
+
 /* ---- alpha volumes and alpha-grid masks (models/tensorBase.py:42-79 AlphaGridMask, :565-702) ----------------------------
  * A mask is the occupancy grid of updateAlphaMask, bit-packed exactly as `save` (:465-469) stores it: the bool volume of
  * logical shape (G2, G1, G0, T) flattened in C order, eight entries per byte, first entry in the most significant bit

@@ -13,8 +13,12 @@
 // rdrf_selftest_sort / rdrf_selftest_scatter (host code only): the radix sort as sorted_scatter_prepare calls it, and the
 // gradient scatter through the product's own launch functions (launch_scatter, scatter_dyn_*_sorted of rdrf_scatter.hip) on
 // data the caller supplies; reference: tests/_scatter_prim.py.
+//
+// rdrf_selftest_gather / rdrf_selftest_encodings: the forward VM gather and the positional encodings through the device functions
+// of the forward kernels; reference: tests/_gather_prim.py.
 #include <vector>
 
+#include "rdrf_fwd_dev.hpp"
 #include "rdrf_bwd_dev.hpp"
 #include "rdrf_bwd_host.hpp"
 #include "rdrf_sort_dev.hpp"
@@ -703,6 +707,126 @@ extern "C" int rdrf_selftest_scatter_last(int* out, int cap) {
     out[n++] = r.l[i].tw; out[n++] = r.l[i].slice_steps;
   }
   return n;
+}
+
+// ------------------------------------------------------------------------------------------------
+// rdrf_selftest_gather / rdrf_selftest_encodings: the forward VM gather (shared taps) and the positional encodings as the forward
+// kernels call them, on points the caller supplies; reference: tests/_gather_prim.py.  One wave per 32 points, lane = 32 h + s
+// holds half h of point s in the canonical layout; a lane past M evaluates point 0 and stores nothing.  The raw registers go
+// out in LOGICAL column order through the index maps the pack jobs of rdrf_fwd.hip lay the first-layer weights out with
+// (seg_imap o elem_of): slot kk of half h is column seg_imap(seg, elem_of(kk, h), in_dim), so a gather order that disagrees with
+// the weight columns shows up as a permuted row.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+template <int NK>
+RDRF_D void gt_store(const float (&v)[NK], float* __restrict__ out, int row, int ld, int seg, int kk0, int in_dim, int col0, int h) {
+#pragma unroll
+  for (int kk = 0; kk < NK; ++kk) {
+    const int col = seg_imap(seg, elem_of(kk0 + kk, h), in_dim);
+    if (col >= 0) out[(size_t)row * ld + (col - col0)] = v[kk];
+  }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(64) void k_st_gather(const RdrfVM vm, const float* __restrict__ xn, int M, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63, h = lane >> 5, row = blockIdx.x * 32 + (lane & 31);
+  const bool act = row < M;
+  const int idx = act ? row : 0;
+  const float x0 = xn[(size_t)idx * 3 + 0], x1 = xn[(size_t)idx * 3 + 1], x2 = xn[(size_t)idx * 3 + 2];
+  if constexpr (KIND == RDRF_SCK_STATIC_DENSITY) {   // static_density_body / k_alpha_static / k_point_static
+    const float f = static_density_feature(vm, x0, x1, x2);
+    if (act && h == 0) out[row] = f;
+  } else if constexpr (KIND == RDRF_SCK_STATIC_APP) {   // static_app_body: basis columns SEG_IDENT of 72
+    float G[36];
+    gather_level_app<0>(vm, point_taps(vm, x0, x1, x2, 0), h, G);
+    if (act) gt_store<36>(G, out, row, 72, SEG_IDENT, 0, 72, 0, h);
+  } else if constexpr (KIND == RDRF_SCK_DYN_DENSITY) {   // head_raw: first-layer columns SEG_IDENT of 72
+    float Fv[36];
+    gather_level_den<0>(vm, point_taps(vm, x0, x1, x2, 0), h, Fv);
+    gather_level_den<12>(vm, point_taps(vm, x0, x1, x2, 1), h, Fv);
+    gather_level_den<24>(vm, point_taps(vm, x0, x1, x2, 2), h, Fv);
+    if (act) gt_store<36>(Fv, out, row, 72, SEG_IDENT, 0, 72, 0, h);
+  } else {   // dyn_app_body: level by level, basis columns SEG_IDENT of 216 at slots 36 lv ..
+    {
+      float A[36];
+      gather_level_app<0>(vm, point_taps(vm, x0, x1, x2, 0), h, A);
+      if (act) gt_store<36>(A, out, row, 216, SEG_IDENT, 0, 216, 0, h);
+    }
+    {
+      float A[36];
+      gather_level_app<0>(vm, point_taps(vm, x0, x1, x2, 1), h, A);
+      if (act) gt_store<36>(A, out, row, 216, SEG_IDENT, 36, 216, 0, h);
+    }
+    {
+      float A[36];
+      gather_level_app<0>(vm, point_taps(vm, x0, x1, x2, 2), h, A);
+      if (act) gt_store<36>(A, out, row, 216, SEG_IDENT, 72, 216, 0, h);
+    }
+  }
+}
+
+// X0 -> [xn 3 | sin 30 | cos 30 | t] = columns 72 .. 135 of the heads' first layer, X1 -> [sin 8 | cos 8] = columns 136 .. 151
+__global__ __launch_bounds__(64) void k_st_encodings(const float* __restrict__ xn, const float* __restrict__ t, int M,
+                                                     float* __restrict__ x0_out, float* __restrict__ x1_out) {
+  const int lane = threadIdx.x & 63, h = lane >> 5, row = blockIdx.x * 32 + (lane & 31);
+  const bool act = row < M;
+  const int idx = act ? row : 0;
+  const float tt = t[idx];
+  float X0[32], X1[8];
+  fill_x0(X0, xn[(size_t)idx * 3 + 0], xn[(size_t)idx * 3 + 1], xn[(size_t)idx * 3 + 2], tt, h);
+  fill_x1(X1, tt, h);
+  if (act) {
+    gt_store<32>(X0, x0_out, row, 64, SEG_DEN1_X0, 0, 152, 72, h);
+    gt_store<8>(X1, x1_out, row, 16, SEG_DEN1_X1, 0, 152, 136, h);
+  }
+}
+
+// every address of the gather is a clamped tap index times a stride: inside the arrays for any axis of at least one texel
+bool gather_vm_ok(const RdrfVM& v, int c0, int c1) {
+  if (!vm_ok(v, c0, c1)) return false;
+  for (int i = 0; i < 3; ++i) {
+    if (v.W[i] < 1 || v.H[i] < 1 || v.L[i] < 1 || !v.plane[i] || !v.line[i]) return false;
+    const bool w_fast = v.sW[i] == v.C[i] && v.sH[i] == v.W[i] * v.C[i], h_fast = v.sH[i] == v.C[i] && v.sW[i] == v.H[i] * v.C[i];
+    if (!w_fast && !h_fast) return false;   // the two storage orders of a plane: the arrays hold H W C floats
+    if ((((uintptr_t)v.plane[i] | (uintptr_t)v.line[i]) & 15) != 0) return false;
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" int rdrf_selftest_gather(int kind, const RdrfVM* vm, int nsets, const float* xn, int M, float* out, rdrf_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RDRF_CHECK(kind >= RDRF_SCK_STATIC_DENSITY && kind <= RDRF_SCK_DYN_APP, -1, "selftest_gather: unknown kind %d", kind);
+  RDRF_CHECK(nsets >= 1 && nsets <= 2, -1, "selftest_gather: one or two factor sets (got %d)", nsets);
+  if (M == 0) return 0;   // empty batch: a no-op
+  RDRF_CHECK(vm && xn && out && M > 0 && M <= (1 << 24), -1, "selftest_gather: bad arguments");
+  const bool app = kind == RDRF_SCK_STATIC_APP || kind == RDRF_SCK_DYN_APP;
+  const int nf = kind == RDRF_SCK_STATIC_DENSITY ? 1 : (kind == RDRF_SCK_DYN_APP ? 216 : 72);
+  for (int set = 0; set < nsets; ++set)
+    RDRF_CHECK(gather_vm_ok(vm[set], app ? 48 : 16, app ? 12 : 4), -1,
+               "selftest_gather: factor set %d: component counts, one grid of at least one texel per axis, W-fastest or H-fastest "
+               "planes, 16-byte aligned", set);
+  const dim3 grid((M + 31) / 32), block(64);
+  for (int set = 0; set < nsets; ++set) {
+    float* o = out + (size_t)set * M * nf;
+    switch (kind) {
+      case RDRF_SCK_STATIC_DENSITY: RDRF_LAUNCH("selftest_gather", k_st_gather<RDRF_SCK_STATIC_DENSITY>, grid, block, stream, vm[set], xn, M, o); break;
+      case RDRF_SCK_STATIC_APP: RDRF_LAUNCH("selftest_gather", k_st_gather<RDRF_SCK_STATIC_APP>, grid, block, stream, vm[set], xn, M, o); break;
+      case RDRF_SCK_DYN_DENSITY: RDRF_LAUNCH("selftest_gather", k_st_gather<RDRF_SCK_DYN_DENSITY>, grid, block, stream, vm[set], xn, M, o); break;
+      default: RDRF_LAUNCH("selftest_gather", k_st_gather<RDRF_SCK_DYN_APP>, grid, block, stream, vm[set], xn, M, o); break;
+    }
+  }
+  return 0;
+}
+
+extern "C" int rdrf_selftest_encodings(const float* xn, const float* t, int M, float* x0_out, float* x1_out, rdrf_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (M == 0) return 0;   // empty batch: a no-op
+  RDRF_CHECK(xn && t && x0_out && x1_out && M > 0 && M <= (1 << 24), -1, "selftest_encodings: bad arguments");
+  RDRF_LAUNCH("selftest_encodings", k_st_encodings, dim3((M + 31) / 32), dim3(64), stream, xn, t, M, x0_out, x1_out);
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
