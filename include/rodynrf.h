@@ -898,6 +898,26 @@ int rdrf_selftest_scatter_last(int* out, int cap);
 int rdrf_selftest_gather(int kind, const RdrfVM* vm, int nsets, const float* xn, int M, float* out, rdrf_stream_t stream);
 int rdrf_selftest_encodings(const float* xn, const float* t, int M, float* x0_out, float* x1_out, rdrf_stream_t stream);
 
+/* The per-field ray scan on arrays the caller supplies, through the kernels and the launch geometry of the entry points.
+ * rdrf_selftest_ray_scan: sigma [N][S] -> dists -> alpha -> transmittance scan -> weight, the appearance-mask compaction and the zero
+ * fill of the colours.  width 32: k_ray_scan (the dynamic field's flat density phase), width 64: k_static_scan (the per-ray half of
+ * the static field's density kernel).  rays [N][6], z [N][S]; weight, dists [N][S]; list: the flat indices of the samples with
+ * weight > weight_thres, appended from *counter on (the counter is ADDED to; ascending within a ray, rays in arrival order); rgb
+ * (nullable) [N][S][3] is zeroed.
+ * rdrf_selftest_ray_scan_bwd: the same scan backward.  width 32: k_ray_scan_bwd, raw [N][S][2] (the density head's output in slot
+ * 0), out = gsig [N][S], the total d(sigma) of every sample.  width 64: k_static_density_bwd, raw [N][S], out = gf rows
+ * [N][32 ceil(S / 32)], d(density feature) = d(sigma) act'(raw) at valid samples and 0 elsewhere (padding columns untouched).
+ * sigma = valid ? act(raw) : 0 (act = RDRF_ACT_*).  g_weight, g_sigma, g_dists [N][S]: nullable cotangents; g_z [N][S], g_rays [N][6]:
+ * nullable, ACCUMULATED into (g_rays columns 3..5, ndc / contract rays only).
+ * Both: N = 0 is a no-op; S in 1 .. 4096; -1 on bad arguments. */
+int rdrf_selftest_ray_scan(int width, const float* rays, const float* z, const float* sigma, int N, int S, int ray_type,
+                           float distance_scale, float weight_thres, float* weight, float* dists, int* list, int* counter,
+                           float* rgb, rdrf_stream_t stream);
+int rdrf_selftest_ray_scan_bwd(int width, const float* rays, const float* z, const uint8_t* valid, const float* raw, int N, int S,
+                               int act, float density_shift, float distance_scale, int ray_type, const float* g_weight,
+                               const float* g_sigma, const float* g_dists, float* out, float* g_z, float* g_rays,
+                               rdrf_stream_t stream);
+
 /* ---- alpha volumes and alpha-grid masks (models/tensorBase.py:42-79 AlphaGridMask, :565-702) ----------------------------
  * A mask is the occupancy grid of updateAlphaMask, bit-packed exactly as `save` (:465-469) stores it: the bool volume of
  * logical shape (G2, G1, G0, T) flattened in C order, eight entries per byte, first entry in the most significant bit

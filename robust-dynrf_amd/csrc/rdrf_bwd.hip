@@ -679,6 +679,16 @@ static void fill_dyn_g(DynG& g, const RdrfDynamicParams* G) {
   g.l5w = G->l5w; g.dw2 = G->dw2; g.bw2 = G->bw2;
 }
 
+// the two ray scan backward kernels with their launch geometry: the entry points below and ray_scan_bwd_on_arrays
+static int launch_static_density_bwd(const BwdArgs& a, const StaticW& w, float* gf, hipStream_t stream) {
+  RDRF_LAUNCH("static_density_bwd", k_static_density_bwd, dim3(a.N), dim3(64), stream, a, w, gf);   // a wave per ray
+  return 0;
+}
+static int launch_ray_scan_bwd(const BwdArgs& a, hipStream_t stream) {
+  RDRF_LAUNCH("ray_scan_bwd", k_ray_scan_bwd, dim3((a.N + 15) / 16), dim3(512), stream, a);   // 16 rays per workgroup
+  return 0;
+}
+
 // `valid` of a feature-mode batch: 1 for the M points, 0 for the padding of the last 32-point tile
 static int pad_valid_tiles(uint8_t* valid, int M, size_t mp, hipStream_t stream) {
   RDRF_FILL(valid, 0, mp, stream);
@@ -930,7 +940,7 @@ extern "C" int rdrf_static_bwd(const RdrfStaticParams* P, const RdrfFieldCfg* cf
     RDRF_TRY(dw_launch(D, stream, "dw_static"));
   }
   if (g_sigma != nullptr || g_weight != nullptr || ((g_rays != nullptr || g_z != nullptr) && g_dists != nullptr)) {
-    RDRF_LAUNCH("static_density_bwd", k_static_density_bwd, dim3(N), dim3(64), stream, a, w, b.gf);
+    RDRF_TRY(launch_static_density_bwd(a, w, b.gf, stream));
     if (g_sigma != nullptr || g_weight != nullptr) {
       ScatterArgs sa;
       fill_scatter_common(sa, a);
@@ -1010,7 +1020,7 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
     const int smode = scatter_mode(ns, stream);
     a.dfs = smode != 0 ? b.dfs : nullptr;
     if (flat) {
-      RDRF_LAUNCH("ray_scan_bwd", k_ray_scan_bwd, dim3((N + 15) / 16), dim3(512), stream, a);   // 16 rays per workgroup
+      RDRF_TRY(launch_ray_scan_bwd(a, stream));
       RDRF_LAUNCH("dyn_heads_bwd", (k_dyn_density_bwd<0, false, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
     } else RDRF_LAUNCH("dyn_heads_bwd", (k_dyn_density_bwd<0, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
     const bool has_d = g_sigma != nullptr || g_weight != nullptr, has_b = g_blending != nullptr;
@@ -1258,4 +1268,25 @@ int warp_bwd_on_rows(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int N,
   D.n = 0;
   add_density_phase_dw(D, grows1, act1, G, (int)t1, false, false, true, false);
   return dw_launch(D, stream, "dw_warp");
+}
+
+// ------------------------------------------------------------------------------------------------
+// the ray scan backward alone on caller-owned arrays (rdrf_bwd_host.hpp; rdrf_selftest_ray_scan_bwd)
+// ------------------------------------------------------------------------------------------------
+int ray_scan_bwd_on_arrays(int width, const float* rays, const float* z, const uint8_t* valid, const float* raw, int N, int S,
+                           int act, float density_shift, float distance_scale, int ray_type, const float* g_weight,
+                           const float* g_sigma, const float* g_dists, float* out, float* g_z, float* g_rays, hipStream_t stream) {
+  BwdArgs a;
+  memset(&a, 0, sizeof(a));
+  a.rays = rays; a.z = z; a.valid = valid; a.N = N; a.S = S;
+  a.distance_scale = distance_scale; a.density_shift = density_shift; a.act = act; a.ray_type = ray_type;
+  a.g_weight = g_weight; a.g_sigma = g_sigma; a.g_dists = g_dists; a.g_z = g_z; a.g_rays = g_rays;
+  a.sp.raw = const_cast<float*>(raw);
+  if (width == 32) {
+    a.gsig = out;
+    return launch_ray_scan_bwd(a, stream);
+  }
+  StaticW w;
+  memset(&w, 0, sizeof(w));   // k_static_density_bwd reads no weight
+  return launch_static_density_bwd(a, w, out, stream);
 }

@@ -138,6 +138,13 @@ int warp_bwd_on_rows(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int N,
                      float* dxw, float* dxn, const float* g_xyz_prime, const RdrfDynamicParams* G, float* g_xyz, float* dtout,
                      float* dtp, float* pk, uint8_t* valid, hipStream_t stream);
 
+// The ray scan backward alone on arrays the caller supplies (rdrf_selftest_ray_scan_bwd), launched as the entry points launch
+// it: width 32 k_ray_scan_bwd (raw [N][S][2], out = gsig [N][S]), width 64 k_static_density_bwd (raw [N][S], out = gf rows
+// [N][32 ceil(S / 32)]).  Cotangents and g_z / g_rays nullable.
+int ray_scan_bwd_on_arrays(int width, const float* rays, const float* z, const uint8_t* valid, const float* raw, int N, int S,
+                           int act, float density_shift, float distance_scale, int ray_type, const float* g_weight,
+                           const float* g_sigma, const float* g_dists, float* out, float* g_z, float* g_rays, hipStream_t stream);
+
 // ------------------------------------------------------------------------------------------------
 // backward-data kernels with the weight gradients formed in the kernel (rdrf_bwd_fused.hip)
 // ------------------------------------------------------------------------------------------------

@@ -298,6 +298,12 @@ extern "C" int rdrf_static_fwd(const RdrfStaticParams* P, const RdrfFieldCfg* cf
                             stream_, 0);
 }
 
+// the per-ray scan of the flat density phase (rdrf_render_host.hpp): rdrf_dynamic_fwd_ex below and rdrf_selftest_ray_scan
+int launch_ray_scan(const FieldArgs& a, hipStream_t stream) {
+  RDRF_LAUNCH("ray_scan", k_ray_scan, dim3((a.N + 15) / 16), dim3(512), stream, a);
+  return 0;
+}
+
 extern "C" int rdrf_dynamic_fwd_ex(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg,
                                    const float* rays, const float* ts, const float* xyz,
                                    const float* z, const uint8_t* valid, int N, int S,
@@ -333,7 +339,7 @@ extern "C" int rdrf_dynamic_fwd_ex(const RdrfDynamicParams* P, const RdrfFieldCf
   if (flat) {
     if (saved != nullptr) RDRF_LAUNCH("dyn_density", k_dyn_density_flat<true>, dim3(g3.grid), dim3(g3.block), stream, a, w);
     else RDRF_LAUNCH("dyn_density", k_dyn_density_flat<false>, dim3(g3.grid), dim3(g3.block), stream, a, w);
-    RDRF_LAUNCH("ray_scan", k_ray_scan, dim3((N + 15) / 16), dim3(512), stream, a);
+    RDRF_TRY(launch_ray_scan(a, stream));
   } else if (saved != nullptr) RDRF_LAUNCH("dyn_density", (k_dyn_density<false, true>), dim3(g1.grid), dim3(g1.block), stream, a, w);
   else RDRF_LAUNCH("dyn_density", (k_dyn_density<false, false>), dim3(g1.grid), dim3(g1.block), stream, a, w);
 #ifdef RDRF_DETERMINISTIC

@@ -16,6 +16,12 @@ void fill_common(FieldArgs& a, const RdrfFieldCfg* cfg, const float* rays, const
 // pack area, counter, tout, xw and list out of a rdrf_forward_workspace_bytes(N, S) slice; with `saved`, the training buffers
 int ws_carve_fwd(FieldArgs& a, void* ws, size_t ws_bytes, int N, int S, void* saved, size_t saved_bytes, int dynamic);
 int fwd_dynq();   // FieldArgs::dynq of the forward launches
+// The per-ray scans over stored sigmas with their production launch geometry, each in the unit that defines its kernel:
+// k_ray_scan (rdrf_fwd.hip; 32 wide, 16 rays per workgroup) and k_static_scan (rdrf_render_masked.hip; 64 wide, 4 rays per
+// workgroup).  They read a.rays, z, sigma, N, S, ray_type, distance_scale, weight_thres and write a.weight, dists, list, counter
+// (added to) and rgb (zero fill; nullable).  The entry points launch them; rdrf_selftest_ray_scan does on caller-owned arrays.
+int launch_ray_scan(const FieldArgs& a, hipStream_t stream);
+int launch_static_scan(const FieldArgs& a, hipStream_t stream);
 
 struct RenderCall {
   const RdrfStaticParams* PS;

@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void k_static_scan(FieldArgs a) {
       const int j = j0 + lane;
       const bool act = ray && j < a.S;
       const int idx = n * a.S + (act ? j : 0);
-      if (ray) zero_rgb_round<64>(a.rgb, n, a.S, j0, lane);
+      if (ray && a.rgb != nullptr) zero_rgb_round<64>(a.rgb, n, a.S, j0, lane);   // (nullable, as in static_density_body)
       const float sigma = act ? a.sigma[idx] : 0.0f;
       float ds;
       const float wt = weight_round<64>(a, sigma, act, idx, j, lane, nrm, carry, ds);
@@ -218,6 +218,10 @@ int launch_static_density_list(const FieldArgs& as, const StaticW& wst, const in
               list_s, ctr, kept);
   return 0;
 }
+int launch_static_scan(const FieldArgs& as, hipStream_t stream) {
+  RDRF_LAUNCH("static_scan", k_static_scan, dim3((as.N + 3) / 4), dim3(256), stream, as);   // 4 rays per workgroup: one list append
+  return 0;
+}
 int launch_dyn_density_list(const FieldArgs& ad, const DynW& wdy, const int* list_d, const int* count, hipStream_t stream) {
   const Geo g3 = geo_for_tiles(ad.N, ad.S);
   RDRF_LAUNCH("dyn_density_list", k_dyn_density_list, dim3(g3.grid), dim3(g3.block), stream, ad, wdy, list_d, count);
@@ -294,7 +298,7 @@ extern "C" int rdrf_render_masked_fwd(const RdrfStaticParams* PS, const RdrfFiel
   RDRF_LAUNCH("mask_keep", k_keep, dim3((ns + 256 * KEEP_ROUNDS - 1) / (256 * KEEP_ROUNDS)), dim3(256), stream, k);
 
   RDRF_TRY(launch_static_density_list(as, wst, m.list_s, m.ctr, (long long*)kept, stream));
-  RDRF_LAUNCH("static_scan", k_static_scan, dim3((N + 3) / 4), dim3(256), stream, as);   // 4 rays per workgroup: one list append
+  RDRF_TRY(launch_static_scan(as, stream));
   const Geo g3 = geo_for_tiles(N, S);
   RDRF_TRY(launch_dyn_density_list(ad, wdy, m.list_d, m.ctr + CTR_KEPT_D, stream));
   RDRF_LAUNCH("ray_scan", k_masked_ray_scan, dim3((N + 15) / 16), dim3(512), stream, ad);

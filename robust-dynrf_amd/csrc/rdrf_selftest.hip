@@ -16,11 +16,15 @@
 //
 // rdrf_selftest_gather / rdrf_selftest_encodings: the forward VM gather and the positional encodings through the device functions
 // of the forward kernels; reference: tests/_gather_prim.py.
+//
+// rdrf_selftest_ray_scan / rdrf_selftest_ray_scan_bwd (host code only): the per-field ray scan, forward and backward at both
+// widths, through the entry points' launchers on arrays the caller supplies; reference: tests/_scan_prim.py.
 #include <vector>
 
 #include "rdrf_fwd_dev.hpp"
 #include "rdrf_bwd_dev.hpp"
 #include "rdrf_bwd_host.hpp"
+#include "rdrf_render_host.hpp"
 #include "rdrf_sort_dev.hpp"
 
 namespace {
@@ -827,6 +831,44 @@ extern "C" int rdrf_selftest_encodings(const float* xn, const float* t, int M, f
   RDRF_CHECK(xn && t && x0_out && x1_out && M > 0 && M <= (1 << 24), -1, "selftest_encodings: bad arguments");
   RDRF_LAUNCH("selftest_encodings", k_st_encodings, dim3((M + 31) / 32), dim3(64), stream, xn, t, M, x0_out, x1_out);
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// rdrf_selftest_ray_scan / rdrf_selftest_ray_scan_bwd (host code only): the per-field ray scan on caller-owned arrays, through the
+// launchers of the entry points (rdrf_render_host.hpp, rdrf_bwd_host.hpp); reference: tests/_scan_prim.py
+// ------------------------------------------------------------------------------------------------
+extern "C" int rdrf_selftest_ray_scan(int width, const float* rays, const float* z, const float* sigma, int N, int S, int ray_type,
+                                      float distance_scale, float weight_thres, float* weight, float* dists, int* list,
+                                      int* counter, float* rgb, rdrf_stream_t stream_) {
+  RDRF_CHECK(width == 32 || width == 64, -1, "selftest_ray_scan: width is 32 (k_ray_scan) or 64 (k_static_scan), got %d", width);
+  if (N == 0) return 0;   // empty batch: a no-op
+  RDRF_CHECK(rays && z && sigma && weight && dists && list && counter && N > 0, -1, "selftest_ray_scan: bad arguments");
+  RDRF_CHECK(S >= 1 && S <= 4096, -1, "selftest_ray_scan: S in 1 .. 4096 (got %d)", S);
+  RDRF_CHECK(ray_type >= RDRF_RAY_NDC && ray_type <= RDRF_RAY_OTHER, -1, "selftest_ray_scan: unknown ray type %d", ray_type);
+  RDRF_CHECK((size_t)N * S * 3 < (size_t)INT32_MAX, -1, "selftest_ray_scan: N * S * 3 must stay below 2^31");
+  FieldArgs a;
+  memset(&a, 0, sizeof(a));
+  a.rays = rays; a.z = z; a.N = N; a.S = S;
+  a.distance_scale = distance_scale; a.weight_thres = weight_thres; a.ray_type = ray_type;
+  a.sigma = const_cast<float*>(sigma); a.weight = weight; a.dists = dists; a.rgb = rgb;
+  a.list = list; a.counter = counter;
+  return width == 32 ? launch_ray_scan(a, (hipStream_t)stream_) : launch_static_scan(a, (hipStream_t)stream_);
+}
+
+extern "C" int rdrf_selftest_ray_scan_bwd(int width, const float* rays, const float* z, const uint8_t* valid, const float* raw, int N,
+                                          int S, int act, float density_shift, float distance_scale, int ray_type,
+                                          const float* g_weight, const float* g_sigma, const float* g_dists, float* out, float* g_z,
+                                          float* g_rays, rdrf_stream_t stream_) {
+  RDRF_CHECK(width == 32 || width == 64, -1, "selftest_ray_scan_bwd: width is 32 (k_ray_scan_bwd) or 64 (k_static_density_bwd), got %d",
+             width);
+  if (N == 0) return 0;   // empty batch: a no-op
+  RDRF_CHECK(rays && z && valid && raw && out && N > 0, -1, "selftest_ray_scan_bwd: bad arguments");
+  RDRF_CHECK(S >= 1 && S <= 4096, -1, "selftest_ray_scan_bwd: S in 1 .. 4096, the carry slots of the kernels (got %d)", S);
+  RDRF_CHECK(act == RDRF_ACT_RELU || act == RDRF_ACT_SOFTPLUS, -1, "selftest_ray_scan_bwd: unknown activation %d", act);
+  RDRF_CHECK(ray_type >= RDRF_RAY_NDC && ray_type <= RDRF_RAY_OTHER, -1, "selftest_ray_scan_bwd: unknown ray type %d", ray_type);
+  RDRF_CHECK((size_t)N * (S + 31) * 3 < (size_t)INT32_MAX, -1, "selftest_ray_scan_bwd: N * S * 3 must stay below 2^31");
+  return ray_scan_bwd_on_arrays(width, rays, z, valid, raw, N, S, act, density_shift, distance_scale, ray_type, g_weight, g_sigma,
+                                g_dists, out, g_z, g_rays, (hipStream_t)stream_);
 }
 
 // ------------------------------------------------------------------------------------------------
