@@ -1010,6 +1010,32 @@ int rdrf_query_points(const void* params, int dynamic, const RdrfFieldCfg* cfg, 
                       int t_per_point, const float* viewdirs, float* sigma, float* rgb, float* blending, float* xyz_prime,
                       void* ws, size_t ws_bytes, rdrf_stream_t stream);
 
+/* ---- mesh simplification: vertex clustering of an indexed triangle mesh on the device ----------------------------------------
+ * verts [V][3] and faces [F][3] (int vertex indices) are device arrays; origin, cell and n are host arrays: a lattice of
+ * n[0] x n[1] x n[2] cells of size cell[] from origin[].  The cell of a vertex is, per axis,
+ * c = clamp(floor((v - origin) / cell), 0, n - 1), formed in fp32 without contraction; a coordinate for which
+ * (v - origin) / cell >= 0 is false (NaN among them) goes to cell 0.  The vertices of one cell form a cluster; clusters ascend
+ * by key (c0 n[1] + c1) n[2] + c2, their members by original index.  A cluster's position is the mean of its members: fp64 sums
+ * in member order, one fp64 division, one rounding to fp32.  normals (nullable): summed in fp64, scaled by the largest component
+ * and normalised in fp64, rounded once; a zero sum stays zero.  colors (nullable, [V][3] bytes): per channel
+ * floor((2 sum + k) / (2 k)), the mean rounded half up.  A face is mapped through the clusters and kept iff its three clusters
+ * differ (a face with an index outside [0, V) is dropped); kept faces keep their order and their winding.  Duplicate faces are
+ * not merged.  drop_unreferenced: only the clusters that a kept face references are emitted (renumbered in ascending key order);
+ * 0: every cluster.  No atomics on global memory; the same bits from every build.
+ * rdrf_simplify_count writes counts = {V', F'} (device) and, where remap is given, remap[v] = the output index of vertex v's
+ * cluster (-1: dropped); the caller reads the two counts, allocates, and hands the same ws to rdrf_simplify_emit with the same
+ * V and F.  V == 0 or F == 0: counts = {0, 0}, nothing else is written.  Refused before any launch (rdrf_simplify_ws_bytes
+ * returns 0 for them): n below 1, n[0] n[1] n[2] >= 2^31, V or F >= 2^31 (the vertex indices are ints and the lane index
+ * blockIdx.x * 256 + threadIdx.x of the kernels is 32-bit); by rdrf_simplify_count also a cell size that is not positive and
+ * finite.  The size function does not carry the *_workspace_bytes suffix for the reason given at rdrf_render_masked_ws_bytes. */
+size_t rdrf_simplify_ws_bytes(int64_t V, int64_t F, const int n[3]);
+int rdrf_simplify_count(const float* verts, int64_t V, const int* faces, int64_t F, const float origin[3], const float cell[3],
+                        const int n[3], int drop_unreferenced, void* ws, size_t ws_bytes, int64_t* counts, int* remap,
+                        rdrf_stream_t stream);
+int rdrf_simplify_emit(const float* verts, const float* normals, const unsigned char* colors, int64_t V, const int* faces,
+                       int64_t F, const void* ws, float* verts_out, float* normals_out, unsigned char* colors_out, int* faces_out,
+                       int64_t nv, int64_t nf, rdrf_stream_t stream);
+
 /* timing hook: average device time (ms) of the dominant kernel launches recorded with HIP events
  * since the last reset; used by bench.py for the roofline figure. */
 void rdrf_prof_reset(void);

@@ -35,11 +35,12 @@ def _cap(volume, aabb):
 
 
 @torch.no_grad()
-def extract_isosurface(volume, level, aabb, t_index=0, normals=False, flip=False, cap=False):
+def extract_isosurface(volume, level, aabb, t_index=0, normals=False, flip=False, cap=False, simplify=None):
     """volume: device tensor [G0,G1,G2] or [G0,G1,G2,T] (slice t_index is meshed, in place) -> (verts [nv,3] float32,
     faces [nf,3] int32[, normals [nv,3]]).  A sample is inside iff v >= level; verts ascend in (lattice point, edge kind),
     faces in (cube, tetrahedron, triangle).  cap=True closes the surface where it reaches the volume boundary.
-    One host read (the two counts) between the counting and the emitting launches; an empty mesh skips the second."""
+    One host read (the two counts) between the counting and the emitting launches; an empty mesh skips the second.
+    simplify=K: the mesh is then clustered (simplify_mesh) on the lattice simplify_lattice(aabb, volume.shape, K, cap)."""
     L.require_device(volume)
     if volume.dim() not in (3, 4):
         raise L.RdrfError(f"extract_isosurface: the volume must be [G0,G1,G2] or [G0,G1,G2,T], not {tuple(volume.shape)}")
@@ -67,7 +68,108 @@ def extract_isosurface(volume, level, aabb, t_index=0, normals=False, flip=False
         box_c = (C.c_float * 6)(*[float(v) for v in box])
         L.check(L.lib.rdrf_iso_emit(L.ptr(vol), G0, G1, G2, T, t_index, float(level), box_c, int(bool(flip)), L.ptr(ws),
                                     L.ptr(verts), L.ptr(nrm), L.ptr(faces), nv, nf, stream), "rdrf_iso_emit")
+    if simplify is not None:
+        return _simplify(verts, faces, simplify_lattice(box, (G0, G1, G2), simplify), nrm, None, True, False, "extract_isosurface")
     return (verts, faces, nrm) if normals else (verts, faces)
+
+
+# ---- mesh simplification: vertex clustering on the kernels of csrc/rdrf_simplify.hip -----------------------------------------
+def simplify_lattice(aabb, shape, K, cap=False):
+    """the clustering lattice of simplify=K for a meshed volume of `shape` = (G0, G1, G2) samples over aabb (cap=True: the
+    volume and the box that cap=True meshes, one sample and one cell larger on every side): clusters K lattice cells wide from
+    aabb_min, cell_a = K spacing_a, n_a = ceil((G_a - 1) / K).  Returns dict(aabb, cell, grid), the arguments of simplify_mesh."""
+    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+        raise L.RdrfError(f"simplify must be a whole number of lattice cells >= 1, not {K!r}")
+    box = _aabb6(aabb)
+    G = [int(g) for g in shape[:3]]
+    if cap:
+        a = box.double().view(2, 3)
+        h = (a[1] - a[0]) / torch.tensor([g - 1 for g in G], dtype=torch.float64)
+        box = torch.stack((a[0] - h, a[1] + h)).float().reshape(-1)
+        G = [g + 2 for g in G]
+    a = box.double().view(2, 3)
+    cell = [float(K * (a[1, d] - a[0, d]) / (G[d] - 1)) for d in range(3)]
+    return {"aabb": box, "cell": cell, "grid": [-(-(G[d] - 1) // K) for d in range(3)]}
+
+
+def _simplify(verts, faces, lattice, normals, colors, drop_unreferenced, return_remap, who):
+    """the two native calls on a resolved lattice dict(aabb, cell, grid) -> (verts, faces[, normals][, colors][, remap])"""
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    dev, stream = verts.device, L.stream_of(verts)
+    origin = (C.c_float * 3)(*[float(v) for v in lattice["aabb"][:3]])
+    cell = (C.c_float * 3)(*[float(v) for v in lattice["cell"]])
+    n = (C.c_int * 3)(*[int(v) for v in lattice["grid"]])
+    nbytes = L.lib.rdrf_simplify_ws_bytes(V, F, n)
+    ws = L.workspace(dev, nbytes) if nbytes else None   # 0: a refused shape, which rdrf_simplify_count reports by name
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    remap = torch.full((V,), -1, dtype=torch.int32, device=dev) if return_remap else None
+    L.check(L.lib.rdrf_simplify_count(L.ptr(verts), V, L.ptr(faces), F, origin, cell, n, int(bool(drop_unreferenced)), L.ptr(ws),
+                                      0 if ws is None else ws.numel(), L.ptr(counts), L.ptr(remap), stream), f"{who}: rdrf_simplify_count")
+    nv, nf = (int(v) for v in counts.cpu().tolist())   # the one sync
+    out_v = torch.empty(nv, 3, dtype=torch.float32, device=dev)
+    out_f = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+    out_n = torch.empty(nv, 3, dtype=torch.float32, device=dev) if normals is not None else None
+    out_c = torch.empty(nv, 3, dtype=torch.uint8, device=dev) if colors is not None else None
+    if nv > 0 or nf > 0:
+        L.check(L.lib.rdrf_simplify_emit(L.ptr(verts), L.ptr(normals), L.ptr(colors), V, L.ptr(faces), F, L.ptr(ws), L.ptr(out_v),
+                                         L.ptr(out_n), L.ptr(out_c), L.ptr(out_f), nv, nf, stream), f"{who}: rdrf_simplify_emit")
+    out = [out_v, out_f] + [o for o in (out_n, out_c, remap) if o is not None]
+    return tuple(out)
+
+
+@torch.no_grad()
+def simplify_mesh(verts, faces, cell=None, grid=None, aabb=None, normals=None, colors=None, drop_unreferenced=True,
+                  return_remap=False):
+    """Vertex clustering of a device mesh: verts [V,3] float32, faces [F,3] int32 -> (verts, faces[, normals][, colors][, remap]).
+    The lattice starts at aabb_min (aabb=None: the box of the vertices, one host read): `cell` (a scalar or three numbers) gives
+    n = ceil(extent / cell) cells per axis, `grid` (three counts) gives cell = extent / grid; both together are used as they
+    are (what simplify_lattice returns).  A cluster's vertex is the mean of its members, its normal the normalised sum, its
+    colour ([V,3] uint8) the mean rounded half up; a face survives iff its three vertices land in different clusters, in its
+    old place in the order and with its winding; duplicate faces are not merged.  drop_unreferenced=False keeps the clusters
+    no surviving face uses.  remap [V] int32: the new index of every old vertex, -1 where its cluster was dropped."""
+    who = "simplify_mesh"
+    L.require_device(verts, faces, normals, colors)
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise L.RdrfError(f"{who}: verts must be [V,3] float32, not {tuple(verts.shape)} {verts.dtype}")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise L.RdrfError(f"{who}: faces must be [F,3] int32, not {tuple(faces.shape)} {faces.dtype}")
+    if normals is not None and (normals.shape != verts.shape or normals.dtype != torch.float32):
+        raise L.RdrfError(f"{who}: normals must be [V,3] float32 like verts, not {tuple(normals.shape)} {normals.dtype}")
+    if colors is not None and (colors.shape != verts.shape or colors.dtype != torch.uint8):
+        raise L.RdrfError(f"{who}: colors must be [V,3] uint8, not {tuple(colors.shape)} {colors.dtype}")
+    if cell is None and grid is None:
+        raise L.RdrfError(f"{who}: give cell (the cluster size) or grid (the cell counts over the aabb)")
+    verts, faces = verts.contiguous(), faces.contiguous()
+    normals = None if normals is None else normals.contiguous()
+    colors = None if colors is None else colors.contiguous()
+    if aabb is None:
+        if verts.shape[0] == 0:
+            box = torch.tensor([0.0, 0.0, 0.0, 1.0, 1.0, 1.0])
+        else:
+            box = torch.cat((verts.amin(0), verts.amax(0))).cpu()
+    else:
+        box = _aabb6(aabb)
+    ext = (box[3:].double() - box[:3].double()).tolist()
+    if cell is not None:
+        cell = [float(v) for v in torch.as_tensor(cell, dtype=torch.float64).reshape(-1).tolist()]
+        if len(cell) not in (1, 3):
+            raise L.RdrfError(f"{who}: cell must be a scalar or three numbers, not {len(cell)}")
+        cell = cell * 3 if len(cell) == 1 else cell
+    if grid is not None:
+        grid = [int(v) for v in grid]
+        if len(grid) != 3:
+            raise L.RdrfError(f"{who}: grid must be three counts, not {len(grid)}")
+    if cell is None:
+        cell = [ext[d] / grid[d] if grid[d] > 0 else 0.0 for d in range(3)]
+    elif grid is None:
+        if not all(c > 0.0 and c == c and c != float("inf") for c in cell):
+            raise L.RdrfError(f"{who}: cell sizes must be positive and finite, not {cell}")
+        if not all(e == e and abs(e) != float("inf") for e in ext):
+            raise L.RdrfError(f"{who}: the box of the vertices is not finite ({box.tolist()}): pass aabb")
+        grid = [max(1, int(-(-ext[d] // cell[d]))) for d in range(3)]
+        if grid[0] * grid[1] * grid[2] >= 2 ** 31:
+            raise L.RdrfError(f"{who}: cell {cell} over the extent {ext} gives {grid[0]} x {grid[1]} x {grid[2]} cells, the keys are below 2^31")
+    return _simplify(verts, faces, {"aabb": box, "cell": cell, "grid": grid}, normals, colors, drop_unreferenced, return_remap, who)
 
 
 def ndc_to_world(pts, H, W, focal):
@@ -135,30 +237,44 @@ def _to_world(field, verts, faces, space, H, W, focal):
     return world, face_vertex_normals(world, faces)
 
 
-def _mesh_of_slice(field, alpha, k, level, space, H, W, focal, kw):
+def _mesh_of_slice(field, alpha, k, level, space, H, W, focal, kw, color=None):
+    """color (colored_mesh): field-space vertices -> [nv,3] uint8, taken on the unsimplified mesh; clustering (simplify=K)
+    comes after it and before the mapping to world space"""
     want_normals = bool(kw.get("normals", False))
+    kw = dict(kw)
+    K = kw.pop("simplify", None)
     out = extract_isosurface(alpha, level, field.aabb, t_index=k, **kw)
-    verts, faces = out[0], out[1]
+    verts, faces, nrm = out[0], out[1], (out[2] if want_normals else None)
+    colors = None if color is None else color(verts)
+    if K is not None:
+        lattice = simplify_lattice(field.aabb, alpha.shape, K, bool(kw.get("cap", False)))
+        out = _simplify(verts, faces, lattice, nrm, colors, True, False, "field_mesh")
+        verts, faces = out[0], out[1]
+        nrm = out[2] if want_normals else None
+        colors = None if color is None else out[-1]
     world, wn = _to_world(field, verts, faces, space, H, W, focal)
-    if not want_normals:
-        return world, faces
-    return world, faces, (out[2] if wn is None else wn)
+    mesh = (world, faces) if not want_normals else (world, faces, (nrm if wn is None else wn))
+    return mesh if color is None else mesh + (colors,)
 
 
 def _check_kw(kw):
     if "colors" in kw:
         raise L.RdrfError("field_mesh / mesh_sequence take no colors=: colours come from colored_mesh, vertex_colors and "
                           "export_mesh(..., color_view=) (write_ply takes colours a caller computed)")
-    bad = set(kw) - {"normals", "flip", "cap"}
+    bad = set(kw) - {"normals", "flip", "cap", "simplify"}
     if bad:
         raise TypeError(f"unexpected arguments {sorted(bad)}")
+    K = kw.get("simplify")
+    if K is not None and (isinstance(K, bool) or not isinstance(K, int) or K < 1):
+        raise L.RdrfError(f"simplify must be a whole number of lattice cells >= 1, not {K!r}")
 
 
 @torch.no_grad()
 def field_mesh(field, t=None, level=0.005, gridSize=None, space="field", H=None, W=None, focal=None, **kw):
     """getDenseAlpha(gridSize, times=[t]) -> extract_isosurface.  t=None only for the static field (its alpha does not
     depend on the time).  space="world": the vertices of an ndc field through NDC2world (needs H, W, focal); normals are then
-    recomputed from the transformed faces.  kw: normals, flip, cap."""
+    recomputed from the transformed faces.  kw: normals, flip, cap, simplify (K: vertex clustering K lattice cells wide, in
+    field space)."""
     _check_kw(kw)
     if t is None:
         if field.DYNAMIC:
@@ -200,18 +316,19 @@ def vertex_colors(field, verts, t=None, view=(0, 0, 1)):
 
 @torch.no_grad()
 def colored_mesh(field, t=None, level=0.005, gridSize=None, view=(0, 0, 1), space="field", H=None, W=None, focal=None,
-                 normals=False, flip=False, cap=False):
+                 normals=False, flip=False, cap=False, simplify=None):
     """field_mesh with colours: (verts, faces[, normals], colors [nv,3] uint8).  The colours are those of the field-space
-    vertices (vertex_colors), taken before any NDC2world mapping, so space="world" moves the vertices and keeps the colours."""
+    vertices (vertex_colors), taken before any NDC2world mapping, so space="world" moves the vertices and keeps the colours.
+    simplify=K clusters the coloured mesh: a cluster's colour is the mean of its members' colours."""
     if space not in ("field", "world"):
         raise L.RdrfError(f"space must be \"field\" or \"world\", not {space!r}")
-    out = field_mesh(field, t, level, gridSize, "field", normals=normals, flip=flip, cap=cap)
-    verts, faces = out[0], out[1]
-    colors = vertex_colors(field, verts, t, view)
-    world, wn = _to_world(field, verts, faces, space, H, W, focal)
-    if not normals:
-        return world, faces, colors
-    return world, faces, (out[2] if wn is None else wn), colors
+    if t is None and field.DYNAMIC:
+        raise L.RdrfError("field_mesh: the dynamic field's alpha depends on the time: pass t")
+    alpha, _ = field.getDenseAlpha(gridSize, times=[0.0 if t is None else float(t)])
+    kw = dict(normals=normals, flip=flip, cap=cap)
+    if simplify is not None:
+        kw["simplify"] = simplify
+    return _mesh_of_slice(field, alpha, 0, level, space, H, W, focal, kw, color=lambda verts: vertex_colors(field, verts, t, view))
 
 
 # ---- PLY (binary little-endian), numpy only ----------------------------------------------------------------------------
@@ -312,7 +429,8 @@ def load_field(path, device="cuda"):
 def export_mesh(field_or_ckpt_path, ply_path, t=None, level=0.005, gridSize=None, space="field", H=None, W=None, focal=None,
                 device="cuda", color_view=None, **kw):
     """train.py:107-118: the field (or the checkpoint at a path) -> dense alpha -> isosurface -> PLY.  Returns the mesh.
-    color_view: a view direction; the PLY then carries the vertex colours of colored_mesh, which come last in the mesh."""
+    color_view: a view direction; the PLY then carries the vertex colours of colored_mesh, which come last in the mesh.
+    kw: normals, flip, cap, simplify."""
     field = load_field(field_or_ckpt_path, device) if isinstance(field_or_ckpt_path, (str, bytes)) or hasattr(
         field_or_ckpt_path, "__fspath__") else field_or_ckpt_path
     if color_view is None:

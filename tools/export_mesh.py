@@ -2,10 +2,11 @@
 """Checkpoint -> isosurface mesh (the reference's --export_mesh, train.py:107-118), on the device.
 
     python tools/export_mesh.py ckpt.th out.ply [--time T] [--level L] [--grid G0 G1 G2] [--cap] [--normals] [--flip]
-                                                [--world H W focal] [--color-view X Y Z]
+                                                [--world H W focal] [--color-view X Y Z] [--simplify K]
 
 --time is required for a dynamic field (times run over [-1, 1]); --world maps the vertices of an ndc field to world space;
---color-view writes vertex colours: the field's rgb at the field-space vertices seen along the direction X Y Z (used as given)."""
+--color-view writes vertex colours: the field's rgb at the field-space vertices seen along the direction X Y Z (used as given);
+--simplify K clusters the vertices K lattice cells wide (mean position, normal and colour per cluster; degenerate faces dropped)."""
 import argparse
 import os
 import sys
@@ -25,9 +26,12 @@ def main():
     ap.add_argument("--flip", action="store_true")
     ap.add_argument("--world", type=float, nargs=3, default=None, metavar=("H", "W", "focal"))
     ap.add_argument("--color-view", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
+    ap.add_argument("--simplify", type=int, default=None, metavar="K")
     a = ap.parse_args()
     import rodynrf
     kw = dict(cap=a.cap, normals=a.normals, flip=a.flip)
+    if a.simplify is not None:
+        kw.update(simplify=a.simplify)
     if a.world is not None:
         kw.update(space="world", H=a.world[0], W=a.world[1], focal=a.world[2])
     if a.color_view is not None:
