@@ -918,6 +918,42 @@ int rdrf_selftest_ray_scan_bwd(int width, const float* rays, const float* z, con
                                const float* g_sigma, const float* g_dists, float* out, float* g_z, float* g_rays,
                                rdrf_stream_t stream);
 
+/* The heads' backward of the dynamic field's density phase alone (what the backward entry points run between the ray scan
+ * backward and the density / blending scatter), on rows the caller supplies, with the entry points' launch geometry.
+ * mode RDRF_HEADS_FLAT: k_dyn_density_bwd<0, false, true> on the T = ceil(N S / 32) flat tiles of [N][S], as rdrf_dynamic_bwd runs
+ * it.  raw [N S][2] the heads' raw outputs, valid [N S], g_sigma [N S] the TOTAL d(sigma) of every sample (the ray scan backward's
+ * output), g_blending [N S] nullable d(blending); live_d: the density head receives a gradient.  dfs (nullable) [N S][144]: the
+ * d(feature) results go there as sample-major records instead of into the d(feature) rows.  The gradients of the two heads' second
+ * layers (dw2, db2, bw2, bb2 of grads) are ADDED into.
+ * mode RDRF_HEADS_FEAT: k_dyn_density_bwd<0, true> on T = ceil(N / 32) tiles of N points (S is ignored), as
+ * rdrf_dynamic_features_bwd runs it.  g_sigma, g_blending [N]: nullable gradients of the RAW head outputs; raw, valid and live_d
+ * are not read, dfs must be NULL, grads is left alone.
+ * Both: cfg gives act and density_shift; act1 [T][576][32] saved density-phase rows (the two heads' hidden rows are read), grows1
+ * [T][544][32] gradient rows, pre-filled by a caller that compares them whole: a live head writes its dz and d(feature) rows, the
+ * d(X0) rows and the small-layer dz rows 3 and 4 are always written.  ws: 16-byte aligned scratch of
+ * rdrf_selftest_heads_bwd_workspace_bytes(N, S).  N = 0 is a no-op; -1 on bad arguments, -3 when rows, records or workspace are too
+ * small.  rdrf_selftest_heads_describe (host only): the launch geometry at this shape and the row offsets the other describe
+ * functions do not report, as ints (layout: csrc/rdrf_selftest.hip); returns the number written. */
+#define RDRF_HEADS_FLAT 0
+#define RDRF_HEADS_FEAT 1
+size_t rdrf_selftest_heads_bwd_workspace_bytes(int N, int S);
+int rdrf_selftest_heads_describe(int mode, int N, int S, int* out, int cap);
+int rdrf_selftest_heads_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int mode, int N, int S, const float* act1,
+                            size_t act1_floats, const float* raw, const uint8_t* valid, const float* g_sigma,
+                            const float* g_blending, int live_d, float* grows1, size_t grows1_floats, float* dfs, size_t dfs_floats,
+                            const RdrfDynamicParams* grads, void* ws, size_t ws_bytes, rdrf_stream_t stream);
+
+/* The dynamic field's time branch alone, through the launchers of the entry points.  rdrf_selftest_time_branch: ts [N] -> tout
+ * [N][32] = W2 relu(W1 [t, sin(2^f t), cos(2^f t), f = 0..7] + b1) + b2 in columns 0..29, zero in columns 30 and 31 (k_time_branch,
+ * 8 rays per workgroup); zero64: nullable block of 64 ints, cleared on the way.  rdrf_selftest_time_branch_bwd: dtout [N][32] and the
+ * nullable partial records dtp [ceil(N S / 32)][2][32] of the flat tiles (dtp_floats long) -> the gradients of time_layer1 /
+ * time_layer2 (l1w, l1b, l2w, l2b of grads), ADDED into (k_time_branch_bwd, 32 rays per workgroup).  With dtp a ray that crosses a
+ * tile edge takes its d(tout) from the records of its tiles and a ray inside one tile from dtout; without, every ray from dtout.
+ * N = 0 is a no-op; -1 on bad arguments, -3 when dtp is too small. */
+int rdrf_selftest_time_branch(const RdrfDynamicParams* P, const float* ts, int N, float* tout, int* zero64, rdrf_stream_t stream);
+int rdrf_selftest_time_branch_bwd(const RdrfDynamicParams* P, const float* ts, int N, int S, const float* dtout, const float* dtp,
+                                  size_t dtp_floats, const RdrfDynamicParams* grads, rdrf_stream_t stream);
+
 /* ---- alpha volumes and alpha-grid masks (models/tensorBase.py:42-79 AlphaGridMask, :565-702) ----------------------------
  * A mask is the occupancy grid of updateAlphaMask, bit-packed exactly as `save` (:465-469) stores it: the bool volume of
  * logical shape (G2, G1, G0, T) flattened in C order, eight entries per byte, first entry in the most significant bit

@@ -688,6 +688,25 @@ static int launch_ray_scan_bwd(const BwdArgs& a, hipStream_t stream) {
   RDRF_LAUNCH("ray_scan_bwd", k_ray_scan_bwd, dim3((a.N + 15) / 16), dim3(512), stream, a);   // 16 rays per workgroup
   return 0;
 }
+// The heads' kernel of the dynamic field's density phase (k_dyn_density_bwd<0>) with its launch geometry: the persistent one
+// over the flat 32-sample tiles of the [N * S] array (training), the rays (wave per ray) or the a.N pseudo rays of feature
+// mode.  The entry points below and heads_bwd_on_rows.
+enum HeadsForm { HEADS_RAY, HEADS_FLAT, HEADS_FEAT };
+long heads_bwd_units(int N, int S, int flat) { return flat ? ((long)N * S + 31) / 32 : (long)N; }
+static int launch_heads_bwd(const char* name, HeadsForm form, const BwdArgs& a, const DynW& w, const DynG& gw, hipStream_t stream) {
+  const Geo g = geo_for_units(heads_bwd_units(a.N, a.S, form == HEADS_FLAT));
+  if (form == HEADS_FLAT) RDRF_LAUNCH(name, (k_dyn_density_bwd<0, false, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+  else if (form == HEADS_FEAT) RDRF_LAUNCH(name, (k_dyn_density_bwd<0, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+  else RDRF_LAUNCH(name, (k_dyn_density_bwd<0, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+  return 0;
+}
+// k_time_branch_bwd over N rays (feature mode: points), TB_RPB rays per workgroup; dtp: the flat tiles' partial records or nullptr
+int launch_time_branch_bwd(const float* ts, const DynW& w, int N, const float* dtout, const float* dtp, int S,
+                           const RdrfDynamicParams* G, hipStream_t stream) {
+  RDRF_LAUNCH("time_branch_bwd", k_time_branch_bwd, dim3((N + TB_RPB - 1) / TB_RPB), dim3(128), stream, ts, w, N, dtout, dtp, S,
+              G->l1w, G->l1b, G->l2w, G->l2b);
+  return 0;
+}
 
 // `valid` of a feature-mode batch: 1 for the M points, 0 for the padding of the last 32-point tile
 static int pad_valid_tiles(uint8_t* valid, int M, size_t mp, hipStream_t stream) {
@@ -1019,10 +1038,8 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
     const Geo g = geo_for_units(flat ? (long)t1 : (long)N);
     const int smode = scatter_mode(ns, stream);
     a.dfs = smode != 0 ? b.dfs : nullptr;
-    if (flat) {
-      RDRF_TRY(launch_ray_scan_bwd(a, stream));
-      RDRF_LAUNCH("dyn_heads_bwd", (k_dyn_density_bwd<0, false, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
-    } else RDRF_LAUNCH("dyn_heads_bwd", (k_dyn_density_bwd<0, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+    if (flat) RDRF_TRY(launch_ray_scan_bwd(a, stream));
+    RDRF_TRY(launch_heads_bwd("dyn_heads_bwd", flat ? HEADS_FLAT : HEADS_RAY, a, w, gw, stream));
     const bool has_d = g_sigma != nullptr || g_weight != nullptr, has_b = g_blending != nullptr;
     if (smode != 0) {
       if (has_d || has_b) {
@@ -1042,8 +1059,7 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
     if (warp_fused) RDRF_TRY(launch_warp_fused(a, gw, G, (long)t1, stream));
     else if (flat) RDRF_LAUNCH("dyn_warp_bwd", (k_dyn_density_bwd<1, false, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
     else RDRF_LAUNCH("dyn_warp_bwd", (k_dyn_density_bwd<1, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
-    RDRF_LAUNCH("time_branch_bwd", k_time_branch_bwd, dim3((N + TB_RPB - 1) / TB_RPB), dim3(128), stream, ts, w,
-                N, b.dtout, flat ? (const float*)b.dtp : nullptr, S, G->l1w, G->l1b, G->l2w, G->l2b);
+    RDRF_TRY(launch_time_branch_bwd(ts, w, N, b.dtout, flat ? (const float*)b.dtp : nullptr, S, G, stream));
     add_density_phase_dw(D, b.grows1, a.sp.act1, G, (int)t1, has_d, has_b, a.small_dw != 0, warp_fused);
   }
   return dw_launch(D, stream, "dw_dyn");
@@ -1177,7 +1193,7 @@ extern "C" int rdrf_dynamic_features_bwd(const RdrfDynamicParams* P, const RdrfF
     RDRF_TRY(launch_scatter("feat_scatter_dyn_app", SCATTER_12_3_27, sa, (long)Np, stream));
     add_feat_dyn_app_dw(D, b.grows3, a.sp.act3, G, Np);
   }
-  RDRF_LAUNCH("feat_dyn_heads_bwd", (k_dyn_density_bwd<0, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+  RDRF_TRY(launch_heads_bwd("feat_dyn_heads_bwd", HEADS_FEAT, a, w, gw, stream));
   if (g_density != nullptr || g_blending != nullptr) {
     ScatterArgs sa;
     fill_scatter_common(sa, a);
@@ -1185,8 +1201,7 @@ extern "C" int rdrf_dynamic_features_bwd(const RdrfDynamicParams* P, const RdrfF
     RDRF_TRY(launch_scatter("feat_scatter_dyn_density", SCATTER_4_1_9, sa, (long)Np, stream));
   }
   RDRF_LAUNCH("feat_dyn_warp_bwd", (k_dyn_density_bwd<1, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
-  RDRF_LAUNCH("time_branch_bwd", k_time_branch_bwd, dim3((M + TB_RPB - 1) / TB_RPB), dim3(128), stream, t, w, M,
-              b.dtout, (const float*)nullptr, 32, G->l1w, G->l1b, G->l2w, G->l2b);
+  RDRF_TRY(launch_time_branch_bwd(t, w, M, b.dtout, nullptr, 32, G, stream));
   add_density_phase_dw(D, b.grows1, a.sp.act1, G, Np, g_density != nullptr, g_blending != nullptr);
   return dw_launch(D, stream, "feat_dw_dyn");
 }
@@ -1268,6 +1283,34 @@ int warp_bwd_on_rows(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int N,
   D.n = 0;
   add_density_phase_dw(D, grows1, act1, G, (int)t1, false, false, true, false);
   return dw_launch(D, stream, "dw_warp");
+}
+
+// ------------------------------------------------------------------------------------------------
+// the heads' backward alone on caller-supplied rows (rdrf_bwd_host.hpp; rdrf_selftest_heads_bwd)
+// ------------------------------------------------------------------------------------------------
+int heads_bwd_on_rows(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int feat, int N, int S, int M, const float* act1,
+                      const float* raw, const uint8_t* valid, const float* gsig, const float* g_sigma, const float* g_blending,
+                      int live_d, float* grows1, float* dfs, const RdrfDynamicParams* G, float* pk, hipStream_t stream) {
+  BwdArgs a;
+  fill_bwd_common(a, cfg, nullptr, nullptr, nullptr, nullptr, valid, N, S);
+  a.small_dw = 1;
+  a.sp.act1 = const_cast<float*>(act1);
+  a.sp.raw = const_cast<float*>(raw);
+  a.grows1 = grows1;
+  a.g_blending = g_blending;
+  if (feat) {
+    a.M = M; a.g_sigma = g_sigma;
+  } else {
+    a.gsig = const_cast<float*>(gsig); a.dfs = dfs;
+    a.g_sigma = live_d ? gsig : nullptr;   // never read on flat tiles: the kernel takes the head's liveness from it
+  }
+  DynW w;
+  fill_dyn_w(w, P);
+  DynG gw;
+  memset(&gw, 0, sizeof(gw));
+  gw.dw2 = G->dw2; gw.db2 = G->db2; gw.bw2 = G->bw2; gw.bb2 = G->bb2;
+  RDRF_TRY(pack_image(a.pk, P->packed_bwd, pk, stream, dyn_pack_jobs_bwd, P));
+  return launch_heads_bwd(feat ? "feat_dyn_heads_bwd" : "dyn_heads_bwd", feat ? HEADS_FEAT : HEADS_FLAT, a, w, gw, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -138,6 +138,20 @@ int warp_bwd_on_rows(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int N,
                      float* dxw, float* dxn, const float* g_xyz_prime, const RdrfDynamicParams* G, float* g_xyz, float* dtout,
                      float* dtp, float* pk, uint8_t* valid, hipStream_t stream);
 
+// The heads' backward of the density phase alone, on rows the caller supplies (rdrf_selftest_heads_bwd): k_dyn_density_bwd<0>
+// as rdrf_dynamic_bwd launches it on the flat tiles of [N][S] (feat == 0: raw, valid, gsig, nullable g_blending and dfs; live_d:
+// the density head gets a gradient) or as rdrf_dynamic_features_bwd does on the N = ceil(M / 32) pseudo rays of S = 32 points
+// (feat == 1: nullable g_sigma / g_blending of the raw outputs).  The small layers' gradients are added into G (flat tiles only).
+// pk: PACK_AREA_FLOATS floats for the weight images.  heads_bwd_units: the units the launch geometry (geo_for_units) is sized for.
+long heads_bwd_units(int N, int S, int flat);
+int heads_bwd_on_rows(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int feat, int N, int S, int M, const float* act1,
+                      const float* raw, const uint8_t* valid, const float* gsig, const float* g_sigma, const float* g_blending,
+                      int live_d, float* grows1, float* dfs, const RdrfDynamicParams* G, float* pk, hipStream_t stream);
+// k_time_branch_bwd with the entry points' geometry (32 rays per workgroup of 128 threads); dtp nullable; G: l1w, l1b, l2w, l2b
+struct DynW;
+int launch_time_branch_bwd(const float* ts, const DynW& w, int N, const float* dtout, const float* dtp, int S,
+                           const RdrfDynamicParams* G, hipStream_t stream);
+
 // The ray scan backward alone on arrays the caller supplies (rdrf_selftest_ray_scan_bwd), launched as the entry points launch
 // it: width 32 k_ray_scan_bwd (raw [N][S][2], out = gsig [N][S]), width 64 k_static_density_bwd (raw [N][S], out = gf rows
 // [N][32 ceil(S / 32)]).  Cotangents and g_z / g_rays nullable.

@@ -304,6 +304,13 @@ int launch_ray_scan(const FieldArgs& a, hipStream_t stream) {
   return 0;
 }
 
+// the time branch of N rays or points, 8 per workgroup (rdrf_render_host.hpp): the two entry points below and
+// rdrf_selftest_time_branch; zero64: nullable counter block, cleared on the way
+int launch_time_branch(const float* ts, const DynW& w, int N, float* tout, int* zero64, hipStream_t stream) {
+  RDRF_LAUNCH("time_branch", k_time_branch, dim3((N + 7) / 8), dim3(256), stream, ts, w, N, tout, zero64);
+  return 0;
+}
+
 extern "C" int rdrf_dynamic_fwd_ex(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg,
                                    const float* rays, const float* ts, const float* xyz,
                                    const float* z, const uint8_t* valid, int N, int S,
@@ -331,7 +338,7 @@ extern "C" int rdrf_dynamic_fwd_ex(const RdrfDynamicParams* P, const RdrfFieldCf
   // (rdrf_dynamic_bwd) reads them the same way: both sides take the switch from rdrf_flat_density()
   const bool flat = rdrf_flat_density();
   if (!flat && rgb != nullptr) RDRF_FILL(rgb, 0, (size_t)N * S * 3 * sizeof(float), stream);   // flat: k_ray_scan
-  RDRF_LAUNCH("time_branch", k_time_branch, dim3((N + 7) / 8), dim3(256), stream, ts, w, N, a.tout, a.counter);
+  RDRF_TRY(launch_time_branch(ts, w, N, a.tout, a.counter, stream));
   const Geo g1 = geo_for_units(N), g3 = geo_for_tiles(N, S);
 #ifdef RDRF_DETERMINISTIC
   RDRF_FILL(a.list, 0x7f, (size_t)N * S * sizeof(int), stream);
@@ -437,7 +444,7 @@ extern "C" int rdrf_dynamic_features_fwd(const RdrfDynamicParams* P, const RdrfF
   DynW w;
   fill_dyn_w(w, P);
   RDRF_TRY(pack_image(a.pk, P->packed_fwd, (float*)a.pk, stream, dyn_pack_jobs_fwd, P));
-  RDRF_LAUNCH("time_branch", k_time_branch, dim3((M + 7) / 8), dim3(256), stream, t, w, M, a.tout, (int*)nullptr);
+  RDRF_TRY(launch_time_branch(t, w, M, a.tout, nullptr, stream));
   const Geo g = geo_for_units(Np);
   RDRF_LAUNCH("feat_dyn_density", k_dyn_density<true>, dim3(g.grid), dim3(g.block), stream, a, w);
   if (app != nullptr) RDRF_LAUNCH("feat_dyn_app", k_dyn_app<true>, dim3(g.grid), dim3(g.block), stream, a, w);

@@ -22,6 +22,11 @@ int fwd_dynq();   // FieldArgs::dynq of the forward launches
 // (added to) and rgb (zero fill; nullable).  The entry points launch them; rdrf_selftest_ray_scan does on caller-owned arrays.
 int launch_ray_scan(const FieldArgs& a, hipStream_t stream);
 int launch_static_scan(const FieldArgs& a, hipStream_t stream);
+// k_time_branch (rdrf_fwd.hip) over N rays or points, 8 per workgroup of 256 threads: ts [N] -> tout [N][32]; zero64: the counter
+// block of the density phase that follows, cleared on the way (nullable).  The training and feature-mode forward launch it;
+// rdrf_selftest_time_branch does on caller-owned arrays.
+struct DynW;
+int launch_time_branch(const float* ts, const DynW& w, int N, float* tout, int* zero64, hipStream_t stream);
 
 struct RenderCall {
   const RdrfStaticParams* PS;

@@ -19,6 +19,10 @@
 //
 // rdrf_selftest_ray_scan / rdrf_selftest_ray_scan_bwd (host code only): the per-field ray scan, forward and backward at both
 // widths, through the entry points' launchers on arrays the caller supplies; reference: tests/_scan_prim.py.
+//
+// rdrf_selftest_heads_bwd / rdrf_selftest_time_branch / rdrf_selftest_time_branch_bwd (host code only): the heads' backward tile
+// (k_dyn_density_bwd<0> on flat tiles and in feature mode) and the time branch through the entry points' launchers;
+// reference: tests/_heads_prim.py.
 #include <vector>
 
 #include "rdrf_fwd_dev.hpp"
@@ -869,6 +873,97 @@ extern "C" int rdrf_selftest_ray_scan_bwd(int width, const float* rays, const fl
   RDRF_CHECK((size_t)N * (S + 31) * 3 < (size_t)INT32_MAX, -1, "selftest_ray_scan_bwd: N * S * 3 must stay below 2^31");
   return ray_scan_bwd_on_arrays(width, rays, z, valid, raw, N, S, act, density_shift, distance_scale, ray_type, g_weight, g_sigma,
                                 g_dists, out, g_z, g_rays, (hipStream_t)stream_);
+}
+
+// ------------------------------------------------------------------------------------------------
+// rdrf_selftest_heads_bwd / rdrf_selftest_time_branch / rdrf_selftest_time_branch_bwd (host code only): the heads' backward tile of
+// the dynamic field's density phase and the time branch, forward and backward, on rows and arrays the caller supplies, through
+// the launchers of the entry points (rdrf_bwd_host.hpp, rdrf_render_host.hpp); reference: tests/_heads_prim.py
+// ------------------------------------------------------------------------------------------------
+static void carve_heads_bwd(float*& pk, WsCarver& c) { pk = c.take<float>(PACK_AREA_FLOATS); }
+extern "C" size_t rdrf_selftest_heads_bwd_workspace_bytes(int N, int S) {   // the weight images only: the same at every shape
+  (void)N; (void)S;
+  float* pk;
+  WsCarver c;
+  carve_heads_bwd(pk, c);
+  return c.off;
+}
+
+// [0] ints used, [1] workgroups and [2] waves per workgroup of the launch (a wave walks the tiles wg * waves + wave, + grid * waves,
+// ...), [3] tiles, [4] saved rows per tile, [5] gradient rows per tile, [6] first d(X0) row, [7] first small-layer dz row (the
+// heads write rows + 3 and + 4), [8] floats per sample-major record.  The other rows: rdrf_selftest_dw_describe (dz, saved
+// activations) and rdrf_selftest_scatter_describe (d(feature) rows, record offsets).
+extern "C" int rdrf_selftest_heads_describe(int mode, int N, int S, int* out, int cap) {
+  RDRF_CHECK(mode == RDRF_HEADS_FLAT || mode == RDRF_HEADS_FEAT, -1, "selftest_heads_describe: unknown mode %d", mode);
+  RDRF_CHECK(N >= 0 && (mode == RDRF_HEADS_FEAT || S >= 1), -1, "selftest_heads_describe: bad shape %d x %d", N, S);
+  RDRF_CHECK(out != nullptr && cap >= 9, -3, "selftest_heads_describe: description buffer too small (%d < 9 ints)", out ? cap : 0);
+  const long units = mode == RDRF_HEADS_FEAT ? heads_bwd_units((N + 31) / 32, 32, 0) : heads_bwd_units(N, S, 1);
+  const Geo g = geo_for_units(units);
+  int n = 0;
+  out[n++] = 9; out[n++] = g.grid; out[n++] = g.block / 64; out[n++] = (int)units; out[n++] = sv::K1_ROWS; out[n++] = sv::K1G_ROWS;
+  out[n++] = sv::K1G_DX0; out[n++] = sv::K1G_SM; out[n++] = DFS_FLOATS;
+  return n;
+}
+
+extern "C" int rdrf_selftest_heads_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int mode, int N, int S, const float* act1,
+                                       size_t act1_floats, const float* raw, const uint8_t* valid, const float* g_sigma,
+                                       const float* g_blending, int live_d, float* grows1, size_t grows1_floats, float* dfs,
+                                       size_t dfs_floats, const RdrfDynamicParams* grads, void* ws, size_t ws_bytes,
+                                       rdrf_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RDRF_CHECK(mode == RDRF_HEADS_FLAT || mode == RDRF_HEADS_FEAT, -1, "selftest_heads_bwd: unknown mode %d", mode);
+  if (N == 0) return 0;   // empty batch: a no-op
+  const bool feat = mode == RDRF_HEADS_FEAT;
+  RDRF_CHECK(P && cfg && grads && act1 && grows1 && ws && N > 0, -1, "selftest_heads_bwd: bad arguments");
+  RDRF_CHECK(cfg->act == RDRF_ACT_RELU || cfg->act == RDRF_ACT_SOFTPLUS, -1, "selftest_heads_bwd: unknown activation %d", cfg->act);
+  if (feat) {
+    RDRF_CHECK(dfs == nullptr, -1, "selftest_heads_bwd: feature mode writes no sample-major records");
+    RDRF_CHECK(N <= (1 << 24), -1, "selftest_heads_bwd: at most 2^24 points (got %d)", N);
+  } else {
+    RDRF_CHECK(S >= 1 && S <= 4096, -1, "selftest_heads_bwd: S in 1 .. 4096 (got %d)", S);
+    RDRF_CHECK((size_t)N * S * 3 < (size_t)INT32_MAX, -1, "selftest_heads_bwd: N * S * 3 must stay below 2^31");
+    RDRF_CHECK(raw && valid && g_sigma, -1, "selftest_heads_bwd: flat tiles take raw, valid and the total d(sigma)");
+    RDRF_CHECK(grads->dw2 && grads->db2 && grads->bw2 && grads->bb2, -1, "selftest_heads_bwd: null small-layer gradient");
+  }
+  RDRF_CHECK((((uintptr_t)act1 | (uintptr_t)grows1 | (uintptr_t)ws | (uintptr_t)dfs) & 15) == 0, -1,
+             "selftest_heads_bwd: rows, records and workspace must be 16-byte aligned");
+  const size_t ns = feat ? (size_t)N : (size_t)N * S, tiles = (ns + 31) / 32;
+  RDRF_CHECK(act1_floats >= tiles * sv::K1_ROWS * 32 && grows1_floats >= tiles * sv::K1G_ROWS * 32, -3,
+             "selftest_heads_bwd: rows too small for %zu tiles", tiles);
+  RDRF_CHECK(dfs == nullptr || dfs_floats >= ns * DFS_FLOATS, -3, "selftest_heads_bwd: records too small (%zu < %zu floats)", dfs_floats,
+             ns * DFS_FLOATS);
+  WsCarver c(ws, ws_bytes);
+  float* pk;
+  carve_heads_bwd(pk, c);
+  RDRF_CHECK(c.ok(), -3, "selftest_heads_bwd: workspace too small");
+  return heads_bwd_on_rows(P, cfg, feat ? 1 : 0, feat ? (int)tiles : N, feat ? 32 : S, feat ? N : 0, act1, raw, valid,
+                           feat ? nullptr : g_sigma, feat ? g_sigma : nullptr, g_blending, live_d != 0, grows1, dfs, grads, pk, stream);
+}
+
+extern "C" int rdrf_selftest_time_branch(const RdrfDynamicParams* P, const float* ts, int N, float* tout, int* zero64,
+                                         rdrf_stream_t stream_) {
+  if (N == 0) return 0;   // empty batch: a no-op
+  RDRF_CHECK(P && ts && tout && N > 0 && N <= (1 << 24), -1, "selftest_time_branch: bad arguments");
+  RDRF_CHECK(P->l1w && P->l1b && P->l2w && P->l2b, -1, "selftest_time_branch: null time-branch weights");
+  DynW w;
+  fill_dyn_w(w, P);
+  return launch_time_branch(ts, w, N, tout, zero64, (hipStream_t)stream_);
+}
+
+extern "C" int rdrf_selftest_time_branch_bwd(const RdrfDynamicParams* P, const float* ts, int N, int S, const float* dtout,
+                                             const float* dtp, size_t dtp_floats, const RdrfDynamicParams* grads,
+                                             rdrf_stream_t stream_) {
+  if (N == 0) return 0;   // empty batch: a no-op
+  RDRF_CHECK(P && ts && dtout && grads && N > 0 && S >= 1 && S <= 4096, -1, "selftest_time_branch_bwd: bad arguments");
+  RDRF_CHECK((size_t)N * S * 3 < (size_t)INT32_MAX, -1, "selftest_time_branch_bwd: N * S * 3 must stay below 2^31");
+  RDRF_CHECK(P->l1w && P->l1b && P->l2w && P->l2b, -1, "selftest_time_branch_bwd: null time-branch weights");
+  RDRF_CHECK(grads->l1w && grads->l1b && grads->l2w && grads->l2b, -1, "selftest_time_branch_bwd: null time-branch gradient");
+  const size_t tiles = ((size_t)N * S + 31) / 32;
+  RDRF_CHECK(dtp == nullptr || dtp_floats >= tiles * 64, -3, "selftest_time_branch_bwd: partial records too small (%zu < %zu floats)",
+             dtp_floats, tiles * 64);
+  DynW w;
+  fill_dyn_w(w, P);
+  return launch_time_branch_bwd(ts, w, N, dtout, dtp, S, grads, (hipStream_t)stream_);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -30,6 +30,9 @@ PARENT = {
         8432004, (512, 115): 16173056, (4096, 115): 70488576},
     'rdrf_selftest_warp_bwd_workspace_bytes': {(1, 1): 4195072, (1, 32): 4195072, (1, 33): 4195072, (33, 45): 4196352, (4, 33):
         4195072, (512, 115): 4253696, (4096, 115): 4665856},
+    # (added after that commit: the weight images only, the same at every shape -- held to this as its upper bound)
+    'rdrf_selftest_heads_bwd_workspace_bytes': {(1, 1): 4194304, (1, 32): 4194304, (1, 33): 4194304, (33, 45): 4194304, (4, 33):
+        4194304, (512, 115): 4194304, (4096, 115): 4194304},
     'rdrf_selftest_scatter_workspace_bytes': {(1, 1): 15616, (1, 32): 16896, (1, 33): 16896, (33, 45): 103936, (4, 33): 23296,
         (512, 115): 3719424, (4096, 115): 29686272},
     'rdrf_frame_depth_loss_workspace_bytes': {(1, 1): 264, (1, 32): 512, (1, 33): 520, (33, 45): 616, (4, 33): 520, (512, 115):
@@ -72,6 +75,7 @@ KEPT = ["rdrf_forward_workspace_bytes", "rdrf_render_workspace_bytes", "rdrf_ren
         "rdrf_render_motion_workspace_bytes", "rdrf_flow_to_image_workspace_bytes", "rdrf_ssim_workspace_bytes",
         "rdrf_frame_depth_loss_workspace_bytes"] + [k for k in PARENT if "saved_bytes" in k]
 DERIVED = ["rdrf_workspace_bytes", "rdrf_features_bwd_workspace_bytes", "rdrf_selftest_warp_bwd_workspace_bytes",
+           "rdrf_selftest_heads_bwd_workspace_bytes",
            "rdrf_selftest_scatter_workspace_bytes", "rdrf_compute_alpha_workspace_bytes"]
 
 
