@@ -954,6 +954,36 @@ int rdrf_selftest_time_branch(const RdrfDynamicParams* P, const float* ts, int N
 int rdrf_selftest_time_branch_bwd(const RdrfDynamicParams* P, const float* ts, int N, int S, const float* dtout, const float* dtp,
                                   size_t dtp_floats, const RdrfDynamicParams* grads, rdrf_stream_t stream);
 
+/* The backward-data kernels of the appearance phase alone (what the backward entry points run in front of the appearance scatter
+ * and the appearance dW products), on saved rows the caller supplies, with the entry points' launchers and launch geometry.
+ * field RDRF_APP_DYN: P is a RdrfDynamicParams (k_dyn_app_bwd); RDRF_APP_STATIC_FEA / RDRF_APP_STATIC_TE: P is a RdrfStaticParams
+ * with the MLP_Fea / MLP_Fea_TimeEmbedding head (k_static_app_bwd); cfg gives the box, ray_type (RDRF_RAY_*) and the head come from
+ * the arguments.
+ * mode RDRF_APP_ROWS / RDRF_APP_RECORDS: the ray path over the compacted samples list[0 .. *count) of [N][S] (list [N S] and count
+ * in device memory; the list is checked against N S on the host first).  act3 [T][rows][32], T = ceil(N S / 32): the saved
+ * appearance rows, of which H2, H1 and X0 (dynamic) or P (static) are read -- finite in all 32 lanes of every tile read; rays
+ * [N][6]; g_rgb [N S][3] nullable (then every dz is 0).  Written: the rows DZV, DZ2, DZ1, DF and DA of the first ceil(count / 32)
+ * tiles of grows3 [T][544][32]; dynamic: dxn [N S][3] of the listed samples, and with RDRF_APP_RECORDS the d(app features) as
+ * sample-major records dfa [count][216] INSTEAD of the DA rows (dfa non-null exactly then; dfa_floats >= N S 216); static: the
+ * view-direction gradient ADDED into g_rays [N][6] columns 3..5 (nullable).
+ * mode RDRF_APP_FEAT: N points (S is ignored), g_feat [N][27]: DF and DA rows of ceil(N / 32) tiles; act3, list, count, rays,
+ * g_rgb, dxn and g_rays are not read or written.
+ * ws: 16-byte aligned scratch of rdrf_selftest_app_bwd_workspace_bytes(N, S).  N = 0 is a no-op; -1 on bad arguments, -3 when rows,
+ * records or workspace are too small.  rdrf_selftest_app_describe (host only): the launch geometry at this shape and the rows of a
+ * tile, as ints (layout: csrc/rdrf_selftest.hip; record offsets: rdrf_selftest_scatter_describe); returns the number written. */
+#define RDRF_APP_DYN 0
+#define RDRF_APP_STATIC_FEA 1
+#define RDRF_APP_STATIC_TE 2
+#define RDRF_APP_ROWS 0
+#define RDRF_APP_RECORDS 1
+#define RDRF_APP_FEAT 2
+size_t rdrf_selftest_app_bwd_workspace_bytes(int N, int S);
+int rdrf_selftest_app_describe(int field, int mode, int N, int S, int* out, int cap);
+int rdrf_selftest_app_bwd(const void* P, const RdrfFieldCfg* cfg, int field, int mode, int ray_type, int N, int S, const float* act3,
+                          size_t act3_floats, const int* list, const int* count, const float* rays, const float* g_rgb,
+                          const float* g_feat, float* grows3, size_t grows3_floats, float* dfa, size_t dfa_floats, float* dxn,
+                          float* g_rays, void* ws, size_t ws_bytes, rdrf_stream_t stream);
+
 /* ---- alpha volumes and alpha-grid masks (models/tensorBase.py:42-79 AlphaGridMask, :565-702) ----------------------------
  * A mask is the occupancy grid of updateAlphaMask, bit-packed exactly as `save` (:465-469) stores it: the bool volume of
  * logical shape (G2, G1, G0, T) flattened in C order, eight entries per byte, first entry in the most significant bit

@@ -253,6 +253,9 @@ SIGNATURES = {
     "rdrf_selftest_heads_bwd": (i32, [vp, vp, i32, i32, i32, vp, usz, vp, vp, vp, vp, i32, vp, usz, vp, usz, vp, vp, usz, vp]),
     "rdrf_selftest_time_branch": (i32, [vp, vp, i32, vp, vp, vp]),
     "rdrf_selftest_time_branch_bwd": (i32, [vp, vp, i32, i32, vp, vp, usz, vp, vp]),
+    "rdrf_selftest_app_bwd_workspace_bytes": (usz, [i32, i32]),
+    "rdrf_selftest_app_describe": (i32, [i32, i32, i32, i32, C.POINTER(C.c_int), i32]),
+    "rdrf_selftest_app_bwd": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, usz, vp, vp, vp, vp, vp, vp, usz, vp, usz, vp, vp, vp, usz, vp]),
     "rdrf_compute_alpha_workspace_bytes": (usz, [i32, i32]),
     "rdrf_compute_alpha": (i32, [vp, i32, vp, vp, i32, vp, i32, f32, C.POINTER(RdrfAlphaMask), vp, vp, vp, usz, vp]),
     "rdrf_alpha_mask_build": (i32, [vp, i32, i32, i32, i32, f32, vp, vp, vp]),

@@ -707,6 +707,29 @@ int launch_time_branch_bwd(const float* ts, const DynW& w, int N, const float* d
               G->l1w, G->l1b, G->l2w, G->l2b);
   return 0;
 }
+// The backward-data kernels of the appearance phase with their launch geometry: persistent over the compacted 32-sample tiles of
+// the [N * S] array (ray path; APP_RECORDS: the dynamic field's d(app features) as sample-major records in a.dfa) or over the a.N
+// pseudo rays of feature mode.  The entry points below and app_bwd_on_rows.
+long app_bwd_units(int N, int S, int feat) { return feat ? (long)N : ((long)N * S + 31) / 32; }
+int launch_dyn_app_bwd(const char* name, AppBwdForm form, const BwdArgs& a, const DynW& w, const DynG& gw, hipStream_t stream) {
+  const Geo g = geo_for_units(app_bwd_units(a.N, a.S, form == APP_FEAT));
+  if (form == APP_RECORDS) RDRF_LAUNCH(name, (k_dyn_app_bwd<false, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+  else if (form == APP_FEAT) RDRF_LAUNCH(name, k_dyn_app_bwd<true>, dim3(g.grid), dim3(g.block), stream, a, w, gw);
+  else RDRF_LAUNCH(name, (k_dyn_app_bwd<false, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+  return 0;
+}
+// feature mode runs the MLP_Fea instantiation for either head: only the basis backward is left of the kernel
+int launch_static_app_bwd(const char* name, int head, AppBwdForm form, const BwdArgs& a, const StaticW& w, const StaticG& gw,
+                          hipStream_t stream) {
+  const Geo g = geo_for_units(app_bwd_units(a.N, a.S, form == APP_FEAT));
+  if (form == APP_FEAT)
+    RDRF_LAUNCH(name, (k_static_app_bwd<RDRF_HEAD_MLP_FEA, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+  else if (head == RDRF_HEAD_MLP_FEA)
+    RDRF_LAUNCH(name, (k_static_app_bwd<RDRF_HEAD_MLP_FEA, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+  else
+    RDRF_LAUNCH(name, (k_static_app_bwd<RDRF_HEAD_MLP_FEA_TIMEEMBEDDING, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+  return 0;
+}
 
 // `valid` of a feature-mode batch: 1 for the M points, 0 for the padding of the last 32-point tile
 static int pad_valid_tiles(uint8_t* valid, int M, size_t mp, hipStream_t stream) {
@@ -939,13 +962,7 @@ extern "C" int rdrf_static_bwd(const RdrfStaticParams* P, const RdrfFieldCfg* cf
   RDRF_TRY(pack_image(a.pk, P->packed_bwd, b.pk, stream, static_pack_jobs_bwd, P, cfg->static_head));
   const size_t t3 = ((size_t)N * S + 31) / 32;
   if (g_rgb != nullptr) {
-    const Geo g = geo_for_units((long)t3);
-    if (cfg->static_head == RDRF_HEAD_MLP_FEA)
-      RDRF_LAUNCH("static_app_bwd", (k_static_app_bwd<RDRF_HEAD_MLP_FEA, false>), dim3(g.grid), dim3(g.block),
-                  stream, a, w, gw);
-    else
-      RDRF_LAUNCH("static_app_bwd", (k_static_app_bwd<RDRF_HEAD_MLP_FEA_TIMEEMBEDDING, false>), dim3(g.grid),
-                  dim3(g.block), stream, a, w, gw);
+    RDRF_TRY(launch_static_app_bwd("static_app_bwd", cfg->static_head, APP_ROWS, a, w, gw, stream));
     const int* cnt = &a.sp.hdr->count;
     ScatterArgs sa;
     fill_scatter_common(sa, a);
@@ -1014,11 +1031,9 @@ extern "C" int rdrf_dynamic_bwd(const RdrfDynamicParams* P, const RdrfFieldCfg* 
   DwJobs D;
   D.n = 0;
   if (g_rgb != nullptr) {
-    const Geo g = geo_for_units((long)t3);
     const int smode_app = scatter_mode(ns, stream);
     a.dfa = smode_app != 0 ? b.dfa : nullptr;   // sorted: k_dyn_app_bwd writes sample-major records instead of DA rows
-    if (smode_app != 0) RDRF_LAUNCH("dyn_app_bwd", (k_dyn_app_bwd<false, true>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
-    else RDRF_LAUNCH("dyn_app_bwd", (k_dyn_app_bwd<false, false>), dim3(g.grid), dim3(g.block), stream, a, w, gw);
+    RDRF_TRY(launch_dyn_app_bwd("dyn_app_bwd", smode_app != 0 ? APP_RECORDS : APP_ROWS, a, w, gw, stream));
     if (smode_app != 0) {
       rdrf_prof_begin("scatter_dyn_app", stream);
       const int rc = scatter_dyn_app_sorted(a, b, P, G, stream);
@@ -1139,9 +1154,7 @@ extern "C" int rdrf_static_features_bwd(const RdrfStaticParams* P, const RdrfFie
     StaticG gw;
     fill_static_g(gw, G);
     RDRF_TRY(pack_image(a.pk, P->packed_bwd, b.pk, stream, static_pack_jobs_bwd, P, cfg->static_head));
-    const Geo g = geo_for_units(Np);
-    RDRF_LAUNCH("feat_static_app_bwd", (k_static_app_bwd<RDRF_HEAD_MLP_FEA, true>), dim3(g.grid), dim3(g.block),
-                stream, a, w, gw);
+    RDRF_TRY(launch_static_app_bwd("feat_static_app_bwd", cfg->static_head, APP_FEAT, a, w, gw, stream));
     ScatterArgs sa = sa0;
     scatter_app_set(sa, P->app, G->app, b.grows3);
     RDRF_TRY(launch_scatter("feat_scatter_static_app", SCATTER_12_3_9, sa, (long)Np, stream));
@@ -1184,7 +1197,7 @@ extern "C" int rdrf_dynamic_features_bwd(const RdrfDynamicParams* P, const RdrfF
   DwJobs D;
   D.n = 0;
   if (g_app != nullptr) {
-    RDRF_LAUNCH("feat_dyn_app_bwd", k_dyn_app_bwd<true>, dim3(g.grid), dim3(g.block), stream, a, w, gw);
+    RDRF_TRY(launch_dyn_app_bwd("feat_dyn_app_bwd", APP_FEAT, a, w, gw, stream));
     ScatterArgs sa;
     fill_scatter_common(sa, a);
     scatter_app_set(sa, P->app, G->app, b.grows3);
@@ -1311,6 +1324,39 @@ int heads_bwd_on_rows(const RdrfDynamicParams* P, const RdrfFieldCfg* cfg, int f
   gw.dw2 = G->dw2; gw.db2 = G->db2; gw.bw2 = G->bw2; gw.bb2 = G->bb2;
   RDRF_TRY(pack_image(a.pk, P->packed_bwd, pk, stream, dyn_pack_jobs_bwd, P));
   return launch_heads_bwd(feat ? "feat_dyn_heads_bwd" : "dyn_heads_bwd", feat ? HEADS_FEAT : HEADS_FLAT, a, w, gw, stream);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the appearance backward-data kernels alone on caller-supplied rows (rdrf_bwd_host.hpp; rdrf_selftest_app_bwd)
+// ------------------------------------------------------------------------------------------------
+int app_bwd_on_rows(const void* P, const RdrfFieldCfg* cfg, int dynamic, AppBwdForm form, int N, int S, int M, const float* act3,
+                    const int* list, const int* count, const float* rays, const float* g_rgb, const float* g_feat, float* grows3,
+                    float* dfa, float* dxn, float* g_rays, float* pk, hipStream_t stream) {
+  BwdArgs a;
+  fill_bwd_common(a, cfg, rays, nullptr, nullptr, nullptr, nullptr, N, S);
+  static_assert(offsetof(SavedHdr, count) == 0, "the device count stands for the saved buffer's header");
+  a.sp.hdr = reinterpret_cast<SavedHdr*>(const_cast<int*>(count));
+  a.sp.list = const_cast<int*>(list);
+  a.sp.act3 = const_cast<float*>(act3);
+  a.g_rgb = g_rgb; a.g_feat = g_feat; a.g_rays = g_rays;
+  a.grows3 = grows3; a.dfa = dfa; a.dxn_app = dxn;
+  if (form == APP_FEAT) { a.M = M; a.in_norm = 1; }
+  if (dynamic) {
+    const RdrfDynamicParams* PD = static_cast<const RdrfDynamicParams*>(P);
+    DynW w;
+    fill_dyn_w(w, PD);
+    DynG gw;
+    memset(&gw, 0, sizeof(gw));
+    RDRF_TRY(pack_image(a.pk, PD->packed_bwd, pk, stream, dyn_pack_jobs_bwd, PD));
+    return launch_dyn_app_bwd(form == APP_FEAT ? "feat_dyn_app_bwd" : "dyn_app_bwd", form, a, w, gw, stream);
+  }
+  const RdrfStaticParams* PS = static_cast<const RdrfStaticParams*>(P);
+  StaticW w;
+  fill_static_w(w, PS);
+  StaticG gw;
+  memset(&gw, 0, sizeof(gw));
+  RDRF_TRY(pack_image(a.pk, PS->packed_bwd, pk, stream, static_pack_jobs_bwd, PS, cfg->static_head));
+  return launch_static_app_bwd(form == APP_FEAT ? "feat_static_app_bwd" : "static_app_bwd", cfg->static_head, form, a, w, gw, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -152,6 +152,26 @@ struct DynW;
 int launch_time_branch_bwd(const float* ts, const DynW& w, int N, const float* dtout, const float* dtp, int S,
                            const RdrfDynamicParams* G, hipStream_t stream);
 
+// The backward-data kernels of the appearance phase (k_dyn_app_bwd, k_static_app_bwd: rdrf_bwd.hip) with the entry points' geometry,
+// geo_for_units of app_bwd_units: the tiles of [N][S] on the ray path, the N pseudo rays of feature mode.  APP_RECORDS (dynamic
+// only): d(app features) go to a.dfa as sample-major records; head: RDRF_HEAD_* of the static field (feature mode runs the
+// MLP_Fea instantiation for either).  The four backward entry points launch them; app_bwd_on_rows does on caller-supplied rows
+// (rdrf_selftest_app_bwd): dynamic != 0: P is a RdrfDynamicParams, else a RdrfStaticParams with cfg->static_head; ray path: act3
+// [tiles][K3_ROWS | S3_ROWS][32], list [N S] and the device count of the compacted samples, rays [N][6], nullable g_rgb [N S][3],
+// dxn [N S][3] (dynamic), nullable g_rays [N][6] (static, added into); feature mode: N = ceil(M / 32), S = 32, g_feat [M][27].
+// grows3 [tiles][K3G_ROWS][32]; pk: PACK_AREA_FLOATS floats for the weight image.
+enum AppBwdForm { APP_ROWS, APP_RECORDS, APP_FEAT };
+struct StaticW;
+struct StaticG;
+struct DynG;
+long app_bwd_units(int N, int S, int feat);
+int launch_dyn_app_bwd(const char* name, AppBwdForm form, const BwdArgs& a, const DynW& w, const DynG& gw, hipStream_t stream);
+int launch_static_app_bwd(const char* name, int head, AppBwdForm form, const BwdArgs& a, const StaticW& w, const StaticG& gw,
+                          hipStream_t stream);
+int app_bwd_on_rows(const void* P, const RdrfFieldCfg* cfg, int dynamic, AppBwdForm form, int N, int S, int M, const float* act3,
+                    const int* list, const int* count, const float* rays, const float* g_rgb, const float* g_feat, float* grows3,
+                    float* dfa, float* dxn, float* g_rays, float* pk, hipStream_t stream);
+
 // The ray scan backward alone on arrays the caller supplies (rdrf_selftest_ray_scan_bwd), launched as the entry points launch
 // it: width 32 k_ray_scan_bwd (raw [N][S][2], out = gsig [N][S]), width 64 k_static_density_bwd (raw [N][S], out = gf rows
 // [N][32 ceil(S / 32)]).  Cotangents and g_z / g_rays nullable.

@@ -23,6 +23,9 @@
 // rdrf_selftest_heads_bwd / rdrf_selftest_time_branch / rdrf_selftest_time_branch_bwd (host code only): the heads' backward tile
 // (k_dyn_density_bwd<0> on flat tiles and in feature mode) and the time branch through the entry points' launchers;
 // reference: tests/_heads_prim.py.
+//
+// rdrf_selftest_app_bwd (host code only): the backward-data kernels of the appearance phase (k_dyn_app_bwd, k_static_app_bwd) on
+// saved rows the caller supplies, through the entry points' launchers; reference: tests/_app_prim.py.
 #include <vector>
 
 #include "rdrf_fwd_dev.hpp"
@@ -964,6 +967,96 @@ extern "C" int rdrf_selftest_time_branch_bwd(const RdrfDynamicParams* P, const f
   DynW w;
   fill_dyn_w(w, P);
   return launch_time_branch_bwd(ts, w, N, dtout, dtp, S, grads, (hipStream_t)stream_);
+}
+
+// ------------------------------------------------------------------------------------------------
+// rdrf_selftest_app_bwd (host code only): the backward-data kernels of the appearance phase on saved rows, a compaction list and
+// cotangents the caller supplies, through the launchers of the entry points (rdrf_bwd_host.hpp); reference: tests/_app_prim.py
+// ------------------------------------------------------------------------------------------------
+static void carve_app_bwd(float*& pk, WsCarver& c) { pk = c.take<float>(PACK_AREA_FLOATS); }
+extern "C" size_t rdrf_selftest_app_bwd_workspace_bytes(int N, int S) {   // the weight image only: the same at every shape
+  (void)N; (void)S;
+  float* pk;
+  WsCarver c;
+  carve_app_bwd(pk, c);
+  return c.off;
+}
+static bool app_field_ok(int field) { return field == RDRF_APP_DYN || field == RDRF_APP_STATIC_FEA || field == RDRF_APP_STATIC_TE; }
+static bool app_mode_ok(int mode) { return mode == RDRF_APP_ROWS || mode == RDRF_APP_RECORDS || mode == RDRF_APP_FEAT; }
+
+// [0] ints used, [1] workgroups and [2] waves per workgroup of the launch (the waves of workgroup b take the tiles b, b + grid,
+// ... from the workgroup's queue: the first `waves` of them one each, then whoever is done first), [3] tiles the launch is sized
+// for (the kernel walks ceil(count / 32) of them), [4] saved rows per tile, [5] gradient rows per tile, [6] .. [10] first row of
+// DZV, DZ2, DZ1, DF, DA, [11] .. [13] first of the saved rows the ray path reads: H2, H1, and X0 (dynamic) or P (static), [14]
+// floats per sample-major record (0: the field writes none), [15] DA rows the field writes.  The offset of every feature quad in
+// a record, and the level / plane / component behind every DA row: rdrf_selftest_scatter_describe (RDRF_SCK_DYN_APP / STATIC_APP).
+extern "C" int rdrf_selftest_app_describe(int field, int mode, int N, int S, int* out, int cap) {
+  RDRF_CHECK(app_field_ok(field), -1, "selftest_app_describe: unknown field %d", field);
+  RDRF_CHECK(app_mode_ok(mode), -1, "selftest_app_describe: unknown mode %d", mode);
+  RDRF_CHECK(N >= 0 && (mode == RDRF_APP_FEAT || S >= 1), -1, "selftest_app_describe: bad shape %d x %d", N, S);
+  RDRF_CHECK(out != nullptr && cap >= 16, -3, "selftest_app_describe: description buffer too small (%d < 16 ints)", out ? cap : 0);
+  const bool dyn = field == RDRF_APP_DYN;
+  const long units = mode == RDRF_APP_FEAT ? app_bwd_units((N + 31) / 32, 32, 1) : app_bwd_units(N, S, 0);
+  const Geo g = geo_for_units(units);
+  int n = 0;
+  out[n++] = 16; out[n++] = g.grid; out[n++] = g.block / 64; out[n++] = (int)units;
+  out[n++] = dyn ? sv::K3_ROWS : sv::S3_ROWS; out[n++] = sv::K3G_ROWS;
+  out[n++] = sv::K3G_DZV; out[n++] = sv::K3G_DZ2; out[n++] = sv::K3G_DZ1; out[n++] = sv::K3G_DF; out[n++] = sv::K3G_DA;
+  out[n++] = dyn ? sv::K3_H2 : sv::S3_H2; out[n++] = dyn ? sv::K3_H1 : sv::S3_H1; out[n++] = dyn ? sv::K3_X0 : sv::S3_P;
+  out[n++] = dyn ? DFA_FLOATS : 0; out[n++] = dyn ? 112 : 48;
+  return n;
+}
+
+extern "C" int rdrf_selftest_app_bwd(const void* P, const RdrfFieldCfg* cfg, int field, int mode, int ray_type, int N, int S,
+                                     const float* act3, size_t act3_floats, const int* list, const int* count, const float* rays,
+                                     const float* g_rgb, const float* g_feat, float* grows3, size_t grows3_floats, float* dfa,
+                                     size_t dfa_floats, float* dxn, float* g_rays, void* ws, size_t ws_bytes, rdrf_stream_t stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  RDRF_CHECK(app_field_ok(field), -1, "selftest_app_bwd: unknown field %d", field);
+  RDRF_CHECK(app_mode_ok(mode), -1, "selftest_app_bwd: unknown mode %d", mode);
+  RDRF_CHECK(mode != RDRF_APP_RECORDS || field == RDRF_APP_DYN, -1, "selftest_app_bwd: only the dynamic field writes sample-major records");
+  RDRF_CHECK((mode == RDRF_APP_RECORDS) == (dfa != nullptr), -1, "selftest_app_bwd: records go with RDRF_APP_RECORDS and nothing else");
+  if (N == 0) return 0;   // empty batch: a no-op
+  const bool feat = mode == RDRF_APP_FEAT, dyn = field == RDRF_APP_DYN;
+  RDRF_CHECK(P && cfg && grows3 && ws && N > 0, -1, "selftest_app_bwd: bad arguments");
+  RDRF_CHECK(ray_type == RDRF_RAY_NDC || ray_type == RDRF_RAY_CONTRACT || ray_type == RDRF_RAY_OTHER, -1,
+             "selftest_app_bwd: unknown ray type %d", ray_type);
+  if (feat) {
+    RDRF_CHECK(g_feat != nullptr, -1, "selftest_app_bwd: feature mode takes g_feat");
+    RDRF_CHECK(N <= (1 << 24), -1, "selftest_app_bwd: at most 2^24 points (got %d)", N);
+  } else {
+    RDRF_CHECK(S >= 1 && S <= 4096, -1, "selftest_app_bwd: S in 1 .. 4096 (got %d)", S);
+    RDRF_CHECK((size_t)N * S * 3 < (size_t)INT32_MAX, -1, "selftest_app_bwd: N * S * 3 must stay below 2^31");
+    RDRF_CHECK(act3 && list && count && rays, -1, "selftest_app_bwd: the ray path takes saved rows, the list, its count and rays");
+    RDRF_CHECK(!dyn || dxn != nullptr, -1, "selftest_app_bwd: the dynamic field writes dxn");
+  }
+  RDRF_CHECK((((uintptr_t)act3 | (uintptr_t)grows3 | (uintptr_t)ws | (uintptr_t)dfa) & 15) == 0, -1,
+             "selftest_app_bwd: rows, records and workspace must be 16-byte aligned");
+  const size_t ns = feat ? (size_t)N : (size_t)N * S, tiles = (ns + 31) / 32;
+  RDRF_CHECK((feat || act3_floats >= tiles * (dyn ? sv::K3_ROWS : sv::S3_ROWS) * 32) && grows3_floats >= tiles * sv::K3G_ROWS * 32, -3,
+             "selftest_app_bwd: rows too small for %zu tiles", tiles);
+  RDRF_CHECK(dfa == nullptr || dfa_floats >= ns * DFA_FLOATS, -3, "selftest_app_bwd: records too small (%zu < %zu floats)", dfa_floats,
+             ns * DFA_FLOATS);
+  WsCarver c(ws, ws_bytes);
+  float* pk;
+  carve_app_bwd(pk, c);
+  RDRF_CHECK(c.ok(), -3, "selftest_app_bwd: workspace too small");
+  if (!feat) {   // the kernels index g_rgb, dxn, rays and the records by what the list holds: looked at before anything is launched
+    std::vector<int> hl(ns);
+    int hc = 0;
+    RDRF_HIP(hipMemcpyAsync(&hc, count, sizeof(int), hipMemcpyDeviceToHost, stream));
+    RDRF_HIP(hipMemcpyAsync(hl.data(), list, ns * sizeof(int), hipMemcpyDeviceToHost, stream));
+    RDRF_HIP(hipStreamSynchronize(stream));
+    RDRF_CHECK(hc >= 0 && (size_t)hc <= ns, -1, "selftest_app_bwd: count %d outside 0 .. %zu", hc, ns);
+    for (int i = 0; i < hc; ++i)
+      RDRF_CHECK(hl[i] >= 0 && (size_t)hl[i] < ns, -1, "selftest_app_bwd: list[%d] = %d outside 0 .. %zu", i, hl[i], ns - 1);
+  }
+  RdrfFieldCfg cf = *cfg;
+  cf.ray_type = ray_type;
+  cf.static_head = field == RDRF_APP_STATIC_TE ? RDRF_HEAD_MLP_FEA_TIMEEMBEDDING : RDRF_HEAD_MLP_FEA;
+  const AppBwdForm form = feat ? APP_FEAT : (mode == RDRF_APP_RECORDS ? APP_RECORDS : APP_ROWS);
+  return app_bwd_on_rows(P, &cf, dyn ? 1 : 0, form, feat ? (int)tiles : N, feat ? 32 : S, feat ? N : 0, act3, list, count, rays,
+                         feat ? nullptr : g_rgb, feat ? g_feat : nullptr, grows3, dfa, dxn, feat ? nullptr : g_rays, pk, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

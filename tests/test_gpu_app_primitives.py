@@ -1,0 +1,376 @@
+"""The backward-data kernels of the appearance phase, each alone on saved rows, a compaction list and cotangents the test supplies,
+against the float64 references and the derived bounds of tests/_app_prim.py (its docstring has the derivations; no tolerance here
+was set from a measurement):
+  rdrf_selftest_app_bwd   k_dyn_app_bwd<false, false | true> and <true>; k_static_app_bwd<MLP_Fea | TimeEmbedding, false> and <., true>
+through the launchers and the launch geometry of the entry points.
+
+Every output is pre-filled with a NaN pattern between guard bands (g_rays, which is added into, with random values), so whatever the
+kernel must not write -- the tiles past ceil(count / 32), the rows between its blocks, the DA rows of a run with records, dxn of
+samples and g_rays of rays that are not in the list -- is compared bit for bit with the pre-fill.  The saved rows hold NaN wherever
+the kernel must not read; the rows it reads hold +0.0, -0.0, 2^-126 and ordinary values of both signs in every tile, padding lanes
+included.  An output whose reference is exactly 0 (closed gates, padding lanes, DF slots 27..31) has the bound 0 and must be exactly
+0.  No sample is excluded from any comparison.  Every comparison records error / bound with record_margin
+(profiles/app_bwd_margins.txt holds one run)."""
+import ctypes as C
+import importlib
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import _app_prim as Q   # noqa: E402
+from _util import record_margin   # noqa: E402
+
+pytestmark = pytest.mark.gpu
+GUARD = 256
+NANBITS = 0xFFFFFFFF
+# position of the replaced tensors in the fields' parameter lists (robust-dynrf_amd/_params.py: the VM factors first)
+SLOTS = {"dyn": {"basis": 18, "w1": 19, "w2": 21, "w3": 23, "b3": 24}, "static": {"basis": 12, "w1": 13, "w2": 15, "w3": 17, "b3": 18}}
+FIELD_MODES = [("dyn", "rows"), ("dyn", "rec"), ("fea", "rows"), ("te", "rows")]
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+class Guarded:
+    """a device array between two guard bands of the NaN pattern"""
+
+    def __init__(self, host):
+        host = np.ascontiguousarray(host, dtype=np.float32)
+        self.shape, n = host.shape, host.size
+        self.flat = torch.from_numpy(np.full(n + 2 * GUARD, Q.NAN, dtype=np.float32)).cuda()
+        self.t = self.flat[GUARD:GUARD + n]
+        self.t.copy_(torch.from_numpy(host.reshape(-1)))
+
+    def guards_intact(self):
+        g = torch.cat([self.flat[:GUARD], self.flat[-GUARD:]]).cpu().numpy().view(np.uint32)
+        return bool((g == NANBITS).all())
+
+    def host(self):
+        return self.t.cpu().numpy().reshape(self.shape)
+
+
+class Harness:
+    """one small field of each kind for the parameter structs, the appearance weights replaced per call"""
+
+    def __init__(self):
+        import rodynrf
+        from _gpu_util import COMMON
+        self.L = importlib.import_module("robust-dynrf_amd._lib")
+        self.F = importlib.import_module("robust-dynrf_amd.fields")
+        aabb = torch.tensor([[-1.0, -1.0, -1.0], [1.0, 1.0, 1.0]])
+        kw = dict(COMMON, near_far=[0.0, 1.0], density_shift=-10.0, fea2denseAct="relu")
+        torch.manual_seed(3)
+        self.field = {"dyn": rodynrf.TensorVMSplit_TimeEmbedding(aabb, [24, 26, 16], 12, "cuda:0", shadingMode="MLP_Fea_late_view", fea_pe=0, **kw),
+                      "fea": rodynrf.TensorVMSplit(aabb, [24, 26, 16], 12, "cuda:0", shadingMode="MLP_Fea", fea_pe=2, **kw),
+                      "te": rodynrf.TensorVMSplit(aabb, [24, 26, 16], 12, "cuda:0", shadingMode="MLP_Fea_TimeEmbedding", fea_pe=2, **kw)}
+        self.params = {k: [p.detach() for p in f._param_list()] for k, f in self.field.items()}
+        for k in Q.FIELDS:
+            W = Q.app_weights(k)
+            for name, i in SLOTS["dyn" if k == "dyn" else "static"].items():
+                assert tuple(self.params[k][i].shape) == W[name].shape, (k, name, tuple(self.params[k][i].shape))
+        self.lay = {k: Q.layout(self.L, k) for k in Q.FIELDS}
+        self.ws = torch.zeros(self.L.lib.rdrf_selftest_app_bwd_workspace_bytes(1, 1), dtype=torch.uint8, device="cuda:0")
+
+    def structs(self, field, W):
+        params = list(self.params[field])
+        for name, i in SLOTS["dyn" if field == "dyn" else "static"].items():
+            params[i] = torch.from_numpy(np.ascontiguousarray(W[name])).cuda()
+        P = (self.F._dynamic_struct if field == "dyn" else self.F._static_struct)(params)
+        return P, self.F._cfg_struct(self.field[field], "ndc"), params
+
+    def call(self, c, W, act, lst, cnt, rays, g_rgb, g_feat, grw, rec, dxn, gr, mode=None, field=None, ray_type=None, N=None, S=None,
+             act_floats=None, grw_floats=None, rec_floats=None, ws=None, ws_bytes=None):
+        """the raw call -> rc; the keyword arguments override what the case says (error tests)"""
+        L = self.L
+        P, cfg, keep = self.structs(c["field"], W)
+        ws = self.ws if ws is None else ws
+        p = L.ptr
+        numel = lambda t: 0 if t is None else t.numel()   # noqa: E731
+        rc = L.lib.rdrf_selftest_app_bwd(
+            C.byref(P), C.byref(cfg), Q.FIELDS[c["field"]] if field is None else field, Q.MODES[c["mode"]] if mode is None else mode,
+            Q.ray_type_id(L, c["ray_type"]) if ray_type is None else ray_type, c["N"] if N is None else N, c["S"] if S is None else S, p(act),
+            C.c_size_t(numel(act) if act_floats is None else act_floats), p(lst), p(cnt), p(rays), p(g_rgb), p(g_feat), p(grw),
+            C.c_size_t(numel(grw) if grw_floats is None else grw_floats), p(rec),
+            C.c_size_t(numel(rec) if rec_floats is None else rec_floats), p(dxn), p(gr), p(ws),
+            C.c_size_t(ws.numel() if ws_bytes is None else ws_bytes), L.stream_of(self.ws))
+        torch.cuda.synchronize()
+        del keep
+        return rc
+
+    def run(self, c, W, pre_rays=None, poison=True, with_g_rays=True):
+        """-> {'grows' [tiles][544][32], 'rec' [ns][216] | None, 'dxn' [ns][3] | None, 'g_rays' [N][6] | None} (numpy)"""
+        L, lay = self.L, self.lay[c["field"]]
+        feat, dyn = c["mode"] == "feat", c["field"] == "dyn"
+        dev = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()   # noqa: E731
+        ns = c["N"] if feat else c["N"] * c["S"]
+        tiles = (ns + 31) // 32
+        if feat:
+            act = torch.from_numpy(np.full((tiles, lay["rows"], 32), Q.NAN, dtype=np.float32)).cuda()
+            lst = cnt = rays = g_rgb = None
+            g_feat = dev(c["g_feat"])
+        else:
+            act, lst, rays, g_rgb, g_feat = dev(Q.app_rows(c, lay, poison)), dev(c["list"]), dev(c["rays"]), dev(c["g_rgb"]), None
+            cnt = torch.full((64,), c["count"], dtype=torch.int32, device="cuda:0")
+        out = {"grows": Guarded(np.full((tiles, lay["grows"], 32), Q.NAN, dtype=np.float32)), "rec": None, "dxn": None, "g_rays": None}
+        if c["mode"] == "rec":
+            out["rec"] = Guarded(np.full((ns, lay["rec"]), Q.NAN, dtype=np.float32))
+        if dyn and not feat:
+            out["dxn"] = Guarded(np.full((ns, 3), Q.NAN, dtype=np.float32))
+        if not dyn and not feat and with_g_rays:
+            out["g_rays"] = Guarded(pre_rays)
+        t = lambda k: None if out[k] is None else out[k].t   # noqa: E731
+        L.check(self.call(c, W, act, lst, cnt, rays, g_rgb, g_feat, t("grows"), t("rec"), t("dxn"), t("g_rays")), "rdrf_selftest_app_bwd")
+        for k, g in out.items():
+            assert g is None or g.guards_intact(), f"the guard bands of {k} were written"
+        return {k: (None if g is None else g.host()) for k, g in out.items()}
+
+
+_H = []
+
+
+def _harness():
+    if not _H:
+        _H.append(Harness())
+    return _H[0]
+
+
+def _pre_rays(N, seed=11):
+    return np.random.default_rng([seed, N]).standard_normal((N, 6)).astype(np.float32)
+
+
+def _bounded(H, tag, name, got, ref):
+    r = Q.ratio(got, ref[0], ref[1])
+    record_margin(f"{tag} {name}", r)
+    assert r <= 1.0, f"{tag}: {name} sits at {r:.3f} of its bound"
+
+
+def _check(H, c, W, tag, **kw):
+    """one call: every written row, record, dxn and g_rays against its bound, everything else against the pre-fill; -> the outputs"""
+    lay = H.lay[c["field"]]
+    feat, dyn, n = c["mode"] == "feat", c["field"] == "dyn", c["n"]
+    pre = None if (dyn or feat) else _pre_rays(c["N"])
+    got = H.run(c, W, pre_rays=pre, **kw)
+    ref = Q.app_reference(c, W, lay, pre_rays=None if pre is None else pre[:, 3:6])
+    T = (n + 31) // 32
+    grw = got["grows"]
+    written = np.zeros(lay["grows"], dtype=bool)
+    blocks = {"dF": (lay["DF"], 32)}
+    if c["mode"] != "rec":
+        blocks["dA"] = (lay["DA"], 2 * lay["nda"])
+    if not feat:
+        blocks.update(dzv=(lay["DZV"], 3), dz2=(lay["DZ2"], 128), dz1=(lay["DZ1"], 128))
+    for name, (r0, nr) in blocks.items():
+        written[r0:r0 + nr] = True
+        _bounded(H, tag, name, Q.rows_of(grw[:T], r0, nr, n), ref[name])
+        pad = grw[:T, r0:r0 + nr, :].transpose(0, 2, 1).reshape(T * 32, nr)[n:]
+        assert (bits(pad) == 0).all(), f"{tag}: padding lanes of {name} are not +0.0"
+    assert (bits(grw[T:]) == NANBITS).all(), f"{tag}: a tile past ceil(count / 32) was written"
+    assert (bits(grw[:T, ~written, :]) == NANBITS).all(), f"{tag}: a row outside the kernel's blocks was written"
+    df = Q.rows_of(grw[:T], lay["DF"], 32, n)
+    assert (df[:, 27:] == 0).all(), f"{tag}: DF slots 27..31"
+    if feat:
+        return got
+    idx = c["list"][:n].astype(np.int64)
+    if dyn:
+        _bounded(H, tag, "dxn", got["dxn"][idx], ref["dxn"])
+        rest = np.ones(len(got["dxn"]), dtype=bool)
+        rest[idx] = False
+        assert (bits(got["dxn"][rest]) == NANBITS).all(), f"{tag}: dxn of a sample outside the list was written"
+        if c["mode"] == "rec":
+            _bounded(H, tag, "rec", got["rec"][:n], ref["rec"])
+            assert (bits(got["rec"][n:]) == NANBITS).all(), f"{tag}: a record past count was written"
+    elif got["g_rays"] is not None:
+        _bounded(H, tag, "g_rays", got["g_rays"][:, 3:6].astype(np.float64), ref["g_rays"])
+        assert np.array_equal(bits(got["g_rays"][:, :3]), bits(pre[:, :3])), f"{tag}: g_rays columns 0..2"
+        rest = np.ones(c["N"], dtype=bool)
+        rest[idx // c["S"]] = False
+        assert np.array_equal(bits(got["g_rays"][rest]), bits(pre[rest])), f"{tag}: g_rays of a ray outside the list"
+    return got
+
+
+def _shape(count, S):
+    return max(1, -(-(count + 9) // S)), S   # N S larger than the count
+
+
+@pytest.mark.parametrize("field,mode", FIELD_MODES)
+def test_counts_and_S(field, mode):
+    H = _harness()
+    for ci, count in enumerate(Q.COUNTS):
+        for S in Q.S_VALUES:
+            N, S = _shape(count, S)
+            c = Q.app_case(field, mode, N, S, count, "ndc" if (ci + S) % 2 else "contract", seed=ci)
+            _check(H, c, Q.app_weights(field, ci), f"{field} {mode} {N}x{S} count {count}")
+
+
+@pytest.mark.parametrize("field", sorted(Q.FIELDS))
+def test_feature_mode(field):
+    H = _harness()
+    for M in (1, 31, 32, 33, 95):
+        _check(H, Q.app_case(field, "feat", M, 1, M), Q.app_weights(field), f"{field} feat {M}")
+
+
+@pytest.mark.parametrize("ray_type", Q.RAY_TYPES)
+@pytest.mark.parametrize("field", ["fea", "te"])
+def test_static_ray_types(field, ray_type):
+    H = _harness()
+    _check(H, Q.app_case(field, "rows", 9, 13, 95, ray_type, seed=3), Q.app_weights(field, 1), f"{field} rows 9x13 count 95 {ray_type}")
+
+
+@pytest.mark.parametrize("field,mode,which", [("dyn", "rows", 0), ("dyn", "rec", 1), ("fea", "rows", 1), ("te", "rows", 0), ("te", "rows", 1),
+                                              ("dyn", "feat", 1), ("fea", "feat", 1)])
+def test_large_shapes(field, mode, which):
+    """the smallest tile counts (from the describe) with several waves per workgroup (which = 0) and with a second round of the
+    workgroups' tile queues (which = 1); the CPU file asserts both geometries"""
+    H = _harness()
+    t = Q.large_tiles(H.L, field)[which]
+    count = (t - 1) * 32 + 3
+    if mode == "feat":
+        c = Q.app_case(field, "feat", count, 1, count)
+        g = Q.app_describe(H.L, field, mode, count, 1)
+    else:
+        N, S = _shape(count, 13)
+        c = Q.app_case(field, mode, N, S, count, "ndc")
+        g = Q.app_describe(H.L, field, mode, N, S)
+    assert g["waves"] > 1 and (c["n"] + 31) // 32 == t and (which == 0 or t > g["grid"] * g["waves"])
+    _check(H, c, Q.app_weights(field), f"{field} {mode} {t} tiles")
+
+
+@pytest.mark.parametrize("field,mode", FIELD_MODES)
+def test_unread_rows_and_null_outputs(field, mode):
+    """NaN in every saved row the kernel must not read changes no bit; g_rgb == nullptr: every dz row exactly 0 and g_rays unchanged;
+    g_rays == nullptr: the rest unchanged bit for bit"""
+    H = _harness()
+    W = Q.app_weights(field)
+    c = Q.app_case(field, mode, 9, 13, 95, "ndc", seed=5)
+    a = _check(H, c, W, f"{field} {mode} poisoned")
+    pre = None if field == "dyn" else _pre_rays(c["N"])
+    b = H.run(c, W, pre_rays=pre, poison=False)
+    for k in a:   # (g_rays is a sum of atomics in no fixed order: held to its bound above, where a NaN read would show)
+        assert a[k] is None or k == "g_rays" or np.array_equal(bits(a[k]), bits(b[k])), f"{k} depends on a saved row it must not read"
+    if field != "dyn":
+        d = H.run(c, W, with_g_rays=False)
+        assert d["g_rays"] is None and np.array_equal(bits(a["grows"]), bits(d["grows"]))
+    c0 = dict(c, g_rgb=None)
+    z = _check(H, c0, W, f"{field} {mode} no g_rgb")
+    lay = H.lay[field]
+    for r0, nr in ((lay["DZV"], 3), (lay["DZ2"], 128), (lay["DZ1"], 128), (lay["DF"], 32)):
+        assert (z["grows"][:3, r0:r0 + nr, :] == 0).all()
+    if field != "dyn":
+        assert np.array_equal(z["g_rays"], pre), "g_rays changed without a cotangent"
+
+
+def test_feature_mode_reads_no_saved_row():
+    H = _harness()   # run() hands feature mode an act3 that is NaN everywhere; nullptr must give the same bits
+    for field in Q.FIELDS:
+        c, W = Q.app_case(field, "feat", 70, 1, 70), Q.app_weights(field)
+        a = H.run(c, W)
+        g = Guarded(np.full(a["grows"].shape, Q.NAN, dtype=np.float32))
+        H.L.check(H.call(c, W, None, None, None, None, None, torch.from_numpy(c["g_feat"]).cuda(), g.t, None, None, None, act_floats=0),
+                  "rdrf_selftest_app_bwd")
+        assert np.array_equal(bits(a["grows"]), bits(g.host()))
+
+
+@pytest.mark.parametrize("field,mode", FIELD_MODES)
+def test_saturated_logits_and_single_channels(field, mode):
+    H = _harness()
+    for bias in ([-95.0, 95.0, -87.5], [88.0, -104.0, 17.0], [-88.5, 103.0, -16.7]):
+        W = Q.app_weights(field, 2)
+        W["b3"] = np.asarray(bias, dtype=np.float32)
+        got = _check(H, Q.app_case(field, mode, 5, 13, 33, "contract", seed=7), W, f"{field} {mode} logits near {bias}")
+        assert np.isfinite(got["grows"][:2, :3, :]).all()
+    for ch in range(3):
+        _check(H, Q.app_case(field, mode, 5, 13, 33, "ndc", seed=8, g_channel=ch), Q.app_weights(field, 3), f"{field} {mode} channel {ch}")
+
+
+def test_records_against_rows():
+    """k_dyn_app_bwd<false, true> and <false, false> on one input: the same dA bits at the offsets the scatter's describe reports,
+    every other row and dxn identical"""
+    H = _harness()
+    lay = H.lay["dyn"]
+    W = Q.app_weights("dyn", 4)
+    for count, S in ((95, 13), (33, 1), (64, 70)):
+        N, S = _shape(count, S)
+        cr = Q.app_case("dyn", "rows", N, S, count, "ndc", seed=9)
+        a, b = H.run(cr, W), H.run(dict(cr, mode="rec"), W)
+        T = (count + 31) // 32
+        dA = Q.rows_of(a["grows"][:T], lay["DA"], 2 * lay["nda"], count)
+        for e0, off in lay["quads"]:
+            assert np.array_equal(bits(b["rec"][:count, off:off + 4]), bits(dA[:, e0:e0 + 4])), f"quad at DA element {e0}"
+        assert np.array_equal(bits(a["grows"][:, :lay["DA"]]), bits(b["grows"][:, :lay["DA"]])) and np.array_equal(bits(a["dxn"]), bits(b["dxn"]))
+
+
+@pytest.mark.parametrize("field", sorted(Q.FIELDS))
+def test_a_sample_is_independent_of_its_batch(field):
+    """the same samples in other tiles and lanes of a batch of another size give the same bits in every row (and in dxn)"""
+    H = _harness()
+    lay = H.lay[field]
+    W = Q.app_weights(field, 5)
+    A = Q.app_case(field, "rows", 9, 13, 95, "ndc", seed=10)
+    sel = np.random.default_rng(12).permutation(95)[:40]
+    B = dict(A, count=40, n=40, T=2)
+    B["list"] = A["list"].copy()
+    B["list"][:40] = A["list"][sel]
+    for k in ("H2", "H1", "IN"):
+        B[k] = np.ascontiguousarray(np.concatenate([A[k][sel], A[k][40:64]]))
+    pre = None if field == "dyn" else _pre_rays(9)
+    a, b = H.run(A, W, pre_rays=pre), H.run(B, W, pre_rays=pre)
+    ra, rb = Q.rows_of(a["grows"][:3], 0, lay["grows"], 95), Q.rows_of(b["grows"][:2], 0, lay["grows"], 40)
+    assert np.array_equal(bits(ra[sel]), bits(rb))
+    if field == "dyn":
+        idx = B["list"][:40]
+        assert np.array_equal(bits(a["dxn"][idx]), bits(b["dxn"][idx]))
+
+
+@pytest.mark.parametrize("field", sorted(Q.FIELDS))
+def test_feature_mode_matches_the_ray_path(field):
+    """a feature-mode run fed the ray path's dF gives the ray path's DA rows bit for bit"""
+    H = _harness()
+    lay = H.lay[field]
+    W = Q.app_weights(field, 6)
+    c = Q.app_case(field, "rows", 9, 13, 95, "contract", seed=13)
+    a = H.run(c, W, pre_rays=None if field == "dyn" else _pre_rays(9))
+    dF = Q.rows_of(a["grows"][:3], lay["DF"], 32, 95)
+    f = H.run(dict(Q.app_case(field, "feat", 95, 1, 95), g_feat=np.ascontiguousarray(dF[:, :27])), W)
+    for r0, nr in ((lay["DF"], 32), (lay["DA"], 2 * lay["nda"])):
+        assert np.array_equal(bits(a["grows"][:3, r0:r0 + nr]), bits(f["grows"][:3, r0:r0 + nr]))
+
+
+def test_error_codes():
+    H = _harness()
+    L = H.L
+    W = Q.app_weights("dyn")
+    c = Q.app_case("dyn", "rec", 9, 13, 95, "ndc")
+    lay = H.lay["dyn"]
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()   # noqa: E731
+    act, lst, rays, g = dev(Q.app_rows(c, lay)), dev(c["list"]), dev(c["rays"]), dev(c["g_rgb"])
+    cnt = torch.full((64,), 95, dtype=torch.int32, device="cuda:0")
+    grw = torch.zeros(4 * 544 * 32 + 4, device="cuda:0")
+    rec, dxn = torch.zeros(117 * 216, device="cuda:0"), torch.zeros(117 * 3, device="cuda:0")
+    base = (c, W, act, lst, cnt, rays, g, None, grw, rec, dxn, None)
+    assert H.call(*base) == 0
+    sub = lambda i, v: base[:i] + (v,) + base[i + 1:]   # noqa: E731
+    assert H.call(*base, field=3) == -1 and H.call(*base, mode=3) == -1 and H.call(*base, ray_type=3) == -1
+    assert H.call(*base, field=1) == -1 and H.call(*base, mode=2) == -1, "records of a static field or in feature mode"
+    assert H.call(*sub(9, None)) == -1 and H.call(*sub(9, None), mode=0) == 0, "records exactly with RDRF_APP_RECORDS"
+    assert H.call(*base, S=0) == -1 and H.call(*base, S=4097) == -1 and H.call(*base, N=-1) == -1
+    assert H.call(*base, N=1 << 19, S=4096) == -1, "N S 3 < 2^31"
+    for i in (2, 3, 4, 5, 8, 10):
+        assert H.call(*sub(i, None)) == -1, f"null argument {i}"
+    assert H.call(*sub(2, act.view(-1)[1:]), act_floats=act.numel()) == -1 and H.call(*sub(8, grw[1:])) == -1, "alignment"
+    assert H.call(*sub(9, rec[1:]), rec_floats=rec.numel()) == -1 and H.call(*base, ws=H.ws[4:]) == -1, "alignment"
+    assert H.call(*base, act_floats=act.numel() - 1) == -3 and H.call(*base, grw_floats=4 * 544 * 32 - 1) == -3
+    assert H.call(*base, rec_floats=117 * 216 - 1) == -3 and H.call(*base, ws_bytes=H.ws.numel() - 1) == -3
+    assert H.call(*sub(4, torch.full((64,), 118, dtype=torch.int32, device="cuda:0"))) == -1, "count beyond N S"
+    bad = c["list"].copy()
+    bad[7] = 117
+    assert H.call(*sub(3, dev(bad))) == -1, "a list entry beyond N S"
+    assert H.call(*base, N=0) == 0, "an empty batch is a no-op"
+    cf = Q.app_case("dyn", "feat", 70, 1, 70)
+    assert H.call(cf, W, None, None, None, None, None, None, grw, None, None, None, act_floats=0) == -1, "feature mode takes g_feat"

@@ -33,6 +33,8 @@ PARENT = {
     # (added after that commit: the weight images only, the same at every shape -- held to this as its upper bound)
     'rdrf_selftest_heads_bwd_workspace_bytes': {(1, 1): 4194304, (1, 32): 4194304, (1, 33): 4194304, (33, 45): 4194304, (4, 33):
         4194304, (512, 115): 4194304, (4096, 115): 4194304},
+    'rdrf_selftest_app_bwd_workspace_bytes': {(1, 1): 4194304, (1, 32): 4194304, (1, 33): 4194304, (33, 45): 4194304, (4, 33):
+        4194304, (512, 115): 4194304, (4096, 115): 4194304},
     'rdrf_selftest_scatter_workspace_bytes': {(1, 1): 15616, (1, 32): 16896, (1, 33): 16896, (33, 45): 103936, (4, 33): 23296,
         (512, 115): 3719424, (4096, 115): 29686272},
     'rdrf_frame_depth_loss_workspace_bytes': {(1, 1): 264, (1, 32): 512, (1, 33): 520, (33, 45): 616, (4, 33): 520, (512, 115):
@@ -75,7 +77,7 @@ KEPT = ["rdrf_forward_workspace_bytes", "rdrf_render_workspace_bytes", "rdrf_ren
         "rdrf_render_motion_workspace_bytes", "rdrf_flow_to_image_workspace_bytes", "rdrf_ssim_workspace_bytes",
         "rdrf_frame_depth_loss_workspace_bytes"] + [k for k in PARENT if "saved_bytes" in k]
 DERIVED = ["rdrf_workspace_bytes", "rdrf_features_bwd_workspace_bytes", "rdrf_selftest_warp_bwd_workspace_bytes",
-           "rdrf_selftest_heads_bwd_workspace_bytes",
+           "rdrf_selftest_heads_bwd_workspace_bytes", "rdrf_selftest_app_bwd_workspace_bytes",
            "rdrf_selftest_scatter_workspace_bytes", "rdrf_compute_alpha_workspace_bytes"]
 
 
