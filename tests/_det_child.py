@@ -1,9 +1,13 @@
-"""Child program of the deterministic-library checks (the library is chosen when robust-dynrf_amd._lib is imported, so they run
-in a process of their own with RDRF_DETERMINISTIC=1):
+"""The one child program of the twin-process tests (tests/_twin.py starts it).  The library is chosen when robust-dynrf_amd._lib is
+imported, so a test that compares two libraries runs the other one in a process of its own: librodynrf_det.so with
+RDRF_DETERMINISTIC=1, which this program then asserts it got, or whatever RDRF_LIB names.  Every mode saves its result to OUT
+with torch.save:
 
+    python tests/_det_child.py case MODULE [FUNC [ARG ...]] OUT   MODULE.FUNC(*ARGS) (default det_case); tensors go to the CPU, numpy arrays become tensors, at any depth
     python tests/_det_child.py dw OUT       tests/test_gpu_dw_primitives.py: the exact-integer cases of _DET_SIZES against
                                             librodynrf_det.so, the gradient buffer bound to a fixed-point shadow as the fields
-                                            bind theirs; writes the number of cases that ran to OUT
+                                            bind theirs; the number of cases that ran
+    python tests/_det_child.py dw_runs OUT  tests/test_gpu_dw_runs.py: DET_CASE, the gradient buffer bound the same way
     python tests/_det_child.py scatter OUT  tests/test_gpu_scatter_primitives.py: det_cases(), every call's flat output buffer bound
                                             to a shadow; the planes and lines must not move before the fold
     python tests/_det_child.py poison OUT   tests/test_gpu_poisoned_scratch.py: every case, bit for bit per tensor"""
@@ -15,6 +19,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 
@@ -96,9 +101,33 @@ def poison(L):
     return len(T.CASES) + 1
 
 
+def dw_runs(L):
+    import test_gpu_dw_primitives as T
+    import test_gpu_dw_runs as R
+    plan, flags, ntiles = R.DET_CASE
+    pl = T._plan(plan, flags)
+    pl.call = _bound_call(L, pl)
+    R.exact_with_nan_elsewhere(pl, ntiles)
+    return 1
+
+
+def _to_cpu(v):
+    if isinstance(v, torch.Tensor):
+        return v.detach().cpu()
+    if isinstance(v, (np.ndarray, np.generic)):
+        return torch.from_numpy(np.asarray(v))
+    if isinstance(v, dict):
+        return {k: _to_cpu(x) for k, x in v.items()}
+    return type(v)(_to_cpu(x) for x in v) if isinstance(v, (list, tuple)) else v
+
+
+def case(L, module, func="det_case", *args):
+    return _to_cpu(getattr(importlib.import_module(module), func)(*args))
+
+
 if __name__ == "__main__":
     L = importlib.import_module("robust-dynrf_amd._lib")
-    assert L.DETERMINISTIC and L.lib.rdrf_deterministic() == 1
-    n = {"dw": dw, "scatter": scatter, "poison": poison}[sys.argv[1]](L)
-    with open(sys.argv[2], "w") as f:
-        f.write(str(n))
+    if os.environ.get("RDRF_DETERMINISTIC") == "1":
+        assert L.DETERMINISTIC and L.lib.rdrf_deterministic() == 1
+    mode, *args, out = sys.argv[1:]
+    torch.save({"case": case, "dw": dw, "dw_runs": dw_runs, "scatter": scatter, "poison": poison}[mode](L, *args), out)

@@ -12,6 +12,26 @@ CASES = ["ndc_relu", "ndc_relu_long", "ndc_softplus", "contract_relu_te", "contr
 RTOL = 1e-4
 
 
+def pkg(name="_lib"):
+    """robust-dynrf_amd.<name>, imported on first use (the package's directory name is no Python identifier; importing _lib
+    loads the library, which the CPU tests that import this file must not do)"""
+    import importlib
+    return importlib.import_module("robust-dynrf_amd." + name)
+
+
+def rodynrf():
+    import rodynrf
+    return rodynrf
+
+
+def profile_line(env_var, text):
+    """env_var=<file>: append one line to a profile kept under profiles/ (the tests that measure print the same line)"""
+    path = os.environ.get(env_var)
+    if path:
+        with open(path, "a") as f:
+            f.write(text + "\n")
+
+
 def load_case(name):
     z = np.load(os.path.join(GOLDEN, name + ".npz"))
     g = {k: z[k] for k in z.files}

@@ -7,12 +7,13 @@ import os
 import pytest
 import torch
 
+from _util import pkg
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_library_exports_every_declared_symbol():
-    import importlib
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     hdr = open(os.path.join(ROOT, "include", "rodynrf.h")).read()
     declared = set(re.findall(r"\b(rdrf_[a-z0-9_]+)\s*\(", hdr))
     declared -= {"rdrf_stream_t"}
@@ -28,8 +29,7 @@ def test_signature_table_matches_the_header():
     include/rodynrf.h: an entry per function, the same arity, every scalar parameter and the return value of the matching
     ctypes type, every pointer or array parameter a pointer type.  A prototype the parser cannot read fails the count."""
     import ctypes as C
-    import importlib
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     hdr = open(os.path.join(ROOT, "include", "rodynrf.h")).read()
     hdr = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
     protos = re.findall(r"^\s*((?:const\s+)?[A-Za-z_]\w*(?:\s*\*)?)\s+(rdrf_\w+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M)
@@ -79,7 +79,7 @@ def test_state_dict_contract_and_layout():
     assert p.stride() == (c * h * w, 1, w * c, c)  # XY plane: [y][x][C] storage
     p = dy.density_plane[1]
     _, c, h, w = p.shape
-    F = __import__("importlib").import_module("robust-dynrf_amd.fields")
+    F = pkg("fields")
     want = (c * h * w, 1, c, h * c) if F.Z_FAST else (c * h * w, 1, w * c, c)
     assert p.stride() == want  # XZ plane: [z][x][C] (x fastest) unless fields.Z_FAST
     assert len(st.get_optparam_groups()) == 6 and len(dy.get_optparam_groups()) == 18
@@ -87,9 +87,8 @@ def test_state_dict_contract_and_layout():
 
 
 def test_no_cpu_fallback():
-    import importlib
     import rodynrf
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     rays = torch.zeros(4, 6)
     rays[:, 5] = 1
     with pytest.raises(L.RdrfError):

@@ -1,13 +1,14 @@
 """No GPU: the float64 references of tests/_app_prim.py (the backward-data kernels of the appearance phase) against torch autograd of
 the appearance MLPs written out here from their formulas; a float32 evaluation in the kernels' order against every bound the GPU
 file uses; the power of the generated inputs against eight planted defects; the describe layouts against each other."""
-import importlib
 import os
 import sys
 
 import numpy as np
 import pytest
 import torch
+
+from _util import pkg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -17,16 +18,12 @@ import _app_prim as Q   # noqa: E402
 f64 = np.float64
 
 
-def _L():
-    return importlib.import_module("robust-dynrf_amd._lib")
-
-
 _LAY = {}
 
 
 def _lay(field):
     if field not in _LAY:
-        _LAY[field] = Q.layout(_L(), field)
+        _LAY[field] = Q.layout(pkg(), field)
     return _LAY[field]
 
 
@@ -35,7 +32,7 @@ IDS = [f"{c['field']}-{c['mode']}-{c['N']}x{c['S']}-{c['count']}-{c['ray_type']}
 
 
 def test_entry_points_are_declared_and_sized():
-    L = _L()
+    L = pkg()
     for name in ("rdrf_selftest_app_bwd", "rdrf_selftest_app_describe", "rdrf_selftest_app_bwd_workspace_bytes"):
         assert name in L.SIGNATURES and hasattr(L.lib, name)
         assert name in open(os.path.join(ROOT, "include", "rodynrf.h")).read()
@@ -43,7 +40,7 @@ def test_entry_points_are_declared_and_sized():
 
 
 def test_describe_agrees_with_the_other_describes():
-    L = _L()
+    L = pkg()
     for field in Q.FIELDS:
         lay = _lay(field)   # its assertions: the dz1 job's rows, the P row order, the scatter's first DA row and record size
         dyn = field == "dyn"
@@ -63,7 +60,7 @@ def test_describe_agrees_with_the_other_describes():
 
 def test_geometry_of_the_large_shapes():
     """the smallest tile counts with several waves per workgroup and with waves that take a second tile from the queue"""
-    L = _L()
+    L = pkg()
     for field in Q.FIELDS:
         t_waves, t_walk = Q.large_tiles(L, field)
         assert t_waves < t_walk <= 2050
@@ -76,7 +73,7 @@ def test_geometry_of_the_large_shapes():
 
 def test_errors_of_describe():
     import ctypes as C
-    L = _L()
+    L = pkg()
     buf = (C.c_int * 16)()
     assert L.lib.rdrf_selftest_app_describe(3, 0, 1, 1, buf, 16) == -1
     assert L.lib.rdrf_selftest_app_describe(0, 3, 1, 1, buf, 16) == -1

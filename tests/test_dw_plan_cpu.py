@@ -7,21 +7,18 @@ four, at most 30 blocks, at most 4 (2 in the 2-set instantiation) products per w
 path (density phase with the small layers and the warp MLP formed by their backward-data kernels) no block is staged that no
 product reads; the two-kernel list with both heads live stages exactly one, the K1G_SM bridge."""
 import ctypes as C
-import importlib
 
 import pytest
 
 import _dw_prim as P
+
+from _util import pkg
 
 MAX_RUNS, MAX_BLK, WAVES = 4, 30, 12
 PAIRS = (P.PLANS + [("DENSITY", f) for f in P.DENSITY_FLAGS if f != 3] + [("DENSITY", f) for f in range(8, 16)]
          + [("DYN", f) for f in (13, 14, 15)])
 FLAT = {13: 8, 14: 8, 15: 13}     # flat training path: staged blocks of the density-phase launch (2 dz + 3 + 3; 4 dz + 3 + 3 + 3)
 NTILES = [1, 300, 511, 512, 1025]
-
-
-def _lib():
-    return importlib.import_module("robust-dynrf_amd._lib")
 
 
 def launches(L, plan, flags, ntiles, cap=1 << 14):
@@ -54,14 +51,14 @@ def unused_blocks(launch):
 
 
 def test_symbol_is_bound():
-    L = _lib()
+    L = pkg()
     assert hasattr(L.lib, "rdrf_selftest_dw_plan") and "rdrf_selftest_dw_plan" in L.SYMBOLS
 
 
 @pytest.mark.parametrize("ntiles", [1, 1025])
 @pytest.mark.parametrize("plan,flags", PAIRS, ids=[f"{p}-{f}" for p, f in PAIRS])
 def test_launches_are_well_formed_and_cover_the_job_list(plan, flags, ntiles):
-    L = _lib()
+    L = pkg()
     desc = P.describe(L, plan, flags)
     ls = launches(L, plan, flags, ntiles)
     formed = []
@@ -96,7 +93,7 @@ def test_launches_are_well_formed_and_cover_the_job_list(plan, flags, ntiles):
 @pytest.mark.parametrize("flags", sorted(FLAT))
 @pytest.mark.parametrize("plan", ["DENSITY", "DYN"])
 def test_flat_training_path_stages_only_operands(plan, flags):
-    L = _lib()
+    L = pkg()
     for ntiles in NTILES:
         l = launches(L, plan, flags, ntiles)[-1]           # DYN: the density phase is the second region
         assert len(l["blocks"]) == FLAT[flags]
@@ -107,7 +104,7 @@ def test_flat_training_path_stages_only_operands(plan, flags):
 
 @pytest.mark.parametrize("plan", ["DENSITY", "DYN"])
 def test_two_kernel_list_bridges_the_one_block_hole(plan):
-    L = _lib()
+    L = pkg()
     l = launches(L, plan, 7, 257)[-1]
     un = unused_blocks(l)
     assert len(un) == 1 and un[0][0] == 0, un              # one dz block: K1G_SM between DZ4 and DZD
@@ -117,7 +114,7 @@ def test_two_kernel_list_bridges_the_one_block_hole(plan):
 
 
 def test_error_paths():
-    L = _lib()
+    L = pkg()
     out = (C.c_int * 8)()
     assert L.lib.rdrf_selftest_dw_plan(99, 0, 4, out, 8) == -1 and b"unknown plan" in L.lib.rdrf_last_error()
     assert L.lib.rdrf_selftest_dw_plan(L.DW_PLANS["DENSITY"], 15, 0, out, 8) == -1

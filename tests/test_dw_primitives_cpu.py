@@ -1,13 +1,14 @@
 """CPU side of the stand-alone dW harness (rdrf_selftest_dw, tests/_dw_prim.py): the symbols, the job-list descriptions of every
 plan, the reference builder against a plain loop, and the exactness bound of integer rows at every tile count listed."""
 import ctypes as C
-import importlib
 import os
 
 import numpy as np
 import pytest
 
 import _dw_prim as P
+
+from _util import pkg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -19,7 +20,7 @@ def test_both_libraries_export_the_dw_selftest(name):
 
 
 def test_the_binding_lists_the_dw_selftest():
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     assert "rdrf_selftest_dw" in L.SYMBOLS and "rdrf_selftest_dw_describe" in L.SYMBOLS
 
 
@@ -60,7 +61,7 @@ def test_reference_agrees_with_a_plain_triple_loop():
 def test_parse_round_trip_of_the_product_plans():
     """the description of every plan parses to its full length; every job's rows and blocks lie inside the strides; a plan's
     parameters are fields of the struct it names"""
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     seen = set()
     for plan, flags in P.PLANS + [("DENSITY", f) for f in P.DENSITY_FLAGS]:
         d = P.describe(L, plan, flags)

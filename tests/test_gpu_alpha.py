@@ -4,8 +4,6 @@ F.max_pool3d / np.packbits), sample_alpha against values the reference computed 
 checkpoint keys against a file the reference wrote, updateAlphaMask / filtering_rays end to end."""
 import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,7 +11,8 @@ import torch
 
 import _alpha_prim as A
 from _gpu_util import COMMON
-from _util import GOLDEN, record_margin
+from _twin import CHILD, assert_same_dict, run_twin
+from _util import GOLDEN, pkg, record_margin
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -68,8 +67,7 @@ def check_alpha(name, alpha, sigma_fwd, length):
 @pytest.mark.parametrize("act", ["relu", "softplus"])
 @pytest.mark.parametrize("which", ["static", "dynamic"])
 def test_compute_alpha_matches_forward_sigma(which, act):
-    from importlib import import_module
-    alpha_mod = import_module("robust-dynrf_amd.alpha")
+    alpha_mod = pkg("alpha")
     field = fields(act)[which == "dynamic"]
     for M in (1, 31, 32, 33, 65):
         for Tn in (2, 3):
@@ -88,8 +86,7 @@ def test_compute_alpha_matches_forward_sigma(which, act):
 
 @pytest.mark.parametrize("which", ["static", "dynamic"])
 def test_dense_alpha_with_a_partial_last_slab(which, monkeypatch):
-    from importlib import import_module
-    alpha_mod = import_module("robust-dynrf_amd.alpha")
+    alpha_mod = pkg("alpha")
     field = fields("relu")[which == "dynamic"]
     monkeypatch.setattr(alpha_mod, "SLAB_POINTS", 2 * GRID[1] * GRID[2])   # slabs of 2 rows: 9 = 4 x 2 + 1
     alpha, dense = field.getDenseAlpha()
@@ -134,8 +131,7 @@ def test_compute_alpha_with_a_mask(which):
 
 
 def _build(alpha, thres):
-    from importlib import import_module
-    bits, stats = import_module("robust-dynrf_amd.alpha").build_mask(torch.from_numpy(alpha).to(DEV), thres)
+    bits, stats = pkg("alpha").build_mask(torch.from_numpy(alpha).to(DEV), thres)
     return bits.cpu().numpy(), stats.cpu().tolist()
 
 
@@ -299,9 +295,8 @@ def test_update_alpha_mask_and_filtering_rays(which):
 
 
 def det_case():
-    """the compute_alpha case both libraries run (tests/_alpha_det_child.py)"""
-    from importlib import import_module
-    alpha_mod = import_module("robust-dynrf_amd.alpha")
+    """the compute_alpha case both libraries run (tests/_det_child.py case)"""
+    alpha_mod = pkg("alpha")
     out = {}
     for which in (0, 1):
         field = fields("softplus")[which]
@@ -311,14 +306,5 @@ def det_case():
 
 
 def test_deterministic_library_computes_the_same_alpha(tmp_path):
-    mine = det_case()
-    env = dict(os.environ, RDRF_DETERMINISTIC="1")
-    env.pop("RDRF_MARGINS", None)
-    env.pop("RDRF_LIB", None)
-    out = str(tmp_path / "det.pt")
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_alpha_det_child.py")
-    r = subprocess.run([sys.executable, child, out], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    det = torch.load(out)
-    for k, v in mine.items():
-        assert torch.equal(v.cpu(), det[k]), k
+    ours = det_case()
+    assert_same_dict(run_twin(tmp_path, [CHILD, "case", "test_gpu_alpha"], det=True), ours)

@@ -12,7 +12,6 @@ included.  An output whose reference is exactly 0 (closed gates, padding lanes, 
 0.  No sample is excluded from any comparison.  Every comparison records error / bound with record_margin
 (profiles/app_bwd_margins.txt holds one run)."""
 import ctypes as C
-import importlib
 import os
 import sys
 
@@ -24,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _app_prim as Q   # noqa: E402
-from _util import record_margin   # noqa: E402
+from _util import pkg, record_margin   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 GUARD = 256
@@ -62,8 +61,8 @@ class Harness:
     def __init__(self):
         import rodynrf
         from _gpu_util import COMMON
-        self.L = importlib.import_module("robust-dynrf_amd._lib")
-        self.F = importlib.import_module("robust-dynrf_amd.fields")
+        self.L = pkg()
+        self.F = pkg("fields")
         aabb = torch.tensor([[-1.0, -1.0, -1.0], [1.0, 1.0, 1.0]])
         kw = dict(COMMON, near_far=[0.0, 1.0], density_shift=-10.0, fea2denseAct="relu")
         torch.manual_seed(3)

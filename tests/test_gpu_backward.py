@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import CASES, assert_close, elementwise_excess, record_margin
+from _util import CASES, assert_close, elementwise_excess, pkg, record_margin
 
 pytestmark = pytest.mark.gpu
 
@@ -285,8 +285,7 @@ def test_pruned_branches_match_autograd():
     oracle and every appearance parameter gets NO gradient -- the appearance backward, its scatter
     and its dW jobs are skipped exactly as autograd skips them in the reference."""
     import ctypes as C
-    import importlib
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
 
     def launches(name):
         ms, n = C.c_double(0), C.c_int(0)
@@ -456,8 +455,7 @@ def test_sorted_scatter_passes_the_same_parity_tests():
     the automatic choice from 300 k samples per launch; from there the density / blending passes also take
     their LDS-window form, k_scatter_tiled): the golden-gradient, mid-size oracle gradient, pruning and
     fused-accumulation tests are re-run with the sorted path forced at their small sizes."""
-    import importlib
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     try:
         for mode in ("sorted", "sorted_plain"):   # with the LDS plane windows, and the form large grids fall back to
             L.set_scatter_mode(mode)
@@ -478,11 +476,10 @@ def test_tiled_scatter_matches_plain_sorted_scatter_at_benchmark_shape():
     4096 rays x 115 samples at grid [141,157,94], both heads live -- instead of only through the cross-path bound of the
     trainer test: the two paths form the same sums in another order, so their distance must stay within 3 x the
     run-to-run spread of ONE path (fp32 atomics arrive in a different order every run), floor 2e-6 relative L2."""
-    import importlib
     import rodynrf
-    S_ = importlib.import_module("robust-dynrf_amd.step")
-    L = importlib.import_module("robust-dynrf_amd._lib")
-    RU = importlib.import_module("robust-dynrf_amd.ray_utils")
+    S_ = pkg("step")
+    L = pkg()
+    RU = pkg("ray_utils")
     cfg = S_.scene_config("nvidia", "stage0")
     dev = torch.device("cuda", 0)
     st, dy = S_.build_fields(cfg, dev)

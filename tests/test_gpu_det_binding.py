@@ -10,25 +10,21 @@ and sorted / tiled scatter (rdrf_scatter.hip), dW products (rdrf_dw.hip) -- thro
 sorted scatter mode, feature mode and scene flow, at the shapes of smoke().  No parameter slice is excluded from the
 zero assertion: no kernel of these paths writes a parameter gradient other than through grad_add."""
 import json
-import os
-import subprocess
-import sys
 
 import pytest
 
+from _twin import CHILD, run_twin
+from _util import pkg
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _child():
-    import importlib
-
+def det_case():
+    """what the deterministic library runs (tests/_det_child.py case): one report line per step"""
     import torch
-    sys.path.insert(0, ROOT)
     import rodynrf
     from _gpu_util import COMMON, make_rays
-    L = importlib.import_module("robust-dynrf_amd._lib")
-    assert L.DETERMINISTIC and L.lib.rdrf_deterministic() == 1
+    L = pkg()
     torch.manual_seed(3)
     N, S, M, grid = 48, 40, 100, [24, 26, 16]
     dev = "cuda:0"
@@ -104,20 +100,11 @@ def _child():
     sf_f, sf_b = dy.get_forward_backward_scene_flow(gx, ct)
     ((sf_f * w_rgb).sum() + (sf_b * w_rgb.flip(0)).sum()).backward()
     check("scene flow", dy)
-    assert len(report) == 6
     assert not bad, "\n".join(bad)
+    return report
 
 
-def test_every_gradient_addition_reaches_the_fixed_point_shadow():
-    env = dict(os.environ, RDRF_DETERMINISTIC="1")
-    env.pop("RDRF_LIB", None)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "child"], env=env, cwd=ROOT, capture_output=True, text=True,
-                       timeout=600)
-    print(r.stdout)
-    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
-    assert r.stdout.count('"step"') == 6, r.stdout
-
-
-if __name__ == "__main__":
-    assert sys.argv[1:] == ["child"]
-    _child()
+def test_every_gradient_addition_reaches_the_fixed_point_shadow(tmp_path):
+    report = run_twin(tmp_path, [CHILD, "case", "test_gpu_det_binding"], det=True)
+    print("\n".join(json.dumps(r) for r in report))
+    assert len(report) == 6, report

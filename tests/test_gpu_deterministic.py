@@ -9,7 +9,7 @@ import sys
 import pytest
 import torch
 
-from _util import record_margin
+from _util import pkg, record_margin
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,8 +48,7 @@ def test_deterministic_build_is_bit_reproducible_and_matches_the_atomic_build(tm
 
 
 def test_product_build_refuses_the_deterministic_entry_points():
-    import importlib
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     if L.DETERMINISTIC:
         pytest.skip("running under the deterministic build")
     assert L.lib.rdrf_deterministic() == 0

@@ -13,17 +13,14 @@ int64 / float64 reference built from rdrf_selftest_dw_describe alone (tests/_dw_
 (d) the row contract of rdrf_dw.hip from the kernel's side: 3e38 in the activation slots past `count` changes no bit.
 (e) error paths; the deterministic library gives the bits of (a)."""
 import ctypes as C
-import importlib
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import _dw_prim as P
-from _util import record_margin
+from _twin import CHILD, run_twin
+from _util import pkg, profile_line, record_margin
 
 pytestmark = pytest.mark.gpu
 
@@ -35,15 +32,11 @@ def _ids(plans):
     return [f"{p}-{f}" for p, f in plans]
 
 
-def _lib():
-    return importlib.import_module("robust-dynrf_amd._lib")
-
-
 class Plan:
     """a plan's description, and its gradient tensors as views of one flat cuda buffer behind the struct the product passes"""
 
     def __init__(self, plan, flags):
-        L = _lib()
+        L = pkg()
         self.plan, self.flags = plan, flags
         self.desc = P.describe(L, plan, flags)
         self.cls = L.RdrfDynamicParams if self.desc["dynamic"] else L.RdrfStaticParams
@@ -74,7 +67,7 @@ class Plan:
 
     def call(self, A, B, ntiles, count=None, pre=None, check=True):
         """A, B: flat cuda rows; pre: flat float64 numpy pre-fill (None: keep).  Returns (rc, flat gradients)"""
-        L = _lib()
+        L = pkg()
         if pre is not None:
             self.flat.copy_(torch.from_numpy(pre).float())
         cnt = None if count is None else torch.tensor([count], dtype=torch.int32, device="cuda")
@@ -209,14 +202,6 @@ def test_one_product_at_a_time(plan, flags):
 
 
 # ---- (c) accuracy on real numbers -----------------------------------------------------------------------------------------
-def _profile_line(text):
-    """RDRF_DW_PRIM_TABLE=<file>: one line per case (measured e beside e_seq32), for profiles/"""
-    path = os.environ.get("RDRF_DW_PRIM_TABLE")
-    if path:
-        with open(path, "a") as f:
-            f.write(text + "\n")
-
-
 def _e_seq32(desc, A, B, ntiles, rows_per_job=4):
     """the metric of a sequential fp32 accumulation in sample order, over rows_per_job out rows of every job (all columns,
     and the bias): max |sum32 - sum64| / sum |dz| |in|"""
@@ -276,7 +261,7 @@ def test_dense_accuracy_against_float64(plan, flags, ntiles):
     rel = np.abs(got[own] - ref[own]) / mag[own]
     e = float(rel.max())
     print(f"{plan}-{flags} ntiles = {ntiles}: e = {e:.3e}   e_seq32 = {e32:.3e}   e / e_seq32 = {e / e32:.3f}")
-    _profile_line(f"{plan:12s} {flags:2d} {ntiles:4d} {e:.3e} {e32:.3e} {e / e32:.3f}")
+    profile_line("RDRF_DW_PRIM_TABLE", f"{plan:12s} {flags:2d} {ntiles:4d} {e:.3e} {e32:.3e} {e / e32:.3f}")
     record_margin(f"dW {plan}-{flags} ntiles {ntiles} e / (2 e_seq32)", e / bound)
     assert e <= bound, (f"{plan}-{flags} ntiles = {ntiles}: e = {e:.3e} > 2 x e_seq32 = {bound:.3e} (e_seq32 is the largest error of "
                         "4 sampled out rows per job, e of all rows: if this misses narrowly, compare on all rows before blaming the kernel)")
@@ -305,7 +290,7 @@ def test_finite_activations_behind_zero_dz_change_no_bit(plan, flags, count):
 
 # ---- (e) error paths, the deterministic library ---------------------------------------------------------------------------
 def test_error_paths():
-    L = _lib()
+    L = pkg()
     pl = _plan("STATIC_FEA", 0)
     sa, sb, _ = pl.desc["regions"][0]
     A, B = torch.ones(2 * sa * 32, device="cuda"), torch.ones(2 * sb * 32, device="cuda")
@@ -363,10 +348,4 @@ def _det_case(plan, flags, size, kind):
 def test_same_bits_in_the_deterministic_library(tmp_path):
     """librodynrf_det.so in a child process (the library is chosen at import), its gradient buffer bound to a fixed-point
     shadow as the fields bind theirs: after the fold, the int64 sums again, bit for bit"""
-    path = str(tmp_path / "det.txt")
-    env = dict(os.environ, RDRF_DETERMINISTIC="1")
-    env.pop("RDRF_LIB", None)
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_det_child.py")
-    r = subprocess.run([sys.executable, child, "dw", path], env=env, timeout=600, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert int(open(path).read()) == 2 * len(P.PLANS) + len(P.COUNT_PLANS)
+    assert run_twin(tmp_path, [CHILD, "dw"], det=True) == 2 * len(P.PLANS) + len(P.COUNT_PLANS)

@@ -7,9 +7,6 @@ sums built from rdrf_selftest_dw_describe alone (tests/_dw_prim.py).  Every row 
 HB and the dz rows no job names: what used to be staged as bridges -- holds NaN: a plan that stages one of them and multiplies it,
 or addresses a run one block off, cannot stay bit-equal.  Tile counts give a workgroup 0, 1, 2 or 3 tiles at grids of 256 and of
 512 and both buffer parities at loop exit."""
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,6 +14,8 @@ import torch
 
 import _dw_prim as P
 import test_gpu_dw_primitives as T
+
+from _twin import CHILD, run_twin
 
 pytestmark = pytest.mark.gpu
 
@@ -75,10 +74,4 @@ def test_one_product_at_a_time(plan, flags):
 def test_same_bits_in_the_deterministic_library(tmp_path):
     """librodynrf_det.so in a child process (the library is chosen at import): DET_CASE, the gradient buffer bound to a
     fixed-point shadow, gives the int64 sums bit for bit"""
-    path = str(tmp_path / "det.txt")
-    env = dict(os.environ, RDRF_DETERMINISTIC="1")
-    env.pop("RDRF_LIB", None)
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_dw_runs_child.py")
-    r = subprocess.run([sys.executable, child, path], env=env, timeout=300, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert int(open(path).read()) == 1
+    assert run_twin(tmp_path, [CHILD, "dw_runs"], det=True, timeout=300) == 1

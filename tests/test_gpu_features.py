@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import CASES, GOLDEN, assert_close
+from _util import CASES, GOLDEN, assert_close, pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -145,8 +145,7 @@ def test_features_fused_grad_and_no_grad_paths():
     """fused_grad accumulates the compute_* gradients straight into the flat buffer; under no_grad
     nothing is saved; a second backward raises instead of crashing."""
     from _gpu_util import fields_from_case
-    import importlib
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     g, st, dy, _ = fields_from_case("ndc_relu")
     xn = torch.from_numpy(g["fn.xn"]).cuda()
     t = torch.from_numpy(g["fn.t"]).cuda()
@@ -226,11 +225,10 @@ def test_packed_weight_images_follow_the_weights():
     """The packed MLP images are cached per (weights, stream): an optimiser-style in-place update, a `.data` edit
     followed by invalidate_packed(), and a FlatAdam step must all be seen by the next call; results equal the
     uncached path bit for bit."""
-    import importlib
     import rodynrf
     from _gpu_util import COMMON, make_rays
-    F = importlib.import_module("robust-dynrf_amd.fields")
-    O_ = importlib.import_module("robust-dynrf_amd.optim")
+    F = pkg("fields")
+    O_ = pkg("optim")
     torch.manual_seed(2)
     aabb = torch.tensor([[-1.5, -1.67, -1.0], [1.5, 1.67, 1.0]])
     kw = dict(COMMON, near_far=[0.0, 1.0], density_shift=-10.0, fea2denseAct="relu")

@@ -8,29 +8,26 @@ which sums it over the lanes of the sample's tile slot, so there it agrees to fp
 g_rays and g_z (tile composition changes the order of the dW partial sums and of d(tout)).  That the deterministic library,
 which runs the flat form by default, gives identical parameter gradients run after run is the check of
 test_gpu_deterministic.py (complete training steps at S = 40 and at the benchmark's S = 115)."""
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "robust-dynrf_amd")
-TOOLS_LIB = os.path.join(PKG, "librodynrf_tools.so")
+from _twin import CHILD, run_twin, tools_lib
+from _util import pkg
+
 # S = 115 at the benchmark's 4096 rays (sorted scatter), S = 13 (nvidia_no_poses / davis stage 0), S = 270, and batches
 # whose N * S is not a multiple of 32 (the last flat tile is partial)
 SHAPES = [(4096, 115), (1024, 13), (1001, 13), (512, 270), (1000, 115)]
 
 
-def _child(out, N, S, mode):
+def density_case(N, S, mode):
+    """what both settings of RDRF_FLAT compute (tests/_det_child.py case)"""
     import torch
-    sys.path.insert(0, ROOT)
-    import importlib
     import rodynrf
-    St = importlib.import_module("robust-dynrf_amd.step")
-    RU = importlib.import_module("robust-dynrf_amd.ray_utils")
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    N, S = int(N), int(S)
+    St = pkg("step")
+    RU = pkg("ray_utils")
+    L = pkg()
     L.set_scatter_mode(mode)
     torch.manual_seed(0)
     cfg = St.scene_config("nvidia", "stage0")
@@ -61,16 +58,13 @@ def _child(out, N, S, mode):
     for n, p in dy.named_parameters():
         if p.grad is not None:
             res["p." + n] = p.grad.cpu().numpy()
-    np.savez(out, **res)
+    return res
 
 
-def _run(tmp, tag, N, S, env, mode="auto"):
-    out = os.path.join(tmp, f"{tag}_{N}_{S}_{mode}.npz")
-    e = dict(os.environ, **env)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), out, str(N), str(S), mode], env=e, cwd=ROOT,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (tag, r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    return dict(np.load(out))
+def _run(tmp_path, N, S, flat, mode):
+    res = run_twin(tmp_path, [CHILD, "case", "test_gpu_flat_density", "density_case", str(N), str(S), mode], lib=tools_lib(),
+                   extra_env={"RDRF_FLAT": flat})
+    return {k: v.numpy() for k, v in res.items()}
 
 
 def _rel(a, b):
@@ -82,10 +76,8 @@ def _rel(a, b):
 @pytest.mark.parametrize("mode", ["auto", "sorted"])
 @pytest.mark.parametrize("N,S", SHAPES)
 def test_flat_density_phase_matches_wave_per_ray(tmp_path, N, S, mode):
-    if not os.path.exists(TOOLS_LIB):
-        subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc"), "-j16", "tools"], timeout=1800)
-    base = _run(str(tmp_path), "ray", N, S, {"RDRF_LIB": TOOLS_LIB, "RDRF_FLAT": "0"}, mode)
-    flat = _run(str(tmp_path), "flat", N, S, {"RDRF_LIB": TOOLS_LIB, "RDRF_FLAT": "1"}, mode)
+    base = _run(tmp_path, N, S, "0", mode)
+    flat = _run(tmp_path, N, S, "1", mode)
     assert sorted(base) == sorted(flat)
     bad = []
     for k in sorted(base):
@@ -101,6 +93,3 @@ def test_flat_density_phase_matches_wave_per_ray(tmp_path, N, S, mode):
                 bad.append(f"{k}: rel. L2 {r:.3e}")
     assert not bad, "\n".join(bad)
 
-
-if __name__ == "__main__":
-    _child(sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), sys.argv[4])

@@ -1,13 +1,12 @@
 """Induced flow / disparity (renderer.py:1266-1392) through the C ABI against the
 vectors generated from the reference and against the oracle at the benchmark shape."""
-import importlib
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from _util import assert_close
+from _util import assert_close, pkg
 
 pytestmark = pytest.mark.gpu
 G = np.load(os.path.join(os.path.dirname(__file__), "golden", "induce_flow.npz"))
@@ -123,7 +122,7 @@ def test_gather_rows_backward_matches_torch_index_backward(T, N):
     """ray_utils.gather_rows (the [T,3,4] camera matrices of the neighbour frames, train.py:1895-1948): forward = table[idx]
     bit for bit, backward (rdrf_rows_scatter_add: LDS accumulation per workgroup; the 1000-row table takes the global-atomic
     fallback) against torch's index backward."""
-    RU = importlib.import_module("robust-dynrf_amd.ray_utils")
+    RU = pkg("ray_utils")
     dev = torch.device("cuda", 0)
     g = torch.Generator().manual_seed(5)
     table = torch.randn(T, 3, 4, generator=g).to(dev)

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import CASES, FWD_ELEM, assert_close
+from _util import CASES, FWD_ELEM, assert_close, pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -134,8 +134,7 @@ def test_selftest_mfma_layer():
     """The MFMA layer primitive (pack -> LDS -> v_mfma_f32_32x32x2_f32 chain) against a matmul with
     an ASYMMETRIC weight (catches operand / output transposes)."""
     import ctypes as C
-    import importlib
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     g = torch.Generator().manual_seed(0)
     M = 77
     x = torch.randn(M, 64, generator=g).cuda()
@@ -309,11 +308,10 @@ def test_c_abi_error_paths():
     """The C entry points never crash on bad arguments: they return a negative code and leave a
     message for rdrf_last_error() (which the ctypes binding turns into RdrfError)."""
     import ctypes as C
-    import importlib
     import rodynrf
     from _gpu_util import fields_from_case
-    L = importlib.import_module("robust-dynrf_amd._lib")
-    F = importlib.import_module("robust-dynrf_amd.fields")
+    L = pkg()
+    F = pkg("fields")
     g, st, dy, _ = fields_from_case("ndc_relu")
     dev = "cuda"
     rays = torch.from_numpy(g["rays"]).to(dev)

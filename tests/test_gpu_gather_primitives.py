@@ -11,7 +11,6 @@ product; an fma only lowers it) and |err| <= 32 u sum_f P_f Lm_f for the static 
 the bound of test_abi_cpu.py::test_sincos_pe_formula on the fast path, 4 ulp of 1 (OpenCL's sin / cos accuracy, |result| <= 1) for
 every lane of a wave that holds a wild lane.  The ratios of one RDRF_MARGINS run are in profiles/gather_margins.txt."""
 import ctypes as C
-import importlib
 
 import numpy as np
 import pytest
@@ -19,7 +18,7 @@ import torch
 
 import _gather_prim as G
 from _scatter_prim import plane_dims
-from _util import FWD_ELEM, elementwise_excess, record_margin
+from _util import FWD_ELEM, elementwise_excess, pkg, record_margin
 
 pytestmark = pytest.mark.gpu
 
@@ -27,15 +26,11 @@ GUARD = -7.0
 f32 = np.float32
 
 
-def _L():
-    return importlib.import_module("robust-dynrf_amd._lib")
-
-
 class DevSets:
     """factor sets on the device as an RdrfVM array; order "W": planes stored [H][W][C], "H": [W][H][C]"""
 
     def __init__(self, kind, sets, grid, order="W"):
-        L = _L()
+        L = pkg()
         self.kind, self.n = kind, len(sets)
         self.vm = (L.RdrfVM * self.n)()
         self.keep = []
@@ -52,7 +47,7 @@ class DevSets:
 
     def run(self, xn):
         """-> [nsets][M][F] float64; the rows behind M keep their fill"""
-        L = _L()
+        L = pkg()
         xn = np.ascontiguousarray(xn, dtype=f32).reshape(-1, 3)
         M = xn.shape[0]
         F = 1 if self.kind == "STATIC_DENSITY" else G.nfeat(self.kind)
@@ -254,7 +249,7 @@ def test_dynamic_feature_entry_points(how, grid):
 
 # ---- encodings ---------------------------------------------------------------------------------------------------------------
 def _run_encodings(xn, t):
-    L = _L()
+    L = pkg()
     xn = np.ascontiguousarray(xn, dtype=f32).reshape(-1, 3)
     t = np.ascontiguousarray(t, dtype=f32).reshape(-1)
     M = len(t)

@@ -11,7 +11,6 @@ near-singular sets, where elements whose divisor bound exceeds RHO_LIMIT are che
 meets the same bounds on the same cases (test_geom_primitives_cpu.py); profiles/geom_kernels_margins.txt holds both sets of ratios
 and the mutation table."""
 import ctypes as C
-import importlib
 import types
 
 import numpy as np
@@ -19,13 +18,9 @@ import pytest
 import torch
 
 import _geom_prim as G
-from _util import record_margin
+from _util import pkg, record_margin
 
 pytestmark = pytest.mark.gpu
-
-
-def _L():
-    return importlib.import_module("robust-dynrf_amd._lib")
 
 
 def _cu(a):
@@ -46,7 +41,7 @@ def _raygen_fwd(c):
 
 
 def _raygen_bwd(c, g):
-    L = _L()
+    L = pkg()
     ids, uv, poses, focal = _cu(c["ids"]), _cu(c["uv"]), _cu(c["poses"]), _cu(np.asarray(c["focal"]).reshape(1))
     gp, gf, tg = _cu(c["pre_p"]), _cu(c["pre_f"]), _cu(g)
     L.check(L.lib.rdrf_generate_rays_uv_bwd(L.ptr(ids), L.ptr(uv), c["view_shift"], L.ptr(poses), L.ptr(focal), len(c["ids"]), c["T"],
@@ -151,7 +146,7 @@ def test_samplers_match_float64(kind):
 @pytest.mark.parametrize("kind", ["ndc", "contract"])
 def test_sample_bwd_matches_float64(kind):
     """g_rays += onto a pre-fill; contract rows with samples on both sides of nrm = 1 and the arg-max on every axis and sign"""
-    L = _L()
+    L = pkg()
     for S in G.SAMPLE_BWD_S:
         for N in (1, 3, 6):
             c = G.sample_bwd_case(kind, N, S)
@@ -161,7 +156,7 @@ def test_sample_bwd_matches_float64(kind):
 
 
 def _world_bwd(c):
-    L = _L()
+    L = pkg()
     rays, z, g, gz, gr = _cu(c["rays"]), _cu(c["z"]), _cu(c["g"]), _cu(c["gz"]), _cu(c["pre"])
     ab = (C.c_float * 6)(*[float(v) for v in np.asarray(c["box"]).reshape(-1)])
     L.check(L.lib.rdrf_sample_world_bwd(L.ptr(rays), L.ptr(z), z.shape[0], z.shape[1], c["near"], c["far"], ab, L.ptr(g), L.ptr(gz), L.ptr(gr),
@@ -183,7 +178,7 @@ def test_sample_world_bwd_matches_float64(S):
 
 # ---- induced flow -----------------------------------------------------------------------------------------------------------
 def _flow_gpu(c, g_flow=True, g_disp=True, null=None):
-    L = _L()
+    L = pkg()
     N, S = c["w"].shape
     rt = L.RAY_TYPES["contract" if c["contract"] else "ndc"]
     f, c2w, w, pts, p2d, rays = (_cu(np.asarray(c[k]).reshape(1) if k == "focal" else c[k]) for k in ("focal", "c2w", "w", "pts", "p2d", "rays"))

@@ -3,12 +3,11 @@ phases) captured as a HIP graph and replayed.  A replay must be THE iteration th
 parameters, ray indices, sampling jitter, white-background coins and iteration scalars -- all of which change from
 replay to replay and reach the captured kernels through static device memory only (ABI 6: white_dev of
 rdrf_composite_*, coef_dev of RdrfLossTerm)."""
-import importlib
 
 import pytest
 import torch
 
-from _util import assert_close, record_margin
+from _util import assert_close, pkg, record_margin
 
 pytestmark = pytest.mark.gpu
 
@@ -39,7 +38,7 @@ def _sync_eager_to(tr_e, tr_g):
 
 @pytest.mark.parametrize("name", ["nvidia", "nvidia_no_poses", "davis"])
 def test_captured_iteration_replays_the_eager_iteration(name):
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     dev = torch.device("cuda", 0)
     cfg = S_.scene_config(name, "stage0")
     cfg.update(SHAPES[name])
@@ -98,7 +97,7 @@ def test_captured_iteration_replays_the_eager_iteration(name):
 def test_graph_training_run_reduces_loss():
     """the same short run as test_short_training_run_reduces_loss, through replays (Adam, TV and the learning-rate decay
     stay outside the graph and must keep acting on the buffers the captured kernels read)"""
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     cfg = S_.balloon1_config("stage0")
     cfg.update(grid=[36, 40, 24], n_samples=48, batch_size=512, H=27, W=48, T=6)
     cfg["focal"] = max(cfg["H"], cfg["W"]) / 2.0 * 3.0 ** 0.5
@@ -115,7 +114,7 @@ def test_graph_training_run_reduces_loss():
 
 
 def test_graph_refuses_data_parallel_shards():
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     cfg = S_.balloon1_config("stage0")
     cfg.update(grid=[24, 26, 16], n_samples=24, batch_size=64, H=27, W=48, T=6)
     tr = S_.Trainer(cfg, torch.device("cuda", 0), graph=True)

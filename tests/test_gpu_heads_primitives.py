@@ -16,7 +16,6 @@ Time branch backward: every dtout / dtp slot dtout_of_ray must not read holds Na
 the relu gate classes of the generator (exactly 0 by construction, or 16 forward bounds away) leave nothing to exclude.
 Every comparison records error / bound with record_margin (profiles/heads_time_margins.txt holds one run)."""
 import ctypes as C
-import importlib
 import os
 import sys
 
@@ -28,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _heads_prim as Q   # noqa: E402
-from _util import record_margin   # noqa: E402
+from _util import pkg, record_margin   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 GUARD = 256
@@ -39,15 +38,11 @@ SMALL = ("dw2", "db2", "bw2", "bb2")
 TIME = ("l1w", "l1b", "l2w", "l2b")
 
 
-def _L():
-    return importlib.import_module("robust-dynrf_amd._lib")
-
-
 def _pidx():
     """position of each replaced tensor in the dynamic field's parameter list, from the field names of RdrfDynamicParams: the list
     is the planes and lines of the factor sets (six tensors per RdrfVM field), then one tensor per pointer field in struct order
     (robust-dynrf_amd/_params.py _dynamic_struct)"""
-    L = _L()
+    L = pkg()
     fields = L.RdrfDynamicParams._fields_
     nvm = sum(1 for _, t in fields if t is L.RdrfVM)
     names = [n for n, t in fields if t is not L.RdrfVM]
@@ -81,8 +76,8 @@ class Harness:
     def __init__(self):
         import rodynrf
         from _gpu_util import COMMON
-        self.L = _L()
-        self.F = importlib.import_module("robust-dynrf_amd.fields")
+        self.L = pkg()
+        self.F = pkg("fields")
         aabb = torch.tensor([[-1.0, -1.0, -1.0], [1.0, 1.0, 1.0]])
         kw = dict(COMMON, near_far=[0.0, 1.0], density_shift=Q.SHIFT, fea2denseAct="relu")
         torch.manual_seed(3)

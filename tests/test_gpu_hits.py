@@ -20,10 +20,6 @@ k counted from the kernel's operations in units of 2^-24, the largest relative e
     the slope, and is taken from the reference itself, as test_gpu_track_vis.py takes the rounding of its query depth.
 Depth: |z_hit - z_ref| <= residual bound / slope + 2 ulp(z), on the rays above _hits_prim.SLOPE_FLOOR."""
 import functools
-import importlib
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -32,7 +28,9 @@ import torch
 import _hits_prim as H
 import _track_vis_prim as P
 import test_gpu_track_vis as V
-from _util import RTOL, record_margin
+import _util
+from _twin import CHILD, assert_same_dict, run_twin, same_bits
+from _util import RTOL, pkg, record_margin
 from oracle import rodynrf_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -42,24 +40,13 @@ U24 = H.U24
 T8 = H.TAUS[8]
 
 
-def _rodynrf():
-    import rodynrf
-    return rodynrf
-
-
-def _same(a, b):
-    if a.dtype == torch.bool or a.dtype == torch.uint8:
-        return a.shape == b.shape and torch.equal(a, b)
-    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
 def same_hits(a, b):
-    return all(_same(a[n], b[n]) for n in ("z", "hit", "xyz", "owner"))
+    return all(same_bits(a[n], b[n]) for n in ("z", "hit", "xyz", "owner"))
 
 
 def from_planes(rt, pl, tau, sel=None):
     rays, z, ss, sd, b = (t.to(DEV) if sel is None else t[sel].to(DEV) for t in pl)
-    return _rodynrf().hits_from_planes(rays, z, ss, sd, b, tau=tau, ray_type=rt, distance_scale=H.DISTANCE_SCALE[rt])
+    return _util.rodynrf().hits_from_planes(rays, z, ss, sd, b, tau=tau, ray_type=rt, distance_scale=H.DISTANCE_SCALE[rt])
 
 
 check_against_reference = H.check_against_reference
@@ -85,13 +72,13 @@ def test_hits_from_planes_against_the_float64_reference(rt, S, N):
     for n_tau in (1, 3):
         sub = from_planes(rt, pl, H.TAUS[n_tau])
         rows = [T8.index(t) for t in H.TAUS[n_tau]]
-        assert all(_same(sub[n], got[n][rows]) for n in ("z", "hit", "xyz", "owner")), n_tau
+        assert all(same_bits(sub[n], got[n][rows]) for n in ("z", "hit", "xyz", "owner")), n_tau
     one = from_planes(rt, pl, 0.5)
-    assert one["z"].shape == (N,) and _same(one["z"], got["z"][3]) and _same(one["xyz"], got["xyz"][3])
+    assert one["z"].shape == (N,) and same_bits(one["z"], got["z"][3]) and same_bits(one["xyz"], got["xyz"][3])
     assert same_hits(from_planes(rt, pl, T8), got)
     for i in sorted({0, N // 2, N - 1}):
         alone = from_planes(rt, pl, T8, sel=slice(i, i + 1))
-        assert all(_same(alone[n], got[n][:, i:i + 1]) for n in ("z", "hit", "xyz", "owner")), i
+        assert all(same_bits(alone[n], got[n][:, i:i + 1]) for n in ("z", "hit", "xyz", "owner")), i
     # monotone in tau, bit for bit: the depth never falls, a ray that misses a level misses every later one
     zz, hh = got["z"], got["hit"]
     assert bool((zz[1:] >= zz[:-1]).all()) and bool((hh[1:].int() <= hh[:-1].int()).all())
@@ -99,7 +86,7 @@ def test_hits_from_planes_against_the_float64_reference(rt, S, N):
     if rt == "ndc":
         rays = pl[0].to(DEV)
         want = rays[None, :, :3] + rays[None, :, 3:] * got["z"][..., None]
-        assert _same(got["xyz"], want)
+        assert same_bits(got["xyz"], want)
 
 
 # ---- 2. regimes, each on the smallest shape that shows it --------------------------------------------------------------
@@ -154,7 +141,7 @@ def test_regimes(rt):
     hn[0, 8] = float("nan")
     clean, got = from_planes(rt, (rays, z, zero, half, torch.ones(1, S)), T8), from_planes(rt, (rays, z, zero, hn, torch.ones(1, S)), T8)
     assert bool(clean["hit"][:4].all()) and not bool(clean["hit"][4:].any())
-    assert all(_same(got[n][:4], clean[n][:4]) for n in ("z", "hit", "xyz", "owner"))
+    assert all(same_bits(got[n][:4], clean[n][:4]) for n in ("z", "hit", "xyz", "owner"))
     assert not bool(got["hit"][4:].any()) and bool(torch.isnan(got["z"][4:]).all()) and bool(torch.isnan(got["xyz"][4:]).all())
     bn = torch.ones(1, S)
     bn[0, 2] = float("nan")                           # a NaN blending in front of everything
@@ -196,7 +183,7 @@ def batch(rt, n=96):
 @pytest.mark.parametrize("rt", ["ndc", "contract"])
 @pytest.mark.parametrize("S", [13, 65])
 def test_render_hits_paths_maps_and_planes(rt, S):
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     _, st, dy = V.scene(rt)[:3]
     rays, ts = batch(rt)
     dens = rodynrf.render_hits(st, dy, rays, ts, T8, N_samples=S, ray_type=rt)
@@ -204,9 +191,9 @@ def test_render_hits_paths_maps_and_planes(rt, S):
     assert same_hits(dens, full)                                     # the density-only path and the render give equal bits
     maps = rodynrf.render_rays(st, dy, rays, ts, N_samples=S, ray_type=rt, maps=True)
     for n in rodynrf.RenderMaps._fields:
-        assert _same(full[n], getattr(maps, n)), n
+        assert same_bits(full[n], getattr(maps, n)), n
     some = rodynrf.render_hits(st, dy, rays, ts, T8, N_samples=S, ray_type=rt, maps=("depth", "acc_d"))
-    assert same_hits(some, full) and _same(some["depth"], maps.depth) and "rgb" not in some
+    assert same_hits(some, full) and same_bits(some["depth"], maps.depth) and "rgb" not in some
     # the kernel alone on forward()'s own planes
     with torch.no_grad():
         xyz, z, valid = rodynrf.sampleXYZ(dy, rays, S, ray_type=rt, is_train=False)
@@ -217,7 +204,7 @@ def test_render_hits_paths_maps_and_planes(rt, S):
     # a miss sits on the last sample, with that sample's bits
     miss = ~dens["hit"]
     assert bool(dens["hit"].any())
-    assert _same(dens["xyz"][miss], xyz[:, -1][None].expand(8, -1, -1)[miss]) and bool((dens["z"][miss] == z[:, -1][None].expand(8, -1)[miss]).all())
+    assert same_bits(dens["xyz"][miss], xyz[:, -1][None].expand(8, -1, -1)[miss]) and bool((dens["z"][miss] == z[:, -1][None].expand(8, -1)[miss]).all())
     # against the float64 reference on these planes (the inputs of a trained-like field, not synthetic ones)
     pl = tuple(t.cpu() for t in (rays, z, o_s.sigma, o_d.sigma, o_d.blending))
     worst = check_against_reference(rt, pl, dens, T8, f"{rt} S={S} render_hits", scale=float(dy.distance_scale))[0]
@@ -229,7 +216,7 @@ def test_hits_against_the_oracle_end_to_end(rt):
     """the oracle's own sigmas and blending through the float64 reference: the transmittance of the ORACLE's planes at the
     native z_hit equals L within RTOL, the bound test_visibility_against_the_oracle_end_to_end puts on its visibilities"""
     from _gpu_util import oracle_cfg, oracle_sd
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     g, st, dy = V.scene(rt)[:3]
     rays, ts = batch(rt, 24)
     S = 13
@@ -258,8 +245,8 @@ def test_hits_against_the_oracle_end_to_end(rt):
 
 @pytest.mark.parametrize("rt", ["ndc", "contract"])
 def test_batch_run_and_chunks_give_the_same_bits(rt, monkeypatch):
-    rodynrf = _rodynrf()
-    R = importlib.import_module("robust-dynrf_amd.renderer")
+    rodynrf = _util.rodynrf()
+    R = pkg("renderer")
     _, st, dy = V.scene(rt)[:3]
     rays, ts = batch(rt)
     S = 65
@@ -267,19 +254,19 @@ def test_batch_run_and_chunks_give_the_same_bits(rt, monkeypatch):
     assert same_hits(rodynrf.render_hits(st, dy, rays, ts, T8, N_samples=S, ray_type=rt, maps=("rgb",)), whole)
     for i in (0, 41, 95):
         alone = rodynrf.render_hits(st, dy, rays[i:i + 1], ts[i:i + 1], T8, N_samples=S, ray_type=rt)
-        assert all(_same(alone[n], whole[n][:, i:i + 1]) for n in ("z", "hit", "xyz", "owner")), i
+        assert all(same_bits(alone[n], whole[n][:, i:i + 1]) for n in ("z", "hit", "xyz", "owner")), i
     one = rodynrf.render_hits(st, dy, rays, ts, 0.9, N_samples=S, ray_type=rt)
-    assert all(_same(one[n], whole[n][5]) for n in ("z", "hit", "xyz", "owner"))
+    assert all(same_bits(one[n], whole[n][5]) for n in ("z", "hit", "xyz", "owner"))
     monkeypatch.setattr(R, "_hits_chunk", lambda N, S: 37)
     parts = rodynrf.render_hits(st, dy, rays, ts, T8, N_samples=S, ray_type=rt, maps=("rgb",))
-    assert same_hits(parts, whole) and _same(parts["rgb"], whole["rgb"])
+    assert same_hits(parts, whole) and same_bits(parts["rgb"], whole["rgb"])
     empty = rodynrf.render_hits(st, dy, rays[:0], ts[:0], T8, N_samples=S, ray_type=rt)
     assert empty["z"].shape == (8, 0) and empty["xyz"].shape == (8, 0, 3)
 
 
 def det_case():
-    """what both libraries compute (tests/_hits_det_child.py)"""
-    rodynrf = _rodynrf()
+    """what both libraries compute (tests/_det_child.py case)"""
+    rodynrf = _util.rodynrf()
     out = {}
     for rt in ("ndc", "contract"):
         _, st, dy = V.scene(rt)[:3]
@@ -296,55 +283,45 @@ def det_case():
 
 
 def test_deterministic_library_gives_the_same_bits(tmp_path):
-    ours = {k: v.cpu() for k, v in det_case().items()}
-    env = dict(os.environ, RDRF_DETERMINISTIC="1")
-    env.pop("RDRF_MARGINS", None)
-    env.pop("RDRF_LIB", None)
-    out = str(tmp_path / "det.pt")
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_hits_det_child.py")
-    r = subprocess.run([sys.executable, child, out], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    det = torch.load(out)
-    assert sorted(det) == sorted(ours)
-    for k in ours:
-        assert _same(det[k], ours[k]), k
+    ours = det_case()
+    assert_same_dict(run_twin(tmp_path, [CHILD, "case", "test_gpu_hits"], det=True), ours)
 
 
 # ---- 4. what is built on the hits --------------------------------------------------------------------------------------
 @pytest.mark.parametrize("rt", ["ndc", "contract"])
 def test_hit_tracks_start_on_the_surface(rt):
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     st, dy, p9, focal, T, Hh, W, pixels = V.tiny_scene(rt)
     S, frame = 13, 2
     base = rodynrf.render_tracks(st, dy, p9, focal, frame, pixels, Hh, W, N_samples=S, ray_type=rt)
     hit = rodynrf.render_hit_tracks(st, dy, p9, focal, frame, pixels, Hh, W, N_samples=S, ray_type=rt, tau=0.3)
     again = rodynrf.render_tracks(st, dy, p9, focal, frame, pixels, Hh, W, N_samples=S, ray_type=rt)
-    assert _same(again[0].points, base[0].points) and _same(again[1], base[1])       # render_tracks is what it was
+    assert same_bits(again[0].points, base[0].points) and same_bits(again[1], base[1])       # render_tracks is what it was
     ids = pixels[:, 1] * W + pixels[:, 0] + frame * Hh * W
     rays = rodynrf.generate_rays(ids, p9, focal, Hh, W, ndc=rt == "ndc", near=1.0)
     ts = torch.full((pixels.shape[0],), 2.0 * frame / (T - 1) - 1.0, device=DEV)
     h = rodynrf.render_hits(st, dy, rays, ts, 0.3, N_samples=S, ray_type=rt)
     assert bool(h["hit"].any())
     want = torch.where(h["hit"][:, None], h["xyz"], base[0].points[:, frame])
-    assert _same(hit[0].points[:, frame], want) and _same(hit[1], base[1])
+    assert same_bits(hit[0].points[:, frame], want) and same_bits(hit[1], base[1])
     assert hit[0].points.shape == base[0].points.shape
 
 
 @pytest.mark.parametrize("rt", ["ndc", "contract"])
 def test_point_cloud_and_hit_view(rt):
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     st, dy, p9, focal, T, Hh, W, _ = V.tiny_scene(rt)
     c2w = rodynrf.pose_to_mtx(p9.detach().float())[2]
     S = 13
     hv = rodynrf.hit_view(st, dy, c2w, focal, Hh, W, 0.2, tau=0.3, N_samples=S, ray_type=rt, maps=("rgb", "depth"))
     assert hv["z"].shape == (Hh, W) and hv["xyz"].shape == (Hh, W, 3) and hv["rgb"].shape == (Hh, W, 3) and hv["hit"].dtype == torch.bool
     multi = rodynrf.hit_view(st, dy, c2w, focal, Hh, W, 0.2, tau=(0.3, 0.6), N_samples=S, ray_type=rt)
-    assert multi["z"].shape == (2, Hh, W) and _same(multi["z"][0], hv["z"]) and _same(multi["xyz"][0], hv["xyz"])
+    assert multi["z"].shape == (2, Hh, W) and same_bits(multi["z"][0], hv["z"]) and same_bits(multi["xyz"][0], hv["xyz"])
     xyz, rgb, owner = rodynrf.point_cloud(st, dy, c2w, focal, Hh, W, 0.2, tau=0.3, N_samples=S, ray_type=rt)
     keep = hv["hit"].reshape(-1)
     assert 0 < int(keep.sum()) == xyz.shape[0]
-    assert _same(xyz, hv["xyz"].reshape(-1, 3)[keep]) and _same(owner, hv["owner"].reshape(-1)[keep])
-    assert _same(rgb, hv["rgb"].reshape(-1, 3)[keep].clamp(0.0, 1.0))
+    assert same_bits(xyz, hv["xyz"].reshape(-1, 3)[keep]) and same_bits(owner, hv["owner"].reshape(-1)[keep])
+    assert same_bits(rgb, hv["rgb"].reshape(-1, 3)[keep].clamp(0.0, 1.0))
     dyn = rodynrf.point_cloud(st, dy, c2w, focal, Hh, W, 0.2, tau=0.3, N_samples=S, ray_type=rt, min_owner=0.5)
     sta = rodynrf.point_cloud(st, dy, c2w, focal, Hh, W, 0.2, tau=0.3, N_samples=S, ray_type=rt, max_owner=0.5)
     assert dyn[0].shape[0] + sta[0].shape[0] >= xyz.shape[0] and bool((dyn[2] >= 0.5).all()) and bool((sta[2] <= 0.5).all())

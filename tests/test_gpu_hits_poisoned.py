@@ -3,13 +3,15 @@ the workspace are filled with 0xFF bytes (a NaN in every float, -1 in every list
 bands around the outputs and behind the workspace.  Every requested output is fully written and has the bits of the run on
 fresh buffers, on the render path and on the density-only path, with the packed weight images and with images packed into the
 workspace; the guards stay untouched.  The kernels may read only what the call itself wrote."""
-import importlib
 
 import pytest
 import torch
 
 import test_gpu_hits as T
 import test_gpu_track_vis as V
+
+from _twin import same_bits
+from _util import pkg
 
 pytestmark = pytest.mark.gpu
 G = 257
@@ -28,9 +30,9 @@ def _poisoned(shape, dtype):
 @pytest.mark.parametrize("maps", [False, True], ids=["density-only", "render"])
 @pytest.mark.parametrize("rt,S", [("ndc", 65), ("contract", 13)])
 def test_poisoned_outputs_and_workspace(rt, S, maps, packed, monkeypatch):
-    R = importlib.import_module("robust-dynrf_amd.renderer")
-    F = importlib.import_module("robust-dynrf_amd.fields")
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    R = pkg("renderer")
+    F = pkg("fields")
+    L = pkg()
     monkeypatch.setattr(F, "PACK_CACHE", packed)
     _, st, dy = V.scene(rt)[:3]
     rays, ts = T.batch(rt)
@@ -50,10 +52,10 @@ def test_poisoned_outputs_and_workspace(rt, S, maps, packed, monkeypatch):
     R._render_hits_raw(st, dy, rays, ts, taus, S, rt, names, bufs=bufs, mbufs=mbufs, ws=ws[:nbytes])
     torch.cuda.synchronize()
     for n in shapes:
-        assert T._same(bufs[n].contiguous(), ref[n]), n
+        assert same_bits(bufs[n].contiguous(), ref[n]), n
     assert bool((bufs["hit"] <= 1).all()) and bool(torch.isfinite(bufs["z"]).all()) and bool(torch.isfinite(bufs["xyz"]).all())
     for n in names:
-        assert T._same(mbufs[n].contiguous(), mref[n]), n
+        assert same_bits(mbufs[n].contiguous(), mref[n]), n
     for n, big in bigs.items():
         flat = big.view(torch.uint8)
         g = G * big.element_size()

@@ -21,16 +21,14 @@ slab that crosses every i plane, so vertices and cubes lie on both sides of poin
 read.  (260,256,256) = 17 039 360 points is the smallest convenient shape past 2^24 points, where s2[1] comes into play: a
 fault in that term can show at no smaller size.  It is zero but for two small noisy blobs, one at the start and one across
 point 2^24, so the restatement walks a few hundred cubes.  The tests assert where the owners lie."""
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import _iso_prim as P
-from _util import GOLDEN, load_case, record_margin
+from _twin import CHILD, run_twin
+from _util import GOLDEN, load_case, pkg, record_margin
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -250,7 +248,7 @@ def test_empty_and_full_volumes():
 
 
 def det_case():
-    """what both libraries run (tests/_iso_det_child.py)"""
+    """what both libraries run (tests/_det_child.py case)"""
     vol = seeded_volume((9, 17, 33), 3)
     out = {}
     for k, o in enumerate(gpu_mesh(vol, 0.5, BOX, normals=True)):
@@ -261,8 +259,7 @@ def det_case():
 
 
 def test_two_runs_and_a_poisoned_workspace_give_the_same_bits():
-    from importlib import import_module
-    L = import_module("robust-dynrf_amd._lib")
+    L = pkg()
     first = det_case()
     again = det_case()
     for k in first:
@@ -277,14 +274,7 @@ def test_two_runs_and_a_poisoned_workspace_give_the_same_bits():
 
 def test_deterministic_library_extracts_the_same_mesh(tmp_path):
     mine = det_case()
-    env = dict(os.environ, RDRF_DETERMINISTIC="1")
-    env.pop("RDRF_MARGINS", None)
-    env.pop("RDRF_LIB", None)
-    out = str(tmp_path / "det.pt")
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_iso_det_child.py")
-    r = subprocess.run([sys.executable, child, out], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    det = torch.load(out)
+    det = run_twin(tmp_path, [CHILD, "case", "test_gpu_iso"], det=True)
     assert set(det) == set(mine)
     for k, v in mine.items():
         assert v.numpy().tobytes() == det[k].numpy().tobytes(), k

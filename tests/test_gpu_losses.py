@@ -3,7 +3,7 @@ writes (train.py:1323-1421, 1522-1627, 1828-1832, 2293-2299), values and gradien
 import pytest
 import torch
 
-from _util import assert_close
+from _util import assert_close, pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -108,9 +108,8 @@ def test_frame_depth_loss_matches_reference_loop(N, T):
     own median / autograd): values and gradients, with empty frames, a single-ray frame (skipped), even / odd counts
     (lower median), a mask, exact ties at the median (the gradient is spread evenly over them, ATen's
     evenly_distribute_backward), a loss weight folded in, and one frame holding most of the batch."""
-    import importlib
     from oracle import rodynrf_oracle as O
-    LS = importlib.import_module("robust-dynrf_amd.losses")
+    LS = pkg("losses")
     g = torch.Generator().manual_seed(3)
     frame = torch.randint(0, T - 2, (N,), generator=g)          # frames T-2, T-1 stay empty
     frame[:1] = T - 2                                           # one frame with a single ray: skipped

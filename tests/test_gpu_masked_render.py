@@ -7,13 +7,13 @@ run in the same test; every RenderMaps field with torch.equal.  The density kern
 kept samples in 32-entry tiles, so the shapes and masks below put list lengths at 0, inside one tile and past a tile without
 filling the last one, tiles that span several rays and tiles that straddle a ray's end."""
 import functools
-import importlib
-import os
-import subprocess
-import sys
 
 import pytest
 import torch
+
+import _util
+from _twin import CHILD, assert_same_dict, run_twin
+from _util import pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -31,11 +31,6 @@ PARAMS = [(c, n, s, ("random", "random2")) for c in CASES for n, s in SHAPES]
 PARAMS += [(c, 64, 115, p) for c in CASES for p in PAIRS]
 PARAMS += [(c, n, 13, ("cell", "cell")) for c in CASES for n in (1, 7)]
 IDS = [f"{c}-{n}x{s}-{p[0]}-{p[1]}" for c, n, s, p in PARAMS]
-
-
-def _rodynrf():
-    import rodynrf
-    return rodynrf
 
 
 @functools.lru_cache(maxsize=None)
@@ -78,7 +73,7 @@ def sub_box(field):
 def make_mask(kind, field, xyz=None, valid=None, box=None):
     """the mask volumes of the issue: all ones, all zeros, a depth slab, a seeded random volume (~30 % occupied), slice 0 only,
     and one occupied cell on the path of ray 0"""
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     if kind is None:
         return None
     G2, G1, G0, T = VOL
@@ -108,7 +103,7 @@ def make_mask(kind, field, xyz=None, valid=None, box=None):
 
 def composed(case, rays, ts, S, masks):
     """the defining composition -> (the 13 outputs of raw2outputs, valid, valid_s, valid_d)"""
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     st, dy, rt = fields(case)
     with torch.no_grad():
         xyz, z, valid = rodynrf.sampleXYZ(dy, rays, S, ray_type=rt, is_train=False)
@@ -121,7 +116,7 @@ def composed(case, rays, ts, S, masks):
 
 
 def masks_for(case, N, S, pair):
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     st, dy, rt = fields(case)
     rays, ts = make_rays(case, N)
     xyz = valid = None
@@ -140,7 +135,7 @@ def same_maps(m, ref, what):
 @functools.lru_cache(maxsize=None)
 def run_case(case, N, S, pair):
     """one masked render checked against the composition -> (kept_s, kept_d, valid count, partial flags)"""
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     st, dy, rt = fields(case)
     rays, ts, masks = masks_for(case, N, S, pair)
     ref, valid, vs, vd = composed(case, rays, ts, S, masks)
@@ -189,7 +184,7 @@ def test_kept_counts_cover_the_tile_edges():
 def test_trivial_masks(case):
     """all-ones masks over a box that holds the field's give the bits of the unmasked render; all-zero masks the composition's
     (every sample dropped)"""
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     st, dy, rt = fields(case)
     N, S = 64, 115
     rays, ts = make_rays(case, N)
@@ -215,7 +210,7 @@ def test_trivial_masks(case):
 def test_poisoned_workspace_changes_no_bit(case):
     """nothing downstream of the keep pass depends on what the workspace held before the call"""
     from test_gpu_poisoned_scratch import scratch_fill
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     st, dy, rt = fields(case)
     N, S, pair = 64, 115, ("slab", "random2")
     rays, ts, masks = masks_for(case, N, S, pair)
@@ -230,7 +225,7 @@ def test_poisoned_workspace_changes_no_bit(case):
 
 def view_case():
     """a 9 x 7 view of the ndc case with two different masks: whole image, in chunks of 20 rays"""
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     st, dy, rt = fields("ndc_relu")
     masks = (make_mask("slab", st), make_mask("random2", dy))
     c2w = torch.tensor([[1.0, 0.0, 0.0, 0.05], [0.0, 1.0, 0.0, -0.02], [0.0, 0.0, 1.0, 0.0]])
@@ -240,8 +235,8 @@ def view_case():
 
 
 def det_case():
-    """what both libraries compute (tests/_masked_det_child.py): the maps of two masked renders"""
-    rodynrf = _rodynrf()
+    """what both libraries compute (tests/_det_child.py case): the maps of two masked renders"""
+    rodynrf = _util.rodynrf()
     out = {}
     for case in ("ndc_relu", "contract_softplus_te"):
         st, dy, rt = fields(case)
@@ -261,25 +256,15 @@ def test_chunked_image_equals_the_whole_image():
 
 def test_deterministic_library_gives_the_same_bits(tmp_path):
     """librodynrf_det.so exports the entry points and runs the same path: the maps and the kept counts of the default build"""
-    ours = {k: v.cpu() for k, v in det_case().items()}
-    env = dict(os.environ, RDRF_DETERMINISTIC="1")
-    env.pop("RDRF_MARGINS", None)
-    env.pop("RDRF_LIB", None)
-    out = str(tmp_path / "det.pt")
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_masked_det_child.py")
-    r = subprocess.run([sys.executable, child, out], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    det = torch.load(out)
-    assert sorted(det) == sorted(ours)
-    for k in ours:
-        assert torch.equal(det[k], ours[k]), k
+    ours = det_case()
+    assert_same_dict(run_twin(tmp_path, [CHILD, "case", "test_gpu_masked_render"], det=True), ours)
 
 
 def test_render_view_with_the_fields_own_masks():
     """updateAlphaMask on both fields of a small case, then render_view(alpha_masks=True): the composition with the fields'
     alphaMask, clamped as render_view clamps"""
     from _gpu_util import fields_from_case
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     _, st, dy, _ = fields_from_case("ndc_relu", DEV)   # fresh fields: the masks stay out of the shared ones
     lat = (12, 13, 8)
     for f in (st, dy):
@@ -312,7 +297,7 @@ def test_render_view_with_the_fields_own_masks():
 
 
 def test_out_of_scope_combinations_raise():
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     st, dy, rt = fields("ndc_relu")
     rays, ts, masks = masks_for("ndc_relu", 7, 13, ("slab", "slab"))
     eye = torch.eye(4)[:3]
@@ -321,7 +306,7 @@ def test_out_of_scope_combinations_raise():
     with pytest.raises(NotImplementedError):
         rodynrf.render_rays(st, dy, rays, ts, 13, ray_type=rt, alpha_masks=masks,
                             motion=dict(H=1, W=7, focal=10.0, c2w_f=eye, c2w_b=eye))
-    R = importlib.import_module("robust-dynrf_amd.renderer")
+    R = pkg("renderer")
     with pytest.raises(NotImplementedError):
         R.render_chunks(st, dy, rays, ts, 4, 13, ray_type=rt, alpha_masks=masks)
     with pytest.raises(ValueError):

@@ -18,17 +18,14 @@ about 1.5e-5 of sum |w x| and passes them all (tests/test_mlp_primitives_cpu.py 
 The forms do not depend on the RDRF_APP_F32 / RDRF_HEADS_F32 build switches: RDRF_LIB=<a tools/build_variant.sh library> runs
 this file against such a build."""
 import ctypes as C
-import importlib
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import _mlp_prim as P
-from _util import record_margin
+from _twin import CHILD, assert_same_dict, run_twin
+from _util import pkg, profile_line, record_margin
 
 pytestmark = pytest.mark.gpu
 
@@ -39,13 +36,9 @@ IDS = [f"{f}-{k}-{o}" for f, k, o in P.INSTANCES]
 B3_IDS = [f"{f}-{k}-{o}" for f, k, o in P.B3_INSTANCES]
 
 
-def _lib():
-    return importlib.import_module("robust-dynrf_amd._lib")
-
-
 def _call(form, x, w, K, OUT, M=None, ws_bytes=WS_BYTES):
     """x: cuda [>= M][n_in], w: cuda [OUT][K] -> (rc, y [M + 32][n_out]); the 32 extra rows keep their canary"""
-    L = _lib()
+    L = pkg()
     n_in, n_out = P.dims(form, K, OUT)
     M = x.shape[0] if M is None else M
     assert x.shape[1] == n_in and tuple(w.shape) == (OUT, K) and x.is_contiguous() and w.is_contiguous()
@@ -58,20 +51,12 @@ def _call(form, x, w, K, OUT, M=None, ws_bytes=WS_BYTES):
 
 
 def _run(form, x, w, K, OUT, M=None):
-    L = _lib()
+    L = pkg()
     rc, y = _call(form, x, w, K, OUT, M)
     L.check(rc, f"selftest_layer {form} {K} -> {OUT}")
     M = x.shape[0] if M is None else M
     assert bool((y[M:] == CANARY).all()), "rows past M were written"
     return y[:M]
-
-
-def _profile_line(text):
-    """RDRF_MLP_PRIM_TABLE=<file>: one line per dense case (measured e beside e_seq32), for profiles/"""
-    path = os.environ.get("RDRF_MLP_PRIM_TABLE")
-    if path:
-        with open(path, "a") as f:
-            f.write(text + "\n")
 
 
 # ---- (a) dense accuracy ---------------------------------------------------------------------------------------------------
@@ -88,7 +73,7 @@ def test_dense_accuracy_against_float64(form, K, OUT, family):
     y64, d = P.ref64(x, We)
     e = P.metric(y, y64, d)
     print(f"{form:10s} {K:3d} -> {OUT:3d} {family:6s} M = 2^20: e = {e:.3e}   e_seq32 = {e32:.3e}   e / (2 e_seq32) = {e / bound:.3f}")
-    _profile_line(f"{form:10s} {K:4d} {OUT:4d} {family:7s} {e:.3e} {e32:.3e} {e / bound:.3f}")
+    profile_line("RDRF_MLP_PRIM_TABLE", f"{form:10s} {K:4d} {OUT:4d} {family:7s} {e:.3e} {e32:.3e} {e / bound:.3f}")
     record_margin(f"{form} {K}->{OUT} {family} dense e / (2 e_seq32)", e / bound)
     worst = e
     for m in P.RAGGED:
@@ -136,34 +121,25 @@ def test_same_bits_twice(form, K, OUT):
         pytest.fail(f"{form} {K}->{OUT}: {len(diff)} outputs differ between two calls, first {diff[:8].tolist()}")
 
 
+def det_case():
+    """what both libraries compute (tests/_det_child.py case): the first 2^16 rows of every bf16 x 3 instance's dense case"""
+    out = {}
+    for form, K, OUT in P.B3_INSTANCES:
+        xg, wg = _dense_case(form, K, OUT)
+        out[f"{form}-{K}-{OUT}"] = _run(form, xg, wg, K, OUT)[:1 << 16]
+    return out
+
+
 def test_same_bits_in_the_deterministic_library(tmp_path):
     """librodynrf_det.so in a child process (the library is chosen at import) writes the bits of the product library"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = ("import sys, numpy as np, torch\n"
-            f"sys.path[:0] = [{root!r}, {os.path.join(root, 'tests')!r}]\n"
-            "import _mlp_prim as P\n"
-            "from test_gpu_mlp_primitives import _dense_case, _run\n"
-            "out = {}\n"
-            "for form, K, OUT in P.B3_INSTANCES:\n"
-            "    xg, wg = _dense_case(form, K, OUT)\n"
-            "    out[f'{form}-{K}-{OUT}'] = _run(form, xg, wg, K, OUT)[:1 << 16].cpu().numpy()\n"
-            "np.savez(sys.argv[1], **out)\n")
-    out = {}
-    for det in ("0", "1"):
-        path = str(tmp_path / f"det{det}.npz")
-        env = dict(os.environ, RDRF_DETERMINISTIC=det)
-        env.pop("RDRF_LIB", None)
-        subprocess.run([sys.executable, "-c", code, path], check=True, env=env, timeout=900)
-        z = np.load(path)
-        out[det] = {k: z[k] for k in z.files}
-    assert sorted(out["0"]) == sorted(B3_IDS)
-    for k in B3_IDS:
-        assert np.array_equal(out["0"][k].view(np.int32), out["1"][k].view(np.int32)), k
+    out = {det: run_twin(tmp_path, [CHILD, "case", "test_gpu_mlp_primitives"], det=det, timeout=900) for det in (False, True)}
+    assert sorted(out[False]) == sorted(B3_IDS)
+    assert_same_dict(out[True], out[False])
 
 
 # ---- (d) error paths ------------------------------------------------------------------------------------------------------
 def test_error_paths():
-    L = _lib()
+    L = pkg()
     x = torch.randn(64, 64, device="cuda")
     w = torch.randn(64, 64, device="cuda")
     rc, y = _call("B3", x, w, 64, 64)

@@ -3,7 +3,6 @@ reference's own per-frame chain (tests/golden/motion_*.npz, make_golden_motion.p
 chunkings, repeats and map subsets, the colour maps left untouched, the composition of the public calls at a real shape,
 edge shapes, and the flow pictures against flow_viz.flow_to_image."""
 import ctypes as C
-import importlib
 import os
 
 import numpy as np
@@ -11,7 +10,8 @@ import pytest
 import torch
 
 from _gpu_util import fields_from_case
-from _util import GOLDEN, assert_close
+from _twin import CHILD, assert_same_dict, run_twin, same_bits
+from _util import GOLDEN, assert_close, pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -31,9 +31,9 @@ def _case(name):
 def _native(st, dy, rays, ts, S, rt, cams, want=MOTION, mode="auto", first=0, maps=None):
     """rdrf_render_motion_fwd with caller-owned buffers: all five motion buffers exist and are pre-filled with a canary, only
     the pointers of `want` are passed.  Returns (dict of the five buffers, dict of the requested RenderMaps buffers)."""
-    L = importlib.import_module("robust-dynrf_amd._lib")
-    F = importlib.import_module("robust-dynrf_amd.fields")
-    R = importlib.import_module("robust-dynrf_amd.renderer")
+    L = pkg()
+    F = pkg("fields")
+    R = pkg("renderer")
     N, dev = rays.shape[0], rays.device
     bufs = {n: torch.full((N, 3) if n == "delta_xyz" else (N, 2), CANARY, device=dev) for n in MOTION}
     MM = L.MotionMapsC(*[bufs[n].data_ptr() if n in want else None for n in MOTION])
@@ -81,10 +81,6 @@ def _composition(st, dy, rays, ts, S, rt, cams, first=0):
             delta_xyz=torch.sum(w_d[..., None] * (o_d[5] - xyz), 1), w_d=w_d)
 
 
-def _same(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
-
-
 # ---- 1. reference parity ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", ["auto", "sequence", "fused"])
 @pytest.mark.parametrize("case", CASES)
@@ -112,58 +108,48 @@ def test_motion_maps_same_bits_everywhere(case):
     for mode in ("sequence", "fused"):                       # the three modes
         got, _ = _native(st, dy, rays, ts, S, rt, cams, mode=mode)
         for k in MOTION:
-            assert _same(got[k], base[k]), (mode, k)
+            assert same_bits(got[k], base[k]), (mode, k)
     for rep in range(3):                                     # three repeats
         got, _ = _native(st, dy, rays, ts, S, rt, cams)
         for k in MOTION:
-            assert _same(got[k], base[k]), (rep, k)
+            assert same_bits(got[k], base[k]), (rep, k)
     # whole image vs chunks with first_pixel: multiples of 32 rays (96), of S (40), of neither (37, 100), through the
     # public call and through render_frame's chunk loop
     for chunk in (96, S, 37, 100):
         parts = [rodynrf.render_rays(st, dy, rays[c0:c0 + chunk], ts[c0:c0 + chunk], S, ray_type=rt,
                                      motion=dict(cams, first_pixel=c0))[1] for c0 in range(0, N, chunk)]
         for k in MOTION:
-            assert _same(torch.cat([getattr(p, k) for p in parts]), base[k]), (chunk, k)
-    R = importlib.import_module("robust-dynrf_amd.renderer")
+            assert same_bits(torch.cat([getattr(p, k) for p in parts]), base[k]), (chunk, k)
+    R = pkg("renderer")
     _, img = R._render_image(st, dy, rays, ts, cams["H"], cams["W"], S, rt, 100, False, dict(cams))
     for k in MOTION:
-        assert _same(getattr(img, k).reshape(N, -1), base[k]), k
+        assert same_bits(getattr(img, k).reshape(N, -1), base[k]), k
     # any subset gives the bits of the full request; an unrequested buffer keeps its canary
     subsets = [(k,) for k in MOTION] + [("flow_f", "flow_s_b"), ("flow_b", "delta_xyz"), ("flow_s_f", "flow_s_b", "delta_xyz")]
     for want in subsets:
         got, _ = _native(st, dy, rays, ts, S, rt, cams, want=want)
         for k in MOTION:
             if k in want:
-                assert _same(got[k], base[k]), (want, k)
+                assert same_bits(got[k], base[k]), (want, k)
             else:
                 assert bool((got[k] == CANARY).all()), (want, k)
     part = rodynrf.render_rays(st, dy, rays, ts, S, ray_type=rt, motion=dict(cams, maps=("flow_b",)))[1]
-    assert _same(part.flow_b, base["flow_b"]) and part.flow_f is None and part.delta_xyz is None
+    assert same_bits(part.flow_b, base["flow_b"]) and part.flow_f is None and part.delta_xyz is None
 
 
-def test_motion_maps_same_bits_in_the_deterministic_library():
+def det_case():
+    """what both libraries compute (tests/_det_child.py case): the five motion maps of motion_ndc"""
+    import rodynrf
+    g, st, dy, rays, ts, S, rt, cams = _case("motion_ndc")
+    mm = rodynrf.render_rays(st, dy, rays, ts, S, ray_type=rt, motion=cams)[1]
+    return {k: getattr(mm, k) for k in MOTION}
+
+
+def test_motion_maps_same_bits_in_the_deterministic_library(tmp_path):
     """librodynrf_det.so in a child process (the library is chosen at import) writes the bits of the product library"""
-    import subprocess
-    import sys
-    import tempfile
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = ("import sys, numpy as np, torch\n"
-            f"sys.path[:0] = [{root!r}, {os.path.join(root, 'tests')!r}]\n"
-            "import rodynrf\n"
-            "from test_gpu_motion_maps import _case, MOTION\n"
-            "g, st, dy, rays, ts, S, rt, cams = _case('motion_ndc')\n"
-            "mm = rodynrf.render_rays(st, dy, rays, ts, S, ray_type=rt, motion=cams)[1]\n"
-            "np.savez(sys.argv[1], **{k: getattr(mm, k).cpu().numpy() for k in MOTION})\n")
-    out = {}
-    with tempfile.TemporaryDirectory() as d:
-        for det in ("0", "1"):
-            path = os.path.join(d, f"det{det}.npz")
-            subprocess.run([sys.executable, "-c", code, path], check=True, env=dict(os.environ, RDRF_DETERMINISTIC=det),
-                           timeout=600)
-            z = np.load(path)
-            out[det] = {k: z[k] for k in MOTION}
-    for k in MOTION:
-        assert np.array_equal(out["0"][k].view(np.int32), out["1"][k].view(np.int32)), k
+    out = {det: run_twin(tmp_path, [CHILD, "case", "test_gpu_motion_maps"], det=det) for det in (False, True)}
+    assert sorted(out[False]) == sorted(MOTION)
+    assert_same_dict(out[True], out[False])
 
 
 # ---- 3. the existing maps keep their bits -------------------------------------------------------------------------------
@@ -175,12 +161,12 @@ def test_render_maps_unchanged_by_motion(case):
         ref = rodynrf.render_rays(st, dy, rays, ts, S, ray_type=rt, mode=mode, maps=True)
         got, mm = rodynrf.render_rays(st, dy, rays, ts, S, ray_type=rt, mode=mode, maps=True, motion=cams)
         for k in rodynrf.RenderMaps._fields:
-            assert _same(getattr(got, k), getattr(ref, k)), (mode, k)
+            assert same_bits(getattr(got, k), getattr(ref, k)), (mode, k)
         rgb, depth = rodynrf.render_rays(st, dy, rays, ts, S, ray_type=rt, mode=mode)
         (rgb2, depth2), _ = rodynrf.render_rays(st, dy, rays, ts, S, ray_type=rt, mode=mode, motion=cams)
-        assert _same(rgb, rgb2) and _same(depth, depth2), mode
+        assert same_bits(rgb, rgb2) and same_bits(depth, depth2), mode
         sub, _ = rodynrf.render_rays(st, dy, rays, ts, S, ray_type=rt, mode=mode, maps=("depth_d", "blending"), motion=cams)
-        assert _same(sub.depth_d, ref.depth_d) and _same(sub.blending, ref.blending) and sub.rgb is None
+        assert same_bits(sub.depth_d, ref.depth_d) and same_bits(sub.blending, ref.blending) and sub.rgb is None
 
 
 # ---- 4. composition at a real shape -------------------------------------------------------------------------------------
@@ -192,7 +178,7 @@ def test_motion_maps_match_the_composition_at_stage0():
     2.3e-5 (flow_s_b), 2.0e-7 (delta_xyz).  The static flows are the tight ones: the projected pixel coordinate is up to 240,
     two of its fp32 ulps are 3e-5 px, and the static forward flow itself is at most half a pixel on this frame."""
     import rodynrf
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     dev = torch.device("cuda", 0)
     cfg = S_.scene_config("nvidia", "stage0")
     torch.manual_seed(7)

@@ -3,20 +3,19 @@ the bilinear VM upsampling vs F.interpolate, density_L1 / blending_L1 vs the ref
 gradients (tests/golden/tv.npz) and vs the dense einsum at the Balloon1 grid, and the uv / view-shift ray
 generator vs the oracle."""
 import ctypes as C
-import importlib
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from _util import GOLDEN, assert_close
+from _util import GOLDEN, assert_close, pkg
 
 pytestmark = pytest.mark.gpu
 
 
 def test_adam_step_matches_torch_adam():
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     g = torch.Generator().manual_seed(0)
     n, split = 4096 + 512, 1024
     p0 = torch.randn(n, generator=g)
@@ -43,7 +42,7 @@ def test_flat_adam_trains_like_torch_adam_on_the_fields():
     state_dict() keeps the reference's keys / shapes."""
     import rodynrf
     from _gpu_util import fields_from_case
-    O = importlib.import_module("robust-dynrf_amd.optim")
+    O = pkg("optim")
     g, st, dy, _ = fields_from_case("ndc_relu")
     g2, st2, dy2, _ = fields_from_case("ndc_relu")
     dev = "cuda"

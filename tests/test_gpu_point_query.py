@@ -5,15 +5,13 @@ normalised view direction gets the sample's bits -- sigma, blending and xyz_prim
 the forward computed a colour for (weight > rayMarch_weight_thres).  The rest holds the query to the goldens, to itself under
 permutation, sub-batching, chunking and the two time modes, to the float64 reference of tests/_point_prim.py for a view
 direction that is not a unit vector, and the coloured meshes to field_mesh + vertex_colors."""
-import os
-import subprocess
-import sys
 
 import pytest
 import torch
 
 from _point_prim import point_reference, ray_norm_viewdirs
-from _util import FWD_ELEM, assert_close
+from _twin import CHILD, assert_same_dict, run_twin, same_bits
+from _util import FWD_ELEM, assert_close, pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -44,10 +42,6 @@ def case(name):
         c["query"] = {w: f.query_points(c["pts"], c["t"], c["vd"], want=OUTS[w]) for w, f in c["fields"].items()}
         _cases[name] = c
     return _cases[name]
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.contiguous().cpu().numpy().tobytes() == b.contiguous().cpu().numpy().tobytes()
 
 
 # ---- 1. identity with forward -----------------------------------------------------------------------------------------------
@@ -218,9 +212,8 @@ def test_call_surface():
 def test_workspace_size_is_what_the_launch_demands():
     """the exact size runs, one byte less is refused (on the device this time: the CPU test sees the refusal only)"""
     import ctypes as C
-    from importlib import import_module
-    L = import_module("robust-dynrf_amd._lib")
-    F = import_module("robust-dynrf_amd.fields")
+    L = pkg()
+    F = pkg("fields")
     c, pts, t, vd = batch165()
     for which, dyn in (("static", 0), ("dynamic", 1)):
         field = c["fields"][which]
@@ -290,7 +283,7 @@ def test_colored_mesh(which, tmp_path):
 
 # ---- 8. deterministic twin ------------------------------------------------------------------------------------------------------
 def det_case():
-    """what both libraries run (tests/_point_det_child.py)"""
+    """what both libraries run (tests/_det_child.py case)"""
     c, pts, t, vd = batch165(spread_times=True)
     out = {}
     for which, field in c["fields"].items():
@@ -301,15 +294,6 @@ def det_case():
 
 
 def test_deterministic_library_gives_the_same_bits(tmp_path):
-    mine = det_case()
-    env = dict(os.environ, RDRF_DETERMINISTIC="1")
-    env.pop("RDRF_MARGINS", None)
-    env.pop("RDRF_LIB", None)
-    out = str(tmp_path / "det.pt")
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_point_det_child.py")
-    r = subprocess.run([sys.executable, child, out], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    det = torch.load(out)
-    assert set(det) == set(mine) and len(mine) == 12
-    for k, v in mine.items():
-        assert same_bits(v, det[k]), k
+    ours = det_case()
+    assert len(ours) == 12
+    assert_same_dict(run_twin(tmp_path, [CHILD, "case", "test_gpu_point_query"], det=True), ours)

@@ -10,15 +10,12 @@ library; in the product library (fp32 atomics arrive in another order every run)
 test_tiled_scatter_matches_plain_sorted_scatter_at_benchmark_shape: relative L2 <= max(3 x the run-to-run spread of the
 zero-filled path, 2e-6)."""
 import contextlib
-import importlib
-import os
-import subprocess
-import sys
 
 import pytest
 import torch
 
-from _util import record_margin
+from _twin import CHILD, run_twin
+from _util import pkg, record_margin
 
 pytestmark = pytest.mark.gpu
 
@@ -29,14 +26,10 @@ CASES = [("ndc", "ray", "full", True), ("ndc", "sorted", "no_rgb", True), ("ndc"
 IDS = ["-".join(str(v) for v in c) for c in CASES]
 
 
-def _mods():
-    return importlib.import_module("robust-dynrf_amd._lib"), importlib.import_module("robust-dynrf_amd.fields")
-
-
 @contextlib.contextmanager
 def scratch_fill(byte):
     """every saved-row buffer and every workspace the entry points get is filled with `byte` first"""
-    L, F = _mods()
+    L, F = pkg(), pkg("fields")
     orig = F._alloc_saved, F._feat_saved, L.workspace
     seen = {"saved": 0, "workspace": 0}
 
@@ -66,7 +59,7 @@ def poisoned_scratch():
 def _fields(rt, seed=3):
     import rodynrf
     from _gpu_util import COMMON
-    L, _ = _mods()
+    L = pkg()
     torch.manual_seed(seed)
     contract = rt == "contract"
     aabb = torch.tensor([[-2.0, -2.0, -2.0], [2.0, 2.0, 2.0]] if contract else [[-1.5, -1.67, -1.0], [1.5, 1.67, 1.0]])
@@ -119,7 +112,7 @@ def _collect(fields, out):
 def run_rays(st, dy, batch, rt, mode, loss_kind, rgb):
     """forward + backward of both fields with raw2outputs and scene flow -> {name: tensor} of every output and gradient"""
     import rodynrf
-    L, _ = _mods()
+    L = pkg()
     rays, ts, xyz, z, valid, tgt = batch
     _zero_grads(st, dy)
     L.set_scatter_mode(mode)
@@ -173,7 +166,7 @@ def _vec(res, prefix):
 def _compare(poison, zero_a, zero_b, what):
     """bit-equal in the deterministic library; else relative L2 <= max(3 x spread of the zero-filled path, 2e-6), over the
     outputs, over the gradients and for every tensor on its own"""
-    L, _ = _mods()
+    L = pkg()
     assert sorted(poison) == sorted(zero_a) == sorted(zero_b)
     assert any(k.startswith("grad.st.") for k in poison) and any(k.startswith("grad.dy.") for k in poison)
     if L.DETERMINISTIC:
@@ -231,11 +224,4 @@ def test_feature_entry_points_on_poisoned_scratch(poisoned_scratch):
 
 def test_poisoned_scratch_changes_no_bit_in_the_deterministic_library(tmp_path):
     """the same cases against librodynrf_det.so in a child process (the library is chosen at import): every tensor bit for bit"""
-    env = dict(os.environ, RDRF_DETERMINISTIC="1")
-    env.pop("RDRF_LIB", None)
-    env.pop("RDRF_MARGINS", None)
-    path = str(tmp_path / "det.txt")
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_det_child.py")
-    r = subprocess.run([sys.executable, child, "poison", path], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert int(open(path).read()) == len(CASES) + 1
+    assert run_twin(tmp_path, [CHILD, "poison"], det=True) == len(CASES) + 1

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import CASES, assert_close, load_case
+from _util import CASES, assert_close, load_case, pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -102,12 +102,11 @@ def test_every_entry_point_of_the_family_gives_the_bits_of_the_maps_sequence():
     motion and track-seed calls, their render maps.  rdrf_render_world_fwd takes world-space rays only and the sequence of
     rdrf_render_maps_fwd refuses them, so the world fields are held to that entry point's own sequence mode, and so is the
     masked render on world rays."""
-    import importlib
     import rodynrf
     import test_gpu_masked_render as MR
     import ctypes as C
-    R = importlib.import_module("robust-dynrf_amd.renderer")
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    R = pkg("renderer")
+    L = pkg()
     N, S = 70, 37
 
     def family(case, world):

@@ -7,7 +7,6 @@ samples: no multiple of 32, rays cross tile edges, the last tile is ragged).
 Under RDRF_DETERMINISTIC=1 (librodynrf_det.so) the gradient comparisons are bitwise; the last test re-runs them there."""
 import ctypes as C
 import functools
-import importlib
 import os
 import subprocess
 import sys
@@ -15,7 +14,7 @@ import sys
 import pytest
 import torch
 
-from _util import assert_close, record_margin
+from _util import assert_close, pkg, record_margin
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,10 +23,6 @@ CASES = ["ndc_relu", "contract_relu_te"]
 SHAPES = [(c, s) for c in CASES for s in (13, 45)]
 # outputs of the 10-tuple that stay differentiable when the colours are values only
 LIVE = {"static": (7, 4), "dynamic": (2, 4, 5, 7)}
-
-
-def _mods():
-    return importlib.import_module("robust-dynrf_amd.fields"), importlib.import_module("robust-dynrf_amd._lib")
 
 
 @functools.lru_cache(maxsize=None)
@@ -69,7 +64,7 @@ def test_no_grad_forward_saves_nothing_and_returns_the_same_bits(case, S, kind):
     """A field call under torch.no_grad() with parameters that require grad (ctx.needs_input_grad says True there): every
     output bit-equal to the grad-mode call, and the allocation peak rises over the call by less than the saved buffer the
     call used to allocate; the grad-mode call, measured the same way, rises by at least that buffer."""
-    F, L = _mods()
+    F, L = pkg("fields"), pkg()
     rt, fields, inp = _inputs(case, S)
     field = fields[kind]
     assert all(p.requires_grad for p in field.parameters())
@@ -115,7 +110,7 @@ def test_value_rgb_changes_no_output_and_no_gradient(case, S, kind):
     xyz_prime, sigma): parameter gradients, g_xyz and g_z bit-equal to the rgb=True run in the deterministic library; in
     the product library (fp32 atomics arrive in another order every run) within 3 x the run-to-run spread of two rgb=True
     runs, floor 2e-6 relative L2 -- the convention of test_tiled_scatter_matches_plain_sorted_scatter_at_benchmark_shape."""
-    F, L = _mods()
+    F, L = pkg("fields"), pkg()
     rt, fields, inp = _inputs(case, S)
     field = fields[kind]
     k = 1 if kind == "dynamic" else 0
@@ -159,7 +154,7 @@ def test_backward_refuses_a_colour_gradient_for_a_buffer_without_appearance_rows
     """C ABI: rdrf_saved_bytes_ex(RDRF_SAVE_NO_APP) is the full size minus the appearance block; rdrf_*_bwd given such a
     buffer and a non-NULL g_rgb returns a negative code with a message and touches no gradient output (pre-filled with a
     sentinel); half of that buffer is refused as too small; the same buffer without g_rgb differentiates."""
-    F, L = _mods()
+    F, L = pkg("fields"), pkg()
     rt, fields, inp = _inputs(case, S)
     field = fields[kind]
     dyn = kind == "dynamic"
@@ -230,8 +225,8 @@ def test_trainer_dead_work_saves_only_what_a_backward_reads(it):
     saved-byte accounting of every field call): nothing for the value-only static call of passes A-D nor for the dead
     dynamic forward of pass E, no appearance rows for the dynamic passes B-D, full rows for pass A (dynamic) and pass E
     (static) alone."""
-    F, L = _mods()
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    F, L = pkg("fields"), pkg()
+    S_ = pkg("step")
     cfg = S_.scene_config("nvidia", "stage0")
     cfg.update(SMALL_NVIDIA)
     cfg["focal"] = max(cfg["H"], cfg["W"]) / 2.0 * 3.0 ** 0.5

@@ -24,21 +24,14 @@ against the exact dz |d| scale, relative errors in units of u = 2^-24, line by l
              ... * distance_scale     one rounding                                         4.5 u
 4.5 u = 2.25 ulp: the test allows 3 ulp.
 The compaction is checked exactly, against the kernel's own stored weights.  profiles/scan_margins.txt holds the ratios of one run."""
-import importlib
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if __name__ == "__main__":   # the child of test_forward_entry_gives_the_dynamic_fields_own_weights: no conftest has set the path
-    sys.path.insert(0, ROOT)
-
 import _scan_prim as Q
-from _util import record_margin
+from _twin import CHILD, run_twin, tools_lib
+from _util import pkg, record_margin
 
 pytestmark = pytest.mark.gpu
 
@@ -49,10 +42,6 @@ CNT0 = 5                                           # the counter's pre-fill: it 
 COMBOS = (("relu", "ndc", 25.0), ("softplus", "contract", 1.0), ("softplus", "world", 25.0), ("relu", "world", 1.0))
 RT = {"ndc": 0, "contract": 1, "world": 2}
 ACT = {"relu": 0, "softplus": 1}
-
-
-def _L():
-    return importlib.import_module("robust-dynrf_amd._lib")
 
 
 class Guarded:
@@ -75,7 +64,7 @@ class Guarded:
 
 def run_fwd(width, x, rt, scale, thres, rgb=True):
     """-> weight, dists [N,S], list (whole buffer), counter, rgb or None, all on the CPU"""
-    L = _L()
+    L = pkg()
     n, S = x["z"].shape
     rays, z, sigma = x["rays"].cuda(), x["z"].cuda(), x["sigma"].cuda()
     w, d = Guarded((n, S)), Guarded((n, S))
@@ -100,7 +89,7 @@ def _prefill(n, S):
 def run_bwd(width, x, act, rt, scale, cot, want_z=True, want_rays=True, rows=None):
     """-> out ([N,S] gsig or [N,Sp] gf rows, poison kept), g_z, g_rays (None where not asked) on the CPU.  rows: run these rays
     alone, pre-filled as the full run pre-fills them"""
-    L = _L()
+    L = pkg()
     n, S = x["z"].shape
     pz, pr = _prefill(n, S)
     sel = slice(None) if rows is None else rows
@@ -322,15 +311,15 @@ def test_a_ray_does_not_depend_on_the_batch(width):
             assert torch.equal(w1, wf[rows]) and torch.equal(d1, df[rows])
 
 
-TOOLS_LIB = os.path.join(ROOT, "robust-dynrf_amd", "librodynrf_tools.so")
 FIELD_SHAPES = ((17, 33), (3, 129))
 
 
-def _field_child(out, flat):
-    """the dynamic field's own forward (tools build, RDRF_FLAT from the environment) at FIELD_SHAPES: rays, z, sigma, weight, dists"""
+def field_case():
+    """the dynamic field's own forward (tools build, RDRF_FLAT from the environment) at FIELD_SHAPES: rays, z, sigma, weight, dists
+    (tests/_det_child.py case)"""
     import rodynrf
-    St = importlib.import_module("robust-dynrf_amd.step")
-    RU = importlib.import_module("robust-dynrf_amd.ray_utils")
+    St = pkg("step")
+    RU = pkg("ray_utils")
     torch.manual_seed(0)
     cfg = St.scene_config("nvidia", "stage0")
     dev = torch.device("cuda", 0)
@@ -350,21 +339,17 @@ def _field_child(out, flat):
             torch.cuda.synchronize()
             for k, t in (("rays", rays), ("z", o[8]), ("sigma", o[7]), ("weight", o[4]), ("dists", o[9])):
                 res[f"{k}_{n}_{S}"] = t.detach().float().cpu().numpy()
-    np.savez(out, **res)
+    return res
 
 
 def test_forward_entry_gives_the_dynamic_fields_own_weights(tmp_path):
     """width 32: the weights and dists of rdrf_selftest_ray_scan, bit for bit, from the sigmas the dynamic field's forward wrote -- on
     flat tiles (k_dyn_density_flat + k_ray_scan) and wave per ray (k_dyn_density: weight_round<32> in place), which must agree too"""
-    if not os.path.exists(TOOLS_LIB):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "robust-dynrf_amd", "csrc"), "-j16", "tools"], timeout=1800)
     got = {}
     for flat in ("0", "1"):
-        out = str(tmp_path / f"field_flat{flat}.npz")
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), out, flat], cwd=ROOT, capture_output=True, text=True, timeout=300,
-                           env=dict(os.environ, RDRF_LIB=TOOLS_LIB, RDRF_FLAT=flat))
-        assert r.returncode == 0, (flat, r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-        got[flat] = dict(np.load(out))
+        res = run_twin(tmp_path, [CHILD, "case", "test_gpu_scan_primitives", "field_case"], lib=tools_lib(), extra_env={"RDRF_FLAT": flat},
+                       timeout=300)
+        got[flat] = {k: v.numpy() for k, v in res.items()}
     for n, S in FIELD_SHAPES:
         a, b = got["0"], got["1"]
         for k in ("rays", "z", "sigma", "weight", "dists"):
@@ -378,7 +363,7 @@ def test_forward_entry_gives_the_dynamic_fields_own_weights(tmp_path):
 
 
 def test_entry_points_check_their_arguments():
-    L = _L()
+    L = pkg()
     x = Q.generate("thin", 2, 8)
     z = x["z"].cuda()
     buf = torch.zeros(4096, device="cuda")
@@ -400,6 +385,3 @@ def test_entry_points_check_their_arguments():
     assert b"selftest_ray_scan_bwd" in L.lib.rdrf_last_error()
     torch.cuda.synchronize()
 
-
-if __name__ == "__main__":
-    _field_child(sys.argv[1], sys.argv[2])

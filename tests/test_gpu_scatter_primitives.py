@@ -8,17 +8,15 @@ sorted and sorted_plain forms.  Dense class: normal values on odd grids, e = |g 
 of a sequential fp32 evaluation.  Workspaces are filled with 0xFF before every call; gradient tensors sit in one flat buffer with
 guard gaps that must keep their fill."""
 import ctypes as C
-import importlib
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import _scatter_prim as P
-from _util import record_margin
+from _twin import CHILD, run_twin
+from _util import pkg, record_margin
 
 pytestmark = pytest.mark.gpu
 
@@ -28,10 +26,6 @@ GAP = -2.0
 VISITED = set()          # launch-policy branches the file has seen taken (rdrf_selftest_scatter_last)
 MARGINS = []
 DET = None               # tests/_det_child.py: binds every call's gradient buffer to a fixed-point shadow (deterministic library)
-
-
-def _lib():
-    return importlib.import_module("robust-dynrf_amd._lib")
 
 
 def _modes(desc):
@@ -44,7 +38,7 @@ _DESC = {}
 def _desc(kind, grid):
     key = (kind, tuple(grid))
     if key not in _DESC:
-        _DESC[key] = P.describe(_lib(), kind, list(grid))
+        _DESC[key] = P.describe(pkg(), kind, list(grid))
     return _DESC[key]
 
 
@@ -52,7 +46,7 @@ class Dev:
     """a case on the device: factor values, and every output as a view of one flat buffer with 64-float guard gaps"""
 
     def __init__(self, case, order="W"):
-        L = _lib()
+        L = pkg()
         self.case, self.order, d = case, order, case["desc"]
         self.d = d
         self.shapes = P.shapes(case)
@@ -116,7 +110,7 @@ class Dev:
         return out
 
     def call(self, mode, pre, check=True):
-        L = _lib()
+        L = pkg()
         self.flat.copy_(torch.from_numpy(self.flatten(pre)).float())
         if self.d["rec_floats"]:
             self.ws.fill_(0xFF)
@@ -164,7 +158,7 @@ class Dev:
 
 
 def last_record():
-    L = _lib()
+    L = pkg()
     buf = (C.c_int * 32)()
     n = L.lib.rdrf_selftest_scatter_last(buf, 32)
     assert n >= 4 and buf[0] == n
@@ -220,7 +214,7 @@ SORT_BITS = [1, 9, 10, 18, 19, 27, 28]
 
 
 def _sort_call(keys, bits, count=None, n_mul=0):
-    L = _lib()
+    L = pkg()
     n = len(keys)
     k = torch.from_numpy(keys.view(np.int32)).cuda()
     ko = torch.full((n,), -1, dtype=torch.int32, device="cuda")
@@ -545,7 +539,7 @@ def test_dense_values_stay_within_twice_the_sequential_fp32_error(kind, grid):
 
 # ---- error paths ---------------------------------------------------------------------------------------------------------------
 def test_error_paths():
-    L = _lib()
+    L = pkg()
     case = dyadic_case("DYN_DENSITY", [9, 9, 9], 2, 33, flat=1)
     dev = Dev(case)
     pre = int_prefill(case)
@@ -623,13 +617,7 @@ def test_same_bits_in_the_deterministic_library(tmp_path):
     """librodynrf_det.so in a child process (the library is chosen at import), the flat gradient buffer of every call bound to a
     fixed-point shadow as the fields bind theirs: after the fold, the int64 sums again, bit for bit; before it, no plane or line
     element has moved (an addition that missed the shadow)"""
-    path = str(tmp_path / "det.txt")
-    env = dict(os.environ, RDRF_DETERMINISTIC="1")
-    env.pop("RDRF_LIB", None)
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_det_child.py")
-    r = subprocess.run([sys.executable, child, "scatter", path], env=env, timeout=600, capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert int(open(path).read()) == 3 * len(P.KINDS) + 1 + 4
+    assert run_twin(tmp_path, [CHILD, "scatter"], det=True) == 3 * len(P.KINDS) + 1 + 4
 
 
 # ---- last: every branch of the launch policy was really taken ------------------------------------------------------------------

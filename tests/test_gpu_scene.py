@@ -3,7 +3,6 @@ float tables built the way step.SyntheticScene builds its own, Scene as a drop-i
 in eager and captured form, the run driver Trainer.fit with the reference's resolution schedule, learning on an analytic
 video, save / load of a run's state, evaluate()."""
 import ctypes as C
-import importlib
 import math
 import os
 import subprocess
@@ -13,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import assert_close, record_margin
+from _util import assert_close, pkg, record_margin
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,11 +23,6 @@ SMALL = {
     "nvidia_no_poses": dict(grid=[17, 19, 11], n_samples=13, batch_size=64),
 }
 T6, H27, W48 = 6, 27, 48
-
-
-def _mods():
-    return (importlib.import_module("robust-dynrf_amd.step"), importlib.import_module("robust-dynrf_amd.scene"),
-            importlib.import_module("robust-dynrf_amd._lib"))
 
 
 def _dev():
@@ -49,7 +43,7 @@ def random_arrays(T, H, W, seed=0, poses=True):
 
 
 def small_cfg(name, **over):
-    S_, _, _ = _mods()
+    S_ = pkg("step")
     cfg = S_.scene_config(name, "stage0")
     cfg.update(SMALL[name])
     cfg.update(T=None, H=None, W=None)    # the scene's
@@ -59,7 +53,7 @@ def small_cfg(name, **over):
 
 @pytest.fixture(scope="module")
 def scene_posed():
-    _, SC, _ = _mods()
+    SC = pkg("scene")
     a = random_arrays(T6, H27, W48)
     held = [(a["poses"][2], -0.2, a["rgb"][2])]
     return SC.Scene(**a, heldout=held, device=_dev())
@@ -67,7 +61,7 @@ def scene_posed():
 
 @pytest.fixture(scope="module")
 def scene_unposed():
-    _, SC, _ = _mods()
+    SC = pkg("scene")
     return SC.Scene(**random_arrays(T6, H27, W48, seed=1, poses=False), device=_dev())
 
 
@@ -102,7 +96,7 @@ def gather_ids(N, total, seed):
 @pytest.mark.parametrize("rgb_dtype", ["uint8", "float32"])
 @pytest.mark.parametrize("optional", [True, False])
 def test_gather_matches_indexing_of_float_tables(rgb_dtype, optional):
-    _, SC, _ = _mods()
+    SC = pkg("scene")
     T, H, W = 3, 5, 7
     total = T * H * W
     a = random_arrays(T, H, W, seed=3, poses=False)
@@ -135,7 +129,7 @@ def test_gather_matches_indexing_of_float_tables(rgb_dtype, optional):
 
 
 def L_():
-    return _mods()[2]
+    return pkg()
 
 
 def test_gather_of_an_empty_batch_touches_nothing(scene_posed):
@@ -158,7 +152,7 @@ def test_gather_of_an_empty_batch_touches_nothing(scene_posed):
 
 def test_scene_is_a_drop_in_for_the_synthetic_scene():
     """a Scene built from a SyntheticScene's own tensors returns the same make_batch dict, bit for bit"""
-    S_, SC, _ = _mods()
+    S_, SC = pkg("step"), pkg("scene")
     T, H, W = 4, 12, 16
     cfg = dict(T=T, H=H, W=W, focal=W / 2.0 * math.sqrt(3.0))
     syn = S_.SyntheticScene(cfg, _dev())
@@ -184,7 +178,7 @@ def test_trainer_on_a_scene_eager_and_captured(name, scene_posed, scene_unposed)
     """one eager step and captured iterations of Trainer(data=scene); a replay is the eager iteration on the same state, by
     the criterion of tests/test_gpu_graph.py (losses at 2e-6, gradients at 5e-5 relative L2, the field of view -- one float
     every ray adds to -- at 2e-3)."""
-    S_, _, _ = _mods()
+    S_ = pkg("step")
     scene = scene_posed if name == "nvidia" else scene_unposed
     cfg = small_cfg(name)
     tr_g = S_.Trainer(dict(cfg), _dev(), graph=True, data=scene)
@@ -235,7 +229,7 @@ def test_trainer_on_a_scene_eager_and_captured(name, scene_posed, scene_unposed)
 
 
 def test_trainer_refuses_a_config_of_another_shape(scene_posed, scene_unposed):
-    S_, _, _ = _mods()
+    S_ = pkg("step")
     with pytest.raises(ValueError, match="H"):
         S_.Trainer(small_cfg("nvidia", H=H27 + 1), _dev(), data=scene_posed)
     with pytest.raises(ValueError, match="poses"):
@@ -243,7 +237,7 @@ def test_trainer_refuses_a_config_of_another_shape(scene_posed, scene_unposed):
 
 
 def test_trainer_step_on_a_shard_of_a_scene(scene_posed):
-    S_, _, _ = _mods()
+    S_ = pkg("step")
     tr = S_.Trainer(small_cfg("nvidia"), _dev(), data=scene_posed)
     loss = tr.step(shard=(1, 2))
     tr.finish_step()
@@ -252,7 +246,7 @@ def test_trainer_step_on_a_shard_of_a_scene(scene_posed):
 
 # ---- fit: the resolution schedule ----------------------------------------------------------------------------------
 def test_fit_follows_the_resolution_schedule(scene_unposed):
-    S_, _, _ = _mods()
+    S_ = pkg("step")
     cfg = small_cfg("nvidia_no_poses", upsamp_list=[3, 6, 9, 12], n_iters=16, N_voxel_init=16 ** 3, N_voxel_final=32 ** 3,
                     batch_size=256)
     del cfg["grid"], cfg["n_samples"]          # the trainer starts at the schedule's first stage
@@ -326,7 +320,7 @@ def test_fit_learns_an_analytic_video(capsys):
     """200 iterations at a fixed seed on the analytic video: the photometric term (3 x the mean squared error of the composited
     colours against the video's, train.py:1323) averaged over the last 20 iterations is lower than over the first 20.
     Measured: profiles/r11_scene_fit.txt."""
-    S_, SC, _ = _mods()
+    S_, SC = pkg("step"), pkg("scene")
     scene = SC.Scene(**analytic_video(), device=_dev(), seed=11)
     cfg = small_cfg("nvidia", batch_size=256)
     torch.manual_seed(0)
@@ -353,7 +347,7 @@ def _draws(rng, S, n=140):
 
 
 def test_save_and_load_restore_a_run(tmp_path, scene_unposed):
-    S_, SC, _ = _mods()
+    S_, SC = pkg("step"), pkg("scene")
     import rodynrf
     scene = scene_unposed
     cfg = small_cfg("nvidia_no_poses", n_iters=1000)    # a visible decay of every rate per step
@@ -429,7 +423,7 @@ def test_resumed_run_is_bit_identical_in_the_deterministic_build(tmp_path):
 
 # ---- evaluate ------------------------------------------------------------------------------------------------------
 def test_evaluate_equals_the_public_calls_made_by_hand(scene_posed):
-    S_, SC, _ = _mods()
+    S_, SC = pkg("step"), pkg("scene")
     import rodynrf
     scene = scene_posed
     tr = S_.Trainer(small_cfg("nvidia"), _dev(), data=scene)

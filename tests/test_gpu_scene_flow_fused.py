@@ -20,33 +20,24 @@ col(e) being the slot order of the first layer's input rows as rdrf_selftest_dw_
     k_dw3 -- identical on the exact inputs, both within the bound of (b) on the dense ones, g_pts bit-identical in both.
 The int64 / float64 side is checked against plain loops without a GPU (test_reference_against_plain_loops)."""
 import ctypes as C
-import importlib
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "robust-dynrf_amd")
-TOOLS_LIB = os.path.join(PKG, "librodynrf_tools.so")
+from _twin import CHILD, run_twin, tools_lib
+from _util import pkg, profile_line
+
 ROWS, R_X, R_H0, R_H2, R_H4 = 256, 0, 64, 128, 192
 SHAPES = [(64, 36), (64, 64), (64, 64), (6, 64)]   # scene_flow_mlp.{0,2,4,6}.weight
 PREFILL = 3
 DENSE_TILES = 257
 
 
-def _lib():
-    return importlib.import_module("robust-dynrf_amd._lib")
-
-
 def _x_cols():
     """element (row of the X block) -> column of scene_flow_mlp.0.weight, -1: padding; from the scene-flow plan's description"""
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
     import _dw_prim as P
-    desc = P.describe(_lib(), "SCENE_FLOW", 0)
+    desc = P.describe(pkg(), "SCENE_FLOW", 0)
     job = [j for j in desc["jobs"] if j["in_dim"] == 36]
     assert len(job) == 1
     cols = np.full(64, -1, dtype=np.int64)
@@ -57,7 +48,7 @@ def _x_cols():
 
 
 def geometry(ntiles):
-    L = _lib()
+    L = pkg()
     g, w = C.c_int(0), C.c_int(0)
     L.check(L.lib.rdrf_selftest_sf_geometry(int(ntiles), C.byref(g), C.byref(w)), "rdrf_selftest_sf_geometry")
     return g.value, w.value
@@ -180,8 +171,8 @@ class Harness:
     def __init__(self):
         import rodynrf
         from _gpu_util import COMMON
-        self.L = _lib()
-        self.F = importlib.import_module("robust-dynrf_amd.fields")
+        self.L = pkg()
+        self.F = pkg("fields")
         aabb = torch.tensor([[-1.5, -1.67, -1.0], [1.5, 1.67, 1.0]])
         kw = dict(COMMON, near_far=[0.0, 1.0], density_shift=-10.0, fea2denseAct="relu")
         torch.manual_seed(3)
@@ -301,14 +292,6 @@ def dense_reference(seed=0):
     return (n, rows, W, gf, gb), ref, mag, e_seq32(rows, W, gf, gb, n, ref)
 
 
-def _profile_line(text):
-    """RDRF_SF_FUSED_TABLE=<file>: one line per case (measured e beside e_seq32), for profiles/"""
-    path = os.environ.get("RDRF_SF_FUSED_TABLE")
-    if path:
-        with open(path, "a") as f:
-            f.write(text + "\n")
-
-
 _DENSE = []
 
 
@@ -326,7 +309,7 @@ def test_dense_accuracy_against_float64():
     assert all(np.isfinite(a).all() for a in dW + db) and np.isfinite(g_pts).all()
     e = metric((dW, db), ref, mag)
     print(f"scene flow fused, {DENSE_TILES} tiles: e = {e:.3e}   e_seq32 = {e32:.3e}   e / e_seq32 = {e / e32:.3f}")
-    _profile_line(f"scene_flow_fused {DENSE_TILES:4d} {e:.3e} {e32:.3e} {e / e32:.3f}")
+    profile_line("RDRF_SF_FUSED_TABLE", f"scene_flow_fused {DENSE_TILES:4d} {e:.3e} {e32:.3e} {e / e32:.3f}")
     record_margin(f"dW scene flow fused ntiles {DENSE_TILES} e / (2 e_seq32)", e / (2.0 * e32))
     assert e <= 2.0 * e32, f"e = {e:.3e} > 2 x e_seq32 = {2.0 * e32:.3e}"
 
@@ -368,9 +351,8 @@ def test_workspace_contents_do_not_matter():
 
 
 # ---- (d) the tools build: fused against the two-kernel path ----------------------------------------------------------------
-def _child(out):
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
+def ab_case():
+    """what both settings of RDRF_SF_FUSED compute (tests/_det_child.py case)"""
     H = Harness()
     res = {}
     for n in exact_counts():
@@ -383,20 +365,15 @@ def _child(out):
     for i in range(4):
         res[f"d.w{i}"], res[f"d.b{i}"] = dW[i], db[i]
     res["d.pts"] = g_pts
-    np.savez(out, **res)
+    return res
 
 
 @pytest.mark.gpu
 def test_fused_against_two_kernel_path(tmp_path):
-    if not os.path.exists(TOOLS_LIB):
-        subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc"), "-j16", "tools"], timeout=1800)
     got = {}
     for fused in ("1", "0"):
-        out = str(tmp_path / f"sf_{fused}.npz")
-        env = dict(os.environ, RDRF_LIB=TOOLS_LIB, RDRF_SF_FUSED=fused)
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), out], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, (fused, r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-        got[fused] = dict(np.load(out))
+        res = run_twin(tmp_path, [CHILD, "case", "test_gpu_scene_flow_fused", "ab_case"], lib=tools_lib(), extra_env={"RDRF_SF_FUSED": fused})
+        got[fused] = {k: v.numpy() for k, v in res.items()}
     assert sorted(got["1"]) == sorted(got["0"])
     for k in sorted(got["1"]):
         a, b = got["1"][k], got["0"][k]
@@ -408,6 +385,3 @@ def test_fused_against_two_kernel_path(tmp_path):
         print(f"tools build, RDRF_SF_FUSED={fused}: e = {e:.3e}   e_seq32 = {e32:.3e}")
         assert e <= 2.0 * e32, (fused, e, e32)
 
-
-if __name__ == "__main__":
-    _child(sys.argv[1])

@@ -3,10 +3,6 @@ tests/_simplify_prim.py: bit-equal counts, remap, faces, colours and positions o
 structure changes, bounds counted from the kernels' operations on general inputs, the properties of a clustered real mesh,
 isolation (poisoned workspace, guarded outputs, untouched inputs) and determinism (two runs, the deterministic twin)."""
 import ctypes as C
-import os
-import subprocess
-import sys
-from importlib import import_module
 
 import numpy as np
 import pytest
@@ -14,7 +10,8 @@ import torch
 
 import _iso_prim as P
 import _simplify_prim as S
-from _util import record_margin
+from _twin import CHILD, run_twin
+from _util import pkg, record_margin
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -22,7 +19,7 @@ GUARD = 5   # poisoned rows in front of every output
 
 
 def sort_tile():
-    L = import_module("robust-dynrf_amd._lib")
+    L = pkg()
     out = (C.c_ulong * 9)()
     assert L.lib.rdrf_selftest_sort_describe(1, 100000, 18, out, 9) == 9
     return int(out[4])
@@ -31,7 +28,7 @@ def sort_tile():
 def run(verts, faces, origin, cell, n, normals=None, colors=None, drop=True, ws_byte=0xFF):
     """the two native calls on numpy inputs with a poisoned workspace of exactly the advertised size and guarded, oversized
     outputs; checks that nothing outside [0, nv) / [0, nf) was written and that the inputs are unchanged"""
-    L = import_module("robust-dynrf_amd._lib")
+    L = pkg()
     v_np = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3)
     f_np = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
     V, F = len(v_np), len(f_np)
@@ -328,7 +325,7 @@ def test_python_surface_lattices_and_refusals():
 
 # ---- determinism -------------------------------------------------------------------------------------------------------------
 def det_case():
-    """what both libraries run (tests/_simplify_det_child.py)"""
+    """what both libraries run (tests/_det_child.py case)"""
     out = {}
     verts, faces, normals, colors = general_case()
     for byte in (0xFF, 0x00):
@@ -353,14 +350,7 @@ def test_two_runs_and_both_workspace_poisons_give_the_same_bits():
 
 def test_deterministic_library_gives_the_same_bits(tmp_path):
     mine = det_case()
-    env = dict(os.environ, RDRF_DETERMINISTIC="1")
-    env.pop("RDRF_MARGINS", None)
-    env.pop("RDRF_LIB", None)
-    out = str(tmp_path / "det.pt")
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_simplify_det_child.py")
-    r = subprocess.run([sys.executable, child, out], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    det = torch.load(out)
+    det = run_twin(tmp_path, [CHILD, "case", "test_gpu_simplify"], det=True)
     assert set(det) == set(mine)
     for k, v in mine.items():
         assert v.numpy().tobytes() == det[k].numpy().tobytes(), k

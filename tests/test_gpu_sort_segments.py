@@ -4,11 +4,12 @@ nseg independent stable sorts of seg_len consecutive entries over the low `bits`
 GLOBAL positions segment * seg_len + index.  Segment lengths at the 64-entry round, the wave-quarter (512) and the 2048-entry tile
 edges (a tile must not straddle two segments); bits at the one-, two- and three-pass edges and with an uneven last digit.  Output
 and temporary storage are filled with 0xFF before every call."""
-import importlib
 
 import numpy as np
 import pytest
 import torch
+
+from _util import pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -16,13 +17,9 @@ SEG_LENS = [1, 63, 64, 65, 511, 512, 513, 2047, 2048, 2049, 3 * 2048 + 1]
 BITS = [1, 8, 9, 10, 17, 18, 19]
 
 
-def _lib():
-    return importlib.import_module("robust-dynrf_amd._lib")
-
-
 def seg_sort(keys, nseg, seg_len, bits, count=None):
     """-> (keys_out, order, temp after the call) as uint32 / uint8 arrays; outputs pre-filled with 0xFF bytes"""
-    L = _lib()
+    L = pkg()
     n = nseg * seg_len
     assert len(keys) == n
     k = torch.from_numpy(keys.view(np.int32).copy()).cuda()
@@ -96,7 +93,7 @@ def test_a_device_count_sets_length_and_stride_and_the_rest_is_left_alone(count)
 @pytest.mark.parametrize("seg_len", [2049, 3 * 2048 + 1])
 def test_three_segments_over_kb_bits_equal_one_sort_over_kb_plus_two(kb, seg_len):
     """keys as the key kernel of the sorted scatter builds them: segment p carries p << kb above its cell bits"""
-    L = _lib()
+    L = pkg()
     rng = np.random.default_rng(kb * seg_len)
     n = 3 * seg_len
     cell = rng.integers(0, 1 << kb, n, dtype=np.uint64)
@@ -116,7 +113,7 @@ def test_three_segments_over_kb_bits_equal_one_sort_over_kb_plus_two(kb, seg_len
 
 
 def test_bad_arguments_are_refused():
-    L = _lib()
+    L = pkg()
     k = torch.zeros(64, dtype=torch.int32, device="cuda")
     tmp = torch.zeros(1 << 16, dtype=torch.uint8, device="cuda")
     st = L.stream_of(k)

@@ -10,20 +10,15 @@ and torch.equal for the exact cases (integer scatter, identity resize, zero Adam
 oracle evaluation meets the same bounds on the same cases (test_step_primitives_cpu.py); profiles/step_kernels_margins.txt
 holds both sets of ratios and the fault table."""
 import ctypes as C
-import importlib
 
 import numpy as np
 import pytest
 import torch
 
 import _step_prim as P
-from _util import record_margin
+from _util import pkg, record_margin
 
 pytestmark = pytest.mark.gpu
-
-
-def _L():
-    return importlib.import_module("robust-dynrf_amd._lib")
 
 
 def _cu(a):
@@ -38,7 +33,7 @@ def _check(got, ref, cond, k, tag, extra=0.0):
 
 # ---- Adam -------------------------------------------------------------------------------------------------------------------
 def _adam_gpu(p, g, m, v, split, step, gs):
-    L = _L()
+    L = pkg()
     h = P.ADAM_HYPER
     tp, tg, tm, tv = _cu(p), _cu(g), _cu(m), _cu(v)
     L.check(L.lib.rdrf_adam_step(L.ptr(tp), L.ptr(tg), L.ptr(tm), L.ptr(tv), C.c_size_t(p.size), C.c_size_t(split), h["lr0"], h["lr1"],
@@ -83,7 +78,7 @@ def test_adam_seven_chained_steps_match_float64():
 
 # ---- loss terms -------------------------------------------------------------------------------------------------------------
 def _terms(reducer=None):
-    return importlib.import_module("robust-dynrf_amd.losses").LossTerms(reducer)
+    return pkg("losses").LossTerms(reducer)
 
 
 LOSS_COMBOS = (("plain", "mean", False, -1.0), ("plain", "mean", True, 1.0), ("plain", "weight", True, -1.0),
@@ -190,7 +185,7 @@ def test_loss_terms_two_rank_statistics_recombine(norm):
 
 # ---- frame depth loss ----------------------------------------------------------------------------------------------------------
 def _fdl(pred, gt, frame, T, mask, coef=0.04):
-    LS = importlib.import_module("robust-dynrf_amd.losses")
+    LS = pkg("losses")
     p = _cu(pred).requires_grad_(True)
     loss = LS.frame_depth_loss(p, _cu(gt), _cu(frame), T, mask=None if mask is None else _cu(mask), coef=coef)
     (loss * 1.7).backward()
@@ -228,7 +223,7 @@ def test_frame_depth_loss_every_frame_skipped_is_pinned():
 def test_distortion_loss_matches_float64(S):
     """per ray through the C ABI (with g_w pre-filled: the backward accumulates), and the mean through flatten_eff_distloss"""
     import rodynrf
-    L = _L()
+    L = pkg()
     w, m, iv = P.dist_inputs(S, 0)
     N = w.shape[0]
     pre = P.rng(11, S).standard_normal((N, S)).astype(np.float32)
@@ -264,8 +259,8 @@ class _PlainField:
 def test_tv_matches_float64(shape):
     """the two sums and their gradient through TVLoss (k_tv_fwd / k_tv_bwd), and the one-pass gradient through
     TVLoss.accumulate_grad_ (k_tv_grad, quad and scalar paths) into PRE-FILLED gradients, in three storage orders"""
-    R = importlib.import_module("robust-dynrf_amd.regularizers")
-    L = _L()
+    R = pkg("regularizers")
+    L = pkg()
     C_, H, W = shape
     x, pre = P.tv_inputs(C_, H, W, 0)
     reg = R.TVLoss(1.0)
@@ -298,8 +293,8 @@ def test_tv_matches_float64(shape):
 
 def test_tv_grad_more_tensors_than_one_launch_holds():
     """20 tensors (RDRF_TV_MAX is 16) in one accumulate_grad_ call: the second launch's coefficients and tensors line up"""
-    R = importlib.import_module("robust-dynrf_amd.regularizers")
-    assert _L().TV_MAX == 16
+    R = pkg("regularizers")
+    assert pkg().TV_MAX == 16
     planes, refs = [], []
     for i in range(20):
         C_, H, W = P.TV_SHAPES[3 + i % 4]
@@ -332,8 +327,8 @@ def _cl(a):
 def test_dense_l1_matches_float64(grid):
     """rdrf_dense_l1_fwd / bwd as density_L1 / blending_L1 call them (fields._vm_struct on channel-last factors), both
     activations, normal and small-integer factors (f == 0 exactly under ReLU), gradients accumulated into pre-filled buffers"""
-    L = _L()
-    F = importlib.import_module("robust-dynrf_amd.fields")
+    L = pkg()
+    F = pkg("fields")
     X, Y, Z = grid
     for act in ("relu", "softplus"):
         for regime in ("normal", "integer"):
@@ -363,8 +358,8 @@ def test_upsample_matches_float64_and_identity_is_bit_exact():
     both axes in launches of up to 16 tensors.  Pinned points (rounded source index integral on both axes, the exact product not
     above it: every point of an identity resize, and row / column 121 of 157 -> 133, where the fused lambda falls below 0 and
     only the clamp gives 0) are the source texel bit for bit."""
-    L = _L()
-    R = importlib.import_module("robust-dynrf_amd.regularizers")
+    L = pkg()
+    R = pkg("regularizers")
     jobs = []
     for (hi, ho) in P.UP_PAIRS:
         for (wi, wo) in P.UP_PAIRS:
@@ -394,8 +389,8 @@ def test_upsample_matches_float64_and_identity_is_bit_exact():
 def test_rows_scatter_add_is_exact(case):
     """integer-valued gradients: exact in any order.  Through the C ABI with a pre-filled table and indices -1 / R (skipped:
     torch refuses them in the forward gather), and through gather_rows' backward with the indices in range"""
-    L = _L()
-    RU = importlib.import_module("robust-dynrf_amd.ray_utils")
+    L = pkg()
+    RU = pkg("ray_utils")
     R_, C_, N = case
     idx, g, pre = P.rsa_inputs(R_, C_, N, 0)
     table, ti, tg = _cu(pre), _cu(idx), _cu(g)

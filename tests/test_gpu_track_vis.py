@@ -23,18 +23,17 @@ the unit is 2^-24, the largest relative error of one rounded fp32 operation.
   zq: the kernel forms it in fp32, the reference in float64 from the same points.  Its rounding bound dz is
     _track_vis_prim.zq_rounding; the term is max |ref(zq +- dz) - ref(zq)|, the reference's own change over that interval."""
 import functools
-import importlib
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import _track_vis_prim as P
-from _util import GOLDEN, RTOL, load_case, record_margin
+import _util
+from _twin import CHILD, assert_same_dict, run_twin, same_bits
+from _util import GOLDEN, RTOL, load_case, pkg, record_margin
 from oracle import rodynrf_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -48,11 +47,6 @@ SHIFT = {"ndc": -2.0, "contract": -3.0}
 CASE = {"ndc": "motion_ndc", "contract": "motion_contract"}
 C_FACTOR, C0 = 14, 5
 U24 = 2.0 ** -24
-
-
-def _rodynrf():
-    import rodynrf
-    return rodynrf
 
 
 def scan_geometry():
@@ -76,7 +70,7 @@ def scene(rt, shift=None, blend_bias=None):
     """blend_bias: the blending head puts out this constant before its sigmoid (40: blending is exactly 1).
     (g, static field, dynamic field, cams [9,3,4] on the device, poses9 [3,9] + slot -> camera table on the host, focal, H, W)"""
     from _gpu_util import COMMON
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     g, sd_s, _, sd_d, _ = load_case(CASE[rt])
     kw = dict(COMMON, near_far=[float(v) for v in g["meta.near_far"]], density_shift=SHIFT[rt] if shift is None else shift,
               fea2denseAct=str(g["meta.act"]))
@@ -121,7 +115,7 @@ def step_of(rt, S):
 
 
 def tracks_of(rt, M, n_fwd, n_bwd):
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     _, st, dy, cams, _, focal, H, W = scene(rt)
     p0, t0 = seeds(rt, M)
     K = n_bwd + 1 + n_fwd
@@ -130,7 +124,7 @@ def tracks_of(rt, M, n_fwd, n_bwd):
 
 
 def native(rt, tr, t0, cams, n_fwd, n_bwd, S, margin, fields=None):
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     _, st, dy, _, _, focal, H, W = scene(rt)
     if fields is not None:
         st, dy = fields
@@ -153,7 +147,7 @@ def slot_times(t0, n_fwd, n_bwd):
 
 def reference(rt, tr, t0, n_fwd, n_bwd, S, margin, fields=None):
     """float64 reference on the project's own forward(rgb=False) outputs for host-built rays -> dict of [M*K] arrays"""
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     _, st, dy, cams, (poses9, table), focal, H, W = scene(rt)
     if fields is not None:
         st, dy = fields
@@ -247,37 +241,33 @@ def test_visibility_against_the_oracle_end_to_end(rt):
 
 
 # ---- 3. bit identities -------------------------------------------------------------------------------------------------
-def _same(a, b):
-    return a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
-
-
 @pytest.mark.parametrize("rt", ["ndc", "contract"])
 def test_a_slot_does_not_depend_on_its_batch_or_on_the_run(rt):
     S, margin = 64, 2.0 * step_of(rt, 64)
     tr, t0, cams = tracks_of(rt, 70, 5, 3)
     whole = native(rt, tr, t0, cams, 5, 3, S, margin)
-    assert _same(native(rt, tr, t0, cams, 5, 3, S, margin), whole)
+    assert same_bits(native(rt, tr, t0, cams, 5, 3, S, margin), whole)
     for i in (0, 17, 69):
         alone = native(rt, tr.points[i:i + 1], t0[i:i + 1], cams, 5, 3, S, margin)
-        assert _same(alone, whole[i:i + 1]), i
+        assert same_bits(alone, whole[i:i + 1]), i
     for k in (0, 3, 8):   # one slot of one point: its own camera and its own time
         t_k = slot_times(t0.cpu(), 5, 3)[:, k].to(DEV)
         alone = native(rt, tr.points[5:6, k:k + 1], t_k[5:6], cams[k:k + 1], 0, 0, S, margin)
-        assert _same(alone, whole[5:6, k:k + 1]), k
+        assert same_bits(alone, whole[5:6, k:k + 1]), k
 
 
 @pytest.mark.parametrize("rt", ["ndc", "contract"])
 def test_chunked_calls_give_the_same_bits(rt, monkeypatch):
-    R = importlib.import_module("robust-dynrf_amd.renderer")
+    R = pkg("renderer")
     S, margin = 13, 0.0
     tr, t0, cams = tracks_of(rt, 70, 5, 3)
     whole = native(rt, tr, t0, cams, 5, 3, S, margin)
     monkeypatch.setattr(R, "_track_vis_chunk", lambda M, K, S, H, W: 32)
-    assert _same(native(rt, tr, t0, cams, 5, 3, S, margin), whole)
+    assert same_bits(native(rt, tr, t0, cams, 5, 3, S, margin), whole)
 
 
 def det_case():
-    """what both libraries compute (tests/_track_vis_det_child.py)"""
+    """what both libraries compute (tests/_det_child.py case)"""
     out = {}
     for rt in ("ndc", "contract"):
         tr, t0, cams = tracks_of(rt, 70, 5, 3)
@@ -287,24 +277,14 @@ def det_case():
 
 
 def test_deterministic_library_gives_the_same_bits(tmp_path):
-    ours = {k: v.cpu() for k, v in det_case().items()}
-    env = dict(os.environ, RDRF_DETERMINISTIC="1")
-    env.pop("RDRF_MARGINS", None)
-    env.pop("RDRF_LIB", None)
-    out = str(tmp_path / "det.pt")
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_track_vis_det_child.py")
-    r = subprocess.run([sys.executable, child, out], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    det = torch.load(out)
-    assert sorted(det) == sorted(ours)
-    for k in ours:
-        assert _same(det[k], ours[k]), k
+    ours = det_case()
+    assert_same_dict(run_twin(tmp_path, [CHILD, "case", "test_gpu_track_vis"], det=True), ours)
 
 
 @functools.lru_cache(maxsize=None)
 def tiny_scene(rt):
     from _gpu_util import COMMON
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     torch.manual_seed(31)
     aabb = torch.tensor([[-1.5, -1.67, -1.0], [1.5, 1.67, 1.0]]) if rt == "ndc" else torch.tensor([[-2.0] * 3, [2.0] * 3])
     kw = dict(COMMON, near_far=[0.0, 1.0] if rt == "ndc" else [0.0, 256.0], density_shift=-2.0, fea2denseAct="softplus")
@@ -326,7 +306,7 @@ def tiny_scene(rt):
 @pytest.mark.parametrize("rt", ["ndc", "contract"])
 def test_visibility_of_render_tracks_own_tracks(rt):
     """render_tracks' Tracks go into track_visibility as they are, with the cameras and times its docstring names"""
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     st, dy, p9, focal, T, H, W, pixels = tiny_scene(rt)
     S, frame = 13, 2
     margin = 3.0 * step_of(rt, S)
@@ -337,10 +317,10 @@ def test_visibility_of_render_tracks_own_tracks(rt):
     cams = rodynrf.pose_to_mtx(p9.detach().float())[frame - n_bwd: frame + n_fwd + 1]
     vis = rodynrf.track_visibility(st, dy, tracks, ts, n_fwd, n_bwd, T, cams, focal, H, W, N_samples=S, ray_type=rt, margin=margin)
     assert vis.shape == (40, T) and bool(torch.isfinite(vis).all()) and bool(((vis >= 0) & (vis <= 1)).all())
-    assert _same(vis, rodynrf.track_visibility(st, dy, tracks.points, ts, n_fwd, n_bwd, T, cams, focal, H, W, N_samples=S,
+    assert same_bits(vis, rodynrf.track_visibility(st, dy, tracks.points, ts, n_fwd, n_bwd, T, cams, focal, H, W, N_samples=S,
                                                ray_type=rt, margin=margin))
     again = rodynrf.render_tracks(st, dy, p9, focal, frame, pixels, H, W, N_samples=S, ray_type=rt)   # the render is left as it was
-    assert _same(again[0].points, tracks.points) and _same(again[1], acc_d)
+    assert same_bits(again[0].points, tracks.points) and same_bits(again[1], acc_d)
     # a seed sits inside the density that defines it: with the margin it is seen better than without
     raw = rodynrf.track_visibility(st, dy, tracks, ts, n_fwd, n_bwd, T, cams, focal, H, W, N_samples=S, ray_type=rt)
     assert bool((raw <= vis).all()) and float(raw[:, frame].mean()) < float(vis[:, frame].mean())
@@ -349,7 +329,7 @@ def test_visibility_of_render_tracks_own_tracks(rt):
 # ---- 4. regimes --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("rt", ["ndc", "contract"])
 def test_regimes(rt):
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     S = 13
     tr, t0, cams = tracks_of(rt, 70, 5, 3)
     _, st, dy, _, _, focal, H, W = scene(rt)

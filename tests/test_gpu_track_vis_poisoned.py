@@ -3,12 +3,14 @@ are filled with 0xFF bytes (a NaN in every float, -1 in every list entry and cou
 both.  Every visibility is finite and has the bits of the run on fresh buffers; the guards stay untouched.  The kernels may
 read only what the call itself wrote: the list counter is cleared by the time-branch launch, sigma and blending of every sample
 that no density kernel visits are zero-filled by the keep pass."""
-import importlib
 
 import pytest
 import torch
 
 import test_gpu_track_vis as V
+
+from _twin import same_bits
+from _util import pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -16,9 +18,9 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("packed", [True, False], ids=["packed-image", "packs-into-workspace"])
 @pytest.mark.parametrize("rt,M,S", [("ndc", 33, 65), ("contract", 70, 13)])
 def test_poisoned_output_and_workspace(rt, M, S, packed, monkeypatch):
-    R = importlib.import_module("robust-dynrf_amd.renderer")
-    F = importlib.import_module("robust-dynrf_amd.fields")
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    R = pkg("renderer")
+    F = pkg("fields")
+    L = pkg()
     monkeypatch.setattr(F, "PACK_CACHE", packed)
     _, st, dy, _, _, focal, H, W = V.scene(rt)
     n_fwd, n_bwd, K, G = 5, 3, 9, 257
@@ -36,6 +38,6 @@ def test_poisoned_output_and_workspace(rt, M, S, packed, monkeypatch):
     R._track_visibility_raw(st, dy, tr.points, t0, n_fwd, n_bwd, dt, cams, focal, H, W, S, rt, margin, vis=vis, ws=ws[:nbytes])
     torch.cuda.synchronize()
     assert bool(torch.isfinite(vis).all())
-    assert V._same(vis.contiguous(), ref)
+    assert same_bits(vis.contiguous(), ref)
     assert bool((big[:G].view(torch.uint8) == 0xFF).all()) and bool((big[G + M * K:].view(torch.uint8) == 0xFF).all())
     assert bool((ws[nbytes:] == 0xFF).all())

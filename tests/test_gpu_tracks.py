@@ -12,17 +12,16 @@ and the projection of slot k adds one more evaluation: (k + 1) * 1e-4 * max|ref|
 COMPOSITION of public calls.  The native chain is not given this room: per output and slot its error against the fixture
 must not exceed the error the composition shows there in the same run -- the composition's measured margin plus nothing."""
 import functools
-import importlib
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from _util import GOLDEN, assert_close, record_margin
+import _util
+from _twin import CHILD, assert_same_dict, run_twin
+from _util import GOLDEN, assert_close, pkg, record_margin
 
 pytestmark = pytest.mark.gpu
 
@@ -56,11 +55,6 @@ M_MULTI = _m_multi()
 SIZES = (1, 31, 32, 33, 70)
 
 
-def _rodynrf():
-    import rodynrf
-    return rodynrf
-
-
 @functools.lru_cache(maxsize=None)
 def fixture():
     z = np.load(os.path.join(GOLDEN, "tracks.npz"))
@@ -70,7 +64,7 @@ def fixture():
 @functools.lru_cache(maxsize=None)
 def field(rt):
     from _gpu_util import COMMON
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     z = fixture()
     kw = dict(COMMON, near_far=[0.0, 1.0] if rt == "ndc" else [0.0, 256.0], density_shift=float(z["meta.density_shift"]),
               fea2denseAct=str(z["meta.act"]))
@@ -106,7 +100,7 @@ def seeds(rt, M):
 
 def compose(dy, p0, t0, n_fwd, n_bwd, rt, cams=None, focal=None, H=None, W=None):
     """the chain by public calls, one launch sequence per step and slot"""
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     M, K = p0.shape[0], n_bwd + 1 + n_fwd
     dt = 2.0 / (T_VIDEO - 1)
     pts = [None] * K
@@ -137,7 +131,7 @@ def compose(dy, p0, t0, n_fwd, n_bwd, rt, cams=None, focal=None, H=None, W=None)
 
 
 def native(dy, p0, t0, n_fwd, n_bwd, rt, with_cams=True):
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     cams, focal, H, W = cameras()
     K = n_bwd + 1 + n_fwd
     if not with_cams:
@@ -245,7 +239,7 @@ def test_track_points_against_the_reference_chain(rt):
 # ---- 4 -----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("rt", ["ndc", "contract"])
 def test_outputs_do_not_depend_on_the_split_or_on_the_requested_outputs(rt):
-    R = importlib.import_module("robust-dynrf_amd.renderer")
+    R = pkg("renderer")
     dy = field(rt)
     p0, t0 = seeds(rt, 70)
     cams, focal, H, W = cameras()
@@ -266,9 +260,9 @@ def test_outputs_do_not_depend_on_the_split_or_on_the_requested_outputs(rt):
 @pytest.mark.parametrize("packed", [True, False], ids=["packed-image", "packs-into-workspace"])
 @pytest.mark.parametrize("rt,M", [("ndc", 33), ("contract", 70)])
 def test_poisoned_workspace_and_guard_bands(rt, M, packed, monkeypatch):
-    R = importlib.import_module("robust-dynrf_amd.renderer")
-    F = importlib.import_module("robust-dynrf_amd.fields")
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    R = pkg("renderer")
+    F = pkg("fields")
+    L = pkg()
     monkeypatch.setattr(F, "PACK_CACHE", packed)
     dy = field(rt)
     p0, t0 = seeds(rt, M)
@@ -304,7 +298,7 @@ def tiny_scene(rt, empty=False):
     """empty: relu density and a dynamic density head that puts out -1 everywhere -- sigma_d is exactly 0, acc_d = 0, every seed
     is its ray's far point"""
     from _gpu_util import COMMON
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     torch.manual_seed(31)
     aabb = torch.tensor([[-1.5, -1.67, -1.0], [1.5, 1.67, 1.0]]) if rt == "ndc" else torch.tensor([[-2.0] * 3, [2.0] * 3])
     kw = dict(COMMON, near_far=[0.0, 1.0] if rt == "ndc" else [0.0, 256.0], density_shift=-1.0, fea2denseAct="relu" if empty else "softplus")
@@ -329,7 +323,7 @@ def tiny_scene(rt, empty=False):
 
 @pytest.mark.parametrize("rt", ["ndc", "contract"])
 def test_render_tracks_on_a_tiny_scene(rt):
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     st, dy, p9, focal, T, H, W, pixels = tiny_scene(rt)
     S, frame = 13, 2
     ids = pixels[:, 1] * W + pixels[:, 0] + frame * H * W
@@ -386,7 +380,7 @@ def test_render_tracks_on_a_tiny_scene(rt):
 @pytest.mark.parametrize("rt", ["ndc", "contract"])
 def test_render_tracks_seeds_in_empty_space_are_the_far_points(rt):
     """the (1 - acc_d) far leg of the seed, which the scene above (acc_d = 1 on every ray) leaves at 0"""
-    rodynrf = _rodynrf()
+    rodynrf = _util.rodynrf()
     st, dy, p9, focal, T, H, W, pixels = tiny_scene(rt, True)
     S, frame = 13, 3
     tracks, acc_d = rodynrf.render_tracks(st, dy, p9, focal, frame, pixels, H, W, span=1, N_samples=S, ray_type=rt)
@@ -408,7 +402,7 @@ def test_render_tracks_seeds_in_empty_space_are_the_far_points(rt):
 
 # ---- 7 -----------------------------------------------------------------------------------------
 def det_case():
-    """what both libraries compute (tests/_tracks_det_child.py): the (5, 3) tracks of test 2 at M = 70"""
+    """what both libraries compute (tests/_det_child.py case): the (5, 3) tracks of test 2 at M = 70"""
     out = {}
     for rt in ("ndc", "contract"):
         p0, t0 = seeds(rt, 70)
@@ -418,15 +412,5 @@ def det_case():
 
 
 def test_deterministic_library_gives_the_same_bits(tmp_path):
-    ours = {k: v.cpu() for k, v in det_case().items()}
-    env = dict(os.environ, RDRF_DETERMINISTIC="1")
-    env.pop("RDRF_MARGINS", None)
-    env.pop("RDRF_LIB", None)
-    out = str(tmp_path / "det.pt")
-    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_tracks_det_child.py")
-    r = subprocess.run([sys.executable, child, out], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    det = torch.load(out)
-    assert sorted(det) == sorted(ours)
-    for k in ours:
-        assert torch.equal(det[k], ours[k]), k
+    ours = det_case()
+    assert_same_dict(run_twin(tmp_path, [CHILD, "case", "test_gpu_tracks"], det=True), ours)

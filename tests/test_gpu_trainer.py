@@ -2,20 +2,19 @@
 a small synthetic scene stays finite and reduces the loss -- catches sign / accumulation mistakes in
 the fused-gradient, pruning and optimiser wiring that per-kernel parity tests cannot see."""
 import functools
-import importlib
 
 import numpy as np
 
 import pytest
 import torch
 
-from _util import assert_close, record_margin
+from _util import assert_close, pkg, record_margin
 
 pytestmark = pytest.mark.gpu
 
 
 def test_short_training_run_reduces_loss():
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     cfg = S_.balloon1_config("stage0")
     cfg.update(grid=[36, 40, 24], n_samples=48, batch_size=512, H=27, W=48, T=6)
     cfg["focal"] = max(cfg["H"], cfg["W"]) / 2.0 * 3.0 ** 0.5
@@ -50,7 +49,7 @@ def test_two_rank_step_with_exact_statistics_matches_single_process(mode, tmp_pa
     import os
     import subprocess
     import sys
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cfg = dp_check_cfg(S_)
     torch.manual_seed(0)
@@ -166,7 +165,7 @@ def test_trainer_step_gradient_matches_oracle_step(name, it):
     margins 0.12-0.30.  The version of this comparison that is pinned to the REFERENCE's own trainer at 1e-4 is
     test_trainer_step_matches_reference_trainer_iteration.)"""
     from oracle import rodynrf_oracle_step as OS
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     cfg = S_.scene_config(name, "stage0")
     cfg.update(SMALL[name])
     cfg["focal"] = max(cfg["H"], cfg["W"]) / 2.0 * 3.0 ** 0.5
@@ -243,7 +242,7 @@ def test_config_workloads_run_at_full_shape(name, stage, rays):
     finite parameters, gradients reach every factor family, poses and focal; and size-independent properties:
     repeat runs of the forward are bit-identical, a slice of the batch run alone reproduces its outputs."""
     import rodynrf
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     cfg = S_.scene_config(name, stage)
     cfg["batch_size"] = rays
     dev = torch.device("cuda", 0)
@@ -283,7 +282,7 @@ def test_full_size_batch_independence_and_gradient_additivity():
     for every ray of the full batch); (2) gradients of a sum-type loss are additive over ray subsets
     (the scatter / dW accumulation of 471k samples equals the sum of its halves)."""
     import rodynrf
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     cfg = S_.balloon1_config("stage0")
     dev = torch.device("cuda", 0)
     st, dy = S_.build_fields(cfg, dev)
@@ -351,7 +350,7 @@ def test_pass_structure_matches_reference_fixture(case, dead_work):
     from _gpu_util import ELEM
     from _util import load_case, load_pass_structure, pass_structure_cfg, pass_structure_draws
     from oracle.rodynrf_oracle_step import ReplayRng
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     g, sd_s, _, sd_d, _ = load_case(case)
     p = load_pass_structure(case)
     cfg = pass_structure_cfg(g)
@@ -416,7 +415,7 @@ def test_upsample_restarts_learning_rates_like_the_reference():
     Adam starts at lr_init / lr_basis again (not at the decayed rates), the moments and the step count are dropped,
     the pose rate restarts at lr_pose and the focal rate is switched on from upsamp_list[3]; with
     lr_upsample_reset = 0 the rates continue at lr * lr_decay_target_ratio ** (iteration / n_iters)."""
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     cfg = S_.scene_config("nvidia_no_poses", "stage0")
     cfg.update(SMALL["nvidia_no_poses"])
     cfg["focal"] = max(cfg["H"], cfg["W"]) / 2.0 * 3.0 ** 0.5
@@ -450,7 +449,7 @@ def test_batched_passes_match_one_pass_per_launch(name, stage, it, monkeypatch):
     late stage (B alone, C + D batched), at [706,786,471] / S = 578 with 3 x 4096 rays in one dynamic call (7.1 M
     samples: the batched buffers pass 2^32 floats, the per-pass ones do not) and 4 x 4096 in the static call of the pose
     block's passes P1-P4, and on contracted rays (davis)."""
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     cfg = S_.scene_config(name, stage)
     if name == "nvidia_no_poses":   # lift step.BATCH_MAX_SAMPLES (6 M): all of B-D / P1-P4 in one call each
         monkeypatch.setattr(S_, "BATCH_MAX_SAMPLES", 1 << 40)
@@ -522,7 +521,7 @@ def test_trainer_step_matches_reference_trainer_iteration(name, batched):
     fp32 and fp64 evaluations on top."""
     from _util import load_trainer_iter
     from oracle import rodynrf_oracle_step as OS
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     p, cfg, batch, sd_s, sd_d, poses, focal, draws = load_trainer_iter(name)
     dev = torch.device("cuda", 0)
     tr = S_.Trainer(dict(cfg), dev, dead_work=True, batch_passes=batched)
@@ -584,7 +583,7 @@ def test_dead_work_pruning_changes_nothing(name, batched):
     of passes E / P3 / P4 and the appearance phase (colours) of both fields in passes B-D and P1-P4 (forward(rgb=False)) --
     against dead_work=True: the same draws, the same loss values, the same gradients (up to the order of the atomic
     accumulation) for both fields, the pose table and the field of view."""
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     cfg = S_.scene_config(name, "stage0")
     cfg.update(SMALL[name])
     cfg["focal"] = max(cfg["H"], cfg["W"]) / 2.0 * 3.0 ** 0.5

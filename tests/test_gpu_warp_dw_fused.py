@@ -25,18 +25,14 @@ col(e) being the slot order of layer3's input rows as rdrf_selftest_dw_describe 
     order of the atomic additions differ, and neither path repeats its own bits there.  The two-kernel path's e is recorded
     beside the fused kernel's.  The deterministic library gives the same bits twice on the dense rows."""
 import ctypes as C
-import importlib
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "robust-dynrf_amd")
-TOOLS_LIB = os.path.join(PKG, "librodynrf_tools.so")
+from _twin import CHILD, run_twin, tools_lib
+from _util import pkg, profile_line
+
 ROWS, GROWS = 576, 544
 R_X0, R_T, R_H3, R_H4, G_DX0 = 0, 96, 128, 192, 480
 SHAPES = {"l3": (64, 93), "l4": (64, 64), "l5": (3, 64)}
@@ -47,15 +43,10 @@ DENSE_TILES = 257
 DT_FILL = 7.0   # dtout / dtp slots the kernel does not write keep this
 
 
-def _lib():
-    return importlib.import_module("robust-dynrf_amd._lib")
-
-
 def _in_cols():
     """row of [X0 (64) | T (32)] -> column of layer3.weight, -1: padding; from the density plan's description"""
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
     import _dw_prim as P
-    desc = P.describe(_lib(), "DENSITY", 0)
+    desc = P.describe(pkg(), "DENSITY", 0)
     job = [j for j in desc["jobs"] if j["in_dim"] == 93]
     assert len(job) == 1
     cols = np.full(96, -1, dtype=np.int64)
@@ -68,7 +59,7 @@ def _in_cols():
 
 
 def geometry(ntiles):
-    L = _lib()
+    L = pkg()
     g, w = C.c_int(0), C.c_int(0)
     L.check(L.lib.rdrf_selftest_warp_geometry(int(ntiles), C.byref(g), C.byref(w)), "rdrf_selftest_warp_geometry")
     return g.value, w.value
@@ -179,8 +170,8 @@ class Harness:
     def __init__(self):
         import rodynrf
         from _gpu_util import COMMON
-        self.L = _lib()
-        self.F = importlib.import_module("robust-dynrf_amd.fields")
+        self.L = pkg()
+        self.F = pkg("fields")
         aabb = torch.tensor([[-1.0, -1.0, -1.0], [1.0, 1.0, 1.0]])
         kw = dict(COMMON, near_far=[0.0, 1.0], density_shift=-10.0, fea2denseAct="relu")
         torch.manual_seed(3)
@@ -339,14 +330,6 @@ def _dense():
     return _DENSE[0]
 
 
-def _profile_line(text):
-    """RDRF_WARP_FUSED_TABLE=<file>: one line per case (measured e beside e_seq32), for profiles/"""
-    path = os.environ.get("RDRF_WARP_FUSED_TABLE")
-    if path:
-        with open(path, "a") as f:
-            f.write(text + "\n")
-
-
 @pytest.mark.gpu
 def test_dense_accuracy_against_float64():
     from _util import record_margin
@@ -355,7 +338,7 @@ def test_dense_accuracy_against_float64():
     assert all(np.isfinite(out[q][k]).all() for q in ("dW", "db") for k in LAYERS) and np.isfinite(out["g_xyz"]).all()
     e = metric(out, ref, mag)
     print(f"warp fused, {c['act'].shape[0]} tiles: e = {e:.3e}   e_seq32 = {e32:.3e}   e / e_seq32 = {e / e32:.3f}")
-    _profile_line(f"warp_fused     {c['act'].shape[0]:4d} {e:.3e} {e32:.3e} {e / e32:.3f}")
+    profile_line("RDRF_WARP_FUSED_TABLE", f"warp_fused     {c['act'].shape[0]:4d} {e:.3e} {e32:.3e} {e / e32:.3f}")
     record_margin(f"dW warp fused ntiles {c['act'].shape[0]} e / (2 e_seq32)", e / (2.0 * e32))
     assert e <= 2.0 * e32, f"e = {e:.3e} > 2 x e_seq32 = {2.0 * e32:.3e}"
 
@@ -415,35 +398,35 @@ def _flatten(res, out, tag):
         res[f"{tag}.{k}"] = out[k]
 
 
-def _child(mode, path):
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
+def ab_case():
+    """what both settings of RDRF_WARP_FUSED compute (tests/_det_child.py case)"""
     H = Harness()
     res = {}
-    if mode == "det":
-        assert H.L.DETERMINISTIC and H.L.lib.rdrf_deterministic() == 1
-        c = dense_case()
-        for rep in ("r0", "r1"):
-            _flatten(res, H.run(c, prefill=False, det=True), rep)
-    else:
-        for N, S in exact_cases():
-            _flatten(res, check_exact(H.run, N, S, 0), f"x{N}_{S}")
-        _flatten(res, H.run(dense_case(), prefill=False), "d")
-        _flatten(res, H.run(dense_case(1, T=1, S=9), prefill=False), "o")   # one tile: one wave on both paths
-    np.savez(path, **res)
+    for N, S in exact_cases():
+        _flatten(res, check_exact(H.run, N, S, 0), f"x{N}_{S}")
+    _flatten(res, H.run(dense_case(), prefill=False), "d")
+    _flatten(res, H.run(dense_case(1, T=1, S=9), prefill=False), "o")   # one tile: one wave on both paths
+    return res
 
 
-def _run_child(mode, out, env):
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), mode, out], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (mode, r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    return dict(np.load(out))
+def det_twice_case():
+    """the dense rows twice in the deterministic library"""
+    H = Harness()
+    res = {}
+    c = dense_case()
+    for rep in ("r0", "r1"):
+        _flatten(res, H.run(c, prefill=False, det=True), rep)
+    return res
+
+
+def _run_child(tmp_path, func, **kw):
+    res = run_twin(tmp_path, [CHILD, "case", "test_gpu_warp_dw_fused", func], **kw)
+    return {k: v.numpy() for k, v in res.items()}
 
 
 @pytest.mark.gpu
 def test_fused_against_two_kernel_path(tmp_path):
-    if not os.path.exists(TOOLS_LIB):
-        subprocess.check_call(["make", "-C", os.path.join(PKG, "csrc"), "-j16", "tools"], timeout=1800)
-    got = {f: _run_child("ab", str(tmp_path / f"warp_{f}.npz"), dict(os.environ, RDRF_LIB=TOOLS_LIB, RDRF_WARP_FUSED=f)) for f in ("1", "0")}
+    got = {f: _run_child(tmp_path, "ab_case", lib=tools_lib(), extra_env={"RDRF_WARP_FUSED": f}) for f in ("1", "0")}
     assert sorted(got["1"]) == sorted(got["0"])
     for k in sorted(got["1"]):
         a, b = got["1"][k], got["0"][k]
@@ -455,19 +438,16 @@ def test_fused_against_two_kernel_path(tmp_path):
         out = dict(dW={k: got[f][f"d.w.{k}"] for k in LAYERS}, db={k: got[f][f"d.b.{k}"] for k in LAYERS})
         e = metric(out, ref, mag)
         print(f"tools build, RDRF_WARP_FUSED={f}: e = {e:.3e}   e_seq32 = {e32:.3e}")
-        _profile_line(f"tools_fused={f}  {c['act'].shape[0]:4d} {e:.3e} {e32:.3e} {e / e32:.3f}")
+        profile_line("RDRF_WARP_FUSED_TABLE", f"tools_fused={f}  {c['act'].shape[0]:4d} {e:.3e} {e32:.3e} {e / e32:.3f}")
         assert e <= 2.0 * e32, (f, e, e32)
 
 
 @pytest.mark.gpu
 def test_deterministic_library_repeats_its_bits(tmp_path):
-    got = _run_child("det", str(tmp_path / "warp_det.npz"), dict(os.environ, RDRF_DETERMINISTIC="1"))
+    got = _run_child(tmp_path, "det_twice_case", det=True)
     keys = sorted(k[3:] for k in got if k.startswith("r0."))
     assert keys and all(np.array_equal(got["r0." + k].view(np.uint32), got["r1." + k].view(np.uint32)) for k in keys)
     c, ref, mag, e32 = _dense()
     out = dict(dW={k: got[f"r0.w.{k}"] for k in LAYERS}, db={k: got[f"r0.b.{k}"] for k in LAYERS})
     assert metric(out, ref, mag) <= 2.0 * e32
 
-
-if __name__ == "__main__":
-    _child(sys.argv[1], sys.argv[2])

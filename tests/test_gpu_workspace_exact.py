@@ -21,6 +21,8 @@ import torch
 import test_gpu_poisoned_scratch as PS
 from test_gpu_poisoned_scratch import M, N, S
 
+from _util import pkg
+
 pytestmark = pytest.mark.gpu
 
 TAIL, CANARY, SENT = 64 << 10, 0xA5, 7.0
@@ -28,7 +30,7 @@ TAIL, CANARY, SENT = 64 << 10, 0xA5, 7.0
 
 @contextlib.contextmanager
 def exact_workspaces():
-    L, _ = PS._mods()
+    L = pkg()
     orig, handed = L.workspace, []
 
     def exact(device, nbytes):
@@ -75,7 +77,7 @@ def test_feature_entry_points_stay_inside_the_requested_workspace():
 def _short_case(name):
     """-> (backward(ws, ws_bytes) -> rc, gradient tensors pre-filled with SENT, size function value) after the forward call that
     fills the saved buffer; everything the calls point to is kept alive by the closure"""
-    L, F = PS._mods()
+    L, F = pkg(), pkg("fields")
     st, dy = PS._fields("ndc")
     rays, ts, xyz, z, valid, _ = PS._batch(dy, "ndc")
     rays, ts, xyz, z = (L.f32c(t) for t in (rays, ts, xyz, z))

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from _util import GOLDEN, assert_close
+from _util import GOLDEN, assert_close, pkg
 
 pytestmark = pytest.mark.gpu
 
@@ -292,10 +292,9 @@ def test_refusals():
     """what the reference has no world branch for still raises: motion maps and induced flow; and the render entry points of
     the other two ray types refuse a world-space config instead of sampling it as a contracted one"""
     import ctypes as C
-    import importlib
     import rodynrf
-    L = importlib.import_module("robust-dynrf_amd._lib")
-    F = importlib.import_module("robust-dynrf_amd.fields")
+    L = pkg()
+    F = pkg("fields")
     g = fixture()[0]
     st, dy = fields("a")
     rays, ts = dev(g["rays"]), dev(g["ts"])

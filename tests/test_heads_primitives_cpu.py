@@ -6,7 +6,6 @@
     exactly the ones dtout_of_ray must not read;
   * the reference of dtout_of_ray equals a brute-force per-sample sum at every (N, S) used;
   * the layouts the library reports are consistent with each other, and the three entry points are declared."""
-import importlib
 import os
 import re
 import sys
@@ -15,6 +14,8 @@ import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+from _util import pkg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -27,18 +28,14 @@ NEW = ("rdrf_selftest_heads_bwd_workspace_bytes", "rdrf_selftest_heads_describe"
 _LAY = []
 
 
-def _L():
-    return importlib.import_module("robust-dynrf_amd._lib")
-
-
 def _lay():
     if not _LAY:
-        _LAY.append(Q.layout(_L()))
+        _LAY.append(Q.layout(pkg()))
     return _LAY[0]
 
 
 def test_entry_points_are_declared():
-    L = _L()
+    L = pkg()
     header = open(os.path.join(ROOT, "include", "rodynrf.h")).read()
     for name in NEW:
         assert name in L.SIGNATURES and hasattr(L.lib, name) and re.search(r"\b%s\(" % name, header), name
@@ -54,7 +51,7 @@ def test_layouts_agree_with_each_other():
     assert sorted(s for *_, s in lay["fmap"]) == list(range(lay["nfeat"])) and 2 * lay["set_floats"] == lay["rec"]
     spans = sorted([(lay["DZ"][0], 64), (lay["DZ"][1], 64), (lay["DF"][0], 96), (lay["DF"][1], 96), (lay["DX0"], 64), (lay["SM"][0] - 3, 5)])
     assert all(a + n <= b for (a, n), (b, _) in zip(spans, spans[1:])) and spans[-1][0] + spans[-1][1] <= lay["grows"]
-    L = _L()
+    L = pkg()
     for N, S in Q.FLAT_SHAPES:
         g = Q.heads_describe(L, 0, N, S)
         assert g["tiles"] == (N * S + 31) // 32 and g["grid"] * g["waves"] >= min(g["tiles"], 256) and 1 <= g["waves"] <= 8
@@ -120,7 +117,7 @@ def test_heads_reference_equals_autograd(mode, act, live):
 @pytest.mark.parametrize("mode,shape", [("flat", s) for s in Q.FLAT_SHAPES] + [("feat", (m, 1)) for m in Q.FEAT_SIZES])
 @pytest.mark.parametrize("act", ["relu", "softplus"])
 def test_heads_float32_evaluation_meets_every_bound(mode, shape, act):
-    lay, W, L = _lay(), Q.heads_weights(), _L()
+    lay, W, L = _lay(), Q.heads_weights(), pkg()
     c = Q.heads_case(mode, shape[0], shape[1], act, ("d", "b"), seed=2)
     geo = Q.heads_describe(L, 0 if mode == "flat" else 1, shape[0], shape[1])
     pre = {k: np.zeros(64 if k[1] == "w" else 1) for k in ("dw2", "db2", "bw2", "bb2")}
@@ -135,7 +132,7 @@ def test_heads_float32_evaluation_meets_every_bound(mode, shape, act):
 def test_heads_small_sums_across_waves_and_tiles():
     """the two large shapes of the GPU file: more than one wave per workgroup, and waves that walk more than one tile; the small-layer
     sums of a float32 evaluation in the kernel's order meet the derived bound there as well"""
-    L = _L()
+    L = pkg()
     g = Q.heads_describe(L, 0, *Q.FLAT_WAVES)
     assert g["waves"] > 1 and g["grid"] > 1 and g["grid"] * g["waves"] >= g["tiles"]
     gw = Q.heads_describe(L, 0, *Q.FLAT_WALK)

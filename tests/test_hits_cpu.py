@@ -4,7 +4,6 @@ the kernel's formulas against the GPU file's own bounds, the ABI additions, the 
 come before any device work) and the vertex-only PLY."""
 import ctypes as C
 import hashlib
-import importlib
 import inspect
 import os
 import re
@@ -16,12 +15,10 @@ import torch
 import _hits_prim as H
 import _track_vis_prim as P
 
+from _util import pkg
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T8 = H.TAUS[8]
-
-
-def _L():
-    return importlib.import_module("robust-dynrf_amd._lib")
 
 
 @pytest.mark.parametrize("rt", ["ndc", "contract"])
@@ -141,7 +138,7 @@ def test_an_fp32_evaluation_lies_inside_the_gpu_bounds(rt, S):
 
 
 def test_abi_additions():
-    L = _L()
+    L = pkg()
     hdr = open(os.path.join(ROOT, "include", "rodynrf.h")).read()
     for sym in ("rdrf_hits_from_planes", "rdrf_render_hits_ws_bytes", "rdrf_render_hits_fwd"):
         assert re.search(r"\b" + sym + r"\s*\(", hdr), sym
@@ -200,7 +197,7 @@ def test_argument_errors_come_before_device_work():
     with pytest.raises(ValueError):
         rodynrf.render_hit_tracks(None, None, torch.zeros(3, 9), 10.0, 0, torch.zeros(2, 2), 4, 4, tau=(0.2, 0.4))
     # the C entry points refuse the same before touching the device
-    L = _L()
+    L = pkg()
     PS, PD, cs, cd = L.RdrfStaticParams(), L.RdrfDynamicParams(), L.RdrfFieldCfg(), L.RdrfFieldCfg()
     out = L.HitsC()
 

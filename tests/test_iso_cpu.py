@@ -15,6 +15,8 @@ import torch
 
 import _iso_prim as P
 
+from _util import pkg
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 UNIT = [[0.0, 0.0, 0.0], [1.0, 1.0, 1.0]]
 
@@ -121,7 +123,7 @@ def test_ply_round_trip_is_bit_exact(tmp_path, nv, with_normals, with_colors):
 
 
 def test_header_and_binding():
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     hdr = open(os.path.join(ROOT, "include", "rodynrf.h")).read()
     order = re.findall(r"^\s*(?:size_t|int)\s+(rdrf_\w+)\s*\(", hdr, flags=re.M)
     names = ["rdrf_iso_ws_bytes", "rdrf_iso_count", "rdrf_iso_emit"]
@@ -140,7 +142,7 @@ def test_header_and_binding():
 
 def test_size_refusals_return_before_any_launch():
     """null volume, workspace and counts: a call that got as far as a launch would fault; these return from the argument checks"""
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
 
     def count(G, T=1, t=0):
         rc = L.lib.rdrf_iso_count(None, G[0], G[1], G[2], T, t, 0.5, None, 0, None, None)

@@ -11,6 +11,8 @@ import pytest
 
 import _mlp_prim as P
 
+from _util import pkg
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -84,8 +86,7 @@ def test_split3_is_exact_and_truncating():
 
 
 def test_both_libraries_export_the_layer_selftest():
-    import importlib
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     assert "rdrf_selftest_layer" in L.SYMBOLS and hasattr(L.lib, "rdrf_selftest_layer")
     hdr = open(os.path.join(ROOT, "include", "rodynrf.h")).read()
     for name, value in L.SELFTEST_FORMS.items():

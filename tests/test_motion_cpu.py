@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+from _util import pkg
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MOTION = ("flow_f", "flow_b", "flow_s_f", "flow_s_b", "delta_xyz")
 
@@ -36,7 +38,7 @@ def test_motion_kernels_do_not_spill():
 
 def test_motion_surface_is_exported():
     import rodynrf
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     assert rodynrf.MotionMaps._fields == MOTION
     for name in ("MotionMaps", "flow_to_image", "delta_xyz_image", "render_rays", "render_frame", "render_view"):
         assert name in rodynrf.__all__ and hasattr(rodynrf, name), name
@@ -68,7 +70,7 @@ def _header_struct(name):
 
 
 def test_struct_sizes_match_the_header():
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     ctype = {"ptr": C.c_void_p, "int": C.c_int, "i64": C.c_int64}
     for name, cls in (("RdrfMotionMaps", L.MotionMapsC), ("RdrfMotionCams", L.MotionCamsC)):
         fields = _header_struct(name)

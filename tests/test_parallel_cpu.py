@@ -7,14 +7,15 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
+from _util import pkg
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _worker(rank, world, port, q):
     sys.path.insert(0, ROOT)
-    import importlib
-    P = importlib.import_module("robust-dynrf_amd.parallel")
-    F = importlib.import_module("robust-dynrf_amd.fields")
+    P = pkg("parallel")
+    F = pkg("fields")
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
                       WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     P.init_distributed("gloo")
@@ -79,8 +80,7 @@ def _ref_adam(p, g, m, v, t, lr_of, b1=0.9, b2=0.99, eps=1e-8):
 
 def _worker_exchange(rank, world, port, q):
     sys.path.insert(0, ROOT)
-    import importlib
-    P = importlib.import_module("robust-dynrf_amd.parallel")
+    P = pkg("parallel")
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
                       WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     P.init_distributed("gloo")
@@ -146,8 +146,7 @@ def _worker_world4(rank, world, port, q):
     """world 4: the FlatExchange round trip of _worker_exchange, then a batch that does not divide by the world size: every
     rank must raise BEFORE a collective is posted (ADVICE r3 #2: no hang), and a barrier afterwards must still complete"""
     sys.path.insert(0, ROOT)
-    import importlib
-    P = importlib.import_module("robust-dynrf_amd.parallel")
+    P = pkg("parallel")
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
                       WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     P.init_distributed("gloo")

@@ -2,7 +2,6 @@
 every layer of the boundary, the workspace size against the carve of the launch, and the float64 per-point reference of
 tests/_point_prim.py against the reference-generated goldens on their own sample points."""
 import ctypes as C
-import importlib
 import os
 import re
 
@@ -10,7 +9,7 @@ import pytest
 import torch
 
 from _point_prim import golden_points, point_reference, ray_norm_viewdirs
-from _util import assert_close, load_case
+from _util import assert_close, load_case, pkg
 from oracle import rodynrf_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,7 +20,7 @@ MASKED = {"ndc_relu": (164, 74, 416), "ndc_softplus": (112, 115, 208), "contract
 
 
 def test_symbols_on_every_layer():
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     hdr = open(os.path.join(ROOT, "include", "rodynrf.h")).read()
     names = ["rdrf_query_points_ws_bytes", "rdrf_query_points"]
     for name in names:
@@ -40,7 +39,7 @@ def test_symbols_on_every_layer():
 def test_workspace_size_is_the_carve(dynamic, per_point):
     """non-decreasing in M, whole 256-byte blocks, and exactly what the launch demands: with one byte less the entry point
     returns the workspace code.  That check precedes every dereference and every launch, so it runs without a device."""
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     size = lambda M: L.lib.rdrf_query_points_ws_bytes(dynamic, M, per_point)
     Ms = [0, 1, 31, 32, 33, 165, 4096, 65536, 1 << 20, L.QUERY_POINTS_MAX]
     sizes = [size(M) for M in Ms]

@@ -6,11 +6,12 @@ No case can reach a launch: the parameter structs hold no factor grids, so the l
 counts) refuses whatever the earlier ones let through; the one case with valid grids (the masked render's workspace check,
 which comes after them) has a short workspace.  Pointers other than the structs are never read: they point at a dummy."""
 import ctypes as C
-import importlib
 
 import pytest
 
-L = importlib.import_module("robust-dynrf_amd._lib")
+from _util import pkg
+
+L = pkg()
 
 NDC, CONTRACT, WORLD = 0, 1, 2
 N0, S0 = 5, 7

@@ -2,7 +2,6 @@
 symbols, the layout descriptions of the four kinds, and the numpy reference against float64 autograd through F.grid_sample on
 strided sub-arrays (an independent formulation of the same operation)."""
 import ctypes as C
-import importlib
 import os
 
 import numpy as np
@@ -12,13 +11,11 @@ import torch.nn.functional as F
 
 import _scatter_prim as P
 
+from _util import pkg
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("rdrf_selftest_sort_temp_bytes", "rdrf_selftest_sort", "rdrf_selftest_scatter_workspace_bytes", "rdrf_selftest_scatter",
        "rdrf_selftest_scatter_describe", "rdrf_selftest_scatter_last")
-
-
-def _lib():
-    return importlib.import_module("robust-dynrf_amd._lib")
 
 
 @pytest.mark.parametrize("name", ["librodynrf.so", "librodynrf_det.so"])
@@ -28,11 +25,11 @@ def test_both_libraries_export_the_scatter_selftests(name):
 
 
 def test_the_binding_lists_the_scatter_selftests():
-    assert all(s in _lib().SYMBOLS for s in NEW)
+    assert all(s in pkg().SYMBOLS for s in NEW)
 
 
 def test_describe_and_host_calls_work_without_a_device():
-    L = _lib()
+    L = pkg()
     for kind in P.KINDS:
         d = P.describe(L, kind, [9, 17, 33])
         assert d["wk"] == [12, 12, 20] and (1 << d["kb"]) - 1 >= 20 * 36 > (1 << (d["kb"] - 1)) - 1
@@ -47,7 +44,7 @@ def test_describe_and_host_calls_work_without_a_device():
 
 @pytest.mark.parametrize("kind", P.KINDS)
 def test_every_layout_is_a_bijection_of_features_onto_rows_and_record_slots(kind):
-    d = P.describe(_lib(), kind)
+    d = P.describe(pkg(), kind)
     fm = P.feature_map(d)
     assert len(fm) == d["nfeat"] == {"STATIC_DENSITY": 24, "DYN_DENSITY": 72, "STATIC_APP": 72, "DYN_APP": 216}[kind]
     rows = [r for r, *_ in fm]
@@ -118,7 +115,7 @@ def _autograd(case, mode):
 @pytest.mark.parametrize("kind", P.KINDS)
 def test_reference_agrees_with_float64_autograd_through_grid_sample(kind):
     """non-dyadic grid, random coordinates with out-of-range ones, dead samples, an unsorted list"""
-    d = P.describe(_lib(), kind, [17, 19, 11])
+    d = P.describe(pkg(), kind, [17, 19, 11])
     rng = np.random.default_rng(5)
     N, S = 3, 37
     coords = rng.uniform(-1.3, 1.3, (N * S, 3))
@@ -143,7 +140,7 @@ def test_reference_agrees_with_float64_autograd_through_grid_sample(kind):
 
 def _exact_case(kind, seed=1, **kw):
     grid = [9, 17, 9]
-    d = P.describe(_lib(), kind, grid)
+    d = P.describe(pkg(), kind, grid)
     rng = np.random.default_rng(seed)
     N, S = 2, 33
     return P.make_case(d, grid, N, S, P.dyadic_coords(rng, grid, N * S), rng, **kw)
@@ -186,7 +183,7 @@ def test_overwritten_and_accumulated_coordinate_gradients_differ_only_in_the_pre
 
 def test_keys_sort_and_counts_of_the_reference():
     grid = [9, 17, 9]
-    d = P.describe(_lib(), "DYN_DENSITY", grid)
+    d = P.describe(pkg(), "DYN_DENSITY", grid)
     coords = np.array([[-1, -1, -1], [1, 1, 1], [0, 0, 0], [1.0001, 0, 0], [1.6, 0, 0], [1e30, 0, 0], [0, 0, 0], [0, 0, 0]], dtype=np.float32)
     valid = np.array([1, 1, 1, 1, 1, 1, 0, 1])
     case = P.make_case(d, grid, 1, 8, coords, np.random.default_rng(0), valid=valid, sm_dead=[7])
@@ -234,7 +231,7 @@ def test_fp32_sums_in_permuted_orders_against_the_sequential_one(kind, grid, cap
     summation order meets; the kernels meet it (measured worst ratio 1.55) because run sums form in a tree and the line sums in
     fp64.  What is asserted here is what the number format guarantees for ANY order: n fp32 additions and at most 6 roundings
     inside a term give e <= (n + 6) 2^-24, n = the largest number of terms an element receives."""
-    d = P.describe(_lib(), kind, grid)
+    d = P.describe(pkg(), kind, grid)
     case = P.dense_case(d, grid)
     g64, mag = P.reference(case, "ray", "f64")
     tm32 = P.terms(case, np.float32)

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from _util import pkg
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -185,8 +187,7 @@ def test_make_batch_refuses_host_tables():
 
 # ---- boundary ------------------------------------------------------------------------------------------------------
 def test_header_declares_the_gather_and_the_version_stays_6():
-    import importlib
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     hdr = open(os.path.join(ROOT, "include", "rodynrf.h")).read()
     assert re.search(r"\bint\s+rdrf_gather_batch\s*\(\s*const\s+RdrfSceneTables\s*\*", hdr)
     assert "} RdrfSceneTables;" in hdr and "} RdrfBatch;" in hdr

@@ -14,8 +14,10 @@ import torch
 
 import _simplify_prim as S
 
+from _util import pkg
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-L = importlib.import_module("robust-dynrf_amd._lib")
+L = pkg()
 
 _dummy = (C.c_char * 256)()
 PTR = C.addressof(_dummy)

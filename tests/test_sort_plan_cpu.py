@@ -4,21 +4,18 @@ The sorted scatter sorts the three planes' keys as three segments over the kb ce
 passes of 8 bits, kb = 17 (final stage) two passes of 9, kb = 19 three passes; the segmented temp-size formula must cover what the
 sort carves out of its temporary storage at every shape the GPU tests use."""
 import ctypes as C
-import importlib
 
 import pytest
+
+from _util import pkg
 
 SEG_LENS = [1, 63, 64, 65, 511, 512, 513, 2047, 2048, 2049, 3 * 2048 + 1]
 BITS = [1, 8, 9, 10, 17, 18, 19]
 TILE = 2048
 
 
-def _lib():
-    return importlib.import_module("robust-dynrf_amd._lib")
-
-
 def describe(nseg, seg_len, bits):
-    L = _lib()
+    L = pkg()
     out = (C.c_ulonglong * 16)()
     n = L.lib.rdrf_selftest_sort_describe(nseg, seg_len, bits, out, 16)
     assert n == 9 and out[0] == 9, L.lib.rdrf_last_error()
@@ -27,7 +24,7 @@ def describe(nseg, seg_len, bits):
 
 
 def test_symbols_are_bound():
-    L = _lib()
+    L = pkg()
     for s in ("rdrf_selftest_sort_seg_temp_bytes", "rdrf_selftest_sort_seg", "rdrf_selftest_sort_describe"):
         assert s in L.SYMBOLS and hasattr(L.lib, s)
 
@@ -49,7 +46,7 @@ def test_the_sorted_bits_alone_save_the_final_stage_a_pass():
 
 @pytest.mark.parametrize("nseg", [1, 3])
 def test_temp_formula_covers_the_carver(nseg):
-    L = _lib()
+    L = pkg()
     for seg_len in SEG_LENS + [0, 4096 * 115, 4096 * 345]:
         for bits in BITS + [32]:
             d = describe(nseg, seg_len, bits)
@@ -64,7 +61,7 @@ def test_temp_formula_covers_the_carver(nseg):
 
 
 def test_describe_rejects_bad_arguments():
-    L = _lib()
+    L = pkg()
     out = (C.c_ulonglong * 16)()
     assert L.lib.rdrf_selftest_sort_describe(3, 100, 0, out, 16) == -1
     assert L.lib.rdrf_selftest_sort_describe(0, 100, 9, out, 16) == -1

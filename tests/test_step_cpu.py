@@ -1,15 +1,16 @@
 """Host logic of robust-dynrf_amd/step.py that needs no GPU: the pass-batching plan and the draw order of the pooled
 jitter generator (the batched and the per-pass paths must consume the same random numbers in the same order)."""
 import collections
-import importlib
 import types
 
 import pytest
 import torch
 
+from _util import pkg
+
 
 def test_batch_groups_respect_the_sample_cap(monkeypatch):
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     monkeypatch.setattr(S_, "BATCH_MAX_SAMPLES", 6_000_000)
     assert S_.batch_groups(range(4), 4096 * 115) == [[0, 1, 2, 3]]                 # benchmark shape: one call
     assert S_.batch_groups([1, 2, 3], 4096 * 270) == [[1, 2, 3]]                   # final stage
@@ -26,7 +27,7 @@ def test_step_rng_pool_and_coin_streams():
     """StepRng: the coins come from its own seeded generator (the same sequence whatever happens in between); the
     jitter vectors are consecutive 64-float-aligned slices of one pooled uniform draw, so taking (jitter, coin) for four
     passes up front (ray_passes) or one pass at a time (ray_pass) consumes the same values in the same order."""
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     dev = torch.device("cpu")
     a, b = S_.StepRng(seed=11), S_.StepRng(seed=11)
     coins_a = [a.coin() for _ in range(16)]
@@ -142,7 +143,7 @@ def test_pass_plans_draws_calls_and_counts(name, dead_work, late, monkeypatch):
     """One iteration's passes A-E (and P1-P4 with poses) through step.run_passes, batched and one call per pass: the draws
     (jitter, then a coin unless the pass does not composite, in pass order -- the same in both modes), which field's box
     samples each pass, the passes, colour flag and grad mode of every field call, and what PASSES counts."""
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     poses, d = name == "nvidia_no_poses", int(dead_work)
     n_pass = 9 if poses else 5
     dead_rgb = "value" if dead_work else False
@@ -180,7 +181,7 @@ def test_pass_plans_draws_calls_and_counts(name, dead_work, late, monkeypatch):
 
 
 def test_image_terms_subset_runs_passes_a_and_e(monkeypatch):
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     it = _StubIteration(S_, monkeypatch, "nvidia", True, False, 0)
     capture = {}
     it.tr.losses(it.batch(), terms="image_AE", capture=capture)
@@ -191,7 +192,7 @@ def test_image_terms_subset_runs_passes_a_and_e(monkeypatch):
 
 
 def test_ray_pass_is_one_pass_of_the_runner_and_draws_nothing_in_eval(monkeypatch):
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     it = _StubIteration(S_, monkeypatch, "nvidia", True, False, 0)
     rays, ts = torch.zeros(N_RAYS, 6), torch.zeros(N_RAYS)
     out = S_.ray_pass(it.tr.st, it.tr.dy, rays, ts, N_SAMPLES, "ndc", it, is_train=False)
@@ -208,9 +209,9 @@ def test_ray_pass_is_one_pass_of_the_runner_and_draws_nothing_in_eval(monkeypatc
 
 
 def test_field_and_map_tuples_keep_their_slot_order():
-    S_ = importlib.import_module("robust-dynrf_amd.step")
-    R_ = importlib.import_module("robust-dynrf_amd.renderer")
-    F_ = importlib.import_module("robust-dynrf_amd.fields")
+    S_ = pkg("step")
+    R_ = pkg("renderer")
+    F_ = pkg("fields")
     assert S_.FieldOut is F_.FieldOut and S_.RayMaps is R_.RayMaps
     f = F_.FieldOut(*range(10))
     assert tuple(f) == tuple(range(10)) and isinstance(f, tuple)
@@ -278,11 +279,10 @@ def test_resolution_schedule_matches_the_reference_formulas():
     """step.scene_config("nvidia", stage) for the five stages of configs/Nvidia.txt's schedule: the grids / sample counts are
     those of utils.py:58-65 N_to_reso / cal_n_samples (restated in the oracle) on the log-spaced voxel counts of
     train.py:937-947, and resolution_schedule() covers the 100 000 iterations once."""
-    import importlib
     import numpy as np
     import torch
     from oracle import rodynrf_oracle as O
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     aabb = torch.tensor(S_.scene_config("nvidia", "stage0")["aabb"])
     nvox = torch.round(torch.exp(torch.linspace(np.log(2097156), np.log(27000000), 5))).long().tolist()
     sched = S_.resolution_schedule("nvidia")
@@ -300,7 +300,7 @@ def test_graph_rng_hands_out_the_same_static_slices_every_iteration():
     """GraphRng (Trainer(graph=True)): the draws of an iteration are fixed slices of static memory -- the same storage at
     capture and at every replay -- refilled by begin(); coins are one-element fp32 tensors holding 0 or 1; frozen keeps
     the contents (tests replay fixed draws)."""
-    S_ = importlib.import_module("robust-dynrf_amd.step")
+    S_ = pkg("step")
     dev = torch.device("cpu")
     r = S_.GraphRng(dev, pool_floats=4096)
     seen = []

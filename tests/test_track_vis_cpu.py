@@ -2,7 +2,6 @@
 reference of tests/_track_vis_prim.py against the oracle's compositor, the slot's ray and depth against the oracle's ray
 generation and projection, the ABI additions, and the argument checks (which raise before any device work)."""
 import ctypes as C
-import importlib
 import inspect
 import os
 import re
@@ -12,16 +11,12 @@ import pytest
 import torch
 
 import _track_vis_prim as P
-from _util import load_case
+from _util import load_case, pkg
 from oracle import rodynrf_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASE = {"ndc": "motion_ndc", "contract": "motion_contract"}
 SHIFT = {"ndc": -2.0, "contract": -3.0}      # tests/test_gpu_track_vis.py SHIFT
-
-
-def _L():
-    return importlib.import_module("robust-dynrf_amd._lib")
 
 
 def _oracle_ray_inputs(rt, S, n=48):
@@ -124,7 +119,7 @@ def test_the_point_lies_on_its_slot_ray_at_its_depth(rt):
 
 
 def test_abi_additions():
-    L = _L()
+    L = pkg()
     hdr = open(os.path.join(ROOT, "include", "rodynrf.h")).read()
     for sym in ("rdrf_track_visibility_ws_bytes", "rdrf_track_visibility_fwd"):
         assert re.search(r"\b" + sym + r"\s*\(", hdr), sym
@@ -181,7 +176,7 @@ def test_argument_errors_come_before_device_work():
     with pytest.raises(ValueError):
         call(T=1)
     # the C entry point refuses what the track entry points refuse (no device is touched: the checks come first)
-    L = _L()
+    L = pkg()
     PS, PD, cs, cd = L.RdrfStaticParams(), L.RdrfDynamicParams(), L.RdrfFieldCfg(), L.RdrfFieldCfg()
     cam = L.TrackCamsC(8, 8, 3, 1, 1)
 

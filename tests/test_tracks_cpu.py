@@ -14,16 +14,14 @@ import numpy as np
 import pytest
 import torch
 
+from _util import pkg
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMS = ("rdrf_track_points_fwd", "rdrf_track_ws_bytes", "rdrf_render_track_seeds_fwd")
 
 
-def _L():
-    return importlib.import_module("robust-dynrf_amd._lib")
-
-
 def test_header_binding_and_library_agree():
-    L = _L()
+    L = pkg()
     hdr = open(os.path.join(ROOT, "include", "rodynrf.h")).read()
     for sym in SYMS:
         assert re.search(r"\b" + sym + r"\(", hdr), sym
@@ -63,7 +61,7 @@ def test_point_single_has_the_reference_signature():
 
 
 def test_workspace_bytes_is_monotone():
-    L = _L()
+    L = pkg()
     f = L.lib.rdrf_track_ws_bytes
     sizes = [[int(f(M, K)) for K in (1, 2, 9, 25, 100, 1000)] for M in (0, 1, 31, 32, 33, 70, 4096, 65569, 1 << 22)]
     assert all(v > 0 for row in sizes for v in row)
@@ -88,7 +86,7 @@ def _call(L, ray_type=0, n_fwd=1, n_bwd=1, K=None, with_out=True, pix=False, M=0
 
 
 def test_c_entry_validates_its_arguments():
-    L = _L()
+    L = pkg()
     assert _call(L) == 0                                   # M == 0: a no-op once the arguments are sound
     assert _call(L, K=3) == 0
     for kw, word in ((dict(n_fwd=-1), "step counts"), (dict(n_bwd=-2), "step counts"), (dict(K=4), "cameras"),

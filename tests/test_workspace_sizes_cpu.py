@@ -11,9 +11,10 @@ entry point), so they cannot be too small; here they are held to be no larger th
 terms, positive, whole 256-byte blocks and non-decreasing in each argument.  rdrf_features_workspace_bytes keeps its form
 (rdrf_workspace_bytes(Np, 32) + a closed term that is no multiple of 256), so it is held to that form and to the parent's value
 as an upper bound instead."""
-import importlib
 
 import pytest
+
+from _util import pkg
 
 NS = [(1, 1), (1, 32), (1, 33), (33, 45), (4, 33), (512, 115), (4096, 115)]
 MS = [1, 32, 33, 77, 4096]
@@ -83,7 +84,7 @@ DERIVED = ["rdrf_workspace_bytes", "rdrf_features_bwd_workspace_bytes", "rdrf_se
 
 def _call(key, shape):
     import ctypes as C
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     name, _, fixed = key.partition("[")
     args = [int(v) for v in fixed.rstrip("]").split(",") if v] + list(shape if isinstance(shape, tuple) else (shape,))
     if name == "rdrf_saved_bytes_ex":      # (kind, N, S, flags): the flags come last
@@ -94,7 +95,7 @@ def _call(key, shape):
 
 
 def test_the_table_covers_every_exported_size_function_at_the_agreed_shapes():
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     exported = {s for s in L.SYMBOLS if s.endswith("_workspace_bytes") or "_saved_bytes" in s}
     assert {k.partition("[")[0] for k in PARENT} == exported
     assert sorted(KEPT + DERIVED + ["rdrf_features_workspace_bytes"]) == sorted(PARENT)

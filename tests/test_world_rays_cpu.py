@@ -7,15 +7,14 @@ import re
 import numpy as np
 import torch
 
-from _util import GOLDEN
+from _util import GOLDEN, pkg
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("rdrf_sample_world", "rdrf_sample_world_bwd", "rdrf_render_world_fwd")
 
 
 def test_header_declares_and_library_exports_the_world_symbols():
-    import importlib
-    L = importlib.import_module("robust-dynrf_amd._lib")
+    L = pkg()
     hdr = open(os.path.join(ROOT, "include", "rodynrf.h")).read()
     declared = set(re.findall(r"\b(rdrf_[a-z0-9_]+)\s*\(", hdr))
     for sym in NEW_SYMBOLS:
