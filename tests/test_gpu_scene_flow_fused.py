@@ -11,7 +11,9 @@ col(e) being the slot order of the first layer's input rows as rdrf_selftest_dw_
     accumulation can change a bit: torch.equal with the int64 sums, on integer pre-filled gradients, at sample counts around
     the tile edge, with fewer tiles than waves, with a nearly empty last workgroup and with grid * waves + 3 tiles (some
     waves walk a second tile; grid and waves come from rdrf_selftest_sf_geometry, the helper the launch uses); with the point
-    gradient absent and with only one of the two upstream gradients.
+    gradient absent and with only one of the two upstream gradients.  g_pts of the same runs, onto its zero pre-fill, is
+    fl32(e inv32) bit for bit, e the exact gradient of the normalised point from the float64 reference of tests/_warp_prim.py
+    (the harness's box has no power-of-two inv: one rounding, contracted or not).  Dense inputs: tests/test_gpu_warp_primitives.py.
 (b) accuracy: dense normal rows and weights at 257 tiles, e = max |dW - dW64| / sum |dz| |in| within 2 x e_seq32, the same
     metric of an fp32 evaluation that sums the samples sequentially (the form tests/test_gpu_dw_primitives.py (c) holds k_dw3 to).
 (c) poison: 3e38 in every activation slot of the samples whose upstream gradient is zero and of the slots past N * S changes
@@ -32,6 +34,8 @@ ROWS, R_X, R_H0, R_H2, R_H4 = 256, 0, 64, 128, 192
 SHAPES = [(64, 36), (64, 64), (64, 64), (6, 64)]   # scene_flow_mlp.{0,2,4,6}.weight
 PREFILL = 3
 DENSE_TILES = 257
+GUARD = 64   # floats of NaN on either side of g_pts
+BOX = [[-1.5, -1.67, -1.0], [1.5, 1.67, 1.0]]   # the harness's own box: no inv is a power of two
 
 
 def _x_cols():
@@ -173,17 +177,29 @@ class Harness:
         from _gpu_util import COMMON
         self.L = pkg()
         self.F = pkg("fields")
-        aabb = torch.tensor([[-1.5, -1.67, -1.0], [1.5, 1.67, 1.0]])
+        aabb = torch.tensor(BOX)
         kw = dict(COMMON, near_far=[0.0, 1.0], density_shift=-10.0, fea2denseAct="relu")
         torch.manual_seed(3)
         self.dy = rodynrf.TensorVMSplit_TimeEmbedding(aabb, [24, 26, 16], 12, "cuda:0", shadingMode="MLP_Fea_late_view", fea_pe=0, **kw)
         self.params = [p.detach() for p in self.dy._param_list()]
         self.cfg = self.F._cfg_struct(self.dy, "ndc")
 
-    def run(self, n, rows, W, gf, gb, pts=True, ws_byte=None, prefill=True):
-        """-> ([dW0..3], [db0..3], g_pts or None) as numpy; gradients pre-filled with small integers (added into)"""
+    def cfg_for(self, box):
+        """the field's configuration on another box [[lo 3], [hi 3]] (None: the harness's own, BOX)"""
+        if box is None:
+            return self.cfg
+        cfg = type(self.cfg).from_buffer_copy(self.cfg)
+        for i, v in enumerate(np.asarray(box, dtype=np.float32).reshape(6)):
+            cfg.aabb[i] = float(v)
+        return cfg
+
+    def run(self, n, rows, W, gf, gb, pts=True, ws_byte=None, prefill=True, box=None, pts_fill=None):
+        """-> ([dW0..3], [db0..3], g_pts or None) as numpy; gradients pre-filled with small integers (added into).  g_pts (pre-filled
+        with pts_fill [n][3], else zeros) sits between NaN-poisoned guard bands of GUARD floats; self.guards_intact tells whether
+        the last call left them alone, self.pts_buffer is the buffer after the call (untouched when the kernel got no g_pts)"""
         L, dev = self.L, "cuda:0"
         N, S = n, 1
+        cfg = self.cfg_for(box)
         params = list(self.params)
         biases = [torch.zeros(s[0], device=dev) for s in SHAPES]
         for i in range(4):
@@ -203,15 +219,21 @@ class Harness:
         assert saved.numel() == ((n + 31) // 32) * ROWS * 32
         xyz = torch.zeros(N, S, 3, device=dev)
         ts = torch.zeros(N, device=dev)
-        g_pts = torch.zeros(N, S, 3, device=dev) if pts else None
+        band = torch.full((GUARD + n * 3 + GUARD,), float("nan"), device=dev)
+        pbuf = band[GUARD:GUARD + n * 3].view(N, S, 3).zero_()
+        if pts_fill is not None:
+            pbuf.copy_(torch.from_numpy(np.ascontiguousarray(pts_fill, dtype=np.float32)).view(N, S, 3))
+        g_pts = pbuf if pts else None
         cgf = None if gf is None else torch.from_numpy(gf).to(dev).contiguous()
         cgb = None if gb is None else torch.from_numpy(gb).to(dev).contiguous()
         nbytes = L.lib.rdrf_workspace_bytes(N, S)
         ws = torch.full((nbytes,), 0 if ws_byte is None else ws_byte, dtype=torch.uint8, device=dev)
-        L.check(L.lib.rdrf_scene_flow_bwd(C.byref(P), C.byref(self.cfg), L.ptr(xyz), L.ptr(ts), N, S, L.ptr(cgf), L.ptr(cgb), C.byref(G),
+        L.check(L.lib.rdrf_scene_flow_bwd(C.byref(P), C.byref(cfg), L.ptr(xyz), L.ptr(ts), N, S, L.ptr(cgf), L.ptr(cgb), C.byref(G),
                                           L.ptr(g_pts), L.ptr(saved), C.c_size_t(saved.numel() * 4), L.ptr(ws), C.c_size_t(ws.numel()),
                                           L.stream_of(saved)), "rdrf_scene_flow_bwd")
         torch.cuda.synchronize()
+        self.guards_intact = bool(torch.isnan(torch.cat([band[:GUARD], band[-GUARD:]])).all())
+        self.pts_buffer = pbuf.cpu().numpy().reshape(n, 3)
         dW = [g.cpu().numpy() for g in gw]
         db = [g.cpu().numpy() for g in gbias]
         return dW, db, (None if g_pts is None else g_pts.cpu().numpy()), pre_w, pre_b
@@ -251,7 +273,17 @@ def check_exact(run, n, seed, gf_on=True, gb_on=True, pts=True):
             f"n = {n}: db of layer {layer}: {int((got_b != want_b.float()).sum())} entries differ"
     assert (g_pts is None) == (not pts)
     if g_pts is not None:
-        assert np.isfinite(g_pts).all()
+        # against the float64 reference of tests/_warp_prim.py: on integers the gradient e of the normalised point is exact (the
+        # guard asserts every partial sum below 2^24) and, onto the zero pre-fill, g_pts = fl32(e inv32): one rounding, the same
+        # whether the product is contracted into the addition or not
+        import _warp_prim as Q
+        lay = Q.sf_layout(pkg())
+        cq = dict(n=n, rows=rows, W=W, gf=gf, gb=gb, pre=np.zeros((n, 3), dtype=np.float32), box=np.asarray(BOX, dtype=np.float32))
+        Q.sf_exact_guard(cq, lay)
+        e = Q.sf_reference(cq, lay)["e"][0]
+        want = e.astype(np.float32) * Q.box_inv(cq["box"])[None, :]
+        assert np.array_equal(e, np.rint(e)) and want.dtype == np.float32
+        assert np.array_equal(g_pts.reshape(n, 3).view(np.uint32), (want + np.float32(0.0)).view(np.uint32)), f"n = {n}: g_pts differs"
     return dW, db, g_pts
 
 

@@ -13,7 +13,9 @@ col(e) being the slot order of layer3's input rows as rdrf_selftest_dw_describe 
     partial sum stays below 2^24 (computed from the case), so no order of accumulation can change a bit: torch.equal with the
     int64 sums, gradients pre-filled with small integers, at N S = 1, 31, 32, 33, 129, 160, 257 and 32 (grid waves + 3) (grid and
     waves from rdrf_selftest_warp_geometry, the helper the launch uses), and with rays of 45 samples (a tile spans rays; d(tout)
-    goes through the tiles' partial records).
+    goes through the tiles' partial records).  The data gradients of the same runs -- g_xyz onto its integer pre-fill and the dd
+    rows -- are compared bit for bit with the float64 reference of tests/_warp_prim.py (exact on these inputs); g_xyz, dtout and dtp
+    sit between NaN guard bands that must stay intact.  Other boxes and dense inputs: tests/test_gpu_warp_primitives.py.
 (2) accuracy: dense normal rows at 257 tiles, e = max |dW - dW64| / sum |dz| |in| within 2 x e_seq32, the same metric of an fp32
     evaluation that sums the samples one after the other (the bound tests/test_gpu_dw_primitives.py holds k_dw3 to).
 (3) row contract: 3e38 in every activation slot of the samples whose dd is zero and of the slots past N S changes no bit; nor do
@@ -41,6 +43,7 @@ LAYERS = ("l3", "l4", "l5")
 PREFILL = 3
 DENSE_TILES = 257
 DT_FILL = 7.0   # dtout / dtp slots the kernel does not write keep this
+GUARD = 64      # floats of NaN on either side of g_xyz, dtout and dtp
 
 
 def _in_cols():
@@ -179,10 +182,22 @@ class Harness:
         self.params = [p.detach() for p in self.dy._param_list()]
         self.cfg = self.F._cfg_struct(self.dy, "ndc")
 
-    def run(self, c, gx=True, gp=True, ws_byte=0, prefill=True, det=False):
-        """-> dict of numpy arrays: dW / db per layer, g_xyz, dtout, dtp, and the pre-fills"""
+    def cfg_for(self, box):
+        """the field's configuration on another box [[lo 3], [hi 3]] (None: the harness's own)"""
+        if box is None:
+            return self.cfg
+        cfg = type(self.cfg).from_buffer_copy(self.cfg)
+        for i, v in enumerate(np.asarray(box, dtype=np.float32).reshape(6)):
+            cfg.aabb[i] = float(v)
+        return cfg
+
+    def run(self, c, gx=True, gp=True, ws_byte=0, prefill=True, det=False, box=None):
+        """-> dict of numpy arrays: dW / db per layer, g_xyz, dtout, dtp, and the pre-fills.  g_xyz (pre-filled with c["pre"] if the
+        case has one), dtout and dtp sit between NaN-poisoned guard bands of GUARD floats: "guards" tells whether each pair is intact;
+        without gx the kernel gets no g_xyz and "g_xyz_unused" is the buffer it must not have touched"""
         L, dev = self.L, "cuda:0"
         N, S = c["N"], c["S"]
+        cfg = self.cfg_for(box)
         n, T = N * S, c["act"].shape[0]
         params = list(self.params)
         rng = np.random.default_rng(5)
@@ -202,16 +217,19 @@ class Harness:
         act = torch.from_numpy(c["act"]).to(dev).contiguous()
         grw = torch.from_numpy(c["grw"]).to(dev).contiguous()
         dxw, dxn = torch.from_numpy(c["dxw"]).to(dev).contiguous(), torch.from_numpy(c["dxn"]).to(dev).contiguous()
-        cgp = torch.from_numpy(c["gp"]).to(dev).contiguous() if gp else None
-        g_xyz = torch.from_numpy(np.arange(n * 3, dtype=np.float32).reshape(n, 3) % 5).to(dev) if gx else None
-        dtout = torch.full((N, 32), DT_FILL, device=dev)
-        dtp = torch.full((T, 2, 32), DT_FILL, device=dev)
+        cgp = torch.from_numpy(c["gp"]).to(dev).contiguous() if gp and c["gp"] is not None else None
+        pre_g = c["pre"] if c.get("pre") is not None else np.arange(n * 3, dtype=np.float32).reshape(n, 3) % 5
+        bands = {k: torch.full((GUARD + m + GUARD,), float("nan"), device=dev) for k, m in (("g_xyz", n * 3), ("dtout", N * 32), ("dtp", T * 64))}
+        gbuf = bands["g_xyz"][GUARD:GUARD + n * 3].view(n, 3).copy_(torch.from_numpy(np.ascontiguousarray(pre_g, dtype=np.float32)))
+        g_xyz = gbuf if gx else None
+        dtout = bands["dtout"][GUARD:GUARD + N * 32].view(N, 32).fill_(DT_FILL)
+        dtp = bands["dtp"][GUARD:GUARD + T * 64].view(T, 2, 32).fill_(DT_FILL)
         ws = torch.full((L.lib.rdrf_selftest_warp_bwd_workspace_bytes(N, S),), ws_byte, dtype=torch.uint8, device=dev)
         shadow = None
         if det:
             shadow = torch.zeros(flat.numel(), dtype=torch.int64, device=dev)
             L.check(L.lib.rdrf_det_bind(1, L.ptr(flat), C.c_size_t(flat.numel()), L.ptr(shadow), L.stream_of(flat)), "rdrf_det_bind")
-        L.check(L.lib.rdrf_selftest_warp_bwd(C.byref(P), C.byref(self.cfg), N, S, L.ptr(act), C.c_size_t(act.numel()), L.ptr(grw),
+        L.check(L.lib.rdrf_selftest_warp_bwd(C.byref(P), C.byref(cfg), N, S, L.ptr(act), C.c_size_t(act.numel()), L.ptr(grw),
                                              C.c_size_t(grw.numel()), L.ptr(dxw), L.ptr(dxn), L.ptr(cgp), C.byref(G), L.ptr(g_xyz),
                                              L.ptr(dtout), L.ptr(dtp), L.ptr(ws), C.c_size_t(ws.numel()), L.stream_of(act)),
                 "rdrf_selftest_warp_bwd")
@@ -230,6 +248,8 @@ class Harness:
             res["pre_b"][k] = pre[o:o + sizes[3 + i]]
             o += sizes[3 + i]
         res["g_xyz"] = None if g_xyz is None else g_xyz.cpu().numpy()
+        res["g_xyz_unused"], res["pre_g"] = (gbuf.cpu().numpy() if g_xyz is None else None), np.asarray(pre_g, dtype=np.float32)
+        res["guards"] = {k: bool(torch.isnan(torch.cat([b[:GUARD], b[-GUARD:]])).all()) for k, b in bands.items()}
         res["dtout"], res["dtp"] = dtout.cpu().numpy(), dtp.cpu().numpy()
         res["sm"] = grw[:, 128:131].cpu().numpy()   # the small-layer dz rows 0..2 the kernel writes
         return res
@@ -270,8 +290,19 @@ def check_exact(run, N, S, seed, **kw):
         assert torch.equal(got_b.to(torch.int64), want_b) and torch.equal(got_b, want_b.float()), \
             f"N {N} S {S}: db of {k}: {int((got_b != want_b.float()).sum())} entries differ"
     assert np.array_equal(ray_dtout(c, out["dtout"], out["dtp"]), ref[2]), f"N {N} S {S}: d(tout) differs"
+    # the data gradients against the float64 reference of tests/_warp_prim.py: on integers and the unit box every sum is exact
+    import _warp_prim as Q
+    lay = Q.warp_layout(pkg())
+    cq = dict(c, box=Q.BOX_UNIT, pre=out["pre_g"])
+    Q.warp_exact_guard(cq, lay)   # asserts that every partial sum stays below 2^24
+    want = Q.warp_reference(cq, lay)
+    T = c["act"].shape[0]
+    assert np.array_equal(out["sm"].transpose(0, 2, 1).reshape(T * 32, 3).astype(np.float64), want["dd"][0]), f"N {N} S {S}: the dd rows differ"
     if out["g_xyz"] is not None:
-        assert np.isfinite(out["g_xyz"]).all()
+        assert np.array_equal(out["g_xyz"].astype(np.float64), want["g_xyz"][0]), f"N {N} S {S}: g_xyz differs"
+    else:
+        assert np.array_equal(out["g_xyz_unused"], out["pre_g"])
+    assert all(out["guards"].values()), out["guards"]
     return out
 
 
