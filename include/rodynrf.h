@@ -1102,6 +1102,33 @@ int rdrf_simplify_emit(const float* verts, const float* normals, const unsigned 
                        int64_t F, const void* ws, float* verts_out, float* normals_out, unsigned char* colors_out, int* faces_out,
                        int64_t nv, int64_t nf, rdrf_stream_t stream);
 
+/* ---- whole-scene volumes: both fields at M points x T times, composed as the renderer composes a sample ---------------------
+ * xyz[M][3] are un-normalised points (each field normalises them with its own box), times[T] a DEVICE array, every output
+ * [M][T] and nullable: a null output is not written and, where that saves work, not computed (sigma_s alone: the dynamic
+ * field is not evaluated; no alpha and no owner: the static field only for sigma_s; a head nobody reads is skipped).  Per
+ * point and time, in fp32, in this order:
+ *   sigma_d, blending   the bits rdrf_query_points gives the point at that time (fill_x0, load_tout, warp_mlp, warp_point,
+ *                       head_raw<false>, head_raw<true>, density_act; the sigmoid 1 / (1 + expf(-f)) of k_point_dyn): the warp
+ *                       is evaluated once for both heads
+ *   sigma_s             the bits rdrf_query_points gives the static field (static_density_feature, density_act)
+ *   masks               mask_s / mask_d (each nullable): a field whose mask sample at the point and time is <= 0 gets sigma 0
+ *                       there, as in rdrf_compute_alpha; blending is not masked
+ *   a_d = 1 - expf(-sigma_d * length),  a_s = 1 - expf(-sigma_s * length)       (rdrf_compute_alpha's expression)
+ *   w_d = a_d * b,  w_s = a_s * (1 - b)
+ *   alpha = 1 - (1 - w_d) * (1 - w_s)    one minus the compositor's per-sample factor WITHOUT its + 1e-10; no contraction
+ *   owner = w_d / (w_d + w_s), 0 where the sum is 0: the owner of rdrf_render_hits_fwd
+ * A NaN in sigma_s, sigma_d or blending of an entry gives NaN in alpha and owner of that entry and nowhere else.  No aabb test:
+ * a point outside a field's box gets what rdrf_query_points gives it.  An entry depends on its own point and time only, not on
+ * M, T, the other points, the outputs asked for, the run or the build: no atomics, the deterministic library runs the same
+ * code.  No allocation, no synchronisation, no read-back: the call can be captured into a graph.  M == 0 is a no-op.  Refused
+ * before any device work: M < 0, T < 1, every output null, M * T >= 2^31, a workspace below rdrf_scene_alpha_ws_bytes(M, T)
+ * (which does not carry the *_workspace_bytes suffix for the reason given at rdrf_render_masked_ws_bytes). */
+size_t rdrf_scene_alpha_ws_bytes(int M, int T);
+int rdrf_scene_alpha(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                     const RdrfFieldCfg* cfg_d, const float* xyz, int M, const float* times, int T, float length,
+                     const RdrfAlphaMask* mask_s, const RdrfAlphaMask* mask_d, float* alpha, float* owner, float* sigma_s,
+                     float* sigma_d, float* blending, void* ws, size_t ws_bytes, rdrf_stream_t stream);
+
 /* timing hook: average device time (ms) of the dominant kernel launches recorded with HIP events
  * since the last reset; used by bench.py for the roofline figure. */
 void rdrf_prof_reset(void);

@@ -272,6 +272,9 @@ SIGNATURES = {
     "rdrf_simplify_ws_bytes": (usz, [i64, i64, vp]),
     "rdrf_simplify_count": (i32, [vp, i64, vp, i64, vp, vp, vp, i32, vp, usz, vp, vp, vp]),
     "rdrf_simplify_emit": (i32, [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp]),
+    "rdrf_scene_alpha_ws_bytes": (usz, [i32, i32]),
+    "rdrf_scene_alpha": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, f32, C.POINTER(RdrfAlphaMask), C.POINTER(RdrfAlphaMask), vp, vp,
+                              vp, vp, vp, vp, usz, vp]),
     "rdrf_prof_reset": (None, []),
     "rdrf_prof_enable": (i32, [i32]),
     "rdrf_prof_get": (i32, [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),

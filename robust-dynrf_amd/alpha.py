@@ -162,9 +162,9 @@ def lattice_times(tSize):
     return torch.tensor([k / (tSize - 1.0) * 2.0 - 1.0 for k in range(tSize)], dtype=torch.float32)
 
 
-@torch.no_grad()
-def get_dense_alpha(field, gridSize=None, times=None):
-    """models/tensorBase.py:565-589 -> (alpha [G0,G1,G2,T], dense_xyz [G0,G1,G2,3]); one native call per slab of G0"""
+def _dense_lattice(field, gridSize, times):
+    """the lattice of getDenseAlpha over field.aabb -> (gs, times [T] on the device, dense_xyz [G0,G1,G2,3], the slabs
+    (i0, i1) of G0 that hold at most SLAB_POINTS points each)"""
     gs = [int(v) for v in (field.gridSize.tolist() if gridSize is None else gridSize)]
     dev = field.aabb.device
     times = lattice_times(int(field.tSize.item())) if times is None else torch.as_tensor(times, dtype=torch.float32).reshape(-1)
@@ -172,14 +172,100 @@ def get_dense_alpha(field, gridSize=None, times=None):
     samples = torch.stack(torch.meshgrid(torch.linspace(0, 1, gs[0], device=dev), torch.linspace(0, 1, gs[1], device=dev),
                                          torch.linspace(0, 1, gs[2], device=dev), indexing="ij"), -1)
     dense_xyz = field.aabb[0] * (1 - samples) + field.aabb[1] * samples
-    T = times.numel()
-    alpha = torch.empty(gs[0], gs[1], gs[2], T, device=dev)
     rows = max(1, SLAB_POINTS // (gs[1] * gs[2]))
-    for i0 in range(0, gs[0], rows):
-        i1 = min(gs[0], i0 + rows)
+    return gs, times, dense_xyz, [(i0, min(gs[0], i0 + rows)) for i0 in range(0, gs[0], rows)]
+
+
+@torch.no_grad()
+def get_dense_alpha(field, gridSize=None, times=None):
+    """models/tensorBase.py:565-589 -> (alpha [G0,G1,G2,T], dense_xyz [G0,G1,G2,3]); one native call per slab of G0"""
+    gs, times, dense_xyz, slabs = _dense_lattice(field, gridSize, times)
+    T = times.numel()
+    alpha = torch.empty(gs[0], gs[1], gs[2], T, device=times.device)
+    for i0, i1 in slabs:
         alpha_volume(field, dense_xyz[i0:i1].reshape(-1, 3), times, field._step_host, field.alphaMask,
                      out=alpha[i0:i1].view(-1, T))
     return alpha, dense_xyz
+
+
+# ---- whole-scene volumes: both fields composed as the renderer composes a sample (csrc/rdrf_scene_alpha.hip) ----------------
+SCENE_OUTPUTS = ("alpha", "owner", "sigma_s", "sigma_d", "blending")
+SCENE_MAX_ENTRIES = (1 << 31) - 1   # include/rodynrf.h rdrf_scene_alpha: M * T of one call
+
+
+def check_scene_fields(tensorf_static, tensorf, who):
+    """the static field first, the dynamic field second, both on one device"""
+    if getattr(tensorf_static, "DYNAMIC", None) is not False:
+        raise L.RdrfError(f"{who}: tensorf_static must be the static field (TensorVMSplit)")
+    if getattr(tensorf, "DYNAMIC", None) is not True:
+        raise L.RdrfError(f"{who}: tensorf must be the dynamic field (TensorVMSplit_TimeEmbedding)")
+    ds, dd = tensorf_static.aabb.device, tensorf.aabb.device
+    if ds != dd:
+        raise L.RdrfError(f"{who}: tensorf_static is on {ds} and tensorf on {dd}: both fields must be on one device")
+
+
+@torch.no_grad()
+def scene_alpha_volume(tensorf_static, tensorf, xyz, times, length=None, masks="fields", want=("alpha",), _out=None):
+    """rdrf_scene_alpha: xyz [M,3] un-normalised, times [T] -> a dict of [M,T] tensors, one per name in `want` out of
+    SCENE_OUTPUTS.  With a_f = 1 - exp(-sigma_f length) and the dynamic field's blending b:
+    alpha = 1 - (1 - a_d b)(1 - a_s (1 - b)), what the compositor takes from the light at a sample of that length;
+    owner = a_d b / (a_d b + a_s (1 - b)), the dynamic field's share (0 where both are empty).
+    length: the sample length, by default the dynamic field's step (what getDenseAlpha uses).  masks: "fields" (each field's
+    alphaMask), None, or (mask_s, mask_d), each an AlphaGridMask or None: a field is empty where its mask is."""
+    who = "scene_alpha_volume"
+    want = (want,) if isinstance(want, str) else tuple(want)
+    bad = [w for w in want if w not in SCENE_OUTPUTS]
+    if bad or not want:
+        raise L.RdrfError(f"{who}: want = {want!r} must be a non-empty subset of {SCENE_OUTPUTS}")
+    check_scene_fields(tensorf_static, tensorf, who)
+    if isinstance(masks, str) and masks == "fields":
+        masks = (tensorf_static.alphaMask, tensorf.alphaMask)
+    elif masks is None:
+        masks = (None, None)
+    elif not isinstance(masks, (tuple, list)) or len(masks) != 2 or not all(m is None or isinstance(m, AlphaGridMask) for m in masks):
+        raise L.RdrfError(f"{who}: masks must be \"fields\", None or (mask_s, mask_d) of AlphaGridMask / None, not {masks!r}")
+    if not torch.is_tensor(xyz) or xyz.dim() < 1 or xyz.shape[-1] != 3:
+        raise L.RdrfError(f"{who}: xyz must be a tensor [..., 3]")
+    L.require_device(xyz)
+    xyz = L.f32c(xyz.detach()).reshape(-1, 3)
+    dev = xyz.device
+    if dev != tensorf.aabb.device:
+        raise L.RdrfError(f"{who}: xyz is on {dev} and the fields on {tensorf.aabb.device}")
+    times = L.f32c(torch.as_tensor(times, dtype=torch.float32).detach().reshape(-1).to(dev))
+    M, T = xyz.shape[0], times.numel()
+    if T < 1:
+        raise L.RdrfError(f"{who}: times is empty")
+    length = float(tensorf._step_host if length is None else length)
+    out = {w: torch.empty(M, T, device=dev) for w in want} if _out is None else _out
+    if M == 0:
+        return out
+    PS, cs = field_structs(tensorf_static, tensorf_static._param_list(), "ndc")
+    PD, cd = field_structs(tensorf, tensorf._param_list(), "ndc")
+    ms, md = (None if m is None else m._struct() for m in masks)
+    chunk = min(M, SCENE_MAX_ENTRIES // T)
+    ws = L.workspace(dev, L.lib.rdrf_scene_alpha_ws_bytes(chunk, T))
+    for a in range(0, M, chunk):
+        b = min(M, a + chunk)
+        o = [L.ptr(out[w][a:b]) if w in out else None for w in SCENE_OUTPUTS]
+        L.check(L.lib.rdrf_scene_alpha(C.byref(PS), C.byref(cs), C.byref(PD), C.byref(cd), L.ptr(xyz[a:b]), b - a, L.ptr(times), T,
+                                       length, None if ms is None else C.byref(ms), None if md is None else C.byref(md), *o,
+                                       L.ptr(ws), ws.numel(), L.stream_of(xyz)), "rdrf_scene_alpha")
+    return out
+
+
+@torch.no_grad()
+def scene_dense_alpha(tensorf_static, tensorf, gridSize=None, times=None, want_owner=False):
+    """getDenseAlpha of the whole scene -> (alpha [G0,G1,G2,T][, owner [G0,G1,G2,T]], dense_xyz [G0,G1,G2,3]): the lattice
+    of get_dense_alpha over the DYNAMIC field's aabb (its gridSize and lattice times by default), scene_alpha_volume with
+    each field's alphaMask and the dynamic field's step per slab."""
+    check_scene_fields(tensorf_static, tensorf, "scene_dense_alpha")
+    gs, times, dense_xyz, slabs = _dense_lattice(tensorf, gridSize, times)
+    T = times.numel()
+    vols = {w: torch.empty(gs[0], gs[1], gs[2], T, device=times.device) for w in (("alpha", "owner") if want_owner else ("alpha",))}
+    for i0, i1 in slabs:
+        scene_alpha_volume(tensorf_static, tensorf, dense_xyz[i0:i1].reshape(-1, 3), times, want=tuple(vols),
+                           _out={w: v[i0:i1].view(-1, T) for w, v in vols.items()})
+    return tuple(vols.values()) + (dense_xyz,)
 
 
 def build_mask(alpha, thres):

@@ -331,6 +331,78 @@ def colored_mesh(field, t=None, level=0.005, gridSize=None, view=(0, 0, 1), spac
     return _mesh_of_slice(field, alpha, 0, level, space, H, W, focal, kw, color=lambda verts: vertex_colors(field, verts, t, view))
 
 
+# ---- whole-scene meshes: the isosurface of the composed alpha volume (alpha.scene_dense_alpha, csrc/rdrf_scene_alpha.hip) ---
+def _scene_t(t, who):
+    if t is None:
+        raise L.RdrfError(f"{who}: the scene's alpha depends on the time: pass t")
+    return float(t)
+
+
+@torch.no_grad()
+def scene_mesh(tensorf_static, tensorf, t=None, level=0.005, gridSize=None, space="field", H=None, W=None, focal=None, **kw):
+    """field_mesh of the whole scene at time t: scene_dense_alpha(gridSize, times=[t]) -> extract_isosurface.  The lattice and
+    the box are the dynamic field's; kw as field_mesh: normals, flip, cap, simplify."""
+    from .alpha import scene_dense_alpha
+    _check_kw(kw)
+    t = _scene_t(t, "scene_mesh")
+    alpha, _ = scene_dense_alpha(tensorf_static, tensorf, gridSize, times=[t])
+    return _mesh_of_slice(tensorf, alpha, 0, level, space, H, W, focal, kw)
+
+
+def scene_mesh_sequence(tensorf_static, tensorf, times, level=0.005, gridSize=None, space="field", H=None, W=None, focal=None, **kw):
+    """mesh_sequence of the whole scene: an iterator of one mesh per time from a single scene_dense_alpha over all times.  The
+    arguments are checked here, at the call, not at the first next()."""
+    from .alpha import check_scene_fields, scene_dense_alpha
+    _check_kw(kw)
+    check_scene_fields(tensorf_static, tensorf, "scene_mesh_sequence")
+    times = [float(v) for v in torch.as_tensor(times, dtype=torch.float32).reshape(-1).tolist()]
+    if space not in ("field", "world"):
+        raise L.RdrfError(f"space must be \"field\" or \"world\", not {space!r}")
+
+    @torch.no_grad()
+    def meshes():
+        if not times:
+            return
+        alpha, _ = scene_dense_alpha(tensorf_static, tensorf, gridSize, times=times)
+        for k in range(len(times)):
+            yield _mesh_of_slice(tensorf, alpha, k, level, space, H, W, focal, kw)
+
+    return meshes()
+
+
+@torch.no_grad()
+def scene_vertex_colors(tensorf_static, tensorf, verts, t=None, view=(0, 0, 1)):
+    """[nv,3] uint8 colours of FIELD-SPACE vertices of a scene mesh: rgb = o rgb_d + (1 - o) rgb_s with rgb_d / rgb_s the two
+    fields' query_points colours at the vertex (time t, the one direction `view` used as given) and o the `owner` of
+    scene_alpha_volume there; quantised as vertex_colors does."""
+    from .alpha import scene_alpha_volume
+    t = _scene_t(t, "scene_vertex_colors")
+    view = tuple(float(v) for v in view)
+    o = scene_alpha_volume(tensorf_static, tensorf, verts, [t], want=("owner",))["owner"]
+    rgb_d = tensorf.query_points(verts, t, view, want=("rgb",))["rgb"]
+    rgb_s = tensorf_static.query_points(verts, None, view, want=("rgb",))["rgb"]
+    rgb = o * rgb_d + (1.0 - o) * rgb_s
+    return torch.round(rgb.clamp(0.0, 1.0) * 255.0).to(torch.uint8)
+
+
+@torch.no_grad()
+def colored_scene_mesh(tensorf_static, tensorf, t=None, level=0.005, gridSize=None, view=(0, 0, 1), space="field", H=None, W=None,
+                       focal=None, normals=False, flip=False, cap=False, simplify=None):
+    """colored_mesh of the whole scene: (verts, faces[, normals], colors [nv,3] uint8), the colours (scene_vertex_colors) taken
+    on the unsimplified field-space mesh, before clustering and before any NDC2world mapping."""
+    from .alpha import scene_dense_alpha
+    if space not in ("field", "world"):
+        raise L.RdrfError(f"space must be \"field\" or \"world\", not {space!r}")
+    t = _scene_t(t, "colored_scene_mesh")
+    kw = dict(normals=normals, flip=flip, cap=cap)
+    if simplify is not None:
+        kw["simplify"] = simplify
+    _check_kw(kw)
+    alpha, _ = scene_dense_alpha(tensorf_static, tensorf, gridSize, times=[t])
+    return _mesh_of_slice(tensorf, alpha, 0, level, space, H, W, focal, kw,
+                          color=lambda verts: scene_vertex_colors(tensorf_static, tensorf, verts, t, view))
+
+
 # ---- PLY (binary little-endian), numpy only ----------------------------------------------------------------------------
 def _np(x, dtype):
     if torch.is_tensor(x):
@@ -427,12 +499,23 @@ def load_field(path, device="cuda"):
 
 @torch.no_grad()
 def export_mesh(field_or_ckpt_path, ply_path, t=None, level=0.005, gridSize=None, space="field", H=None, W=None, focal=None,
-                device="cuda", color_view=None, **kw):
+                device="cuda", color_view=None, static=None, **kw):
     """train.py:107-118: the field (or the checkpoint at a path) -> dense alpha -> isosurface -> PLY.  Returns the mesh.
     color_view: a view direction; the PLY then carries the vertex colours of colored_mesh, which come last in the mesh.
-    kw: normals, flip, cap, simplify."""
-    field = load_field(field_or_ckpt_path, device) if isinstance(field_or_ckpt_path, (str, bytes)) or hasattr(
-        field_or_ckpt_path, "__fspath__") else field_or_ckpt_path
+    static: the static field (or its checkpoint's path) next to a dynamic `field_or_ckpt_path`: the mesh is then the whole
+    scene's (scene_mesh / colored_scene_mesh) at time t.  kw: normals, flip, cap, simplify."""
+    is_path = lambda f: isinstance(f, (str, bytes)) or hasattr(f, "__fspath__")
+    field = load_field(field_or_ckpt_path, device) if is_path(field_or_ckpt_path) else field_or_ckpt_path
+    if static is not None:
+        _check_kw(kw)
+        st = load_field(static, device) if is_path(static) else static
+        if color_view is None:
+            out = scene_mesh(st, field, t, level, gridSize, space, H, W, focal, **kw)
+            write_ply(ply_path, out[0], out[1], normals=out[2] if len(out) > 2 else None)
+        else:
+            out = colored_scene_mesh(st, field, t, level, gridSize, color_view, space, H, W, focal, **kw)
+            write_ply(ply_path, out[0], out[1], normals=out[2] if len(out) > 3 else None, colors=out[-1])
+        return out
     if color_view is None:
         out = field_mesh(field, t, level, gridSize, space, H, W, focal, **kw)
         write_ply(ply_path, out[0], out[1], normals=out[2] if len(out) > 2 else None)

@@ -2,11 +2,13 @@
 """Checkpoint -> isosurface mesh (the reference's --export_mesh, train.py:107-118), on the device.
 
     python tools/export_mesh.py ckpt.th out.ply [--time T] [--level L] [--grid G0 G1 G2] [--cap] [--normals] [--flip]
-                                                [--world H W focal] [--color-view X Y Z] [--simplify K]
+                                                [--world H W focal] [--color-view X Y Z] [--simplify K] [--with-static CKPT]
 
 --time is required for a dynamic field (times run over [-1, 1]); --world maps the vertices of an ndc field to world space;
 --color-view writes vertex colours: the field's rgb at the field-space vertices seen along the direction X Y Z (used as given);
---simplify K clusters the vertices K lattice cells wide (mean position, normal and colour per cluster; degenerate faces dropped)."""
+--simplify K clusters the vertices K lattice cells wide (mean position, normal and colour per cluster; degenerate faces dropped);
+--with-static CKPT: ckpt.th is the dynamic field and CKPT the static one, and the mesh is the whole scene's at --time: the
+isosurface of the alpha the renderer composes from both, colours blended by the dynamic field's share."""
 import argparse
 import os
 import sys
@@ -27,6 +29,7 @@ def main():
     ap.add_argument("--world", type=float, nargs=3, default=None, metavar=("H", "W", "focal"))
     ap.add_argument("--color-view", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
     ap.add_argument("--simplify", type=int, default=None, metavar="K")
+    ap.add_argument("--with-static", default=None, metavar="CKPT")
     a = ap.parse_args()
     import rodynrf
     kw = dict(cap=a.cap, normals=a.normals, flip=a.flip)
@@ -36,6 +39,8 @@ def main():
         kw.update(space="world", H=a.world[0], W=a.world[1], focal=a.world[2])
     if a.color_view is not None:
         kw.update(color_view=tuple(a.color_view))
+    if a.with_static is not None:
+        kw.update(static=a.with_static)
     out = rodynrf.export_mesh(a.ckpt, a.ply, t=a.time, level=a.level, gridSize=a.grid, **kw)
     print(f"{a.ply}: {out[0].shape[0]} vertices, {out[1].shape[0]} faces")
 
