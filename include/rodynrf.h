@@ -1129,6 +1129,47 @@ int rdrf_scene_alpha(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, cons
                      const RdrfAlphaMask* mask_s, const RdrfAlphaMask* mask_d, float* alpha, float* owner, float* sigma_s,
                      float* sigma_d, float* blending, void* ws, size_t ws_bytes, rdrf_stream_t stream);
 
+/* ---- texture atlases: a mesh turned into a point batch, a point batch into an RGB8 image --------------------------------------
+ * A per-face atlas of fixed layout for an indexed triangle mesh on the device, verts [nv][3] (in the field's coordinates) and
+ * faces [F][3] (int vertex indices, which the caller has checked: the kernels index verts with them).  q = the side of a square
+ * in texels (RDRF_BAKE_TEXELS_MIN to _MAX), the atlas Wt >= q texels wide, R = Wt / q squares to a row.  Square s = f >> 1 has
+ * its origin at ((s % R) q, (s / R) q) and holds face 2s where i + j <= q - 1 and face 2s + 1 elsewhere, (i, j) the texel's
+ * indices inside the square.  The layout needs q ceil(ceil(F / 2) / R) rows; Ht may be larger.  A texel's barycentric weights,
+ * in fp32:  lower  w1 = i / (q - 2), w2 = j / (q - 2);  upper  w1 = (q - 1 - i) / (q - 3), w2 = (q - 1 - j) / (q - 3);
+ * w0 = (1 - w1) - w2; its point is (w0 v0 + w1 v1) + w2 v2, every operation rounded once (no contraction).  These are the
+ * weights of the texel's centre (i + 0.5, j + 0.5) against the local corners  lower (0.5, 0.5), (q - 1.5, 0.5), (0.5, q - 1.5)
+ * / upper (q - 0.5, q - 0.5), (2.5, q - 0.5), (q - 0.5, 2.5), so the diagonals i + j = q - 1 and i + j = q lie just outside
+ * their triangles (w0 < 0) and a bilinear fetch at a UV inside a face's triangle reads texels of that face only.  The upper
+ * half of the last square of an odd F, the squares from ceil(F / 2) on, the columns from R q on and rows past the layout's
+ * belong to no face: point 0, direction (0, 0, 1), face -1, colour `fill`.
+ * view: a HOST array of three floats handed to every texel as given, or NULL: minus the unit normal of the texel's face,
+ * n = (v1 - v0) x (v2 - v0), -n / sqrt(n . n) in fp32; a face whose n . n is 0 or not finite takes (0, 0, 1).
+ * rdrf_bake_texels is the geometry stage alone, in image order: points and viewdirs [Ht][Wt][3], face [Ht][Wt] (nullable).
+ * rdrf_bake_texture evaluates one field (params / dynamic / cfg as rdrf_query_points; t: a DEVICE float, read by the dynamic
+ * field) and writes tex [Ht][Wt][3] bytes, round-half-even(clamp(rgb, 0, 1) 255) with rgb the bits rdrf_query_points gives the
+ * texel's point and direction; rdrf_bake_scene_texture forms rgb = o rgb_d + (1 - o) rgb_s first (four roundings), o the
+ * `owner` of rdrf_scene_alpha at the point and time with the given length and masks.  A NaN colour gives 0.  The texels are
+ * evaluated in chunks of chunk_squares whole squares (chunk_squares q q <= RDRF_QUERY_POINTS_MAX); the workspace,
+ * rdrf_bake_ws_bytes(scene, dynamic, q, chunk_squares) (0 for a refused q or chunk; named *_ws_bytes for the reason given at
+ * rdrf_render_masked_ws_bytes), depends on the chunk and not on the atlas, and a texel does not depend on the chunking.
+ * fill: a HOST array of three bytes.  Every byte of tex is written exactly once per call; F == 0 writes `fill` everywhere and
+ * touches no field.  No atomics, the deterministic library runs the same code; no allocation, no synchronisation, no
+ * read-back.  Refused before any device work: q outside its range, Wt < q, Ht below the layout's, Wt Ht >= 2^31, null
+ * pointers, a chunk outside its range, a workspace below the size call's. */
+#define RDRF_BAKE_TEXELS_MIN 4
+#define RDRF_BAKE_TEXELS_MAX 64
+int rdrf_bake_texels(const float* verts, const int* faces, int F, int q, int Wt, int Ht, const float* view, float* points,
+                     float* viewdirs, int* face, rdrf_stream_t stream);
+size_t rdrf_bake_ws_bytes(int scene, int dynamic, int q, int chunk_squares);
+int rdrf_bake_texture(const void* params, int dynamic, const RdrfFieldCfg* cfg, const float* verts, const int* faces, int F, int q,
+                      int Wt, int Ht, const float* view, const float* t, const unsigned char* fill, int chunk_squares,
+                      unsigned char* tex, void* ws, size_t ws_bytes, rdrf_stream_t stream);
+int rdrf_bake_scene_texture(const RdrfStaticParams* PS, const RdrfFieldCfg* cfg_s, const RdrfDynamicParams* PD,
+                            const RdrfFieldCfg* cfg_d, const float* verts, const int* faces, int F, int q, int Wt, int Ht,
+                            const float* view, const float* t, float length, const RdrfAlphaMask* mask_s,
+                            const RdrfAlphaMask* mask_d, const unsigned char* fill, int chunk_squares, unsigned char* tex, void* ws,
+                            size_t ws_bytes, rdrf_stream_t stream);
+
 /* timing hook: average device time (ms) of the dominant kernel launches recorded with HIP events
  * since the last reset; used by bench.py for the roofline figure. */
 void rdrf_prof_reset(void);

@@ -20,6 +20,7 @@ ACTS = {"relu": 0, "softplus": 1}
 HEADS = {"MLP_Fea": 0, "MLP_Fea_TimeEmbedding": 1}
 SAVE_NO_APP = 1   # include/rodynrf.h RDRF_SAVE_NO_APP (flags of rdrf_saved_bytes_ex / rdrf_*_fwd_ex)
 QUERY_POINTS_MAX = 1 << 24   # include/rodynrf.h RDRF_QUERY_POINTS_MAX: the largest batch of one rdrf_query_points call
+BAKE_TEXELS_MIN, BAKE_TEXELS_MAX = 4, 64   # include/rodynrf.h RDRF_BAKE_TEXELS_MIN / _MAX: the side of an atlas square
 
 fp = C.POINTER(C.c_float)
 
@@ -275,6 +276,11 @@ SIGNATURES = {
     "rdrf_scene_alpha_ws_bytes": (usz, [i32, i32]),
     "rdrf_scene_alpha": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, f32, C.POINTER(RdrfAlphaMask), C.POINTER(RdrfAlphaMask), vp, vp,
                               vp, vp, vp, vp, usz, vp]),
+    "rdrf_bake_texels": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "rdrf_bake_ws_bytes": (usz, [i32, i32, i32, i32]),
+    "rdrf_bake_texture": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, usz, vp]),
+    "rdrf_bake_scene_texture": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, f32, C.POINTER(RdrfAlphaMask),
+                                     C.POINTER(RdrfAlphaMask), vp, i32, vp, vp, usz, vp]),
     "rdrf_prof_reset": (None, []),
     "rdrf_prof_enable": (i32, [i32]),
     "rdrf_prof_get": (i32, [C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_int)]),

@@ -8,6 +8,10 @@ counter-clockwise seen from the low-value side (the reference reverses skimage's
 winding).  DESIGN.md, "Isosurface meshes", has the algorithm and the ordering rules.
 """
 import ctypes as C
+import math
+import os
+import struct
+import zlib
 
 import numpy as np
 import torch
@@ -403,6 +407,186 @@ def colored_scene_mesh(tensorf_static, tensorf, t=None, level=0.005, gridSize=No
                           color=lambda verts: scene_vertex_colors(tensorf_static, tensorf, verts, t, view))
 
 
+# ---- texture atlases: the field per texel of a per-face atlas (csrc/rdrf_bake.hip; DESIGN.md, "Texture atlases") -------------
+def _texels(texels, who):
+    if isinstance(texels, bool) or not isinstance(texels, int) or not L.BAKE_TEXELS_MIN <= texels <= L.BAKE_TEXELS_MAX:
+        raise L.RdrfError(f"{who}: texels must be a whole number from {L.BAKE_TEXELS_MIN} to {L.BAKE_TEXELS_MAX}, not {texels!r}")
+    return texels
+
+
+def atlas_layout(n_faces, texels=8, width=None):
+    """(Wt, Ht, R) of the atlas of n_faces faces: squares of texels x texels, two faces to a square, R = Wt // texels squares
+    to a row, Ht = texels * ceil(ceil(n_faces / 2) / R).  width=None: the smallest power of two that holds
+    ceil(sqrt(ceil(n_faces / 2))) squares side by side; a given width must hold one square."""
+    q = _texels(texels, "atlas_layout")
+    F = int(n_faces)
+    if F < 0:
+        raise L.RdrfError(f"atlas_layout: {F} faces")
+    nsq = (F + 1) // 2
+    if width is None:
+        side = math.isqrt(nsq)
+        need = q * max(1, side if side * side == nsq else side + 1)
+        Wt = 1 << (need - 1).bit_length()
+    else:
+        if isinstance(width, bool) or not isinstance(width, int) or width < q:
+            raise L.RdrfError(f"atlas_layout: an atlas {width!r} texels wide holds no square of {q}")
+        Wt = width
+    R = Wt // q
+    return Wt, q * (-(-nsq // R)), R
+
+
+def atlas_uv(n_faces, texels=8, width=None, device=None):
+    """[n_faces,3,2] float32: the texture coordinates of every face's three corners, in the order of its vertices, u to the
+    right and v up the array's rows (write_obj writes row y of the texture at image row Ht - 1 - y).  The corners sit on
+    texel centres half a texel inside the face's half of its square, so a bilinear fetch inside the triangle stays on the
+    face's own texels."""
+    q = _texels(texels, "atlas_uv")
+    Wt, Ht, R = atlas_layout(n_faces, q, width)
+    f = np.arange(int(n_faces), dtype=np.int64)
+    s, upper = f >> 1, (f & 1).astype(bool)
+    lower_c = np.array([[0.5, 0.5], [q - 1.5, 0.5], [0.5, q - 1.5]])
+    upper_c = np.array([[q - 0.5, q - 0.5], [2.5, q - 0.5], [q - 0.5, 2.5]])
+    local = np.where(upper[:, None, None], upper_c[None], lower_c[None])
+    origin = np.stack(((s % R) * q, (s // R) * q), -1).astype(np.float64)
+    uv = (origin[:, None, :] + local) / np.array([Wt, max(Ht, 1)], dtype=np.float64)
+    return torch.from_numpy(uv.astype(np.float32)).to("cpu" if device is None else device)
+
+
+def _bake_mesh(verts, faces, who):
+    """the checks of a mesh whose faces index the kernels' reads: shapes, types, and every index inside [0, nv) (one host read)"""
+    if not torch.is_tensor(verts) or verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32:
+        raise L.RdrfError(f"{who}: verts must be a [nv,3] float32 tensor")
+    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise L.RdrfError(f"{who}: faces must be a [F,3] int32 tensor")
+    if faces.shape[0] > 0:
+        lo, hi = int(faces.min()), int(faces.max())
+        if lo < 0 or hi >= verts.shape[0]:
+            raise L.RdrfError(f"{who}: face indices run from {lo} to {hi}, the mesh has {verts.shape[0]} vertices")
+    L.require_device(verts, faces)
+    if verts.device != faces.device:
+        raise L.RdrfError(f"{who}: verts are on {verts.device} and faces on {faces.device}")
+    return verts.contiguous(), faces.contiguous()
+
+
+def _bake_view(view, who):
+    """None for "normal" (the kernels then look at each face along minus its normal), else a host array of three floats"""
+    if isinstance(view, str):
+        if view != "normal":
+            raise L.RdrfError(f"{who}: view must be three numbers or \"normal\", not {view!r}")
+        return None
+    v = [float(x) for x in view]
+    if len(v) != 3:
+        raise L.RdrfError(f"{who}: view must be three numbers or \"normal\", not {view!r}")
+    return (C.c_float * 3)(*v)
+
+
+def _bake_fill(fill, who):
+    """the colour of the texels no face owns: three whole numbers from 0 to 255, as a host array of three bytes"""
+    v = list(fill) if isinstance(fill, (tuple, list)) or torch.is_tensor(fill) or isinstance(fill, np.ndarray) else None
+    if v is None or len(v) != 3 or not all(float(x) == int(x) and 0 <= int(x) <= 255 for x in v):
+        raise L.RdrfError(f"{who}: fill must be three whole numbers from 0 to 255, not {fill!r}")
+    return (C.c_ubyte * 3)(*[int(x) for x in v])
+
+
+@torch.no_grad()
+def bake_texels(verts, faces, texels=8, width=None, view=(0, 0, 1)):
+    """The geometry stage of a bake: dict(points [Ht,Wt,3], viewdirs [Ht,Wt,3], face [Ht,Wt] int32) over the atlas
+    atlas_layout(F, texels, width).  points: where each texel lies on its face (FIELD-SPACE verts in, field-space points
+    out); viewdirs: `view` as given, or with view="normal" minus the unit normal of the texel's face ((0, 0, 1) for a face
+    without one); face: the owning face, -1 where there is none (points 0 there).  query_points at these points bakes any
+    quantity of a field."""
+    who = "bake_texels"
+    q = _texels(texels, who)
+    Wt, Ht, _ = atlas_layout(int(faces.shape[0]) if torch.is_tensor(faces) and faces.dim() == 2 else 0, q, width)
+    view_c = _bake_view(view, who)
+    verts, faces = _bake_mesh(verts, faces, who)
+    dev = verts.device
+    out = {"points": torch.empty(Ht, Wt, 3, device=dev), "viewdirs": torch.empty(Ht, Wt, 3, device=dev),
+           "face": torch.empty(Ht, Wt, dtype=torch.int32, device=dev)}
+    L.check(L.lib.rdrf_bake_texels(L.ptr(verts), L.ptr(faces), int(faces.shape[0]), q, Wt, Ht, view_c, L.ptr(out["points"]),
+                                   L.ptr(out["viewdirs"]), L.ptr(out["face"]), L.stream_of(verts)), "rdrf_bake_texels")
+    return out
+
+
+@torch.no_grad()
+def bake_texture(field, verts, faces, t=None, texels=8, width=None, view=(0, 0, 1), fill=(0, 0, 0), static=None, _chunk=None):
+    """(texture [Ht,Wt,3] uint8, uv [F,3,2] float32): the field's colour per texel of the atlas of a FIELD-SPACE mesh,
+    round(clamp(rgb, 0, 1) * 255) of query_points at the points and directions bake_texels gives, bit for bit; texels no face
+    owns are `fill`.  static=: `field` is the dynamic field and the colours are the whole scene's, o rgb_d + (1 - o) rgb_s as
+    in scene_vertex_colors.  t is required for the dynamic field and for the scene.  The texels are evaluated in chunks of
+    whole squares (at most _chunk points), so the scratch does not grow with the atlas."""
+    from ._params import field_structs
+    who = "bake_texture"
+    q = _texels(texels, who)
+    Wt, Ht, _ = atlas_layout(int(faces.shape[0]) if torch.is_tensor(faces) and faces.dim() == 2 else 0, q, width)
+    view_c = _bake_view(view, who)
+    fill_c = _bake_fill(fill, who)
+    limit = L.QUERY_POINTS_MAX if _chunk is None else int(_chunk)
+    if not q * q <= limit <= L.QUERY_POINTS_MAX:
+        raise L.RdrfError(f"{who}: chunks of {limit} points, a chunk holds one square of {q * q} texels to {L.QUERY_POINTS_MAX} points")
+    if static is not None:
+        from .alpha import check_scene_fields
+        check_scene_fields(static, field, who)
+        t = _scene_t(t, who)
+    elif field.DYNAMIC:
+        if t is None:
+            raise L.RdrfError(f"{who}: the dynamic field's colours depend on the time: pass t")
+        t = float(t)
+    verts, faces = _bake_mesh(verts, faces, who)
+    dev, F = verts.device, int(faces.shape[0])
+    if dev != field.aabb.device:
+        raise L.RdrfError(f"{who}: the mesh is on {dev} and the field on {field.aabb.device}")
+    squares = max(1, min(limit // (q * q), (F + 1) // 2))
+    tex = torch.empty(Ht, Wt, 3, dtype=torch.uint8, device=dev)
+    uv = atlas_uv(F, q, Wt, device=dev)
+    t_dev = None if t is None else torch.full((1,), t, dtype=torch.float32, device=dev)
+    ws = L.workspace(dev, L.lib.rdrf_bake_ws_bytes(int(static is not None), int(field.DYNAMIC), q, squares))
+    P, cfg = field_structs(field, field._param_list(), "ndc")
+    common = (L.ptr(verts), L.ptr(faces), F, q, Wt, Ht, view_c, L.ptr(t_dev))
+    tail = (fill_c, squares, L.ptr(tex), L.ptr(ws), ws.numel(), L.stream_of(verts))
+    if static is None:
+        L.check(L.lib.rdrf_bake_texture(C.byref(P), int(field.DYNAMIC), C.byref(cfg), *common, *tail), "rdrf_bake_texture")
+    else:
+        PS, cs = field_structs(static, static._param_list(), "ndc")
+        ms, md = (None if f.alphaMask is None else f.alphaMask._struct() for f in (static, field))   # as scene_vertex_colors
+        L.check(L.lib.rdrf_bake_scene_texture(C.byref(PS), C.byref(cs), C.byref(P), C.byref(cfg), *common, float(field._step_host),
+                                              None if ms is None else C.byref(ms), None if md is None else C.byref(md), *tail),
+                "rdrf_bake_scene_texture")
+    return tex, uv
+
+
+@torch.no_grad()
+def textured_mesh(field, t=None, level=0.005, gridSize=None, texels=8, view=(0, 0, 1), space="field", H=None, W=None, focal=None,
+                  normals=False, flip=False, cap=False, simplify=None, static=None):
+    """field_mesh (static=: scene_mesh, `field` the dynamic field) with a texture atlas: (verts, faces[, normals], uv, texture).
+    The texture is baked (bake_texture) on the final field-space mesh -- after simplify=K, so its resolution does not shrink
+    with the vertex count, and before any NDC2world mapping: space="world" moves the vertices and keeps uv and texels."""
+    if space not in ("field", "world"):
+        raise L.RdrfError(f"space must be \"field\" or \"world\", not {space!r}")
+    if space == "world" and (H is None or W is None or focal is None):   # before the volume, the meshing and the bake
+        raise L.RdrfError("space=\"world\" maps NDC vertices through NDC2world and needs H, W and focal")
+    _texels(texels, "textured_mesh")
+    _bake_view(view, "textured_mesh")
+    kw = dict(normals=normals, flip=flip, cap=cap)
+    if simplify is not None:
+        kw["simplify"] = simplify
+    _check_kw(kw)
+    if static is not None:
+        from .alpha import scene_dense_alpha
+        t = _scene_t(t, "textured_mesh")
+        alpha, _ = scene_dense_alpha(static, field, gridSize, times=[t])
+    else:
+        if t is None and field.DYNAMIC:
+            raise L.RdrfError("textured_mesh: the dynamic field's alpha depends on the time: pass t")
+        alpha, _ = field.getDenseAlpha(gridSize, times=[0.0 if t is None else float(t)])
+    mesh = _mesh_of_slice(field, alpha, 0, level, "field", None, None, None, kw)
+    verts, faces = mesh[0], mesh[1]
+    texture, uv = bake_texture(field, verts, faces, t, texels, None, view, static=static)
+    world, wn = _to_world(field, verts, faces, space, H, W, focal)
+    out = (world, faces) if not normals else (world, faces, (mesh[2] if wn is None else wn))
+    return out + (uv, texture)
+
+
 # ---- PLY (binary little-endian), numpy only ----------------------------------------------------------------------------
 def _np(x, dtype):
     if torch.is_tensor(x):
@@ -483,6 +667,122 @@ def read_ply(path):
             "colors": stack(("red", "green", "blue"), np.uint8) if has_c else None}
 
 
+# ---- OBJ + MTL + PNG: a textured mesh as three files, standard library and numpy only ------------------------------------------
+def _png_chunk(kind, data):
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+
+def write_png(path, image):
+    """image [H,W,3] uint8, row 0 at the top: an 8-bit RGB PNG, every scanline with filter 0"""
+    img = _np(image, "u1")
+    if img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise L.RdrfError(f"write_png: the image must be [H,W,3] with H, W >= 1, not {img.shape}")
+    Hh, Ww = img.shape[:2]
+    rows = np.zeros((Hh, 1 + Ww * 3), dtype=np.uint8)
+    rows[:, 1:] = img.reshape(Hh, Ww * 3)
+    with open(path, "wb") as out:
+        out.write(b"\x89PNG\r\n\x1a\n" + _png_chunk(b"IHDR", struct.pack(">IIBBBBB", Ww, Hh, 8, 2, 0, 0, 0))
+                  + _png_chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + _png_chunk(b"IEND", b""))
+
+
+def read_png(path):
+    """what write_png writes -> [H,W,3] uint8 (8-bit RGB, filter 0 on every scanline; anything else is refused)"""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError(f"{path}: not a PNG")
+    pos, idat, head = 8, b"", None
+    while pos < len(data):
+        n, kind = struct.unpack(">I", data[pos:pos + 4])[0], data[pos + 4:pos + 8]
+        body = data[pos + 8:pos + 8 + n]
+        if kind == b"IHDR":
+            head = struct.unpack(">IIBBBBB", body)
+        elif kind == b"IDAT":
+            idat += body
+        pos += 12 + n
+    if head is None or head[2:] != (8, 2, 0, 0, 0):
+        raise ValueError(f"{path}: only 8-bit RGB without interlacing is read")
+    Ww, Hh = head[:2]
+    rows = np.frombuffer(zlib.decompress(idat), dtype=np.uint8).reshape(Hh, 1 + Ww * 3)
+    if rows[:, 0].any():
+        raise ValueError(f"{path}: only scanlines with filter 0 are read")
+    return np.ascontiguousarray(rows[:, 1:]).reshape(Hh, Ww, 3)
+
+
+def _obj_paths(path):
+    base = os.path.splitext(os.fspath(path))[0]
+    return base + ".obj", base + ".mtl", base + ".png"
+
+
+def write_obj(path, verts, faces, uv, texture, normals=None):
+    """A textured mesh as <base>.obj (v, vt -- three per face --, optional vn, f a/ta[/na] ...), <base>.mtl (map_Kd) and
+    <base>.png, <base> = path without its suffix.  uv [F,3,2] and texture [Ht,Wt,3] uint8 as bake_texture returns them: row y
+    of the texture is written at image row Ht - 1 - y (OBJ's v runs upwards).  Floats are written with nine significant
+    digits, which read_obj reads back to the same float32.  Returns the three paths."""
+    v = _np(verts, "<f4").reshape(-1, 3)
+    f = _np(faces, "<i4").reshape(-1, 3)
+    vt = _np(uv, "<f4").reshape(-1, 2)
+    tex = _np(texture, "u1")
+    n = None if normals is None else _np(normals, "<f4").reshape(-1, 3)
+    if vt.shape[0] != 3 * f.shape[0]:
+        raise L.RdrfError(f"write_obj: uv must be [F,3,2] for the {f.shape[0]} faces, not {np.shape(uv)}")
+    if tex.ndim != 3 or tex.shape[2] != 3 or tex.shape[0] < 1 or tex.shape[1] < 1:
+        raise L.RdrfError(f"write_obj: the texture must be [Ht,Wt,3] uint8 with texels in it (an empty mesh has no atlas), not {tex.shape}")
+    obj, mtl, png = _obj_paths(path)
+    write_png(png, tex[::-1])
+    with open(mtl, "w") as out:
+        out.write(f"newmtl baked\nKa 0 0 0\nKd 1 1 1\nKs 0 0 0\nillum 0\nmap_Kd {os.path.basename(png)}\n")
+    lines = [f"mtllib {os.path.basename(mtl)}", "usemtl baked"]
+    lines += ["v %.9g %.9g %.9g" % tuple(r) for r in v.tolist()]
+    lines += ["vt %.9g %.9g" % tuple(r) for r in vt.tolist()]
+    if n is not None:
+        lines += ["vn %.9g %.9g %.9g" % tuple(r) for r in n.tolist()]
+    fmt = "f %d/%d %d/%d %d/%d" if n is None else "f %d/%d/%d %d/%d/%d %d/%d/%d"
+    corners = np.stack((f + 1, 3 * np.arange(len(f))[:, None] + np.arange(1, 4)[None]) + (() if n is None else (f + 1,)), -1)
+    lines += [fmt % tuple(r) for r in corners.reshape(len(f), -1).tolist()]
+    with open(obj, "w") as out:
+        out.write("\n".join(lines) + "\n")
+    return obj, mtl, png
+
+
+def read_obj(path):
+    """what write_obj writes -> dict(verts [nv,3] f32, faces [F,3] i32, uv [F,3,2] f32, normals [nv,3] f32 or None, texture
+    [Ht,Wt,3] uint8 with the row flip undone, mtl: the material file's text)"""
+    obj, _, _ = _obj_paths(path)
+    v, vt, vn, f, ft, mtllib = [], [], [], [], [], None
+    with open(obj) as src:
+        for line in src:
+            w = line.split()
+            if not w:
+                continue
+            if w[0] == "v":
+                v.append([float(x) for x in w[1:4]])
+            elif w[0] == "vt":
+                vt.append([float(x) for x in w[1:3]])
+            elif w[0] == "vn":
+                vn.append([float(x) for x in w[1:4]])
+            elif w[0] == "f":
+                if len(w) != 4:
+                    raise ValueError(f"{obj}: only triangles are read")
+                c = [x.split("/") for x in w[1:]]
+                f.append([int(x[0]) - 1 for x in c])
+                ft.append([int(x[1]) - 1 for x in c])
+            elif w[0] == "mtllib":
+                mtllib = w[1]
+    if mtllib is None:
+        raise ValueError(f"{obj}: no mtllib")
+    with open(os.path.join(os.path.dirname(obj), mtllib)) as src:
+        mtl = src.read()
+    maps = [line.split()[1] for line in mtl.split("\n") if line.split()[:1] == ["map_Kd"]]
+    if len(maps) != 1:
+        raise ValueError(f"{mtllib}: one map_Kd is read, not {len(maps)}")
+    arr = lambda x, dt, cols: np.asarray(x, dtype=dt).reshape(-1, cols)
+    vt, ft = arr(vt, np.float32, 2), arr(ft, np.int32, 3)
+    return {"verts": arr(v, np.float32, 3), "faces": arr(f, np.int32, 3), "uv": vt[ft.reshape(-1)].reshape(-1, 3, 2),
+            "normals": arr(vn, np.float32, 3) if vn else None,
+            "texture": np.ascontiguousarray(read_png(os.path.join(os.path.dirname(obj), maps[0]))[::-1]), "mtl": mtl}
+
+
 def load_field(path, device="cuda"):
     """the reload recipe of train.py:433-447 on this package's classes; the class is told from the state dict"""
     from .fields import TensorVMSplit, TensorVMSplit_TimeEmbedding
@@ -499,13 +799,27 @@ def load_field(path, device="cuda"):
 
 @torch.no_grad()
 def export_mesh(field_or_ckpt_path, ply_path, t=None, level=0.005, gridSize=None, space="field", H=None, W=None, focal=None,
-                device="cuda", color_view=None, static=None, **kw):
+                device="cuda", color_view=None, static=None, texture=None, **kw):
     """train.py:107-118: the field (or the checkpoint at a path) -> dense alpha -> isosurface -> PLY.  Returns the mesh.
     color_view: a view direction; the PLY then carries the vertex colours of colored_mesh, which come last in the mesh.
     static: the static field (or its checkpoint's path) next to a dynamic `field_or_ckpt_path`: the mesh is then the whole
-    scene's (scene_mesh / colored_scene_mesh) at time t.  kw: normals, flip, cap, simplify."""
+    scene's (scene_mesh / colored_scene_mesh) at time t.  kw: normals, flip, cap, simplify.
+    texture=q: a textured mesh (textured_mesh, squares of q texels) goes to an OBJ, an MTL and a PNG instead (write_obj; the
+    suffix of ply_path is replaced); color_view is then the bake's view direction, three numbers (default (0, 0, 1)) or
+    "normal"."""
     is_path = lambda f: isinstance(f, (str, bytes)) or hasattr(f, "__fspath__")
+    if texture is not None:   # refused before a checkpoint is loaded
+        _check_kw(kw)
+        _texels(texture, "export_mesh")
+    elif isinstance(color_view, str):
+        raise L.RdrfError("export_mesh: color_view=\"normal\" is a direction per texel: it needs texture=")
     field = load_field(field_or_ckpt_path, device) if is_path(field_or_ckpt_path) else field_or_ckpt_path
+    if texture is not None:
+        st = load_field(static, device) if static is not None and is_path(static) else static
+        out = textured_mesh(field, t, level, gridSize, texture, (0, 0, 1) if color_view is None else color_view, space, H, W, focal,
+                            static=st, **kw)
+        write_obj(ply_path, out[0], out[1], out[-2], out[-1], normals=out[2] if len(out) > 4 else None)
+        return out
     if static is not None:
         _check_kw(kw)
         st = load_field(static, device) if is_path(static) else static
